@@ -12,12 +12,16 @@ all-reduce of the flat gradient, N > 1] -> K5 Adam + NonNeg -> K3 simple_norm_co
 (weak scaling): 1024 clips = config 4's 8192/8 shard.  `--scaling strong` fixes the GLOBAL batch instead
 (`--global-batch`, default 8192 = config 4's) and gives every rank 8192 / N clips per step: the form
 north_star's ">= 6.5x strong scaling at 8 GPUs" is worded in; its N = 1 denominator (one GPU, batch
-8192) is also in every default N = 1 line as "reference_global_batch_8192_1gpu".  Rank 0 additionally
-times the reference's own batch of 512 at N = 1 ("reference_batch_512").
+8192) is also in every --full N = 1 line as "reference_global_batch_8192_1gpu".  With --full, rank 0
+additionally times the reference's own batch of 512 at N = 1 ("reference_batch_512").
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the stream the kernels run
-on (lipasr_mfcc_profile_*), `cpu_baseline` times the oracle (a NumPy restatement of the reference path;
-TensorFlow / librosa are not installable here) on the host cores for a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, ...).  --full adds everything else: `roofline` is measured live with HIP events
+on the stream the kernels run on (lipasr_mfcc_profile_*), `train_graph_ms` / `allreduce_ms` over untimed
+extra steps, the other configurations as `reference_*` records, and `cpu_baseline` times the oracle (a
+NumPy restatement of the reference path, which itself needs TensorFlow / librosa) on the host cores for a
+bounded sample; the --skip-* options leave parts of that out.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -159,9 +163,46 @@ def make_pool(n_clips, device, seed):
     return waves, y
 
 
-def run_config(opt, pool, batch, rank, world, device, steps, warmup, profile):
+DUMP_FEATURE_ROWS = 4096                # --dump-outputs: at most this many rows of the step's features (a seeded sample beyond)
+
+
+def dump_outputs(out_dir, pipe, model, batch, constraint):
+    """What the timed step hands its caller after the last timed step, as float32 .npy files: every layer's updated
+    parameters and BatchNorm moving statistics, the per-row losses, the product norms of the projection and the
+    standardised MFCC features the step trained on (a fixed, seeded sample of rows when the batch is larger than
+    DUMP_FEATURE_ROWS).  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for i, b in enumerate(model._blocks):
+        w, bias = b["dense"].get_weights()
+        arrays[f"block{i}_dense_kernel"], arrays[f"block{i}_dense_bias"] = w, bias
+        if b["bn"] is not None:
+            for key, a in zip(("gamma", "beta", "moving_mean", "moving_variance"), b["bn"].get_weights()):
+                arrays[f"block{i}_bn_{key}"] = a
+    arrays["loss_rows"] = model._loss_rows[:batch].cpu().numpy()
+    if constraint == "product":
+        arrays["product_norms"] = pipe.norms.cpu().numpy()
+    feats = pipe.feats[:batch]
+    if batch > DUMP_FEATURE_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(batch, DUMP_FEATURE_ROWS, replace=False))
+        arrays["features_row_index"] = rows.astype(np.float64)
+        feats = feats[torch.as_tensor(rows, device=feats.device)]
+    arrays["features"] = feats.cpu().numpy()
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=a.dtype if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes, more than 64 MiB"
+    return total
+
+
+def run_config(opt, pool, batch, rank, world, device, steps, warmup, profile, dump_dir=None):
     """Builds model + pipeline for one per-GPU batch, times `steps` steps; returns (seconds, extras).
-    opt: dict(constraint=, pgd=, pgd_eps=, bf16=, pre_extracted=, graph="auto"|"on"|"off")."""
+    opt: dict(constraint=, pgd=, pgd_eps=, bf16=, pre_extracted=, graph="auto"|"on"|"off").
+    profile: also the per-kernel figures -- MFCC kernel times inside the timed steps, the classifier's part of the step and
+    the all-reduce over untimed extra steps, the MFCC stage alone on the whole chip.  dump_dir: write what the last timed
+    step computed there (dump_outputs) before anything else runs."""
     import torch.distributed as dist
 
     import lipasr._native as N
@@ -251,24 +292,27 @@ def run_config(opt, pool, batch, rank, world, device, steps, warmup, profile):
     N.check(N.lib.lipasr_timer_elapsed_ms(pipe.h.h, tid.value, C.byref(ev_ms)))
     extras = {"event_ms_per_step": ev_ms.value / steps, "host_enqueue_ms_per_step": t_host / steps * 1e3, "final_norm": float(pipe.norms[-1].item()) if opt.get("constraint", "product") == "product" else None,
               "loss": float(model._loss_rows[:batch].mean().item())}
+    if dump_dir:
+        extras["dump_bytes"] = dump_outputs(dump_dir, pipe, model, batch, opt.get("constraint", "product"))
     if profile and pre:
         extras["mfcc_ms"] = {"resample": 0.0, "stft_mel": 0.0, "dct": 0.0, "calls": 0}
     elif profile:
         ms3, n = pipe.ex.profile_end()
         extras["mfcc_ms"] = dict(ms3, calls=n)
     extras["mfcc_fused"] = fused
-    # the classifier part of the step, timed on ITS stream while the MFCC of the next batch runs beside it (untimed extra
-    # steps after the measured region, so that the two event records per step do not touch `value`)
-    n_prof = min(20, steps)
-    pipe.profile_train(n_prof)
-    dp.time_collectives(True)  # HIP events around the gradient all-reduce of these untimed steps
-    for i in range(n_prof):
-        one(warmup + steps + i)
-    pipe.synchronize()
-    extras["train_graph_ms"] = pipe.train_ms()
     extras["hip_graph"] = bool(pipe.use_graph)
-    extras["allreduce_ms"] = dp.collective_ms()
     extras["comm"] = comm
+    if profile:
+        # the classifier part of the step, timed on ITS stream while the MFCC of the next batch runs beside it (untimed extra
+        # steps after the measured region, so that the two event records per step do not touch `value`)
+        n_prof = min(20, steps)
+        pipe.profile_train(n_prof)
+        dp.time_collectives(True)  # HIP events around the gradient all-reduce of these untimed steps
+        for i in range(n_prof):
+            one(warmup + steps + i)
+        pipe.synchronize()
+        extras["train_graph_ms"] = pipe.train_ms()
+        extras["allreduce_ms"] = dp.collective_ms()
     standalone = None
     if profile and not pre:
         # the same MFCC kernels alone on the whole chip (untimed, AFTER the measured region: thirteen extractions stream 0.8 GB
@@ -445,7 +489,14 @@ def main():
     ap.add_argument("--fit-api", action="store_true", help="only time the Keras-shaped fit() entry (used by the main run as a child process)")
     ap.add_argument("--skip-other-configs", action="store_true", help="do not add the config 2 / config 2 bf16 / config 5 records (N = 1 only)")
     ap.add_argument("--dry-run-dp", action="store_true", help="rehearse the world > 1 control flow on the CPU (gloo, stand-in replica); prints a line marked dry_run, not a measurement")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline and per-kernel figures, the classifier's and the "
+                    "all-reduce's share of the step, the other configurations and batch sizes (N = 1) and the CPU baseline; the --skip-* "
+                    "options leave parts of it out.  Without it the run sets up, warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (parameters, BatchNorm "
+                    "statistics, per-row losses, product norms, standardised features) to DIR/<name>.npy, float32, rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     opt = {"constraint": None if args.constraint == "none" else args.constraint, "pgd": args.pgd, "pgd_eps": args.pgd_eps, "bf16": args.bf16,
            "pre_extracted": args.pre_extracted, "graph": "off" if args.no_graph else args.graph, "int16": args.int16,
            "compute": "float32" if args.exact_fp32 else os.environ.get("LIPASR_COMPUTE", "float16x2")}
@@ -497,7 +548,8 @@ def main():
             raise SystemExit(f"--scaling strong: global batch {args.global_batch} is not a multiple of {world} ranks")
         batch = args.global_batch // world
     pool = make_pool(max(args.pool_clips, 8 * batch) // batch * batch, device, seed=1234 + rank)
-    dt, ex = run_config(opt, pool, batch, rank, world, device, args.steps, args.warmup, profile=True)
+    dt, ex = run_config(opt, pool, batch, rank, world, device, args.steps, args.warmup, profile=args.full,
+                        dump_dir=args.dump_outputs if rank == 0 else None)
     t = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -509,62 +561,63 @@ def main():
 
     global_batch = batch * world
     value = global_batch * args.steps / dt
-    ms = ex["mfcc_ms"]
-    stage_ms = ms["resample"] + ms["stft_mel"] + ms["dct"]
-    dom = max(("resample", "stft_mel", "dct"), key=lambda k: ms[k])
-    bytes_per_utt = (32000 + 3520) if args.int16 else MFCC_BYTES_PER_UTT  # the 16-bit PCM variant reads 2 B per sample
-    achieved = bytes_per_utt * batch / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
-    # HBM traffic of the stage per launch: PMC counters cannot be read from inside this process, so the value is
-    # the committed rocprofv3 measurement of the same kernels (separate --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH
-    # doubled per MI355X_MICROARCH.md), scaled to this batch.
-    traffic, traffic_src, traffic_fused, traffic_stale = None, None, None, None
-    for name in ("r05_mfcc_pmc.json", "r04_mfcc_pmc.json", "r03_mfcc_pmc.json", "r02_mfcc_pmc.json"):
-        try:
-            with open(os.path.join(ROOT, "profiles", name)) as f:
-                eor = json.load(f)["end_of_round"]
-            traffic_stale = eor.get("source_sha16") != mfcc_source_sha()  # (files before round 4 carry no hash: stale)
-            key = "fused_stage_bytes_per_utt" if ex.get("mfcc_fused") and "fused_stage_bytes_per_utt" in eor else "stage_bytes_per_utt"
-            traffic = round(eor[key] * batch)
-            if "fused_stage_bytes_per_utt" in eor:
-                traffic_fused = round(eor["fused_stage_bytes_per_utt"] * batch)
-            traffic_src = f"profiles/{name} (rocprofv3 --pmc, per launch, scaled by batch)"
-            break
-        except Exception:
-            continue
-    if args.int16:  # the committed counter passes ran on float32 clips
-        traffic, traffic_src, traffic_fused = None, None, None
-    names = mfcc_kernel_names(bool(ex.get("mfcc_fused")))
-    roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                "stage": "MFCC (K1 = " + (" + ".join(dict.fromkeys(v for v in names.values() if not v.startswith("(")))) + ")",
-                "dominant_kernel": names[dom],
-                "kernel_names": names,
-                "algorithmic_bytes_per_utt": bytes_per_utt, "units_per_launch": batch,
-                "kernel_ms": {k: round(ms[k], 4) for k in ("resample", "stft_mel", "dct")},
-                "fp32_flop_frac": round(MFCC_FLOP_PER_UTT * batch / (stage_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5) if stage_ms > 0 else 0.0,
-                "traffic_x_algorithmic": round(traffic / (bytes_per_utt * batch), 3) if traffic else None,
-                "fused_path_traffic": traffic_fused,  # the resample + STFT kernel (int16 / ragged input, or LIPASR_MFCC_FUSED=1): y stays in LDS
-                "note": "stage is fp32-compute-bound (8.7 MFLOP/utt vs 67.5 kB/utt): see DESIGN.md"}
-    if ex.get("mfcc_cus"):
-        # the pipeline confines the MFCC stream to a share of the CUs (DESIGN.md, step level): its kernels take longer by
-        # design while the step gets shorter; `frac` above is what the timed region shows, the fields below put it in context
-        share = ex["mfcc_cus"] / ex["n_cus"]
-        roofline["cu_share"] = round(share, 4)
-        roofline["frac_of_share"] = round(achieved / HBM_PEAK_GBS / share, 5)
-    if ex.get("mfcc_standalone_ms"):
-        sa = ex["mfcc_standalone_ms"]
-        sa_ms = sa["resample"] + sa["stft_mel"] + sa["dct"]
-        sa_ach = bytes_per_utt * batch / (sa_ms * 1e-3) / 1e9
-        roofline["standalone_whole_chip"] = {"kernel_ms": sa, "achieved": round(sa_ach, 2), "frac": round(sa_ach / HBM_PEAK_GBS, 5),
-                                             "fp32_flop_frac": round(MFCC_FLOP_PER_UTT * batch / (sa_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5)}
-    cls_tflops = TRAIN_FLOP_PER_UTT * batch / (ex["train_graph_ms"] * 1e-3) / 1e12 if not args.pgd and ex["train_graph_ms"] > 0 else None
-    if args.pre_extracted:
-        tf = TRAIN_FLOP_PER_UTT * batch / (ex["event_ms_per_step"] * 1e-3) / 1e12
-        roofline = {"bound": "mfma", "achieved": round(tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / FP32_PEAK_TFLOPS, 5),
-                    "traffic": None, "stage": "dense classifier train step (" + ("fp16 two-plane split on v_mfma_f32_32x32x16_f16 x 3: algorithmic fp32 FLOPs priced "
-                                                  "against the fp32 matrix peak" if opt["compute"] == "float16x2" and not args.bf16 else "v_mfma_f32_32x32x2_f32, exact fp32") + ")",
-                    "algorithmic_flop_per_utt": TRAIN_FLOP_PER_UTT, "units_per_launch": batch,
-                    "note": "whole step incl. BatchNorm, Adam and projection kernels; GEMM-only time is in profiles/"}
+    if args.full:  # roofline and per-kernel figures: the MFCC kernel times were taken inside the timed steps
+        ms = ex["mfcc_ms"]
+        stage_ms = ms["resample"] + ms["stft_mel"] + ms["dct"]
+        dom = max(("resample", "stft_mel", "dct"), key=lambda k: ms[k])
+        bytes_per_utt = (32000 + 3520) if args.int16 else MFCC_BYTES_PER_UTT  # the 16-bit PCM variant reads 2 B per sample
+        achieved = bytes_per_utt * batch / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
+        # HBM traffic of the stage per launch: PMC counters cannot be read from inside this process, so the value is
+        # the committed rocprofv3 measurement of the same kernels (separate --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH
+        # doubled per MI355X_MICROARCH.md), scaled to this batch.
+        traffic, traffic_src, traffic_fused, traffic_stale = None, None, None, None
+        for name in ("r05_mfcc_pmc.json", "r04_mfcc_pmc.json", "r03_mfcc_pmc.json", "r02_mfcc_pmc.json"):
+            try:
+                with open(os.path.join(ROOT, "profiles", name)) as f:
+                    eor = json.load(f)["end_of_round"]
+                traffic_stale = eor.get("source_sha16") != mfcc_source_sha()  # (files before round 4 carry no hash: stale)
+                key = "fused_stage_bytes_per_utt" if ex.get("mfcc_fused") and "fused_stage_bytes_per_utt" in eor else "stage_bytes_per_utt"
+                traffic = round(eor[key] * batch)
+                if "fused_stage_bytes_per_utt" in eor:
+                    traffic_fused = round(eor["fused_stage_bytes_per_utt"] * batch)
+                traffic_src = f"profiles/{name} (rocprofv3 --pmc, per launch, scaled by batch)"
+                break
+            except Exception:
+                continue
+        if args.int16:  # the committed counter passes ran on float32 clips
+            traffic, traffic_src, traffic_fused = None, None, None
+        names = mfcc_kernel_names(bool(ex.get("mfcc_fused")))
+        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                    "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                    "stage": "MFCC (K1 = " + (" + ".join(dict.fromkeys(v for v in names.values() if not v.startswith("(")))) + ")",
+                    "dominant_kernel": names[dom],
+                    "kernel_names": names,
+                    "algorithmic_bytes_per_utt": bytes_per_utt, "units_per_launch": batch,
+                    "kernel_ms": {k: round(ms[k], 4) for k in ("resample", "stft_mel", "dct")},
+                    "fp32_flop_frac": round(MFCC_FLOP_PER_UTT * batch / (stage_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5) if stage_ms > 0 else 0.0,
+                    "traffic_x_algorithmic": round(traffic / (bytes_per_utt * batch), 3) if traffic else None,
+                    "fused_path_traffic": traffic_fused,  # the resample + STFT kernel (int16 / ragged input, or LIPASR_MFCC_FUSED=1): y stays in LDS
+                    "note": "stage is fp32-compute-bound (8.7 MFLOP/utt vs 67.5 kB/utt): see DESIGN.md"}
+        if ex.get("mfcc_cus"):
+            # the pipeline confines the MFCC stream to a share of the CUs (DESIGN.md, step level): its kernels take longer by
+            # design while the step gets shorter; `frac` above is what the timed region shows, the fields below put it in context
+            share = ex["mfcc_cus"] / ex["n_cus"]
+            roofline["cu_share"] = round(share, 4)
+            roofline["frac_of_share"] = round(achieved / HBM_PEAK_GBS / share, 5)
+        if ex.get("mfcc_standalone_ms"):
+            sa = ex["mfcc_standalone_ms"]
+            sa_ms = sa["resample"] + sa["stft_mel"] + sa["dct"]
+            sa_ach = bytes_per_utt * batch / (sa_ms * 1e-3) / 1e9
+            roofline["standalone_whole_chip"] = {"kernel_ms": sa, "achieved": round(sa_ach, 2), "frac": round(sa_ach / HBM_PEAK_GBS, 5),
+                                                 "fp32_flop_frac": round(MFCC_FLOP_PER_UTT * batch / (sa_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5)}
+        cls_tflops = TRAIN_FLOP_PER_UTT * batch / (ex["train_graph_ms"] * 1e-3) / 1e12 if not args.pgd and ex["train_graph_ms"] > 0 else None
+        if args.pre_extracted:
+            tf = TRAIN_FLOP_PER_UTT * batch / (ex["event_ms_per_step"] * 1e-3) / 1e12
+            roofline = {"bound": "mfma", "achieved": round(tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / FP32_PEAK_TFLOPS, 5),
+                        "traffic": None, "stage": "dense classifier train step (" + ("fp16 two-plane split on v_mfma_f32_32x32x16_f16 x 3: algorithmic fp32 FLOPs priced "
+                                                      "against the fp32 matrix peak" if opt["compute"] == "float16x2" and not args.bf16 else "v_mfma_f32_32x32x2_f32, exact fp32") + ")",
+                        "algorithmic_flop_per_utt": TRAIN_FLOP_PER_UTT, "units_per_launch": batch,
+                        "note": "whole step incl. BatchNorm, Adam and projection kernels; GEMM-only time is in profiles/"}
     out = {"metric": "utterances/sec (train, 1 s@16 kHz)", "value": round(value, 1), "unit": "utterances/sec", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
            "scaling": args.scaling, "vs_baseline": None, "dtype": "bf16" if args.bf16 else DTYPE_NAMES[opt["compute"]], "data": "synthetic",
@@ -578,27 +631,33 @@ def main():
                                   + (", data-parallel RCCL gradient all-reduce" if world > 1 else ", 1xMI355X"),
                       "baseline_config": 5 if args.pgd else (2 if args.pre_extracted else (4 if world > 1 else 3)), "global_batch": global_batch, "per_gpu_batch": batch,
                       "clip": "1 s @ 16 kHz int16 PCM" if args.int16 else "1 s @ 16 kHz fp32", "resident_pool_clips_per_gpu": ex["pool_clips"], "parallelism": f"dp{world}", "hip_graph": ex["hip_graph"]},
-           "roofline": roofline, "mfcc_stream": ex.get("mfcc_stream"),
+           "mfcc_stream": ex.get("mfcc_stream"),
            # CUs of the two CU-masked streams (disjoint): feature extraction | classifier chain
            "cu_partition": {"mfcc": ex.get("mfcc_cus"), "classifier": ex.get("train_cus") or ex.get("n_cus")},
-           # the classifier's part of the step (attack + fwd/bwd [+ all-reduce] + Adam + projection), HIP events on the training
-           # stream while the next batch's MFCC runs on its own stream; TFLOP/s = 9.59 MFLOP/utt x batch / that time
-           "train_graph_ms": round(ex["train_graph_ms"], 4), "host_enqueue_ms_per_step": round(ex["host_enqueue_ms_per_step"], 4), "classifier_tflops": round(cls_tflops, 2) if cls_tflops else None,
-           "classifier_fp32_mfma_frac": round(cls_tflops / FP32_PEAK_TFLOPS, 4) if cls_tflops else None,
+           "host_enqueue_ms_per_step": round(ex["host_enqueue_ms_per_step"], 4),
            "event_ms_per_step": round(ex["event_ms_per_step"], 4), "final_product_norm": ex["final_norm"], "loss": round(ex["loss"], 4),
-           # data parallel: how many ranks the collective backend really reduced over (SUM of ones, not WORLD_SIZE echoed), its
-           # version, the gradient all-reduce's duration (HIP events, untimed extra steps) and the share of the classifier's part
-           # of the step it exposes (the exchange is not overlapped: DESIGN.md 5)
-           "rccl_ranks_seen": ex["comm"]["ranks_seen"], "rccl_version": ex["comm"]["rccl_version"], "comm_backend": ex["comm"]["backend"],
-           "allreduce_ms": round(ex["allreduce_ms"], 4) if ex.get("allreduce_ms") is not None else None,
-           "allreduce_exposed_frac": round(ex["allreduce_ms"] / ex["train_graph_ms"], 4) if ex.get("allreduce_ms") and ex["train_graph_ms"] > 0 else None}
-    if world == 1 and not args.skip_b512 and batch != 512:
+           # data parallel: how many ranks the collective backend really reduced over (SUM of ones, not WORLD_SIZE echoed), its version
+           "rccl_ranks_seen": ex["comm"]["ranks_seen"], "rccl_version": ex["comm"]["rccl_version"], "comm_backend": ex["comm"]["backend"]}
+    if args.dump_outputs:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": ex["dump_bytes"]}
+    if args.full:
+        out.update({
+            "roofline": roofline,
+            # the classifier's part of the step (attack + fwd/bwd [+ all-reduce] + Adam + projection), HIP events on the training
+            # stream while the next batch's MFCC runs on its own stream; TFLOP/s = 9.59 MFLOP/utt x batch / that time
+            "train_graph_ms": round(ex["train_graph_ms"], 4), "classifier_tflops": round(cls_tflops, 2) if cls_tflops else None,
+            "classifier_fp32_mfma_frac": round(cls_tflops / FP32_PEAK_TFLOPS, 4) if cls_tflops else None,
+            # the gradient all-reduce's duration (HIP events, untimed extra steps) and the share of the classifier's part of the
+            # step it exposes (the exchange is not overlapped: DESIGN.md 5)
+            "allreduce_ms": round(ex["allreduce_ms"], 4) if ex.get("allreduce_ms") is not None else None,
+            "allreduce_exposed_frac": round(ex["allreduce_ms"] / ex["train_graph_ms"], 4) if ex.get("allreduce_ms") and ex["train_graph_ms"] > 0 else None})
+    if args.full and world == 1 and not args.skip_b512 and batch != 512:
         dt5, ex5 = run_config(opt, pool, 512, rank, world, device, args.steps, args.warmup, profile=True)
         out["reference_batch_512"] = {"value": round(512 * args.steps / dt5, 1), "ms_per_step": round(dt5 / args.steps * 1e3, 4),
                                       "mfcc_ms": {k: round(v, 4) for k, v in ex5["mfcc_ms"].items() if k != "calls"},
                                       "train_graph_ms": round(ex5["train_graph_ms"], 4), "event_ms_per_step": round(ex5["event_ms_per_step"], 4),
                                       "mfcc_stream": ex5.get("mfcc_stream")}
-    if world == 1 and not args.skip_other_configs and not (args.pgd or args.pre_extracted or args.bf16):
+    if args.full and world == 1 and not args.skip_other_configs and not (args.pgd or args.pre_extracted or args.bf16):
         # the other single-GPU BASELINE configurations, in the driver-run record (short runs; each is its own model + pipeline)
         k, w = min(args.steps, 50), min(args.warmup, 10)
         if opt["compute"] != "float32":  # the headline's step with the training GEMMs on exact fp32 MFMA chains (round 4's arithmetic)
@@ -620,11 +679,11 @@ def main():
         except Exception as e:
             out["reference_fit_api_batch_512"] = {"error": f"{type(e).__name__}: {e}"[:200]}
         pool = None
-    if world == 1 and not args.skip_cpu_baseline:
+    if args.full and world == 1 and not args.skip_cpu_baseline:
         pool = None
         torch.cuda.empty_cache()
         out["cpu_baseline"] = cpu_baseline(512)
-    else:
+    elif args.full:
         out["cpu_baseline"] = None
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -4,8 +4,8 @@
 out=$1; var=$2; a=$3; b=$4; steps=${5:-200}
 for rep in 1 2; do
 for v in "$a" "$b"; do
-  env $var=$v python bench.py --steps $steps --warmup 20 --skip-cpu-baseline --skip-other-configs --skip-b512 > /tmp/ab3.json 2>/tmp/ab3.err || { tail -5 /tmp/ab3.err; exit 1; }
-  python - "$var=$v" /tmp/ab3.json >> "$out" <<'P'
+  env $var=$v python bench.py --full --steps $steps --warmup 20 --skip-cpu-baseline --skip-other-configs --skip-b512 > "$out.run.json" 2> "$out.run.err" || { tail -5 "$out.run.err"; exit 1; }
+  python - "$var=$v" "$out.run.json" >> "$out" <<'P'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 r = d["roofline"]

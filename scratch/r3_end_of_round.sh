@@ -5,9 +5,9 @@
 # profiles/ by hand).
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/eor3; mkdir -p $O
 cd $R
-timeout -k 10 500 python bench.py --steps 200 --warmup 20 > $O/bench_config3.json 2> $O/bench_config3.err || exit 1
+timeout -k 10 500 python bench.py --full --steps 200 --warmup 20 > $O/bench_config3.json 2> $O/bench_config3.err || exit 1
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --steps 50 --warmup 10 --skip-cpu-baseline --skip-b512 --skip-other-configs --pool-clips 16384 > $O/prof.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --steps 50 --warmup 10 --skip-cpu-baseline --skip-b512 --skip-other-configs --pool-clips 16384 > $O/prof.log 2>&1 || exit 1
 cd $R
 bash scratch/pmc_r3.sh 0 default > $O/pmc_default.txt 2>&1
 bash scratch/pmc_r3.sh 1024 fused > $O/pmc_fused.txt 2>&1

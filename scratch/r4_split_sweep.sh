@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4: config 3 step time against the CU split (MFCC share), 300-step runs
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4_split; mkdir -p $O
-B="--steps 300 --warmup 30 --skip-cpu-baseline --skip-other-configs --skip-b512"
+B="--full --steps 300 --warmup 30 --skip-cpu-baseline --skip-other-configs --skip-b512"
 for cus in 64 96 128; do
   for rep in 1 2; do
     LIPASR_MFCC_CUS=$cus python $R/bench.py $B > $O/c3_${cus}_$rep.json 2>>$O/err.log

@@ -4,15 +4,15 @@
 # passes of the MFCC stage (HBM-side FETCH_SIZE / WRITE_SIZE and the instruction mix) -> profiles/r05_mfcc_pmc.json.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/eor5; mkdir -p $O
 cd $R
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_default_run.json 2> $O/bench_default_run.err || exit 1
-timeout -k 10 600 python bench.py --steps 200 --warmup 20 --skip-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err || exit 1
-timeout -k 10 300 python bench.py --pre-extracted --steps 200 --warmup 20 --skip-cpu-baseline --skip-other-configs --skip-b512 > $O/bench_config2.json 2> $O/bench_config2.err || exit 1
-timeout -k 10 300 python bench.py --exact-fp32 --steps 200 --warmup 20 --skip-cpu-baseline --skip-other-configs --skip-b512 > $O/bench_config3_exact_fp32.json 2> $O/bench_config3_exact.err || exit 1
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_default_run.json 2> $O/bench_default_run.err || exit 1
+timeout -k 10 600 python bench.py --full --steps 200 --warmup 20 --skip-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err || exit 1
+timeout -k 10 300 python bench.py --full --pre-extracted --steps 200 --warmup 20 --skip-cpu-baseline --skip-other-configs --skip-b512 > $O/bench_config2.json 2> $O/bench_config2.err || exit 1
+timeout -k 10 300 python bench.py --full --exact-fp32 --steps 200 --warmup 20 --skip-cpu-baseline --skip-other-configs --skip-b512 > $O/bench_config3_exact_fp32.json 2> $O/bench_config3_exact.err || exit 1
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --steps 50 --warmup 10 --skip-cpu-baseline --skip-b512 --skip-other-configs --pool-clips 16384 > $O/prof.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --steps 50 --warmup 10 --skip-cpu-baseline --skip-b512 --skip-other-configs --pool-clips 16384 > $O/prof.log 2>&1 || exit 1
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/config3_kernel_stats.csv
 rm -rf $O/prof
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -o run -- python3 $R/bench.py --pre-extracted --steps 100 --warmup 10 --skip-cpu-baseline --skip-b512 --skip-other-configs > $O/prof2.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -o run -- python3 $R/bench.py --full --pre-extracted --steps 100 --warmup 10 --skip-cpu-baseline --skip-b512 --skip-other-configs > $O/prof2.log 2>&1 || exit 1
 cp $(find $O/prof2 -name "*kernel_stats.csv" | head -1) $O/config2_kernel_stats.csv
 rm -rf $O/prof2
 cd $R

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the classifier's stream confined to the CUs the MFCC stream does not use (LIPASR_TRAIN_CUS=rest) against the default
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
-F="--skip-cpu-baseline --skip-b512 --skip-other-configs --steps 300 --warmup 20"
+F="--full --skip-cpu-baseline --skip-b512 --skip-other-configs --steps 300 --warmup 20"
 P='import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d["ms_per_step"], d.get("train_graph_ms"))'
 {
 for rep in 1 2 3; do
