@@ -111,6 +111,12 @@ struct Philox {
   __host__ __device__ static inline float u01(uint32_t x) { return ((x >> 8) + 1u) * (1.0f / 16777216.0f); }
 };
 
+// lp_attack.hip: norm 1, 2 or +inf -> code 1, 2 or 0 (else LIPASR_EINVAL with a message naming fn); the Lp step kernel on
+// [rows][n] (any n, any alignment) -- lipasr_mlp_attack_step_lp's second launch
+int lp_norm_code(const char* fn, float norm, int* code);
+int lp_step_launch(float* x_adv, const float* x0, const float* g, int rows, int n, int norm, float alpha, float eps,
+                   hipStream_t st);
+
 // spectral.hip: lipasr_project_product with an optional device counter bumped by its single-workgroup kernel
 int project_product_bump(lipasr_handle_t h, float* const* Ws, const int* rows, const int* cols, int n_layers, float rho,
                          const int* order, int n_order, float* norms_out, int* bump, lipasr_stream_t stream);

@@ -3227,6 +3227,27 @@ int lipasr_mlp_attack_step(lipasr_mlp_t m, const float* params, const float* bns
   return attack_common(m, params, bnstate, x_adv, y_onehot, batch, nullptr, x_adv, x0, alpha, eps, S(stream));
 }
 
+// Lp FGM / PGD iteration: norm inf is lipasr_mlp_attack_step (the fused K4 epilogue).  L1 / L2: the dX GEMM of layer 0 stores g
+// into the ping-pong gradient buffer that backward_infer does not read at layer 0 (both are max_batch x max(widths) wide, the
+// input width included), then the row-wise step kernel of lp_attack.hip -- two launches, no allocation, capturable.
+int lipasr_mlp_attack_step_lp(lipasr_mlp_t m, const float* params, const float* bnstate, float* x_adv, const float* x0,
+                              const float* y_onehot, int batch, float norm, float alpha, float eps, lipasr_stream_t stream) {
+  int code = 0;
+  int rc = lp_norm_code("lipasr_mlp_attack_step_lp", norm, &code);
+  if (rc != LIPASR_OK) return rc;
+  if (code == 0) return lipasr_mlp_attack_step(m, params, bnstate, x_adv, x0, y_onehot, batch, alpha, eps, stream);
+  rc = check_batch("lipasr_mlp_attack_step_lp", m, batch);
+  if (rc != LIPASR_OK) return rc;
+  LP_CHECK_ARG(params && x_adv && x0 && y_onehot, "lipasr_mlp_attack_step_lp: null argument");
+  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_attack_step_lp: bnstate is null");
+  LP_CHECK_ARG(eps >= 0.0f && !(alpha != alpha), "lipasr_mlp_attack_step_lp: eps=%g alpha=%g", (double)eps, (double)alpha);
+  // backward_infer writes layer n-1's input gradient into G0, then alternates: at layer 0 it reads G[(n-2) % 2]
+  float* g = m->ws + (((m->n_layers - 1) & 1) ? m->offG1 : m->offG0);
+  rc = attack_common(m, params, bnstate, x_adv, y_onehot, batch, g, nullptr, nullptr, 0.0f, 0.0f, S(stream));
+  if (rc != LIPASR_OK) return rc;
+  return lp_step_launch(x_adv, x0, g, batch, m->L[0].n_in, code, alpha, eps, S(stream));
+}
+
 int lipasr_mlp_output_vjp(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, const float* v,
                           int on_logits, int batch, float* probs_out, float* dx, lipasr_stream_t stream) {
   int rc = check_batch("lipasr_mlp_output_vjp", m, batch);

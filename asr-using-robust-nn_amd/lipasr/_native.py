@@ -69,6 +69,8 @@ PROTOTYPES = {
     "lipasr_bn_correction": (i32, [c_h, c_f, c_f, i32, c_f, c_s]),
     "lipasr_sv_clip": (i32, [c_h, c_f, i32, i32, f32, c_f, c_f, c_s]),
     "lipasr_sign_step": (i32, [c_h, c_f, c_f, c_f, sz, f32, f32, c_s]),
+    "lipasr_lp_step": (i32, [c_h, c_f, c_f, c_f, i32, i32, f32, f32, f32, c_s]),
+    "lipasr_lp_ball_init": (i32, [c_h, c_f, c_f, i32, i32, f32, f32, u64, c_f, i32, c_s]),
     "lipasr_scaler_fit": (i32, [c_h, c_f, i32, i32, c_f, c_f, c_s]),
     "lipasr_scaler_apply": (i32, [c_h, c_f, i32, i32, c_f, c_f, c_f, c_s]),
     "lipasr_gemm_f32": (i32, [c_h, i32, i32, i32, i32, i32, c_f, i32, c_f, i32, c_f, i32, c_s]),
@@ -99,6 +101,7 @@ PROTOTYPES = {
     "lipasr_mlp_exchange_errors": (i32, [c_h, C.POINTER(C.c_int)]),
     "lipasr_mlp_output_vjp": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, c_f, c_f, c_s]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
+    "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
     "lipasr_mfcc_plan": (i32, [c_h, i32, i32, i32]),
     "lipasr_mfcc_plan_ex": (i32, [c_h, i32, i32, i32, i32, i32]),

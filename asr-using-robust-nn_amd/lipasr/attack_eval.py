@@ -9,6 +9,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     "[S]imple/[M]ixture/[SNR]"                             kind="simple" | "mixture" | "snr"       (:326)
     "noise over [A]udio or [M]FCC"                         over="audio" | "mfcc"                   (:327)
     "[F]GSM/Carlini[L2]/Carlini[Linf]/[P]GD/[J]SMA"        kind="fgsm" | "l2" | "linf" | "pgd" | "jsma"   (:494)
+    (no prompt: ART's norm keyword of FGM / PGD)           --norm inf | 1 | 2 (default inf, the reference's)
 """
 from __future__ import annotations
 
@@ -127,6 +128,7 @@ def main(argv=None):
     ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points")
+    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword")
     args = ap.parse_args(argv)
     import os
 
@@ -140,8 +142,13 @@ def main(argv=None):
             labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)  # :298-304
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
+    kw = {}
+    if args.norm != "inf":
+        if args.kind not in ("fgsm", "pgd"):
+            raise ValueError("--norm applies to --kind fgsm and pgd")
+        kw["norm"] = int(args.norm)
     return white_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, standardize=args.standardize,
-                           points=args.points)
+                           points=args.points, **kw)
 
 
 if __name__ == "__main__":

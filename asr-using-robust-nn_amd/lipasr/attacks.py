@@ -4,7 +4,9 @@ White-box: ``TensorFlowV2Classifier`` / ``FastGradientMethod`` / ``ProjectedGrad
 the ART constructor keywords the reference uses (``estimator=``, ``eps=``) plus the ART defaults it
 relies on (norm=inf, eps_step=0.1, max_iter=100, batch_size=32, untargeted, y=None -> the model's own
 predictions, no clip_values).  Each PGD iteration is ONE native call: inference forward, CE gradient,
-backward to the input and the sign step fused into the last backward GEMM's epilogue (K4).
+backward to the input and the sign step fused into the last backward GEMM's epilogue (K4).  ART's other
+``norm`` (1, 2), ``targeted`` and ``num_random_init`` keywords run the same call in its Lp form
+(lipasr_mlp_attack_step_lp: the step is a second launch) and a native random start (lipasr_lp_ball_init).
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.
@@ -408,16 +410,43 @@ class CarliniLInfMethod(_Carlini):
         return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
 
 
+_NORMS = {np.inf: math.inf, "inf": math.inf, 1: 1.0, 2: 2.0}
+_ball_calls = [0]
+
+
+def _norm_value(norm):
+    """ART's norm keyword (np.inf, "inf", 1, 2) -> the float the C ABI takes (inf, 1.0, 2.0)."""
+    try:
+        return _NORMS[norm]
+    except (KeyError, TypeError):
+        raise ValueError(f"norm={norm!r}: np.inf, 'inf', 1 and 2 are supported") from None
+
+
 class _SignAttack:
+    """FGM / PGD over the native iteration.  norm=inf, untargeted, no random start (the reference's call) runs
+    lipasr_mlp_attack_step, whose K4 sign step is fused into the last backward GEMM; every other setting runs
+    lipasr_mlp_attack_step_lp (norm inf: the same fused launch; norm 1, 2: dX GEMM + the row-wise Lp step kernel).
+    ART semantics (1.9-1.10, restated -- parity unpinned): targeted=True descends the CE toward ``y`` (required); with
+    num_random_init = k > 0 every one of the max(1, k) restarts starts from x0 + a draw of ART's random_sphere
+    (lipasr_lp_ball_init) before its first iteration."""
+
     def __init__(self, estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init):
         if not isinstance(estimator, TensorFlowV2Classifier):
             raise TypeError("estimator must be a lipasr TensorFlowV2Classifier")
-        if norm not in (np.inf, "inf", math.inf):
-            raise NotImplementedError("only norm=inf (the ART default the reference uses) is implemented")
-        if targeted or num_random_init:
-            raise NotImplementedError("targeted / random-init variants are not used by the reference")
+        self.norm = _norm_value(norm)
+        if int(num_random_init) < 0:
+            raise ValueError("num_random_init must be >= 0")
         self.estimator, self.eps, self.eps_step = estimator, float(eps), float(eps_step)
         self.max_iter, self.batch_size = int(max_iter), int(batch_size)
+        self.targeted, self.num_random_init = bool(targeted), int(num_random_init)
+        # random starts: Philox key (seed, restart, first row of the batch) and a device counter that moves with every generate()
+        _ball_calls[0] += 1
+        self.seed = 0xBA11000000000000 + _ball_calls[0]
+        self._draws = None
+
+    @property
+    def _default_path(self):
+        return math.isinf(self.norm) and not self.targeted and self.num_random_init == 0
 
     def _labels(self, m, xb, y):
         if y is not None:
@@ -426,16 +455,60 @@ class _SignAttack:
         N.check(N.lib.lipasr_mlp_own_labels(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), xb.shape[0], N.ptr(yb), N.stream_ptr()))
         return yb
 
+    def _step(self, m, xa, x0, yb, alpha, eps):
+        """One native iteration in place on xa."""
+        if self._default_path:
+            N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
+                                                 alpha, eps, N.stream_ptr()))
+        else:
+            a = -alpha if self.targeted else alpha  # ART: gradient x (1 - 2 targeted)
+            N.check(N.lib.lipasr_mlp_attack_step_lp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb),
+                                                    xa.shape[0], self.norm, a, eps, N.stream_ptr()))
+
+    def _random_init(self, xa, x0, restart, row0):
+        """xa <- x0 + one draw of ART's random_sphere(rows, n, eps, norm) for restart ``restart`` of the rows starting at
+        ``row0`` of the generate() call (the Philox key: (seed, restart, row0); the counter: this attack's generate() count)."""
+        key = (self.seed + 0x9E3779B97F4A7C15 * (restart + 1) + 0xBF58476D1CE4E5B9 * row0) & 0xFFFFFFFFFFFFFFFF
+        h = N.get_handle(xa.device.index)
+        N.check(N.lib.lipasr_lp_ball_init(h.h, N.ptr(xa), N.ptr(x0), xa.shape[0], xa.shape[1], self.norm, self.eps, key,
+                                          N.ptr(self._draws), 0, N.stream_ptr()))
+
+    def _start(self, xa, x0, restart, row0):
+        if self.num_random_init > 0:
+            self._random_init(xa, x0, restart, row0)
+        else:
+            xa.copy_(x0)
+
+    def _success(self, m, x0, yb, xa):
+        """ART compute_success_array: argmax at xa == target (targeted) or != the clean prediction (untargeted)."""
+        pa = m.predict_device(xa.contiguous(), logits=True).argmax(dim=1)
+        if self.targeted:
+            return pa == yb.argmax(dim=1)
+        return pa != m.predict_device(x0.contiguous(), logits=True).argmax(dim=1)
+
+    def _targets(self, m, xt, yt):
+        if self.targeted and yt is None:
+            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
+        bs = min(self.batch_size, m._max_batch)
+        return torch.cat([self._labels(m, xt[s:s + bs], None if yt is None else yt[s:s + bs]) for s in range(0, xt.shape[0], bs)])
+
     def generate_device(self, xt, yt=None):
         """x: float32 device tensor; returns a NEW device tensor (the input is left untouched)."""
         m = self.estimator.model
-        adv = xt.clone()
-        bs = min(self.batch_size, m._max_batch)
-        for s in range(0, xt.shape[0], bs):
-            x0 = xt[s:s + bs]
-            xa = adv[s:s + bs]
-            yb = self._labels(m, x0, None if yt is None else yt[s:s + bs])
-            self._run(m, xa, x0, yb)
+        if self._default_path:  # the reference's call: exactly the launches of round 5
+            adv = xt.clone()
+            bs = min(self.batch_size, m._max_batch)
+            for s in range(0, xt.shape[0], bs):
+                x0 = xt[s:s + bs]
+                xa = adv[s:s + bs]
+                yb = self._labels(m, x0, None if yt is None else yt[s:s + bs])
+                self._run(m, xa, x0, yb)
+            return adv
+        if self._draws is None:
+            self._draws = torch.zeros(1, dtype=torch.int32, device=xt.device)
+        y_all = self._targets(m, xt, yt)
+        adv = self._generate_lp(m, xt, y_all)
+        self._draws += 1  # the next generate() draws fresh random starts
         return adv
 
     def generate(self, x, y=None):
@@ -446,7 +519,9 @@ class _SignAttack:
 
 
 class FastGradientMethod(_SignAttack):
-    """ART FastGradientMethod(estimator=, eps=) (attacks.py:506-510): x + eps * sign(grad), one step, no clipping."""
+    """ART FastGradientMethod(estimator=, eps=) (attacks.py:506-510): x + eps * d(grad), one step.  d = sign (norm inf: no
+    clipping on the reference's call), g / ||g||_1 or g / ||g||_2, projected on the eps ball around x as ART does.
+    num_random_init = k > 1 keeps the whole restart with the highest success rate (the first on ties: ART's compute_success)."""
 
     def __init__(self, estimator, eps=0.3, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps, 1, batch_size, norm, targeted, num_random_init)
@@ -455,10 +530,29 @@ class FastGradientMethod(_SignAttack):
         N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
                                              self.eps, math.inf, N.stream_ptr()))
 
+    def _generate_lp(self, m, xt, y_all):
+        bs = min(self.batch_size, m._max_batch)
+        best, best_rate = None, None
+        for r in range(max(1, self.num_random_init)):
+            adv = torch.empty_like(xt)
+            for s in range(0, xt.shape[0], bs):
+                x0, xa, yb = xt[s:s + bs], adv[s:s + bs], y_all[s:s + bs]
+                self._start(xa, x0, r, s)
+                self._step(m, xa, x0, yb, self.eps, self.eps)
+            if self.num_random_init > 1:
+                rate = float(torch.cat([self._success(m, xt[s:s + bs], y_all[s:s + bs], adv[s:s + bs])
+                                        for s in range(0, xt.shape[0], bs)]).float().mean())
+                if best_rate is None or rate > best_rate:
+                    best, best_rate = adv, rate
+            else:
+                best = adv
+        return best
+
 
 class ProjectedGradientDescent(_SignAttack):
     """ART ProjectedGradientDescent(estimator=, eps=) (attacks.py:657-661): max_iter steps of
-    x <- x0 + clip(x + eps_step * sign(grad) - x0, -eps, eps)."""
+    x <- x0 + P_eps(x + eps_step * d(grad) - x0), d and P as FastGradientMethod's.  With num_random_init = k > 0, restart 0's
+    result is kept and every later restart overwrites the rows where it succeeds (ART's compute_success_array)."""
 
     def __init__(self, estimator, eps=0.3, eps_step=0.1, max_iter=100, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init)
@@ -468,11 +562,38 @@ class ProjectedGradientDescent(_SignAttack):
             N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
                                                  self.eps_step, self.eps, N.stream_ptr()))
 
+    def _generate_lp(self, m, xt, y_all):
+        bs = min(self.batch_size, m._max_batch)
+        adv = torch.empty_like(xt)
+        for s in range(0, xt.shape[0], bs):
+            x0, yb, out = xt[s:s + bs], y_all[s:s + bs], adv[s:s + bs]
+            xa = torch.empty_like(x0)
+            for r in range(max(1, self.num_random_init)):
+                self._start(xa, x0, r, s)
+                for _ in range(self.max_iter):
+                    self._step(m, xa, x0, yb, self.eps_step, self.eps)
+                if r == 0:
+                    out.copy_(xa)
+                else:
+                    ok = self._success(m, x0, yb, xa)
+                    out[ok] = xa[ok]
+        return adv
+
 
 def sign_step(x_adv, x0, g, alpha, eps):
     """Stand-alone K4 on device tensors, in place on x_adv."""
     h = N.get_handle(x_adv.device.index)
     N.check(N.lib.lipasr_sign_step(h.h, N.ptr(x_adv), N.ptr(x0), N.ptr(g), x_adv.numel(), float(alpha), float(eps), N.stream_ptr()))
+    return x_adv
+
+
+def lp_step(x_adv, x0, g, alpha, eps, norm):
+    """Stand-alone K4 in any norm (lipasr_lp_step) on device tensors [rows, n] (or [n]), in place on x_adv: ART's step
+    x' = x_adv + alpha d(g) and projection onto the eps ball around x0; alpha < 0 is the targeted step, eps = inf no projection."""
+    h = N.get_handle(x_adv.device.index)
+    rows, n = (1, x_adv.numel()) if x_adv.dim() == 1 else (x_adv.shape[0], x_adv[0].numel())
+    N.check(N.lib.lipasr_lp_step(h.h, N.ptr(x_adv), N.ptr(x0), N.ptr(g), rows, n, _norm_value(norm), float(alpha), float(eps),
+                                 N.stream_ptr()))
     return x_adv
 
 

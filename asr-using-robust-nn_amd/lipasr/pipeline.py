@@ -30,7 +30,8 @@ class TrainPipeline:
                  sync_inputs=True, overlap_buckets=False, sync_bn=False, train_cus="auto"):
         """constraint: 'product' (simple_norm_constraint, all layers), 'per_layer' (norm_constraint) or None.
         affine: (mean, scale) float64 device tensors [20*utterance_length] or None.
-        pgd: dict(eps=, eps_step=, max_iter=) for adversarial training on the standardised features.
+        pgd: dict(eps=, eps_step=, max_iter=[, norm=np.inf | 1 | 2][, num_random_init=0 | 1]) for adversarial training on the
+        standardised features (norm and random start as ART's ProjectedGradientDescent).
         extractor: a feature extractor ``f(waves, mean, scale, out=)`` replacing the 2048/512 MFCC plan, e.g.
         ``speaker_recognition.WindowMfcc`` (441/220 windows -> 2020 features; pass utterance_length=101).
         mfcc_cus: how many of the GPU's CUs the feature-extraction stream may use (a CU-masked HIP stream, spread
@@ -50,6 +51,15 @@ class TrainPipeline:
         were just produced on the caller's stream or are temporaries; a loop over a resident pool that was filled and
         synchronised beforehand (bench.py) may pass False."""
         self.sync_inputs = bool(sync_inputs)
+        if pgd:
+            from .attacks import _norm_value
+
+            self._pgd_norm = _norm_value(pgd.get("norm", float("inf")))
+            rinit = int(pgd.get("num_random_init", 0))
+            if rinit not in (0, 1):
+                raise ValueError(f"pgd num_random_init={rinit}: 0 or 1 (more restarts inside training are not supported)")
+            self._pgd_rinit = rinit == 1
+            self._pgd_seed = (0xBA11000000000000 + int(model._seed)) & 0xFFFFFFFFFFFFFFFF  # + the rank, folded in by the kernel
         self._train_cus = train_cus
         # Data parallel, gradient exchange.  False: two HIP graphs around ONE all-reduce of the whole flat buffer.  True:
         # three graphs around two buckets, everything but [dW_0 | db_0] (44 % of the bytes) reduced beside the dW_0 GEMM.
@@ -270,32 +280,41 @@ class TrainPipeline:
                                f"after {self._flag_timeout_ms} ms without the other stream's signal; LIPASR_GPU_FLAGS=0 uses events")
 
     # ---- pieces (all enqueue on the current stream)
+    def _pgd_loop(self, bsz, x, y):
+        """PGD on x with the batch's labels into self.x_adv[:bsz].  norm inf: the fused sign-step iteration; norm 1 / 2: its Lp
+        form (one launch more per iteration).  num_random_init=1: the start is x + a draw from the eps ball keyed by the model's
+        device step counter and the replica rank, so every step (eager or a replayed graph) draws a fresh one."""
+        m = self.model
+        eps, eps_step = float(self.pgd["eps"]), float(self.pgd.get("eps_step", 0.1))
+        xa = self.x_adv[:bsz]
+        if self._pgd_rinit:
+            N.check(N.lib.lipasr_lp_ball_init(self.h.h, N.ptr(xa), N.ptr(x), bsz, xa.shape[1], self._pgd_norm, eps, self._pgd_seed,
+                                              N.ptr(m._step), self.dp.rank, N.stream_ptr()))
+        else:
+            xa.copy_(x)
+        for _ in range(int(self.pgd.get("max_iter", 20))):
+            if self._pgd_norm == float("inf"):
+                N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x), N.ptr(y), bsz,
+                                                     eps_step, eps, N.stream_ptr()))
+            else:
+                N.check(N.lib.lipasr_mlp_attack_step_lp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x), N.ptr(y), bsz,
+                                                        self._pgd_norm, eps_step, eps, N.stream_ptr()))
+        return xa
+
     def _attack_and_train(self, bsz, b, global_batch, defer_dw0=False):
         m = self.model
         x = self._feats2[b][:bsz]
         y = self._labels2[b][:bsz]
         if self.pgd:
-            xa = self.x_adv[:bsz]
-            xa.copy_(x)
-            for _ in range(int(self.pgd.get("max_iter", 20))):
-                N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x), N.ptr(y), bsz,
-                                                     float(self.pgd.get("eps_step", 0.1)), float(self.pgd["eps"]), N.stream_ptr()))
-            x = xa
+            x = self._pgd_loop(bsz, x, y)
         m.train_fwd_bwd(x, y, inv_batch=1.0 / float(global_batch), defer_dw0=defer_dw0)
 
     def _attack_only(self, bsz, b):
         """The PGD inner loop alone (inference-mode BatchNorm: nothing to synchronise); returns the training input."""
-        m = self.model
         x = self._feats2[b][:bsz]
         if not self.pgd:
             return x
-        y = self._labels2[b][:bsz]
-        xa = self.x_adv[:bsz]
-        xa.copy_(x)
-        for _ in range(int(self.pgd.get("max_iter", 20))):
-            N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x), N.ptr(y), bsz,
-                                                 float(self.pgd.get("eps_step", 0.1)), float(self.pgd["eps"]), N.stream_ptr()))
-        return xa
+        return self._pgd_loop(bsz, x, self._labels2[b][:bsz])
 
     def _syncbn_step(self, bsz, b, gb):
         """Synchronized BatchNorm: [PGD loop] -> segment 0 | all-reduce | segment 1 | ... | gradient all-reduce | update.

@@ -8,10 +8,10 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 500 = round 5.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 510.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
- * lipasr_debug_launch_count).
+ * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -157,6 +157,28 @@ int lipasr_sv_clip(lipasr_handle_t h, const float* X, int R, int n, float hi, fl
  * NaN gradients count as 0.  eps = +inf gives the plain FGSM step. */
 int lipasr_sign_step(lipasr_handle_t h, float* x_adv, const float* x0, const float* g, size_t n,
                      float alpha, float eps, lipasr_stream_t stream);
+
+/* ------------------------------------------------------------------ K4 in any norm (ART FastGradientMethod / ProjectedGradientDescent,
+ * norm=1, 2 or inf).  `norm` is 1.0f, 2.0f or +INFINITY; anything else returns LIPASR_EINVAL.  tol = 1e-7 (ART's 10e-8).
+ * lipasr_lp_step: one step plus projection, in place on x_adv [rows][n] (any n), per row:
+ *   g   <- g with NaN entries set to 0
+ *   d   <- sign(g) (inf) | g / (sum|g| + tol) (1) | g / (||g||_2 + tol) (2)
+ *   x'  <- x_adv + alpha d             (a negative alpha descends: the targeted attack, ART's (1 - 2 targeted) factor)
+ *   x_adv <- x0 + clip(x' - x0, -eps, eps) (inf) | x0 + (x' - x0) min(1, eps / (||x' - x0||_p + tol)) (1, 2);  eps = +inf: x'
+ * Under norm 1 and 2 a row whose gradient norm is not finite (a +-inf entry) takes no step and is only projected; under norm
+ * inf a +-inf entry steps by its sign (as lipasr_sign_step does).  One wavefront per row, reductions in a fixed order:
+ * bit-identical on every run; norm inf gives lipasr_sign_step's bits. */
+int lipasr_lp_step(lipasr_handle_t h, float* x_adv, const float* x0, const float* g, int rows, int n, float norm, float alpha,
+                   float eps, lipasr_stream_t stream);
+/* ART's random start (random_sphere(rows, n, eps, norm), the num_random_init of FGM / PGD): x_adv <- x0 + delta, delta
+ * uniform on [-eps, eps]^n (inf), uniform in the L2 ball (2: eps U^(1/n) a / |a|, a Gaussian -- the law of ART's gammainc
+ * form), or ART's L1 draw (1: radius eps sqrt(U), split as r E_i / sum E_j with exponential E_i and random signs -- the gaps
+ * of sorted uniforms, not uniform in the L1 ball).  Philox keyed like the dropout masks: key seed + rank x golden ratio,
+ * counter (element group, row, *counter_dev) -- counter_dev is a device int (NULL counts as 0) read by the kernel, so a
+ * replayed graph draws afresh whenever the caller's counter moves, and equal (seed, *counter_dev, rank) give equal bits.
+ * eps finite and >= 0. */
+int lipasr_lp_ball_init(lipasr_handle_t h, float* x_adv, const float* x0, int rows, int n, float norm, float eps, uint64_t seed,
+                        const int* counter_dev, int rank, lipasr_stream_t stream);
 
 /* ------------------------------------------------------------------ A2: StandardScaler
  * sklearn StandardScaler().fit_transform (train_constraints.py:28-31, attacks.py:61-63):
@@ -343,6 +365,14 @@ int lipasr_mlp_output_vjp(lipasr_mlp_t m, const float* params, const float* bnst
 int lipasr_mlp_attack_step(lipasr_mlp_t m, const float* params, const float* bnstate, float* x_adv,
                            const float* x0, const float* y_onehot, int batch, float alpha, float eps,
                            lipasr_stream_t stream);
+
+/* One FGM / PGD iteration in any norm (1.0f, 2.0f or +INFINITY; else LIPASR_EINVAL): norm inf IS lipasr_mlp_attack_step
+ * (same launches, same bits).  Norm 1, 2: inference forward at x_adv, CE gradient, backward to the input with dx stored in a
+ * plan workspace buffer, then the lipasr_lp_step kernel -- one launch more than the fused inf path, because the step needs
+ * a norm over the whole row of dx and the row spans several column tiles of the dX GEMM.  alpha < 0 is the targeted attack
+ * (ART multiplies the gradient by 1 - 2 targeted; y_onehot then holds the targets). */
+int lipasr_mlp_attack_step_lp(lipasr_mlp_t m, const float* params, const float* bnstate, float* x_adv, const float* x0,
+                              const float* y_onehot, int batch, float norm, float alpha, float eps, lipasr_stream_t stream);
 
 /* ART y=None: labels := one-hot argmax of the estimator's own prediction. */
 int lipasr_mlp_own_labels(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x,
