@@ -13,7 +13,7 @@ void set_error(const char* fmt, ...) {
 }
 
 void mfcc_plan_free(MfccPlan* p);  // mfcc.hip
-void mlp_plan_free(lipasr_mlp* m);   // dense.hip
+void mlp_plan_free(lipasr_mlp* m);   // mlp.hip
 
 }  // namespace lipasr
 

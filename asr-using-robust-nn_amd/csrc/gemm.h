@@ -1,0 +1,176 @@
+// The dense classifier's GEMM interface: what a launch is told (GemmArgs, its epilogues and dropout arguments), the grouped
+// launch's argument block, and the host entry points of gemm.hip that the plan (mlp.hip) calls.  The tile kernels, the
+// choice of one (pick_gemm) and the launchers live in gemm.hip.
+#pragma once
+#include "mlp.h"
+
+namespace lipasr {
+
+enum Epi {
+  EPI_STORE = 0,
+  EPI_BIAS = 1,
+  EPI_BIAS_RELU = 2,
+  EPI_BIAS_RELU_BN = 3,
+  EPI_DZ_INFER = 4,
+  EPI_SIGNSTEP = 5,
+  EPI_BIAS_RELU_STATS = 6,  // training forward: a = relu(acc + b) and per-tile column sums of a, a^2
+  EPI_DH_STATS = 7,         // training backward: g = acc * dropout and per-tile column sums of g, g * xhat
+  EPI_DZ_NOBN = 8,          // training backward through Dropout -> ReLU without BatchNorm
+  EPI_BIAS_SOFTMAX_CE = 9,  // last layer (N <= 32, one column tile): logits, softmax, CE loss and (p - y) / B in one
+  EPI_BIAS_RELU_BNX = 10,   // round 5, training forward: a = relu(acc + b), BatchNorm statistics exchanged between the row tiles of
+                            // the column block inside the launch, h = dropout(BN(a)) -- no apply kernel
+  EPI_DH_BNX = 11           // round 5, training backward: g = acc * dropout, sums of g, g xhat exchanged, dz = BN/ReLU backward
+};
+
+// ---------------------------------------------------------------------------------------------
+// dropout multiplier: 0 or 1/(1-rate), Philox keyed by (seed; element/4, layer, step)
+// ---------------------------------------------------------------------------------------------
+struct DropArgs {
+  int mode;  // 0 off, 1 philox, 2 external
+  float rate;
+  uint64_t seed;
+  const int* step_dev;
+  int layer;
+  const float* mask;
+};
+
+__device__ __forceinline__ float dropout_mult(const DropArgs& d, int step, size_t e) {
+  if (d.mode == 0 || d.rate <= 0.0f) return 1.0f;
+  if (d.mode == 2) return d.mask ? d.mask[e] : 1.0f;
+  uint32_t o[4];
+  Philox::gen(d.seed, (uint64_t)(e >> 2), (uint32_t)d.layer, (uint32_t)step, o);
+  const float u = Philox::u01(o[e & 3]);
+  return u > d.rate ? 1.0f / (1.0f - d.rate) : 0.0f;
+}
+
+
+struct GemmArgs {
+  const float* A;
+  const float* B;
+  float* C;
+  int M, N, K, lda, ldb, ldc;
+  int epi;
+  const float* bias;
+  const float* gamma;
+  const float* beta;
+  const float* mmean;
+  const float* mvar;
+  float* aux;        // EPI_BIAS_RELU_BN: optional post-ReLU store; EPI_DZ_INFER: post-ReLU activations (read)
+  const float* x0;   // EPI_SIGNSTEP
+  float* x_adv;
+  float alpha, eps;
+  float* part;             // *_STATS: [2][gridDim.y][N] per-row-tile column partial sums
+  const float* save_mean;  // EPI_DH_STATS: batch mean [N], rstd at +N
+  DropArgs drop;           // EPI_DH_STATS / EPI_DZ_NOBN
+  int ones_row;            // AMODE 1 only: row M-1 of op(A) is all ones (bias gradient = column sums of B)
+  float* extra_out;        // its output row goes here instead of C
+  // EPI_BIAS_SOFTMAX_CE (what softmax_ce_kernel computes, fused): labels in, the rest optional outputs
+  const float* y;          // [M][N] one-hot
+  float inv_batch;
+  float* prob;             // [M][N]
+  float* dz;               // [M][N] (p - y) * inv_batch
+  float* loss_rows;        // [M]
+  float* correct_rows;     // [M]
+  // 0: exact fp32 (v_mfma_f32_32x32x2_f32).  1: operands rounded to bf16 (RNE) at the MFMA, fp32 accumulate
+  // (v_mfma_f32_32x32x16_bf16): BASELINE config 2's arithmetic; memory stays fp32.
+  int bf16;
+  const unsigned* sa_dyn;  // arithmetic mode 2: the operand's largest magnitude (float bits, written by its producer's epilogue): the
+  const unsigned* sb_dyn;  // scale is derived from it at run time (gradients: their size is not known beforehand); else sa / sb
+  unsigned* amax_out;      // EPI_DH_BNX: max |dz| of this launch is folded into this word (atomic max of float bits)
+  unsigned* amax_zero;     // forward launches: workgroup (0, 0) clears this word (the backward pass of the same step fills it)
+  float sa, sb;       // arithmetic mode 2: powers of two that bring op(A) and B into fp16's range before the split (the accumulator is divided by sa sb)
+  int lds_min_tiles;  // host side only: 64x64 tiles from which launch_gemm takes the LDS-tiled kernel (0 = the default)
+  const float* zeros; // >= 16 bytes of zeros in device memory (the ring kernel's source for k >= K in the last k-step), or null
+  int cus;            // host side: CUs the launch may use (the plan's budget; 0 = unknown, the whole device)
+  int ring;           // host side / grouped launch: this problem takes the LDS-DMA ring tile (mode 2, ring_legal)
+  int xcd_map;        // 1: workgroup -> tile by xcd_tile() (a compact patch of the tile grid per XCD); 0: blockIdx as it comes
+  // EPI_BIAS_RELU_BNX / EPI_DH_BNX (the exchange epilogue)
+  unsigned long long* xc_gran;  // [32-column block][xc_rt_max][128] {tag, value}
+  unsigned* xc_ctrl;            // [32-column block][32]: word 0 generation, word 1 arrivals
+  int* xc_err;
+  int xc_rt_max;
+  int Bstat;                    // rows the statistics are taken over
+  float grad_scale;             // EPI_DH_BNX: factor on dgamma / dbeta
+  float* h_out;                 // EPI_BIAS_RELU_BNX: BatchNorm + dropout output (C receives the post-ReLU activations)
+  float* mmean_w;               // EPI_BIAS_RELU_BNX: moving statistics (updated by row tile 0), saved batch mean | rstd
+  float* mvar_w;
+  float* save_w;
+  float* dgamma;                // EPI_DH_BNX
+  float* dbeta;
+};
+
+// mode 2, operands whose size is not known beforehand (gradients): the producer's epilogue leaves max |x| as float bits; the
+// scale 2^(14 - e) with max = f 2^e, f in [0.5, 1), puts the largest value in [2^13, 2^14) -- a factor 4 under fp16's 65504
+// The maximum lives in kAmaxSlots words, one per 64-byte line: 2048 wavefronts folding their maxima into ONE word cost the backward
+// kernels 10-22 us each (atomics execute at the memory side, one address serialises them); spread over 64 lines they run side by
+// side, and a consumer reads the 64 words with one coalesced... strided load per wavefront and a wave maximum.
+constexpr int kAmaxSlots = 64, kAmaxStride = 16;  // words
+__device__ __forceinline__ float scale_from_amax(const unsigned* p, const float fallback) {
+  if (!p) return fallback;
+  const float a = wave_max(__uint_as_float(p[(threadIdx.x & 63) * kAmaxStride]));
+  if (!(a > 0.0f) || !(a < INFINITY)) return 1.0f;  // all zero, or NaN / inf (which then propagate as they should)
+  int e = 0;
+  (void)frexpf(a, &e);
+  return ldexpf(1.0f, 14 - e);
+}
+__device__ __forceinline__ void amax_publish(unsigned* out, float m) {
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) {
+    const unsigned w = (blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    atomicMax(out + (w & (kAmaxSlots - 1)) * kAmaxStride, __float_as_uint(m));  // (non-negative floats order like their bits; NaN is the largest)
+  }
+}
+// workgroup (0, 0) of a forward launch clears the words the backward pass of the same step will fold into
+__device__ __forceinline__ void amax_clear(unsigned* out) {
+  if (threadIdx.x < kAmaxSlots) out[threadIdx.x * kAmaxStride] = 0u;
+}
+
+// Several independent GEMMs of one (AMODE, BMODE) in ONE launch: the six weight-gradient GEMMs of a training step
+// (outputs from 880x1024 down to 64x10, all with K = batch) fill the chip together instead of running as six
+// mostly latency-bound launches.  Block b belongs to the problem whose tile range contains it.
+constexpr int kMaxGroup = 8;
+struct GemmGroup {
+  int n;
+  int tile_start[kMaxGroup + 1];
+  GemmArgs g[kMaxGroup];
+};
+
+// ---- host side (gemm.hip)
+// lipasr_debug_gemm_mode(mode): A/B-timing and profiling knobs, never a different backend.  mode 0 (every field at its default
+// below) is what ships; the bits are decoded in that one function and documented here.
+struct GemmKnobs {
+  int gemm_mode = 0;       // bits 0-1: 0 auto, 1 split-K kernel only, 2 LDS kernel wherever it is legal (profiling knob)
+  bool split_dw0 = false;  // bit 2: the first layer's weight gradient as its own launch
+  bool group_lds = true;   // bit 3 clears it: the grouped launch on 32x32 fragment tiles (round 2)
+  int xcd_map = 0;         // bit 4 SETS it (round 5: measured, not kept): the XCD-aware blockIdx -> tile map of xcd_tile().
+                           // Same box, interleaved: config 2 0.3177 with it against 0.3148 without, config 3 0.3653 against 0.3625; the counters
+                           // (TCC hit 67 % on the weight-gradient launch either way) say the operand panels are not what misses.
+  bool no_ring = false;    // bit 5: arithmetic mode 2 on the register-staged tiles only (no LDS-DMA ring)
+  int ring_tile = 2;       // weight-gradient group: 2 = the 128 x 128 tile with the split pass, 1 = the 64 x 64 ring tile (bit 6),
+                           // 3 = the 128 x 128 tile that splits per fragment (bit 7)
+  bool ring2 = true;       // bit 8 clears it: no 128 x 64 exchange tiles
+  bool ring_x1 = true;     // bit 9 clears it: no loader-wavefront instance for exchange launches of one workgroup per CU
+};
+const GemmKnobs& gemm_knobs();
+
+enum GemmKind { GK_FRAG4 = 0, GK_FRAG16, GK_LDS, GK_RING, GK_RING_X1, GK_RING2, GK_KINDS };
+
+// what pick_gemm chose: the instance, one workgroup's output tile (grid = ceil(N / tile_n) x ceil(M / tile_m)), the launch shape
+struct GemmPick {
+  int kind;  // GemmKind
+  int tile_m, tile_n, threads;
+  size_t lds_bytes;
+  const void* fn;
+};
+
+// amode / bmode: 1 = the operand is k-major in memory (P[k ld + i])
+int pick_gemm(int amode, int bmode, const GemmArgs& g, GemmPick* out);  // the choice only: launches nothing, counts nothing
+int launch_gemm(int amode, int bmode, const GemmArgs& g, hipStream_t st);
+int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st);  // up to kMaxGroup weight-gradient style GEMMs (AMODE 1, BMODE 1) per grid
+GemmArgs gemm_args(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, int epi);
+// row tiles of a launch = the leading extent of the *_STATS epilogues' column partials
+int gemm_row_tiles(int amode, int bmode, const GemmArgs& g);
+// may the (M, N, K) GEMM of a plan take the exchange epilogue (EPI_*_BNX)?  bmode 1: forward, 0: input gradient
+bool exchange_fits(int bmode, int arith, int M, int N, int K, int lds_min_tiles, int xc_rt_max, int cus);
+
+}  // namespace lipasr

@@ -1,5 +1,6 @@
-// K2: the dense classifier on fp32 MFMA (gfx950), plus BatchNorm / dropout / softmax-CE kernels and
-// the plan-level forward / backward / predict / attack sequences.
+// K2: the dense classifier's GEMMs on fp32 / bf16 / fp16 MFMA (gfx950): the tile kernels, the choice of one for a problem
+// (pick_gemm) and the launchers.  The interface is gemm.h; the BatchNorm / dropout / softmax-CE kernels and the plan-level
+// forward / backward / predict / attack sequences that call these launchers are mlp.hip.
 //
 // GEMM design (v_mfma_f32_32x32x2_f32, exact fp32 fma chains):
 //   The classifier's GEMMs are small (M = batch 512..1024, N <= 1024, K <= 1024): with one 32x32
@@ -13,106 +14,17 @@
 //
 //   Epilogues fuse: bias (+ReLU), inference BatchNorm affine, the ReLU/BN backward mask of the
 //   inference-mode input gradient, and the FGSM/PGD sign step (K4) on the last backward GEMM.
-#include "mlp.h"
+#include "gemm.h"
+#include <cstdint>
+#include <map>
+#include <mutex>
 #include <type_traits>
+#include <utility>
 
 namespace lipasr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-enum Epi {
-  EPI_STORE = 0,
-  EPI_BIAS = 1,
-  EPI_BIAS_RELU = 2,
-  EPI_BIAS_RELU_BN = 3,
-  EPI_DZ_INFER = 4,
-  EPI_SIGNSTEP = 5,
-  EPI_BIAS_RELU_STATS = 6,  // training forward: a = relu(acc + b) and per-tile column sums of a, a^2
-  EPI_DH_STATS = 7,         // training backward: g = acc * dropout and per-tile column sums of g, g * xhat
-  EPI_DZ_NOBN = 8,          // training backward through Dropout -> ReLU without BatchNorm
-  EPI_BIAS_SOFTMAX_CE = 9,  // last layer (N <= 32, one column tile): logits, softmax, CE loss and (p - y) / B in one
-  EPI_BIAS_RELU_BNX = 10,   // round 5, training forward: a = relu(acc + b), BatchNorm statistics exchanged between the row tiles of
-                            // the column block inside the launch, h = dropout(BN(a)) -- no apply kernel
-  EPI_DH_BNX = 11           // round 5, training backward: g = acc * dropout, sums of g, g xhat exchanged, dz = BN/ReLU backward
-};
-
-// ---------------------------------------------------------------------------------------------
-// dropout multiplier: 0 or 1/(1-rate), Philox keyed by (seed; element/4, layer, step)
-// ---------------------------------------------------------------------------------------------
-struct DropArgs {
-  int mode;  // 0 off, 1 philox, 2 external
-  float rate;
-  uint64_t seed;
-  const int* step_dev;
-  int layer;
-  const float* mask;
-};
-
-__device__ __forceinline__ float dropout_mult(const DropArgs& d, int step, size_t e) {
-  if (d.mode == 0 || d.rate <= 0.0f) return 1.0f;
-  if (d.mode == 2) return d.mask ? d.mask[e] : 1.0f;
-  uint32_t o[4];
-  Philox::gen(d.seed, (uint64_t)(e >> 2), (uint32_t)d.layer, (uint32_t)step, o);
-  const float u = Philox::u01(o[e & 3]);
-  return u > d.rate ? 1.0f / (1.0f - d.rate) : 0.0f;
-}
-
-
-struct GemmArgs {
-  const float* A;
-  const float* B;
-  float* C;
-  int M, N, K, lda, ldb, ldc;
-  int epi;
-  const float* bias;
-  const float* gamma;
-  const float* beta;
-  const float* mmean;
-  const float* mvar;
-  float* aux;        // EPI_BIAS_RELU_BN: optional post-ReLU store; EPI_DZ_INFER: post-ReLU activations (read)
-  const float* x0;   // EPI_SIGNSTEP
-  float* x_adv;
-  float alpha, eps;
-  float* part;             // *_STATS: [2][gridDim.y][N] per-row-tile column partial sums
-  const float* save_mean;  // EPI_DH_STATS: batch mean [N], rstd at +N
-  DropArgs drop;           // EPI_DH_STATS / EPI_DZ_NOBN
-  int ones_row;            // AMODE 1 only: row M-1 of op(A) is all ones (bias gradient = column sums of B)
-  float* extra_out;        // its output row goes here instead of C
-  // EPI_BIAS_SOFTMAX_CE (what softmax_ce_kernel computes, fused): labels in, the rest optional outputs
-  const float* y;          // [M][N] one-hot
-  float inv_batch;
-  float* prob;             // [M][N]
-  float* dz;               // [M][N] (p - y) * inv_batch
-  float* loss_rows;        // [M]
-  float* correct_rows;     // [M]
-  // 0: exact fp32 (v_mfma_f32_32x32x2_f32).  1: operands rounded to bf16 (RNE) at the MFMA, fp32 accumulate
-  // (v_mfma_f32_32x32x16_bf16): BASELINE config 2's arithmetic; memory stays fp32.
-  int bf16;
-  const unsigned* sa_dyn;  // arithmetic mode 2: the operand's largest magnitude (float bits, written by its producer's epilogue): the
-  const unsigned* sb_dyn;  // scale is derived from it at run time (gradients: their size is not known beforehand); else sa / sb
-  unsigned* amax_out;      // EPI_DH_BNX: max |dz| of this launch is folded into this word (atomic max of float bits)
-  unsigned* amax_zero;     // forward launches: workgroup (0, 0) clears this word (the backward pass of the same step fills it)
-  float sa, sb;       // arithmetic mode 2: powers of two that bring op(A) and B into fp16's range before the split (the accumulator is divided by sa sb)
-  int lds_min_tiles;  // host side only: 64x64 tiles from which launch_gemm takes the LDS-tiled kernel (0 = the default)
-  const float* zeros; // >= 16 bytes of zeros in device memory (the ring kernel's source for k >= K in the last k-step), or null
-  int cus;            // host side: CUs the launch may use (the plan's budget; 0 = unknown, the whole device)
-  int ring;           // host side / grouped launch: this problem takes the LDS-DMA ring tile (mode 2, ring_legal)
-  int xcd_map;        // 1: workgroup -> tile by xcd_tile() (a compact patch of the tile grid per XCD); 0: blockIdx as it comes
-  // EPI_BIAS_RELU_BNX / EPI_DH_BNX (the exchange epilogue)
-  unsigned long long* xc_gran;  // [32-column block][xc_rt_max][128] {tag, value}
-  unsigned* xc_ctrl;            // [32-column block][32]: word 0 generation, word 1 arrivals
-  int* xc_err;
-  int xc_rt_max;
-  int Bstat;                    // rows the statistics are taken over
-  float grad_scale;             // EPI_DH_BNX: factor on dgamma / dbeta
-  float* h_out;                 // EPI_BIAS_RELU_BNX: BatchNorm + dropout output (C receives the post-ReLU activations)
-  float* mmean_w;               // EPI_BIAS_RELU_BNX: moving statistics (updated by row tile 0), saved batch mean | rstd
-  float* mvar_w;
-  float* save_w;
-  float* dgamma;                // EPI_DH_BNX
-  float* dbeta;
-};
 
 // eight consecutive-k fp32 operand values of a lane -> one bf16 fragment (lane (r, h) holds k = 8 h + j, j < 8)
 __device__ __forceinline__ bf16x8 to_bf16x8(const float (&v)[8]) {
@@ -177,31 +89,6 @@ __device__ __forceinline__ void split8(const float (&x)[8], const float scale, f
   }
   hi = __builtin_bit_cast(f16x8, make_uint4(h[0], h[1], h[2], h[3]));
   lo = __builtin_bit_cast(f16x8, make_uint4(l[0], l[1], l[2], l[3]));
-}
-// mode 2, operands whose size is not known beforehand (gradients): the producer's epilogue leaves max |x| as float bits; the
-// scale 2^(14 - e) with max = f 2^e, f in [0.5, 1), puts the largest value in [2^13, 2^14) -- a factor 4 under fp16's 65504
-// The maximum lives in kAmaxSlots words, one per 64-byte line: 2048 wavefronts folding their maxima into ONE word cost the backward
-// kernels 10-22 us each (atomics execute at the memory side, one address serialises them); spread over 64 lines they run side by
-// side, and a consumer reads the 64 words with one coalesced... strided load per wavefront and a wave maximum.
-constexpr int kAmaxSlots = 64, kAmaxStride = 16;  // words
-__device__ __forceinline__ float scale_from_amax(const unsigned* p, const float fallback) {
-  if (!p) return fallback;
-  const float a = wave_max(__uint_as_float(p[(threadIdx.x & 63) * kAmaxStride]));
-  if (!(a > 0.0f) || !(a < INFINITY)) return 1.0f;  // all zero, or NaN / inf (which then propagate as they should)
-  int e = 0;
-  (void)frexpf(a, &e);
-  return ldexpf(1.0f, 14 - e);
-}
-__device__ __forceinline__ void amax_publish(unsigned* out, float m) {
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) {
-    const unsigned w = (blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    atomicMax(out + (w & (kAmaxSlots - 1)) * kAmaxStride, __float_as_uint(m));  // (non-negative floats order like their bits; NaN is the largest)
-  }
-}
-// workgroup (0, 0) of a forward launch clears the words the backward pass of the same step will fold into
-__device__ __forceinline__ void amax_clear(unsigned* out) {
-  if (threadIdx.x < kAmaxSlots) out[threadIdx.x * kAmaxStride] = 0u;
 }
 // one 16-deep chunk: acc += a b on three fp16 matrix instructions
 template <bool UA = false>  // UA: the A operand is unscaled (sa == 1: activations)
@@ -837,15 +724,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_f32_kernel(GemmArgs g) {  // run
   gemm_tile<AMODE, BMODE, NW, BF, X>(g, bx, by, gridDim.y);
 }
 
-// Several independent GEMMs of one (AMODE, BMODE) in ONE launch: the six weight-gradient GEMMs of a training step
-// (outputs from 880x1024 down to 64x10, all with K = batch) fill the chip together instead of running as six
-// mostly latency-bound launches.  Block b belongs to the problem whose tile range contains it.
-constexpr int kMaxGroup = 8;
-struct GemmGroup {
-  int n;
-  int tile_start[kMaxGroup + 1];
-  GemmArgs g[kMaxGroup];
-};
 
 template <int AMODE, int BMODE, int NW, int BF = 0>
 __global__ __launch_bounds__(64 * NW) void gemm_f32_grouped_kernel(GemmGroup grp) {
@@ -1902,13 +1780,98 @@ __global__ __launch_bounds__(512 + 64 * kR2Loaders) void gemm_ring2_kernel(GemmA
   gemm_ring2_tile<BMODE>(g, blockIdx.x, blockIdx.y, gridDim.y);
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Host side.  pick_gemm is the ONE place that decides which instance runs a problem; launch_gemm, gemm_row_tiles and
+// exchange_fits all go through it or through the predicates it is written with.
+// ---------------------------------------------------------------------------------------------
+static GemmKnobs g_knobs;
+const GemmKnobs& gemm_knobs() { return g_knobs; }
+static long g_launch_count[2] = {0, 0};  // lipasr_debug_launch_count: 0 = launches on 128 x 64 exchange tiles, 1 = weight-gradient launches with 128 x 128 split-pass tiles
+
+// CUs of the current device, asked once per device (for launches whose caller leaves GemmArgs::cus at 0)
+static int device_cus() {
+  static int cached[16] = {};
+  int dev = 0; (void)hipGetDevice(&dev);
+  int& c = cached[dev & 15];
+  if (!c) { hipDeviceProp_t prop; c = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
+  return c;
+}
+
+// The one place that raises a kernel's dynamic LDS limit, once per (kernel, device).  false: the device refused the size (kept
+// too, so that a refused size is asked once).
+static bool ensure_dyn_lds(const void* fn, size_t bytes) {
+  if (bytes <= 48 * 1024) return true;
+  struct Limit { size_t granted = 0, refused = SIZE_MAX; };
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, Limit> limits;
+  int dev = 0; (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(mu);
+  Limit& l = limits[{fn, dev}];
+  if (bytes <= l.granted) return true;
+  if (bytes >= l.refused) return false;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) { l.granted = bytes; return true; }
+  (void)hipGetLastError();
+  l.refused = bytes;
+  return false;
+}
+
+// Every instantiated GEMM kernel, indexed by what the templates are parameterised on; null = not instantiated.
+// arithmetic mode (GemmArgs::bf16: 0 exact fp32, 1 bf16 operands, 2 fp16 two-plane split) -> index
+static int arith_index(int bf16) { return bf16 == 2 ? 2 : bf16 == 1 ? 1 : 0; }
+struct GemmTable {
+  const void* fn[GK_KINDS][2][2][2][3] = {};  // [kind][exchange epilogue][AMODE][BMODE][arithmetic]
+  const void* grouped_frag[3] = {}, *grouped_lds[3] = {}, *grouped_ring = nullptr;  // weight-gradient groups (AMODE 1, BMODE 1)
+  template <int A, int B, int AR> void plain() {
+    fn[GK_FRAG4][0][A][B][AR] = reinterpret_cast<const void*>(gemm_f32_kernel<A, B, 4, AR>);
+    fn[GK_FRAG16][0][A][B][AR] = reinterpret_cast<const void*>(gemm_f32_kernel<A, B, 16, AR>);
+    fn[GK_LDS][0][A][B][AR] = reinterpret_cast<const void*>(gemm_lds_kernel<A, B, AR>);
+  }
+  template <int A, int B> void plain_modes() {
+    plain<A, B, 0>(); plain<A, B, 1>(); plain<A, B, 2>();
+    fn[GK_RING][0][A][B][2] = reinterpret_cast<const void*>(gemm_ring_kernel<A, B>);
+  }
+  template <int B, int AR> void exchange() {  // forward (NN) or input-gradient (NT) GEMMs only: AMODE 0
+    fn[GK_FRAG4][1][0][B][AR] = reinterpret_cast<const void*>(gemm_f32_kernel<0, B, 4, AR, true>);
+    fn[GK_LDS][1][0][B][AR] = reinterpret_cast<const void*>(gemm_lds_kernel<0, B, AR, kLdsBKMax, true>);
+  }
+  template <int B> void exchange_modes() {
+    exchange<B, 0>(); exchange<B, 1>(); exchange<B, 2>();
+    fn[GK_RING][1][0][B][2] = reinterpret_cast<const void*>(gemm_ring_kernel<0, B, true>);
+    fn[GK_RING_X1][1][0][B][2] = reinterpret_cast<const void*>(gemm_ring_x1_kernel<B>);
+    fn[GK_RING2][1][0][B][2] = reinterpret_cast<const void*>(gemm_ring2_kernel<B>);
+  }
+  template <int AR> void grouped() {
+    grouped_frag[AR] = reinterpret_cast<const void*>(gemm_f32_grouped_kernel<1, 1, 4, AR>);
+    grouped_lds[AR] = reinterpret_cast<const void*>(gemm_lds_grouped_kernel<1, 1, AR>);
+  }
+  GemmTable() {
+    plain_modes<0, 0>(); plain_modes<0, 1>(); plain_modes<1, 0>(); plain_modes<1, 1>();
+    exchange_modes<0>(); exchange_modes<1>();
+    grouped<0>(); grouped<1>(); grouped<2>();
+    grouped_ring = reinterpret_cast<const void*>(gemm_ring_grouped_kernel);
+  }
+};
+static const GemmTable& gemm_table() { static const GemmTable t; return t; }
+
+constexpr size_t frag_gemm_bytes(int nw) { return (size_t)(nw * 32 * 32 + 4 * 8 * 8) * sizeof(float); }
+
+// the instance of a kind with its tile and launch shape
+static GemmPick gemm_instance(int kind, bool exchange, int amode, int bmode, int ar) {
+  static const struct { int tile_m, tile_n, threads; size_t lds; } shape[GK_KINDS] = {
+      {32, 32, 256, frag_gemm_bytes(4)},
+      {32, 32, 1024, frag_gemm_bytes(16)},
+      {64, 64, 512, lds_gemm_bytes(kLdsBKMax)},
+      {64, 64, 512 + 64 * kRingLoaders, ring_gemm_bytes()},
+      {64, 64, 512 + 64 * kRingLoadersOnePerCu, ring_gemm_bytes()},
+      {128, 64, 512 + 64 * kR2Loaders, ring2_bytes()}};
+  return GemmPick{kind, shape[kind].tile_m, shape[kind].tile_n, shape[kind].threads, shape[kind].lds,
+                  gemm_table().fn[kind][exchange ? 1 : 0][amode][bmode][ar]};
+}
+
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// amode / bmode: 1 = the operand is k-major in memory (P[k ld + i])
-static int g_ring_tile = 2;  // weight-gradient group: 2 = the 128 x 128 tile with the split pass, 3 = the 128 x 128 tile that splits per fragment (lipasr_debug_gemm_mode
-                             // bit 7), 1 = the 64 x 64 ring tile (bit 6)
-static int g_no_ring = 0;  // lipasr_debug_gemm_mode bit 5: arithmetic mode 2 on the register-staged tiles only (A/B knob)
 static bool ring_legal(int amode, int bmode, const GemmArgs& g) {
-  if (g_no_ring || g.bf16 != 2 || g.M < 64 || g.N < 64 || g.K < 32) return false;
+  if (g_knobs.no_ring || g.bf16 != 2 || g.M < 64 || g.N < 64 || g.K < 32) return false;
   if ((g.K & 31) && (!g.zeros || (g.K & 3))) return false;  // a K tail needs the zero source, and whole 16-byte chunks
   if ((g.lda & 3) || (g.ldb & 3) || !aligned16(g.A) || !aligned16(g.B)) return false;
   const int m_real = g.ones_row ? g.M - 1 : g.M;
@@ -1920,30 +1883,112 @@ static bool ring_legal(int amode, int bmode, const GemmArgs& g) {
 // The 128 x 64 exchange tile (gemm_ring2_tile) pays where the 64 x 64 tiling would put two workgroups on (nearly) every CU of the
 // plan's share: then it halves the workgroups and moves 3/4 of the bytes per CU; with fewer tiles than that it would leave CUs idle.
 // One workgroup per CU (124 KB of LDS) and every workgroup resident (the exchange): at most `cus` tiles.
-static int g_ring2 = 1;  // lipasr_debug_gemm_mode bit 8 clears it (A/B knob)
-static int g_ring_x1 = 1;  // bit 9 clears it: no loader-wavefront instance for exchange launches of one workgroup per CU
-static long g_launch_count[2] = {0, 0};  // lipasr_debug_launch_count: 0 = launches on 128 x 64 exchange tiles, 1 = weight-gradient launches with 128 x 128 split-pass tiles
-static bool use_ring2(int bmode, const GemmArgs& g) {
-  if (!g_ring2 || g.bf16 != 2 || g.M < 128 || g.N < 64 || !ring_legal(0, bmode, g)) return false;
-  if (bmode == 0 && g.N < 64) return false;
-  int cus = g.cus;
-  if (cus <= 0) { hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev); cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
+static bool use_ring2(int bmode, const GemmArgs& g, int cus) {
+  if (!g_knobs.ring2 || g.bf16 != 2 || g.M < 128 || g.N < 64 || !ring_legal(0, bmode, g)) return false;
   const long tiles = (long)((g.M + 127) / 128) * ((g.N + 63) / 64);
   return 4 * tiles >= 3 * (long)cus && tiles <= (long)cus && (g.M + 127) / 128 <= g.xc_rt_max;
 }
 
-// arithmetic mode (GemmArgs::bf16: 0 exact fp32, 1 bf16 operands, 2 fp16 two-plane split) -> template instance
-#define LP_DISPATCH_AR(ar, M) \
-  do {                        \
-    if ((ar) == 2) { M(2) }   \
-    else if ((ar) == 1) { M(1) } \
-    else { M(0) }             \
-  } while (0)
+constexpr int kLdsMinTiles = 224;  // measured on MI355X (scratch/time_gemm.py): the LDS kernel wins from ~one tile per CU
 
-// launches up to kMaxGroup weight-gradient style GEMMs (AMODE 1, BMODE 1) as one grid
-static int g_group_lds = 1;  // lipasr_debug_gemm_mode bit 3 clears it: the grouped launch on 32x32 fragment tiles (round 2)
+static bool use_lds_gemm(int M, int N, int K, int min_tiles = 0) {
+  if (g_knobs.gemm_mode == 1) return false;
+  const bool legal = M >= 64 && N >= 64 && K >= 32;
+  if (g_knobs.gemm_mode == 2) return legal;
+  const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
+  return legal && tiles >= (min_tiles > 0 ? min_tiles : kLdsMinTiles);
+}
 
-static int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
+int pick_gemm(int amode, int bmode, const GemmArgs& g, GemmPick* out) {
+  if (g.M <= 0 || g.N <= 0 || g.K <= 0) { set_error("gemm: empty problem %dx%dx%d", g.M, g.N, g.K); return LIPASR_EINVAL; }
+  const bool lds_k = use_lds_gemm(g.M, g.N, g.K, g.lds_min_tiles);
+  const bool exchange = g.epi == EPI_BIAS_RELU_BNX || g.epi == EPI_DH_BNX;
+  int kind;
+  if (g.epi == EPI_BIAS_SOFTMAX_CE) {  // one 32-wide column tile, 4 wavefronts: the epilogue reduces along lanes
+    if (g.N > 32) { set_error("gemm: the fused softmax epilogue needs N <= 32 (got %d)", g.N); return LIPASR_EINVAL; }
+    if (amode != 0 || bmode != 1) { set_error("gemm: the fused softmax epilogue is a forward (NN) epilogue"); return LIPASR_EINVAL; }
+    kind = GK_FRAG4;
+  } else if (exchange) {  // the exchange epilogue: forward (NN) or input-gradient (NT) GEMMs only
+    if (amode != 0) { set_error("gemm: the exchange epilogue needs a row-major A operand"); return LIPASR_EINVAL; }
+    const int cus = g.cus > 0 ? g.cus : device_cus();
+    if (use_ring2(bmode, g, cus)) kind = GK_RING2;  // 128 x 64 tiles, one workgroup per CU of the plan's share
+    else if (lds_k && ring_legal(0, bmode, g))      // at most one workgroup per CU: the instance with loader wavefronts
+      kind = (g_knobs.ring_x1 && (long)((g.N + 63) / 64) * ((g.M + 63) / 64) <= (long)cus) ? GK_RING_X1 : GK_RING;
+    else kind = lds_k ? GK_LDS : GK_FRAG4;
+  } else if (lds_k) {
+    kind = ring_legal(amode, bmode, g) ? GK_RING : GK_LDS;
+  } else {
+    // Few output tiles and a long K (the dW GEMMs of the narrow layers, K = batch): 16 wavefronts split K so that
+    // the serial chain of chunk loads per wavefront stays short.  Not for the *_STATS epilogues (never needed there).
+    const long tiles = (long)((g.N + 31) / 32) * ((g.M + 31) / 32);
+    const bool deep = tiles <= 192 && g.K >= 512 && g.epi != EPI_BIAS_RELU_STATS && g.epi != EPI_DH_STATS;
+    kind = deep ? GK_FRAG16 : GK_FRAG4;
+  }
+  *out = gemm_instance(kind, exchange, amode ? 1 : 0, bmode ? 1 : 0, kind >= GK_RING ? 2 : arith_index(g.bf16));
+  if (!out->fn) { set_error("gemm: no kernel instance for this problem"); return LIPASR_EINVAL; }  // (a hole in the table: a bug)
+  return LIPASR_OK;
+}
+
+int launch_gemm(int amode, int bmode, const GemmArgs& g, hipStream_t st) {
+  GemmPick p;
+  const int rc = pick_gemm(amode, bmode, g, &p);
+  if (rc != LIPASR_OK) return rc;
+  if (p.kind == GK_RING2) ++g_launch_count[0];
+  (void)ensure_dyn_lds(p.fn, p.lds_bytes);
+  void* args[] = {const_cast<GemmArgs*>(&g)};
+  (void)hipLaunchKernel(p.fn, dim3((g.N + p.tile_n - 1) / p.tile_n, (g.M + p.tile_m - 1) / p.tile_m), dim3(p.threads), args, p.lds_bytes, st);
+  LP_LAUNCH_CHECK();
+  return LIPASR_OK;
+}
+
+int gemm_row_tiles(int amode, int bmode, const GemmArgs& g) {
+  GemmPick p;
+  return pick_gemm(amode, bmode, g, &p) == LIPASR_OK ? (g.M + p.tile_m - 1) / p.tile_m : 0;
+}
+
+// The exchange epilogue (EPI_*_BNX) spins until every row tile of its column block has published: every workgroup of the launch
+// must be able to be resident at the same time.  Workgroups per CU = the occupancy query capped by the SGPR admission rule,
+// times the CUs the plan's stream may use.  The row tiles must also fit the granule regions.  Anything else takes the launch
+// chain (GEMM + apply kernel).
+static int blocks_per_cu(const GemmPick& p) {
+  int occ = 0;
+  // the query answers 0 for a dynamic LDS size the kernel has not been allowed yet (launch_gemm raises the limit at a kernel's FIRST
+  // launch -- which, for the exchange instances, only happens once this function has said they fit: in a fresh process the first
+  // mode-2 training step then took the launch chain for every LDS-tiled layer, found by the launch-count test hook)
+  (void)ensure_dyn_lds(p.fn, p.lds_bytes);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, p.fn, p.threads, p.lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  // MI355X_MICROARCH.md (residency): the hardware admits 256-thread blocks up to floor(800 / (ceil(sgpr / 16) 16 + 16)) per CU,
+  // which the query does not know about (it can be one high).  These kernels use 102-106 SGPRs (GemmArgs is a large by-value
+  // argument): 800 / 128 = 6 blocks of four wavefronts = 24 wavefronts per CU.
+  const int by_sgpr = 24 / (p.threads / 64);
+  return std::min(occ, by_sgpr);
+}
+
+// This is DELIBERATELY the conservative bound, kept as it was when the fuse-or-chain decision was measured: it is asked before the
+// launch's GemmArgs exist, so it counts 64 x 64 (or 32 x 32) tiles by pick_gemm's own use_lds_gemm although the 128 x 64 instance
+// would make half as many, and takes the smaller occupancy of the LDS and the 64 x 64 ring instance although pick_gemm may take
+// the loader instances (one workgroup per CU, and only where the tiles are at most the CUs: inside this bound).  A launch this
+// admits is resident whichever instance runs it; tightening it changes which layers fuse and needs measurements of its own.
+bool exchange_fits(int bmode, int arith, int M, int N, int K, int lds_min_tiles, int xc_rt_max, int cus) {
+  const bool lds_k = use_lds_gemm(M, N, K, lds_min_tiles);
+  const int ts = lds_k ? 64 : 32;
+  const long row_tiles = (M + ts - 1) / ts, tiles = row_tiles * ((N + ts - 1) / ts);
+  if (row_tiles > xc_rt_max || row_tiles > 64) return false;
+  // [BMODE][fragment | LDS kernel][arithmetic] and the ring instance [BMODE], filled on first use (one device per process in
+  // practice; the kernels' resource use does not depend on the device)
+  static int per_cu[2][2][3] = {{{-1, -1, -1}, {-1, -1, -1}}, {{-1, -1, -1}, {-1, -1, -1}}}, ring_pc[2] = {-1, -1};
+  const int b = bmode ? 1 : 0, ar = arith_index(arith);
+  int& pc = per_cu[b][lds_k ? 1 : 0][ar];
+  if (pc < 0) pc = blocks_per_cu(gemm_instance(lds_k ? GK_LDS : GK_FRAG4, true, 0, b, ar));
+  int per = pc;
+  if (ar == 2 && lds_k) {  // the launch may take the LDS-DMA ring instance (68 KB of LDS): the smaller of the two answers
+    if (ring_pc[b] < 0) ring_pc[b] = blocks_per_cu(gemm_instance(GK_RING, true, 0, b, 2));
+    per = std::min(per, ring_pc[b]);
+  }
+  return per > 0 && tiles <= (long)per * cus;
+}
+
+int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
   int done = 0;
   while (done < n) {
     GemmGroup grp;
@@ -1952,7 +1997,7 @@ static int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
     long big = 0;
     for (int k = 0; k < kMaxGroup && done + k < n; ++k)
       big += (long)((gs[done + k].N + 63) / 64) * ((gs[done + k].M + 63) / 64);
-    const bool lds_tiles = g_group_lds && big >= 128 && gs[done].K >= 64;
+    const bool lds_tiles = g_knobs.group_lds && big >= 128 && gs[done].K >= 64;
     const int ts = lds_tiles ? 64 : 32;
     const int ar = gs[done].bf16;
     // 128 x 128 tiles (one workgroup per CU, half the operand bytes per flop, two accumulators per wavefront).  A CU takes in ~32 GB/s
@@ -1960,14 +2005,12 @@ static int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
     // tiles per CU = 1 MB as well but four per CU 2 MB.  The reference's model makes 105 + 4 tiles: with the split pass and the loader
     // wavefronts 38-40 us on a 128-CU share (64 x 64 ring tiles: 77) and config 2's step 0.310 against 0.316 ms on all 256 CUs, where
     // they leave 150 CUs idle -- so: whenever the tiles cover 40 % of the CUs the launch may use.
-    int ring_tile = g_ring_tile;
+    int ring_tile = g_knobs.ring_tile;
     if (ring_tile >= 2 && lds_tiles && ar == 2) {
       long n128 = 0;
       for (int q = 0; q < kMaxGroup && done + q < n; ++q)
         if (ring_legal(1, 1, gs[done + q])) n128 += (long)((gs[done + q].N + 127) / 128) * ((gs[done + q].M + 127) / 128);
-      int cus = gs[done].cus;
-      if (cus <= 0) { hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev); cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
-      if (10 * n128 < 4 * (long)cus) ring_tile = 1;
+      if (10 * n128 < 4 * (long)(gs[done].cus > 0 ? gs[done].cus : device_cus())) ring_tile = 1;
     }
     int k = 0, tiles = 0;
     bool any_ring = false;
@@ -1975,7 +2018,7 @@ static int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
       const GemmArgs& g = gs[done + k];
       if (g.M <= 0 || g.N <= 0 || g.K <= 0) { set_error("grouped gemm: empty problem"); return LIPASR_EINVAL; }
       grp.g[k] = g;
-      // arithmetic mode 2: the 128 x 128 two-accumulator ring tile for every problem it can take (g_ring_tile 1: the 64 x 64 ring tile)
+      // arithmetic mode 2: the 128 x 128 two-accumulator ring tile for every problem it can take (ring_tile 1: the 64 x 64 ring tile)
       if (lds_tiles && ar == 2 && ring_legal(1, 1, g)) { grp.g[k].ring = ring_tile; any_ring = true; }
       const int tp = grp.g[k].ring >= 2 ? 128 : ts;
       grp.tile_start[k] = tiles;
@@ -1983,640 +2026,58 @@ static int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
     }
     grp.n = k;
     grp.tile_start[k] = tiles;
+    const GemmTable& t = gemm_table();
+    const void* fn = lds_tiles ? t.grouped_lds[arith_index(ar)] : t.grouped_frag[arith_index(ar)];
+    int threads = lds_tiles ? 512 : 256;
+    size_t lds = lds_tiles ? lds_gemm_bytes(kLdsBKMax) : frag_gemm_bytes(4);
     if (any_ring) {
-      // dynamic LDS the kernel may ask for, set once per device: 160 KB (the split-pass tile: the whole CU) where the device grants it
-      static int attr_dev_max[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); int& attr_max = attr_dev_max[attr_dev & 15];
-      if (!attr_max) {
-        const void* fn = reinterpret_cast<const void*>(gemm_ring_grouped_kernel);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring128s_bytes()) == hipSuccess) attr_max = (int)ring128s_bytes();
-        else {
-          (void)hipGetLastError();
-          (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(ring_gemm_bytes(), ring128_bytes()));
-          attr_max = (int)std::max(ring_gemm_bytes(), ring128_bytes());
-        }
-      }
-      if (ring_tile == 2 && (size_t)attr_max < ring128s_bytes()) {  // (never seen on gfx950)
+      fn = t.grouped_ring;
+      // 160 KB of dynamic LDS (the split-pass tile: the whole CU) where the device grants it, else the tile that splits per fragment
+      if (ring_tile == 2 && !ensure_dyn_lds(fn, ring128s_bytes())) {  // (never seen on gfx950)
         ring_tile = 3;
         for (int q = 0; q < k; ++q) if (grp.g[q].ring == 2) grp.g[q].ring = 3;
       }
-      const size_t lds_r = std::max(ring_gemm_bytes(), ring_tile == 2 ? ring128s_bytes() : ring_tile == 3 ? ring128_bytes() : (size_t)0);
+      lds = std::max(ring_gemm_bytes(), ring_tile == 2 ? ring128s_bytes() : ring_tile == 3 ? ring128_bytes() : (size_t)0);
+      threads = ring_tile == 2 ? 512 + 64 * kR128Loaders : 512;  // (loader wavefronts: the split-pass tile only)
       if (ring_tile == 2) ++g_launch_count[1];
-      hipLaunchKernelGGL(gemm_ring_grouped_kernel, dim3(tiles), dim3(ring_tile == 2 ? 512 + 64 * kR128Loaders : 512), lds_r, st, grp);  // (loader wavefronts: the split-pass tile only)
-    } else if (lds_tiles) {
-      constexpr size_t lds_b = lds_gemm_bytes(kLdsBKMax);
-      static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];  /* per device */
-      if (!attr_set) {
-#define LP_M(AR) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_lds_grouped_kernel<1, 1, AR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        LP_M(0) LP_M(1) LP_M(2)
-#undef LP_M
-        attr_set = true;
-      }
-#define LP_M(AR) hipLaunchKernelGGL((gemm_lds_grouped_kernel<1, 1, AR>), dim3(tiles), dim3(512), lds_b, st, grp);
-      LP_DISPATCH_AR(ar, LP_M);
-#undef LP_M
-    } else {
-      const size_t lds = (size_t)(4 * 32 * 32 + 4 * 8 * 8) * sizeof(float);
-#define LP_M(AR) hipLaunchKernelGGL((gemm_f32_grouped_kernel<1, 1, 4, AR>), dim3(tiles), dim3(256), lds, st, grp);
-      LP_DISPATCH_AR(ar, LP_M);
-#undef LP_M
     }
+    (void)ensure_dyn_lds(fn, lds);
+    void* args[] = {&grp};
+    (void)hipLaunchKernel(fn, dim3(tiles), dim3(threads), args, lds, st);
     LP_LAUNCH_CHECK();
     done += k;
   }
   return LIPASR_OK;
 }
 
-static int g_xcd_map = 0;    // lipasr_debug_gemm_mode bit 4 SETS it (round 5: measured, not kept): the XCD-aware blockIdx -> tile map of xcd_tile().
-                             // Same box, interleaved: config 2 0.3177 with it against 0.3148 without, config 3 0.3653 against 0.3625; the counters
-                             // (TCC hit 67 % on the weight-gradient launch either way) say the operand panels are not what misses.
-static int g_gemm_mode = 0;  // 0 auto, 1 split-K kernel only, 2 LDS kernel wherever it is legal (profiling knob)
-static int g_split_dw0 = 0;  // lipasr_debug_gemm_mode bit 2: the first layer's weight gradient as its own launch
-
-constexpr int kLdsMinTiles = 224;  // measured on MI355X (scratch/time_gemm.py): the LDS kernel wins from ~one tile per CU
-
-static bool use_lds_gemm(int M, int N, int K, int min_tiles = 0) {
-  if (g_gemm_mode == 1) return false;
-  const bool legal = M >= 64 && N >= 64 && K >= 32;
-  if (g_gemm_mode == 2) return legal;
-  const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-  return legal && tiles >= (min_tiles > 0 ? min_tiles : kLdsMinTiles);
-}
-
-template <int AMODE, int BMODE, int NW, int BF>
-static void launch_gemm_tb(const GemmArgs& g, hipStream_t st) {
-  const dim3 grid((g.N + 31) / 32, (g.M + 31) / 32);
-  const size_t lds = (size_t)(NW * 32 * 32 + 4 * 8 * 8) * sizeof(float);
-  static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];  /* per device */
-  if (lds > 48 * 1024 && !attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<AMODE, BMODE, NW, BF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm_f32_kernel<AMODE, BMODE, NW, BF>), grid, dim3(64 * NW), lds, st, g);
-}
-
-template <int AMODE, int BMODE, int NW>
-static void launch_gemm_t(const GemmArgs& g, hipStream_t st) {
-#define LP_M(AR) launch_gemm_tb<AMODE, BMODE, NW, AR>(g, st);
-  LP_DISPATCH_AR(g.bf16, LP_M);
-#undef LP_M
-}
-
-static int launch_gemm(int amode, int bmode, const GemmArgs& g, hipStream_t st) {
-  if (g.M <= 0 || g.N <= 0 || g.K <= 0) {
-    set_error("gemm: empty problem %dx%dx%d", g.M, g.N, g.K);
-    return LIPASR_EINVAL;
-  }
-  // Few output tiles and a long K (the dW GEMMs of the narrow layers, K = batch): 16 wavefronts split K so that
-  // the serial chain of chunk loads per wavefront stays short.  Not for the *_STATS epilogues (never needed there).
-  if (g.epi == EPI_BIAS_SOFTMAX_CE) {  // one 32-wide column tile, 4 wavefronts: the epilogue reduces along lanes
-    if (g.N > 32) { set_error("gemm: the fused softmax epilogue needs N <= 32 (got %d)", g.N); return LIPASR_EINVAL; }
-    if (amode == 0 && bmode == 1) launch_gemm_t<0, 1, 4>(g, st);
-    else { set_error("gemm: the fused softmax epilogue is a forward (NN) epilogue"); return LIPASR_EINVAL; }
-    LP_LAUNCH_CHECK();
-    return LIPASR_OK;
-  }
-  if (g.epi == EPI_BIAS_RELU_BNX || g.epi == EPI_DH_BNX) {  // the exchange epilogue: forward (NN) or input-gradient (NT) GEMMs only
-    if (amode != 0) { set_error("gemm: the exchange epilogue needs a row-major A operand"); return LIPASR_EINVAL; }
-    if (use_ring2(bmode, g)) {  // 128 x 64 tiles, one workgroup per CU of the plan's share
-      ++g_launch_count[0];
-      const dim3 grid((g.N + 63) / 64, (g.M + 127) / 128);
-      static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring2_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring2_bytes());
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring2_bytes());
-        attr_set = true;
-      }
-      if (bmode == 0) hipLaunchKernelGGL((gemm_ring2_kernel<0>), grid, dim3(512 + 64 * kR2Loaders), ring2_bytes(), st, g);
-      else hipLaunchKernelGGL((gemm_ring2_kernel<1>), grid, dim3(512 + 64 * kR2Loaders), ring2_bytes(), st, g);
-    } else if (use_lds_gemm(g.M, g.N, g.K, g.lds_min_tiles) && ring_legal(0, bmode, g)) {
-      const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);
-      static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_kernel<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_gemm_bytes());
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_kernel<0, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_gemm_bytes());
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_x1_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_gemm_bytes());
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_x1_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_gemm_bytes());
-        attr_set = true;
-      }
-      int cus = g.cus;
-      if (cus <= 0) { hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev); cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
-      if (g_ring_x1 && (long)grid.x * grid.y <= (long)cus) {  // at most one workgroup per CU: the instance with loader wavefronts
-        if (bmode == 0) hipLaunchKernelGGL((gemm_ring_x1_kernel<0>), grid, dim3(512 + 64 * kRingLoadersOnePerCu), ring_gemm_bytes(), st, g);
-        else hipLaunchKernelGGL((gemm_ring_x1_kernel<1>), grid, dim3(512 + 64 * kRingLoadersOnePerCu), ring_gemm_bytes(), st, g);
-      } else if (bmode == 0) hipLaunchKernelGGL((gemm_ring_kernel<0, 0, true>), grid, dim3(512 + 64 * kRingLoaders), ring_gemm_bytes(), st, g);
-      else hipLaunchKernelGGL((gemm_ring_kernel<0, 1, true>), grid, dim3(512 + 64 * kRingLoaders), ring_gemm_bytes(), st, g);
-    } else if (use_lds_gemm(g.M, g.N, g.K, g.lds_min_tiles)) {
-      const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);
-      constexpr size_t lds_b = lds_gemm_bytes(kLdsBKMax);
-      static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];
-      if (!attr_set) {
-#define LP_M(AR)                                                                                                                                   \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_lds_kernel<0, 0, AR, kLdsBKMax, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b); \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_lds_kernel<0, 1, AR, kLdsBKMax, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        LP_M(0) LP_M(1) LP_M(2)
-#undef LP_M
-        attr_set = true;
-      }
-      if (bmode == 0) {
-#define LP_M(AR) hipLaunchKernelGGL((gemm_lds_kernel<0, 0, AR, kLdsBKMax, true>), grid, dim3(512), lds_b, st, g);
-        LP_DISPATCH_AR(g.bf16, LP_M);
-#undef LP_M
-      } else {
-#define LP_M(AR) hipLaunchKernelGGL((gemm_lds_kernel<0, 1, AR, kLdsBKMax, true>), grid, dim3(512), lds_b, st, g);
-        LP_DISPATCH_AR(g.bf16, LP_M);
-#undef LP_M
-      }
-    } else {
-      const dim3 grid((g.N + 31) / 32, (g.M + 31) / 32);
-      const size_t lds = (size_t)(4 * 32 * 32 + 4 * 8 * 8) * sizeof(float);
-      if (bmode == 0) {
-#define LP_M(AR) hipLaunchKernelGGL((gemm_f32_kernel<0, 0, 4, AR, true>), grid, dim3(256), lds, st, g);
-        LP_DISPATCH_AR(g.bf16, LP_M);
-#undef LP_M
-      } else {
-#define LP_M(AR) hipLaunchKernelGGL((gemm_f32_kernel<0, 1, 4, AR, true>), grid, dim3(256), lds, st, g);
-        LP_DISPATCH_AR(g.bf16, LP_M);
-#undef LP_M
-      }
-    }
-    LP_LAUNCH_CHECK();
-    return LIPASR_OK;
-  }
-  if (use_lds_gemm(g.M, g.N, g.K, g.lds_min_tiles) && ring_legal(amode, bmode, g)) {
-    const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);
-#define LP_RING(A_, B_)                                                                                                                 \
-  {                                                                                                                                     \
-    static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];   \
-    if (!attr_set) {                                                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_kernel<A_, B_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_gemm_bytes()); \
-      attr_set = true;                                                                                                                  \
-    }                                                                                                                                   \
-    hipLaunchKernelGGL((gemm_ring_kernel<A_, B_>), grid, dim3(512 + 64 * kRingLoaders), ring_gemm_bytes(), st, g);                                          \
-  }
-    if (amode == 0 && bmode == 0) LP_RING(0, 0) else if (amode == 0 && bmode == 1) LP_RING(0, 1)
-    else if (amode == 1 && bmode == 0) LP_RING(1, 0) else LP_RING(1, 1)
-#undef LP_RING
-    LP_LAUNCH_CHECK();
-    return LIPASR_OK;
-  }
-  if (use_lds_gemm(g.M, g.N, g.K, g.lds_min_tiles)) {
-    const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);
-    constexpr size_t lds_b = lds_gemm_bytes(kLdsBKMax);
-#define LP_LDS(A_, B_)                                                                                                                  \
-  {                                                                                                                                     \
-    static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];   \
-    if (!attr_set) {                                                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_lds_kernel<A_, B_, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b); \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_lds_kernel<A_, B_, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b); \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_lds_kernel<A_, B_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b); \
-      attr_set = true;                                                                                                                  \
-    }                                                                                                                                   \
-    if (g.bf16 == 2) hipLaunchKernelGGL((gemm_lds_kernel<A_, B_, 2>), grid, dim3(512), lds_b, st, g);                                   \
-    else if (g.bf16 == 1) hipLaunchKernelGGL((gemm_lds_kernel<A_, B_, 1>), grid, dim3(512), lds_b, st, g);                              \
-    else hipLaunchKernelGGL((gemm_lds_kernel<A_, B_, 0>), grid, dim3(512), lds_b, st, g);                                               \
-  }
-    if (amode == 0 && bmode == 0) LP_LDS(0, 0) else if (amode == 0 && bmode == 1) LP_LDS(0, 1)
-    else if (amode == 1 && bmode == 0) LP_LDS(1, 0) else LP_LDS(1, 1)
-#undef LP_LDS
-    LP_LAUNCH_CHECK();
-    return LIPASR_OK;
-  }
-  const long tiles = (long)((g.N + 31) / 32) * ((g.M + 31) / 32);
-  const bool deep = tiles <= 192 && g.K >= 512 && g.epi != EPI_BIAS_RELU_STATS && g.epi != EPI_DH_STATS && g.epi != EPI_BIAS_RELU_BNX &&
-                    g.epi != EPI_DH_BNX;
-  if (deep) {
-    if (amode == 0 && bmode == 0) launch_gemm_t<0, 0, 16>(g, st);
-    else if (amode == 0 && bmode == 1) launch_gemm_t<0, 1, 16>(g, st);
-    else if (amode == 1 && bmode == 0) launch_gemm_t<1, 0, 16>(g, st);
-    else launch_gemm_t<1, 1, 16>(g, st);
-  } else {
-    if (amode == 0 && bmode == 0) launch_gemm_t<0, 0, 4>(g, st);
-    else if (amode == 0 && bmode == 1) launch_gemm_t<0, 1, 4>(g, st);
-    else if (amode == 1 && bmode == 0) launch_gemm_t<1, 0, 4>(g, st);
-    else launch_gemm_t<1, 1, 4>(g, st);
-  }
-  LP_LAUNCH_CHECK();
-  return LIPASR_OK;
-}
-
-// row tiles of the *_STATS epilogues: must follow the kernel choice of launch_gemm for the same (M, N, K)
-static int stats_row_tiles(int M, int N, int K, int min_tiles) { return use_lds_gemm(M, N, K, min_tiles) ? (M + 63) / 64 : (M + 31) / 32; }
-
-// The exchange epilogue (EPI_*_BNX) spins until every row tile of its column block has published: every workgroup of the launch
-// must be able to be resident at the same time.  Workgroups per CU = the occupancy query capped by the SGPR admission rule
-// (blocks_per_cu), times the CUs the plan's stream may use.  The row tiles must also fit the
-// granule regions.  Anything else takes the launch chain (GEMM + apply kernel).
-template <typename K>
-static int blocks_per_cu(K kernel, int threads, size_t lds) {
-  int occ = 0;
-  // the query answers 0 for a dynamic LDS size the kernel has not been allowed yet (the launchers raise the limit at a kernel's FIRST
-  // launch -- which, for the exchange instances, only happens once this function has said they fit: in a fresh process the first
-  // mode-2 training step then took the launch chain for every LDS-tiled layer, found by the launch-count test hook)
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  // MI355X_MICROARCH.md (residency): the hardware admits 256-thread blocks up to floor(800 / (ceil(sgpr / 16) 16 + 16)) per CU,
-  // which the query does not know about (it can be one high).  These kernels use 102-106 SGPRs (GemmArgs is a large by-value
-  // argument): 800 / 128 = 6 blocks of four wavefronts = 24 wavefronts per CU.
-  const int by_sgpr = 24 / (threads / 64);
-  return std::min(occ, by_sgpr);
-}
-
-static bool bnx_fits(const lipasr_mlp* m, bool forward, int M, int N, int K) {
-  if (!m->fuse_bn || !m->xc_gran) return false;
-  const bool lds_k = use_lds_gemm(M, N, K, m->lds_min_tiles);
-  const int ts = lds_k ? 64 : 32;
-  const long row_tiles = (M + ts - 1) / ts, tiles = row_tiles * ((N + ts - 1) / ts);
-  if (row_tiles > m->xc_rt_max || row_tiles > 64) return false;
-  // [forward | backward][fragment | LDS kernel][fp32 | bf16 operands], filled on first use (one device per process in practice;
-  // the kernels' resource use does not depend on the device)
-  static int per_cu[2][2][3] = {{{-1, -1, -1}, {-1, -1, -1}}, {{-1, -1, -1}, {-1, -1, -1}}};
-  const int ar = m->compute_bf16;
-  int& pc = per_cu[forward ? 0 : 1][lds_k ? 1 : 0][ar];
-  if (pc < 0) {
-    const size_t lds_f = (size_t)(4 * 32 * 32 + 4 * 8 * 8) * sizeof(float);
-#define LP_M(AR)                                                                                                              \
-  if (forward) pc = lds_k ? blocks_per_cu(gemm_lds_kernel<0, 1, AR, kLdsBKMax, true>, 512, lds_gemm_bytes(kLdsBKMax))       \
-                          : blocks_per_cu(gemm_f32_kernel<0, 1, 4, AR, true>, 256, lds_f);                                   \
-  else pc = lds_k ? blocks_per_cu(gemm_lds_kernel<0, 0, AR, kLdsBKMax, true>, 512, lds_gemm_bytes(kLdsBKMax))               \
-                  : blocks_per_cu(gemm_f32_kernel<0, 0, 4, AR, true>, 256, lds_f);
-    LP_DISPATCH_AR(ar, LP_M);
-#undef LP_M
-  }
-  int per = pc;
-  if (ar == 2 && lds_k) {  // the launch may take the LDS-DMA ring instance (68 KB of LDS): the smaller of the two answers
-    static int ring_pc[2] = {-1, -1};
-    int& rp = ring_pc[forward ? 0 : 1];
-    if (rp < 0) rp = forward ? blocks_per_cu(gemm_ring_kernel<0, 1, true>, 512 + 64 * kRingLoaders, ring_gemm_bytes()) : blocks_per_cu(gemm_ring_kernel<0, 0, true>, 512 + 64 * kRingLoaders, ring_gemm_bytes());
-    per = std::min(per, rp);
-  }
-  const int cus = m->cu_budget > 0 ? std::min(m->cu_budget, m->n_cus) : m->n_cus;
-  return per > 0 && tiles <= (long)per * cus;
-}
-
-static GemmArgs gemm_args(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
-                          int epi) {
+GemmArgs gemm_args(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, int epi) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.epi = epi;
-  g.xcd_map = g_xcd_map;
+  g.xcd_map = g_knobs.xcd_map;
   g.sa = g.sb = 1.0f;
   return g;
-}
-
-// arithmetic mode of a plan's GEMM + the fp16 range scales of mode 2 by operand kind.  Powers of two (exact): activations and
-// features unscaled (|x| < 65504; BatchNorm outputs are O(1): their low plane is a normal fp16 number down to |x| = 0.12 and loses
-// bits gradually below, on values that weigh little in a sum), kernels x 2^12 (|w| < 16), gradients x 2^8 / 2^floor(log2 g0) where g0 is the
-// size of the gradient at the network's output (the loss gradient is <= 1 / batch: a batch of 1024 gives 2^18, and room for the
-// gradient to grow 256-fold on its way down).  A value outside its range becomes inf in the fp16 conversion and the loss NaN --
-// loud, not silently wrong.  The low plane keeps its full 11 bits while |x| scale >= 2^-3 and degrades gradually below (fp16
-// subnormals): with the first gradient scale tried, a fixed 2^14, the bias gradients of a 1024-row batch (sums of 1024 terms of
-// 1e-6 that cancel to 5e-7) came out 9e-5 off; scaled by the batch they are inside the exact mode's 5e-5.
-enum OperandKind { OP_ACT = 0, OP_WEIGHT = 1, OP_GRAD = 2 };
-static float grad_scale_for(float g0) {  // g0: bound of the gradient at the logits (inv_batch, or 1 for a caller-given upstream vector)
-  int e = 0;
-  (void)frexpf(g0 > 0.0f ? g0 : 1.0f, &e);  // g0 = f 2^e, f in [0.5, 1)
-  return ldexpf(1.0f, 8 - e);               // 2^8 / 2^e >= 2^8 / (2 g0)
-}
-static void set_arith(GemmArgs& g, const lipasr_mlp* m, int kind_a, int kind_b, float g0 = 1.0f, bool training = true) {
-  // Mode 2 is a TRAINING arithmetic: there the activations are BatchNorm outputs (bounded by construction) and the gradients carry
-  // their own measured scale.  Inference-mode activations have no such bound (BatchNorm with moving statistics that have not
-  // adapted yet passes 1e4-sized values: the fp16 conversion overflowed in the first suite run) -- predict / attacks / class
-  // gradients stay on the exact fp32 chains, so every logit-parity statement is about exact fp32 whatever the training mode.
-  g.bf16 = (m->compute_bf16 == 2 && !training) ? 0 : m->compute_bf16;
-  g.zeros = reinterpret_cast<const float*>(m->xc_ctrl + 4);  // words 4 .. 7 of the control block: never written
-  g.cus = m->cu_budget > 0 ? std::min(m->cu_budget, m->n_cus) : m->n_cus;
-  const float sc[3] = {1.0f, 4096.0f, grad_scale_for(g0)};
-  g.sa = sc[kind_a];
-  g.sb = sc[kind_b];
-}
-
-// ---------------------------------------------------------------------------------------------
-// BatchNorm / dropout apply kernels.  The column statistics arrive as per-row-tile partial sums from
-// the producing GEMM's epilogue, so these are plain 2-D elementwise kernels: grid = (column strips of
-// 128, row chunks of 32), 256 threads = 32 float4 column lanes x 8 row lanes, each workgroup re-sums
-// the (few) partials of its columns in fp64 in its prologue.  No cross-workgroup step, fixed order.
-// ---------------------------------------------------------------------------------------------
-constexpr int kApplyRows = 32;
-
-struct ColLane {
-  int j;      // first of this lane's 4 columns
-  bool vec;   // float4 access is legal
-  int N;
-};
-
-__device__ __forceinline__ void ld4(const float* __restrict__ p, size_t row_off, const ColLane& c, float (&v)[4]) {
-  if (c.vec) {
-    const float4 t = *reinterpret_cast<const float4*>(p + row_off + c.j);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (c.j + e < c.N) ? p[row_off + c.j + e] : 0.0f;
-  }
-}
-__device__ __forceinline__ void st4(float* __restrict__ p, size_t row_off, const ColLane& c, const float (&v)[4]) {
-  if (c.vec) {
-    *reinterpret_cast<float4*>(p + row_off + c.j) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (c.j + e < c.N) p[row_off + c.j + e] = v[e];
-  }
-}
-
-// sums the two statistic planes of `part` over the row tiles for this lane's 4 columns (fp64, fixed order)
-__device__ __forceinline__ void sum_partials(const float* __restrict__ part, int n_tiles, const ColLane& c, int rl,
-                                             double (*lds)[32][8], int cl, double (&s1)[4], double (&s2)[4]) {
-  double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int t = rl; t < n_tiles; t += 8) {
-    float v1[4], v2[4];
-    ld4(part, (size_t)t * c.N, c, v1);
-    ld4(part, ((size_t)n_tiles + t) * c.N, c, v2);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { a[e] += (double)v1[e]; a[4 + e] += (double)v2[e]; }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) lds[rl][cl][e] = a[e];
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { t1 += lds[k][cl][e]; t2 += lds[k][cl][4 + e]; }
-    s1[e] = t1;
-    s2[e] = t2;
-  }
-}
-
-// Synchronized BatchNorm: the row-tile partial sums [2][n_tiles][N] of this rank are reduced to [2][N] IN PLACE before the
-// exchange (fp64 accumulation in tile order, one thread per column: it reads all of its 2 n_tiles inputs before it writes the
-// two slots, which are inputs of that thread only), so the collective's length is 2 N whatever the rank's row count and tile
-// size -- ranks with different shard sizes exchange the same number of floats -- and the apply kernels read
-// n_tiles = 1.
-__global__ __launch_bounds__(256) void part_reduce_kernel(float* __restrict__ part, int n_tiles, int N) {
-  const int col = blockIdx.x * 256 + threadIdx.x;
-  if (col >= N) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int t = 0; t < n_tiles; ++t) {
-    s1 += (double)part[(size_t)t * N + col];
-    s2 += (double)part[((size_t)n_tiles + t) * N + col];
-  }
-  part[col] = (float)s1;
-  part[(size_t)N + col] = (float)s2;
-}
-
-struct BnFwdArgs {
-  const float* a;  // [B][N] post-ReLU
-  float* h;        // [B][N] out
-  int B, N, has_bn, n_tiles;
-  int Bstat;          // rows the statistics are taken over (= B; synchronized BatchNorm: the global batch)
-  const float* part;  // [2][n_tiles][N]: sums of a and a^2 per row tile
-  const float* gamma;
-  const float* beta;
-  float* mmean;
-  float* mvar;
-  float* save_mean;  // [N], rstd at save_mean + N
-  DropArgs drop;
-};
-
-// training-mode BatchNorm (batch mean, population variance) + inverted dropout
-__global__ __launch_bounds__(256) void bn_apply_fwd_kernel(BnFwdArgs p) {
-  __shared__ double lds[8][32][8];
-  const int tid = threadIdx.x, cl = tid & 31, rl = tid >> 5;
-  ColLane c;
-  c.j = blockIdx.x * 128 + 4 * cl;
-  c.N = p.N;
-  c.vec = ((p.N & 3) == 0) && (c.j + 3 < p.N);
-  const bool live = c.j < p.N;
-  const int step = p.drop.step_dev ? *p.drop.step_dev : 0;
-  float mean[4] = {0, 0, 0, 0}, rstd[4] = {1, 1, 1, 1}, ga[4] = {1, 1, 1, 1}, be[4] = {0, 0, 0, 0};
-  // this thread's activations start their trip before the statistics are reduced (one memory round trip less)
-  float xin[kApplyRows / 8][4];
-#pragma unroll
-  for (int i = 0; i < kApplyRows / 8; ++i) {
-    const int b = blockIdx.y * kApplyRows + rl + 8 * i;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) xin[i][e] = 0.0f;
-    if (live && b < p.B) ld4(p.a, (size_t)b * p.N, c, xin[i]);
-  }
-  if (p.has_bn) {
-    double s1[4], s2[4];
-    ColLane cc = c;
-    if (!live) { cc.j = 0; cc.vec = false; cc.N = 0; }
-    sum_partials(p.part, p.n_tiles, cc, rl, lds, cl, s1, s2);
-    if (live) {
-      float var[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double m = s1[e] / (double)p.Bstat;
-        double v = s2[e] / (double)p.Bstat - m * m;
-        v = v > 0.0 ? v : 0.0;
-        mean[e] = (float)m;
-        var[e] = (float)v;
-        rstd[e] = (float)(1.0 / sqrt(v + (double)kBnEps));
-      }
-      ld4(p.gamma, 0, c, ga);
-      ld4(p.beta, 0, c, be);
-      if (blockIdx.y == 0 && rl == 0) {
-        float mm[4], mv[4];
-        ld4(p.mmean, 0, c, mm);
-        ld4(p.mvar, 0, c, mv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          mm[e] = mm[e] * kBnMomentum + mean[e] * (1.0f - kBnMomentum);
-          mv[e] = mv[e] * kBnMomentum + var[e] * (1.0f - kBnMomentum);
-        }
-        st4(p.mmean, 0, c, mm);
-        st4(p.mvar, 0, c, mv);
-        st4(p.save_mean, 0, c, mean);
-        st4(p.save_mean, (size_t)p.N, c, rstd);
-      }
-    }
-  }
-  if (!live) return;
-#pragma unroll
-  for (int i = 0; i < kApplyRows / 8; ++i) {
-    const int b = blockIdx.y * kApplyRows + rl + 8 * i;
-    if (b >= p.B) break;
-    const size_t ro = (size_t)b * p.N;
-    float x[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = xin[i][e];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (p.has_bn) x[e] = (x[e] - mean[e]) * rstd[e] * ga[e] + be[e];
-      x[e] *= dropout_mult(p.drop, step, ro + c.j + e);
-    }
-    st4(p.h, ro, c, x);
-  }
-}
-
-struct BnBwdArgs {
-  const float* g;   // [B][N] dh * dropout (from the producing GEMM's epilogue)
-  const float* a;   // [B][N] post-ReLU
-  float* dz;        // [B][N] gradient w.r.t. the pre-activation
-  int B, N, n_tiles;
-  int Bstat;          // rows the statistics were taken over (= B; synchronized BatchNorm: the global batch)
-  float grad_scale;   // 1, or 1 / world when the partial sums were all-reduced (the gradient all-reduce sums them again)
-  const float* part;  // [2][n_tiles][N]: sums of g and g * xhat per row tile
-  const float* gamma;
-  const float* save_mean;
-  float* dgamma;
-  float* dbeta;
-  unsigned* amax_out;  // arithmetic mode 2: max |dz| is folded into this word (see GemmArgs::amax_out); may be null
-};
-
-// backward of BatchNorm(train) -> ReLU given the column sums; also writes dgamma / dbeta
-__global__ __launch_bounds__(256) void bn_apply_bwd_kernel(BnBwdArgs p) {
-  __shared__ double lds[8][32][8];
-  const int tid = threadIdx.x, cl = tid & 31, rl = tid >> 5;
-  ColLane c;
-  c.j = blockIdx.x * 128 + 4 * cl;
-  c.N = p.N;
-  c.vec = ((p.N & 3) == 0) && (c.j + 3 < p.N);
-  const bool live = c.j < p.N;
-  float gin[kApplyRows / 8][4], ain[kApplyRows / 8][4];
-#pragma unroll
-  for (int i = 0; i < kApplyRows / 8; ++i) {
-    const int b = blockIdx.y * kApplyRows + rl + 8 * i;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gin[i][e] = 0.0f; ain[i][e] = 0.0f; }
-    if (live && b < p.B) {
-      ld4(p.g, (size_t)b * p.N, c, gin[i]);
-      ld4(p.a, (size_t)b * p.N, c, ain[i]);
-    }
-  }
-  double s1[4], s2[4];
-  ColLane cc = c;
-  if (!live) { cc.j = 0; cc.vec = false; cc.N = 0; }
-  sum_partials(p.part, p.n_tiles, cc, rl, lds, cl, s1, s2);
-  float omax = 0.0f;
-  if (live) {
-  float mean[4], rstd[4], ga[4], dbt[4], dg[4];
-  ld4(p.save_mean, 0, c, mean);
-  ld4(p.save_mean, (size_t)p.N, c, rstd);
-  ld4(p.gamma, 0, c, ga);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { dbt[e] = (float)s1[e]; dg[e] = (float)s2[e]; }
-  if (blockIdx.y == 0 && rl == 0) {
-    float ob[4], og[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { ob[e] = dbt[e] * p.grad_scale; og[e] = dg[e] * p.grad_scale; }
-    st4(p.dbeta, 0, c, ob);
-    st4(p.dgamma, 0, c, og);
-  }
-  const float invB = 1.0f / (float)p.Bstat;
-#pragma unroll
-  for (int i = 0; i < kApplyRows / 8; ++i) {
-    const int b = blockIdx.y * kApplyRows + rl + 8 * i;
-    if (b >= p.B) break;
-    const size_t ro = (size_t)b * p.N;
-    float gv[4], av[4], o[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gv[e] = gin[i][e]; av[e] = ain[i][e]; }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float xh = (av[e] - mean[e]) * rstd[e];
-      const float d = ga[e] * rstd[e] * (gv[e] - dbt[e] * invB - xh * dg[e] * invB);
-      o[e] = av[e] > 0.0f ? d : 0.0f;
-      if (c.j + e < c.N) omax = fmaxf(omax, fabsf(o[e]));
-    }
-    st4(p.dz, ro, c, o);
-  }
-  }
-  if (p.amax_out) amax_publish(p.amax_out, omax);
-}
-
-// upstream vector at the network output -> dz at the logits, one thread per row (class_gradient and the
-// optimisation-based attacks): on_logits: dz = v;  else out = softmax(z): dz = p * (v - sum_c p_c v_c)
-__global__ __launch_bounds__(256) void softmax_vjp_kernel(const float* __restrict__ z, const float* __restrict__ v, int B,
-                                                           int C, int on_logits, float* __restrict__ prob,
-                                                           float* __restrict__ dz) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  const float* zr = z + (size_t)b * C;
-  const float* vr = v + (size_t)b * C;
-  float mx = zr[0];
-  for (int c = 1; c < C; ++c) mx = fmaxf(mx, zr[c]);
-  float se = 0.0f;
-  for (int c = 0; c < C; ++c) se += expf(zr[c] - mx);
-  const float inv = 1.0f / se;
-  float dot = 0.0f;
-  for (int c = 0; c < C; ++c) dot = fmaf(expf(zr[c] - mx) * inv, vr[c], dot);
-  for (int c = 0; c < C; ++c) {
-    const float pc = expf(zr[c] - mx) * inv;
-    if (prob) prob[(size_t)b * C + c] = pc;
-    dz[(size_t)b * C + c] = on_logits ? vr[c] : pc * (vr[c] - dot);
-  }
-}
-
-// softmax + categorical cross-entropy from logits, one thread per row.
-//   prob (optional), dz = (p - y) * inv_batch (optional), loss_rows = -sum y log_softmax(z) (optional),
-//   correct_rows = [argmax p == argmax y] (optional), onehot_out = one-hot argmax z (optional)
-__global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ z, const float* __restrict__ y, int B,
-                                                          int C, float inv_batch, float* __restrict__ prob,
-                                                          float* __restrict__ dz, float* __restrict__ loss_rows,
-                                                          float* __restrict__ correct_rows,
-                                                          float* __restrict__ onehot_out) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  const float* zr = z + (size_t)b * C;
-  float mx = zr[0];
-  int am = 0;
-  for (int c = 1; c < C; ++c)
-    if (zr[c] > mx) { mx = zr[c]; am = c; }
-  float se = 0.0f;
-  for (int c = 0; c < C; ++c) se += expf(zr[c] - mx);
-  const float lse = logf(se);
-  const float inv = 1.0f / se;
-  float loss = 0.0f, ymax = -INFINITY;
-  int ay = 0;
-  for (int c = 0; c < C; ++c) {
-    const float zs = zr[c] - mx;
-    const float pc = expf(zs) * inv;
-    if (prob) prob[(size_t)b * C + c] = pc;
-    if (y) {
-      const float yc = y[(size_t)b * C + c];
-      if (yc != 0.0f) loss -= yc * (zs - lse);
-      if (yc > ymax) { ymax = yc; ay = c; }
-      if (dz) dz[(size_t)b * C + c] = (pc - yc) * inv_batch;
-    }
-    if (onehot_out) onehot_out[(size_t)b * C + c] = (c == am) ? 1.0f : 0.0f;
-  }
-  if (loss_rows) loss_rows[b] = loss;
-  if (correct_rows) correct_rows[b] = (am == ay) ? 1.0f : 0.0f;
-}
-
-static inline size_t align4(size_t x) { return (x + 3) & ~size_t(3); }
-
-void mlp_plan_free(lipasr_mlp* m) {
-  if (!m) return;
-  if (m->ws) (void)hipFree(m->ws);
-  if (m->xc_gran) (void)hipFree(m->xc_gran);
-  if (m->xc_ctrl) (void)hipFree(m->xc_ctrl);
-  delete m;
 }
 
 }  // namespace lipasr
 
 using namespace lipasr;
 
-// ------------------------------------------------------------------------------------------------
-// plan
-// ------------------------------------------------------------------------------------------------
 extern "C" {
 
 long lipasr_debug_launch_count(int kind) { return (kind == 0 || kind == 1) ? g_launch_count[kind] : -1; }
 
-int lipasr_debug_gemm_mode(int mode) {
-  g_gemm_mode = mode & 3;  // (bits: 0-1 kernel choice, 2 split dW_0, 3 grouped launch on fragment tiles, 4 XCD-aware tile map, 5 no LDS-DMA ring, 6 64 x 64 ring tile for the weight gradients, 7 the 128 x 128 tile without the split pass, 8 no 128 x 64 exchange tiles, 9 no loader instance of the 64 x 64 exchange ring tile)
-  g_split_dw0 = (mode >> 2) & 1;
-  g_group_lds = ((mode >> 3) & 1) ? 0 : 1;
-  g_xcd_map = (mode >> 4) & 1;
-  g_no_ring = (mode >> 5) & 1;
-  g_ring_tile = ((mode >> 6) & 1) ? 1 : ((mode >> 7) & 1) ? 3 : 2;
-  g_ring2 = ((mode >> 8) & 1) ? 0 : 1;
-  g_ring_x1 = ((mode >> 9) & 1) ? 0 : 1;
+int lipasr_debug_gemm_mode(int mode) {  // the bits: GemmKnobs (gemm.h)
+  GemmKnobs k;
+  k.gemm_mode = mode & 3;
+  k.split_dw0 = (mode >> 2) & 1;
+  k.group_lds = !((mode >> 3) & 1);
+  k.xcd_map = (mode >> 4) & 1;
+  k.no_ring = (mode >> 5) & 1;
+  k.ring_tile = ((mode >> 6) & 1) ? 1 : ((mode >> 7) & 1) ? 3 : 2;
+  k.ring2 = !((mode >> 8) & 1);
+  k.ring_x1 = !((mode >> 9) & 1);
+  g_knobs = k;
   return LIPASR_OK;
 }
 
@@ -2643,671 +2104,6 @@ int lipasr_gemm_f16x2(lipasr_handle_t h, int transA, int transB, int M, int N, i
   g.sb = scale_b;
   g.zeros = h->zeros;
   return launch_gemm(transA ? 1 : 0, transB ? 0 : 1, g, S(stream));
-}
-
-int lipasr_mlp_create(lipasr_handle_t h, int n_layers, const int* widths, const int* bn, const float* dropout,
-                      const int* nonneg, int max_batch, lipasr_mlp_t* out) {
-  LP_CHECK_ARG(h && widths && out, "lipasr_mlp_create: null argument");
-  LP_CHECK_ARG(n_layers >= 1 && n_layers <= LIPASR_MAX_LAYERS, "lipasr_mlp_create: n_layers=%d outside [1,%d]", n_layers,
-               LIPASR_MAX_LAYERS);
-  LP_CHECK_ARG(max_batch >= 1, "lipasr_mlp_create: max_batch=%d", max_batch);
-  for (int l = 0; l <= n_layers; ++l) LP_CHECK_ARG(widths[l] >= 1, "lipasr_mlp_create: widths[%d]=%d", l, widths[l]);
-  LP_CHECK_ARG(widths[n_layers] <= 32, "lipasr_mlp_create: %d classes; at most 32 are supported", widths[n_layers]);
-  lipasr_mlp* m = new lipasr_mlp();
-  m->ctx = h;
-  m->n_layers = n_layers;
-  m->max_batch = max_batch;
-  size_t po = 0, so = 0, wo = 0;
-  int maxw = widths[0];
-  for (int l = 0; l < n_layers; ++l) {
-    MlpLayer& L = m->L[l];
-    L.n_in = widths[l];
-    L.n_out = widths[l + 1];
-    const bool last = (l == n_layers - 1);
-    L.bn = !last && bn && bn[l];
-    L.dropout = (!last && dropout) ? dropout[l] : 0.0f;
-    L.nonneg = nonneg && nonneg[l];
-    if (L.dropout < 0.0f || L.dropout >= 1.0f) {
-      delete m;
-      set_error("lipasr_mlp_create: dropout[%d]=%g outside [0,1)", l, (double)L.dropout);
-      return LIPASR_EINVAL;
-    }
-    maxw = L.n_out > maxw ? L.n_out : maxw;
-    L.offW = po; po = align4(po + (size_t)L.n_in * L.n_out);
-    L.offb = po; po = align4(po + L.n_out);
-    if (L.bn) {
-      L.offg = po; po = align4(po + L.n_out);
-      L.offbe = po; po = align4(po + L.n_out);
-      L.offmm = so; so = align4(so + L.n_out);
-      L.offmv = so; so = align4(so + L.n_out);
-    }
-    if (!last) {
-      L.offA = wo; wo = align4(wo + (size_t)max_batch * L.n_out);
-      if (L.bn || L.dropout > 0.0f) { L.offH = wo; wo = align4(wo + (size_t)max_batch * L.n_out); }
-      else L.offH = L.offA;
-      L.offMean = wo; wo = align4(wo + 2 * (size_t)L.n_out);
-    }
-    L.offDz = wo; wo = align4(wo + (size_t)max_batch * L.n_out);
-  }
-  m->n_params = po;
-  m->n_state = so;
-  m->max_width = maxw;
-  const size_t C = widths[n_layers];
-  m->offLogits = wo; wo = align4(wo + (size_t)max_batch * C);
-  m->offProb = wo; wo = align4(wo + (size_t)max_batch * C);
-  m->offDzLast = wo; wo = align4(wo + (size_t)max_batch * C);
-  m->offG0 = wo; wo = align4(wo + (size_t)max_batch * maxw);
-  m->offG1 = wo; wo = align4(wo + (size_t)max_batch * maxw);
-  m->offG2 = wo; wo = align4(wo + (size_t)max_batch * maxw);
-  m->offPart = wo; wo = align4(wo + 2 * (size_t)((max_batch + 31) / 32) * maxw);  // column partials of the *_STATS epilogues
-  m->ws_floats = wo;
-  DeviceGuard g(h->device);
-  if (hipMalloc(&m->ws, wo * sizeof(float)) != hipSuccess) {
-    delete m;
-    set_error("lipasr_mlp_create: workspace allocation of %zu bytes failed", wo * sizeof(float));
-    return LIPASR_ENOMEM;
-  }
-  (void)hipMemset(m->ws, 0, wo * sizeof(float));
-  // exchange epilogue state (round 5): granules and control words per BatchNorm layer and direction, all zero (tag 0 is never used)
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess) m->n_cus = prop.multiProcessorCount;
-    m->xc_rt_max = std::min((max_batch + 31) / 32, 64);
-    const size_t amax_words = (size_t)LIPASR_MAX_LAYERS * kAmaxSlots * kAmaxStride;
-    size_t go = 0, co = 16 + amax_words;  // control words 0 .. 15: the error word (its own 64-byte slot), then amax[layer][slot]
-    for (int dir = 0; dir < 2; ++dir)
-      for (int l = 0; l + 1 < n_layers; ++l) {
-        if (!m->L[l].bn) continue;
-        const size_t nblk = (size_t)(m->L[l].n_out + 31) / 32;
-        m->xc_gran_off[dir][l] = go; go += nblk * m->xc_rt_max * 128;
-        m->xc_ctrl_off[dir][l] = co; co += nblk * 32;
-      }
-    if (hipMalloc(&m->xc_ctrl, co * sizeof(unsigned)) != hipSuccess) {
-      (void)hipGetLastError();
-      mlp_plan_free(m);
-      set_error("lipasr_mlp_create: control-word allocation failed");
-      return LIPASR_ENOMEM;
-    }
-    (void)hipMemset(m->xc_ctrl, 0, co * sizeof(unsigned));
-    m->xc_err = reinterpret_cast<int*>(m->xc_ctrl);
-    m->amax = m->xc_ctrl + 16;  // layer l: m->amax + l * kAmaxSlots * kAmaxStride
-    if (go > 0) {
-      if (hipMalloc(&m->xc_gran, go * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        m->xc_gran = nullptr;  // no exchange state: the launch chain is used
-      } else {
-        (void)hipMemset(m->xc_gran, 0, go * sizeof(unsigned long long));
-      }
-    }
-  }
-  h->mlps.push_back(m);
-  *out = m;
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_destroy(lipasr_mlp_t m) {
-  LP_CHECK_ARG(m != nullptr, "lipasr_mlp_destroy: null plan");
-  DeviceGuard g(m->ctx->device);
-  std::vector<lipasr_mlp*>& v = m->ctx->mlps;
-  for (size_t i = 0; i < v.size(); ++i)
-    if (v[i] == m) { v.erase(v.begin() + i); break; }
-  lipasr::mlp_plan_free(m);
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_sizes(lipasr_mlp_t m, size_t* n_params, size_t* n_state) {
-  LP_CHECK_ARG(m && n_params && n_state, "lipasr_mlp_sizes: null argument");
-  *n_params = m->n_params;
-  *n_state = m->n_state;
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_segment(lipasr_mlp_t m, int layer, int kind, size_t* offset, size_t* count) {
-  LP_CHECK_ARG(m && offset && count, "lipasr_mlp_segment: null argument");
-  LP_CHECK_ARG(layer >= 0 && layer < m->n_layers, "lipasr_mlp_segment: layer %d out of range", layer);
-  const MlpLayer& L = m->L[layer];
-  switch (kind) {
-    case LIPASR_SEG_W: *offset = L.offW; *count = (size_t)L.n_in * L.n_out; break;
-    case LIPASR_SEG_B: *offset = L.offb; *count = L.n_out; break;
-    case LIPASR_SEG_GAMMA: *offset = L.offg; *count = L.bn ? L.n_out : 0; break;
-    case LIPASR_SEG_BETA: *offset = L.offbe; *count = L.bn ? L.n_out : 0; break;
-    case LIPASR_SEG_MMEAN: *offset = L.offmm; *count = L.bn ? L.n_out : 0; break;
-    case LIPASR_SEG_MVAR: *offset = L.offmv; *count = L.bn ? L.n_out : 0; break;
-    default: set_error("lipasr_mlp_segment: unknown kind %d", kind); return LIPASR_EINVAL;
-  }
-  return LIPASR_OK;
-}
-
-}  // extern "C"
-
-namespace lipasr {
-
-static int check_batch(const char* fn, lipasr_mlp_t m, int batch) {
-  LP_CHECK_ARG(m != nullptr, "%s: null plan", fn);
-  LP_CHECK_ARG(batch >= 1 && batch <= m->max_batch, "%s: batch %d outside [1, %d]", fn, batch, m->max_batch);
-  return LIPASR_OK;
-}
-
-static DropArgs drop_for_layer(const lipasr_mlp* m, int l, const lipasr_dropout_cfg* cfg) {
-  DropArgs d;
-  memset(&d, 0, sizeof(d));
-  d.rate = m->L[l].dropout;
-  d.layer = l;
-  if (!cfg || cfg->mode == 0 || d.rate <= 0.0f) { d.mode = 0; return d; }
-  d.mode = cfg->mode;
-  d.seed = cfg->seed;
-  d.step_dev = cfg->step_dev;
-  d.mask = (cfg->mode == 2 && cfg->masks) ? cfg->masks[l] : nullptr;
-  if (cfg->mode == 2 && d.mask == nullptr) d.mode = 0;
-  return d;
-}
-
-// inference-mode forward: fills A_l (post-ReLU, if keep_a) and H_l, logits into m->ws
-// ce_y != nullptr (and <= 32 classes): the last GEMM's epilogue also produces softmax, and (p - y) / batch at
-// m->ws + offDzLast -- the caller then skips softmax_ce_kernel.  Returns through *fused whether it did.
-static int forward_infer(lipasr_mlp* m, const float* params, const float* bnstate, const float* x, int batch,
-                         bool keep_a, float* logits_out, hipStream_t st, const float* ce_y = nullptr,
-                         bool* fused = nullptr) {
-  const float* hin = x;
-  if (fused) *fused = false;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const MlpLayer& L = m->L[l];
-    const bool last = (l == m->n_layers - 1);
-    float* outp = last ? logits_out : (m->ws + L.offH);
-    const bool fuse = last && ce_y && L.n_out <= 32;
-    GemmArgs g = gemm_args(hin, L.n_in, params + L.offW, L.n_out, outp, L.n_out, batch, L.n_out, L.n_in,
-                           last ? (fuse ? EPI_BIAS_SOFTMAX_CE : EPI_BIAS) : EPI_BIAS_RELU_BN);
-    g.bias = params + L.offb;
-    if (fuse) {
-      g.y = ce_y;
-      g.inv_batch = 1.0f / (float)batch;
-      g.prob = m->ws + m->offProb;
-      g.dz = m->ws + m->offDzLast;
-      if (fused) *fused = true;
-    }
-    if (!last) {
-      if (L.bn) {
-        g.gamma = params + L.offg;
-        g.beta = params + L.offbe;
-        g.mmean = bnstate + L.offmm;
-        g.mvar = bnstate + L.offmv;
-      }
-      // when H aliases A (no BN, no dropout) the ReLU output lands in H == A directly
-      g.aux = (keep_a && L.offH != L.offA) ? (m->ws + L.offA) : nullptr;
-    }
-    set_arith(g, m, OP_ACT, OP_WEIGHT, 1.0f, false);
-    int rc = launch_gemm(0, 1, g, st);
-    if (rc != LIPASR_OK) return rc;
-    hin = outp;
-  }
-  return LIPASR_OK;
-}
-
-// inference-mode backward to the input from dz at the logits (in m->ws + offDzLast).
-// final_mode 0: store dx; 1: fused sign step on x_adv.
-static int backward_infer(lipasr_mlp* m, const float* params, const float* bnstate, int batch, float* dx, float* x_adv,
-                          const float* x0, float alpha, float eps, hipStream_t st, float g0 = 1.0f) {
-  const float* gin = m->ws + m->offDzLast;
-  float* pp[2] = {m->ws + m->offG0, m->ws + m->offG1};
-  int cur = 0;
-  for (int l = m->n_layers - 1; l >= 0; --l) {
-    const MlpLayer& L = m->L[l];
-    // dprev[B][n_in] = gin[B][n_out] * W^T ; W stored [n_in][n_out] -> K (= n_out) contiguous
-    if (l > 0) {
-      const MlpLayer& P = m->L[l - 1];
-      GemmArgs g = gemm_args(gin, L.n_out, params + L.offW, L.n_out, pp[cur], L.n_in, batch, L.n_in, L.n_out,
-                             EPI_DZ_INFER);
-      if (P.bn) {
-        g.gamma = params + P.offg;
-        g.mvar = bnstate + P.offmv;
-      }
-      g.aux = m->ws + P.offA;
-      set_arith(g, m, OP_GRAD, OP_WEIGHT, g0, false);
-      int rc = launch_gemm(0, 0, g, st);
-      if (rc != LIPASR_OK) return rc;
-      gin = pp[cur];
-      cur ^= 1;
-    } else {
-      GemmArgs g = gemm_args(gin, L.n_out, params + L.offW, L.n_out, dx, L.n_in, batch, L.n_in, L.n_out,
-                             x_adv ? EPI_SIGNSTEP : EPI_STORE);
-      g.x_adv = x_adv;
-      g.x0 = x0;
-      g.alpha = alpha;
-      g.eps = eps;
-      set_arith(g, m, OP_GRAD, OP_WEIGHT, g0, false);
-      int rc = launch_gemm(0, 0, g, st);
-      if (rc != LIPASR_OK) return rc;
-    }
-  }
-  return LIPASR_OK;
-}
-
-}  // namespace lipasr
-
-extern "C" {
-
-// dw_mode 0: every weight gradient from ONE grouped launch; 1: the first layer's [dW; db] as its own launch after the
-// grouped launch of the others (LDS-tiled 64x64 kernel when legal); 2: the first layer's left out (lipasr_mlp_train_dw0)
-// Segments (synchronized BatchNorm under data parallelism): the launch sequence is cut after every GEMM whose epilogue
-// leaves BatchNorm column partial sums (forward: sums of a, a^2; backward: sums of g, g xhat), i.e. right before the
-// apply kernel that consumes them.  seg < 0 runs everything; otherwise only the launches of segment `seg`, and the caller
-// SUM-all-reduces the partials (segment_exchange_floats) before it runs the next one.  part_ext: caller-owned partials
-// buffer (a torch tensor the caller can hand to its collective), stat_batch: rows the statistics cover (global batch).
-struct SegArgs {
-  int seg = -1;
-  float* part_ext = nullptr;
-  int stat_batch = 0;
-  float grad_scale = 1.0f;
-};
-
-static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, const float* y_onehot,
-                              int batch, float inv_batch, const lipasr_dropout_cfg* dropout, float* grads,
-                              float* loss_rows, float* correct_rows, float* probs, lipasr_stream_t stream, int dw_mode,
-                              const SegArgs& sa = SegArgs()) {
-  int rc = check_batch("lipasr_mlp_train_fwd_bwd", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x && y_onehot && grads, "lipasr_mlp_train_fwd_bwd: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_train_fwd_bwd: bnstate is null");
-  LP_CHECK_ARG(!dropout || (dropout->mode >= 0 && dropout->mode <= 2), "lipasr_mlp_train_fwd_bwd: dropout mode %d",
-               dropout ? dropout->mode : 0);
-  hipStream_t st = S(stream);
-  m->last_inv_batch = inv_batch;
-  const int Lc = m->n_layers;
-  const int C = m->L[Lc - 1].n_out;
-  float* ws = m->ws;
-  float* part = sa.part_ext ? sa.part_ext : (ws + m->offPart);
-  const dim3 apply_block(256);
-  const int bstat = sa.stat_batch > 0 ? sa.stat_batch : batch;
-  int cur = 0;  // current segment
-#define LP_ON (sa.seg < 0 || sa.seg == cur)
-
-  // ---- forward (training mode): GEMM (+bias, ReLU, column partials) -> BatchNorm/dropout apply
-  const float* hin = x;
-  for (int l = 0; l < Lc; ++l) {
-    const MlpLayer& L = m->L[l];
-    const bool last = (l == Lc - 1);
-    float* outp = last ? (ws + m->offLogits) : (ws + L.offA);
-    const bool fuse_ce = last && C <= 32;  // softmax, loss and (p - y) / B in the last GEMM's epilogue
-    // BatchNorm inside this GEMM (exchange epilogue) where the whole grid can be resident; not with synchronized BatchNorm,
-    // whose sums leave the device between the GEMM and the apply kernel
-    const bool bnx = !last && L.bn && sa.seg < 0 && bnx_fits(m, true, batch, L.n_out, L.n_in);
-    GemmArgs g = gemm_args(hin, L.n_in, params + L.offW, L.n_out, outp, L.n_out, batch, L.n_out, L.n_in,
-                           last ? (fuse_ce ? EPI_BIAS_SOFTMAX_CE : EPI_BIAS) : (L.bn ? (bnx ? EPI_BIAS_RELU_BNX : EPI_BIAS_RELU_STATS) : EPI_BIAS_RELU));
-    g.bias = params + L.offb;
-    g.part = part;
-    if (m->compute_bf16 == 2 && !last) g.amax_zero = m->amax + (size_t)l * kAmaxSlots * kAmaxStride;  // the backward pass of this step folds max |dz_l| into it
-    if (bnx) {
-      g.xc_gran = m->xc_gran + m->xc_gran_off[0][l]; g.xc_ctrl = m->xc_ctrl + m->xc_ctrl_off[0][l]; g.xc_err = m->xc_err; g.xc_rt_max = m->xc_rt_max;
-      // LIPASR_XC_NOWAIT=1 (timing probe only, results are WRONG): the exchange epilogue without its wait and sweep, to see what the
-      // exchange instances cost apart from the exchange
-      static const bool xc_nowait = getenv("LIPASR_XC_NOWAIT") != nullptr;
-      g.Bstat = xc_nowait ? -bstat : bstat;
-      g.h_out = ws + L.offH;
-      g.gamma = params + L.offg; g.beta = params + L.offbe;
-      g.mmean_w = bnstate + L.offmm; g.mvar_w = bnstate + L.offmv; g.save_w = ws + L.offMean;
-      g.drop = drop_for_layer(m, l, dropout);
-    }
-    if (fuse_ce) {
-      g.y = y_onehot;
-      g.inv_batch = inv_batch;
-      g.prob = probs ? probs : (ws + m->offProb);
-      g.dz = ws + m->offDzLast;
-      g.loss_rows = loss_rows;
-      g.correct_rows = correct_rows;
-    }
-    set_arith(g, m, OP_ACT, OP_WEIGHT);
-    g.lds_min_tiles = m->lds_min_tiles;
-    if (LP_ON) {
-      rc = launch_gemm(0, 1, g, st);
-      if (rc != LIPASR_OK) return rc;
-      if (sa.seg >= 0 && !last && L.bn) {  // synchronized BatchNorm: [2][row tiles][N] -> [2][N] before the exchange
-        hipLaunchKernelGGL(part_reduce_kernel, dim3((L.n_out + 255) / 256), dim3(256), 0, st, part,
-                           stats_row_tiles(batch, L.n_out, L.n_in, m->lds_min_tiles), L.n_out);
-        LP_LAUNCH_CHECK();
-      }
-    }
-    if (!last && L.bn) ++cur;  // exchange point: the partial sums of a, a^2 are complete
-    if (!last && L.offH != L.offA && LP_ON && !bnx) {
-      BnFwdArgs b;
-      memset(&b, 0, sizeof(b));
-      b.a = ws + L.offA; b.h = ws + L.offH; b.B = batch; b.N = L.n_out; b.has_bn = L.bn ? 1 : 0;
-      b.Bstat = bstat;
-      b.part = part;
-      b.n_tiles = sa.seg >= 0 ? 1 : stats_row_tiles(batch, L.n_out, L.n_in, m->lds_min_tiles);
-      if (L.bn) {
-        b.gamma = params + L.offg; b.beta = params + L.offbe;
-        b.mmean = bnstate + L.offmm; b.mvar = bnstate + L.offmv;
-        b.save_mean = ws + L.offMean;
-      }
-      b.drop = drop_for_layer(m, l, dropout);
-      const dim3 grid((L.n_out + 127) / 128, (batch + kApplyRows - 1) / kApplyRows);
-      hipLaunchKernelGGL(bn_apply_fwd_kernel, grid, apply_block, 0, st, b);
-      LP_LAUNCH_CHECK();
-    }
-    hin = (!last && L.offH != L.offA) ? (ws + L.offH) : outp;
-  }
-  // ---- loss and gradient at the logits (already done by the last GEMM's epilogue for <= 32 classes)
-  if (C > 32 && LP_ON) {
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, ws + m->offLogits, y_onehot, batch,
-                       C, inv_batch, probs ? probs : (ws + m->offProb), ws + m->offDzLast, loss_rows, correct_rows,
-                       (float*)nullptr);
-    LP_LAUNCH_CHECK();
-  }
-
-  // ---- backward.  The dX chain runs first, layer by layer (dX GEMM fused with the dropout backward and the
-  // BatchNorm column sums, then the BatchNorm/ReLU backward apply), keeping every layer's pre-activation gradient;
-  // all weight gradients then come from ONE grouped launch.
-  float* tmp = ws + m->offG0;
-  for (int l = Lc - 1; l >= 1; --l) {
-    const MlpLayer& L = m->L[l];
-    const MlpLayer& P = m->L[l - 1];
-    const float* gin = (l == Lc - 1) ? (ws + m->offDzLast) : (ws + L.offDz);
-    // dh_prev[B][n_in] = gin[B][n_out] * W^T
-    const bool bnx = P.bn && sa.seg < 0 && bnx_fits(m, false, batch, L.n_in, L.n_out);
-    float* out1 = (P.bn && !bnx) ? tmp : (ws + P.offDz);
-    GemmArgs gx = gemm_args(gin, L.n_out, params + L.offW, L.n_out, out1, L.n_in, batch, L.n_in, L.n_out,
-                            P.bn ? (bnx ? EPI_DH_BNX : EPI_DH_STATS) : EPI_DZ_NOBN);
-    gx.aux = ws + P.offA;
-    gx.drop = drop_for_layer(m, l - 1, dropout);
-    gx.part = part;
-    if (P.bn) gx.save_mean = ws + P.offMean;
-    if (bnx) {
-      gx.xc_gran = m->xc_gran + m->xc_gran_off[1][l - 1]; gx.xc_ctrl = m->xc_ctrl + m->xc_ctrl_off[1][l - 1]; gx.xc_err = m->xc_err;
-      gx.xc_rt_max = m->xc_rt_max;
-      gx.Bstat = getenv("LIPASR_XC_NOWAIT") ? -bstat : bstat; gx.grad_scale = sa.grad_scale;
-      gx.gamma = params + P.offg;
-      gx.dgamma = grads + P.offg; gx.dbeta = grads + P.offbe;
-    }
-    set_arith(gx, m, OP_GRAD, OP_WEIGHT, inv_batch);
-    // arithmetic mode 2: the size of a gradient is not known beforehand (BatchNorm's rstd can amplify it 30-fold per layer in an
-    // untrained network): whoever writes dz_l folds max |dz_l| into amax[l], whoever multiplies with dz_l derives its scale from it
-    const bool dyn = m->compute_bf16 == 2;
-    if (dyn && l < Lc - 1 && L.bn) gx.sa_dyn = m->amax + (size_t)l * kAmaxSlots * kAmaxStride;
-    if (dyn && P.bn) gx.amax_out = m->amax + (size_t)(l - 1) * kAmaxSlots * kAmaxStride;
-    gx.lds_min_tiles = m->lds_min_tiles;
-    if (LP_ON) {
-      rc = launch_gemm(0, 0, gx, st);
-      if (rc != LIPASR_OK) return rc;
-      if (sa.seg >= 0 && P.bn) {
-        hipLaunchKernelGGL(part_reduce_kernel, dim3((P.n_out + 255) / 256), dim3(256), 0, st, part,
-                           stats_row_tiles(batch, P.n_out, L.n_out, m->lds_min_tiles), P.n_out);
-        LP_LAUNCH_CHECK();
-      }
-    }
-    if (P.bn) ++cur;  // exchange point: the partial sums of g, g xhat are complete
-    if (P.bn && LP_ON && !bnx) {
-      BnBwdArgs b;
-      memset(&b, 0, sizeof(b));
-      b.g = tmp; b.a = ws + P.offA; b.dz = ws + P.offDz; b.B = batch; b.N = P.n_out;
-      b.Bstat = bstat; b.grad_scale = sa.grad_scale;
-      b.part = part;
-      b.n_tiles = sa.seg >= 0 ? 1 : stats_row_tiles(batch, P.n_out, L.n_out, m->lds_min_tiles);
-      b.gamma = params + P.offg; b.save_mean = ws + P.offMean;
-      b.dgamma = grads + P.offg; b.dbeta = grads + P.offbe;
-      b.amax_out = dyn ? m->amax + (size_t)(l - 1) * kAmaxSlots * kAmaxStride : nullptr;
-      const dim3 grid((P.n_out + 127) / 128, (batch + kApplyRows - 1) / kApplyRows);
-      hipLaunchKernelGGL(bn_apply_bwd_kernel, grid, apply_block, 0, st, b);
-      LP_LAUNCH_CHECK();
-    }
-  }
-  // [dW ; db] = [lin ; 1]^T[n_in+1][B] * gin[B][n_out] for every layer: the all-ones row yields the bias gradient
-  GemmArgs gw[LIPASR_MAX_LAYERS];
-  for (int l = 0; l < Lc; ++l) {
-    const MlpLayer& L = m->L[l];
-    const float* lin = (l == 0) ? x : (ws + m->L[l - 1].offH);
-    const float* gin = (l == Lc - 1) ? (ws + m->offDzLast) : (ws + L.offDz);
-    gw[l] = gemm_args(lin, L.n_in, gin, L.n_out, grads + L.offW, L.n_out, L.n_in + 1, L.n_out, batch, EPI_STORE);
-    gw[l].ones_row = 1;
-    gw[l].extra_out = grads + L.offb;
-    set_arith(gw[l], m, OP_ACT, OP_GRAD, inv_batch);
-    if (m->compute_bf16 == 2 && l < Lc - 1 && L.bn) gw[l].sb_dyn = m->amax + (size_t)l * kAmaxSlots * kAmaxStride;
-  }
-  if (!LP_ON) return LIPASR_OK;
-#undef LP_ON
-  if (dw_mode == 0 || Lc == 1) return launch_gemm_group_tn(gw, Lc, st);
-  rc = launch_gemm_group_tn(gw + 1, Lc - 1, st);
-  if (rc != LIPASR_OK || dw_mode == 2) return rc;
-  return launch_gemm(1, 1, gw[0], st);
-}
-
-int lipasr_mlp_train_fwd_bwd(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, const float* y_onehot,
-                             int batch, float inv_batch, const lipasr_dropout_cfg* dropout, float* grads,
-                             float* loss_rows, float* correct_rows, float* probs, lipasr_stream_t stream) {
-  return train_fwd_bwd_impl(m, params, bnstate, x, y_onehot, batch, inv_batch, dropout, grads, loss_rows, correct_rows, probs,
-                            stream, g_split_dw0 ? 1 : 0);
-}
-
-int lipasr_mlp_train_fwd_bwd_head(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, const float* y_onehot,
-                                  int batch, float inv_batch, const lipasr_dropout_cfg* dropout, float* grads,
-                                  float* loss_rows, float* correct_rows, float* probs, lipasr_stream_t stream) {
-  return train_fwd_bwd_impl(m, params, bnstate, x, y_onehot, batch, inv_batch, dropout, grads, loss_rows, correct_rows, probs,
-                            stream, 2);
-}
-
-int lipasr_mlp_train_dw0(lipasr_mlp_t m, const float* x, int batch, float* grads, lipasr_stream_t stream) {
-  int rc = check_batch("lipasr_mlp_train_dw0", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(x && grads, "lipasr_mlp_train_dw0: null argument");
-  if (m->n_layers == 1) return LIPASR_OK;  // a one-layer plan's head already holds every gradient
-  const MlpLayer& L = m->L[0];
-  GemmArgs g = gemm_args(x, L.n_in, m->ws + L.offDz, L.n_out, grads + L.offW, L.n_out, L.n_in + 1, L.n_out, batch, EPI_STORE);
-  g.ones_row = 1;
-  g.extra_out = grads + L.offb;
-  set_arith(g, m, OP_ACT, OP_GRAD, m->last_inv_batch);
-  if (m->compute_bf16 == 2 && L.bn) g.sb_dyn = m->amax;
-  return launch_gemm(1, 1, g, S(stream));
-}
-
-int lipasr_mlp_train_segments(lipasr_mlp_t m, int* n_segments) {
-  LP_CHECK_ARG(m && n_segments, "lipasr_mlp_train_segments: null argument");
-  int n = 1;
-  for (int l = 0; l + 1 < m->n_layers; ++l)
-    if (m->L[l].bn) n += 2;  // one exchange in the forward pass, one in the backward pass
-  *n_segments = n;
-  return LIPASR_OK;
-}
-
-// floats of the partials buffer to SUM-all-reduce after segment `seg` (0 after the last one)
-int lipasr_mlp_train_segment_exchange(lipasr_mlp_t m, int batch, int seg, size_t* floats) {
-  int rc = check_batch("lipasr_mlp_train_segment_exchange", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(floats != nullptr && seg >= 0, "lipasr_mlp_train_segment_exchange: bad argument");
-  *floats = 0;
-  int cur = 0;
-  for (int l = 0; l + 1 < m->n_layers; ++l)  // forward: layer l's GEMM closes a segment if layer l has BatchNorm
-    if (m->L[l].bn) {
-      if (cur == seg) { *floats = 2 * (size_t)m->L[l].n_out; return LIPASR_OK; }  // reduced to [2][N] by part_reduce_kernel
-      ++cur;
-    }
-  for (int l = m->n_layers - 1; l >= 1; --l)  // backward: the dX GEMM into layer l-1 closes one if layer l-1 has BatchNorm
-    if (m->L[l - 1].bn) {
-      if (cur == seg) { *floats = 2 * (size_t)m->L[l - 1].n_out; return LIPASR_OK; }
-      ++cur;
-    }
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_part_floats(lipasr_mlp_t m, size_t* floats) {
-  LP_CHECK_ARG(m && floats, "lipasr_mlp_part_floats: null argument");
-  *floats = 2 * (size_t)((m->max_batch + 31) / 32) * m->max_width;
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_train_segment(lipasr_mlp_t m, int seg, const float* params, float* bnstate, const float* x, const float* y_onehot,
-                             int batch, float inv_batch, const lipasr_dropout_cfg* dropout, float* grads, float* loss_rows,
-                             float* correct_rows, float* probs, float* part, int stat_batch, float stat_grad_scale,
-                             lipasr_stream_t stream) {
-  LP_CHECK_ARG(m != nullptr && part != nullptr, "lipasr_mlp_train_segment: null argument");
-  int n = 0;
-  (void)lipasr_mlp_train_segments(m, &n);
-  LP_CHECK_ARG(seg >= 0 && seg < n, "lipasr_mlp_train_segment: segment %d outside [0, %d)", seg, n);
-  LP_CHECK_ARG(stat_batch >= batch && stat_grad_scale > 0.0f, "lipasr_mlp_train_segment: stat_batch=%d (< batch %d) or scale %g", stat_batch,
-               batch, (double)stat_grad_scale);
-  SegArgs sa;
-  sa.seg = seg; sa.part_ext = part; sa.stat_batch = stat_batch; sa.grad_scale = stat_grad_scale;
-  return train_fwd_bwd_impl(m, params, bnstate, x, y_onehot, batch, inv_batch, dropout, grads, loss_rows, correct_rows, probs,
-                            stream, 0, sa);
-}
-
-int lipasr_mlp_grad_split(lipasr_mlp_t m, size_t* late_floats) {
-  LP_CHECK_ARG(m && late_floats, "lipasr_mlp_grad_split: null argument");
-  // [W0 | b0] come from lipasr_mlp_train_dw0; what follows in the flat layout (gamma0, beta0, layers 1..) is final after the head
-  const MlpLayer& L = m->L[0];
-  *late_floats = (m->n_layers == 1) ? 0 : (L.bn ? L.offg : m->L[1].offW);
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_predict(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, int batch,
-                       float* probs, float* logits, lipasr_stream_t stream) {
-  int rc = check_batch("lipasr_mlp_predict", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x && (probs || logits), "lipasr_mlp_predict: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_predict: bnstate is null");
-  float* lg = logits ? logits : (m->ws + m->offLogits);
-  rc = forward_infer(m, params, bnstate, x, batch, false, lg, S(stream));
-  if (rc != LIPASR_OK) return rc;
-  if (probs) {
-    const int C = m->L[m->n_layers - 1].n_out;
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3((batch + 255) / 256), dim3(256), 0, S(stream), lg, (const float*)nullptr,
-                       batch, C, 0.0f, probs, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-    LP_LAUNCH_CHECK();
-  }
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_own_labels(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, int batch,
-                          float* y_onehot_out, lipasr_stream_t stream) {
-  int rc = check_batch("lipasr_mlp_own_labels", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x && y_onehot_out, "lipasr_mlp_own_labels: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_own_labels: bnstate is null");
-  float* lg = m->ws + m->offLogits;
-  rc = forward_infer(m, params, bnstate, x, batch, false, lg, S(stream));
-  if (rc != LIPASR_OK) return rc;
-  const int C = m->L[m->n_layers - 1].n_out;
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3((batch + 255) / 256), dim3(256), 0, S(stream), lg, (const float*)nullptr,
-                     batch, C, 0.0f, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, y_onehot_out);
-  LP_LAUNCH_CHECK();
-  return LIPASR_OK;
-}
-
-static int attack_common(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x_eval,
-                         const float* y_onehot, int batch, float* dx, float* x_adv, const float* x0, float alpha,
-                         float eps, hipStream_t st) {
-  float* lg = m->ws + m->offLogits;
-  bool fused = false;
-  int rc = forward_infer(m, params, bnstate, x_eval, batch, true, lg, st, y_onehot, &fused);
-  if (rc != LIPASR_OK) return rc;
-  if (!fused) {
-    const int C = m->L[m->n_layers - 1].n_out;
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, lg, y_onehot, batch, C,
-                       1.0f / (float)batch, m->ws + m->offProb, m->ws + m->offDzLast, (float*)nullptr, (float*)nullptr,
-                       (float*)nullptr);
-    LP_LAUNCH_CHECK();
-  }
-  return backward_infer(m, params, bnstate, batch, dx, x_adv, x0, alpha, eps, st, 1.0f / (float)batch);
-}
-
-int lipasr_mlp_input_grad(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x,
-                          const float* y_onehot, int batch, float* dx, lipasr_stream_t stream) {
-  int rc = check_batch("lipasr_mlp_input_grad", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x && y_onehot && dx, "lipasr_mlp_input_grad: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_input_grad: bnstate is null");
-  return attack_common(m, params, bnstate, x, y_onehot, batch, dx, nullptr, nullptr, 0.0f, 0.0f, S(stream));
-}
-
-int lipasr_mlp_attack_step(lipasr_mlp_t m, const float* params, const float* bnstate, float* x_adv, const float* x0,
-                           const float* y_onehot, int batch, float alpha, float eps, lipasr_stream_t stream) {
-  int rc = check_batch("lipasr_mlp_attack_step", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x_adv && x0 && y_onehot, "lipasr_mlp_attack_step: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_attack_step: bnstate is null");
-  LP_CHECK_ARG(eps >= 0.0f && !(alpha != alpha), "lipasr_mlp_attack_step: eps=%g alpha=%g", (double)eps, (double)alpha);
-  return attack_common(m, params, bnstate, x_adv, y_onehot, batch, nullptr, x_adv, x0, alpha, eps, S(stream));
-}
-
-// Lp FGM / PGD iteration: norm inf is lipasr_mlp_attack_step (the fused K4 epilogue).  L1 / L2: the dX GEMM of layer 0 stores g
-// into the ping-pong gradient buffer that backward_infer does not read at layer 0 (both are max_batch x max(widths) wide, the
-// input width included), then the row-wise step kernel of lp_attack.hip -- two launches, no allocation, capturable.
-int lipasr_mlp_attack_step_lp(lipasr_mlp_t m, const float* params, const float* bnstate, float* x_adv, const float* x0,
-                              const float* y_onehot, int batch, float norm, float alpha, float eps, lipasr_stream_t stream) {
-  int code = 0;
-  int rc = lp_norm_code("lipasr_mlp_attack_step_lp", norm, &code);
-  if (rc != LIPASR_OK) return rc;
-  if (code == 0) return lipasr_mlp_attack_step(m, params, bnstate, x_adv, x0, y_onehot, batch, alpha, eps, stream);
-  rc = check_batch("lipasr_mlp_attack_step_lp", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x_adv && x0 && y_onehot, "lipasr_mlp_attack_step_lp: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_attack_step_lp: bnstate is null");
-  LP_CHECK_ARG(eps >= 0.0f && !(alpha != alpha), "lipasr_mlp_attack_step_lp: eps=%g alpha=%g", (double)eps, (double)alpha);
-  // backward_infer writes layer n-1's input gradient into G0, then alternates: at layer 0 it reads G[(n-2) % 2]
-  float* g = m->ws + (((m->n_layers - 1) & 1) ? m->offG1 : m->offG0);
-  rc = attack_common(m, params, bnstate, x_adv, y_onehot, batch, g, nullptr, nullptr, 0.0f, 0.0f, S(stream));
-  if (rc != LIPASR_OK) return rc;
-  return lp_step_launch(x_adv, x0, g, batch, m->L[0].n_in, code, alpha, eps, S(stream));
-}
-
-int lipasr_mlp_output_vjp(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, const float* v,
-                          int on_logits, int batch, float* probs_out, float* dx, lipasr_stream_t stream) {
-  int rc = check_batch("lipasr_mlp_output_vjp", m, batch);
-  if (rc != LIPASR_OK) return rc;
-  LP_CHECK_ARG(params && x && v && dx, "lipasr_mlp_output_vjp: null argument");
-  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_output_vjp: bnstate is null");
-  hipStream_t st = S(stream);
-  float* lg = m->ws + m->offLogits;
-  rc = forward_infer(m, params, bnstate, x, batch, true, lg, st);
-  if (rc != LIPASR_OK) return rc;
-  const int C = m->L[m->n_layers - 1].n_out;
-  hipLaunchKernelGGL(softmax_vjp_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, lg, v, batch, C, on_logits ? 1 : 0,
-                     probs_out, m->ws + m->offDzLast);
-  LP_LAUNCH_CHECK();
-  return backward_infer(m, params, bnstate, batch, dx, nullptr, nullptr, 0.0f, 0.0f, st);
-}
-
-int lipasr_mlp_set_gemm_tiles(lipasr_mlp_t m, int lds_min_tiles) {
-  LP_CHECK_ARG(m != nullptr && lds_min_tiles >= 0, "lipasr_mlp_set_gemm_tiles: bad argument");
-  m->lds_min_tiles = lds_min_tiles;
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_set_fuse_bn(lipasr_mlp_t m, int mode) {
-  LP_CHECK_ARG(m != nullptr && (mode == 0 || mode == 1), "lipasr_mlp_set_fuse_bn: bad argument");
-  m->fuse_bn = mode;
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_set_cu_budget(lipasr_mlp_t m, int n_cus) {
-  LP_CHECK_ARG(m != nullptr && n_cus >= 0, "lipasr_mlp_set_cu_budget: bad argument");
-  m->cu_budget = n_cus;
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_exchange_errors(lipasr_mlp_t m, int* errors_host) {
-  LP_CHECK_ARG(m != nullptr && errors_host != nullptr, "lipasr_mlp_exchange_errors: null argument");
-  *errors_host = 0;
-  if (!m->xc_err) return LIPASR_OK;
-  DeviceGuard g(m->ctx->device);
-  LP_HIP(hipMemcpy(errors_host, m->xc_err, sizeof(int), hipMemcpyDeviceToHost));  // synchronises with the device
-  if (*errors_host) LP_HIP(hipMemset(m->xc_err, 0, sizeof(int)));
-  return LIPASR_OK;
-}
-
-int lipasr_mlp_set_compute(lipasr_mlp_t m, int mode) {
-  LP_CHECK_ARG(m != nullptr, "lipasr_mlp_set_compute: null plan");
-  LP_CHECK_ARG(mode >= 0 && mode <= 2, "lipasr_mlp_set_compute: mode %d (0 = exact fp32, 1 = bf16 operands, 2 = fp16 two-plane split)", mode);
-  if (mode == 2) {
-    // the split needs operands inside fp16's range: gradients carry a measured scale, kernels are small, and the activations are
-    // bounded because they are BatchNorm outputs -- so every hidden layer must have one (the reference's models do:
-    // train_constraints.py:67-85); a network without runs its activations up without bound (all-positive kernels: 1e4 and more)
-    for (int l = 0; l + 1 < m->n_layers; ++l)
-      if (!m->L[l].bn) {
-        set_error("lipasr_mlp_set_compute: mode 2 (fp16 two-plane split) needs BatchNormalization after every hidden Dense layer (layer %d has none); use mode 0", l);
-        return LIPASR_EUNSUPPORTED;
-      }
-  }
-  m->compute_bf16 = mode;
-  return LIPASR_OK;
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 // three bases 16-byte aligned) and up to 1 024 floats with 4-byte loads (ragged widths); longer rows take
 // lp_step_stream_kernel, which re-reads the row (three passes) -- no model of the project is that wide.
 //
-// lp_ball_init_kernel: one wavefront per row, Philox keyed like the dropout masks (dense.hip, DropArgs): key = seed + rank x
+// lp_ball_init_kernel: one wavefront per row, Philox keyed like the dropout masks (gemm.h, DropArgs): key = seed + rank x
 // golden ratio, counter = (element group, row, *counter_dev).  Counter-based, so the two passes the L1 / L2 draws need (the
 // row's norm, then the scaled write) regenerate the same numbers instead of holding them.
 #include "common.h"

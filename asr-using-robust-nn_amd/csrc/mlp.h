@@ -1,4 +1,4 @@
-// The dense-classifier plan shared by dense.hip (forward/backward) and optim.hip (Adam, projections).
+// The dense-classifier plan shared by mlp.hip (forward/backward) and optim.hip (Adam, projections).
 #pragma once
 #include "common.h"
 
@@ -37,7 +37,7 @@ struct lipasr_mlp {
   int compute_bf16 = 0;  // lipasr_mlp_set_compute: 0 exact fp32, 1 GEMM operands rounded to bf16 at the MFMA, 2 fp16 two-plane split (fp32 accumulate)
   float last_inv_batch = 1.0f;  // the loss-gradient bound of the last training forward (mode 2's gradient scale in lipasr_mlp_train_dw0)
   int lds_min_tiles = 0;  // lipasr_mlp_set_gemm_tiles: training GEMMs take the LDS-tiled kernel from this many 64x64 tiles (0 = default)
-  // Round 5: training-mode BatchNorm inside the GEMM that produces its input (dense.hip, "exchange epilogue").  The row tiles
+  // Round 5: training-mode BatchNorm inside the GEMM that produces its input (gemm.hip, "exchange epilogue").  The row tiles
   // of a 32- (or 64-) column block hand each other their column partial sums through memory INSIDE the launch, so the apply
   // kernels and their launch boundaries go.  Per BatchNorm layer and direction: granules {tag, value} and two control words
   // per 32-column block.

@@ -7,9 +7,11 @@
 // (c) the price of the exchange a fused BatchNorm needs: every workgroup of a column block publishes its partial sums as
 //     8-byte {tag, value} granules (sc1 stores), sweeps the granules of the block's other row tiles until every tag matches,
 //     and the last one through bumps the block's epoch -- measured inside an otherwise empty kernel, R rounds per launch.
-// Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -I asr-using-robust-nn_amd/csrc scratch/link_bench.hip -o scratch/link_bench
+// Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -I asr-using-robust-nn_amd/csrc scratch/link_bench.hip asr-using-robust-nn_amd/csrc/lp_attack.hip -o scratch/link_bench
+// (lp_attack.hip: the plan code in mlp.hip refers to its step launcher)
 // Every spin is bounded (a give-up sets an error word, the grid always drains).
-#include "../asr-using-robust-nn_amd/csrc/dense.hip"
+#include "../asr-using-robust-nn_amd/csrc/gemm.hip"
+#include "../asr-using-robust-nn_amd/csrc/mlp.hip"
 #include <cstdlib>
 
 namespace lipasr {
@@ -285,7 +287,7 @@ int main(int argc, char** argv) {
     launch_gemm(0, 1, g, st);
     BnFwdArgs b;
     memset(&b, 0, sizeof(b));
-    b.a = a1; b.h = h1; b.B = kB; b.N = kN1; b.has_bn = 1; b.Bstat = kB; b.part = part; b.n_tiles = stats_row_tiles(kB, kN1, kK1, 0);
+    b.a = a1; b.h = h1; b.B = kB; b.N = kN1; b.has_bn = 1; b.Bstat = kB; b.part = part; b.n_tiles = gemm_row_tiles(0, 1, g);
     b.gamma = gamma; b.beta = beta; b.mmean = mm; b.mvar = mm + kN1; b.save_mean = save;
     hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3((kN1 + 127) / 128, (kB + kApplyRows - 1) / kApplyRows), dim3(256), 0, st, b);
     GemmArgs g2 = gemm_args(h1, kN1, W2, kN2, a2, kN2, kB, kN2, kN1, EPI_BIAS_RELU_STATS);
