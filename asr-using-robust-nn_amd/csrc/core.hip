@@ -21,7 +21,7 @@ using namespace lipasr;
 
 extern "C" {
 
-int lipasr_version(void) { return 510; }  // 510: the Lp attack entry points (round 4 added lipasr_flag_*, lipasr_debug_chain_head; round 5: see include/lipasr.h)
+int lipasr_version(void) { return 520; }  // 520: the MFCC backward pass (lipasr_mfcc_plan_vjp, lipasr_mfcc_plan_resample_vjp); 510: the Lp attack entry points (round 4 added lipasr_flag_*, lipasr_debug_chain_head; round 5: see include/lipasr.h)
 
 const char* lipasr_last_error(void) { return g_err; }
 

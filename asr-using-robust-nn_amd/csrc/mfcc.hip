@@ -73,12 +73,23 @@ struct MfccPlan {
   // the kernel's fused top_db + DCT epilogue (lipasr_mfcc_plan_set key 4): off by default -- measured on batches that are not
   // cache-warm it loses to the separate dct_kernel (STFT 139 + 5 us against 120 + 19 us per 1024 clips, round 4)
   bool bd_fuse_dct = false;
+  // backward pass (lipasr_mfcc_plan_vjp, kernels in mfcc_vjp.hip): allocated at the first call
+  float* d_gmel = nullptr;      // [batch_max][n_frames][128]
+  float* d_part = nullptr;      // [batch_max][vj_groups][kVjSeg]
+  float* d_gy = nullptr;        // [batch_max][n_y]
+  float* d_dct_rows = nullptr;  // [20][128] plain DCT rows
+  int* d_bin_run = nullptr;     // [1025]
+  int vj_groups = 0;
+  // the resampler's adjoint as a polyphase filter (lipasr_mfcc_plan_resample_vjp): allocated at the first call
+  float* d_rt_taps = nullptr;   // [rt_nt][down]
+  int* d_rt_t0 = nullptr;       // [down]
+  int rt_nt = 0, rt_t0min = 0, rt_t0max = 0;
 };
 
 void mfcc_plan_free(MfccPlan* p) {
   if (!p) return;
   void* ptrs[] = {p->d_hbandh, p->d_groups, p->d_dft, p->d_mel_wlo, p->d_mel_whi, p->d_mel_pstart, p->d_mel_plen, p->d_hband, p->d_lo, p->d_h, p->d_noff, p->d_hann, p->d_tw, p->d_mel_start, p->d_mel_len, p->d_mel_off,
-                  p->d_mel_w, p->d_dct, p->d_y, p->d_db, p->d_fmax};
+                  p->d_mel_w, p->d_dct, p->d_y, p->d_db, p->d_fmax, p->d_gmel, p->d_part, p->d_gy, p->d_dct_rows, p->d_bin_run, p->d_rt_taps, p->d_rt_t0};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   for (hipEvent_t e : p->prof_events) (void)hipEventDestroy(e);
@@ -538,94 +549,7 @@ __global__ __launch_bounds__(256) void copy_pad_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------
 // stage 2: STFT -> power -> mel -> dB
 // ---------------------------------------------------------------------------------------------
-// LDS holds complex points as float2; element e lives at e ^ ((e >> 4) & 7) (no padding).  Unit-stride
-// accesses (every read, the writes of passes 3 and 4) stay a permutation inside aligned 8-element blocks, i.e.
-// conflict-free for ds_read_b64's 32-lane halves, and the stride-8 scatter of pass 1 lands its 16-lane write
-// groups on 16 distinct 8-byte slots (pass 2's stride-64 scatter is 2-way).
-constexpr int kFftLds = 2048 + 72;  // + room for the four weighted-power arrays laid over one buffer
-__device__ __forceinline__ int padi(int i) { return i ^ ((i >> 4) & 7); }
-
-struct cpx { float re, im; };
-__device__ __forceinline__ cpx cadd(cpx a, cpx b) { return {a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cpx csub(cpx a, cpx b) { return {a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cpx cmul(cpx a, cpx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cpx mul_mi(cpx a) { return {a.im, -a.re}; }  // a * (-i)
-
-__device__ __forceinline__ void dft8(cpx (&v)[8]) {
-  const float s = 0.70710678118654752440f;
-  cpx a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]), a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
-  cpx a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]), a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
-  cpx b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
-  cpx b4 = cadd(a4, a6), b6 = csub(a4, a6), b5 = cadd(a5, a7), b7 = csub(a5, a7);
-  // w1 = (1 - i)/sqrt2, w2 = -i, w3 = (-1 - i)/sqrt2
-  cpx t5 = {(b5.re + b5.im) * s, (b5.im - b5.re) * s};
-  cpx t6 = mul_mi(b6);
-  cpx t7 = {(b7.im - b7.re) * s, (-b7.re - b7.im) * s};
-  v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
-  v[1] = cadd(b1, t5); v[5] = csub(b1, t5);
-  v[2] = cadd(b2, t6); v[6] = csub(b2, t6);
-  v[3] = cadd(b3, t7); v[7] = csub(b3, t7);
-}
-
-__device__ __forceinline__ void dft4(cpx (&v)[4]) {
-  cpx a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]), a3 = mul_mi(csub(v[1], v[3]));
-  v[0] = cadd(a0, a2); v[2] = csub(a0, a2); v[1] = cadd(a1, a3); v[3] = csub(a1, a3);
-}
-
-__device__ __forceinline__ void butterfly(cpx (&v)[8]) { dft8(v); }
-__device__ __forceinline__ void butterfly(cpx (&v)[4]) { dft4(v); }
-
-// one Stockham pass of radix R over 2048 points: butterfly j reads src[j + r*2048/R], multiplies by
-// w^r, w = exp(-2 pi i k/(Ns R)), k = j mod Ns, writes dst[(j/Ns) Ns R + k + r Ns].
-// Twiddles: w, w^2, w^4 come from the table, the other powers are one complex product away.
-// In place on one LDS buffer: every thread reads its inputs, the workgroup meets (sync_between), then writes.
-template <int R, int NB>
-__device__ __forceinline__ void fft_pass(float2* __restrict__ buf, int Ns, int j0_, const float2* __restrict__ tw,
-                                         const cpx* __restrict__ regs = nullptr) {
-  constexpr int NR = 2048 / R;
-  cpx vv[NB][R];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (regs) {
-        vv[b][r] = regs[r];  // pass 1: butterfly j's inputs x[j + r*256] are exactly what thread j loaded
-      } else {
-        const float2 t = buf[padi(j0_ + 256 * b + r * NR)];
-        vv[b][r] = {t.x, t.y};
-      }
-    }
-  }
-  if (!regs) __syncthreads();  // all reads of this pass are done before anybody overwrites the buffer
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    cpx (&v)[R] = vv[b];
-    const int j = j0_ + 256 * b;
-    float2* dst = buf;
-  const int k = j & (Ns - 1);
-  if (Ns > 1) {
-    const int tstep = k * (2048 / (Ns * R));
-    const float2 t1 = tw[tstep & 2047], t2 = tw[(2 * tstep) & 2047];
-    const cpx w1 = {t1.x, t1.y}, w2 = {t2.x, t2.y};
-    const cpx w3 = cmul(w1, w2);
-    v[1] = cmul(v[1], w1);
-    v[2] = cmul(v[2], w2);
-    v[3] = cmul(v[3], w3);
-    if (R == 8) {
-      const float2 t4 = tw[(4 * tstep) & 2047];
-      const cpx w4 = {t4.x, t4.y};
-      v[4 % R] = cmul(v[4 % R], w4);
-      v[5 % R] = cmul(v[5 % R], cmul(w1, w4));
-      v[6 % R] = cmul(v[6 % R], cmul(w2, w4));
-      v[7 % R] = cmul(v[7 % R], cmul(w3, w4));
-    }
-  }
-  butterfly(v);
-  const int j0 = (j - k) * R + k;
-#pragma unroll
-  for (int r = 0; r < R; ++r) dst[padi(j0 + r * Ns)] = make_float2(v[r].re, v[r].im);
-  }
-}
+// (padi, cpx, dft8 / dft4 and fft_pass live in stft.h: the backward kernels of mfcc_vjp.hip run the same passes)
 
 constexpr int kTPair = 1028;    // stride of the two float2 (frame 0, frame 1) weighted-power arrays, >= 1025 bins
 
@@ -1874,7 +1798,8 @@ static int launch_fused(const MfccPlan* p, const void* wav, int fmt, const int* 
 static bool stft2_ok(const MfccPlan* p) { return !p->dft && !(p->stage_mask & (64 | 3)); }
 
 static int launch_from_22k(const MfccPlan* p, const float* y, const int* n_valid, int batch, int L, const double* am, const double* as,
-                           float* out, hipStream_t st, hipEvent_t mid = nullptr) {  // mid: recorded between stft_mel and dct
+                           float* out, hipStream_t st, hipEvent_t mid = nullptr, bool stft_only = false) {  // mid: recorded between stft_mel and dct
+  // stft_only: stop after the dB tile and the frame maxima (the backward pass re-running the forward; nothing is written to out)
   StftArgs a;
   fill_stft_args(p, y, &a);
   a.n_valid = n_valid; a.sr_in = p->sr_in; a.n_samp_max = p->n_samp;
@@ -1896,7 +1821,7 @@ static int launch_from_22k(const MfccPlan* p, const float* y, const int* n_valid
     hipLaunchKernelGGL(dft_mel_kernel, dim3((d.total_rows + kDftRows - 1) / kDftRows), dim3(64 * p->dft_tiles), dl, st, d);
   } else if (stft2_ok(p) && p->bd.cfrag && !(p->stage_mask & 256)) {
     // one workgroup per clip: on request (plan key 4) the kernel finishes with the top_db floor and the DCT itself
-    const bool fuse = p->bd_fuse_dct && bdft_can_fuse_dct(p->n_frames, p->bd_seg, L);
+    const bool fuse = !stft_only && p->bd_fuse_dct && bdft_can_fuse_dct(p->n_frames, p->bd_seg, L);
     BdftDct d;
     d.L = L; d.dct_frag = reinterpret_cast<const float4*>(p->d_dct); d.aff_mean = am; d.aff_scale = as; d.out = out;
     const int rc = launch_stft_bdft(a, p->bd, batch, p->bd_seg, fuse ? &d : nullptr, st);
@@ -1912,6 +1837,7 @@ static int launch_from_22k(const MfccPlan* p, const float* y, const int* n_valid
   }
   LP_LAUNCH_CHECK();
   if (mid) LP_HIP(hipEventRecord(mid, st));
+  if (stft_only) return LIPASR_OK;
   return launch_dct(p, batch, L, am, as, out, n_valid, st);
 }
 
@@ -2118,6 +2044,127 @@ static int plan_run(MfccPlan* p, const void* wav, int fmt, const int* n_valid, i
   return LIPASR_OK;
 }
 
+// ---- backward pass ----
+static int vjp_unsupported(const char* fn, const MfccPlan* p) {
+  if (p->dft) {
+    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d", fn, p->n_fft, p->hop);
+    return LIPASR_EUNSUPPORTED;
+  }
+  if (p->n_y <= kNFft) {
+    set_error("%s: the backward pass needs clips longer than the reflect padding (n_y %d <= %d)", fn, p->n_y, kNFft);
+    return LIPASR_EUNSUPPORTED;
+  }
+  return LIPASR_OK;
+}
+
+static int vjp_prepare(MfccPlan* p) {
+  if (p->d_gmel) return LIPASR_OK;
+  DeviceGuard g(p->ctx->device);
+  p->vj_groups = (p->n_frames + kVjFrames - 1) / kVjFrames;
+  MelPairs mp = mel_pairs();
+  std::vector<int> run(kNBins, 0);
+  for (int m = 0; m < kNMels; ++m)
+    for (int i = 0; i < mp.len[m]; ++i) run[mp.start[m] + i] = m;
+  int rc;
+  if (!p->d_bin_run && (rc = upload(&p->d_bin_run, run)) != LIPASR_OK) return rc;
+  if (!p->d_dct_rows && (rc = upload(&p->d_dct_rows, dct_matrix())) != LIPASR_OK) return rc;
+  const size_t ngm = (size_t)p->batch_max * p->n_frames * kNMels, npart = (size_t)p->batch_max * p->vj_groups * kVjSeg,
+               ngy = (size_t)p->batch_max * p->n_y;
+  if ((!p->d_part && hipMalloc(&p->d_part, npart * sizeof(float)) != hipSuccess) ||
+      (!p->d_gy && hipMalloc(&p->d_gy, ngy * sizeof(float)) != hipSuccess) ||
+      hipMalloc(&p->d_gmel, ngm * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("lipasr_mfcc_plan_vjp: intermediate allocation failed");
+    return LIPASR_ENOMEM;
+  }
+  return LIPASR_OK;
+}
+
+// Tables of R^T in polyphase form: for phase r = j mod down, the run of outputs t (relative to up q') with
+// r + left - taps <= pos(t) <= r + left - 1, pos(t) = down floor(t / up) + n_off[t mod up] = floor(t down / up), and their taps.
+static int resample_vjp_prepare(MfccPlan* p) {
+  if (p->identity || p->d_rt_taps) return LIPASR_OK;
+  DeviceGuard g(p->ctx->device);
+  const Polyphase pp = build_polyphase(p->sr_in, kSr);
+  const long up = pp.up, down = pp.down;
+  auto split = [&](long t, long* q, int* ph) {
+    long qq = t / up;
+    if (t - qq * up < 0) --qq;
+    *q = qq; *ph = (int)(t - qq * up);
+  };
+  auto pos = [&](long t) { long q; int ph; split(t, &q, &ph); return down * q + pp.n_off[ph]; };
+  std::vector<int> t0(pp.down), cnt(pp.down);
+  int nt = 0;
+  for (int r = 0; r < pp.down; ++r) {
+    const long A = (long)r + pp.left - pp.taps, B = (long)r + pp.left - 1;
+    long num = A * up, t = num / down;
+    if (num - t * down < 0) --t;  // floor
+    t -= 2;
+    while (pos(t) < A) ++t;
+    t0[r] = (int)t;
+    int c = 0;
+    while (pos(t + c) <= B) ++c;
+    cnt[r] = c;
+    nt = std::max(nt, c);
+  }
+  std::vector<float> ht((size_t)nt * pp.down, 0.0f);
+  for (int r = 0; r < pp.down; ++r)
+    for (int i = 0; i < cnt[r]; ++i) {
+      long q; int ph;
+      split((long)t0[r] + i, &q, &ph);
+      const long k = (long)r - (down * q + pp.n_off[ph]) + pp.left - 1;
+      if (k >= 0 && k < pp.taps) ht[(size_t)i * pp.down + r] = pp.h[(size_t)ph * pp.taps + k];
+    }
+  p->rt_nt = nt;
+  p->rt_t0min = *std::min_element(t0.begin(), t0.end());
+  p->rt_t0max = *std::max_element(t0.begin(), t0.end());
+  int rc;
+  if ((rc = upload(&p->d_rt_t0, t0)) != LIPASR_OK || (rc = upload(&p->d_rt_taps, ht)) != LIPASR_OK) return rc;
+  return LIPASR_OK;
+}
+
+static int plan_resample_vjp(MfccPlan* p, const float* gy, int batch, float* gx, hipStream_t st) {
+  int rc = resample_vjp_prepare(p);
+  if (rc != LIPASR_OK) return rc;
+  ResampleVjpArgs a;
+  a.n_y = p->n_y; a.n_valid = p->n_valid; a.n_samp = p->n_samp; a.up = p->up; a.down = p->down; a.identity = p->identity;
+  a.ht = p->d_rt_taps; a.t0 = p->d_rt_t0; a.nt = p->rt_nt; a.t0min = p->rt_t0min; a.t0max = p->rt_t0max;
+  return launch_resample_vjp(a, gy, gx, batch, st);
+}
+
+static int plan_vjp(MfccPlan* p, const float* sig, int domain, int batch, int L, const double* as, const float* g_feat, float* g_sig,
+                    int flags, hipStream_t st) {
+  LP_CHECK_ARG(sig && g_feat && g_sig, "lipasr_mfcc_plan_vjp: null argument");
+  LP_CHECK_ARG(domain == 0 || domain == 1, "lipasr_mfcc_plan_vjp: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", domain);
+  LP_CHECK_ARG((flags & ~7) == 0, "lipasr_mfcc_plan_vjp: unknown flag bits %d", flags);
+  if (flags & 6) {
+    set_error("lipasr_mfcc_plan_vjp: int16 input and per-clip lengths have no backward pass (float32 rows of one length only)");
+    return LIPASR_EUNSUPPORTED;
+  }
+  int rc = vjp_unsupported("lipasr_mfcc_plan_vjp", p);
+  if (rc != LIPASR_OK) return rc;
+  if ((rc = vjp_prepare(p)) != LIPASR_OK) return rc;
+  // the plan's intermediates are the caller's forward only if that ran the three-kernel form (the fused resample -> STFT kernel
+  // leaves no d_y) with the stage mask's profiling switches off
+  const bool reuse = (flags & 1) && !(domain == 0 && p->fused && p->prefer_fused) && !(p->stage_mask & 3);
+  const float* y = sig;
+  if (domain == 0) {
+    if (!reuse && (rc = launch_resample(p, sig, 0, nullptr, batch, p->d_y, st)) != LIPASR_OK) return rc;
+    y = p->d_y;
+  }
+  if (!reuse && (rc = launch_from_22k(p, y, nullptr, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
+  MfccVjpArgs a;
+  a.y = y; a.n_y = p->n_y; a.n_frames = p->n_frames; a.batch = batch; a.L = L;
+  a.db = p->d_db; a.fmax = p->d_fmax; a.g_feat = g_feat; a.aff_scale = as; a.dct_rows = p->d_dct_rows;
+  a.hann = p->d_hann; a.tw = reinterpret_cast<const float2*>(p->d_tw);
+  a.mel_wlo = p->d_mel_wlo; a.mel_whi = p->d_mel_whi; a.bin_run = p->d_bin_run;
+  a.gmel = p->d_gmel; a.part = p->d_part; a.n_groups = p->vj_groups;
+  a.gy = domain == 0 ? p->d_gy : g_sig;
+  if ((rc = launch_mfcc_vjp(a, st)) != LIPASR_OK) return rc;
+  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st);
+  return LIPASR_OK;
+}
+
 static int plan_profile_begin(MfccPlan* p, int max_calls) {
   LP_CHECK_ARG(p != nullptr && max_calls >= 1 && max_calls <= 100000, "lipasr_mfcc_profile_begin: bad argument");
   DeviceGuard g(p->ctx->device);
@@ -2228,6 +2275,20 @@ int lipasr_mfcc_plan_from_22k(lipasr_mfcc_t p, const float* y, int batch, int n_
   if (rc != LIPASR_OK) return rc;
   LP_CHECK_ARG(y && out, "lipasr_mfcc_plan_from_22k: null argument");
   return plan_from_22k(p, y, batch, n_y, utterance_length, affine_mean, affine_scale, out, S(stream));
+}
+
+int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length, const double* affine_scale,
+                         const float* g_feat, float* g_sig, int flags, lipasr_stream_t stream) {
+  int rc = plan_check("lipasr_mfcc_plan_vjp", p, batch, utterance_length);
+  if (rc != LIPASR_OK) return rc;
+  return plan_vjp(p, sig, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+}
+
+int lipasr_mfcc_plan_resample_vjp(lipasr_mfcc_t p, const float* g_y, int batch, float* g_wav, lipasr_stream_t stream) {
+  int rc = plan_check("lipasr_mfcc_plan_resample_vjp", p, batch, 1);
+  if (rc != LIPASR_OK) return rc;
+  LP_CHECK_ARG(g_y && g_wav, "lipasr_mfcc_plan_resample_vjp: null argument");
+  return plan_resample_vjp(p, g_y, batch, g_wav, S(stream));
 }
 
 int lipasr_mfcc_plan_profile_begin(lipasr_mfcc_t p, int max_calls) { return plan_profile_begin(p, max_calls); }

@@ -52,6 +52,96 @@ __device__ __forceinline__ void lds_barrier2() {
   __builtin_amdgcn_s_barrier();
 }
 
+// ---- LDS Stockham FFT of 2048 complex points (stft_mel_kernel, mfcc_fused_kernel, stft_vjp_kernel) ----
+// LDS holds complex points as float2; element e lives at e ^ ((e >> 4) & 7) (no padding).  Unit-stride
+// accesses (every read, the writes of passes 3 and 4) stay a permutation inside aligned 8-element blocks, i.e.
+// conflict-free for ds_read_b64's 32-lane halves, and the stride-8 scatter of pass 1 lands its 16-lane write
+// groups on 16 distinct 8-byte slots (pass 2's stride-64 scatter is 2-way).
+constexpr int kFftLds = 2048 + 72;  // + room for the four weighted-power arrays laid over one buffer
+__device__ __forceinline__ int padi(int i) { return i ^ ((i >> 4) & 7); }
+
+struct cpx { float re, im; };
+__device__ __forceinline__ cpx cadd(cpx a, cpx b) { return {a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ cpx csub(cpx a, cpx b) { return {a.re - b.re, a.im - b.im}; }
+__device__ __forceinline__ cpx cmul(cpx a, cpx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__device__ __forceinline__ cpx mul_mi(cpx a) { return {a.im, -a.re}; }  // a * (-i)
+
+__device__ __forceinline__ void dft8(cpx (&v)[8]) {
+  const float s = 0.70710678118654752440f;
+  cpx a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]), a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
+  cpx a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]), a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
+  cpx b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
+  cpx b4 = cadd(a4, a6), b6 = csub(a4, a6), b5 = cadd(a5, a7), b7 = csub(a5, a7);
+  // w1 = (1 - i)/sqrt2, w2 = -i, w3 = (-1 - i)/sqrt2
+  cpx t5 = {(b5.re + b5.im) * s, (b5.im - b5.re) * s};
+  cpx t6 = mul_mi(b6);
+  cpx t7 = {(b7.im - b7.re) * s, (-b7.re - b7.im) * s};
+  v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
+  v[1] = cadd(b1, t5); v[5] = csub(b1, t5);
+  v[2] = cadd(b2, t6); v[6] = csub(b2, t6);
+  v[3] = cadd(b3, t7); v[7] = csub(b3, t7);
+}
+
+__device__ __forceinline__ void dft4(cpx (&v)[4]) {
+  cpx a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]), a3 = mul_mi(csub(v[1], v[3]));
+  v[0] = cadd(a0, a2); v[2] = csub(a0, a2); v[1] = cadd(a1, a3); v[3] = csub(a1, a3);
+}
+
+__device__ __forceinline__ void butterfly(cpx (&v)[8]) { dft8(v); }
+__device__ __forceinline__ void butterfly(cpx (&v)[4]) { dft4(v); }
+
+// one Stockham pass of radix R over 2048 points: butterfly j reads src[j + r*2048/R], multiplies by
+// w^r, w = exp(-2 pi i k/(Ns R)), k = j mod Ns, writes dst[(j/Ns) Ns R + k + r Ns].
+// Twiddles: w, w^2, w^4 come from the table, the other powers are one complex product away.
+// In place on one LDS buffer: every thread reads its inputs, the workgroup meets (sync_between), then writes.
+template <int R, int NB>
+__device__ __forceinline__ void fft_pass(float2* __restrict__ buf, int Ns, int j0_, const float2* __restrict__ tw,
+                                         const cpx* __restrict__ regs = nullptr) {
+  constexpr int NR = 2048 / R;
+  cpx vv[NB][R];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (regs) {
+        vv[b][r] = regs[r];  // pass 1: butterfly j's inputs x[j + r*256] are exactly what thread j loaded
+      } else {
+        const float2 t = buf[padi(j0_ + 256 * b + r * NR)];
+        vv[b][r] = {t.x, t.y};
+      }
+    }
+  }
+  if (!regs) __syncthreads();  // all reads of this pass are done before anybody overwrites the buffer
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    cpx (&v)[R] = vv[b];
+    const int j = j0_ + 256 * b;
+    float2* dst = buf;
+  const int k = j & (Ns - 1);
+  if (Ns > 1) {
+    const int tstep = k * (2048 / (Ns * R));
+    const float2 t1 = tw[tstep & 2047], t2 = tw[(2 * tstep) & 2047];
+    const cpx w1 = {t1.x, t1.y}, w2 = {t2.x, t2.y};
+    const cpx w3 = cmul(w1, w2);
+    v[1] = cmul(v[1], w1);
+    v[2] = cmul(v[2], w2);
+    v[3] = cmul(v[3], w3);
+    if (R == 8) {
+      const float2 t4 = tw[(4 * tstep) & 2047];
+      const cpx w4 = {t4.x, t4.y};
+      v[4 % R] = cmul(v[4 % R], w4);
+      v[5 % R] = cmul(v[5 % R], cmul(w1, w4));
+      v[6 % R] = cmul(v[6 % R], cmul(w2, w4));
+      v[7 % R] = cmul(v[7 % R], cmul(w3, w4));
+    }
+  }
+  butterfly(v);
+  const int j0 = (j - k) * R + k;
+#pragma unroll
+  for (int r = 0; r < R; ++r) dst[padi(j0 + r * Ns)] = make_float2(v[r].re, v[r].im);
+  }
+}
+
 // ---- stft_bdft.hip: constant tables of the block-DFT kernel (device pointers, owned by the MFCC plan) ----
 struct BdftTables {
   uint4* cfrag = nullptr;    // [4 tiles][2 planes][64 lanes]: stage-1 matrix (cos | -sin of W64), fp16 hi / lo fragments
@@ -75,5 +165,38 @@ struct BdftDct {
 };
 bool bdft_can_fuse_dct(int n_frames, int seg_frames, int L);
 int launch_stft_bdft(const StftArgs& a, const BdftTables& t, int batch, int seg_frames, const BdftDct* dct, hipStream_t st);
+
+// ---- mfcc_vjp.hip: vector-Jacobian product of the 2048/512 MFCC stage (kernels and their launchers; the plan glue is in mfcc.hip) ----
+constexpr int kVjFrames = 8;                       // frames per workgroup of stft_vjp_kernel (even: frames go through the FFT in pairs)
+constexpr int kVjSeg = (kVjFrames + 3) * 512;      // padded-signal samples those frames cover
+struct MfccVjpArgs {
+  const float* y;          // [batch][n_y] the 22 050 Hz signal the forward read
+  int n_y, n_frames, batch, L;
+  const float* db;         // [batch][n_frames][128] pre-floor dB of the forward
+  const float* fmax;       // [batch][n_frames]
+  const float* g_feat;     // [batch][20 L] cotangent
+  const double* aff_scale; // [20 L] or null
+  const float* dct_rows;   // [20][128]
+  const float* hann;
+  const float2* tw;
+  const float* mel_wlo;    // [1025]
+  const float* mel_whi;
+  const int* bin_run;      // [1025]: the mel filter bin k feeds with weight wlo[k] (and bin_run + 1 with whi[k])
+  float* gmel;             // [batch][n_frames][128] scratch: d loss / d mel
+  float* part;             // [batch][n_groups][kVjSeg] scratch: overlap-added frame gradients of each frame group
+  int n_groups;
+  float* gy;               // [batch][n_y] out
+};
+int launch_mfcc_vjp(const MfccVjpArgs& a, hipStream_t st);
+// gx = R^T gy for the polyphase resampler y[up q + p] = sum_k H[p][k] x[down q + noff[p] - (left - 1) + k], t < n_valid, in its own
+// polyphase form gx[down q' + r] = sum_i HT[i][r] gy[up q' + t0[r] + i] (tables built by the plan, see resample_vjp_kernel)
+struct ResampleVjpArgs {
+  int n_y = 0, n_valid = 0, n_samp = 0, up = 1, down = 1;
+  bool identity = false;
+  const float* ht = nullptr;  // [nt][down]
+  const int* t0 = nullptr;    // [down]
+  int nt = 0, t0min = 0, t0max = 0;
+};
+int launch_resample_vjp(const ResampleVjpArgs& a, const float* gy, float* gx, int batch, hipStream_t st);
 
 }  // namespace lipasr

@@ -16,6 +16,7 @@ from __future__ import annotations
 import argparse
 
 import numpy as np
+import torch
 
 from . import attacks as A
 from .keras import CategoricalCrossentropy, load_model, to_categorical
@@ -80,10 +81,59 @@ def black_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
     return _sweep(models, list(grid)[:points], make, test_labels, "black-box attack")
 
 
+def _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels, kind, standardize, test_filenames, domain, grid,
+                           points, limit, attack_kw):
+    """FGSM / PGD over the audio of ``test_filenames``; see white_box_sweep."""
+    if kind not in ("fgsm", "pgd"):
+        raise ValueError(f"over='audio' runs kind 'fgsm' and 'pgd', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
+    if test_filenames is None:
+        raise ValueError("attacks over audio need test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+    if domain not in ("22k", "input"):
+        raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+    test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+    labels = test_labels[:limit] if limit else test_labels
+    if standardize == "before":
+        train_data, val_data, _ = A.standardize_dataset(train_data, val_data, test_data)
+    # the statistics black_box_sweep(over="audio") uses at sigma = 0: those of (train, val, the files' clean MFCCs)
+    clean = A.black_box_attack_on_audio_dataset(test_filenames, 0, p=0, alpha=0)
+    sc = A.StandardScaler().fit(np.concatenate([np.asarray(train_data), np.asarray(val_data), clean]))
+    n_classes = labels.shape[1]
+    grid = list(AUDIO_SIGMAS if grid is None else grid)[:points]
+    groups = A._files_to_batches(test_filenames)
+    acc = {name: [] for name in models}
+    for item in grid:
+        for name, model in models.items():
+            pred = np.zeros((len(test_filenames), n_classes))
+            for (sr, n), items in groups.items():
+                w = A._to_dev(np.stack([x for _, x in items]))
+                ex = A._extractor(int(sr), int(n), min(w.shape[0], model._max_batch))
+                clf = A.WaveformClassifier(model, n_classes, extractor=ex, mean=sc.mean_, scale=sc.scale_, domain=domain)
+                x = torch.cat([ex.resample(w[s:s + ex.batch_max]) for s in range(0, w.shape[0], ex.batch_max)]) if domain == "22k" else w
+                idx = [i for i, _ in items]
+                cls = A.FastGradientMethod if kind == "fgsm" else A.ProjectedGradientDescent
+                adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x, None) if item != 0 else x
+                pred[idx] = clf.predict_device(adv).cpu().numpy()
+            a = accuracy(pred, labels)
+            acc[name].append(a)
+            print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
+    return grid, {k: np.asarray(v) for k, v in acc.items()}
+
+
 def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="fgsm", standardize="before", grid=None,
-                    points=None, limit=None, **attack_kw):
+                    points=None, limit=None, over="mfcc", test_filenames=None, domain="22k", **attack_kw):
     """attacks.py:493-693.  The models are wrapped as TensorFlowV2Classifier(model=, nb_classes=, input_shape=,
-    loss_object=) (:500-504) and attacked with ART's constructor keywords; JSMA runs on the first 100 test rows (:552)."""
+    loss_object=) (:500-504) and attacked with ART's constructor keywords; JSMA runs on the first 100 test rows (:552).
+    over="audio" (kind fgsm | pgd): the attack perturbs the audio of ``test_filenames`` through WaveformClassifier -- the 22 050 Hz
+    signal (domain="22k", what the black-box audio noise perturbs) or the file's own samples (domain="input"); eps is an
+    amplitude, iterates stay in [-1, 1].  The reference has no such sweep, so the default grid is OURS: AUDIO_SIGMAS, which lays
+    the curve over black_box_sweep(over="audio", kind="simple").  Features are standardized with the statistics of (train, val,
+    clean test MFCCs), fused into the extraction: the statistics black_box_sweep(over="audio") derives at sigma = 0, so the two
+    sweeps agree at strength 0."""
+    if over == "audio":
+        return _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels, kind, standardize, test_filenames, domain,
+                                      grid, points, limit, attack_kw)
+    if over != "mfcc":
+        raise ValueError("over must be 'audio' or 'mfcc'")
     if standardize == "before":
         train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
     n_classes, n_in = test_labels.shape[1], test_data.shape[1]
@@ -143,6 +193,9 @@ def main(argv=None):
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
     kw = {}
+    if args.over == "audio":
+        kw.update(over="audio", test_filenames=np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist())
+        labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
     if args.norm != "inf":
         if args.kind not in ("fgsm", "pgd"):
             raise ValueError("--norm applies to --kind fgsm and pgd")

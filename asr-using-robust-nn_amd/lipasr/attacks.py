@@ -7,6 +7,8 @@ predictions, no clip_values).  Each PGD iteration is ONE native call: inference 
 backward to the input and the sign step fused into the last backward GEMM's epilogue (K4).  ART's other
 ``norm`` (1, 2), ``targeted`` and ``num_random_init`` keywords run the same call in its Lp form
 (lipasr_mlp_attack_step_lp: the step is a second launch) and a native random start (lipasr_lp_ball_init).
+``WaveformClassifier`` puts the MFCC stage in front of the model: the same two attacks then perturb the AUDIO (eps in
+amplitude units), the gradient reaching the samples through the native backward pass of K1 (lipasr_mfcc_plan_vjp).
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.
@@ -19,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .extract_features_construct_dataset import read_wav, _extractor
+from .extract_features_construct_dataset import MfccExtractor, read_wav, _extractor
 from .keras import Model, to_categorical
 
 
@@ -126,6 +128,73 @@ class TensorFlowV2Classifier:
         v = torch.zeros(b, self.nb_classes, device=xt.device)
         v[torch.arange(b, device=xt.device), lab] = 1.0
         return self.output_vjp_device(xt, v)[:, None, :].cpu().numpy()
+
+
+class WaveformClassifier:
+    """Estimator over audio: waveform -> MFCC (K1) -> optional StandardScaler affine -> model.  ``loss_gradient`` follows
+    TensorFlowV2Classifier.loss_gradient's convention (lipasr_mlp_input_grad: d mean CE / d features in inference mode) and
+    carries it to the samples with the backward pass of the MFCC stage (MfccExtractor.vjp).
+    domain="22k" (default): the input is the 22 050 Hz signal [B, extractor.n_y], what the reference's audio noise attacks
+    perturb (librosa.load's output, attacks.py:108-114), so that black-box and white-box audio curves share an amplitude axis;
+    domain="input": the file's samples [B, n_samp] at ``sr_in``.  ``mean`` / ``scale``: [20 * utterance_length] statistics
+    fused into the extraction (both or neither).  ``clip_values``: the attacks clamp their iterates to it."""
+
+    def __init__(self, model, nb_classes, extractor=None, sr_in=16000, n_samp=16000, utterance_length=44, mean=None, scale=None,
+                 domain="22k", clip_values=(-1.0, 1.0)):
+        if not isinstance(model, Model):
+            raise TypeError("model must be a lipasr.keras.Model")
+        if domain not in ("22k", "input"):
+            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+        if (mean is None) != (scale is None):
+            raise ValueError("give both mean and scale or neither")
+        self.model, self.nb_classes, self.utterance_length, self.domain = model, int(nb_classes), int(utterance_length), domain
+        self.extractor = extractor if extractor is not None else MfccExtractor(sr_in, n_samp, batch_max=model._max_batch, device=model._device)
+        self.n = self.extractor.n_y if domain == "22k" else self.extractor.n_samp
+        self.input_shape = (self.n,)
+        n_feat = 20 * self.utterance_length
+        if model._n_classes != self.nb_classes or model._widths[0] != n_feat:
+            raise ValueError("nb_classes / utterance_length do not match the model")
+        dev = self.extractor.device
+        as64 = lambda v: None if v is None else torch.as_tensor(v).to(device=dev, dtype=torch.float64).contiguous().reshape(-1)
+        self.mean, self.scale = as64(mean), as64(scale)
+        if self.mean is not None and (self.mean.numel() != n_feat or self.scale.numel() != n_feat):
+            raise ValueError(f"mean and scale must have {n_feat} elements")
+        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self._bs = min(model._max_batch, self.extractor.batch_max)
+
+    def _check(self, xt):
+        if xt.dim() != 2 or xt.shape[1] != self.n:
+            raise ValueError(f"waveforms must be [B, {self.n}] for domain {self.domain!r}, got {tuple(xt.shape)}")
+
+    def features_device(self, xt):
+        """[B <= batch_max, n] device tensor -> standardised features [B, 20 * utterance_length]."""
+        if self.domain == "22k":
+            return self.extractor.from_22k(xt, self.utterance_length, self.mean, self.scale)
+        return self.extractor(xt, self.utterance_length, self.mean, self.scale)
+
+    def predict_device(self, xt, logits=False):
+        self._check(xt)
+        return torch.cat([self.model.predict_device(self.features_device(xt[s:s + self._bs].contiguous()), logits=logits)
+                          for s in range(0, xt.shape[0], self._bs)])
+
+    def predict(self, x, batch_size=128):
+        return self.predict_device(_to_dev(x)).cpu().numpy()
+
+    def loss_gradient_device(self, xt, yt, out=None):
+        """d mean CE(f(features(x)), y) / dx on device tensors ([B, n], one-hot [B, classes]) -> [B, n]."""
+        self._check(xt)
+        m, ex = self.model, self.extractor
+        out = torch.empty_like(xt) if out is None else out
+        for s in range(0, xt.shape[0], self._bs):
+            xb, yb, ob = xt[s:s + self._bs], yt[s:s + self._bs], out[s:s + self._bs]
+            f = self.features_device(xb)
+            gf = torch.empty_like(f)
+            N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yb), xb.shape[0], N.ptr(gf), N.stream_ptr()))
+            ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+        return out
+
+    def loss_gradient(self, x, y):
+        return self.loss_gradient_device(_to_dev(x), _to_dev(y)).cpu().numpy()
 
 
 def random_targets(labels, nb_classes, rng=None):
@@ -431,8 +500,9 @@ class _SignAttack:
     (lipasr_lp_ball_init) before its first iteration."""
 
     def __init__(self, estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init):
-        if not isinstance(estimator, TensorFlowV2Classifier):
-            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier")
+        if not isinstance(estimator, (TensorFlowV2Classifier, WaveformClassifier)):
+            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        self._wave = isinstance(estimator, WaveformClassifier)
         self.norm = _norm_value(norm)
         if int(num_random_init) < 0:
             raise ValueError("num_random_init must be >= 0")
@@ -492,8 +562,72 @@ class _SignAttack:
         bs = min(self.batch_size, m._max_batch)
         return torch.cat([self._labels(m, xt[s:s + bs], None if yt is None else yt[s:s + bs]) for s in range(0, xt.shape[0], bs)])
 
+    # ---- over audio (WaveformClassifier): features -> lipasr_mlp_input_grad -> MFCC backward -> lipasr_lp_step -> clamp, all on
+    # the device; every keyword keeps its meaning, eps and eps_step are amplitudes
+    def _wave_attack_rows(self, est, xa, x0, yb, restart, row0, g):
+        h = N.get_handle(xa.device.index)
+        self._start(xa, x0, restart, row0)
+        if est.clip_values is not None and self.num_random_init > 0:
+            xa.clamp_(*est.clip_values)
+        alpha = -self.eps_step if self.targeted else self.eps_step
+        for _ in range(self.max_iter):
+            est.loss_gradient_device(xa, yb, out=g)
+            N.check(N.lib.lipasr_lp_step(h.h, N.ptr(xa), N.ptr(x0), N.ptr(g), xa.shape[0], xa.shape[1], self.norm, alpha, self.eps,
+                                         N.stream_ptr()))
+            if est.clip_values is not None:
+                xa.clamp_(*est.clip_values)
+
+    def _wave_success(self, est, x0, yb, xa):
+        pa = est.predict_device(xa, logits=True).argmax(dim=1)
+        if self.targeted:
+            return pa == yb.argmax(dim=1)
+        return pa != est.predict_device(x0, logits=True).argmax(dim=1)
+
+    def _generate_wave(self, xt, yt):
+        est = self.estimator
+        m = est.model
+        est._check(xt)
+        if self.targeted and yt is None:
+            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
+        if self._draws is None:
+            self._draws = torch.zeros(1, dtype=torch.int32, device=xt.device)
+        bs = min(self.batch_size, est._bs)
+        rows = range(0, xt.shape[0], bs)
+        y_all = yt if yt is not None else torch.cat([self._labels(m, est.features_device(xt[s:s + bs].contiguous()), None) for s in rows])
+        g = torch.empty(bs, xt.shape[1], device=xt.device)
+        restarts = max(1, self.num_random_init)
+        whole = isinstance(self, FastGradientMethod)  # ART: FGM keeps the best whole restart, PGD the successful rows of each
+        best, best_rate = None, None
+        adv = torch.empty_like(xt)
+        for r in (range(restarts) if whole else (0,)):
+            cur = adv if r == 0 else torch.empty_like(xt)
+            for s in rows:
+                x0, yb, out = xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs]
+                gb = g[:x0.shape[0]]
+                if whole:
+                    self._wave_attack_rows(est, out, x0, yb, r, s, gb)
+                    continue
+                xa = torch.empty_like(x0)
+                for rr in range(restarts):
+                    self._wave_attack_rows(est, xa, x0, yb, rr, s, gb)
+                    if rr == 0:
+                        out.copy_(xa)
+                    else:
+                        ok = self._wave_success(est, x0, yb, xa)
+                        out[ok] = xa[ok]
+            if whole and restarts > 1:
+                rate = float(torch.cat([self._wave_success(est, xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs]) for s in rows]).float().mean())
+                if best_rate is None or rate > best_rate:
+                    best, best_rate = cur, rate
+            else:
+                best = cur
+        self._draws += 1
+        return best
+
     def generate_device(self, xt, yt=None):
         """x: float32 device tensor; returns a NEW device tensor (the input is left untouched)."""
+        if self._wave:
+            return self._generate_wave(xt, yt)
         m = self.estimator.model
         if self._default_path:  # the reference's call: exactly the launches of round 5
             adv = xt.clone()

@@ -105,6 +105,46 @@ class MfccExtractor:
                                                 N.ptr(out), N.stream_ptr()))
         return out
 
+    def vjp(self, sig, g_feat, utterance_length=STANDARD_UTTERANCE_LENGTH, scale=None, domain="input", reuse_forward=False, out=None,
+            n_valid=None):
+        """Backward pass (lipasr_mfcc_plan_vjp): the gradient w.r.t. ``sig`` of <features(sig), g_feat>.
+        domain="input": sig [B, n_samp] at sr_in (what ``__call__`` takes); domain="22k": sig [B, n_y] (what ``from_22k`` takes).
+        scale: the float64 StandardScaler scale the forward applied, or None.  reuse_forward=True: this extractor's last call
+        was the forward on exactly this ``sig`` on the current stream; its intermediates are read, the bits are the same.
+        2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED)."""
+        if self._plan is None:
+            raise RuntimeError("MfccExtractor used after close()")
+        if domain not in ("input", "22k"):
+            raise ValueError(f"domain={domain!r}: 'input' or '22k'")
+        dom = 0 if domain == "input" else 1
+        n = self.n_samp if dom == 0 else self.n_y
+        b = sig.shape[0]
+        if sig.dim() != 2 or sig.shape[1] != n or not sig.is_contiguous():
+            raise ValueError(f"sig must be contiguous [B, {n}] for domain {domain!r}, got {tuple(sig.shape)}")
+        if sig.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"sig must be float32, got {sig.dtype}")
+        if tuple(g_feat.shape) != (b, N_MFCC * utterance_length) or g_feat.dtype != torch.float32 or not g_feat.is_contiguous():
+            raise ValueError(f"g_feat must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
+        if scale is not None and (scale.dtype != torch.float64 or scale.numel() != N_MFCC * utterance_length):
+            raise ValueError("scale must be a float64 device tensor [20 * utterance_length]")
+        if out is None:
+            out = torch.empty(b, n, device=self.device)
+        elif tuple(out.shape) != (b, n) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 [{b}, {n}]")
+        flags = (1 if reuse_forward else 0) | (2 if sig.dtype == torch.int16 else 0) | (4 if n_valid is not None else 0)
+        N.check(N.lib.lipasr_mfcc_plan_vjp(self._plan, N.ptr(sig), dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat), N.ptr(out),
+                                           flags, N.stream_ptr()))
+        return out
+
+    def resample_vjp(self, g_y, out=None):
+        """Adjoint of ``resample``: [B, n_y] -> [B, n_samp]."""
+        if g_y.dim() != 2 or g_y.shape[1] != self.n_y or g_y.dtype != torch.float32 or not g_y.is_contiguous():
+            raise ValueError(f"g_y must be contiguous float32 [B, {self.n_y}]")
+        if out is None:
+            out = torch.empty(g_y.shape[0], self.n_samp, device=self.device)
+        N.check(N.lib.lipasr_mfcc_plan_resample_vjp(self._plan, N.ptr(g_y), g_y.shape[0], N.ptr(out), N.stream_ptr()))
+        return out
+
 
 _extractors = {}
 

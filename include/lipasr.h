@@ -8,10 +8,11 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 510.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 520.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
+ * 520: the backward pass of the MFCC stage, lipasr_mfcc_plan_vjp and lipasr_mfcc_plan_resample_vjp.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -444,6 +445,33 @@ int lipasr_mfcc_plan_resample(lipasr_mfcc_t p, const float* wav, int batch, floa
 int lipasr_mfcc_plan_from_22k(lipasr_mfcc_t p, const float* y, int batch, int n_y, int utterance_length,
                               const double* affine_mean, const double* affine_scale, float* out,
                               lipasr_stream_t stream);
+
+/* Backward pass of K1 (2048/512 plans): the vector-Jacobian product g_sig = J^T g_feat of the feature map
+ *   out[k L + t] = (c[k][t] - mean) / scale,  c = D max(dB, clipmax - 80),  dB = 10 log10 max(1e-10, W |STFT(R x)|^2)
+ * for a cotangent g_feat [batch][20 L] (what lipasr_mlp_input_grad writes).  In order: Gc = g / scale (frames >= L and the
+ * zero columns of fix_frames receive nothing), Gdbc = D^T Gc, Gdb = Gdbc where dB > clipmax - 80 and 0 elsewhere, the position of
+ * the clip maximum (which may lie in a frame >= L) also receives the sum of Gdbc over the floored elements, Gmel = Gdb (10/ln 10)
+ * / mel where mel > 1e-10, GP = W^T Gmel, Z = 2 GP X on the 1025 one-sided bins (no Hermitian doubling), frame gradient =
+ * hann * Re(sum_k Z[k] e^{+2 pi i k n / 2048}), overlap-add, adjoint of the reflect padding (the flanks fold back onto
+ * y[1 .. 1024] and y[n_y - 1025 .. n_y - 2]), and for domain 0 the adjoint of the resampler (the appended zero sample gets
+ * nothing).  With several equal maxima the FIRST in (frame, mel) order takes the floored sum -- autograd's even split between
+ * them is not reproduced; max(dB, floor) passes the gradient to dB only where dB > floor.  An all-zero clip gives an all-zero
+ * gradient.
+ *   domain 0: sig [batch][n_samp] at the plan's sr_in, g_sig [batch][n_samp];
+ *   domain 1: sig [batch][n_y] at 22 050 Hz (lipasr_mfcc_plan_from_22k's input), g_sig [batch][n_y].
+ *   affine_scale: the StandardScaler scale the forward applied (device double [20 L]) or NULL (= 1).
+ *   flags bit 0: the caller ran THIS plan's forward (lipasr_mfcc_extract for domain 0, lipasr_mfcc_plan_from_22k for domain 1) on
+ *     exactly this signal and batch as the plan's last call, on this stream: the plan's intermediates are read instead of
+ *     re-running the forward kernels.  Same bits either way.  bit 1: the rows are int16 PCM, bit 2: the rows have per-clip
+ *     lengths -- neither has a backward pass: LIPASR_EUNSUPPORTED, as for short-window plans and clips of n_y <= 2048.
+ * Every sum runs in a fixed order (no floating-point atomics): two calls give the same bits.  No host synchronisation; the
+ * plan's backward workspaces are allocated by the first call (make it outside a graph capture). */
+int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length,
+                         const double* affine_scale, const float* g_feat, float* g_sig, int flags,
+                         lipasr_stream_t stream);
+/* g_wav [batch][n_samp] = R^T g_y [batch][n_y]: the adjoint of lipasr_mfcc_plan_resample (any plan whose ratio keeps one
+ * q-block's window of g_y in LDS; its tap table is built by the first call) */
+int lipasr_mfcc_plan_resample_vjp(lipasr_mfcc_t p, const float* g_y, int batch, float* g_wav, lipasr_stream_t stream);
 
 /* Per-kernel HIP-event timing of the next `max_calls` extractions -- lipasr_mfcc_f32 calls, or
  * lipasr_resample_f32 + lipasr_mfcc_from_22k pairs -- recorded on the stream the kernels run on.
