@@ -33,6 +33,13 @@ void set_error(const char* fmt, ...);
 // after a kernel launch: surfaces launch-configuration errors without synchronising
 #define LP_LAUNCH_CHECK() LP_HIP(hipGetLastError())
 
+// core.hip.  ensure_dyn_lds: the one place that raises a kernel's dynamic LDS limit, once per (kernel, device).  false: the device
+// refused the size (kept too, so that a refused size is asked once; the error message is set: callers return LIPASR_EHIP or fall back).
+// device_cus: CUs of the current device, asked once per device.
+bool ensure_dyn_lds(const void* fn, size_t bytes);
+int device_cus();
+#define LP_DYN_LDS(fn, bytes) do { if (!lipasr::ensure_dyn_lds(reinterpret_cast<const void*>(fn), (bytes))) return LIPASR_EHIP; } while (0)
+
 struct MfccPlan;
 
 }  // namespace lipasr

@@ -1,5 +1,7 @@
 // Handle lifetime, error reporting, HIP-event timers and HIP-graph capture for liblipasr.
 #include "common.h"
+#include <map>
+#include <mutex>
 
 namespace lipasr {
 
@@ -10,6 +12,30 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+int device_cus() {
+  static int cached[16] = {};
+  int dev = 0; (void)hipGetDevice(&dev);
+  int& c = cached[dev & 15];
+  if (!c) { hipDeviceProp_t prop; c = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
+  return c;
+}
+
+bool ensure_dyn_lds(const void* fn, size_t bytes) {
+  if (bytes <= 48 * 1024) return true;
+  struct Limit { size_t granted = 0, refused = SIZE_MAX; };
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, Limit> limits;
+  int dev = 0; (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(mu);
+  Limit& l = limits[{fn, dev}];
+  if (bytes <= l.granted) return true;
+  if (bytes >= l.refused) return false;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) { l.granted = bytes; return true; }
+  set_error("hipFuncSetAttribute: %zu bytes of dynamic LDS refused: %s", bytes, hipGetErrorString(hipGetLastError()));
+  l.refused = bytes;
+  return false;
 }
 
 void mfcc_plan_free(MfccPlan* p);  // mfcc.hip

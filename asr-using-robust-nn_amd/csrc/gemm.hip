@@ -16,8 +16,6 @@
 //   inference-mode input gradient, and the FGSM/PGD sign step (K4) on the last backward GEMM.
 #include "gemm.h"
 #include <cstdint>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -38,7 +36,7 @@ __device__ __forceinline__ bf16x8 to_bf16x8(const float (&v)[8]) {
 // that keeps it inside fp16's range) is split into two fp16 planes, hi = RNE(x) and lo = RNE(x - hi) (v_fma_mix: the subtraction
 // reads hi as fp16), and a product is hi hi + hi lo + lo hi accumulated in fp32: products of fp16 numbers are exact in fp32, what
 // is lost is the 2^-22 of the two-plane representation and the lo lo term -- the technique of the resampler and the block-DFT
-// STFT (mfcc.hip, stft_bdft.hip), with three v_mfma_f32_32x32x16_f16 of 32 cycles per 16-deep chunk in place of eight
+// STFT (resample.hip, stft_bdft.hip), with three v_mfma_f32_32x32x16_f16 of 32 cycles per 16-deep chunk in place of eight
 // v_mfma_f32_32x32x2_f32 of 64.  The low plane is ONE asm statement ending in s_nop 1 (a vector-ALU result needs two wait states
 // before a matrix instruction reads it, and the hazard recogniser does not look inside inline asm).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -1788,33 +1786,6 @@ __global__ __launch_bounds__(512 + 64 * kR2Loaders) void gemm_ring2_kernel(GemmA
 static GemmKnobs g_knobs;
 const GemmKnobs& gemm_knobs() { return g_knobs; }
 static long g_launch_count[2] = {0, 0};  // lipasr_debug_launch_count: 0 = launches on 128 x 64 exchange tiles, 1 = weight-gradient launches with 128 x 128 split-pass tiles
-
-// CUs of the current device, asked once per device (for launches whose caller leaves GemmArgs::cus at 0)
-static int device_cus() {
-  static int cached[16] = {};
-  int dev = 0; (void)hipGetDevice(&dev);
-  int& c = cached[dev & 15];
-  if (!c) { hipDeviceProp_t prop; c = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
-  return c;
-}
-
-// The one place that raises a kernel's dynamic LDS limit, once per (kernel, device).  false: the device refused the size (kept
-// too, so that a refused size is asked once).
-static bool ensure_dyn_lds(const void* fn, size_t bytes) {
-  if (bytes <= 48 * 1024) return true;
-  struct Limit { size_t granted = 0, refused = SIZE_MAX; };
-  static std::mutex mu;
-  static std::map<std::pair<const void*, int>, Limit> limits;
-  int dev = 0; (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lock(mu);
-  Limit& l = limits[{fn, dev}];
-  if (bytes <= l.granted) return true;
-  if (bytes >= l.refused) return false;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) { l.granted = bytes; return true; }
-  (void)hipGetLastError();
-  l.refused = bytes;
-  return false;
-}
 
 // Every instantiated GEMM kernel, indexed by what the templates are parameterised on; null = not instantiated.
 // arithmetic mode (GemmArgs::bf16: 0 exact fp32, 1 bf16 operands, 2 fp16 two-plane split) -> index

@@ -864,8 +864,7 @@ static int launch_chain(lipasr_ctx* h, const float* const* Ws, const int* rows, 
       a.rows_per_block = 128;
       const int blocks = (a.n_rows[n - 1] + a.rows_per_block - 1) / a.rows_per_block;
       const size_t lds = lds_f * sizeof(float);
-      if (lds > 48 * 1024)
-        LP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chain_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      LP_DYN_LDS(chain_head_kernel, lds);
       hipLaunchKernelGGL(chain_head_kernel, dim3(blocks), dim3(512), lds, st, a);
       LP_LAUNCH_CHECK();
       pin = cs->P[cur];
@@ -893,9 +892,7 @@ static int launch_chain(lipasr_ctx* h, const float* const* Ws, const int* rows, 
     const float* Wk = (m == 1) ? Ws[0] : Ws[k];
 #define LP_CHAIN(RM)                                                                                          \
   {                                                                                                           \
-    if (lds > 48 * 1024)                                                                                      \
-      LP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chain_step_kernel<RM>),                        \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
+    LP_DYN_LDS(chain_step_kernel<RM>, lds);                                                                   \
     hipLaunchKernelGGL(chain_step_kernel<RM>, dim3(blocks), dim3(256), lds, st, pin, p_mode, Wk, n_rows, n_in, R, \
                        cs->P[cur], emit, cs->gram);                                                           \
   }
@@ -1225,11 +1222,7 @@ int lipasr::project_product_bump(lipasr_handle_t h, float* const* Ws, const int*
     LayerPtrs lp;
     lp.n_layers = n_layers;
     for (int l = 0; l < n_layers; ++l) { lp.W[l] = Ws[l]; lp.rows[l] = rows[l]; lp.cols[l] = cols[l]; }
-    static bool attr_set_dev[16] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_set = attr_set_dev[attr_dev & 15];
-    if (lds > 32 * 1024 && !attr_set) {
-      LP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sigma_scale_layers_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      attr_set = true;
-    }
+    if (lds > 32 * 1024) LP_DYN_LDS(sigma_scale_layers_kernel, 96 * 1024);
     // Workgroups in proportion to the layers' sizes (every one recomputes sigma first -- fp64, the same arithmetic on the same inputs --
     // and they share the CUs' fp64 rate: 64 per layer = 384 took 23.9 us on a 128-CU share, 128 per layer 38.7, 32 per layer 26.6 because
     // layer 1's slice got long)

@@ -1,4 +1,5 @@
-// Shared by the STFT kernels of K1 (mfcc.hip: Stockham kernels; stft_bdft.hip: block-DFT kernel on the matrix pipe).
+// Shared by the STFT kernels of K1 (stft_bdft.hip: the default block-DFT kernel on the matrix pipe; stft_mel.hip and mfcc_fused.hip:
+// Stockham kernels; mfcc_vjp.hip: the backward pass).
 #pragma once
 #include "common.h"
 #include "mfcc_tables.h"
@@ -16,7 +17,7 @@ struct StftArgs {
   const int* mel_len;
   float* db;    // [B][n_frames][128]
   float* fmax;  // [B][n_frames]
-  int stage_mask;  // profiling only: bit0 skip the FFT passes, bit1 skip the mel reduction (results are wrong)
+  int stage_mask;  // StageMask bits (mfcc_plan.h)
   // clips of different lengths in one launch (stft_mel2_kernel, stft_bdft_kernel): samples per clip, or null; n_y / n_frames
   // above are then the longest clip's (the strides of y, db, fmax) and every clip uses its own
   const int* n_valid;
@@ -47,10 +48,14 @@ __device__ __forceinline__ int reflect_once(int j, int n) {
   return lo < n ? lo : 2 * (n - 1) - lo;
 }
 
-__device__ __forceinline__ void lds_barrier2() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): LDS traffic only (the kernel's global stores need no ordering)
+// Workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global access of the
+// wave (vmcnt(0)) -- inside the frame loop that would expose the dB stores of the previous pair (a round trip to L2) at
+// the next pair's first barrier, once per pair.
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
   __builtin_amdgcn_s_barrier();
 }
+__device__ __forceinline__ void lds_barrier2() { lds_barrier(); }  // (the name the dual-FFT, block-DFT and backward kernels use)
 
 // ---- LDS Stockham FFT of 2048 complex points (stft_mel_kernel, mfcc_fused_kernel, stft_vjp_kernel) ----
 // LDS holds complex points as float2; element e lives at e ^ ((e >> 4) & 7) (no padding).  Unit-stride
@@ -139,6 +144,47 @@ __device__ __forceinline__ void fft_pass(float2* __restrict__ buf, int Ns, int j
   const int j0 = (j - k) * R + k;
 #pragma unroll
   for (int r = 0; r < R; ++r) dst[padi(j0 + r * Ns)] = make_float2(v[r].re, v[r].im);
+  }
+}
+
+constexpr int kTPair = 1028;    // stride of the two float2 (frame 0, frame 1) weighted-power arrays, >= 1025 bins
+
+// one Stockham pass with the butterfly's twiddles already in registers (w[r-1] = w^r)
+template <int R>
+__device__ __forceinline__ void fft_pass_regs(float2* __restrict__ buf, int Ns, int j, const cpx (&w)[R - 1], const cpx* __restrict__ regs) {
+  constexpr int NR = 2048 / R;
+  cpx v[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (regs) {
+      v[r] = regs[r];
+    } else {
+      const float2 t = buf[padi(j + r * NR)];
+      v[r] = {t.x, t.y};
+    }
+  }
+  if (!regs) {  // LDS-only barrier (see lds_barrier above)
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_s_barrier();
+  }
+  if (Ns > 1) {
+#pragma unroll
+    for (int r = 1; r < R; ++r) v[r] = cmul(v[r], w[r - 1]);
+  }
+  butterfly(v);
+  const int k = j & (Ns - 1);
+  const int j0 = (j - k) * R + k;
+#pragma unroll
+  for (int r = 0; r < R; ++r) buf[padi(j0 + r * Ns)] = make_float2(v[r].re, v[r].im);
+}
+
+template <int R>
+__device__ __forceinline__ void load_tw(const float2* __restrict__ tw, int j, int Ns, cpx (&w)[R - 1]) {
+  const int tstep = (j & (Ns - 1)) * (2048 / (Ns * R));
+#pragma unroll
+  for (int r = 1; r < R; ++r) {
+    const float2 t = tw[(r * tstep) & 2047];
+    w[r - 1] = {t.x, t.y};
   }
 }
 

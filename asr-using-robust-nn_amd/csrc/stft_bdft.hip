@@ -330,7 +330,7 @@ __device__ __forceinline__ float bd_frame_finish(const BdftArgs& a, float* __res
   return mx;
 }
 
-// The optional fused epilogue: dct_kernel's arithmetic, instruction for instruction (mfcc.hip), on this workgroup's own dB tile:
+// The optional fused epilogue: dct_kernel's arithmetic, instruction for instruction (stft_mel.hip), on this workgroup's own dB tile:
 // top_db floor against the clip maximum, DCT-II as a 32 x 32 x 128 contraction per wavefront on v_mfma_f32_32x32x2_f32
 // (wavefronts 0 and 1: 32 frames each), optional affine in fp64.  The tile comes back from L2 (this workgroup stored it); the
 // ring is free by now and holds the transposed image.  NT = threads of the workgroup; red: one float per wavefront.
@@ -617,13 +617,7 @@ int launch_stft_bdft(const StftArgs& st, const BdftTables& t, int batch, int seg
   seg_frames = std::max(4, (seg_frames + 3) & ~3);
   a.seg_frames = seg_frames;
   const size_t lds = (size_t)kBdLdsFloats * sizeof(float);
-  static bool attr_set_dev[16] = {};  // per device, as the GEMM launchers do (round 4 set the attribute on every launch: ADVICE r4)
-  int attr_dev = 0;
-  (void)hipGetDevice(&attr_dev);
-  if (!attr_set_dev[attr_dev & 15]) {
-    LP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_bdft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set_dev[attr_dev & 15] = true;
-  }
+  LP_DYN_LDS(stft_bdft_kernel, lds);
   hipLaunchKernelGGL(stft_bdft_kernel, dim3((st.n_frames + seg_frames - 1) / seg_frames, batch), dim3(256), lds, stream, a);
   LP_LAUNCH_CHECK();
   return LIPASR_OK;

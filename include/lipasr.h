@@ -482,16 +482,33 @@ int lipasr_mfcc_profile_begin(lipasr_handle_t h, int max_calls);
 int lipasr_mfcc_profile_end(lipasr_handle_t h, float* avg_ms3, int* n_calls);
 int lipasr_mfcc_plan_profile_begin(lipasr_mfcc_t p, int max_calls);
 int lipasr_mfcc_plan_profile_end(lipasr_mfcc_t p, float* avg_ms3, int* n_calls);
-/* knobs of one plan: keys 0 and 1 as lipasr_debug_set; key 2: value != 0 makes the plan run the fused resample -> STFT
- * kernel for every batch (1.7x the algorithmic HBM bytes instead of 4.6x, but about 1.7x the time of the three-kernel path
- * on a whole MI355X: DESIGN.md section 3); by default the fused kernel runs only where the three-kernel path cannot read
- * the input (int16 or per-clip lengths in rows that are not a multiple of 4 samples long).
- * Stage-mask bits of key 0 (2048/512 plans): 256 = the Stockham FFT kernel (stft_mel2_kernel) instead of the block-DFT
- * kernel on the matrix pipe (stft_bdft_kernel, the default since round 4): its parity reference; 64 = the round-2 kernel.
+/* Knobs of one plan.
+ * key 0: the stage mask, for profiling and A/B runs (0 = the default path everywhere).  Every bit:
+ *       1  stft_mel_kernel skips its FFT passes          (wrong results: times the remaining stages)
+ *       2  stft_mel_kernel skips the mel reduction       (wrong results)
+ *       4  the VALU resamplers (resample_reg128_kernel / resample_generic_kernel) instead of any MFMA resampler
+ *       8  resample_mfma_kernel skips its MFMA chain     (wrong results)
+ *      16  the fp32 resamplers instead of the fp16-plane one: its parity reference.  Rows that cannot be read as float4 go to
+ *          resample_mfma_kernel, where the same bit skips the LDS fill (wrong results); aligned rows never reach that kernel
+ *      64  the round-2 STFT kernel (stft_mel_kernel, two frames per workgroup); no per-clip lengths then
+ *     128  never the fused resample -> STFT kernel: always resample, STFT, DCT with the resampled signal in HBM
+ *     256  on the three-kernel path: the Stockham FFT kernel (stft_mel2_kernel) instead of the block-DFT kernel on the
+ *          matrix pipe (stft_bdft_kernel, the default): its parity reference.  Inside the fused kernel: stop before the
+ *          frames (wrong results).  An extraction runs one of the two paths, so the two meanings never meet.
+ *     512  the fused kernel skips the resampling          (wrong results)
+ *   65536, 131072, 262144 (bits 16-18)  resample_persist_h2_kernel skips its MFMA chain / its stores / the prefetch of the
+ *          next window                                    (wrong results)
+ *   Bits 1, 2 and 64 also select stft_mel_kernel; the other bits are unused.
+ * key 1: number of workgroups the persistent resampler aims for = the CUs its stream may use (default 256; a pipeline
+ *   that runs the MFCC on a CU-masked stream sets it to the size of the mask).
+ * key 2: value != 0 makes the plan run the fused resample -> STFT kernel for every batch (1.7x the algorithmic HBM bytes
+ *   instead of 4.6x, but about 1.7x the time of the three-kernel path on a whole MI355X: DESIGN.md section 3); by default
+ *   the fused kernel runs only where the three-kernel path cannot read the input (int16 or per-clip lengths in rows that
+ *   are not a multiple of 4 samples long).
  * key 3: frames per workgroup of the block-DFT kernel (a multiple of 4 in [4, 4096]; default 44 = one workgroup per 1-s clip).
  * key 4: value != 0 lets that kernel apply the top_db floor and the DCT itself when one workgroup covers a whole clip
- * (<= 64 frames, utterance_length <= 64): no dct_kernel launch, bit-identical features; off by default (slower on batches
- * that are not cache-warm: DESIGN.md section 3).
+ *   (<= 64 frames, utterance_length <= 64): no dct_kernel launch, bit-identical features; off by default (slower on batches
+ *   that are not cache-warm: DESIGN.md section 3).
  * Replaces the arithmetic of librosa.feature.mfcc's STFT, extract_features_construct_dataset.py:30. */
 int lipasr_mfcc_plan_set(lipasr_mfcc_t p, int key, int value);
 
@@ -502,12 +519,8 @@ int lipasr_mfcc_plan_set(lipasr_mfcc_t p, int key, int value);
 int lipasr_add_noise_f32(lipasr_handle_t h, float* y, int batch, int n, int mode, float p0, float p1,
                          uint64_t seed, lipasr_stream_t stream);
 
-/* Knobs of the handle's default MFCC plan.  key 0: stage mask for profiling (bit0 skip the FFT passes, bit1 skip the mel
- * reduction -- both give wrong results and exist to time the remaining stages; bit2 selects the VALU resampler instead of
- * the MFMA one; bit7 (128) selects the three-kernel path -- resample, STFT, DCT with the resampled signal in HBM -- instead
- * of the fused resample -> STFT kernel: the parity reference of the fused kernel).
- * key 1: number of workgroups the persistent resampler aims for = the CUs its stream may use (default 256; a
- * pipeline that runs the MFCC on a CU-masked stream sets it to the size of the mask).  Kept in the handle. */
+/* Knobs of the handle's default MFCC plan: keys 0 (the stage mask; its bits are listed at lipasr_mfcc_plan_set), 1 and 2 of
+ * lipasr_mfcc_plan_set.  The value of key 1 is kept in the handle: a later lipasr_mfcc_plan inherits it. */
 int lipasr_debug_set(lipasr_handle_t h, int key, int value);
 
 /* Profiling knob: GEMM kernel choice. bits 0-1: 0 = automatic, 1 = split-K register kernel only, 2 = LDS-tiled kernel

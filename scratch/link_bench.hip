@@ -22,6 +22,14 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
+// stand-ins for core.hip's (which brings the whole handle along): one device, the limit raised on every call
+bool ensure_dyn_lds(const void* fn, size_t bytes) {
+  return bytes <= 48 * 1024 || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+int device_cus() {
+  hipDeviceProp_t prop;
+  return hipGetDeviceProperties(&prop, 0) == hipSuccess ? prop.multiProcessorCount : 256;
+}
 }  // namespace lipasr
 
 #define CK(x)                                                                         \

@@ -1,4 +1,4 @@
-"""NumPy model of the block-DFT STFT kernel (csrc/mfcc.hip: stft_bdft_kernel) -- the arithmetic, stage by stage, with the
+"""NumPy model of the block-DFT STFT kernel (csrc/stft_bdft.hip: stft_bdft_kernel) -- the arithmetic, stage by stage, with the
 fp16 two-plane split emulated, against the float64 oracle.  Not a test: a design tool (error budget per stage).
 
   frame spectrum  X_f[k] = sum_{b<4} (-i)^(b k) B_{f+b}[k],   B_j[k] = sum_{m<512} ypad[512 j + m] e^(-2 pi i m k / 2048)

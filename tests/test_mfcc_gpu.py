@@ -316,10 +316,14 @@ def test_ragged_and_int16_unsupported_plans_say_so(cuda):
     assert not ex.fused
     w = torch.zeros(2, 4410, device="cuda")
     ex(w)
-    with pytest.raises(Exception):
+    import lipasr._native as N
+
+    with pytest.raises(N.LipasrError) as e:
         ex(w, n_valid=torch.full((2,), 4000, dtype=torch.int32, device="cuda"))
-    with pytest.raises(Exception):
+    assert e.value.code == N.EUNSUPPORTED
+    with pytest.raises(N.LipasrError) as e:
         ex(torch.zeros(2, 4410, dtype=torch.int16, device="cuda"))
+    assert e.value.code == N.EUNSUPPORTED
 
 
 def test_two_extractors_do_not_share_state(cuda):
@@ -368,6 +372,25 @@ def test_fp16_plane_resampler_against_fp32_kernel_and_oracle(cuda):
         assert e_f32.max() < 2e-6 and e_h2.max() < 2e-6
         assert e_h2[6:].max() < 2e-9          # relative, not absolute: a clip at -60 dB is as accurate as a loud one
         assert np.abs(y_h2 - y_f32).max() < 2e-6
+
+
+def test_mfma_and_reg128_resamplers_against_oracle(cuda):
+    """The two 16 kHz resampler variants no other test reaches, on full-scale uniform noise against the float64 oracle, to the
+    2e-6 absolute error the other fp32 resamplers are held to: resample_mfma_kernel (the default choice for rows that cannot be
+    read as float4: 1602 samples) and resample_reg128_kernel (stage-mask bit 2 = 4, rows of 1600)."""
+    from lipasr.extract_features_construct_dataset import MfccExtractor
+
+    rng = np.random.default_rng(11)
+    for n, mask, name in ((1602, 0, "resample_mfma_kernel"), (1600, 4, "resample_reg128_kernel")):
+        clips = rng.uniform(-1.0, 1.0, (3, n)).astype(np.float32)
+        ex = MfccExtractor(16000, n, 3)
+        ex.set(0, mask)
+        y = ex.resample(dev(clips)).cpu().numpy()
+        ex.close()
+        ref = np.stack([M.librosa_load_resample(c, 16000) for c in clips])
+        err = np.abs(y - ref).max()
+        print(f"\n{name}: rows of {n}, max|err| vs float64 oracle {err:.2e}")
+        assert y.shape == ref.shape and err < 2e-6, (name, err)
 
 
 # ------------------------------------------------------------------ round 4: block-DFT STFT kernel on the matrix pipe
