@@ -5,7 +5,7 @@
 //   2. stft_bdft_kernel (stft_bdft.hip)           reflect-padded Hann frames -> block-DFT on the matrix pipe -> power -> mel -> dB
 //   3. dct_kernel (stft_mel.hip)                  top_db floor, DCT-II 128 -> 20, layout, optional StandardScaler affine
 // Every other variant (fp32 / VALU resamplers, Stockham and short-window STFTs, the fused resample -> STFT kernel of
-// mfcc_fused.hip) is chosen in ONE place, pick_mfcc_path below; plan_run, plan_resample, plan_from_22k and plan_vjp ask it once
+// mfcc_fused.hip) is chosen in ONE place, pick_mfcc_path below; plan_run, plan_resample, plan_from_22k, plan_vjp and their per-clip-length forms ask it once
 // and hand the kinds to the launchers of mfcc_plan.h.  This file holds no stage kernel except add_noise_kernel.
 #include "mfcc_plan.h"
 #include <memory>
@@ -396,13 +396,24 @@ static int resample_vjp_prepare(MfccPlan* p) {
   return LIPASR_OK;
 }
 
-static int plan_resample_vjp(MfccPlan* p, const float* gy, int batch, float* gx, hipStream_t st) {
+static int plan_resample_vjp(MfccPlan* p, const float* gy, int batch, float* gx, hipStream_t st, const int* nv = nullptr) {
   int rc = resample_vjp_prepare(p);
   if (rc != LIPASR_OK) return rc;
   ResampleVjpArgs a;
   a.n_y = p->n_y; a.n_valid = p->n_valid; a.n_samp = p->n_samp; a.up = p->up; a.down = p->down; a.identity = p->identity;
   a.ht = p->d_rt_taps; a.t0 = p->d_rt_t0; a.nt = p->rt_nt; a.t0min = p->rt_t0min; a.t0max = p->rt_t0max;
+  a.nv = nv; a.sr_in = p->sr_in;
   return launch_resample_vjp(a, gy, gx, batch, st);
+}
+
+static void fill_vjp_args(const MfccPlan* p, const float* y, int batch, int L, const double* as, const float* g_feat, float* gy,
+                          MfccVjpArgs* a) {
+  a->y = y; a->n_y = p->n_y; a->n_frames = p->n_frames; a->batch = batch; a->L = L;
+  a->db = p->d_db; a->fmax = p->d_fmax; a->g_feat = g_feat; a->aff_scale = as; a->dct_rows = p->d_dct_rows;
+  a->hann = p->d_hann; a->tw = reinterpret_cast<const float2*>(p->d_tw);
+  a->mel_wlo = p->d_mel_wlo; a->mel_whi = p->d_mel_whi; a->bin_run = p->d_bin_run;
+  a->gmel = p->d_gmel; a->part = p->d_part; a->n_groups = p->vj_groups;
+  a->gy = gy;
 }
 
 static int plan_vjp(MfccPlan* p, const float* sig, int domain, int batch, int L, const double* as, const float* g_feat, float* g_sig,
@@ -428,14 +439,88 @@ static int plan_vjp(MfccPlan* p, const float* sig, int domain, int batch, int L,
   }
   if (!reuse && (rc = launch_from_22k(p, path.stft, y, nullptr, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
   MfccVjpArgs a;
-  a.y = y; a.n_y = p->n_y; a.n_frames = p->n_frames; a.batch = batch; a.L = L;
-  a.db = p->d_db; a.fmax = p->d_fmax; a.g_feat = g_feat; a.aff_scale = as; a.dct_rows = p->d_dct_rows;
-  a.hann = p->d_hann; a.tw = reinterpret_cast<const float2*>(p->d_tw);
-  a.mel_wlo = p->d_mel_wlo; a.mel_whi = p->d_mel_whi; a.bin_run = p->d_bin_run;
-  a.gmel = p->d_gmel; a.part = p->d_part; a.n_groups = p->vj_groups;
-  a.gy = domain == 0 ? p->d_gy : g_sig;
+  fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
   if ((rc = launch_mfcc_vjp(a, st)) != LIPASR_OK) return rc;
   if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st);
+  return LIPASR_OK;
+}
+
+// ---- clips of different lengths in one launch: n_valid[] (device) holds each row's samples at the plan's input rate ----
+// the plans whose three-kernel forward takes per-clip lengths (pick_mfcc_path): 2048/512 at 16 kHz or 8 kHz, rows of 4 k samples
+static int ragged_unsupported(const char* fn, const MfccPlan* p) {
+  if (!(resample_h2_ok(p, nullptr, 0) && stft2_ok(p))) {
+    set_error("%s: per-clip lengths need a 2048/512 plan at 16 kHz or 8 kHz with rows a multiple of 4 samples; this plan is %d Hz, "
+              "n_fft %d, rows of %d", fn, p->sr_in, p->n_fft, p->n_samp);
+    return LIPASR_EUNSUPPORTED;
+  }
+  return LIPASR_OK;
+}
+
+static int plan_resample_ragged(MfccPlan* p, const void* wav, int fmt, const int* nv, int batch, float* y, hipStream_t st) {
+  LP_CHECK_ARG(wav && nv && y, "lipasr_mfcc_plan_resample_ragged: null argument");
+  LP_CHECK_ARG(fmt == 0 || fmt == 1, "lipasr_mfcc_plan_resample_ragged: sample format %d (0 = float32, 1 = int16 PCM)", fmt);
+  const MfccPath path = pick_mfcc_path(p, wav, fmt, true);
+  if (path.rc != LIPASR_OK) return path.rc;
+  if (path.fused) {
+    set_error("lipasr_mfcc_plan_resample_ragged: this plan runs the fused resample -> STFT kernel for this input (rows of %d samples, "
+              "alignment, or plan key 2): it has no resampled signal to return", p->n_samp);
+    return LIPASR_EUNSUPPORTED;
+  }
+  int rc = launch_resample(p, path.resampler, wav, fmt, nv, batch, y, st);
+  if (rc != LIPASR_OK) return rc;
+  return launch_clear_tail(p, nv, batch, y, st);
+}
+
+static int plan_from_22k_ragged(MfccPlan* p, const float* y, const int* nv, int batch, int L, const double* am, const double* as,
+                                float* out, hipStream_t st) {
+  LP_CHECK_ARG(y && nv && out, "lipasr_mfcc_plan_from_22k_ragged: null argument");
+  LP_CHECK_ARG((am == nullptr) == (as == nullptr), "lipasr_mfcc_plan_from_22k_ragged: give both affine arrays or neither");
+  const MfccPath path = pick_mfcc_path(p, nullptr, 0, true);
+  if (!stft2_ok(p)) {
+    set_error("lipasr_mfcc_plan_from_22k_ragged: per-clip lengths need the 2048/512 kernels (n_fft %d, hop %d, stage mask %d)", p->n_fft,
+              p->hop, p->stage_mask);
+    return LIPASR_EUNSUPPORTED;
+  }
+  return launch_from_22k(p, path.stft, y, nv, batch, L, am, as, out, st);
+}
+
+static int plan_vjp_ragged(MfccPlan* p, const void* sig, int fmt, const int* nv, int domain, int batch, int L, const double* as,
+                           const float* g_feat, float* g_sig, int flags, hipStream_t st) {
+  static const char* fn = "lipasr_mfcc_plan_vjp_ragged";
+  LP_CHECK_ARG(sig && nv && g_feat && g_sig, "%s: null argument", fn);
+  LP_CHECK_ARG(fmt == 0 || fmt == 1, "%s: sample format %d (0 = float32, 1 = int16 PCM)", fn, fmt);
+  LP_CHECK_ARG(domain == 0 || domain == 1, "%s: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", fn, domain);
+  LP_CHECK_ARG((flags & ~1) == 0, "%s: unknown flag bits %d", fn, flags);
+  if (p->dft) {
+    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d", fn, p->n_fft, p->hop);
+    return LIPASR_EUNSUPPORTED;
+  }
+  if (fmt == 1 && domain == 1) {
+    set_error("%s: int16 PCM rows are rows at the plan's input rate (domain 0); the 22 050 Hz signal is float32", fn);
+    return LIPASR_EUNSUPPORTED;
+  }
+  int rc = ragged_unsupported(fn, p);
+  if (rc != LIPASR_OK) return rc;
+  const MfccPath path = pick_mfcc_path(p, domain == 0 ? sig : nullptr, fmt, true);
+  if (path.rc != LIPASR_OK) return path.rc;
+  if (domain == 0 && path.fused) {
+    set_error("%s: this plan runs the fused resample -> STFT kernel for this input (row alignment, or plan key 2), which leaves no "
+              "resampled signal behind for the backward pass", fn);
+    return LIPASR_EUNSUPPORTED;
+  }
+  if ((rc = vjp_prepare(p)) != LIPASR_OK) return rc;
+  // the caller's forward (lipasr_mfcc_extract with n_valid / lipasr_mfcc_plan_from_22k_ragged) left the plan's intermediates
+  const bool reuse = (flags & 1) && !(p->stage_mask & (SM_SKIP_FFT | SM_SKIP_MEL));
+  const float* y = static_cast<const float*>(sig);
+  if (domain == 0) {
+    if (!reuse && (rc = launch_resample(p, path.resampler, sig, fmt, nv, batch, p->d_y, st)) != LIPASR_OK) return rc;
+    y = p->d_y;
+  }
+  if (!reuse && (rc = launch_from_22k(p, path.stft, y, nv, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
+  MfccVjpArgs a;
+  fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
+  if ((rc = launch_mfcc_vjp(a, st, nv, p->sr_in, p->n_samp)) != LIPASR_OK) return rc;
+  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st, nv);
   return LIPASR_OK;
 }
 
@@ -546,6 +631,28 @@ int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batc
   int rc = plan_check("lipasr_mfcc_plan_vjp", p, batch, utterance_length);
   if (rc != LIPASR_OK) return rc;
   return plan_vjp(p, sig, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+}
+
+int lipasr_mfcc_plan_vjp_ragged(lipasr_mfcc_t p, const void* sig, int sample_format, const int* n_valid, int domain, int batch,
+                                int utterance_length, const double* affine_scale, const float* g_feat, float* g_sig, int flags,
+                                lipasr_stream_t stream) {
+  int rc = plan_check("lipasr_mfcc_plan_vjp_ragged", p, batch, utterance_length);
+  if (rc != LIPASR_OK) return rc;
+  return plan_vjp_ragged(p, sig, sample_format, n_valid, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+}
+
+int lipasr_mfcc_plan_resample_ragged(lipasr_mfcc_t p, const void* wav, int sample_format, const int* n_valid, int batch, float* y,
+                                     lipasr_stream_t stream) {
+  int rc = plan_check("lipasr_mfcc_plan_resample_ragged", p, batch, 1);
+  if (rc != LIPASR_OK) return rc;
+  return plan_resample_ragged(p, wav, sample_format, n_valid, batch, y, S(stream));
+}
+
+int lipasr_mfcc_plan_from_22k_ragged(lipasr_mfcc_t p, const float* y, const int* n_valid, int batch, int utterance_length,
+                                     const double* affine_mean, const double* affine_scale, float* out, lipasr_stream_t stream) {
+  int rc = plan_check("lipasr_mfcc_plan_from_22k_ragged", p, batch, utterance_length);
+  if (rc != LIPASR_OK) return rc;
+  return plan_from_22k_ragged(p, y, n_valid, batch, utterance_length, affine_mean, affine_scale, out, S(stream));
 }
 
 int lipasr_mfcc_plan_resample_vjp(lipasr_mfcc_t p, const float* g_y, int batch, float* g_wav, lipasr_stream_t stream) {

@@ -127,6 +127,8 @@ bool build_band_tables(const tables::Polyphase& pp, std::vector<float>* hb_out, 
 std::vector<unsigned int> build_band_h2(const std::vector<float>& hb, const std::vector<int>& lo);
 int launch_resample(const MfccPlan* p, MfccPath::Resampler kind, const void* wav, int fmt, const int* n_valid, int batch, float* y,
                     hipStream_t st);
+// zeros from each clip's int(n ratio) to the end of its row of y (what the resamplers leave there with per-clip lengths is ringing)
+int launch_clear_tail(const MfccPlan* p, const int* n_valid, int batch, float* y, hipStream_t st);
 // stft_mel.hip.  launch_from_22k: STFT + mel + dB by `kind`, then the DCT; mid is recorded between the two; stft_only stops
 // after the dB tile and the frame maxima (the backward pass re-running the forward; nothing is written to out)
 std::vector<float> dct_fragments();

@@ -461,6 +461,21 @@ __global__ __launch_bounds__(256) void copy_pad_kernel(const float* __restrict__
     y[(size_t)u * n_y + i] = i < n_samp ? x[(size_t)u * n_samp + i] : 0.0f;
 }
 
+// With per-clip lengths the resamplers leave the filter's ringing past a clip's int(n ratio) outputs (the STFT kernels, which
+// know the length, read zeros there themselves).  A caller that takes the resampled rows gets fix_length's zeros instead.
+__global__ __launch_bounds__(256) void clear_tail_kernel(float* __restrict__ y, int n_y, const int* __restrict__ nv, int n_samp, int sr_in) {
+  const int u = blockIdx.y;
+  int n_vy, c_y, c_frames;
+  clip_lengths(min(max(nv[u], 0), n_samp), sr_in, &n_vy, &c_y, &c_frames);
+  for (int i = n_vy + blockIdx.x * 256 + threadIdx.x; i < n_y; i += gridDim.x * 256) y[(size_t)u * n_y + i] = 0.0f;
+}
+
+int launch_clear_tail(const MfccPlan* p, const int* n_valid, int batch, float* y, hipStream_t st) {
+  hipLaunchKernelGGL(clear_tail_kernel, dim3(32, batch), dim3(256), 0, st, y, p->n_y, n_valid, p->n_samp, p->sr_in);
+  LP_LAUNCH_CHECK();
+  return LIPASR_OK;
+}
+
 // Banded taps [n_tiles][kRsBand][32] and first-phase offsets [n_tiles] for the MFMA resampler; false when the
 // ratio does not fit its fixed geometry (128 taps, band <= 152 samples, LDS row of 801 floats).
 bool build_band_tables(const Polyphase& pp, std::vector<float>* hb_out, std::vector<int>* lo_out) {

@@ -233,7 +233,15 @@ struct MfccVjpArgs {
   int n_groups;
   float* gy;               // [batch][n_y] out
 };
-int launch_mfcc_vjp(const MfccVjpArgs& a, hipStream_t st);
+// clips of different lengths in one launch (the RAGGED kernel instances): n_y / n_frames / n_groups above are then the row
+// strides and every clip uses its own lengths (clip_lengths), as the forward does.  A type of its own, so that the kernels
+// for one length keep the argument block they had.
+struct MfccVjpRaggedArgs : MfccVjpArgs {
+  const int* n_valid;      // [batch] samples per clip at sr_in
+  int sr_in, n_samp_max;
+};
+// n_valid: null = one length for all
+int launch_mfcc_vjp(const MfccVjpArgs& a, hipStream_t st, const int* n_valid = nullptr, int sr_in = 0, int n_samp_max = 0);
 // gx = R^T gy for the polyphase resampler y[up q + p] = sum_k H[p][k] x[down q + noff[p] - (left - 1) + k], t < n_valid, in its own
 // polyphase form gx[down q' + r] = sum_i HT[i][r] gy[up q' + t0[r] + i] (tables built by the plan, see resample_vjp_kernel)
 struct ResampleVjpArgs {
@@ -242,6 +250,8 @@ struct ResampleVjpArgs {
   const float* ht = nullptr;  // [nt][down]
   const int* t0 = nullptr;    // [down]
   int nt = 0, t0min = 0, t0max = 0;
+  const int* nv = nullptr;    // [batch] samples per clip (device) or null: the RAGGED instance cuts every clip at its own length
+  int sr_in = 0;
 };
 int launch_resample_vjp(const ResampleVjpArgs& a, const float* gy, float* gx, int batch, hipStream_t st);
 

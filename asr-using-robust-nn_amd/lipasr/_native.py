@@ -118,6 +118,9 @@ PROTOTYPES = {
     "lipasr_mfcc_plan_from_22k": (i32, [c_h, c_f, i32, i32, i32, c_f, c_f, c_f, c_s]),
     "lipasr_mfcc_plan_vjp": (i32, [c_h, c_f, i32, i32, i32, c_f, c_f, c_f, i32, c_s]),
     "lipasr_mfcc_plan_resample_vjp": (i32, [c_h, c_f, i32, c_f, c_s]),
+    "lipasr_mfcc_plan_vjp_ragged": (i32, [c_h, c_f, i32, c_f, i32, i32, i32, c_f, c_f, c_f, i32, c_s]),
+    "lipasr_mfcc_plan_resample_ragged": (i32, [c_h, c_f, i32, c_f, i32, c_f, c_s]),
+    "lipasr_mfcc_plan_from_22k_ragged": (i32, [c_h, c_f, c_f, i32, i32, c_f, c_f, c_f, c_s]),
     "lipasr_mfcc_plan_profile_begin": (i32, [c_h, i32]),
     "lipasr_mfcc_plan_profile_end": (i32, [c_h, C.POINTER(f32), PI]),
     "lipasr_mfcc_plan_set": (i32, [c_h, i32, i32]),

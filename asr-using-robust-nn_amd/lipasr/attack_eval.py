@@ -81,6 +81,14 @@ def black_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
     return _sweep(models, list(grid)[:points], make, test_labels, "black-box attack")
 
 
+def _padded_rows(items, n_pad, lens):
+    """[(file index, samples)] -> (float32 device tensor [len(items), n_pad], zero-padded rows; int32 device lengths)."""
+    w = np.zeros((len(items), n_pad), dtype=np.float32)
+    for r, (_, x) in enumerate(items):
+        w[r, :len(x)] = x
+    return A._to_dev(w), torch.as_tensor(lens).to(A._dev())
+
+
 def _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels, kind, standardize, test_filenames, domain, grid,
                            points, limit, attack_kw):
     """FGSM / PGD over the audio of ``test_filenames``; see white_box_sweep."""
@@ -94,25 +102,60 @@ def _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels,
     labels = test_labels[:limit] if limit else test_labels
     if standardize == "before":
         train_data, val_data, _ = A.standardize_dataset(train_data, val_data, test_data)
-    # the statistics black_box_sweep(over="audio") uses at sigma = 0: those of (train, val, the files' clean MFCCs)
-    clean = A.black_box_attack_on_audio_dataset(test_filenames, 0, p=0, alpha=0)
-    sc = A.StandardScaler().fit(np.concatenate([np.asarray(train_data), np.asarray(val_data), clean]))
     n_classes = labels.shape[1]
     grid = list(AUDIO_SIGMAS if grid is None else grid)[:points]
     groups = A._files_to_batches(test_filenames)
+    # A rate whose files differ in length goes through ONE extractor and one WaveformClassifier per model, the clips side by
+    # side with lengths= (16 kHz and 8 kHz: the rates whose plans take per-clip lengths); rows are padded to the longest clip
+    # rounded up to a multiple of 4000 samples, compute_mfcc_all_files' rule, so that the plans are the ones extraction made.
+    # A rate with one length, and every other rate, keeps one group per (rate, length).
+    n_lengths = {}
+    for (sr, n) in groups:
+        n_lengths[sr] = n_lengths.get(sr, 0) + 1
+    ragged = {}  # sr -> [(file index, samples)] in file order
+    for (sr, n), items in groups.items():
+        if sr in (16000, 8000) and n_lengths[sr] > 1:
+            ragged.setdefault(sr, []).extend(items)
+    work = [(sr, n, items, None) for (sr, n), items in groups.items() if sr not in ragged]
+    bmax = min(m._max_batch for m in models.values()) if models else 1
+    for sr, items in ragged.items():
+        items.sort(key=lambda it: it[0])
+        lens = np.array([len(x) for _, x in items], dtype=np.int32)
+        n_pad = -(-int(lens.max()) // 4000) * 4000
+        work.append((sr, n_pad, items, lens))
+    # the statistics black_box_sweep(over="audio") uses at sigma = 0: those of (train, val, the files' clean MFCCs)
+    if not ragged:
+        clean = A.black_box_attack_on_audio_dataset(test_filenames, 0, p=0, alpha=0)
+    else:
+        clean = np.zeros((len(test_filenames), 20 * 44))
+        for sr, n, items, lens in work:
+            idx = [i for i, _ in items]
+            if lens is None:
+                clean[idx] = A.noisy_audio_to_mfcc(np.stack([x for _, x in items]), sr).cpu().numpy()
+                continue
+            w, lt = _padded_rows(items, n, lens)
+            ex = A._extractor(int(sr), int(n), min(w.shape[0], bmax))
+            clean[idx] = torch.cat([ex(w[s:s + ex.batch_max], 44, n_valid=lt[s:s + ex.batch_max])
+                                    for s in range(0, w.shape[0], ex.batch_max)]).cpu().numpy()
+    sc = A.StandardScaler().fit(np.concatenate([np.asarray(train_data), np.asarray(val_data), clean]))
     acc = {name: [] for name in models}
     for item in grid:
         for name, model in models.items():
             pred = np.zeros((len(test_filenames), n_classes))
-            for (sr, n), items in groups.items():
-                w = A._to_dev(np.stack([x for _, x in items]))
-                ex = A._extractor(int(sr), int(n), min(w.shape[0], model._max_batch))
+            for sr, n, items, lens in work:
+                if lens is None:
+                    w, lt = A._to_dev(np.stack([x for _, x in items])), None
+                    ex = A._extractor(int(sr), int(n), min(w.shape[0], model._max_batch))
+                else:
+                    w, lt = _padded_rows(items, n, lens)
+                    ex = A._extractor(int(sr), int(n), min(w.shape[0], bmax))
+                cut = lambda s: None if lt is None else lt[s:s + ex.batch_max]
                 clf = A.WaveformClassifier(model, n_classes, extractor=ex, mean=sc.mean_, scale=sc.scale_, domain=domain)
-                x = torch.cat([ex.resample(w[s:s + ex.batch_max]) for s in range(0, w.shape[0], ex.batch_max)]) if domain == "22k" else w
+                x = torch.cat([ex.resample(w[s:s + ex.batch_max], n_valid=cut(s)) for s in range(0, w.shape[0], ex.batch_max)]) if domain == "22k" else w
                 idx = [i for i, _ in items]
                 cls = A.FastGradientMethod if kind == "fgsm" else A.ProjectedGradientDescent
-                adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x, None) if item != 0 else x
-                pred[idx] = clf.predict_device(adv).cpu().numpy()
+                adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x, None, lengths=lt) if item != 0 else x
+                pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
             a = accuracy(pred, labels)
             acc[name].append(a)
             print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")

@@ -8,7 +8,9 @@ backward to the input and the sign step fused into the last backward GEMM's epil
 ``norm`` (1, 2), ``targeted`` and ``num_random_init`` keywords run the same call in its Lp form
 (lipasr_mlp_attack_step_lp: the step is a second launch) and a native random start (lipasr_lp_ball_init).
 ``WaveformClassifier`` puts the MFCC stage in front of the model: the same two attacks then perturb the AUDIO (eps in
-amplitude units), the gradient reaching the samples through the native backward pass of K1 (lipasr_mfcc_plan_vjp).
+amplitude units), the gradient reaching the samples through the native backward pass of K1 (lipasr_mfcc_plan_vjp).  With
+``lengths=`` a batch holds clips of different lengths, one per row (lipasr_mfcc_plan_vjp_ragged): the perturbation stays inside
+each clip and the rest of the row comes back untouched.
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.
@@ -137,7 +139,11 @@ class WaveformClassifier:
     domain="22k" (default): the input is the 22 050 Hz signal [B, extractor.n_y], what the reference's audio noise attacks
     perturb (librosa.load's output, attacks.py:108-114), so that black-box and white-box audio curves share an amplitude axis;
     domain="input": the file's samples [B, n_samp] at ``sr_in``.  ``mean`` / ``scale``: [20 * utterance_length] statistics
-    fused into the extraction (both or neither).  ``clip_values``: the attacks clamp their iterates to it."""
+    fused into the extraction (both or neither).  ``clip_values``: the attacks clamp their iterates to it.
+    ``lengths`` (features_device, predict*, loss_gradient*): int32 device tensor or array [B], the samples of each row that belong
+    to its clip, counted at ``sr_in`` for EITHER domain (a 22 050 Hz row holds its clip in its first ceil(n * 22050 / sr_in)
+    positions): clips of different lengths in one batch, each treated as if it were alone; the rest of a row is ignored and its
+    gradient is exactly 0.  None: every row is a whole clip, and every call is the one made without the keyword."""
 
     def __init__(self, model, nb_classes, extractor=None, sr_in=16000, n_samp=16000, utterance_length=44, mean=None, scale=None,
                  domain="22k", clip_values=(-1.0, 1.0)):
@@ -166,35 +172,63 @@ class WaveformClassifier:
         if xt.dim() != 2 or xt.shape[1] != self.n:
             raise ValueError(f"waveforms must be [B, {self.n}] for domain {self.domain!r}, got {tuple(xt.shape)}")
 
-    def features_device(self, xt):
-        """[B <= batch_max, n] device tensor -> standardised features [B, 20 * utterance_length]."""
-        if self.domain == "22k":
-            return self.extractor.from_22k(xt, self.utterance_length, self.mean, self.scale)
-        return self.extractor(xt, self.utterance_length, self.mean, self.scale)
+    def lengths_device(self, lengths, b):
+        """``lengths`` as the int32 device tensor [b] the extractor takes (None stays None)."""
+        if lengths is None:
+            return None
+        t = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths).astype(np.int32))
+        t = t.to(device=self.extractor.device, dtype=torch.int32).contiguous()
+        if tuple(t.shape) != (b,):
+            raise ValueError(f"lengths must hold one sample count per row ([{b}]), got {tuple(t.shape)}")
+        return t
 
-    def predict_device(self, xt, logits=False):
+    def clip_mask(self, lt):
+        """bool [B, n]: the positions of each row inside its clip -- [0, n) samples (domain "input"), or the [0, ceil(n * 22050 /
+        sr_in)) positions the kernels derive from it (domain "22k", the same float64 expression as clip_lengths)."""
+        ex = self.extractor
+        n = lt.clamp(0, ex.n_samp)
+        if self.domain == "22k":
+            n = torch.ceil(n.to(torch.float64) * (22050.0 / float(ex.sr_in))).to(torch.int32)
+        return torch.arange(self.n, device=lt.device, dtype=torch.int32)[None, :] < n[:, None]
+
+    def features_device(self, xt, lengths=None):
+        """[B <= batch_max, n] device tensor -> standardised features [B, 20 * utterance_length]."""
+        if lengths is not None:
+            lengths = self.lengths_device(lengths, xt.shape[0])
+        if self.domain == "22k":
+            return self.extractor.from_22k(xt, self.utterance_length, self.mean, self.scale, n_valid=lengths)
+        return self.extractor(xt, self.utterance_length, self.mean, self.scale, n_valid=lengths)
+
+    def predict_device(self, xt, logits=False, lengths=None):
         self._check(xt)
-        return torch.cat([self.model.predict_device(self.features_device(xt[s:s + self._bs].contiguous()), logits=logits)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        return torch.cat([self.model.predict_device(self.features_device(xt[s:s + self._bs].contiguous(),
+                                                                         None if lt is None else lt[s:s + self._bs]), logits=logits)
                           for s in range(0, xt.shape[0], self._bs)])
 
-    def predict(self, x, batch_size=128):
-        return self.predict_device(_to_dev(x)).cpu().numpy()
+    def predict(self, x, batch_size=128, lengths=None):
+        return self.predict_device(_to_dev(x), lengths=lengths).cpu().numpy()
 
-    def loss_gradient_device(self, xt, yt, out=None):
+    def loss_gradient_device(self, xt, yt, out=None, lengths=None):
         """d mean CE(f(features(x)), y) / dx on device tensors ([B, n], one-hot [B, classes]) -> [B, n]."""
         self._check(xt)
         m, ex = self.model, self.extractor
         out = torch.empty_like(xt) if out is None else out
+        lt = self.lengths_device(lengths, xt.shape[0])
         for s in range(0, xt.shape[0], self._bs):
             xb, yb, ob = xt[s:s + self._bs], yt[s:s + self._bs], out[s:s + self._bs]
-            f = self.features_device(xb)
+            lb = None if lt is None else lt[s:s + self._bs]
+            f = self.features_device(xb, lb)
             gf = torch.empty_like(f)
             N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yb), xb.shape[0], N.ptr(gf), N.stream_ptr()))
-            ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+            if lb is None:
+                ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+            else:
+                ex.vjp_ragged(xb, gf, lb, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
         return out
 
-    def loss_gradient(self, x, y):
-        return self.loss_gradient_device(_to_dev(x), _to_dev(y)).cpu().numpy()
+    def loss_gradient(self, x, y, lengths=None):
+        return self.loss_gradient_device(_to_dev(x), _to_dev(y), lengths=lengths).cpu().numpy()
 
 
 def random_targets(labels, nb_classes, rng=None):
@@ -564,26 +598,37 @@ class _SignAttack:
 
     # ---- over audio (WaveformClassifier): features -> lipasr_mlp_input_grad -> MFCC backward -> lipasr_lp_step -> clamp, all on
     # the device; every keyword keeps its meaning, eps and eps_step are amplitudes
-    def _wave_attack_rows(self, est, xa, x0, yb, restart, row0, g):
-        h = N.get_handle(xa.device.index)
-        self._start(xa, x0, restart, row0)
-        if est.clip_values is not None and self.num_random_init > 0:
-            xa.clamp_(*est.clip_values)
-        alpha = -self.eps_step if self.targeted else self.eps_step
-        for _ in range(self.max_iter):
-            est.loss_gradient_device(xa, yb, out=g)
-            N.check(N.lib.lipasr_lp_step(h.h, N.ptr(xa), N.ptr(x0), N.ptr(g), xa.shape[0], xa.shape[1], self.norm, alpha, self.eps,
-                                         N.stream_ptr()))
+    # With per-clip lengths (lens: int32 [rows], mask: bool [rows, n], the positions inside each clip) the iterate lives inside the
+    # clip: the gradient is exactly 0 outside it, a random start is multiplied by the mask (the draw only shrinks: it stays in the
+    # eps ball for norms 1 and 2 as well), and after every clamp the rest of the row is put back from x0 bit for bit (clip_values
+    # is not applied there).
+    def _wave_clamp(self, est, xa, x0, mask):
+        if mask is None:
             if est.clip_values is not None:
                 xa.clamp_(*est.clip_values)
+            return
+        inside = xa if est.clip_values is None else xa.clamp(*est.clip_values)
+        xa.copy_(torch.where(mask, inside, x0))
 
-    def _wave_success(self, est, x0, yb, xa):
-        pa = est.predict_device(xa, logits=True).argmax(dim=1)
+    def _wave_attack_rows(self, est, xa, x0, yb, restart, row0, g, lens=None, mask=None):
+        h = N.get_handle(xa.device.index)
+        self._start(xa, x0, restart, row0)
+        if self.num_random_init > 0:
+            self._wave_clamp(est, xa, x0, mask)
+        alpha = -self.eps_step if self.targeted else self.eps_step
+        for _ in range(self.max_iter):
+            est.loss_gradient_device(xa, yb, out=g, lengths=lens)
+            N.check(N.lib.lipasr_lp_step(h.h, N.ptr(xa), N.ptr(x0), N.ptr(g), xa.shape[0], xa.shape[1], self.norm, alpha, self.eps,
+                                         N.stream_ptr()))
+            self._wave_clamp(est, xa, x0, mask)
+
+    def _wave_success(self, est, x0, yb, xa, lens=None):
+        pa = est.predict_device(xa, logits=True, lengths=lens).argmax(dim=1)
         if self.targeted:
             return pa == yb.argmax(dim=1)
-        return pa != est.predict_device(x0, logits=True).argmax(dim=1)
+        return pa != est.predict_device(x0, logits=True, lengths=lens).argmax(dim=1)
 
-    def _generate_wave(self, xt, yt):
+    def _generate_wave(self, xt, yt, lengths=None):
         est = self.estimator
         m = est.model
         est._check(xt)
@@ -593,7 +638,11 @@ class _SignAttack:
             self._draws = torch.zeros(1, dtype=torch.int32, device=xt.device)
         bs = min(self.batch_size, est._bs)
         rows = range(0, xt.shape[0], bs)
-        y_all = yt if yt is not None else torch.cat([self._labels(m, est.features_device(xt[s:s + bs].contiguous()), None) for s in rows])
+        lt = est.lengths_device(lengths, xt.shape[0])
+        mask_all = None if lt is None else est.clip_mask(lt)
+        cut = lambda t, s: None if t is None else t[s:s + bs]
+        y_all = yt if yt is not None else torch.cat([self._labels(m, est.features_device(xt[s:s + bs].contiguous(), cut(lt, s)), None)
+                                                      for s in rows])
         g = torch.empty(bs, xt.shape[1], device=xt.device)
         restarts = max(1, self.num_random_init)
         whole = isinstance(self, FastGradientMethod)  # ART: FGM keeps the best whole restart, PGD the successful rows of each
@@ -603,20 +652,21 @@ class _SignAttack:
             cur = adv if r == 0 else torch.empty_like(xt)
             for s in rows:
                 x0, yb, out = xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs]
-                gb = g[:x0.shape[0]]
+                gb, lb, mb = g[:x0.shape[0]], cut(lt, s), cut(mask_all, s)
                 if whole:
-                    self._wave_attack_rows(est, out, x0, yb, r, s, gb)
+                    self._wave_attack_rows(est, out, x0, yb, r, s, gb, lb, mb)
                     continue
                 xa = torch.empty_like(x0)
                 for rr in range(restarts):
-                    self._wave_attack_rows(est, xa, x0, yb, rr, s, gb)
+                    self._wave_attack_rows(est, xa, x0, yb, rr, s, gb, lb, mb)
                     if rr == 0:
                         out.copy_(xa)
                     else:
-                        ok = self._wave_success(est, x0, yb, xa)
+                        ok = self._wave_success(est, x0, yb, xa, lb)
                         out[ok] = xa[ok]
             if whole and restarts > 1:
-                rate = float(torch.cat([self._wave_success(est, xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs]) for s in rows]).float().mean())
+                rate = float(torch.cat([self._wave_success(est, xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs], cut(lt, s))
+                                        for s in rows]).float().mean())
                 if best_rate is None or rate > best_rate:
                     best, best_rate = cur, rate
             else:
@@ -624,10 +674,14 @@ class _SignAttack:
         self._draws += 1
         return best
 
-    def generate_device(self, xt, yt=None):
-        """x: float32 device tensor; returns a NEW device tensor (the input is left untouched)."""
+    def generate_device(self, xt, yt=None, lengths=None):
+        """x: float32 device tensor; returns a NEW device tensor (the input is left untouched).  lengths (WaveformClassifier only):
+        the samples of each row that belong to its clip, as WaveformClassifier takes them; every keyword keeps its meaning per row,
+        the perturbation stays inside the clip and the rest of each row is returned as it came."""
+        if lengths is not None and not self._wave:
+            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
         if self._wave:
-            return self._generate_wave(xt, yt)
+            return self._generate_wave(xt, yt, lengths)
         m = self.estimator.model
         if self._default_path:  # the reference's call: exactly the launches of round 5
             adv = xt.clone()
@@ -645,10 +699,12 @@ class _SignAttack:
         self._draws += 1  # the next generate() draws fresh random starts
         return adv
 
-    def generate(self, x, y=None):
+    def generate(self, x, y=None, lengths=None):
+        if lengths is not None and not self._wave:
+            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
         xt = _to_dev(x)
         yt = None if y is None else _to_dev(y)
-        adv = self.generate_device(xt, yt)
+        adv = self.generate_device(xt, yt, lengths)
         return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
 
 

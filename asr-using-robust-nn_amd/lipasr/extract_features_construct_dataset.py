@@ -92,16 +92,45 @@ class MfccExtractor:
                                           N.ptr(out), N.stream_ptr()))
         return out
 
-    def resample(self, waves, out=None):
+    def _lengths(self, n_valid, b):
+        if not torch.is_tensor(n_valid) or n_valid.dtype != torch.int32 or tuple(n_valid.shape) != (b,) or not n_valid.is_cuda \
+                or not n_valid.is_contiguous():
+            raise ValueError(f"n_valid must be a contiguous int32 device tensor [{b}]")
+        return n_valid
+
+    def resample(self, waves, out=None, n_valid=None):
+        """[B, n_samp] at sr_in -> [B, n_y] at 22 050 Hz.  n_valid (int32 device tensor [B], samples at sr_in): clips of different
+        lengths (lipasr_mfcc_plan_resample_ragged; float32 or int16 rows); every row is zero from int(n * 22050 / sr_in) on."""
         y = torch.empty(waves.shape[0], self.n_y, device=self.device) if out is None else out
-        N.check(N.lib.lipasr_mfcc_plan_resample(self._plan, N.ptr(waves), waves.shape[0], N.ptr(y), N.stream_ptr()))
+        if n_valid is None:
+            N.check(N.lib.lipasr_mfcc_plan_resample(self._plan, N.ptr(waves), waves.shape[0], N.ptr(y), N.stream_ptr()))
+            return y
+        b = waves.shape[0]
+        if waves.dim() != 2 or waves.shape[1] != self.n_samp or not waves.is_contiguous() or waves.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"waves must be contiguous float32 or int16 [B, {self.n_samp}], got {waves.dtype} {tuple(waves.shape)}")
+        if tuple(y.shape) != (b, self.n_y) or y.dtype != torch.float32 or not y.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 [{b}, {self.n_y}]")
+        N.check(N.lib.lipasr_mfcc_plan_resample_ragged(self._plan, N.ptr(waves), 1 if waves.dtype == torch.int16 else 0,
+                                                       N.ptr(self._lengths(n_valid, b)), b, N.ptr(y), N.stream_ptr()))
         return y
 
-    def from_22k(self, y, utterance_length=STANDARD_UTTERANCE_LENGTH, mean=None, scale=None, out=None):
+    def from_22k(self, y, utterance_length=STANDARD_UTTERANCE_LENGTH, mean=None, scale=None, out=None, n_valid=None):
+        """[B, n_y] at 22 050 Hz -> features.  n_valid (int32 device tensor [B]): clips of different lengths, counted in samples at
+        sr_in as everywhere else; a row holds its clip in its first ceil(n * 22050 / sr_in) positions
+        (lipasr_mfcc_plan_from_22k_ragged)."""
         if out is None:
             out = torch.empty(y.shape[0], N_MFCC * utterance_length, device=self.device)
-        N.check(N.lib.lipasr_mfcc_plan_from_22k(self._plan, N.ptr(y), y.shape[0], y.shape[1], utterance_length, N.ptr(mean), N.ptr(scale),
-                                                N.ptr(out), N.stream_ptr()))
+        if n_valid is None:
+            N.check(N.lib.lipasr_mfcc_plan_from_22k(self._plan, N.ptr(y), y.shape[0], y.shape[1], utterance_length, N.ptr(mean), N.ptr(scale),
+                                                    N.ptr(out), N.stream_ptr()))
+            return out
+        b = y.shape[0]
+        if y.dim() != 2 or y.shape[1] != self.n_y or y.dtype != torch.float32 or not y.is_contiguous():
+            raise ValueError(f"y must be contiguous float32 [B, {self.n_y}], got {y.dtype} {tuple(y.shape)}")
+        if tuple(out.shape) != (b, N_MFCC * utterance_length) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
+        N.check(N.lib.lipasr_mfcc_plan_from_22k_ragged(self._plan, N.ptr(y), N.ptr(self._lengths(n_valid, b)), b, int(utterance_length),
+                                                       N.ptr(mean), N.ptr(scale), N.ptr(out), N.stream_ptr()))
         return out
 
     def vjp(self, sig, g_feat, utterance_length=STANDARD_UTTERANCE_LENGTH, scale=None, domain="input", reuse_forward=False, out=None,
@@ -110,7 +139,8 @@ class MfccExtractor:
         domain="input": sig [B, n_samp] at sr_in (what ``__call__`` takes); domain="22k": sig [B, n_y] (what ``from_22k`` takes).
         scale: the float64 StandardScaler scale the forward applied, or None.  reuse_forward=True: this extractor's last call
         was the forward on exactly this ``sig`` on the current stream; its intermediates are read, the bits are the same.
-        2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED)."""
+        2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED).  Clips of different lengths
+        in one launch, int16 rows and clips shorter than the reflect padding: ``vjp_ragged``."""
         if self._plan is None:
             raise RuntimeError("MfccExtractor used after close()")
         if domain not in ("input", "22k"):
@@ -133,6 +163,39 @@ class MfccExtractor:
         flags = (1 if reuse_forward else 0) | (2 if sig.dtype == torch.int16 else 0) | (4 if n_valid is not None else 0)
         N.check(N.lib.lipasr_mfcc_plan_vjp(self._plan, N.ptr(sig), dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat), N.ptr(out),
                                            flags, N.stream_ptr()))
+        return out
+
+    def vjp_ragged(self, sig, g_feat, n_valid, utterance_length=STANDARD_UTTERANCE_LENGTH, scale=None, domain="input", reuse_forward=False,
+                   out=None):
+        """``vjp`` for clips of different lengths in one launch (lipasr_mfcc_plan_vjp_ragged).  n_valid: int32 device tensor [B],
+        the samples of each row that belong to its clip, counted at sr_in for BOTH domains; a domain="22k" row holds its clip in
+        its first ceil(n * 22050 / sr_in) positions.  sig: float32, or int16 PCM for domain="input" (the gradient is float32, with
+        respect to pcm / 32768).  The gradient is exactly 0 from each clip's end to the end of its row; a clip may be as short as
+        2 resampled samples, and an empty one gets zeros.  reuse_forward=True: this extractor's last call on the current stream was
+        the forward with the same rows and n_valid (``__call__`` / ``from_22k`` with n_valid).  16 kHz and 8 kHz 2048/512 plans with
+        rows a multiple of 4 samples: anything else raises LipasrError(EUNSUPPORTED)."""
+        if self._plan is None:
+            raise RuntimeError("MfccExtractor used after close()")
+        if domain not in ("input", "22k"):
+            raise ValueError(f"domain={domain!r}: 'input' or '22k'")
+        dom = 0 if domain == "input" else 1
+        n = self.n_samp if dom == 0 else self.n_y
+        b = sig.shape[0]
+        if sig.dim() != 2 or sig.shape[1] != n or not sig.is_contiguous():
+            raise ValueError(f"sig must be contiguous [B, {n}] for domain {domain!r}, got {tuple(sig.shape)}")
+        if sig.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"sig must be float32 or int16, got {sig.dtype}")
+        if tuple(g_feat.shape) != (b, N_MFCC * utterance_length) or g_feat.dtype != torch.float32 or not g_feat.is_contiguous():
+            raise ValueError(f"g_feat must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
+        if scale is not None and (scale.dtype != torch.float64 or scale.numel() != N_MFCC * utterance_length):
+            raise ValueError("scale must be a float64 device tensor [20 * utterance_length]")
+        if out is None:
+            out = torch.empty(b, n, device=self.device)
+        elif tuple(out.shape) != (b, n) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 [{b}, {n}]")
+        N.check(N.lib.lipasr_mfcc_plan_vjp_ragged(self._plan, N.ptr(sig), 1 if sig.dtype == torch.int16 else 0, N.ptr(self._lengths(n_valid, b)),
+                                                  dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat), N.ptr(out),
+                                                  1 if reuse_forward else 0, N.stream_ptr()))
         return out
 
     def resample_vjp(self, g_y, out=None):

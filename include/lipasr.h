@@ -8,11 +8,13 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 520.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 530.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
  * 520: the backward pass of the MFCC stage, lipasr_mfcc_plan_vjp and lipasr_mfcc_plan_resample_vjp.
+ * 530: clips of different lengths in one launch for the backward pass and the split forward: lipasr_mfcc_plan_vjp_ragged,
+ * lipasr_mfcc_plan_resample_ragged, lipasr_mfcc_plan_from_22k_ragged.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -469,6 +471,36 @@ int lipasr_mfcc_plan_from_22k(lipasr_mfcc_t p, const float* y, int batch, int n_
 int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length,
                          const double* affine_scale, const float* g_feat, float* g_sig, int flags,
                          lipasr_stream_t stream);
+/* The same backward pass for clips of different lengths in ONE launch, as lipasr_mfcc_extract's n_valid gives the forward.
+ *   n_valid: device int [batch], required: the samples of each row that belong to its clip, ALWAYS counted at the plan's input
+ *     rate, also for domain 1 (clamped to [0, n_samp]).  Clip u has n_vy = int(n r) resampled samples, n_y = ceil(n r) after
+ *     fix_length and 1 + n_y / 512 frames (none for n_y < 2), r = 22050 / sr_in; a domain-1 row holds its clip in its first
+ *     ceil(n r) positions.  Whatever else a row holds is ignored.
+ *   sample_format: 0 float32, 1 int16 PCM (domain 0 only; it matters where the forward is re-run: g_sig is float32, the gradient
+ *     with respect to pcm * 2^-15).
+ *   g_sig: [batch][n_samp] (domain 0) or [batch][n_y] (domain 1), rows as long as the plan's; the gradient is exactly 0 from the
+ *     clip's end (n_valid[u], or ceil(n r)) to the end of the row, and a clip of n_valid <= 0 (or of fewer than 2 resampled samples)
+ *     gets an all-zero row.
+ *   flags bit 0: the plan's last call on this stream was the forward with per-clip lengths on exactly these rows and this
+ *     n_valid (lipasr_mfcc_extract with n_valid for domain 0, lipasr_mfcc_plan_from_22k_ragged for domain 1).  Same bits.
+ * Clips may be as short as 2 resampled samples: the adjoint of the reflect padding sums every padded position that reflects
+ * onto a sample, in ascending order (np.pad reflects repeatedly once n_y <= 1024); a clip of n_y > 2048 keeps the three-term
+ * form and the bits lipasr_mfcc_plan_vjp gives for it alone.  Runs on the plans whose three-kernel forward takes per-clip
+ * lengths: 2048/512 at 16 kHz or 8 kHz, rows a multiple of 4 samples, 16-byte (float32) / 8-byte (int16) aligned row pointers.
+ * LIPASR_EUNSUPPORTED with a message otherwise: short-window plans, other rates, a plan that runs the fused resample -> STFT
+ * kernel for this input (it leaves no resampled signal behind), int16 with domain 1.  Fixed summation order, no host
+ * synchronisation, workspaces allocated by the first call, as above. */
+int lipasr_mfcc_plan_vjp_ragged(lipasr_mfcc_t p, const void* sig, int sample_format, const int* n_valid, int domain,
+                                int batch, int utterance_length, const double* affine_scale, const float* g_feat,
+                                float* g_sig, int flags /* bit 0: reuse the forward */, lipasr_stream_t stream);
+/* The two halves of lipasr_mfcc_extract with n_valid (same semantics as above; composed they give its bits).  _resample_ragged
+ * leaves zeros from int(n r) to the end of every row of y [batch][n_y]; _from_22k_ragged reads a row's first ceil(n r)
+ * positions, position int(n r) as the zero fix_length appends. */
+int lipasr_mfcc_plan_resample_ragged(lipasr_mfcc_t p, const void* wav, int sample_format, const int* n_valid, int batch,
+                                     float* y, lipasr_stream_t stream);
+int lipasr_mfcc_plan_from_22k_ragged(lipasr_mfcc_t p, const float* y, const int* n_valid, int batch, int utterance_length,
+                                     const double* affine_mean, const double* affine_scale, float* out,
+                                     lipasr_stream_t stream);
 /* g_wav [batch][n_samp] = R^T g_y [batch][n_y]: the adjoint of lipasr_mfcc_plan_resample (any plan whose ratio keeps one
  * q-block's window of g_y in LDS; its tap table is built by the first call) */
 int lipasr_mfcc_plan_resample_vjp(lipasr_mfcc_t p, const float* g_y, int batch, float* g_wav, lipasr_stream_t stream);
