@@ -1785,7 +1785,13 @@ __global__ __launch_bounds__(512 + 64 * kR2Loaders) void gemm_ring2_kernel(GemmA
 // ---------------------------------------------------------------------------------------------
 static GemmKnobs g_knobs;
 const GemmKnobs& gemm_knobs() { return g_knobs; }
-static long g_launch_count[2] = {0, 0};  // lipasr_debug_launch_count: 0 = launches on 128 x 64 exchange tiles, 1 = weight-gradient launches with 128 x 128 split-pass tiles
+constexpr int kEpiCount = EPI_DH_BNX + 1;
+// Test hooks (lipasr_debug_gemm_launches / lipasr_debug_group_launches): launches since load, counted from the GemmPick / group that
+// is actually launched.  Plain host increments; the kernels see nothing of them.
+static long g_gemm_launches[GK_KINDS][2][2][2][3][kEpiCount] = {};  // [kind][exchange][AMODE][BMODE][arithmetic][epilogue]
+static long g_group_launches[3][3] = {};   // [0 fragment, 1 LDS, 2 ring tiles][arithmetic]: grouped weight-gradient launches
+static long g_group_ring_problems[4] = {};  // problems inside ring launches by GemmArgs::ring (0: not ring-legal, on plain tiles)
+static long g_group_ring_launches[4] = {};  // ring launches by the launch's ring tile (1 64 x 64, 2 128 x 128 split pass, 3 per fragment)
 
 // Every instantiated GEMM kernel, indexed by what the templates are parameterised on; null = not instantiated.
 // arithmetic mode (GemmArgs::bf16: 0 exact fp32, 1 bf16 operands, 2 fp16 two-plane split) -> index
@@ -1904,7 +1910,10 @@ int launch_gemm(int amode, int bmode, const GemmArgs& g, hipStream_t st) {
   GemmPick p;
   const int rc = pick_gemm(amode, bmode, g, &p);
   if (rc != LIPASR_OK) return rc;
-  if (p.kind == GK_RING2) ++g_launch_count[0];
+  if (g.epi >= 0 && g.epi < kEpiCount) {
+    const bool exchange = g.epi == EPI_BIAS_RELU_BNX || g.epi == EPI_DH_BNX;
+    ++g_gemm_launches[p.kind][exchange ? 1 : 0][amode ? 1 : 0][bmode ? 1 : 0][p.kind >= GK_RING ? 2 : arith_index(g.bf16)][g.epi];
+  }
   (void)ensure_dyn_lds(p.fn, p.lds_bytes);
   void* args[] = {const_cast<GemmArgs*>(&g)};
   (void)hipLaunchKernel(p.fn, dim3((g.N + p.tile_n - 1) / p.tile_n, (g.M + p.tile_m - 1) / p.tile_m), dim3(p.threads), args, p.lds_bytes, st);
@@ -2010,7 +2019,11 @@ int launch_gemm_group_tn(const GemmArgs* gs, int n, hipStream_t st) {
       }
       lds = std::max(ring_gemm_bytes(), ring_tile == 2 ? ring128s_bytes() : ring_tile == 3 ? ring128_bytes() : (size_t)0);
       threads = ring_tile == 2 ? 512 + 64 * kR128Loaders : 512;  // (loader wavefronts: the split-pass tile only)
-      if (ring_tile == 2) ++g_launch_count[1];
+      ++g_group_launches[2][2];
+      ++g_group_ring_launches[ring_tile];
+      for (int q = 0; q < k; ++q) ++g_group_ring_problems[grp.g[q].ring & 3];
+    } else {
+      ++g_group_launches[lds_tiles ? 1 : 0][arith_index(ar)];
     }
     (void)ensure_dyn_lds(fn, lds);
     void* args[] = {&grp};
@@ -2036,7 +2049,27 @@ using namespace lipasr;
 
 extern "C" {
 
-long lipasr_debug_launch_count(int kind) { return (kind == 0 || kind == 1) ? g_launch_count[kind] : -1; }
+long lipasr_debug_gemm_launches(int kind, int exchange, int amode, int bmode, int arith, int epi) {
+  if (kind < 0 || kind >= GK_KINDS || (exchange | amode | bmode) & ~1 || arith < 0 || arith > 2 || epi < -1 || epi >= kEpiCount) return -1;
+  if (!gemm_table().fn[kind][exchange][amode][bmode][arith]) return -1;
+  const long* c = g_gemm_launches[kind][exchange][amode][bmode][arith];
+  if (epi >= 0) return c[epi];
+  long n = 0;
+  for (int e = 0; e < kEpiCount; ++e) n += c[e];
+  return n;
+}
+
+long lipasr_debug_group_launches(int family, int arith, int variant) {
+  if (family < 0 || family > 2 || arith < 0 || arith > 2) return -1;
+  if (family < 2) return variant == -1 ? g_group_launches[family][arith] : -1;
+  if (arith != 2 || variant < -1 || variant > 3) return -1;  // the ring kernel is a mode-2 kernel
+  return variant == -1 ? g_group_launches[2][2] : g_group_ring_problems[variant];
+}
+
+long lipasr_debug_launch_count(int kind) {
+  if (kind == 0) return lipasr_debug_gemm_launches(GK_RING2, 1, 0, 0, 2, -1) + lipasr_debug_gemm_launches(GK_RING2, 1, 0, 1, 2, -1);
+  return kind == 1 ? g_group_ring_launches[2] : -1;
+}
 
 int lipasr_debug_gemm_mode(int mode) {  // the bits: GemmKnobs (gemm.h)
   GemmKnobs k;
@@ -2052,29 +2085,40 @@ int lipasr_debug_gemm_mode(int mode) {  // the bits: GemmKnobs (gemm.h)
   return LIPASR_OK;
 }
 
+// the stand-alone product in arithmetic `arith`: the checks and the launch of lipasr_gemm_f32 / _f16x2 / lipasr_debug_gemm (`fn` names
+// the entry in the error text)
+static int gemm_entry(const char* fn, lipasr_handle_t h, int arith, int transA, int transB, int M, int N, int K, const float* A, int lda,
+                      const float* B, int ldb, float* C, int ldc, float scale_a, float scale_b, lipasr_stream_t stream) {
+  LP_CHECK_ARG(h && A && B && C, "%s: null argument", fn);
+  LP_CHECK_ARG(arith >= 0 && arith <= 2, "%s: arithmetic mode %d (0 = exact fp32, 1 = bf16 operands, 2 = fp16 two-plane split)", fn, arith);
+  LP_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: empty problem %dx%dx%d", fn, M, N, K);
+  LP_CHECK_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "%s: leading dimension too small", fn);
+  GemmArgs g = gemm_args(A, lda, B, ldb, C, ldc, M, N, K, EPI_STORE);
+  g.bf16 = arith;
+  if (arith == 2) {
+    int ea = 0, eb = 0;
+    LP_CHECK_ARG(scale_a > 0.0f && scale_b > 0.0f && frexpf(scale_a, &ea) == 0.5f && frexpf(scale_b, &eb) == 0.5f,
+                 "%s: the scales must be powers of two (got %g, %g)", fn, (double)scale_a, (double)scale_b);
+    g.sa = scale_a;
+    g.sb = scale_b;
+    g.zeros = h->zeros;
+  }
+  return launch_gemm(transA ? 1 : 0, transB ? 0 : 1, g, S(stream));
+}
+
 int lipasr_gemm_f32(lipasr_handle_t h, int transA, int transB, int M, int N, int K, const float* A, int lda,
                     const float* B, int ldb, float* C, int ldc, lipasr_stream_t stream) {
-  LP_CHECK_ARG(h && A && B && C, "lipasr_gemm_f32: null argument");
-  LP_CHECK_ARG(M > 0 && N > 0 && K > 0, "lipasr_gemm_f32: empty problem %dx%dx%d", M, N, K);
-  LP_CHECK_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "lipasr_gemm_f32: leading dimension too small");
-  GemmArgs g = gemm_args(A, lda, B, ldb, C, ldc, M, N, K, EPI_STORE);
-  return launch_gemm(transA ? 1 : 0, transB ? 0 : 1, g, S(stream));
+  return gemm_entry("lipasr_gemm_f32", h, 0, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, 1.0f, 1.0f, stream);
+}
+
+int lipasr_debug_gemm(lipasr_handle_t h, int arith, int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,
+                      int ldb, float* C, int ldc, float scale_a, float scale_b, lipasr_stream_t stream) {
+  return gemm_entry("lipasr_debug_gemm", h, arith, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, scale_a, scale_b, stream);
 }
 
 int lipasr_gemm_f16x2(lipasr_handle_t h, int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,
                       int ldb, float* C, int ldc, float scale_a, float scale_b, lipasr_stream_t stream) {
-  LP_CHECK_ARG(h && A && B && C, "lipasr_gemm_f16x2: null argument");
-  LP_CHECK_ARG(M > 0 && N > 0 && K > 0, "lipasr_gemm_f16x2: empty problem %dx%dx%d", M, N, K);
-  LP_CHECK_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "lipasr_gemm_f16x2: leading dimension too small");
-  int ea = 0, eb = 0;
-  LP_CHECK_ARG(scale_a > 0.0f && scale_b > 0.0f && frexpf(scale_a, &ea) == 0.5f && frexpf(scale_b, &eb) == 0.5f,
-               "lipasr_gemm_f16x2: the scales must be powers of two (got %g, %g)", (double)scale_a, (double)scale_b);
-  GemmArgs g = gemm_args(A, lda, B, ldb, C, ldc, M, N, K, EPI_STORE);
-  g.bf16 = 2;
-  g.sa = scale_a;
-  g.sb = scale_b;
-  g.zeros = h->zeros;
-  return launch_gemm(transA ? 1 : 0, transB ? 0 : 1, g, S(stream));
+  return gemm_entry("lipasr_gemm_f16x2", h, 2, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, scale_a, scale_b, stream);
 }
 
 }  // extern "C"

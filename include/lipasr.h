@@ -8,13 +8,15 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 530.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 540.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
  * 520: the backward pass of the MFCC stage, lipasr_mfcc_plan_vjp and lipasr_mfcc_plan_resample_vjp.
  * 530: clips of different lengths in one launch for the backward pass and the split forward: lipasr_mfcc_plan_vjp_ragged,
  * lipasr_mfcc_plan_resample_ragged, lipasr_mfcc_plan_from_22k_ragged.
+ * 540: test hooks of the GEMM selector: lipasr_debug_gemm (the stand-alone product in any arithmetic mode), lipasr_debug_gemm_launches
+ * and lipasr_debug_group_launches (launch counters per kernel instance).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -568,6 +570,27 @@ int lipasr_debug_gemm_mode(int mode);
  * 128x64 exchange tiles, 1: grouped weight-gradient launches with 128x128 split-pass tiles; -1 for an unknown kind.  (The choice
  * depends on the plan's CU budget; tests that mean to cover those kernels check that they really ran.) */
 long lipasr_debug_launch_count(int kind);
+
+/* Test hook: launches since the library was loaded that took exactly one GEMM kernel instance, counted where the launch happens.
+ * kind: 0 32x32 fragment tiles with 4 wavefronts, 1 the same with 16 wavefronts splitting K, 2 64x64 LDS tiles, 3 the 64x64
+ * LDS-DMA ring tile, 4 its loader-wavefront instance for one workgroup per CU, 5 the 128x64 exchange tile.  exchange: 1 = the
+ * instance with the BatchNorm exchange epilogue.  amode / bmode: 1 = the operand is k-major in memory (lipasr_gemm_f32:
+ * amode = transA, bmode = !transB).  arith: 0 exact fp32, 1 bf16 operands, 2 fp16 two-plane split.  epi: the epilogue (0 plain
+ * store, 1 bias, 2 bias + ReLU, 3 inference BatchNorm, 4 inference dz, 5 sign step, 6 training forward with column sums, 7 training
+ * backward with column sums, 8 backward without BatchNorm, 9 softmax + CE, 10 / 11 the forward / backward exchange epilogue), or
+ * -1 for any.  Returns -1 for a key the library has no kernel for, so a test can enumerate the instances from the library. */
+long lipasr_debug_gemm_launches(int kind, int exchange, int amode, int bmode, int arith, int epi);
+
+/* Test hook, grouped weight-gradient launches.  family 0: 32x32 fragment tiles, 1: 64x64 LDS tiles (variant -1: launches in
+ * arithmetic `arith`); family 2: the ring kernel (arith 2 only) -- variant -1: launches; variant 1, 2, 3: problems carried on
+ * 64x64 ring tiles, 128x128 split-pass tiles, 128x128 tiles that split per fragment; variant 0: problems the ring layout cannot take,
+ * carried by a ring launch on plain tiles.  -1 for an unknown key. */
+long lipasr_debug_group_launches(int family, int arith, int variant);
+
+/* Test hook: lipasr_gemm_f32 (arith 0) / lipasr_gemm_f16x2 (arith 2) with the arithmetic mode as an argument, which also reaches
+ * the plain product with bf16 operands (arith 1).  The scales are read in mode 2 only (powers of two). */
+int lipasr_debug_gemm(lipasr_handle_t h, int arith, int transA, int transB, int M, int N, int K, const float* A, int lda,
+                      const float* B, int ldb, float* C, int ldc, float scale_a, float scale_b, lipasr_stream_t stream);
 
 /* Profiling knob: how many of the leading (small) steps of the product chain W_m^T ... W_1^T run as ONE launch
  * (chain_head_kernel, fp32 matrix instructions): -1 = automatic (the first two steps, when their panels have <= 256 columns

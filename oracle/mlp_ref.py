@@ -147,21 +147,33 @@ def forward_infer(spec, p: Params, x, return_logits=False):
     raise AssertionError
 
 
-def forward_backward(spec, p: Params, x, y_onehot, masks=None, training=True, need_dx=False):
+def round_bf16(x):
+    """x rounded to the nearest bfloat16 (ties to even), in x's dtype: integer arithmetic on the float32 bit pattern."""
+    x = np.asarray(x)
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    u = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    return u.view(np.float32).astype(x.dtype)
+
+
+def forward_backward(spec, p: Params, x, y_onehot, masks=None, training=True, need_dx=False, round_operands=None):
     """One training-mode forward + backward.
 
     masks[l]: inverted-dropout multiplier array (0 or 1/(1-p)) for layer l, or None.
     Returns dict with logits, loss (mean over batch), grads (dW, db, dgamma, dbeta),
     batch statistics (mean, var) per BN layer and optionally dx.
     Gradient at the logits is (softmax - y)/B (Keras recovers logits from the softmax op).
+    round_operands: optional function applied to both operands of every matrix product (forward, input gradient, weight
+    gradient, and the gradient under the bias gradient's column sum, which is a product with an all-ones row), e.g.
+    round_bf16 for the arithmetic that rounds GEMM operands to bf16 and accumulates exactly; everything else is untouched.
     """
+    rnd = round_operands if round_operands is not None else (lambda a: a)
     L = len(spec)
     B = x.shape[0]
     cache = []
     h = x
     for l, s in enumerate(spec):
         inp = h
-        z = inp @ p.W[l] + p.b[l]
+        z = rnd(inp) @ rnd(p.W[l]) + p.b[l]
         if l == L - 1:
             cache.append(dict(inp=inp))
             logits = z
@@ -206,10 +218,10 @@ def forward_backward(spec, p: Params, x, y_onehot, masks=None, training=True, ne
                 else:
                     g = p.gamma[l] * c["rstd"] * g
             g = g * (c["a"] > 0)
-        dW[l] = c["inp"].T @ g
-        db[l] = g.sum(axis=0)
+        dW[l] = rnd(c["inp"]).T @ rnd(g)
+        db[l] = rnd(g).sum(axis=0)
         if l > 0 or need_dx:
-            g = g @ p.W[l].T
+            g = rnd(g) @ rnd(p.W[l]).T
             if l == 0:
                 dx = g
     stats = [(c.get("mu"), c.get("var")) for c in cache]

@@ -392,6 +392,42 @@ def test_mlp_oracle_gradients_equal_torch_autograd(training):
             np.testing.assert_allclose(prob, torch.softmax(lg, dim=1).detach().numpy(), atol=1e-14)
 
 
+def test_mlp_oracle_operand_rounding():
+    """round_bf16 is torch's float32 -> bfloat16 conversion (nearest, ties to even; not truncation), and forward_backward's
+    round_operands touches the matrix products only: the identity reproduces the plain oracle bit for bit, and with operands that are
+    bf16 numbers already the forward pass of the first layer does not change."""
+    import torch
+
+    rng = np.random.default_rng(3)
+    v = np.concatenate([rng.standard_normal(4096) * 10.0 ** rng.integers(-6, 7, 4096), [1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), 0.0]]).astype(np.float32)
+    want = torch.from_numpy(v).to(torch.bfloat16).to(torch.float32).numpy()
+    np.testing.assert_array_equal(P.round_bf16(v), want)
+    np.testing.assert_array_equal(P.round_bf16(v.astype(np.float64)), want.astype(np.float64))
+    assert np.any(P.round_bf16(v) != (v.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32))  # truncation is something else
+    spec = [P.LayerSpec(13, 11, True, 0.25, True), P.LayerSpec(11, 7, False, 0.0, True), P.LayerSpec(7, 5, False, 0.0, True)]
+    p = P.init_params(spec, seed=4, dtype=np.float64)
+    x = rng.standard_normal((17, 13))
+    y = P.to_categorical(rng.integers(0, 5, 17), 5).astype(np.float64)
+    masks = [(rng.uniform(size=(17, 11)) > 0.25) / 0.75, None, None]
+    plain = P.forward_backward(spec, p, x, y, masks=masks, need_dx=True)
+    same = P.forward_backward(spec, p, x, y, masks=masks, need_dx=True, round_operands=lambda a: a)
+    for k in ("dW", "db", "dgamma", "dbeta"):
+        for a, b in zip(plain[k], same[k]):
+            assert (a is None and b is None) or np.array_equal(a, b)
+    assert np.array_equal(plain["dx"], same["dx"]) and plain["loss"] == same["loss"]
+    rounded = P.forward_backward(spec, p, x, y, masks=masks, need_dx=True, round_operands=P.round_bf16)
+    e = lambda a, b: np.abs(a - b).max() / np.abs(b).max()
+    assert all(1e-5 < e(rounded["dW"][l], plain["dW"][l]) < 3e-2 for l in range(3))  # bf16 operands: 2^-9 per factor
+    # the bias gradient is a product with an all-ones row: its gradient operand is rounded too
+    g_last = (rounded["prob"] - y) / 17
+    np.testing.assert_allclose(rounded["db"][2], P.round_bf16(g_last).sum(axis=0), rtol=0, atol=1e-15)
+    q = p.copy()
+    q.W[0] = P.round_bf16(q.W[0])
+    xr = P.round_bf16(x)
+    assert np.array_equal(P.forward_backward(spec, q, xr, y, masks=masks, round_operands=P.round_bf16)["stats"][0][0],
+                          P.forward_backward(spec, q, xr, y, masks=masks)["stats"][0][0])
+
+
 def test_adam_oracle_equals_torch_adam_up_to_epsilon_placement():
     """Keras-form Adam differs from torch.optim.Adam only in where epsilon sits; with eps -> 0 both agree."""
     import torch
