@@ -5,7 +5,7 @@
 //   2. stft_bdft_kernel (stft_bdft.hip)           reflect-padded Hann frames -> block-DFT on the matrix pipe -> power -> mel -> dB
 //   3. dct_kernel (stft_mel.hip)                  top_db floor, DCT-II 128 -> 20, layout, optional StandardScaler affine
 // Every other variant (fp32 / VALU resamplers, Stockham and short-window STFTs, the fused resample -> STFT kernel of
-// mfcc_fused.hip) is chosen in ONE place, pick_mfcc_path below; plan_run, plan_resample, plan_from_22k, plan_vjp and their per-clip-length forms ask it once
+// mfcc_fused.hip) is chosen in ONE place, pick_mfcc_path below; plan_run, plan_resample, plan_from_22k, plan_vjp, plan_vjp_short and their per-clip-length forms ask it once
 // and hand the kinds to the launchers of mfcc_plan.h.  This file holds no stage kernel except add_noise_kernel.
 #include "mfcc_plan.h"
 #include <memory>
@@ -17,7 +17,8 @@ using namespace tables;
 void mfcc_plan_free(MfccPlan* p) {
   if (!p) return;
   void* ptrs[] = {p->d_hbandh, p->d_groups, p->d_dft, p->d_mel_wlo, p->d_mel_whi, p->d_mel_pstart, p->d_mel_plen, p->d_hband, p->d_lo, p->d_h, p->d_noff, p->d_hann, p->d_tw, p->d_mel_start, p->d_mel_len, p->d_mel_off,
-                  p->d_mel_w, p->d_dct, p->d_y, p->d_db, p->d_fmax, p->d_gmel, p->d_part, p->d_gy, p->d_dct_rows, p->d_bin_run, p->d_rt_taps, p->d_rt_t0};
+                  p->d_mel_w, p->d_dct, p->d_y, p->d_db, p->d_fmax, p->d_gmel, p->d_part, p->d_gy, p->d_dct_rows, p->d_bin_run, p->d_rt_taps, p->d_rt_t0,
+                  p->d_dft_t, p->d_melt_off, p->d_melt_len, p->d_melt_m, p->d_melt_w};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   for (hipEvent_t e : p->prof_events) (void)hipEventDestroy(e);
@@ -320,7 +321,8 @@ static int plan_run(MfccPlan* p, const void* wav, int fmt, const int* n_valid, i
 // ---- backward pass ----
 static int vjp_unsupported(const char* fn, const MfccPlan* p) {
   if (p->dft) {
-    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d", fn, p->n_fft, p->hop);
+    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d (short-window plans: "
+              "lipasr_mfcc_plan_vjp_short)", fn, p->n_fft, p->hop);
     return LIPASR_EUNSUPPORTED;
   }
   if (p->n_y <= kNFft) {
@@ -441,6 +443,86 @@ static int plan_vjp(MfccPlan* p, const float* sig, int domain, int batch, int L,
   MfccVjpArgs a;
   fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
   if ((rc = launch_mfcc_vjp(a, st)) != LIPASR_OK) return rc;
+  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st);
+  return LIPASR_OK;
+}
+
+// ---- short-window plans (dft_mel_kernel's forward): the same chain with dft_vjp_kernel in the middle ----
+// tables and workspaces of the first call: the plain DCT rows, the folded table with bins and samples exchanged (unit-stride
+// B-operand loads of the second contraction), the CSR mel bank by bin, Gmel, the workgroup images and g_y
+static int vjp_short_prepare(MfccPlan* p) {
+  if (p->d_dft_t) return LIPASR_OK;
+  DeviceGuard g(p->ctx->device);
+  int n_wgs, seg, rc;
+  if ((rc = short_vjp_geometry(p->n_fft, p->hop, p->dft_rpc, p->dft_tiles, p->batch_max, &n_wgs, &seg)) != LIPASR_OK) return rc;
+  const int nb = p->dft_tiles * 32, ld = p->dft_tiles * 64;
+  const std::vector<float> T = dft_table(p->n_fft, p->dft_krows, p->dft_tiles);
+  std::vector<float> TT((size_t)nb * ld, 0.0f);
+  for (int b = 0; b < nb; ++b)
+    for (int n = 0; n < std::min(nb, p->dft_krows); ++n) {
+      const size_t src = (size_t)n * ld + (b >> 5) * 64 + (b & 31), dst = (size_t)b * ld + (n >> 5) * 64 + (n & 31);
+      TT[dst] = T[src];
+      TT[dst + 32] = T[src + 32];
+    }
+  const MelSparse ms = mel_sparse(p->n_fft);
+  std::vector<int> off(nb, 0), len(nb, 0), mm;
+  std::vector<float> ww;
+  for (int b = 0; b < nb; ++b) {
+    off[b] = (int)mm.size();
+    for (int m = 0; m < kNMels; ++m) {
+      const int j = b - ms.start[m];
+      if (j >= 0 && j < ms.len[m] && ms.w[ms.off[m] + j] != 0.0f) { mm.push_back(m); ww.push_back(ms.w[ms.off[m] + j]); }
+    }
+    len[b] = (int)mm.size() - off[b];
+  }
+  if (mm.empty()) { mm.push_back(0); ww.push_back(0.0f); }
+  if ((!p->d_dct_rows && (rc = upload(&p->d_dct_rows, dct_matrix())) != LIPASR_OK) || (rc = upload(&p->d_melt_off, off)) != LIPASR_OK ||
+      (rc = upload(&p->d_melt_len, len)) != LIPASR_OK || (rc = upload(&p->d_melt_m, mm)) != LIPASR_OK ||
+      (rc = upload(&p->d_melt_w, ww)) != LIPASR_OK)
+    return rc;
+  const size_t ngm = (size_t)p->batch_max * p->n_frames * kNMels, npart = (size_t)n_wgs * seg, ngy = (size_t)p->batch_max * p->n_y;
+  if ((!p->d_gmel && hipMalloc(&p->d_gmel, ngm * sizeof(float)) != hipSuccess) ||
+      (!p->d_part && hipMalloc(&p->d_part, npart * sizeof(float)) != hipSuccess) ||
+      (!p->d_gy && hipMalloc(&p->d_gy, ngy * sizeof(float)) != hipSuccess)) {
+    (void)hipGetLastError();
+    set_error("lipasr_mfcc_plan_vjp_short: intermediate allocation failed");
+    return LIPASR_ENOMEM;
+  }
+  return upload(&p->d_dft_t, TT);  // last: its presence marks the plan as prepared
+}
+
+static int plan_vjp_short(MfccPlan* p, const float* sig, int domain, int batch, int L, const double* as, const float* g_feat, float* g_sig,
+                          int flags, hipStream_t st) {
+  static const char* fn = "lipasr_mfcc_plan_vjp_short";
+  LP_CHECK_ARG(sig && g_feat && g_sig, "%s: null argument", fn);
+  LP_CHECK_ARG(domain == 0 || domain == 1, "%s: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", fn, domain);
+  LP_CHECK_ARG((flags & ~1) == 0, "%s: unknown flag bits %d", fn, flags);
+  if (!p->dft) {
+    set_error("%s: the short-window backward pass covers the plans made with n_fft, hop other than 2048, 512; this plan is 2048/512 "
+              "(lipasr_mfcc_plan_vjp)", fn);
+    return LIPASR_EUNSUPPORTED;
+  }
+  int rc = vjp_short_prepare(p);
+  if (rc != LIPASR_OK) return rc;
+  const MfccPath path = pick_mfcc_path(p, domain == 0 ? sig : nullptr, 0, false);
+  if (path.rc != LIPASR_OK) return path.rc;
+  const bool reuse = (flags & 1) != 0;  // (the stage mask's profiling switches do not reach dft_mel_kernel)
+  const float* y = sig;
+  if (domain == 0) {
+    if (!reuse && (rc = launch_resample(p, path.resampler, sig, 0, nullptr, batch, p->d_y, st)) != LIPASR_OK) return rc;
+    y = p->d_y;
+  }
+  if (!reuse && (rc = launch_from_22k(p, path.stft, y, nullptr, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
+  MfccVjpArgs a;
+  fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
+  if ((rc = launch_mfcc_vjp_db(a, st)) != LIPASR_OK) return rc;
+  ShortVjpArgs s;
+  s.y = y; s.table = p->d_dft; s.table_t = p->d_dft_t; s.gmel = p->d_gmel;
+  s.melt_off = p->d_melt_off; s.melt_len = p->d_melt_len; s.melt_m = p->d_melt_m; s.melt_w = p->d_melt_w;
+  s.n_y = p->n_y; s.batch = batch; s.hop = p->hop; s.n_fft = p->n_fft; s.k_rows = p->dft_krows; s.n_tiles = p->dft_tiles;
+  s.rpc = p->dft_rpc; s.n_frames = p->n_frames; s.total_rows = batch * p->dft_rpc; s.seg = 0;
+  s.part = p->d_part; s.gy = a.gy;
+  if ((rc = launch_short_vjp(s, st)) != LIPASR_OK) return rc;
   if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st);
   return LIPASR_OK;
 }
@@ -631,6 +713,13 @@ int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batc
   int rc = plan_check("lipasr_mfcc_plan_vjp", p, batch, utterance_length);
   if (rc != LIPASR_OK) return rc;
   return plan_vjp(p, sig, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+}
+
+int lipasr_mfcc_plan_vjp_short(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length, const double* affine_scale,
+                               const float* g_feat, float* g_sig, int flags, lipasr_stream_t stream) {
+  int rc = plan_check("lipasr_mfcc_plan_vjp_short", p, batch, utterance_length);
+  if (rc != LIPASR_OK) return rc;
+  return plan_vjp_short(p, sig, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
 }
 
 int lipasr_mfcc_plan_vjp_ragged(lipasr_mfcc_t p, const void* sig, int sample_format, const int* n_valid, int domain, int batch,

@@ -38,6 +38,7 @@ constexpr float kRhTapScale = 64.0f, kRhSigScale = 2048.0f;
 constexpr int kFuQ = 16;                                    // q-blocks per workgroup = rows of the 16x16x4 MFMA
 constexpr int kFuUp = 441;
 constexpr int kDftRows = 64, kDftGroup = 8, kDftMaxTiles = 8;
+constexpr int kSvRows = 32;                                 // frame rows per workgroup of dft_vjp_kernel (one MFMA row block)
 typedef float rs_f32x16 __attribute__((ext_vector_type(16)));
 
 struct MfccPlan {
@@ -101,6 +102,13 @@ struct MfccPlan {
   float* d_rt_taps = nullptr;   // [rt_nt][down]
   int* d_rt_t0 = nullptr;       // [down]
   int rt_nt = 0, rt_t0min = 0, rt_t0max = 0;
+  // backward pass of the short-window path (lipasr_mfcc_plan_vjp_short, kernels in mfcc_vjp_short.hip): allocated at the first
+  // call, next to d_gmel / d_gy / d_dct_rows above; d_part then holds the workgroup images [workgroups][sv_seg]
+  float* d_dft_t = nullptr;     // [dft_tiles*32 bins][dft_tiles*64]: d_dft with bins and samples exchanged
+  int* d_melt_off = nullptr;    // [dft_tiles*32]: the mel bank by bin (the CSR bank transposed), filters in ascending order
+  int* d_melt_len = nullptr;
+  int* d_melt_m = nullptr;
+  float* d_melt_w = nullptr;
 };
 
 // What one extraction runs.  pick_mfcc_path (mfcc.hip) is the ONE place that decides it; the launchers below take the kind and
@@ -136,6 +144,25 @@ void fill_stft_args(const MfccPlan* p, const float* y, StftArgs* a);
 int launch_dct(const MfccPlan* p, int batch, int L, const double* am, const double* as, float* out, const int* n_valid, hipStream_t st);
 int launch_from_22k(const MfccPlan* p, MfccPath::Stft kind, const float* y, const int* n_valid, int batch, int L, const double* am,
                     const double* as, float* out, hipStream_t st, hipEvent_t mid = nullptr, bool stft_only = false);
+// mfcc_vjp.hip: step 1 of the backward pass alone (DCT^T, top_db floor, dB -> mel into a.gmel), shared with the short-window chain
+int launch_mfcc_vjp_db(const MfccVjpArgs& a, hipStream_t st);
+// mfcc_vjp_short.hip: mel^T, |X|^2, STFT^T and overlap-add of the short-window path, then the adjoint of the reflect padding
+struct ShortVjpArgs {
+  const float* y;        // [batch][n_y] the 22 050 Hz signal the forward read
+  const float* table;    // [k_rows][n_tiles*64] the forward's folded table
+  const float* table_t;  // [n_tiles*32][n_tiles*64] the same weights, [bin][sample]
+  const float* gmel;     // [batch][n_frames][128] d loss / d mel
+  const int* melt_off;   // [n_tiles*32] the mel bank by bin
+  const int* melt_len;
+  const int* melt_m;
+  const float* melt_w;
+  int n_y, batch, hop, n_fft, k_rows, n_tiles, rpc, n_frames, total_rows, seg;
+  float* part;           // [workgroups][seg] scratch: the overlap-added frame gradients of each workgroup's rows
+  float* gy;             // [batch][n_y] out
+};
+// workgroups and image length for `batch` clips; the limits of the kernel (0 = fits, else the message is set)
+int short_vjp_geometry(int n_fft, int hop, int rpc, int n_tiles, int batch, int* n_wgs, int* seg);
+int launch_short_vjp(const ShortVjpArgs& a, hipStream_t st);
 // mfcc_fused.hip
 std::vector<int> build_groups(int n_y, int n_frames, int up);
 int launch_fused(const MfccPlan* p, const void* wav, int fmt, const int* n_valid, int batch, hipStream_t st);

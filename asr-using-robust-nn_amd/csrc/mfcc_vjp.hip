@@ -2,6 +2,7 @@
 // (lipasr_mfcc_plan_vjp, lipasr_mfcc_plan_resample_vjp; the plan glue is in mfcc.hip).  With per-clip lengths the launchers hand
 // over to mfcc_vjp_ragged.hip.
 #include "mfcc_vjp.h"
+#include "mfcc_plan.h"
 
 namespace lipasr {
 
@@ -13,13 +14,30 @@ __global__ __launch_bounds__(256) void copy_cut_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-int launch_mfcc_vjp(const MfccVjpArgs& a, hipStream_t st, const int* n_valid, int sr_in, int n_samp_max) {
+// LDS of mfcc_vjp_db_kernel: the cotangent of one clip
+static int vjp_db_lds(const MfccVjpArgs& a, size_t* lds) {
   const int Tc = std::min(a.n_frames, a.L);
-  const size_t lds = (size_t)kNMfcc * Tc * sizeof(float);
-  if (lds > 40 * 1024) {
-    set_error("lipasr_mfcc_plan_vjp: utterance_length %d with %d frames needs %zu bytes of LDS", a.L, a.n_frames, lds);
+  *lds = (size_t)kNMfcc * Tc * sizeof(float);
+  if (*lds > 40 * 1024) {
+    set_error("lipasr_mfcc_plan_vjp: utterance_length %d with %d frames needs %zu bytes of LDS", a.L, a.n_frames, *lds);
     return LIPASR_EUNSUPPORTED;
   }
+  return LIPASR_OK;
+}
+
+int launch_mfcc_vjp_db(const MfccVjpArgs& a, hipStream_t st) {
+  size_t lds;
+  const int rc = vjp_db_lds(a, &lds);
+  if (rc != LIPASR_OK) return rc;
+  hipLaunchKernelGGL(mfcc_vjp_db_kernel<false>, dim3(a.batch), dim3(256), lds, st, a);
+  LP_LAUNCH_CHECK();
+  return LIPASR_OK;
+}
+
+int launch_mfcc_vjp(const MfccVjpArgs& a, hipStream_t st, const int* n_valid, int sr_in, int n_samp_max) {
+  size_t lds;
+  const int rc = vjp_db_lds(a, &lds);
+  if (rc != LIPASR_OK) return rc;
   const dim3 fold_grid((a.n_y + 255) / 256, a.batch);
   if (n_valid) return launch_mfcc_vjp_ragged(a, lds, n_valid, sr_in, n_samp_max, st);
   hipLaunchKernelGGL(mfcc_vjp_db_kernel<false>, dim3(a.batch), dim3(256), lds, st, a);

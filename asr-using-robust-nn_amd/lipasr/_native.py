@@ -118,6 +118,7 @@ PROTOTYPES = {
     "lipasr_mfcc_plan_from_22k": (i32, [c_h, c_f, i32, i32, i32, c_f, c_f, c_f, c_s]),
     "lipasr_mfcc_plan_vjp": (i32, [c_h, c_f, i32, i32, i32, c_f, c_f, c_f, i32, c_s]),
     "lipasr_mfcc_plan_resample_vjp": (i32, [c_h, c_f, i32, c_f, c_s]),
+    "lipasr_mfcc_plan_vjp_short": (i32, [c_h, c_f, i32, i32, i32, c_f, c_f, c_f, i32, c_s]),
     "lipasr_mfcc_plan_vjp_ragged": (i32, [c_h, c_f, i32, c_f, i32, i32, i32, c_f, c_f, c_f, i32, c_s]),
     "lipasr_mfcc_plan_resample_ragged": (i32, [c_h, c_f, i32, c_f, i32, c_f, c_s]),
     "lipasr_mfcc_plan_from_22k_ragged": (i32, [c_h, c_f, c_f, i32, i32, c_f, c_f, c_f, c_s]),

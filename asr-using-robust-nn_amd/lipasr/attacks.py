@@ -10,7 +10,8 @@ backward to the input and the sign step fused into the last backward GEMM's epil
 ``WaveformClassifier`` puts the MFCC stage in front of the model: the same two attacks then perturb the AUDIO (eps in
 amplitude units), the gradient reaching the samples through the native backward pass of K1 (lipasr_mfcc_plan_vjp).  With
 ``lengths=`` a batch holds clips of different lengths, one per row (lipasr_mfcc_plan_vjp_ragged): the perturbation stays inside
-each clip and the rest of the row comes back untouched.
+each clip and the rest of the row comes back untouched.  Over a short-window extractor (Speaker recognition: n_fft = win_length =
+441, hop 220) the gradient goes through lipasr_mfcc_plan_vjp_short.
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.
@@ -143,7 +144,9 @@ class WaveformClassifier:
     ``lengths`` (features_device, predict*, loss_gradient*): int32 device tensor or array [B], the samples of each row that belong
     to its clip, counted at ``sr_in`` for EITHER domain (a 22 050 Hz row holds its clip in its first ceil(n * 22050 / sr_in)
     positions): clips of different lengths in one batch, each treated as if it were alone; the rest of a row is ignored and its
-    gradient is exactly 0.  None: every row is a whole clip, and every call is the one made without the keyword."""
+    gradient is exactly 0.  None: every row is a whole clip, and every call is the one made without the keyword.
+    A short-window extractor (``MfccExtractor(..., n_fft=441, hop=220)``, the Speaker-recognition features) sends the gradient
+    through ``MfccExtractor.vjp_short``; it has no per-clip lengths (``lengths=`` raises ValueError)."""
 
     def __init__(self, model, nb_classes, extractor=None, sr_in=16000, n_samp=16000, utterance_length=44, mean=None, scale=None,
                  domain="22k", clip_values=(-1.0, 1.0)):
@@ -176,6 +179,8 @@ class WaveformClassifier:
         """``lengths`` as the int32 device tensor [b] the extractor takes (None stays None)."""
         if lengths is None:
             return None
+        if getattr(self.extractor, "short_window", False):
+            raise ValueError("lengths=: a short-window extractor takes rows of one length (there is no per-clip-length short-window path)")
         t = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths).astype(np.int32))
         t = t.to(device=self.extractor.device, dtype=torch.int32).contiguous()
         if tuple(t.shape) != (b,):
@@ -221,7 +226,9 @@ class WaveformClassifier:
             f = self.features_device(xb, lb)
             gf = torch.empty_like(f)
             N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yb), xb.shape[0], N.ptr(gf), N.stream_ptr()))
-            if lb is None:
+            if getattr(ex, "short_window", False):
+                ex.vjp_short(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+            elif lb is None:
                 ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
             else:
                 ex.vjp_ragged(xb, gf, lb, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)

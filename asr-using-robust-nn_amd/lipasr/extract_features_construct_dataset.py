@@ -33,6 +33,8 @@ class MfccExtractor:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.h = N.get_handle(self.device.index)
         self.sr_in, self.n_samp, self.batch_max = int(sr_in), int(n_samp), int(batch_max)
+        self.n_fft, self.hop = int(n_fft), int(hop)
+        self.short_window = (self.n_fft, self.hop) != (2048, 512)  # the plan runs the DFT-contraction path
         plan = N.c_h()
         N.check(N.lib.lipasr_mfcc_create(self.h.h, self.sr_in, self.n_samp, self.batch_max, int(n_fft), int(hop), C.byref(plan)))
         self._plan = plan
@@ -140,7 +142,7 @@ class MfccExtractor:
         scale: the float64 StandardScaler scale the forward applied, or None.  reuse_forward=True: this extractor's last call
         was the forward on exactly this ``sig`` on the current stream; its intermediates are read, the bits are the same.
         2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED).  Clips of different lengths
-        in one launch, int16 rows and clips shorter than the reflect padding: ``vjp_ragged``."""
+        in one launch, int16 rows and clips shorter than the reflect padding: ``vjp_ragged``; short-window extractors: ``vjp_short``."""
         if self._plan is None:
             raise RuntimeError("MfccExtractor used after close()")
         if domain not in ("input", "22k"):
@@ -163,6 +165,34 @@ class MfccExtractor:
         flags = (1 if reuse_forward else 0) | (2 if sig.dtype == torch.int16 else 0) | (4 if n_valid is not None else 0)
         N.check(N.lib.lipasr_mfcc_plan_vjp(self._plan, N.ptr(sig), dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat), N.ptr(out),
                                            flags, N.stream_ptr()))
+        return out
+
+    def vjp_short(self, sig, g_feat, utterance_length, scale=None, domain="22k", reuse_forward=False, out=None):
+        """``vjp`` for a short-window extractor (n_fft / hop other than 2048 / 512; lipasr_mfcc_plan_vjp_short): the gradient w.r.t.
+        ``sig`` of <features(sig), g_feat>, float32 rows of one length.  domain="22k": sig [B, n_y] (what ``from_22k`` takes);
+        domain="input": sig [B, n_samp] at sr_in.  scale and reuse_forward as in ``vjp``.  A 2048/512 extractor raises
+        LipasrError(EUNSUPPORTED): ``vjp`` is for those."""
+        if self._plan is None:
+            raise RuntimeError("MfccExtractor used after close()")
+        if domain not in ("input", "22k"):
+            raise ValueError(f"domain={domain!r}: 'input' or '22k'")
+        dom = 0 if domain == "input" else 1
+        n = self.n_samp if dom == 0 else self.n_y
+        b = sig.shape[0]
+        if sig.dim() != 2 or sig.shape[1] != n or not sig.is_contiguous():
+            raise ValueError(f"sig must be contiguous [B, {n}] for domain {domain!r}, got {tuple(sig.shape)}")
+        if sig.dtype != torch.float32:
+            raise ValueError(f"sig must be float32, got {sig.dtype}")
+        if tuple(g_feat.shape) != (b, N_MFCC * utterance_length) or g_feat.dtype != torch.float32 or not g_feat.is_contiguous():
+            raise ValueError(f"g_feat must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
+        if scale is not None and (scale.dtype != torch.float64 or scale.numel() != N_MFCC * utterance_length):
+            raise ValueError("scale must be a float64 device tensor [20 * utterance_length]")
+        if out is None:
+            out = torch.empty(b, n, device=self.device)
+        elif tuple(out.shape) != (b, n) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 [{b}, {n}]")
+        N.check(N.lib.lipasr_mfcc_plan_vjp_short(self._plan, N.ptr(sig), dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat),
+                                                 N.ptr(out), 1 if reuse_forward else 0, N.stream_ptr()))
         return out
 
     def vjp_ragged(self, sig, g_feat, n_valid, utterance_length=STANDARD_UTTERANCE_LENGTH, scale=None, domain="input", reuse_forward=False,

@@ -11,6 +11,9 @@
 Constraints.py, the Lipschitz read-outs and the attacks are the same files as the voice-digit ones and are
 re-exported.  The window length is not a power of two (441 = 3^2 7^2), so the STFT runs on the short-window
 path of the MFCC plan (lipasr_mfcc_plan_ex: windowed real DFT as an fp32 MFMA contraction).
+
+White-box attacks over the AUDIO of the windows (``waveform_classifier``, ``white_box_audio_sweep``) run FGM / PGD through the
+native backward pass of that path (lipasr_mfcc_plan_vjp_short), as ``attack_eval --over audio`` does for the voice-digit clips.
 """
 import ctypes as C
 
@@ -67,6 +70,12 @@ class WindowMfcc:
     def __call__(self, windows, mean=None, scale=None, out=None):
         return self._ex.from_22k(windows, self.n_frames, mean, scale, out)
 
+    def vjp(self, windows, g_feat, scale=None, reuse_forward=False, out=None):
+        """Backward pass: the gradient w.r.t. ``windows`` [B, n_samp] of <self(windows), g_feat> (MfccExtractor.vjp_short).
+        scale: the float64 StandardScaler scale the forward applied; reuse_forward=True: the last call was the forward on these
+        windows on the current stream."""
+        return self._ex.vjp_short(windows, g_feat, self.n_frames, scale, domain="22k", reuse_forward=reuse_forward, out=out)
+
 
 _window_mfcc = {}
 
@@ -115,6 +124,58 @@ def load_audio_dataset_and_labels(filenames, labels):
         return np.zeros((0, N_FEATURES)), np.array(local_labels)
     feats = mfcc_windows(np.concatenate(windows, axis=0))
     return feats.cpu().numpy().astype(np.float64), np.array(local_labels)
+
+
+def waveform_classifier(model, mean=None, scale=None, batch_max=None, clip_values=(-1, 1)):
+    """``attacks.WaveformClassifier`` over [B, 22050] windows: window -> 441/220 MFCC (2020) -> optional StandardScaler affine ->
+    the 20-speaker model.  FastGradientMethod / ProjectedGradientDescent with this estimator perturb the audio of the windows."""
+    from .attacks import WaveformClassifier
+
+    if not isinstance(model, Model):
+        raise TypeError("model must be a lipasr.keras.Model")
+    ex = WindowMfcc(batch_max=model._max_batch if batch_max is None else batch_max, device=model._device)
+    return WaveformClassifier(model, N_SPEAKERS, extractor=ex._ex, utterance_length=N_FRAMES, mean=mean, scale=scale, domain="22k",
+                              clip_values=clip_values)
+
+
+def white_box_audio_sweep(models, train_data, val_data, test_filenames, test_labels, kind="fgsm", grid=None, points=None, limit=None,
+                          **attack_kw):
+    """The Speaker-recognition counterpart of attack_eval.white_box_sweep(over="audio"): FGM (kind="fgsm") or PGD ("pgd") over the
+    1-s windows of ``test_filenames`` (load_audio_dataset_and_labels' slicing, ``test_labels`` [files] class indices repeated per
+    window).  Features are standardised with the statistics of (train, val, the clean window MFCCs), fused into the extraction;
+    eps is an amplitude, iterates stay in [-1, 1]; grid point 0 is the clean accuracy.  -> (grid, {name: accuracies})."""
+    from . import attacks as A
+    from .attack_eval import AUDIO_SIGMAS, accuracy
+
+    if kind not in ("fgsm", "pgd"):
+        raise ValueError(f"white-box attacks over audio are fgsm and pgd, not {kind!r}")
+    files = list(test_filenames[:limit] if limit else test_filenames)
+    file_labels = list(test_labels[:limit] if limit else test_labels)
+    windows, labels = [], []
+    for path, lab in zip(files, file_labels):
+        w = split_windows(_load_22k(path))
+        windows.append(w)
+        labels.extend([int(lab)] * len(w))
+    if not windows or not labels:
+        raise ValueError("white_box_audio_sweep: the files hold no whole 1-s window")
+    x = A._to_dev(np.concatenate(windows, axis=0))
+    onehot = np.zeros((len(labels), N_SPEAKERS), dtype=np.float32)
+    onehot[np.arange(len(labels)), labels] = 1.0
+    clean = mfcc_windows(x)
+    sc = A.StandardScaler().fit(torch.cat([A._to_dev(train_data), A._to_dev(val_data), clean]))
+    grid = list(AUDIO_SIGMAS if grid is None else grid)[:points]
+    cls = A.FastGradientMethod if kind == "fgsm" else A.ProjectedGradientDescent
+    acc = {name: [] for name in models}
+    clfs = {name: waveform_classifier(model, sc.mean_, sc.scale_, batch_max=min(model._max_batch, x.shape[0])) for name, model in models.items()}
+    for item in grid:
+        for name, clf in clfs.items():
+            adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x) if item != 0 else x
+            a = accuracy(clf.predict_device(adv).cpu().numpy(), onehot)
+            acc[name].append(a)
+            print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
+    for clf in clfs.values():
+        clf.extractor.close()
+    return grid, {k: np.asarray(v) for k, v in acc.items()}
 
 
 def get_file_names_and_labels(file_path):

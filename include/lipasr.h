@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 540.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 550.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -17,6 +17,8 @@
  * lipasr_mfcc_plan_resample_ragged, lipasr_mfcc_plan_from_22k_ragged.
  * 540: test hooks of the GEMM selector: lipasr_debug_gemm (the stand-alone product in any arithmetic mode), lipasr_debug_gemm_launches
  * and lipasr_debug_group_launches (launch counters per kernel instance).
+ * 550: the backward pass of the short-window MFCC plans (n_fft = win_length = 441, hop 220 of Speaker recognition):
+ * lipasr_mfcc_plan_vjp_short.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -495,6 +497,25 @@ int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batc
 int lipasr_mfcc_plan_vjp_ragged(lipasr_mfcc_t p, const void* sig, int sample_format, const int* n_valid, int domain,
                                 int batch, int utterance_length, const double* affine_scale, const float* g_feat,
                                 float* g_sig, int flags /* bit 0: reuse the forward */, lipasr_stream_t stream);
+/* The backward pass for the SHORT-WINDOW plans (lipasr_mfcc_plan_ex / lipasr_mfcc_create with n_fft, hop other than 2048, 512: the
+ * Speaker-recognition features, n_fft = win_length = 441, hop 220).  Arguments, domains, affine_scale and flags bit 0 mean what
+ * they mean for lipasr_mfcc_plan_vjp; rows are float32 and of one length (no other flag bit).  The chain: Gc = g / scale, Gdbc =
+ * D^T Gc, the top_db floor with the floored sum handed to the first clip maximum, Gmel = Gdb (10/ln 10) / mel where mel > 1e-10
+ * (the many empty mel bands of a small n_fft sit at -100 dB and receive nothing) -- the kernel of the 2048/512 chain as it is --
+ * then, per 32 consecutive frame rows of the forward's padded layout: X = frames T recomputed on the fp32 matrix instruction
+ * against the forward's folded table, GP = W^T Gmel from the CSR mel bank by bin, Z = 2 GP X, a second contraction over the bins
+ * against the same table (S[n] = sum_b Zre[b] Tre[n][b], A[n] = sum_b Zim[b] Tim[n][b]), frame sample n <- S[n] + A[n] and
+ * N - n <- S[n] - A[n] (2 S[n] where n pairs with itself; the window is inside the table), overlap-add in ascending frame order
+ * (frames with an all-zero cotangent row are left out: their samples receive exactly 0), the sum of the two workgroup images that
+ * cover a padded position, the adjoint of the single reflection (g_y[i] = gyp[i + pad] + gyp[pad - i] for 1 <= i <= pad, +
+ * gyp[pad + 2 (n_y - 1) - i] for n_y - 1 - pad <= i <= n_y - 2, pad = n_fft / 2), and for domain 0 the adjoint of the resampler.
+ * LIPASR_EUNSUPPORTED with a message: a 2048/512 plan (lipasr_mfcc_plan_vjp is for those, and keeps refusing short-window plans),
+ * n_fft > 33 hop (more than two images of 32 frames would overlap), more than 512 of min(frames, utterance_length).  Fixed
+ * summation order and no floating-point atomics (two calls give the same bits), an all-zero clip gives an all-zero gradient, no
+ * host synchronisation, workspaces allocated by the first call (make it outside a graph capture). */
+int lipasr_mfcc_plan_vjp_short(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length,
+                               const double* affine_scale, const float* g_feat, float* g_sig, int flags,
+                               lipasr_stream_t stream);
 /* The two halves of lipasr_mfcc_extract with n_valid (same semantics as above; composed they give its bits).  _resample_ragged
  * leaves zeros from int(n r) to the end of every row of y [batch][n_y]; _from_22k_ragged reads a row's first ceil(n r)
  * positions, position int(n r) as the zero fix_length appends. */
