@@ -5,8 +5,9 @@
 //   2. stft_bdft_kernel (stft_bdft.hip)           reflect-padded Hann frames -> block-DFT on the matrix pipe -> power -> mel -> dB
 //   3. dct_kernel (stft_mel.hip)                  top_db floor, DCT-II 128 -> 20, layout, optional StandardScaler affine
 // Every other variant (fp32 / VALU resamplers, Stockham and short-window STFTs, the fused resample -> STFT kernel of
-// mfcc_fused.hip) is chosen in ONE place, pick_mfcc_path below; plan_run, plan_resample, plan_from_22k, plan_vjp, plan_vjp_short and their per-clip-length forms ask it once
-// and hand the kinds to the launchers of mfcc_plan.h.  This file holds no stage kernel except add_noise_kernel.
+// mfcc_fused.hip) is chosen in ONE place, pick_mfcc_path below; plan_run, plan_resample, plan_from_22k, their per-clip-length forms
+// and plan_vjp (the one backward chain behind lipasr_mfcc_plan_vjp, _vjp_short and _vjp_ragged) ask it once and hand the kinds to
+// the launchers of mfcc_plan.h.  This file holds no stage kernel except add_noise_kernel.
 #include "mfcc_plan.h"
 #include <memory>
 
@@ -319,21 +320,25 @@ static int plan_run(MfccPlan* p, const void* wav, int fmt, const int* n_valid, i
 }
 
 // ---- backward pass ----
-static int vjp_unsupported(const char* fn, const MfccPlan* p) {
-  if (p->dft) {
-    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d (short-window plans: "
-              "lipasr_mfcc_plan_vjp_short)", fn, p->n_fft, p->hop);
-    return LIPASR_EUNSUPPORTED;
-  }
-  if (p->n_y <= kNFft) {
-    set_error("%s: the backward pass needs clips longer than the reflect padding (n_y %d <= %d)", fn, p->n_y, kNFft);
-    return LIPASR_EUNSUPPORTED;
+// what both kinds of plan keep for the backward pass: the plain DCT rows, Gmel, g_y and the partial images of the middle stage
+// (n_part floats: [batch_max][vj_groups][kVjSeg] for the 2048/512 kernels, [workgroups][seg] for the short-window one)
+static int vjp_workspaces(const char* fn, MfccPlan* p, size_t n_part) {
+  int rc;
+  if (!p->d_dct_rows && (rc = upload(&p->d_dct_rows, dct_matrix())) != LIPASR_OK) return rc;
+  const size_t ngm = (size_t)p->batch_max * p->n_frames * kNMels, ngy = (size_t)p->batch_max * p->n_y;
+  if ((!p->d_gmel && hipMalloc(&p->d_gmel, ngm * sizeof(float)) != hipSuccess) ||
+      (!p->d_part && hipMalloc(&p->d_part, n_part * sizeof(float)) != hipSuccess) ||
+      (!p->d_gy && hipMalloc(&p->d_gy, ngy * sizeof(float)) != hipSuccess)) {
+    (void)hipGetLastError();
+    set_error("%s: intermediate allocation failed", fn);
+    return LIPASR_ENOMEM;
   }
   return LIPASR_OK;
 }
 
-static int vjp_prepare(MfccPlan* p) {
-  if (p->d_gmel) return LIPASR_OK;
+// 2048/512 plans, first call: the mel filter of every bin's run, and the workspaces
+static int vjp_prepare(const char* fn, MfccPlan* p) {
+  if (p->vj_ready) return LIPASR_OK;
   DeviceGuard g(p->ctx->device);
   p->vj_groups = (p->n_frames + kVjFrames - 1) / kVjFrames;
   MelPairs mp = mel_pairs();
@@ -342,16 +347,8 @@ static int vjp_prepare(MfccPlan* p) {
     for (int i = 0; i < mp.len[m]; ++i) run[mp.start[m] + i] = m;
   int rc;
   if (!p->d_bin_run && (rc = upload(&p->d_bin_run, run)) != LIPASR_OK) return rc;
-  if (!p->d_dct_rows && (rc = upload(&p->d_dct_rows, dct_matrix())) != LIPASR_OK) return rc;
-  const size_t ngm = (size_t)p->batch_max * p->n_frames * kNMels, npart = (size_t)p->batch_max * p->vj_groups * kVjSeg,
-               ngy = (size_t)p->batch_max * p->n_y;
-  if ((!p->d_part && hipMalloc(&p->d_part, npart * sizeof(float)) != hipSuccess) ||
-      (!p->d_gy && hipMalloc(&p->d_gy, ngy * sizeof(float)) != hipSuccess) ||
-      hipMalloc(&p->d_gmel, ngm * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("lipasr_mfcc_plan_vjp: intermediate allocation failed");
-    return LIPASR_ENOMEM;
-  }
+  if ((rc = vjp_workspaces(fn, p, (size_t)p->batch_max * p->vj_groups * kVjSeg)) != LIPASR_OK) return rc;
+  p->vj_ready = true;
   return LIPASR_OK;
 }
 
@@ -408,50 +405,10 @@ static int plan_resample_vjp(MfccPlan* p, const float* gy, int batch, float* gx,
   return launch_resample_vjp(a, gy, gx, batch, st);
 }
 
-static void fill_vjp_args(const MfccPlan* p, const float* y, int batch, int L, const double* as, const float* g_feat, float* gy,
-                          MfccVjpArgs* a) {
-  a->y = y; a->n_y = p->n_y; a->n_frames = p->n_frames; a->batch = batch; a->L = L;
-  a->db = p->d_db; a->fmax = p->d_fmax; a->g_feat = g_feat; a->aff_scale = as; a->dct_rows = p->d_dct_rows;
-  a->hann = p->d_hann; a->tw = reinterpret_cast<const float2*>(p->d_tw);
-  a->mel_wlo = p->d_mel_wlo; a->mel_whi = p->d_mel_whi; a->bin_run = p->d_bin_run;
-  a->gmel = p->d_gmel; a->part = p->d_part; a->n_groups = p->vj_groups;
-  a->gy = gy;
-}
-
-static int plan_vjp(MfccPlan* p, const float* sig, int domain, int batch, int L, const double* as, const float* g_feat, float* g_sig,
-                    int flags, hipStream_t st) {
-  LP_CHECK_ARG(sig && g_feat && g_sig, "lipasr_mfcc_plan_vjp: null argument");
-  LP_CHECK_ARG(domain == 0 || domain == 1, "lipasr_mfcc_plan_vjp: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", domain);
-  LP_CHECK_ARG((flags & ~7) == 0, "lipasr_mfcc_plan_vjp: unknown flag bits %d", flags);
-  if (flags & 6) {
-    set_error("lipasr_mfcc_plan_vjp: int16 input and per-clip lengths have no backward pass (float32 rows of one length only)");
-    return LIPASR_EUNSUPPORTED;
-  }
-  int rc = vjp_unsupported("lipasr_mfcc_plan_vjp", p);
-  if (rc != LIPASR_OK) return rc;
-  if ((rc = vjp_prepare(p)) != LIPASR_OK) return rc;
-  const MfccPath path = pick_mfcc_path(p, domain == 0 ? sig : nullptr, 0, false);
-  // the plan's intermediates are the caller's forward only if that ran the three-kernel form (the fused resample -> STFT kernel
-  // leaves no d_y) with the stage mask's profiling switches off
-  const bool reuse = (flags & 1) && !(domain == 0 && prefers_fused(p)) && !(p->stage_mask & (SM_SKIP_FFT | SM_SKIP_MEL));
-  const float* y = sig;
-  if (domain == 0) {
-    if (!reuse && (rc = launch_resample(p, path.resampler, sig, 0, nullptr, batch, p->d_y, st)) != LIPASR_OK) return rc;
-    y = p->d_y;
-  }
-  if (!reuse && (rc = launch_from_22k(p, path.stft, y, nullptr, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
-  MfccVjpArgs a;
-  fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
-  if ((rc = launch_mfcc_vjp(a, st)) != LIPASR_OK) return rc;
-  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st);
-  return LIPASR_OK;
-}
-
-// ---- short-window plans (dft_mel_kernel's forward): the same chain with dft_vjp_kernel in the middle ----
-// tables and workspaces of the first call: the plain DCT rows, the folded table with bins and samples exchanged (unit-stride
-// B-operand loads of the second contraction), the CSR mel bank by bin, Gmel, the workgroup images and g_y
-static int vjp_short_prepare(MfccPlan* p) {
-  if (p->d_dft_t) return LIPASR_OK;
+// short-window plans (dft_mel_kernel's forward), first call: the folded table with bins and samples exchanged (unit-stride
+// B-operand loads of the second contraction), the CSR mel bank by bin, and the workspaces
+static int vjp_short_prepare(const char* fn, MfccPlan* p) {
+  if (p->vj_ready) return LIPASR_OK;
   DeviceGuard g(p->ctx->device);
   int n_wgs, seg, rc;
   if ((rc = short_vjp_geometry(p->n_fft, p->hop, p->dft_rpc, p->dft_tiles, p->batch_max, &n_wgs, &seg)) != LIPASR_OK) return rc;
@@ -476,54 +433,11 @@ static int vjp_short_prepare(MfccPlan* p) {
     len[b] = (int)mm.size() - off[b];
   }
   if (mm.empty()) { mm.push_back(0); ww.push_back(0.0f); }
-  if ((!p->d_dct_rows && (rc = upload(&p->d_dct_rows, dct_matrix())) != LIPASR_OK) || (rc = upload(&p->d_melt_off, off)) != LIPASR_OK ||
-      (rc = upload(&p->d_melt_len, len)) != LIPASR_OK || (rc = upload(&p->d_melt_m, mm)) != LIPASR_OK ||
-      (rc = upload(&p->d_melt_w, ww)) != LIPASR_OK)
+  if ((rc = upload(&p->d_melt_off, off)) != LIPASR_OK || (rc = upload(&p->d_melt_len, len)) != LIPASR_OK ||
+      (rc = upload(&p->d_melt_m, mm)) != LIPASR_OK || (rc = upload(&p->d_melt_w, ww)) != LIPASR_OK ||
+      (rc = vjp_workspaces(fn, p, (size_t)n_wgs * seg)) != LIPASR_OK || (rc = upload(&p->d_dft_t, TT)) != LIPASR_OK)
     return rc;
-  const size_t ngm = (size_t)p->batch_max * p->n_frames * kNMels, npart = (size_t)n_wgs * seg, ngy = (size_t)p->batch_max * p->n_y;
-  if ((!p->d_gmel && hipMalloc(&p->d_gmel, ngm * sizeof(float)) != hipSuccess) ||
-      (!p->d_part && hipMalloc(&p->d_part, npart * sizeof(float)) != hipSuccess) ||
-      (!p->d_gy && hipMalloc(&p->d_gy, ngy * sizeof(float)) != hipSuccess)) {
-    (void)hipGetLastError();
-    set_error("lipasr_mfcc_plan_vjp_short: intermediate allocation failed");
-    return LIPASR_ENOMEM;
-  }
-  return upload(&p->d_dft_t, TT);  // last: its presence marks the plan as prepared
-}
-
-static int plan_vjp_short(MfccPlan* p, const float* sig, int domain, int batch, int L, const double* as, const float* g_feat, float* g_sig,
-                          int flags, hipStream_t st) {
-  static const char* fn = "lipasr_mfcc_plan_vjp_short";
-  LP_CHECK_ARG(sig && g_feat && g_sig, "%s: null argument", fn);
-  LP_CHECK_ARG(domain == 0 || domain == 1, "%s: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", fn, domain);
-  LP_CHECK_ARG((flags & ~1) == 0, "%s: unknown flag bits %d", fn, flags);
-  if (!p->dft) {
-    set_error("%s: the short-window backward pass covers the plans made with n_fft, hop other than 2048, 512; this plan is 2048/512 "
-              "(lipasr_mfcc_plan_vjp)", fn);
-    return LIPASR_EUNSUPPORTED;
-  }
-  int rc = vjp_short_prepare(p);
-  if (rc != LIPASR_OK) return rc;
-  const MfccPath path = pick_mfcc_path(p, domain == 0 ? sig : nullptr, 0, false);
-  if (path.rc != LIPASR_OK) return path.rc;
-  const bool reuse = (flags & 1) != 0;  // (the stage mask's profiling switches do not reach dft_mel_kernel)
-  const float* y = sig;
-  if (domain == 0) {
-    if (!reuse && (rc = launch_resample(p, path.resampler, sig, 0, nullptr, batch, p->d_y, st)) != LIPASR_OK) return rc;
-    y = p->d_y;
-  }
-  if (!reuse && (rc = launch_from_22k(p, path.stft, y, nullptr, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
-  MfccVjpArgs a;
-  fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
-  if ((rc = launch_mfcc_vjp_db(a, st)) != LIPASR_OK) return rc;
-  ShortVjpArgs s;
-  s.y = y; s.table = p->d_dft; s.table_t = p->d_dft_t; s.gmel = p->d_gmel;
-  s.melt_off = p->d_melt_off; s.melt_len = p->d_melt_len; s.melt_m = p->d_melt_m; s.melt_w = p->d_melt_w;
-  s.n_y = p->n_y; s.batch = batch; s.hop = p->hop; s.n_fft = p->n_fft; s.k_rows = p->dft_krows; s.n_tiles = p->dft_tiles;
-  s.rpc = p->dft_rpc; s.n_frames = p->n_frames; s.total_rows = batch * p->dft_rpc; s.seg = 0;
-  s.part = p->d_part; s.gy = a.gy;
-  if ((rc = launch_short_vjp(s, st)) != LIPASR_OK) return rc;
-  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st);
+  p->vj_ready = true;
   return LIPASR_OK;
 }
 
@@ -566,43 +480,101 @@ static int plan_from_22k_ragged(MfccPlan* p, const float* y, const int* nv, int 
   return launch_from_22k(p, path.stft, y, nv, batch, L, am, as, out, st);
 }
 
-static int plan_vjp_ragged(MfccPlan* p, const void* sig, int fmt, const int* nv, int domain, int batch, int L, const double* as,
-                           const float* g_feat, float* g_sig, int flags, hipStream_t st) {
-  static const char* fn = "lipasr_mfcc_plan_vjp_ragged";
-  LP_CHECK_ARG(sig && nv && g_feat && g_sig, "%s: null argument", fn);
-  LP_CHECK_ARG(fmt == 0 || fmt == 1, "%s: sample format %d (0 = float32, 1 = int16 PCM)", fn, fmt);
-  LP_CHECK_ARG(domain == 0 || domain == 1, "%s: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", fn, domain);
-  LP_CHECK_ARG((flags & ~1) == 0, "%s: unknown flag bits %d", fn, flags);
-  if (p->dft) {
-    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d", fn, p->n_fft, p->hop);
-    return LIPASR_EUNSUPPORTED;
-  }
-  if (fmt == 1 && domain == 1) {
-    set_error("%s: int16 PCM rows are rows at the plan's input rate (domain 0); the 22 050 Hz signal is float32", fn);
-    return LIPASR_EUNSUPPORTED;
-  }
-  int rc = ragged_unsupported(fn, p);
+// ---- the backward chain.  The three entry points (lipasr_mfcc_plan_vjp, _vjp_short, _vjp_ragged) describe their call; what
+// differs between them is the named conditions of plan_vjp and nothing else ----
+enum VjpEntry { VJ_ONE_LENGTH, VJ_SHORT, VJ_RAGGED };
+struct VjpCall {
+  const char* fn;
+  VjpEntry entry;
+  const void* sig;     // rows at the plan's input rate (domain 0) or at 22 050 Hz (domain 1)
+  int fmt;             // 0: float32 samples, 1: int16 PCM
+  const int* n_valid;  // per-clip sample counts at the plan's input rate (device), VJ_RAGGED only
+  int domain, batch, L;
+  const double* scale;
+  const float* g_feat;
+  float* g_sig;
+  int flags;
+};
+
+static int plan_vjp(MfccPlan* p, const VjpCall& c, hipStream_t st) {
+  const char* fn = c.fn;
+  const int* nv = c.n_valid;
+  const int domain = c.domain, batch = c.batch, L = c.L;
+  int rc = plan_check(fn, p, batch, L);
   if (rc != LIPASR_OK) return rc;
-  const MfccPath path = pick_mfcc_path(p, domain == 0 ? sig : nullptr, fmt, true);
-  if (path.rc != LIPASR_OK) return path.rc;
-  if (domain == 0 && path.fused) {
+  LP_CHECK_ARG(c.sig && c.g_feat && c.g_sig && (nv || c.entry != VJ_RAGGED), "%s: null argument", fn);
+  LP_CHECK_ARG(c.fmt == 0 || c.fmt == 1, "%s: sample format %d (0 = float32, 1 = int16 PCM)", fn, c.fmt);
+  LP_CHECK_ARG(domain == 0 || domain == 1, "%s: domain %d (0 = the plan's input rate, 1 = 22 050 Hz)", fn, domain);
+  // allowed flag bits: 1 = reuse the caller's forward; the one-length entry also knows 2 and 4 by name, to refuse them
+  LP_CHECK_ARG((c.flags & ~(c.entry == VJ_ONE_LENGTH ? 7 : 1)) == 0, "%s: unknown flag bits %d", fn, c.flags);
+  if (c.flags & 6) {
+    set_error("%s: int16 input and per-clip lengths have no backward pass (float32 rows of one length only)", fn);
+    return LIPASR_EUNSUPPORTED;
+  }
+  // which plans the entry refuses
+  if (c.entry == VJ_SHORT && !p->dft) {
+    set_error("%s: the short-window backward pass covers the plans made with n_fft, hop other than 2048, 512; this plan is 2048/512 "
+              "(lipasr_mfcc_plan_vjp)", fn);
+    return LIPASR_EUNSUPPORTED;
+  }
+  if (c.entry != VJ_SHORT && p->dft) {
+    set_error("%s: the backward pass covers the 2048/512 plans; this plan has n_fft %d, hop %d%s", fn, p->n_fft, p->hop,
+              c.entry == VJ_ONE_LENGTH ? " (short-window plans: lipasr_mfcc_plan_vjp_short)" : "");
+    return LIPASR_EUNSUPPORTED;
+  }
+  if (c.entry == VJ_ONE_LENGTH && p->n_y <= kNFft) {
+    set_error("%s: the backward pass needs clips longer than the reflect padding (n_y %d <= %d)", fn, p->n_y, kNFft);
+    return LIPASR_EUNSUPPORTED;
+  }
+  if (c.entry == VJ_RAGGED) {
+    if (c.fmt == 1 && domain == 1) {
+      set_error("%s: int16 PCM rows are rows at the plan's input rate (domain 0); the 22 050 Hz signal is float32", fn);
+      return LIPASR_EUNSUPPORTED;
+    }
+    if ((rc = ragged_unsupported(fn, p)) != LIPASR_OK) return rc;
+  }
+  const MfccPath path = pick_mfcc_path(p, domain == 0 ? c.sig : nullptr, c.fmt, nv != nullptr);
+  // whether path.rc is checked: the one-length entry does not (float32 rows of one length always have a three-kernel form)
+  if (c.entry != VJ_ONE_LENGTH && path.rc != LIPASR_OK) return path.rc;
+  if (c.entry == VJ_RAGGED && domain == 0 && path.fused) {
     set_error("%s: this plan runs the fused resample -> STFT kernel for this input (row alignment, or plan key 2), which leaves no "
               "resampled signal behind for the backward pass", fn);
     return LIPASR_EUNSUPPORTED;
   }
-  if ((rc = vjp_prepare(p)) != LIPASR_OK) return rc;
-  // the caller's forward (lipasr_mfcc_extract with n_valid / lipasr_mfcc_plan_from_22k_ragged) left the plan's intermediates
-  const bool reuse = (flags & 1) && !(p->stage_mask & (SM_SKIP_FFT | SM_SKIP_MEL));
-  const float* y = static_cast<const float*>(sig);
+  if ((rc = c.entry == VJ_SHORT ? vjp_short_prepare(fn, p) : vjp_prepare(fn, p)) != LIPASR_OK) return rc;
+  // when the caller's forward may be reused: the plan's intermediates are that forward only if it ran with the stage mask's
+  // profiling switches off (they do not reach dft_mel_kernel) and, for the one-length entry, in the three-kernel form (the fused
+  // resample -> STFT kernel leaves no d_y; the ragged entry has refused that case above)
+  const bool reuse = (c.flags & 1) && (c.entry == VJ_SHORT || !(p->stage_mask & (SM_SKIP_FFT | SM_SKIP_MEL))) &&
+                     !(c.entry == VJ_ONE_LENGTH && domain == 0 && prefers_fused(p));
+  const float* y = static_cast<const float*>(c.sig);
   if (domain == 0) {
-    if (!reuse && (rc = launch_resample(p, path.resampler, sig, fmt, nv, batch, p->d_y, st)) != LIPASR_OK) return rc;
+    if (!reuse && (rc = launch_resample(p, path.resampler, c.sig, c.fmt, nv, batch, p->d_y, st)) != LIPASR_OK) return rc;
     y = p->d_y;
   }
   if (!reuse && (rc = launch_from_22k(p, path.stft, y, nv, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
   MfccVjpArgs a;
-  fill_vjp_args(p, y, batch, L, as, g_feat, domain == 0 ? p->d_gy : g_sig, &a);
-  if ((rc = launch_mfcc_vjp(a, st, nv, p->sr_in, p->n_samp)) != LIPASR_OK) return rc;
-  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, g_sig, st, nv);
+  a.y = y; a.n_y = p->n_y; a.n_frames = p->n_frames; a.batch = batch; a.L = L;
+  a.db = p->d_db; a.fmax = p->d_fmax; a.g_feat = c.g_feat; a.aff_scale = c.scale; a.dct_rows = p->d_dct_rows;
+  a.hann = p->d_hann; a.tw = reinterpret_cast<const float2*>(p->d_tw);
+  a.mel_wlo = p->d_mel_wlo; a.mel_whi = p->d_mel_whi; a.bin_run = p->d_bin_run;
+  a.gmel = p->d_gmel; a.part = p->d_part; a.n_groups = p->vj_groups;
+  a.gy = domain == 0 ? p->d_gy : c.g_sig;
+  // the middle stage: dB step, then dft_vjp_kernel (short window) or the Stockham adjoint, which takes the lengths
+  if (c.entry == VJ_SHORT) {
+    if ((rc = launch_mfcc_vjp_db(a, st)) != LIPASR_OK) return rc;
+    ShortVjpArgs s;
+    s.y = y; s.table = p->d_dft; s.table_t = p->d_dft_t; s.gmel = p->d_gmel;
+    s.melt_off = p->d_melt_off; s.melt_len = p->d_melt_len; s.melt_m = p->d_melt_m; s.melt_w = p->d_melt_w;
+    s.n_y = p->n_y; s.batch = batch; s.hop = p->hop; s.n_fft = p->n_fft; s.k_rows = p->dft_krows; s.n_tiles = p->dft_tiles;
+    s.rpc = p->dft_rpc; s.n_frames = p->n_frames; s.total_rows = batch * p->dft_rpc; s.seg = 0;
+    s.part = p->d_part; s.gy = a.gy;
+    rc = launch_short_vjp(s, st);
+  } else {
+    rc = nv ? launch_mfcc_vjp(a, st, nv, p->sr_in, p->n_samp) : launch_mfcc_vjp(a, st);
+  }
+  if (rc != LIPASR_OK) return rc;
+  if (domain == 0) return plan_resample_vjp(p, p->d_gy, batch, c.g_sig, st, nv);
   return LIPASR_OK;
 }
 
@@ -710,24 +682,22 @@ int lipasr_mfcc_plan_from_22k(lipasr_mfcc_t p, const float* y, int batch, int n_
 
 int lipasr_mfcc_plan_vjp(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length, const double* affine_scale,
                          const float* g_feat, float* g_sig, int flags, lipasr_stream_t stream) {
-  int rc = plan_check("lipasr_mfcc_plan_vjp", p, batch, utterance_length);
-  if (rc != LIPASR_OK) return rc;
-  return plan_vjp(p, sig, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+  return plan_vjp(p, {"lipasr_mfcc_plan_vjp", VJ_ONE_LENGTH, sig, 0, nullptr, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags},
+                  S(stream));
 }
 
 int lipasr_mfcc_plan_vjp_short(lipasr_mfcc_t p, const float* sig, int domain, int batch, int utterance_length, const double* affine_scale,
                                const float* g_feat, float* g_sig, int flags, lipasr_stream_t stream) {
-  int rc = plan_check("lipasr_mfcc_plan_vjp_short", p, batch, utterance_length);
-  if (rc != LIPASR_OK) return rc;
-  return plan_vjp_short(p, sig, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+  return plan_vjp(p, {"lipasr_mfcc_plan_vjp_short", VJ_SHORT, sig, 0, nullptr, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags},
+                  S(stream));
 }
 
 int lipasr_mfcc_plan_vjp_ragged(lipasr_mfcc_t p, const void* sig, int sample_format, const int* n_valid, int domain, int batch,
                                 int utterance_length, const double* affine_scale, const float* g_feat, float* g_sig, int flags,
                                 lipasr_stream_t stream) {
-  int rc = plan_check("lipasr_mfcc_plan_vjp_ragged", p, batch, utterance_length);
-  if (rc != LIPASR_OK) return rc;
-  return plan_vjp_ragged(p, sig, sample_format, n_valid, domain, batch, utterance_length, affine_scale, g_feat, g_sig, flags, S(stream));
+  return plan_vjp(p, {"lipasr_mfcc_plan_vjp_ragged", VJ_RAGGED, sig, sample_format, n_valid, domain, batch, utterance_length, affine_scale,
+                      g_feat, g_sig, flags},
+                  S(stream));
 }
 
 int lipasr_mfcc_plan_resample_ragged(lipasr_mfcc_t p, const void* wav, int sample_format, const int* n_valid, int batch, float* y,

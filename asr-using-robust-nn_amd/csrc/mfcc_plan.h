@@ -91,7 +91,8 @@ struct MfccPlan {
   // the kernel's fused top_db + DCT epilogue (lipasr_mfcc_plan_set key 4): off by default -- measured on batches that are not
   // cache-warm it loses to the separate dct_kernel (STFT 139 + 5 us against 120 + 19 us per 1024 clips, round 4)
   bool bd_fuse_dct = false;
-  // backward pass (lipasr_mfcc_plan_vjp, kernels in mfcc_vjp.hip): allocated at the first call
+  // backward pass (plan_vjp in mfcc.hip, kernels in mfcc_vjp.hip): allocated at the first call, which sets vj_ready last
+  bool vj_ready = false;
   float* d_gmel = nullptr;      // [batch_max][n_frames][128]
   float* d_part = nullptr;      // [batch_max][vj_groups][kVjSeg]
   float* d_gy = nullptr;        // [batch_max][n_y]
@@ -102,8 +103,8 @@ struct MfccPlan {
   float* d_rt_taps = nullptr;   // [rt_nt][down]
   int* d_rt_t0 = nullptr;       // [down]
   int rt_nt = 0, rt_t0min = 0, rt_t0max = 0;
-  // backward pass of the short-window path (lipasr_mfcc_plan_vjp_short, kernels in mfcc_vjp_short.hip): allocated at the first
-  // call, next to d_gmel / d_gy / d_dct_rows above; d_part then holds the workgroup images [workgroups][sv_seg]
+  // backward pass of the short-window path (lipasr_mfcc_plan_vjp_short, kernels in mfcc_vjp_short.hip): allocated at the same
+  // first call, next to d_gmel / d_gy / d_dct_rows above; d_part then holds the workgroup images [workgroups][sv_seg]
   float* d_dft_t = nullptr;     // [dft_tiles*32 bins][dft_tiles*64]: d_dft with bins and samples exchanged
   int* d_melt_off = nullptr;    // [dft_tiles*32]: the mel bank by bin (the CSR bank transposed), filters in ascending order
   int* d_melt_len = nullptr;

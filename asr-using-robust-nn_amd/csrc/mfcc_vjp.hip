@@ -1,6 +1,6 @@
 // K1 backward for clips of one length: the instances of the kernels in mfcc_vjp.h that read no length array, and the launchers
-// (lipasr_mfcc_plan_vjp, lipasr_mfcc_plan_resample_vjp; the plan glue is in mfcc.hip).  With per-clip lengths the launchers hand
-// over to mfcc_vjp_ragged.hip.
+// (plan_vjp in mfcc.hip is the one chain that calls them; lipasr_mfcc_plan_resample_vjp runs the last alone).  With per-clip
+// lengths the launchers hand over to mfcc_vjp_ragged.hip.
 #include "mfcc_vjp.h"
 #include "mfcc_plan.h"
 
@@ -35,13 +35,14 @@ int launch_mfcc_vjp_db(const MfccVjpArgs& a, hipStream_t st) {
 }
 
 int launch_mfcc_vjp(const MfccVjpArgs& a, hipStream_t st, const int* n_valid, int sr_in, int n_samp_max) {
-  size_t lds;
-  const int rc = vjp_db_lds(a, &lds);
+  if (n_valid) {
+    size_t lds;
+    const int rc = vjp_db_lds(a, &lds);
+    return rc != LIPASR_OK ? rc : launch_mfcc_vjp_ragged(a, lds, n_valid, sr_in, n_samp_max, st);
+  }
+  const int rc = launch_mfcc_vjp_db(a, st);
   if (rc != LIPASR_OK) return rc;
   const dim3 fold_grid((a.n_y + 255) / 256, a.batch);
-  if (n_valid) return launch_mfcc_vjp_ragged(a, lds, n_valid, sr_in, n_samp_max, st);
-  hipLaunchKernelGGL(mfcc_vjp_db_kernel<false>, dim3(a.batch), dim3(256), lds, st, a);
-  LP_LAUNCH_CHECK();
   hipLaunchKernelGGL(stft_vjp_kernel<false>, dim3(a.n_groups, a.batch), dim3(256), 0, st, a);
   LP_LAUNCH_CHECK();
   hipLaunchKernelGGL(stft_vjp_fold_kernel<false>, fold_grid, dim3(256), 0, st, a.part, a.n_groups, a.n_y, a.gy, n_valid, n_samp_max, sr_in,

@@ -179,7 +179,7 @@ class WaveformClassifier:
         """``lengths`` as the int32 device tensor [b] the extractor takes (None stays None)."""
         if lengths is None:
             return None
-        if getattr(self.extractor, "short_window", False):
+        if self.extractor.short_window:
             raise ValueError("lengths=: a short-window extractor takes rows of one length (there is no per-clip-length short-window path)")
         t = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths).astype(np.int32))
         t = t.to(device=self.extractor.device, dtype=torch.int32).contiguous()
@@ -226,7 +226,7 @@ class WaveformClassifier:
             f = self.features_device(xb, lb)
             gf = torch.empty_like(f)
             N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yb), xb.shape[0], N.ptr(gf), N.stream_ptr()))
-            if getattr(ex, "short_window", False):
+            if ex.short_window:
                 ex.vjp_short(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
             elif lb is None:
                 ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
@@ -635,50 +635,69 @@ class _SignAttack:
             return pa == yb.argmax(dim=1)
         return pa != est.predict_device(x0, logits=True, lengths=lens).argmax(dim=1)
 
-    def _generate_wave(self, xt, yt, lengths=None):
+    # ---- the restart driver.  A row backend is batch(s) -> (attack, success) for the rows starting at s: attack(xa, restart) does
+    # "start, then max_iter iterations" in place on xa, success(xa) is ART's compute_success_array on those rows.
+    def _feature_rows(self, xt, yt):
+        m = self.estimator.model
+        y_all = self._targets(m, xt, yt)
+        bs = min(self.batch_size, m._max_batch)
+
+        def batch(s):
+            x0, yb = xt[s:s + bs], y_all[s:s + bs]
+
+            def attack(xa, restart):
+                self._start(xa, x0, restart, s)
+                for _ in range(self.max_iter):
+                    self._step(m, xa, x0, yb, self.eps_step, self.eps)
+            return attack, lambda xa: self._success(m, x0, yb, xa)
+        return bs, batch
+
+    def _wave_rows(self, xt, yt, lengths):
         est = self.estimator
-        m = est.model
         est._check(xt)
         if self.targeted and yt is None:
             raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-        if self._draws is None:
-            self._draws = torch.zeros(1, dtype=torch.int32, device=xt.device)
         bs = min(self.batch_size, est._bs)
-        rows = range(0, xt.shape[0], bs)
         lt = est.lengths_device(lengths, xt.shape[0])
         mask_all = None if lt is None else est.clip_mask(lt)
         cut = lambda t, s: None if t is None else t[s:s + bs]
-        y_all = yt if yt is not None else torch.cat([self._labels(m, est.features_device(xt[s:s + bs].contiguous(), cut(lt, s)), None)
-                                                      for s in rows])
+        y_all = yt if yt is not None else torch.cat([self._labels(est.model, est.features_device(xt[s:s + bs].contiguous(), cut(lt, s)), None)
+                                                      for s in range(0, xt.shape[0], bs)])
         g = torch.empty(bs, xt.shape[1], device=xt.device)
+
+        def batch(s):
+            x0, yb = xt[s:s + bs].contiguous(), y_all[s:s + bs]
+            gb, lb, mb = g[:x0.shape[0]], cut(lt, s), cut(mask_all, s)
+            return (lambda xa, restart: self._wave_attack_rows(est, xa, x0, yb, restart, s, gb, lb, mb),
+                    lambda xa: self._wave_success(est, x0, yb, xa, lb))
+        return bs, batch
+
+    def _generate_restarts(self, xt, bs, batch):
+        rows = range(0, xt.shape[0], bs)
         restarts = max(1, self.num_random_init)
-        whole = isinstance(self, FastGradientMethod)  # ART: FGM keeps the best whole restart, PGD the successful rows of each
-        best, best_rate = None, None
         adv = torch.empty_like(xt)
-        for r in (range(restarts) if whole else (0,)):
-            cur = adv if r == 0 else torch.empty_like(xt)
+        if not self._best_whole_restart:  # restart 0 is kept, every later restart overwrites the rows where it succeeds
             for s in rows:
-                x0, yb, out = xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs]
-                gb, lb, mb = g[:x0.shape[0]], cut(lt, s), cut(mask_all, s)
-                if whole:
-                    self._wave_attack_rows(est, out, x0, yb, r, s, gb, lb, mb)
-                    continue
-                xa = torch.empty_like(x0)
-                for rr in range(restarts):
-                    self._wave_attack_rows(est, xa, x0, yb, rr, s, gb, lb, mb)
-                    if rr == 0:
+                attack, success = batch(s)
+                out = adv[s:s + bs]
+                xa = torch.empty_like(out)
+                for r in range(restarts):
+                    attack(xa, r)
+                    if r == 0:
                         out.copy_(xa)
                     else:
-                        ok = self._wave_success(est, x0, yb, xa, lb)
+                        ok = success(xa)
                         out[ok] = xa[ok]
-            if whole and restarts > 1:
-                rate = float(torch.cat([self._wave_success(est, xt[s:s + bs].contiguous(), y_all[s:s + bs], cur[s:s + bs], cut(lt, s))
-                                        for s in rows]).float().mean())
+            return adv
+        best, best_rate = adv, None  # the whole restart with the highest success rate, the first on ties
+        for r in range(restarts):
+            cur = adv if r == 0 else torch.empty_like(xt)
+            for s in rows:
+                batch(s)[0](cur[s:s + bs], r)
+            if restarts > 1:
+                rate = float(torch.cat([batch(s)[1](cur[s:s + bs]) for s in rows]).float().mean())
                 if best_rate is None or rate > best_rate:
                     best, best_rate = cur, rate
-            else:
-                best = cur
-        self._draws += 1
         return best
 
     def generate_device(self, xt, yt=None, lengths=None):
@@ -687,10 +706,8 @@ class _SignAttack:
         the perturbation stays inside the clip and the rest of each row is returned as it came."""
         if lengths is not None and not self._wave:
             raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
-        if self._wave:
-            return self._generate_wave(xt, yt, lengths)
         m = self.estimator.model
-        if self._default_path:  # the reference's call: exactly the launches of round 5
+        if self._default_path and not self._wave:  # the reference's call: exactly the launches of round 5
             adv = xt.clone()
             bs = min(self.batch_size, m._max_batch)
             for s in range(0, xt.shape[0], bs):
@@ -701,8 +718,7 @@ class _SignAttack:
             return adv
         if self._draws is None:
             self._draws = torch.zeros(1, dtype=torch.int32, device=xt.device)
-        y_all = self._targets(m, xt, yt)
-        adv = self._generate_lp(m, xt, y_all)
+        adv = self._generate_restarts(xt, *(self._wave_rows(xt, yt, lengths) if self._wave else self._feature_rows(xt, yt)))
         self._draws += 1  # the next generate() draws fresh random starts
         return adv
 
@@ -720,6 +736,8 @@ class FastGradientMethod(_SignAttack):
     clipping on the reference's call), g / ||g||_1 or g / ||g||_2, projected on the eps ball around x as ART does.
     num_random_init = k > 1 keeps the whole restart with the highest success rate (the first on ties: ART's compute_success)."""
 
+    _best_whole_restart = True
+
     def __init__(self, estimator, eps=0.3, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps, 1, batch_size, norm, targeted, num_random_init)
 
@@ -727,29 +745,13 @@ class FastGradientMethod(_SignAttack):
         N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
                                              self.eps, math.inf, N.stream_ptr()))
 
-    def _generate_lp(self, m, xt, y_all):
-        bs = min(self.batch_size, m._max_batch)
-        best, best_rate = None, None
-        for r in range(max(1, self.num_random_init)):
-            adv = torch.empty_like(xt)
-            for s in range(0, xt.shape[0], bs):
-                x0, xa, yb = xt[s:s + bs], adv[s:s + bs], y_all[s:s + bs]
-                self._start(xa, x0, r, s)
-                self._step(m, xa, x0, yb, self.eps, self.eps)
-            if self.num_random_init > 1:
-                rate = float(torch.cat([self._success(m, xt[s:s + bs], y_all[s:s + bs], adv[s:s + bs])
-                                        for s in range(0, xt.shape[0], bs)]).float().mean())
-                if best_rate is None or rate > best_rate:
-                    best, best_rate = adv, rate
-            else:
-                best = adv
-        return best
-
 
 class ProjectedGradientDescent(_SignAttack):
     """ART ProjectedGradientDescent(estimator=, eps=) (attacks.py:657-661): max_iter steps of
     x <- x0 + P_eps(x + eps_step * d(grad) - x0), d and P as FastGradientMethod's.  With num_random_init = k > 0, restart 0's
     result is kept and every later restart overwrites the rows where it succeeds (ART's compute_success_array)."""
+
+    _best_whole_restart = False
 
     def __init__(self, estimator, eps=0.3, eps_step=0.1, max_iter=100, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init)
@@ -758,23 +760,6 @@ class ProjectedGradientDescent(_SignAttack):
         for _ in range(self.max_iter):
             N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
                                                  self.eps_step, self.eps, N.stream_ptr()))
-
-    def _generate_lp(self, m, xt, y_all):
-        bs = min(self.batch_size, m._max_batch)
-        adv = torch.empty_like(xt)
-        for s in range(0, xt.shape[0], bs):
-            x0, yb, out = xt[s:s + bs], y_all[s:s + bs], adv[s:s + bs]
-            xa = torch.empty_like(x0)
-            for r in range(max(1, self.num_random_init)):
-                self._start(xa, x0, r, s)
-                for _ in range(self.max_iter):
-                    self._step(m, xa, x0, yb, self.eps_step, self.eps)
-                if r == 0:
-                    out.copy_(xa)
-                else:
-                    ok = self._success(m, x0, yb, xa)
-                    out[ok] = xa[ok]
-        return adv
 
 
 def sign_step(x_adv, x0, g, alpha, eps):

@@ -135,14 +135,9 @@ class MfccExtractor:
                                                        N.ptr(mean), N.ptr(scale), N.ptr(out), N.stream_ptr()))
         return out
 
-    def vjp(self, sig, g_feat, utterance_length=STANDARD_UTTERANCE_LENGTH, scale=None, domain="input", reuse_forward=False, out=None,
-            n_valid=None):
-        """Backward pass (lipasr_mfcc_plan_vjp): the gradient w.r.t. ``sig`` of <features(sig), g_feat>.
-        domain="input": sig [B, n_samp] at sr_in (what ``__call__`` takes); domain="22k": sig [B, n_y] (what ``from_22k`` takes).
-        scale: the float64 StandardScaler scale the forward applied, or None.  reuse_forward=True: this extractor's last call
-        was the forward on exactly this ``sig`` on the current stream; its intermediates are read, the bits are the same.
-        2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED).  Clips of different lengths
-        in one launch, int16 rows and clips shorter than the reflect padding: ``vjp_ragged``; short-window extractors: ``vjp_short``."""
+    def _vjp_args(self, sig, g_feat, utterance_length, scale, domain, out, dtypes):
+        """The argument check of ``vjp`` / ``vjp_short`` / ``vjp_ragged`` -> (domain code, B, the gradient buffer).  dtypes: what
+        ``sig`` may be (``vjp`` lets int16 through so that the caller sees the library's EUNSUPPORTED)."""
         if self._plan is None:
             raise RuntimeError("MfccExtractor used after close()")
         if domain not in ("input", "22k"):
@@ -152,8 +147,8 @@ class MfccExtractor:
         b = sig.shape[0]
         if sig.dim() != 2 or sig.shape[1] != n or not sig.is_contiguous():
             raise ValueError(f"sig must be contiguous [B, {n}] for domain {domain!r}, got {tuple(sig.shape)}")
-        if sig.dtype not in (torch.float32, torch.int16):
-            raise ValueError(f"sig must be float32, got {sig.dtype}")
+        if sig.dtype not in dtypes:
+            raise ValueError(f"sig must be {' or '.join(str(d).split('.')[-1] for d in dtypes)}, got {sig.dtype}")
         if tuple(g_feat.shape) != (b, N_MFCC * utterance_length) or g_feat.dtype != torch.float32 or not g_feat.is_contiguous():
             raise ValueError(f"g_feat must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
         if scale is not None and (scale.dtype != torch.float64 or scale.numel() != N_MFCC * utterance_length):
@@ -162,6 +157,17 @@ class MfccExtractor:
             out = torch.empty(b, n, device=self.device)
         elif tuple(out.shape) != (b, n) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError(f"out must be contiguous float32 [{b}, {n}]")
+        return dom, b, out
+
+    def vjp(self, sig, g_feat, utterance_length=STANDARD_UTTERANCE_LENGTH, scale=None, domain="input", reuse_forward=False, out=None,
+            n_valid=None):
+        """Backward pass (lipasr_mfcc_plan_vjp): the gradient w.r.t. ``sig`` of <features(sig), g_feat>.
+        domain="input": sig [B, n_samp] at sr_in (what ``__call__`` takes); domain="22k": sig [B, n_y] (what ``from_22k`` takes).
+        scale: the float64 StandardScaler scale the forward applied, or None.  reuse_forward=True: this extractor's last call
+        was the forward on exactly this ``sig`` on the current stream; its intermediates are read, the bits are the same.
+        2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED).  Clips of different lengths
+        in one launch, int16 rows and clips shorter than the reflect padding: ``vjp_ragged``; short-window extractors: ``vjp_short``."""
+        dom, b, out = self._vjp_args(sig, g_feat, utterance_length, scale, domain, out, (torch.float32, torch.int16))
         flags = (1 if reuse_forward else 0) | (2 if sig.dtype == torch.int16 else 0) | (4 if n_valid is not None else 0)
         N.check(N.lib.lipasr_mfcc_plan_vjp(self._plan, N.ptr(sig), dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat), N.ptr(out),
                                            flags, N.stream_ptr()))
@@ -172,25 +178,7 @@ class MfccExtractor:
         ``sig`` of <features(sig), g_feat>, float32 rows of one length.  domain="22k": sig [B, n_y] (what ``from_22k`` takes);
         domain="input": sig [B, n_samp] at sr_in.  scale and reuse_forward as in ``vjp``.  A 2048/512 extractor raises
         LipasrError(EUNSUPPORTED): ``vjp`` is for those."""
-        if self._plan is None:
-            raise RuntimeError("MfccExtractor used after close()")
-        if domain not in ("input", "22k"):
-            raise ValueError(f"domain={domain!r}: 'input' or '22k'")
-        dom = 0 if domain == "input" else 1
-        n = self.n_samp if dom == 0 else self.n_y
-        b = sig.shape[0]
-        if sig.dim() != 2 or sig.shape[1] != n or not sig.is_contiguous():
-            raise ValueError(f"sig must be contiguous [B, {n}] for domain {domain!r}, got {tuple(sig.shape)}")
-        if sig.dtype != torch.float32:
-            raise ValueError(f"sig must be float32, got {sig.dtype}")
-        if tuple(g_feat.shape) != (b, N_MFCC * utterance_length) or g_feat.dtype != torch.float32 or not g_feat.is_contiguous():
-            raise ValueError(f"g_feat must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
-        if scale is not None and (scale.dtype != torch.float64 or scale.numel() != N_MFCC * utterance_length):
-            raise ValueError("scale must be a float64 device tensor [20 * utterance_length]")
-        if out is None:
-            out = torch.empty(b, n, device=self.device)
-        elif tuple(out.shape) != (b, n) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError(f"out must be contiguous float32 [{b}, {n}]")
+        dom, b, out = self._vjp_args(sig, g_feat, utterance_length, scale, domain, out, (torch.float32,))
         N.check(N.lib.lipasr_mfcc_plan_vjp_short(self._plan, N.ptr(sig), dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat),
                                                  N.ptr(out), 1 if reuse_forward else 0, N.stream_ptr()))
         return out
@@ -204,25 +192,7 @@ class MfccExtractor:
         2 resampled samples, and an empty one gets zeros.  reuse_forward=True: this extractor's last call on the current stream was
         the forward with the same rows and n_valid (``__call__`` / ``from_22k`` with n_valid).  16 kHz and 8 kHz 2048/512 plans with
         rows a multiple of 4 samples: anything else raises LipasrError(EUNSUPPORTED)."""
-        if self._plan is None:
-            raise RuntimeError("MfccExtractor used after close()")
-        if domain not in ("input", "22k"):
-            raise ValueError(f"domain={domain!r}: 'input' or '22k'")
-        dom = 0 if domain == "input" else 1
-        n = self.n_samp if dom == 0 else self.n_y
-        b = sig.shape[0]
-        if sig.dim() != 2 or sig.shape[1] != n or not sig.is_contiguous():
-            raise ValueError(f"sig must be contiguous [B, {n}] for domain {domain!r}, got {tuple(sig.shape)}")
-        if sig.dtype not in (torch.float32, torch.int16):
-            raise ValueError(f"sig must be float32 or int16, got {sig.dtype}")
-        if tuple(g_feat.shape) != (b, N_MFCC * utterance_length) or g_feat.dtype != torch.float32 or not g_feat.is_contiguous():
-            raise ValueError(f"g_feat must be contiguous float32 [{b}, {N_MFCC * utterance_length}]")
-        if scale is not None and (scale.dtype != torch.float64 or scale.numel() != N_MFCC * utterance_length):
-            raise ValueError("scale must be a float64 device tensor [20 * utterance_length]")
-        if out is None:
-            out = torch.empty(b, n, device=self.device)
-        elif tuple(out.shape) != (b, n) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError(f"out must be contiguous float32 [{b}, {n}]")
+        dom, b, out = self._vjp_args(sig, g_feat, utterance_length, scale, domain, out, (torch.float32, torch.int16))
         N.check(N.lib.lipasr_mfcc_plan_vjp_ragged(self._plan, N.ptr(sig), 1 if sig.dtype == torch.int16 else 0, N.ptr(self._lengths(n_valid, b)),
                                                   dom, b, int(utterance_length), N.ptr(scale), N.ptr(g_feat), N.ptr(out),
                                                   1 if reuse_forward else 0, N.stream_ptr()))

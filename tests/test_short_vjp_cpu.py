@@ -1,20 +1,20 @@
-"""The float64 oracle of the short-window MFCC backward pass (tests/mfcc_grad_ref_short.py) checked against the forward oracle and
+"""The float64 oracle of the short-window MFCC backward pass (tests/mfcc_grad_ref.py, n_fft= / hop=) checked against the forward oracle and
 against finite differences, the guard on the parity inputs, and the ABI of the new entry point.  No GPU."""
 import numpy as np
 import pytest
 import torch
 
-import mfcc_grad_ref_short as H
+import mfcc_grad_ref as H
 from lipasr import _native as N
 from oracle import mfcc_ref as M
 
-CASES = [(s, i) for s in H.SHAPES for i in range(len(H.CLIP_NAMES))]
-IDS = [f"{s[0]}-{s[1]}-{s[2]}-{H.CLIP_NAMES[i]}" for s, i in CASES]
+CASES = [(s, i) for s in H.SHORT_SHAPES for i in range(len(H.SHORT_CLIP_NAMES))]
+IDS = [f"{s[0]}-{s[1]}-{s[2]}-{H.SHORT_CLIP_NAMES[i]}" for s, i in CASES]
 
 
 @pytest.fixture(scope="module")
 def clips():
-    return {s: H.parity_clips(*s) for s in H.SHAPES}
+    return {s: H.short_parity_clips(*s) for s in H.SHORT_SHAPES}
 
 
 @pytest.mark.parametrize("shape,i", CASES, ids=IDS)
@@ -25,13 +25,13 @@ def test_restatement_forward_matches_the_oracle(clips, shape, i):
     ref = M.mfcc_22k(y, np.float64, n_fft, hop)
     T = ref.shape[1]
     assert T == 1 + n // hop
-    ours = H.features(torch.as_tensor(y), n_fft, hop, T).numpy().reshape(20, T)
+    ours = H.features(torch.as_tensor(y), utterance_length=T, domain="22k", n_fft=n_fft, hop=hop).numpy().reshape(20, T)
     err = float(np.abs(ours - ref).max())
-    print(f"{shape} {H.CLIP_NAMES[i]}: max |restatement - oracle| = {err:.3e} (max |feature| {np.abs(ref).max():.1f})")
+    print(f"{shape} {H.SHORT_CLIP_NAMES[i]}: max |restatement - oracle| = {err:.3e} (max |feature| {np.abs(ref).max():.1f})")
     assert err <= 1e-9
     # fix_frames: a shorter and a longer utterance_length
     for L in (T - 3, T + 2):
-        got = H.features(torch.as_tensor(y), n_fft, hop, L).numpy().reshape(20, L)
+        got = H.features(torch.as_tensor(y), utterance_length=L, domain="22k", n_fft=n_fft, hop=hop).numpy().reshape(20, L)
         assert np.abs(got - M.fix_frames(ref, L)).max() <= 1e-9
 
 
@@ -40,9 +40,9 @@ def test_parity_inputs_keep_clear_of_the_floor_and_of_ties(clips, shape, i):
     """max(db, thr) and max over the clip are not differentiable at ties: every parity clip, at every gain a batch uses it at, must
     stay 1e-2 dB away from both -- over all dB elements, the empty mel bands pinned at -100 dB among them."""
     n_fft, hop, _ = shape
-    for g in H.GAINS:
+    for g in H.SHORT_GAINS:
         to_floor, top_gap, floored = H.guard_margins((np.float32(g) * clips[shape][i]).astype(np.float32), n_fft, hop)
-        print(f"{shape} {H.CLIP_NAMES[i]} gain {g}: closest element to the floor {to_floor:.3e} dB, top gap {top_gap:.3e} dB, {floored} floored")
+        print(f"{shape} {H.SHORT_CLIP_NAMES[i]} gain {g}: closest element to the floor {to_floor:.3e} dB, top gap {top_gap:.3e} dB, {floored} floored")
         assert to_floor >= 1e-2
         assert top_gap >= 1e-2
 
@@ -67,17 +67,17 @@ def test_autograd_gradient_matches_central_differences(clips, shape, i):
     g_feat = rng.standard_normal(20 * L)
     d = rng.standard_normal(n)
     d /= np.linalg.norm(d)  # unit direction: `step` below is the Euclidean length of the perturbation
-    an = float(H.vjp(x, g_feat, n_fft, hop, L) @ d)
+    an = float(H.vjp(x, g_feat, utterance_length=L, domain="22k", n_fft=n_fft, hop=hop) @ d)
     gt = torch.as_tensor(g_feat)
 
     def loss(v):
         with torch.no_grad():
-            return float((H.features(torch.as_tensor(v), n_fft, hop, L) * gt).sum())
+            return float((H.features(torch.as_tensor(v), utterance_length=L, domain="22k", n_fft=n_fft, hop=hop) * gt).sum())
 
     for step in (1e-6, 1e-7):
         fd = (loss(x + step * d) - loss(x - step * d)) / (2 * step)
         rel = abs(fd - an) / abs(an)
-        print(f"{shape} {H.CLIP_NAMES[i]} step {step:g}: autograd {an:.10e} central difference {fd:.10e} rel {rel:.2e}")
+        print(f"{shape} {H.SHORT_CLIP_NAMES[i]} step {step:g}: autograd {an:.10e} central difference {fd:.10e} rel {rel:.2e}")
         assert rel <= 1e-5
 
 

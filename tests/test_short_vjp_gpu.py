@@ -1,5 +1,5 @@
 """The native backward pass of the short-window MFCC stage (lipasr_mfcc_plan_vjp_short: the Speaker-recognition features, n_fft =
-win_length = 441, hop 220) against the float64 autograd oracle of tests/mfcc_grad_ref_short.py, its determinism and edge cases,
+win_length = 441, hop 220) against the float64 autograd oracle of tests/mfcc_grad_ref.py (n_fft=, hop=), its determinism and edge cases,
 and the audio-domain attacks of lipasr.speaker_recognition built on it.
 
 Parity bounds are 8 x the error of the SAME oracle graph evaluated in float32 (computed here, on the CPU), and at most 0.2 % of a
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-import mfcc_grad_ref_short as H
+import mfcc_grad_ref as H
 from helpers import build_model, load_params
 from oracle import mlp_ref as P
 
@@ -25,11 +25,6 @@ def _lengths(shape):
     return (101, 98) if shape == (441, 220, 22050) else (T, T - 3, T + 2)
 
 
-def _errs(g, g64):
-    d = g - g64
-    return float(np.abs(d).max() / np.abs(g64).max()), float(np.linalg.norm(d) / np.linalg.norm(g64))
-
-
 def _short(n_samp, n_fft, hop, batch_max, sr=22050):
     from lipasr.extract_features_construct_dataset import MfccExtractor
 
@@ -41,10 +36,9 @@ def _parity_rows(got, sig, gf, scale, vjp_kw):
     gradient is exactly 0, whether the device gives exactly 0 at every one of them)."""
     rows = []
     for i in range(sig.shape[0]):
-        g64 = H.vjp(sig[i], gf[i], scale=scale, **vjp_kw)
-        g32 = H.vjp(sig[i], gf[i], scale=scale, dtype=torch.float32, **vjp_kw)
-        rows.append((i, _errs(got[i], g64), _errs(g32, g64), float(np.mean(np.sign(got[i]) != np.sign(g64))),
-                     float(np.mean(np.sign(g32) != np.sign(g64))), int((g64 == 0).sum()), bool(np.all(got[i][g64 == 0] == 0))))
+        row = H.parity_row(got[i], sig[i], gf[i], scale=scale, **vjp_kw)
+        g64 = row[4]
+        rows.append((i,) + row[:4] + (int((g64 == 0).sum()), bool(np.all(got[i][g64 == 0] == 0))))
     return rows
 
 
@@ -62,14 +56,14 @@ def _report_and_check(name, rows):
         assert sb <= 0.002, (tag, i, sb)  # the L-inf step takes sign(g)
 
 
-@pytest.mark.parametrize("shape", H.SHAPES, ids=[f"{s[0]}-{s[1]}-{s[2]}" for s in H.SHAPES])
+@pytest.mark.parametrize("shape", H.SHORT_SHAPES, ids=[f"{s[0]}-{s[1]}-{s[2]}" for s in H.SHORT_SHAPES])
 def test_vjp_short_matches_the_float64_oracle(cuda, shape):
     """MI355X, worst row per shape: see DESIGN.md 3 ("Backward pass", short-window plans) for the recorded figures."""
     n_fft, hop, n = shape
     b = BATCH[shape]
     ex = _short(n, n_fft, hop, b)
     assert ex.n_frames == 1 + n // hop and ex.n_y == n
-    sig = H.parity_batch(n_fft, hop, n, b)
+    sig = H.short_parity_batch(n_fft, hop, n, b)
     st = torch.as_tensor(sig).to(cuda).contiguous()
     rng = np.random.default_rng(n_fft * 1000 + hop)
     rows = []
@@ -78,7 +72,7 @@ def test_vjp_short_matches_the_float64_oracle(cuda, shape):
         scale = rng.uniform(0.5, 2.0, 20 * L)
         got = ex.vjp_short(st, torch.as_tensor(gf).to(cuda), L, torch.as_tensor(scale).to(cuda)).double().cpu().numpy()
         assert np.isfinite(got).all()
-        rows += [(f"L={L}", r) for r in _parity_rows(got, sig, gf, scale, dict(n_fft=n_fft, hop=hop, utterance_length=L))]
+        rows += [(f"L={L}", r) for r in _parity_rows(got, sig, gf, scale, dict(n_fft=n_fft, hop=hop, utterance_length=L, domain="22k"))]
         for _, r in rows[-b:]:
             assert r[6], r
             if L < ex.n_frames:  # the samples only frames >= L reach receive exactly 0 (441/220, L = 98: 489 of them)
@@ -90,7 +84,7 @@ def test_vjp_short_matches_the_float64_oracle(cuda, shape):
 @pytest.fixture(scope="module")
 def sr_plan(cuda):
     ex = _short(22050, 441, 220, 8)
-    sig = torch.as_tensor(H.parity_batch(441, 220, 22050, 6)).to(cuda).contiguous()
+    sig = torch.as_tensor(H.short_parity_batch(441, 220, 22050, 6)).to(cuda).contiguous()
     rng = np.random.default_rng(9)
     gf = torch.as_tensor(rng.standard_normal((6, 2020)).astype(np.float32)).to(cuda)
     mean = torch.as_tensor(rng.standard_normal(2020)).to(cuda)
@@ -151,12 +145,6 @@ def test_domain_input_at_16_khz_matches_the_oracle_composed_with_the_resampler_a
     ex.close()
 
 
-def _onehot(lab, n=20):
-    y = np.zeros((len(lab), n), dtype=np.float32)
-    y[np.arange(len(lab)), lab] = 1
-    return y
-
-
 @pytest.fixture(scope="module")
 def sr_model(cuda):
     """The signed-glorot Speaker-recognition unconstrained classifier (an untrained non-negative network with its own labels has an
@@ -169,9 +157,9 @@ def sr_model(cuda):
     load_params(m, p)
     t = np.arange(22050) / 22050.0
     rng = np.random.default_rng(12)
-    w = np.stack([H.parity_batch(441, 220, 22050, 6)[i % 6] * (1.0 - 0.02 * (i // 6)) + 0.002 * rng.standard_normal(22050) +
+    w = np.stack([H.short_parity_batch(441, 220, 22050, 6)[i % 6] * (1.0 - 0.02 * (i // 6)) + 0.002 * rng.standard_normal(22050) +
                   0.05 * np.sin(2 * np.pi * (500.0 + 130.0 * i) * t) for i in range(32)]).astype(np.float32)
-    w[:6] = H.parity_batch(441, 220, 22050, 6)
+    w[:6] = H.short_parity_batch(441, 220, 22050, 6)
     feats = mfcc_windows(w).double().cpu().numpy()
     mean, scale = feats.mean(axis=0), feats.std(axis=0)
     scale[scale == 0.0] = 1.0
@@ -186,10 +174,10 @@ def test_waveform_classifier_loss_gradient_matches_the_composed_oracle(sr_model,
     assert clf.n == 22050 and clf.utterance_length == 101 and clf.nb_classes == 20 and clf.domain == "22k"
     x = sr_model["w"][:6]
     pred = clf.predict(x).argmax(axis=1)
-    y = _onehot((pred + 1 + np.arange(6)) % 20)
+    y = H.onehot((pred + 1 + np.arange(6)) % 20, 20)
     got = clf.loss_gradient(x, y).astype(np.float64)
     assert got.shape == (6, 22050) and np.isfinite(got).all() and np.abs(got).max() > 0
-    kw = dict(n_fft=441, hop=220, utterance_length=101)
+    kw = dict(n_fft=441, hop=220, utterance_length=101, domain="22k")
     f64 = np.stack([H.features(torch.as_tensor(x[i].astype(np.float64)), mean=mean, scale=scale, **kw).numpy() for i in range(6)])
     f32 = np.stack([H.features(torch.as_tensor(x[i].astype(np.float64)), mean=mean, scale=scale, dtype=torch.float32, **kw).numpy() for i in range(6)])
     gf64 = P.input_gradient_infer(spec, p.astype(np.float64), f64, y.astype(np.float64))
@@ -198,7 +186,7 @@ def test_waveform_classifier_loss_gradient_matches_the_composed_oracle(sr_model,
     for i in range(6):
         g64 = H.vjp(x[i], gf64[i], scale=scale, **kw)
         g32 = H.vjp(x[i], gf32[i].astype(np.float64), scale=scale, dtype=torch.float32, **kw)
-        rows.append((i, _errs(got[i], g64), _errs(g32, g64)))
+        rows.append((i, H.errs(got[i], g64), H.errs(g32, g64)))
     yard_inf, yard_2 = max(r[2][0] for r in rows), max(r[2][1] for r in rows)
     for i, (e_inf, e_2), (y_inf, y_2) in rows:
         print(f"loss_gradient window {i}: device inf {e_inf:.3e} two {e_2:.3e} | composed float32 oracle inf {y_inf:.3e} two {y_2:.3e}")
@@ -209,10 +197,6 @@ def test_waveform_classifier_loss_gradient_matches_the_composed_oracle(sr_model,
     with pytest.raises(ValueError):
         clf.loss_gradient(x, y, lengths=[22050] * 6)
     clf.extractor.close()
-
-
-def _mean_ce(prob, y):
-    return float(-np.log(np.maximum(prob[np.arange(len(y)), y], 1e-30)).mean())
 
 
 def test_pgd_linf_over_the_windows(sr_model, cuda):
@@ -229,7 +213,7 @@ def test_pgd_linf_over_the_windows(sr_model, cuda):
     fclf = A.TensorFlowV2Classifier(model=m, nb_classes=20, input_shape=(2020,))
     before = A.ProjectedGradientDescent(estimator=fclf, eps=0.5, eps_step=0.1, max_iter=5).generate_device(fx)
     lab = clf.predict_device(x0).argmax(dim=1).cpu().numpy().astype(np.int64)  # the model's own labels: CE can only be pushed up
-    y = torch.as_tensor(_onehot(lab)).to(cuda)
+    y = torch.as_tensor(H.onehot(lab, 20)).to(cuda)
     adv = A.ProjectedGradientDescent(estimator=clf, eps=eps, eps_step=eps / 4, max_iter=8, batch_size=32).generate_device(x0, y)
     assert torch.equal(x0, keep) and adv.data_ptr() != x0.data_ptr()
     assert float((adv - x0).abs().max()) <= eps + float(np.spacing(np.float32(1.0)))
@@ -238,7 +222,7 @@ def test_pgd_linf_over_the_windows(sr_model, cuda):
     noise = (torch.randint(0, 2, x0.shape, generator=gen).float() * 2 - 1).to(cuda) * eps
     res = {}
     for name, x in (("clean", x0), ("noise", (x0 + noise).clamp_(-1.0, 1.0)), ("pgd", adv)):
-        res[name] = _mean_ce(clf.predict_device(x).double().cpu().numpy(), lab)
+        res[name] = H.mean_ce(clf.predict_device(x).double().cpu().numpy(), lab)
     print(f"pgd-linf over 32 windows, eps {eps}: " + ", ".join(f"{k}: CE {v:.4f}" for k, v in res.items()))
     assert res["pgd"] > res["clean"] and res["pgd"] > res["noise"]
     after = A.ProjectedGradientDescent(estimator=fclf, eps=0.5, eps_step=0.1, max_iter=5).generate_device(fx)

@@ -19,12 +19,6 @@ L = 44
 DOMAINS = ("22k", "input")
 
 
-def _onehot(lab, n=10):
-    y = np.zeros((len(lab), n), dtype=np.float32)
-    y[np.arange(len(lab)), lab] = 1
-    return y
-
-
 @pytest.fixture(scope="module")
 def parity(cuda):
     """The twelve clips, a signed-glorot unconstrained classifier, a scaler fitted on the clips' features and, per clip, a label
@@ -51,7 +45,7 @@ def parity(cuda):
     for n in G.LENGTHS:
         f = ex[n](x[n], L, mean_t, scale_t)
         pred = m.predict_device(f).argmax(dim=1).cpu().numpy()
-        out["y"][n] = _onehot((pred + 1 + np.arange(4)) % 10)
+        out["y"][n] = G.onehot((pred + 1 + np.arange(4)) % 10, 10)
         yt = torch.as_tensor(out["y"][n]).to(cuda)
         gf = torch.empty_like(f)
         N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yt), 4, N.ptr(gf), N.stream_ptr()))
@@ -65,11 +59,6 @@ def _sig(parity, n, domain):
     return parity["y22"][n] if domain == "22k" else parity["x"][n]
 
 
-def _errs(g, g64):
-    d = g - g64
-    return float(np.abs(d).max() / np.abs(g64).max()), float(np.linalg.norm(d) / np.linalg.norm(g64))
-
-
 @pytest.mark.parametrize("domain", DOMAINS)
 def test_vjp_matches_the_float64_oracle(parity, domain):
     """MI355X, worst of the twelve clips: see DESIGN.md 3 ("Backward pass") for the recorded figures."""
@@ -79,12 +68,8 @@ def test_vjp_matches_the_float64_oracle(parity, domain):
         got = parity["ex"][n].vjp(sig, gf, L, parity["scale_t"], domain=domain).double().cpu().numpy()
         assert np.isfinite(got).all()
         for i in range(4):
-            s64, g64f = sig[i].double().cpu().numpy(), gf[i].double().cpu().numpy()
-            g64 = G.vjp(s64, g64f, scale=parity["scale"], domain=domain)
-            g32 = G.vjp(s64, g64f, scale=parity["scale"], domain=domain, dtype=torch.float32)
-            sign_bad = float(np.mean(np.sign(got[i]) != np.sign(g64)))
-            sign_bad32 = float(np.mean(np.sign(g32) != np.sign(g64)))
-            rows.append((n, i, _errs(got[i], g64), _errs(g32, g64), sign_bad, sign_bad32))
+            rows.append((n, i) + G.parity_row(got[i], sig[i].double().cpu().numpy(), gf[i].double().cpu().numpy(), scale=parity["scale"],
+                                              domain=domain)[:4])
     yard_inf, yard_2 = max(r[3][0] for r in rows), max(r[3][1] for r in rows)
     for n, i, (e_inf, e_2), (y_inf, y_2), sb, sb32 in rows:
         print(f"vjp {domain} {G.CLIP_NAMES[i]} n={n}: device inf {e_inf:.3e} two {e_2:.3e} | float32 oracle inf {y_inf:.3e} two {y_2:.3e} | "
@@ -215,10 +200,6 @@ def trained(cuda):
     return dict(model=m, ex=ex, sc=sc, waves=waves, w=w, labels=labels, feats=feats)
 
 
-def _mean_ce(prob, y):
-    return float(-np.log(np.maximum(prob[np.arange(len(y)), y], 1e-30)).mean())
-
-
 @pytest.mark.parametrize("domain", DOMAINS)
 def test_pgd_linf_over_audio(trained, domain, cuda):
     from lipasr import attack_eval as V, attacks as A
@@ -230,7 +211,7 @@ def test_pgd_linf_over_audio(trained, domain, cuda):
     lab = trained["labels"][320:448].astype(np.int64)
     x0 = torch.cat([ex.resample(w[s:s + 64]) for s in (0, 64)]) if domain == "22k" else w
     keep = x0.clone()
-    y = torch.as_tensor(_onehot(lab)).to(cuda)
+    y = torch.as_tensor(G.onehot(lab, 10)).to(cuda)
     adv = A.ProjectedGradientDescent(estimator=clf, eps=eps, eps_step=eps / 4, max_iter=10, batch_size=64).generate_device(x0, y)
     assert torch.equal(x0, keep)
     assert float((adv - x0).abs().max()) <= eps + float(np.spacing(np.float32(1.0)))
@@ -241,7 +222,7 @@ def test_pgd_linf_over_audio(trained, domain, cuda):
     res = {}
     for name, x in (("clean", x0), ("noise", noisy), ("pgd", adv)):
         prob = clf.predict_device(x).double().cpu().numpy()
-        res[name] = (_mean_ce(prob, lab), float((prob.argmax(axis=1) == lab).mean()))
+        res[name] = (G.mean_ce(prob, lab), float((prob.argmax(axis=1) == lab).mean()))
     print(f"pgd-linf over audio, domain {domain}, eps {eps}: " + ", ".join(f"{k}: CE {v[0]:.4f} accuracy {v[1]:.4f}" for k, v in res.items()))
     assert res["pgd"][0] > res["clean"][0] and res["pgd"][0] > res["noise"][0]
     assert res["pgd"][1] <= res["noise"][1]
@@ -250,7 +231,7 @@ def test_pgd_linf_over_audio(trained, domain, cuda):
     assert float((adv2 - x0[:64]).abs().max()) <= eps + float(np.spacing(np.float32(1.0)))
     assert float(adv2.abs().max()) <= 1.0
     # NumPy in, NumPy out
-    g = clf.loss_gradient(x0[:4].cpu().numpy(), _onehot(lab[:4]))
+    g = clf.loss_gradient(x0[:4].cpu().numpy(), G.onehot(lab[:4], 10))
     assert g.shape == (4, x0.shape[1]) and np.isfinite(g).all() and np.abs(g).max() > 0
 
 
@@ -281,7 +262,7 @@ def test_white_box_audio_sweep_anchors_on_the_black_box_sweep(trained, tmp_path,
             f.writeframes((np.clip(trained["waves"][i], -1, 1) * 32767.0).astype("<i2").tobytes())
         files.append(str(path))
     feats = compute_mfcc_all_files(files)
-    labels = _onehot(trained["labels"][32:48].astype(np.int64))
+    labels = G.onehot(trained["labels"][32:48].astype(np.int64), 10)
     models = {"constrained": trained["model"], "unconstrained": trained["model"]}
     args = (models, feats[:24], feats[24:32], feats[32:48], labels)
     _, black = V.black_box_sweep(*args, kind="simple", over="audio", test_filenames=files[32:48], grid=[0])

@@ -1,16 +1,15 @@
 """Per-clip lengths in the MFCC backward pass, the parts that need no GPU: the ABI of the new entry points, the oracle for
-clips shorter than the reflect padding (tests/mfcc_grad_ref_ragged.py) against the forward oracle, the guard on the parity
+clips shorter than the reflect padding (tests/mfcc_grad_ref.py) against the forward oracle, the guard on the parity
 inputs, and keyword validation."""
 import numpy as np
 import pytest
 import torch
 
 import mfcc_grad_ref as G
-import mfcc_grad_ref_ragged as R
 from lipasr import _native as N
 from oracle import mfcc_ref as M
 
-SHORT = tuple(n for n in R.LENGTHS if n < 12000)  # tests/test_wave_attacks_cpu.py covers 12 000 .. 20 000
+SHORT = tuple(n for n in G.RAGGED_LENGTHS if n < 12000)  # tests/test_wave_attacks_cpu.py covers 12 000 .. 20 000
 CASES = [(n, i) for n in SHORT for i in range(len(G.CLIP_NAMES))]
 IDS = [f"{G.CLIP_NAMES[i]}-{n}" for n, i in CASES]
 
@@ -35,7 +34,7 @@ def test_library_exports_and_binds_the_ragged_entry_points():
 def test_restatement_forward_matches_the_oracle_on_short_clips(clips, n, i):
     """The tolerance of tests/test_wave_attacks_cpu.py for the long clips (the oracle's own float32 rounding)."""
     x = clips[n][i]
-    ours = R.features(torch.as_tensor(x.astype(np.float64))).numpy()
+    ours = G.features(torch.as_tensor(x.astype(np.float64))).numpy()
     ref = M.compute_mfcc_batch(x[None, :])[0].reshape(-1).astype(np.float64)
     err = float(np.abs(ours - ref).max())
     print(f"{G.CLIP_NAMES[i]} n={n}: max |restatement - oracle| = {err:.3e} (max |feature| {np.abs(ref).max():.1f})")
@@ -43,17 +42,22 @@ def test_restatement_forward_matches_the_oracle_on_short_clips(clips, n, i):
 
 
 def test_gather_padding_is_the_reflect_pad_where_torch_has_one():
-    """For a clip longer than the padding the gather is mfcc_grad_ref's reflect pad, bit for bit."""
+    """For a clip longer than the padding the gather is torch's reflect pad, bit for bit: the padded signal, and the dB tile through
+    either (the oracle's steps after the padding, restated on torch's padded signal)."""
     x = G.parity_clips(3000)[1].astype(np.float64)
     y = torch.as_tensor(M.librosa_load_resample(x.astype(np.float32), 16000).astype(np.float64))
-    assert torch.equal(R.db_22k(y), G.db_22k(y))
+    yp = torch.nn.functional.pad(y[None, None, :], (M.N_FFT // 2, M.N_FFT // 2), mode="reflect")[0, 0]
+    assert torch.equal(y[torch.as_tensor(np.pad(np.arange(y.shape[0]), M.N_FFT // 2, mode="reflect"))], yp)
+    X = torch.fft.rfft(yp.unfold(0, M.N_FFT, M.HOP) * torch.as_tensor(M.hann_periodic()), dim=1)
+    mel = (X.real ** 2 + X.imag ** 2) @ torch.as_tensor(M.mel_filterbank().astype(np.float64)).T
+    assert torch.equal(G.db_22k(y), 10.0 * torch.log10(torch.clamp(mel, min=1e-10)))
 
 
 @pytest.mark.parametrize("n,i", CASES, ids=IDS)
 def test_parity_inputs_keep_clear_of_the_floor_and_of_ties(clips, n, i):
     """max(db, thr) and max over the clip are not differentiable at ties: every parity clip must stay 1e-2 dB away from both."""
     y = M.librosa_load_resample(clips[n][i], 16000)
-    to_floor, top_gap = R.guard_margins(y)
+    to_floor, top_gap = G.guard_margins(y)[:2]
     print(f"{G.CLIP_NAMES[i]} n={n}: closest element to the floor {to_floor:.3e} dB, top gap {top_gap:.3e} dB")
     assert to_floor >= 1e-2
     assert top_gap >= 1e-2

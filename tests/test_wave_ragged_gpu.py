@@ -1,5 +1,5 @@
 """Clips of different lengths in one launch of the MFCC backward pass (lipasr_mfcc_plan_vjp_ragged) and of the attacks over
-audio (lengths=): parity against the float64 oracle of tests/mfcc_grad_ref_ragged.py on each clip alone, the same bits as the
+audio (lengths=): parity against the float64 oracle of tests/mfcc_grad_ref.py on each clip alone, the same bits as the
 one-length call where that exists, determinism, the edges, int16 rows, the split forward, the attacks and the sweep.
 
 One plan of 20 000-sample rows serves every test.  Parity bounds follow tests/test_wave_attacks_gpu.py: 8 x the error of the SAME
@@ -12,7 +12,6 @@ import pytest
 import torch
 
 import mfcc_grad_ref as G
-import mfcc_grad_ref_ragged as R
 from helpers import build_model, load_params
 from oracle import mlp_ref as P
 
@@ -22,12 +21,6 @@ L = 44
 N_ROW = 20000
 DOMAINS = ("22k", "input")
 SAME_BITS = (3000, 7000, 12000, 16000, 20000)  # multiples of 4 with n_y > 2048: the one-length call exists for the clip alone
-
-
-def _onehot(lab, n=10):
-    y = np.zeros((len(lab), n), dtype=np.float32)
-    y[np.arange(len(lab)), lab] = 1
-    return y
 
 
 def _n22(n):
@@ -62,9 +55,9 @@ def rag(cuda):
     m = build_model(spec, max_batch=48)
     load_params(m, p)
     ex = MfccExtractor(16000, N_ROW, batch_max=48)
-    lens = [n for n in R.LENGTHS for _ in range(4)]
+    lens = [n for n in G.RAGGED_LENGTHS for _ in range(4)]
     x = torch.zeros(len(lens), N_ROW, device=cuda)
-    for k, n in enumerate(R.LENGTHS):
+    for k, n in enumerate(G.RAGGED_LENGTHS):
         x[4 * k:4 * k + 4, :n] = torch.as_tensor(G.parity_clips(n)).to(cuda)
     _fill_tails(x, lens, rng, 10.0)
     lt = _i32(lens, cuda)
@@ -75,7 +68,7 @@ def rag(cuda):
     mean_t, scale_t = torch.as_tensor(mean).to(cuda), torch.as_tensor(scale).to(cuda)
     f = ex(x, L, mean_t, scale_t, n_valid=lt)
     pred = m.predict_device(f).argmax(dim=1).cpu().numpy()
-    y = _onehot((pred + 1 + np.arange(len(lens)) % 4) % 10)
+    y = G.onehot((pred + 1 + np.arange(len(lens)) % 4) % 10, 10)
     gf = torch.empty_like(f)
     N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(torch.as_tensor(y).to(cuda)), len(lens),
                                         N.ptr(gf), N.stream_ptr()))
@@ -86,11 +79,6 @@ def rag(cuda):
 
 def _sig(rag, domain):
     return rag["y22"] if domain == "22k" else rag["x"]
-
-
-def _errs(g, g64):
-    d = g - g64
-    return float(np.abs(d).max() / np.abs(g64).max()), float(np.linalg.norm(d) / np.linalg.norm(g64))
 
 
 @pytest.mark.parametrize("domain", DOMAINS)
@@ -105,13 +93,9 @@ def test_ragged_vjp_matches_the_float64_oracle_on_each_clip_alone(rag, domain):
     rows = []
     for u, n in enumerate(lens):
         e = _end(n, domain)
-        s64, g64f = sig[u, :e].double().cpu().numpy(), gf[u].double().cpu().numpy()
-        g64 = R.vjp(s64, g64f, scale=rag["scale"], domain=domain)
-        g32 = R.vjp(s64, g64f, scale=rag["scale"], domain=domain, dtype=torch.float32)
-        sb = float(np.mean(np.sign(got[u, :e]) != np.sign(g64)))
-        sb32 = float(np.mean(np.sign(g32) != np.sign(g64)))
-        rows.append((u, n, _errs(got[u, :e], g64), _errs(g32, g64), sb, sb32, float(np.abs(got[u, e:]).max()) if e < got.shape[1] else 0.0))
-    yard = {n: (max(r[3][0] for r in rows if r[1] == n), max(r[3][1] for r in rows if r[1] == n)) for n in R.LENGTHS}
+        row = G.parity_row(got[u, :e], sig[u, :e].double().cpu().numpy(), gf[u].double().cpu().numpy(), scale=rag["scale"], domain=domain)
+        rows.append((u, n) + row[:4] + (float(np.abs(got[u, e:]).max()) if e < got.shape[1] else 0.0,))
+    yard = {n: (max(r[3][0] for r in rows if r[1] == n), max(r[3][1] for r in rows if r[1] == n)) for n in G.RAGGED_LENGTHS}
     for u, n, (e_inf, e_2), (y_inf, y_2), sb, sb32, tail in rows:
         print(f"ragged vjp {domain} {G.CLIP_NAMES[u % 4]} n={n}: device inf {e_inf:.3e} two {e_2:.3e} | float32 oracle inf {y_inf:.3e} two "
               f"{y_2:.3e} | bounds {8 * yard[n][0]:.3e} / {8 * yard[n][1]:.3e} | sign mismatches device {100 * sb:.4f}% float32 oracle "
@@ -250,7 +234,7 @@ def test_attacks_with_lengths_equal_the_attack_on_each_clip_alone(rag, domain, c
     keep = x0.clone()
     clf = A.WaveformClassifier(m, 10, extractor=ex, utterance_length=L, mean=rag["mean"], scale=rag["scale"], domain=domain)
     pred = clf.predict_device(x0, lengths=lt).argmax(dim=1).cpu().numpy()
-    y = torch.as_tensor(_onehot((pred + 1 + np.arange(4)) % 10)).to(cuda)
+    y = torch.as_tensor(G.onehot((pred + 1 + np.arange(4)) % 10, 10)).to(cuda)
     eps = 0.01
     attacks = {"pgd": lambda c: A.ProjectedGradientDescent(estimator=c, eps=eps, eps_step=eps / 4, max_iter=5, batch_size=32),
                "fgm": lambda c: A.FastGradientMethod(estimator=c, eps=eps, batch_size=32)}
@@ -316,7 +300,7 @@ def test_white_box_audio_sweep_over_files_of_different_lengths(tmp_path, cuda, c
     m.fit(K.Dataset.from_tensor_slices((sc.transform(feats[:80]).astype(np.float32), K.to_categorical(labels[:80], 10))).batch(16), epochs=6,
           verbose=0)
     test = files[96:112]
-    onehot = _onehot(labels[96:112].astype(np.int64))
+    onehot = G.onehot(labels[96:112].astype(np.int64), 10)
     models = {"constrained": m, "unconstrained": m}
     args = (models, feats[:80], feats[80:96], feats[96:112], onehot)
     _, black = V.black_box_sweep(*args, kind="simple", over="audio", test_filenames=test, grid=[0])
