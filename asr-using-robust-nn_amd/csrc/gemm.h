@@ -1,6 +1,7 @@
 // The dense classifier's GEMM interface: what a launch is told (GemmArgs, its epilogues and dropout arguments), the grouped
-// launch's argument block, and the host entry points of gemm.hip that the plan (mlp.hip) calls.  The tile kernels, the
-// choice of one (pick_gemm) and the launchers live in gemm.hip.
+// launch's argument block, and the host entry points of gemm.hip that the plan (mlp.hip) calls.  The choice of a kernel
+// (pick_gemm) and the launchers live in gemm.hip; the tile kernels live in one translation unit per family (gemm_frag.hip,
+// gemm_lds.hip, gemm_ring.hip, gemm_ring_group.hip, gemm_ring2.hip), each of which registers its instances in the GemmTable.
 #pragma once
 #include "mlp.h"
 
@@ -161,6 +162,37 @@ struct GemmPick {
   int tile_m, tile_n, threads;
   size_t lds_bytes;
   const void* fn;
+};
+
+// Every instantiated GEMM kernel, indexed by what the templates are parameterised on; null = not instantiated.  A family's
+// translation unit takes the addresses of the kernels it instantiates and reports their launch shapes beside them (the threads
+// and LDS bytes are the constants its __launch_bounds__ and LDS carving are written with: the host side restates none of them).
+struct GemmShape {
+  int tile_m, tile_n, threads;
+  size_t lds_bytes;
+};
+struct GemmTable;
+// (internal to the library: not among its dynamic symbols)
+__attribute__((visibility("hidden"))) void register_gemm_frag(GemmTable& t);        // gemm_frag.hip: GK_FRAG4, GK_FRAG16, grouped_frag
+__attribute__((visibility("hidden"))) void register_gemm_lds(GemmTable& t);         // gemm_lds.hip: GK_LDS, grouped_lds
+__attribute__((visibility("hidden"))) void register_gemm_ring(GemmTable& t);        // gemm_ring.hip: GK_RING, GK_RING_X1
+__attribute__((visibility("hidden"))) void register_gemm_ring_group(GemmTable& t);  // gemm_ring_group.hip: grouped_ring
+__attribute__((visibility("hidden"))) void register_gemm_ring2(GemmTable& t);       // gemm_ring2.hip: GK_RING2
+struct GemmTable {
+  const void* fn[GK_KINDS][2][2][2][3] = {};  // [kind][exchange epilogue][AMODE][BMODE][arithmetic]
+  GemmShape shape[GK_KINDS] = {};
+  const void* grouped_frag[3] = {}, *grouped_lds[3] = {}, *grouped_ring = nullptr;  // weight-gradient groups (AMODE 1, BMODE 1)
+  GemmShape grouped_frag_shape = {}, grouped_lds_shape = {};
+  GemmShape grouped_ring_shape[4] = {};  // by the launch's ring tile (GemmArgs::ring: 1, 2 or 3; ring 0 is no ring tile, [0] stays empty)
+  // Built once, by gemm.hip's gemm_table(); nothing else constructs one.  The body sits here, and not in gemm.hip, so that the
+  // constructor stays the inline (weak) function it was and the library's dynamic symbol list does not change.
+  GemmTable() {
+    register_gemm_frag(*this);
+    register_gemm_lds(*this);
+    register_gemm_ring(*this);
+    register_gemm_ring_group(*this);
+    register_gemm_ring2(*this);
+  }
 };
 
 // amode / bmode: 1 = the operand is k-major in memory (P[k ld + i])

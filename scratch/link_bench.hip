@@ -11,6 +11,11 @@
 // (lp_attack.hip: the plan code in mlp.hip refers to its step launcher)
 // Every spin is bounded (a give-up sets an error word, the grid always drains).
 #include "../asr-using-robust-nn_amd/csrc/gemm.hip"
+#include "../asr-using-robust-nn_amd/csrc/gemm_frag.hip"
+#include "../asr-using-robust-nn_amd/csrc/gemm_lds.hip"
+#include "../asr-using-robust-nn_amd/csrc/gemm_ring.hip"
+#include "../asr-using-robust-nn_amd/csrc/gemm_ring_group.hip"
+#include "../asr-using-robust-nn_amd/csrc/gemm_ring2.hip"
 #include "../asr-using-robust-nn_amd/csrc/mlp.hip"
 #include <cstdlib>
 

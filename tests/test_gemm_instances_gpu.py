@@ -1,6 +1,6 @@
 """Every GEMM kernel instance against float64, and proof of which instance ran.
 
-gemm.hip instantiates about sixty kernels (GemmTable: [kind][exchange epilogue][AMODE][BMODE][arithmetic], plus the grouped
+The gemm_*.hip tile units instantiate about sixty kernels (GemmTable: [kind][exchange epilogue][AMODE][BMODE][arithmetic], plus the grouped
 weight-gradient kernels) and pick_gemm / launch_gemm_group_tn choose between them from the shape, the alignment, the arithmetic
 mode, the plan's tile threshold and CU budget, an occupancy query and the lipasr_debug_gemm_mode bits.  The cases below are kept
 in two module-level tables; every case names the instances (and epilogues) it is meant to run, the launch counters
