@@ -44,6 +44,27 @@ __device__ __forceinline__ float dropout_mult(const DropArgs& d, int step, size_
   return u > d.rate ? 1.0f / (1.0f - d.rate) : 0.0f;
 }
 
+// The multipliers of the four consecutive elements (row, col .. col + 3) of a row-major [.][ld] tensor with N valid columns;
+// columns >= N get 0 and are neither drawn nor read.  Every epilogue walks its rows in such groups, col % 4 == 0, and the four
+// elements of a group whose first index is a multiple of 4 share their Philox counter (e >> 2) and take its four outputs in order:
+// ONE generator call gives the same four masks as four calls of dropout_mult that keep one output each.  (The row base is
+// row * ld with ld a run-time value, so the compiler could not see the four counters as equal: it emitted four generators and a
+// select chain per group -- 344 vector instructions, 76 of them v_mad_u64_u32, against 110 and 19 now)  The test is written on ld and col,
+// not on the index, so that it is wave-uniform; whatever fails it -- ld % 4 != 0, a ragged last group -- keeps the call per element.
+__device__ __forceinline__ void dropout_mult4(const DropArgs& d, int step, int row, int ld, int col, int N, float (&m)[4]) {
+  const size_t e0 = (size_t)row * ld + col;
+  if (d.mode == 1 && d.rate > 0.0f && ((ld & 3) == 0) && ((col & 3) == 0) && col + 3 < N) {
+    uint32_t o[4];
+    Philox::gen(d.seed, (uint64_t)(e0 >> 2), (uint32_t)d.layer, (uint32_t)step, o);
+    const float keep = 1.0f / (1.0f - d.rate);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = Philox::u01(o[k]) > d.rate ? keep : 0.0f;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) m[k] = (col + k < N) ? dropout_mult(d, step, e0 + k) : 0.0f;
+}
+
 
 struct GemmArgs {
   const float* A;

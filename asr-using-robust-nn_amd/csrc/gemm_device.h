@@ -116,7 +116,8 @@ __device__ __forceinline__ void load_frag(const float* __restrict__ P, int ld, i
 }
 
 // One output element: returns the value to store; s1/s2 receive the column statistics of the *_STATS epilogues.
-__device__ __forceinline__ float epilogue_elem(const GemmArgs& g, int step, int gm, int gn, float v, float& s1, float& s2) {
+// dm: the element's dropout multiplier, drawn by the caller for its four columns at once (epilogue_dropout4).
+__device__ __forceinline__ float epilogue_elem(const GemmArgs& g, float dm, int gm, int gn, float v, float& s1, float& s2) {
   switch (g.epi) {
     case EPI_BIAS:
       return v + g.bias[gn];
@@ -140,7 +141,7 @@ __device__ __forceinline__ float epilogue_elem(const GemmArgs& g, int step, int 
     }
     case EPI_DH_STATS: {
       const size_t e = (size_t)gm * g.ldc + gn;
-      const float gg = v * dropout_mult(g.drop, step, e);
+      const float gg = v * dm;
       const float xh = (g.aux[e] - g.save_mean[gn]) * g.save_mean[g.N + gn];
       s1 = gg;
       s2 = gg * xh;
@@ -148,7 +149,7 @@ __device__ __forceinline__ float epilogue_elem(const GemmArgs& g, int step, int 
     }
     case EPI_DZ_NOBN: {
       const size_t e = (size_t)gm * g.ldc + gn;
-      return g.aux[e] > 0.0f ? v * dropout_mult(g.drop, step, e) : 0.0f;
+      return g.aux[e] > 0.0f ? v * dm : 0.0f;
     }
     case EPI_SIGNSTEP: {
       const size_t i = (size_t)gm * g.ldc + gn;
@@ -163,6 +164,15 @@ __device__ __forceinline__ float epilogue_elem(const GemmArgs& g, int step, int 
   }
 }
 
+// the dropout multipliers of the row's four columns gn .. gn + 3 for the two epilogues that apply them (1 for every other one)
+__device__ __forceinline__ void epilogue_dropout4(const GemmArgs& g, int step, int gm, int gn, float (&dm)[4]) {
+  if (g.epi == EPI_DH_STATS || g.epi == EPI_DZ_NOBN) {
+    dropout_mult4(g.drop, step, gm, g.ldc, gn, g.N, dm);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dm[e] = 1.0f;
+  }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Round 5: the exchange epilogue.  Training-mode BatchNorm needs column statistics over ALL rows of the batch, i.e. over
@@ -327,13 +337,13 @@ __device__ __forceinline__ void bnx_finish(const GemmArgs& g, const int step, co
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (gm[r] >= g.M) continue;
-    float o[4];
+    float o[4], dm[4];
+    if (fwd) dropout_mult4(g.drop, step, gm[r], g.ldc, gn, g.N, dm);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const size_t idx = (size_t)gm[r] * g.ldc + gn + e;
       if (fwd) {
         float x = (val[r][e] - mean[e]) * rstd[e] * ga[e] + be[e];
-        x *= (gn + e < g.N) ? dropout_mult(g.drop, step, idx) : 0.0f;
+        x *= dm[e];
         o[e] = x;
       } else {
         const float xh = (av[r][e] - mean[e]) * rstd[e];
@@ -406,18 +416,26 @@ __device__ __forceinline__ void bnx_prefetch(const GemmArgs& g, const int gm, co
   }
 }
 
-// the element before the exchange: value kept in registers, its two statistics
-__device__ __forceinline__ void bnx_elem(const GemmArgs& g, const int step, const bool cv, const int gm, const int gn, const float acc,
-                                         const BnxPre& q, const int e, float& val, float& av, float& s1, float& s2) {
+// one row's four columns before the exchange: values kept in registers, their two statistics each (rv: the row is inside M)
+__device__ __forceinline__ void bnx_row4(const GemmArgs& g, const int step, const bool rv, const int gm, const int gn, const float (&acc)[4],
+                                         const BnxPre& q, float (&val)[4], float (&av)[4], float (&s1)[4], float (&s2)[4]) {
   if (g.epi == EPI_BIAS_RELU_BNX) {
-    const float a = cv ? fmaxf(acc + q.p0[e], 0.0f) : 0.0f;
-    val = a; av = a; s1 = a; s2 = a * a;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = (rv && gn + e < g.N) ? fmaxf(acc[e] + q.p0[e], 0.0f) : 0.0f;
+      val[e] = a; av[e] = a; s1[e] = a; s2[e] = a * a;
+    }
   } else {
-    const size_t idx = (size_t)gm * g.ldc + gn;
-    const float gg = cv ? acc * dropout_mult(g.drop, step, idx) : 0.0f;
-    const float a = q.p0[e];
-    const float xh = cv ? (a - q.p1[e]) * q.p2[e] : 0.0f;
-    val = gg; av = a; s1 = gg; s2 = gg * xh;
+    float dm[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (rv) dropout_mult4(g.drop, step, gm, g.ldc, gn, g.N, dm);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool cv = rv && gn + e < g.N;
+      const float gg = cv ? acc[e] * dm[e] : 0.0f;
+      const float a = q.p0[e];
+      const float xh = cv ? (a - q.p1[e]) * q.p2[e] : 0.0f;
+      val[e] = gg; av[e] = a; s1[e] = gg; s2[e] = gg * xh;
+    }
   }
 }
 

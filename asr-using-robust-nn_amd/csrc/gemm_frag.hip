@@ -101,8 +101,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
       }
       const float accv[4] = {s.x, s.y, s.z, s.w};
       float val[1][4], av[1][4], c1[4], c2[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bnx_elem(g, step, gm1[0] < g.M && gn + e < g.N, gm1[0], gn + e, accv[e], xpre, e, val[0][e], av[0][e], c1[e], c2[e]);
+      bnx_row4(g, step, gm1[0] < g.M, gm1[0], gn, accv, xpre, val[0], av[0], c1, c2);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
 #pragma unroll
@@ -225,11 +224,12 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
       }
     } else if (gm < g.M) {
       const float v[4] = {s.x, s.y, s.z, s.w};
-      float o[4];
+      float o[4], dm[4];
+      epilogue_dropout4(g, step, gm, gn, dm);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t1 = 0.0f, t2 = 0.0f;
-        o[e] = (gn + e < g.N) ? epilogue_elem(g, step, gm, gn + e, v[e], t1, t2) : 0.0f;
+        o[e] = (gn + e < g.N) ? epilogue_elem(g, dm[e], gm, gn + e, v[e], t1, t2) : 0.0f;
         cs1[e] = t1;
         cs2[e] = t2;
       }

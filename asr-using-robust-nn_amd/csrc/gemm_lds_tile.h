@@ -109,12 +109,12 @@ __device__ __forceinline__ void lds_tile_epilogue(const GemmArgs& g, const f32x1
       float4 s = *reinterpret_cast<const float4*>(red + row * TS + c4);
       const float4 s2 = *reinterpret_cast<const float4*>(red + TS * TS + row * TS + c4);
       const float accv[4] = {s.x + s2.x, s.y + s2.y, s.z + s2.z, s.w + s2.w};
+      float t1[4], t2[4];
+      bnx_row4(g, step, gm2[pass] < g.M, gm2[pass], gn, accv, xpre[pass], val[pass], av[pass], t1, t2);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float t1, t2;
-        bnx_elem(g, step, gm2[pass] < g.M && gn + e < g.N, gm2[pass], gn + e, accv[e], xpre[pass], e, val[pass][e], av[pass][e], t1, t2);
-        c1[e] += t1;
-        c2[e] += t2;
+        c1[e] += t1[e];
+        c2[e] += t2[e];
       }
     }
 #pragma unroll
@@ -177,11 +177,12 @@ __device__ __forceinline__ void lds_tile_epilogue(const GemmArgs& g, const f32x1
     const int gm = m0 + row;
     if (gm < g.M) {
       const float v[4] = {s.x, s.y, s.z, s.w};
-      float o[4];
+      float o[4], dm[4];
+      epilogue_dropout4(g, step, gm, gn, dm);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t1 = 0.0f, t2 = 0.0f;
-        o[e] = (gn + e < g.N) ? epilogue_elem(g, step, gm, gn + e, v[e], t1, t2) : 0.0f;
+        o[e] = (gn + e < g.N) ? epilogue_elem(g, dm[e], gm, gn + e, v[e], t1, t2) : 0.0f;
         cs1[e] += t1;
         cs2[e] += t2;
       }

@@ -172,12 +172,12 @@ __device__ __forceinline__ void gemm_ring2_tile(const GemmArgs& g, const int bx,
   for (int p4 = 0; p4 < 4; ++p4) {
     const float4 s = *reinterpret_cast<const float4*>(red + (trow + 32 * p4) * TS + c4);
     const float accv[4] = {s.x, s.y, s.z, s.w};
+    float t1[4], t2[4];
+    bnx_row4(g, step, gm4[p4] < g.M, gm4[p4], gn, accv, xpre[p4], val[p4], av[p4], t1, t2);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float t1, t2;
-      bnx_elem(g, step, gm4[p4] < g.M && gn + e < g.N, gm4[p4], gn + e, accv[e], xpre[p4], e, val[p4][e], av[p4][e], t1, t2);
-      c1[e] += t1;
-      c2[e] += t2;
+      c1[e] += t1[e];
+      c2[e] += t2[e];
     }
   }
 #pragma unroll

@@ -193,13 +193,14 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(BnFwdArgs p) {
     const int b = blockIdx.y * kApplyRows + rl + 8 * i;
     if (b >= p.B) break;
     const size_t ro = (size_t)b * p.N;
-    float x[4];
+    float x[4], dm[4];
+    dropout_mult4(p.drop, step, b, p.N, c.j, p.N, dm);
 #pragma unroll
     for (int e = 0; e < 4; ++e) x[e] = xin[i][e];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (p.has_bn) x[e] = (x[e] - mean[e]) * rstd[e] * ga[e] + be[e];
-      x[e] *= dropout_mult(p.drop, step, ro + c.j + e);
+      x[e] *= dm[e];
     }
     st4(p.h, ro, c, x);
   }

@@ -12,11 +12,14 @@ struct SegTable {
 
 // One launch over the flat buffers.  t = *step_dev + 1; lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (Keras
 // optimizer_v2.Adam, epsilon outside the square root and not bias-corrected).
+// flag (may be null): a lipasr_flag_wait counter that receives `flag_value` when this kernel STARTS, i.e. when everything the
+// stream ran before it -- the whole forward / backward pass -- has finished (lipasr_mlp_adam_project_product_signal).
 __global__ __launch_bounds__(256) void adam_nonneg_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v, size_t n4,
                                                            SegTable segs, const int* __restrict__ step_dev, float lr,
-                                                           float b1, float b2, float eps, float gscale) {
+                                                           float b1, float b2, float eps, float gscale, int* flag, int flag_value) {
   __shared__ float lr_t_s;
+  if (flag && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(flag, flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   if (threadIdx.x == 0) {
     const double t = (double)(*step_dev + 1);
     lr_t_s = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
@@ -130,7 +133,7 @@ extern "C" {
 
 static int adam_launch(lipasr_mlp_t m, float* params, const float* grads, float* adam_m, float* adam_v, int* step_dev,
                        float lr, float beta1, float beta2, float eps, float grad_scale, bool bump_step,
-                       lipasr_stream_t stream) {
+                       lipasr_stream_t stream, int* flag = nullptr, int flag_value = 0) {
   LP_CHECK_ARG(m && params && grads && adam_m && adam_v && step_dev, "lipasr_mlp_adam_nonneg: null argument");
   LP_CHECK_ARG(((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
                  reinterpret_cast<uintptr_t>(adam_m) | reinterpret_cast<uintptr_t>(adam_v)) & 15) == 0,
@@ -154,7 +157,7 @@ static int adam_launch(lipasr_mlp_t m, float* params, const float* grads, float*
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_nonneg_kernel, dim3(blocks), dim3(256), 0, S(stream), params, grads, adam_m, adam_v, n4, segs,
-                     step_dev, lr, beta1, beta2, eps, grad_scale);
+                     step_dev, lr, beta1, beta2, eps, grad_scale, flag, flag_value);
   LP_LAUNCH_CHECK();
   if (bump_step) {
     // a second one-thread launch: a last-workgroup ticket inside the Adam kernel measured 11 us slower (atomics
@@ -175,7 +178,15 @@ int lipasr_mlp_adam_project_product(lipasr_mlp_t m, float* params, const float* 
                                     int* step_dev, float lr, float beta1, float beta2, float eps, float grad_scale,
                                     float rho, const int* order, int n_order, float* norms_out,
                                     lipasr_stream_t stream) {
-  int rc = adam_launch(m, params, grads, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, grad_scale, false, stream);
+  return lipasr_mlp_adam_project_product_signal(m, params, grads, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, grad_scale, rho, order,
+                                                n_order, norms_out, nullptr, 0, stream);
+}
+
+int lipasr_mlp_adam_project_product_signal(lipasr_mlp_t m, float* params, const float* grads, float* adam_m, float* adam_v,
+                                           int* step_dev, float lr, float beta1, float beta2, float eps, float grad_scale,
+                                           float rho, const int* order, int n_order, float* norms_out, int* flag, int value,
+                                           lipasr_stream_t stream) {
+  int rc = adam_launch(m, params, grads, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, grad_scale, false, stream, flag, value);
   if (rc != LIPASR_OK) return rc;
   float* Ws[LIPASR_MAX_LAYERS];
   int rows[LIPASR_MAX_LAYERS], cols[LIPASR_MAX_LAYERS];

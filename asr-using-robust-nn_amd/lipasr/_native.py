@@ -90,6 +90,7 @@ PROTOTYPES = {
     "lipasr_mlp_adam_nonneg": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, f32, f32, f32, f32, f32, c_s]),
     "lipasr_mlp_project_product": (i32, [c_h, c_f, f32, PI, i32, c_f, c_s]),
     "lipasr_mlp_adam_project_product": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, f32, f32, f32, f32, f32, f32, PI, i32, c_f, c_s]),
+    "lipasr_mlp_adam_project_product_signal": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, f32, f32, f32, f32, f32, f32, PI, i32, c_f, C.c_void_p, i32, c_s]),
     "lipasr_mlp_project_per_layer": (i32, [c_h, c_f, f32, c_f, i32, i32, c_f, c_s]),
     "lipasr_mlp_product_norm": (i32, [c_h, c_f, c_f, c_s]),
     "lipasr_mlp_predict": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_f, c_s]),
@@ -140,7 +141,20 @@ PROTOTYPES = {
     "lipasr_debug_table": (i32, [i32, i32, C.POINTER(f32), i32]),
 }
 
+# entry points an older build named by LIPASR_LIBRARY (the parent commit's, for A/B timing) does not have yet: name -> the
+# lipasr_version() that added it.  Callers ask has() and otherwise make the calls the entry point stands for.
+SINCE = {"lipasr_mlp_adam_project_product_signal": 560}
+lib.lipasr_version.restype = i32
+_VERSION = lib.lipasr_version()
+
+
+def has(name) -> bool:
+    return _VERSION >= SINCE.get(name, 0)
+
+
 for _name, (_res, _args) in PROTOTYPES.items():
+    if not has(_name):
+        continue
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync
     _fn.restype = _res
     _fn.argtypes = _args

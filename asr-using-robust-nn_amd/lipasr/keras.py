@@ -575,9 +575,16 @@ class Model:
         N.check(N.lib.lipasr_mlp_adam_nonneg(self._plan, N.ptr(self._params), N.ptr(self._grads), N.ptr(self._adam_m), N.ptr(self._adam_v),
                                              N.ptr(self._step), lr, b1, b2, eps, grad_scale, N.stream_ptr()))
 
-    def apply_adam_project_product(self, rho, order, norms_out, grad_scale=1.0):
-        """Adam + NonNeg + simple_norm_constraint (``order``: N.int_array of layer visits) as one native call."""
+    def apply_adam_project_product(self, rho, order, norms_out, grad_scale=1.0, flag=None, value=0):
+        """Adam + NonNeg + simple_norm_constraint (``order``: N.int_array of layer visits) as one native call.
+        flag (device pointer of an int32 counter): the Adam kernel stores ``value`` there when it starts, i.e. when the step's
+        forward and backward pass are done (lipasr_mlp_adam_project_product_signal)."""
         lr, b1, b2, eps = self._adam
+        if flag is not None:
+            N.check(N.lib.lipasr_mlp_adam_project_product_signal(self._plan, N.ptr(self._params), N.ptr(self._grads), N.ptr(self._adam_m),
+                                                                 N.ptr(self._adam_v), N.ptr(self._step), lr, b1, b2, eps, grad_scale, float(rho),
+                                                                 order, len(order), N.ptr(norms_out), flag, int(value), N.stream_ptr()))
+            return
         N.check(N.lib.lipasr_mlp_adam_project_product(self._plan, N.ptr(self._params), N.ptr(self._grads), N.ptr(self._adam_m),
                                                       N.ptr(self._adam_v), N.ptr(self._step), lr, b1, b2, eps, grad_scale, float(rho), order,
                                                       len(order), N.ptr(norms_out), N.stream_ptr()))

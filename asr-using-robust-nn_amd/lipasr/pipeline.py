@@ -131,6 +131,14 @@ class TrainPipeline:
             self._flags = torch.zeros(2 * self._nbuf, dtype=torch.int32, device=self.dev)  # ready[b] | free[b]
             self._flag_err = torch.zeros(1, dtype=torch.int32).pin_memory()                # 1: a wait is overdue, 2: a wait gave up
             self._flag_timeout_ms = int(_os.environ.get("LIPASR_FLAG_TIMEOUT_MS", "30000"))  # what a wait sits out before it reports
+        # "classifier done with buffer b" is true as soon as the step's forward / backward pass is: the eager single-device step
+        # with the product constraint lets its Adam kernel raise free[b] when it starts (lipasr_mlp_adam_project_product_signal)
+        # instead of ending with a one-wavefront signal launch, 2.5-5 us and a launch boundary on the critical stream.  Every
+        # other shape of a step (graphs, data parallel, synchronized BatchNorm, another constraint) keeps the trailing launch.
+        # LIPASR_ADAM_SIGNAL=0: the trailing launch everywhere (A/B timing).
+        self._adam_signal = (self._flags is not None and self.dp.world == 1 and not self.sync_bn and not self.use_graph
+                             and self.constraint == "product" and N.has("lipasr_mlp_adam_project_product_signal")
+                             and _os.environ.get("LIPASR_ADAM_SIGNAL", "1") == "1")
         self._ev_feat = [torch.cuda.Event() for _ in range(self._nbuf)]   # features of buffer b are ready
         self._ev_free = [None] * self._nbuf                             # training has finished reading buffer b
         self._i = 0
@@ -372,11 +380,11 @@ class TrainPipeline:
         hb.wait()
         self._update()
 
-    def _update(self):
+    def _update(self, free_flag=None):
         m = self.model
         if self.constraint == "product":
             # Adam + NonNeg + simple_norm_constraint in one native call (the step counter moves inside the projection)
-            m.apply_adam_project_product(self.rho, self._order, self.norms)
+            m.apply_adam_project_product(self.rho, self._order, self.norms, flag=free_flag, value=self._i)
             return
         m.apply_adam()
         if self.constraint == "per_layer":
@@ -497,7 +505,7 @@ class TrainPipeline:
             elif not self.use_graph:
                 if self.dp.world == 1:
                     self._attack_and_train(bsz, b, gb)
-                    self._update()
+                    self._update(self._flags[self._nbuf + b:].data_ptr() if self._adam_signal else None)
                 elif self.overlap_buckets:
                     self._attack_and_train(bsz, b, gb, defer_dw0=True)
                     self._reduce_and_update_eager(bsz, b)
@@ -532,7 +540,9 @@ class TrainPipeline:
                     N.check(N.lib.lipasr_graph_launch(self.h.h, g[1], N.stream_ptr()))
             if prof is not None:
                 prof[1].record(self.stream)
-            if self._flags is not None:
+            if self._adam_signal:
+                pass  # free[b] went out with the Adam kernel
+            elif self._flags is not None:
                 N.check(N.lib.lipasr_flag_signal(self.h.h, self._flags[self._nbuf + b:].data_ptr(), self._i, N.stream_ptr()))
             else:
                 ev = torch.cuda.Event()

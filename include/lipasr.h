@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 550.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 560.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -19,6 +19,7 @@
  * and lipasr_debug_group_launches (launch counters per kernel instance).
  * 550: the backward pass of the short-window MFCC plans (n_fft = win_length = 441, hop 220 of Speaker recognition):
  * lipasr_mfcc_plan_vjp_short.
+ * 560: lipasr_mlp_adam_project_product_signal (the optimizer step that also raises a lipasr_flag_wait counter when it starts).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -306,6 +307,16 @@ int lipasr_mlp_adam_project_product(lipasr_mlp_t m, float* params, const float* 
                                     float* adam_v, int* step_dev, float lr, float beta1, float beta2,
                                     float eps, float grad_scale, float rho, const int* order,
                                     int n_order, float* norms_out, lipasr_stream_t stream);
+/* The same call, which also does what lipasr_flag_signal(flag, value) in front of it would do: the first thread of the Adam
+ * kernel stores `value` to `flag` (release, device scope) when the kernel starts.  By then everything `stream` ran before --
+ * a training step's forward and backward pass, i.e. every read of the step's input batch -- has finished, so a pipeline whose
+ * other stream waits (lipasr_flag_wait) to refill that batch's buffer needs no one-wavefront signal launch at the end of the
+ * step, on its critical stream.  flag == NULL: exactly lipasr_mlp_adam_project_product. */
+int lipasr_mlp_adam_project_product_signal(lipasr_mlp_t m, float* params, const float* grads, float* adam_m,
+                                           float* adam_v, int* step_dev, float lr, float beta1, float beta2,
+                                           float eps, float grad_scale, float rho, const int* order,
+                                           int n_order, float* norms_out, int* flag, int value,
+                                           lipasr_stream_t stream);
 int lipasr_mlp_project_product(lipasr_mlp_t m, float* params, float rho, const int* order, int n_order,
                                float* norms_out, lipasr_stream_t stream);
 int lipasr_mlp_project_per_layer(lipasr_mlp_t m, float* params, float rho, float* v_state, int warm,
