@@ -41,6 +41,7 @@ int device_cus();
 #define LP_DYN_LDS(fn, bytes) do { if (!lipasr::ensure_dyn_lds(reinterpret_cast<const void*>(fn), (bytes))) return LIPASR_EHIP; } while (0)
 
 struct MfccPlan;
+struct DolphinPlan;
 
 }  // namespace lipasr
 
@@ -59,6 +60,7 @@ struct lipasr_ctx {
   std::vector<struct lipasr_mlp*> mlps;    // classifier plans made on this handle and still alive
   lipasr::MfccPlan* mfcc = nullptr;               // the handle's default MFCC plan (lipasr_mfcc_plan); also in mfcc_plans
   std::vector<lipasr::MfccPlan*> mfcc_plans;      // every MFCC plan made on this handle and still alive
+  std::vector<lipasr::DolphinPlan*> dolphin_plans;  // every DolphinAttack plan made on this handle and still alive
 };
 
 namespace lipasr {

@@ -128,6 +128,13 @@ PROTOTYPES = {
     "lipasr_mfcc_plan_set": (i32, [c_h, i32, i32]),
     "lipasr_mfcc_profile_begin": (i32, [c_h, i32]),
     "lipasr_mfcc_profile_end": (i32, [c_h, C.POINTER(f32), PI]),
+    "lipasr_dolphin_create": (i32, [c_h, i32, i32, i32, C.c_double, C.c_double, C.POINTER(c_h)]),
+    "lipasr_dolphin_destroy": (i32, [c_h]),
+    "lipasr_dolphin_bandpass": (i32, [c_h, c_f, c_f, i32, c_f, c_s]),
+    "lipasr_dolphin_generate": (i32, [c_h, c_f, c_f, i32, c_f, c_f, c_s]),
+    "lipasr_dolphin_record": (i32, [c_h, c_f, c_f, i32, f32, f32, c_f, c_s]),
+    "lipasr_dolphin_generate_recorded": (i32, [c_h, c_f, c_f, i32, f32, f32, c_f, c_s]),
+    "lipasr_dolphin_table": (i32, [i32, i32, C.POINTER(C.c_double), i32]),
     "lipasr_add_noise_f32": (i32, [c_h, c_f, i32, i32, i32, f32, f32, u64, c_s]),
     "lipasr_debug_set": (i32, [c_h, i32, i32]),
     "lipasr_debug_gemm_mode": (i32, [i32]),
@@ -143,7 +150,9 @@ PROTOTYPES = {
 
 # entry points an older build named by LIPASR_LIBRARY (the parent commit's, for A/B timing) does not have yet: name -> the
 # lipasr_version() that added it.  Callers ask has() and otherwise make the calls the entry point stands for.
-SINCE = {"lipasr_mlp_adam_project_product_signal": 560}
+SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create": 570, "lipasr_dolphin_destroy": 570,
+         "lipasr_dolphin_bandpass": 570, "lipasr_dolphin_generate": 570, "lipasr_dolphin_record": 570,
+         "lipasr_dolphin_generate_recorded": 570, "lipasr_dolphin_table": 570}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -331,6 +340,16 @@ def shutdown():
 import atexit  # noqa: E402
 
 atexit.register(shutdown)
+
+
+def dolphin_table(which: int, sr_in: int = 16000):
+    """Host-only fp64 tables of the DolphinAttack chain (0 SOS[10][6], 1 h_up, 2 h_dn, 3 M^64 [10][4]) as numpy float64."""
+    import numpy as np
+
+    n = check(lib.lipasr_dolphin_table(which, sr_in, None, 0))
+    out = np.zeros(n, dtype=np.float64)
+    check(lib.lipasr_dolphin_table(which, sr_in, out.ctypes.data_as(C.POINTER(C.c_double)), n))
+    return out
 
 
 def debug_table(which: int, sr_in: int = 16000):

@@ -10,6 +10,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     "noise over [A]udio or [M]FCC"                         over="audio" | "mfcc"                   (:327)
     "[F]GSM/Carlini[L2]/Carlini[Linf]/[P]GD/[J]SMA"        kind="fgsm" | "l2" | "linf" | "pgd" | "jsma"   (:494)
     (no prompt: ART's norm keyword of FGM / PGD)           --norm inf | 1 | 2 (default inf, the reference's)
+    (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
 """
 from __future__ import annotations
 
@@ -28,6 +29,9 @@ SNRS = [60, 30, 20, 15, 10, 5, 0]                                               
 MFCC_SIGMAS = np.linspace(0, 100, 20)                                                 # :312
 MFCC_ALPHAS = np.linspace(0, 100, 30)                                                 # :452
 MIXTURE_P = 0.01                                                                      # :355, :451
+# ours (the reference has no such sweep): the constant added to the normalised voice before the carrier multiplies it --
+# dolphin_attack.m's 0.001 first, the DolphinAttack paper's 1 last
+DOLPHIN_CARRIER_LEVELS = [0.001, 0.01, 0.1, 0.3, 1.0]
 
 
 def accuracy(predictions, labels_onehot):
@@ -210,6 +214,67 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
     return _sweep(clfs, grid, make, labels, "adversarial")
 
 
+def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, grid=DOLPHIN_CARRIER_LEVELS, a1=1.0, a2=0.5,
+                  standardize="before", points=None, limit=None):
+    """DolphinAttack (lipasr.dolphin) against the carrier level: every file of ``test_filenames`` (16 kHz) becomes amplitude-
+    modulated ultrasound on a 30 kHz carrier, a microphone with the non-linearity a1 s + a2 s^2 records it
+    (DolphinAttack.generate_recorded: the 192 kHz signal never reaches memory), and the recorded 16 kHz clip goes through the
+    MFCC extractor with the file's own length.  Features are standardized with the statistics of (train, val, clean test MFCCs),
+    as in white_box_sweep(over="audio").  Accuracy is against the command's OWN label: a high value means that the inaudible
+    command was understood.  A grid item of None stands for no attack (the file itself through the same extraction): there the
+    sweep agrees with black_box_sweep(over="audio") at sigma 0.  Returns (grid, {model name: accuracies})."""
+    from .dolphin import DolphinAttack
+
+    if test_filenames is None:
+        raise ValueError("dolphin_sweep needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+    test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+    labels = test_labels[:limit] if limit else test_labels
+    clips = []
+    for fn in test_filenames:
+        x, sr = A.read_wav(fn)
+        if sr != 16000:
+            raise ValueError(f"{fn}: {sr} Hz; the DolphinAttack chain takes 16 kHz files")
+        clips.append(x)
+    if standardize == "before":
+        train_data, val_data, _ = A.standardize_dataset(train_data, val_data, test_data)
+    grid = list(grid)[:points]
+    lens = np.array([len(x) for x in clips], dtype=np.int32)
+    same = bool(np.all(lens == lens[0]))
+    # one length: rows as they are, extraction as black_box_sweep(over="audio") runs it; several: rows padded to the longest clip
+    # rounded up to a multiple of 4000 samples (compute_mfcc_all_files' rule), each clip with its own length
+    n_pad = int(lens[0]) if same else -(-int(lens.max()) // 4000) * 4000
+    w, lt = _padded_rows(list(enumerate(clips)), n_pad, lens)
+    lt = None if same else lt
+    bmax = min(w.shape[0], 256)
+    ex = A._extractor(16000, n_pad, bmax)
+
+    def features(rows):
+        out = []
+        for s in range(0, rows.shape[0], ex.batch_max):
+            r = rows[s:s + ex.batch_max]
+            out.append(ex.from_22k(ex.resample(r), 44) if lt is None else ex(r, 44, n_valid=lt[s:s + ex.batch_max]))
+        return torch.cat(out)
+
+    clean = features(w)
+    sc = A.StandardScaler().fit(torch.cat([A._to_dev(train_data), A._to_dev(val_data), clean]))
+    acc = {name: [] for name in models}
+    for item in grid:
+        if item is None:
+            feats = clean
+        else:
+            da = DolphinAttack(16000, n_pad, bmax, carrier_level=float(item))
+            rec = torch.cat([da.generate_recorded(w[s:s + bmax], None if lt is None else lt[s:s + bmax], a1=a1, a2=a2)
+                             for s in range(0, w.shape[0], bmax)])
+            da.close()
+            feats = features(rec)
+        x = sc.transform_device(feats).cpu().numpy()
+        for name, model in models.items():
+            a = accuracy(model.predict(x), labels)
+            acc[name].append(a)
+            print(f"Accuracy on DolphinAttack recordings{'' if name == 'constrained' else ' ' + name}: {a * 100}% (carrier level {item})")
+    return grid, {k: np.asarray(v) for k, v in acc.items()}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="attacks.py's evaluation menu as flags")
     ap.add_argument("--path", default="processed_google_dataset/")
@@ -217,7 +282,7 @@ def main(argv=None):
     ap.add_argument("--constrained", default="bin/models_constrained/model_constrained_Rho01_dropout01.h5")
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
-    ap.add_argument("--attack", choices=["black", "white"], default="black")
+    ap.add_argument("--attack", choices=["black", "white", "dolphin"], default="black")
     ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points")
@@ -235,6 +300,10 @@ def main(argv=None):
             labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)  # :298-304
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
+    if args.attack == "dolphin":
+        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
+        labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
+        return dolphin_sweep(models, train_data, val_data, test_data, labels, names, standardize=args.standardize, points=args.points)
     kw = {}
     if args.over == "audio":
         kw.update(over="audio", test_filenames=np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist())

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 560.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 570.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -20,6 +20,8 @@
  * 550: the backward pass of the short-window MFCC plans (n_fft = win_length = 441, hop 220 of Speaker recognition):
  * lipasr_mfcc_plan_vjp_short.
  * 560: lipasr_mlp_adam_project_product_signal (the optimizer step that also raises a lipasr_flag_wait counter when it starts).
+ * 570: the DolphinAttack chain (ultrasonic AM generator and microphone model): lipasr_dolphin_create / _destroy / _bandpass /
+ * _generate / _record / _generate_recorded and the host-only lipasr_dolphin_table.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -64,6 +66,7 @@ extern "C" {
 typedef struct lipasr_ctx* lipasr_handle_t;
 typedef struct lipasr_mlp* lipasr_mlp_t;
 typedef struct lipasr_mfcc* lipasr_mfcc_t;
+typedef struct lipasr_dolphin* lipasr_dolphin_t;
 typedef void* lipasr_stream_t; /* hipStream_t */
 
 /* ------------------------------------------------------------------ core */
@@ -577,6 +580,42 @@ int lipasr_mfcc_plan_profile_end(lipasr_mfcc_t p, float* avg_ms3, int* n_calls);
  *   that are not cache-warm: DESIGN.md section 3).
  * Replaces the arithmetic of librosa.feature.mfcc's STFT, extract_features_construct_dataset.py:30. */
 int lipasr_mfcc_plan_set(lipasr_mfcc_t p, int key, int value);
+
+/* ------------------------------------------------------------------ DolphinAttack: inaudible voice commands
+ * "Voice digit recogniton/dolphin_attack.m": a 16 kHz voice command as amplitude-modulated ultrasound at 192 kHz, and -- what the
+ * script stops short of -- the signal a microphone with a quadratic non-linearity records from it.  One clip of n valid samples x:
+ *   band-pass  v = SOS(x): Butterworth order 10, 100 Hz - 7 kHz, as ten biquads (zero initial state, causal).  The script's
+ *              filter(b, a, x) on the 20th-order transfer function is unstable in double precision (roots of a at radius 1.0036);
+ *              this is the filter that butter() call designs.
+ *   up         u[k] = sum_j h_up[k + 120 - 12 j] v[j], k < 12 n (MATLAB resample(v, 12, 1): firls x Kaiser(5), 241 taps, sum 12)
+ *   peak 1     m1 = max|u|,  uh = u / m1 (0 when m1 = 0)
+ *   modulate   s'[k] = (uh[k] + carrier_level) cos(2 pi carrier_hz k / 192000), the phase (k carrier_hz) mod 192000 in integers
+ *   peak 2     m2 = max|s'|,  s = s' / m2 (a silent clip gives the carrier at amplitude 1; 0 when m2 = 0)
+ *   microphone w = a1 s + a2 s^2
+ *   record     r[i] = sum_k h_dn[12 i + 120 - k] w[k], i < n (resample(w, 1, 12): the same filter with sum 1)
+ * The script's carrier_level is 0.001, which makes the recorded signal essentially v^2; 1 is the DolphinAttack paper's form.
+ * Arrays: wav, voice, rec [batch][n_samp_max] float32; ultrasound [batch][12 n_samp_max]; peaks [batch][2] = {m1, m2}; n_valid
+ * device int [batch] or NULL (= n_samp_max): samples at or past n_valid[u] are never read, outputs at or past n_valid[u]
+ * (12 n_valid[u]) are written as 0, the peaks are taken over the valid part, and a clip's result is bit-identical to launching
+ * it alone.  The band-pass runs in fp64 (one workgroup per clip, a chunked scan per section), everything else in fp32; sums run
+ * in a fixed order.  No launch function synchronises or allocates.  lipasr_dolphin_generate_recorded gives the bits of
+ * _generate followed by _record without the [batch][12 n_samp_max] array ever existing (the 192 kHz signal stays in LDS).
+ * Errors: sr_in other than 16000: LIPASR_EUNSUPPORTED; carrier_hz not an integer in (7000, 89000), carrier_level < 0, batch >
+ * batch_max, a null or destroyed plan: LIPASR_EINVAL.  Plans still alive are freed by lipasr_destroy, next to the MFCC plans. */
+int lipasr_dolphin_create(lipasr_handle_t h, int sr_in, int n_samp_max, int batch_max, double carrier_hz, double carrier_level,
+                          lipasr_dolphin_t* out);
+int lipasr_dolphin_destroy(lipasr_dolphin_t p);
+int lipasr_dolphin_bandpass(lipasr_dolphin_t p, const float* wav, const int* n_valid, int batch, float* voice, lipasr_stream_t stream);
+int lipasr_dolphin_generate(lipasr_dolphin_t p, const float* wav, const int* n_valid, int batch, float* ultrasound, float* peaks_or_null,
+                            lipasr_stream_t stream);
+int lipasr_dolphin_record(lipasr_dolphin_t p, const float* ultrasound, const int* n_valid, int batch, float a1, float a2, float* rec,
+                          lipasr_stream_t stream);
+int lipasr_dolphin_generate_recorded(lipasr_dolphin_t p, const float* wav, const int* n_valid, int batch, float a1, float a2,
+                                     float* rec, lipasr_stream_t stream);
+/* Host-only (no GPU needed), fp64 as built: which 0 the band-pass as SOS[10][6] (b0 b1 b2 a0 a1 a2 per section), 1 h_up[241],
+ * 2 h_dn[241], 3 each section's state-transition matrix to the power 64 [10][4] (the carry of the chunked scan).  Returns the
+ * element count (negative = error); out may be NULL to query the size. */
+int lipasr_dolphin_table(int which, int sr_in, double* out, int cap);
 
 /* A12 audio-domain noise on device, Philox RNG (attacks.py:73-86, 145-183, 222-245), in place on
  * y [batch][n]:  mode 0: y + N(0, p0)               (add_white_noise, sigma = p0)
