@@ -305,6 +305,29 @@ __global__ __launch_bounds__(256) void softmax_vjp_kernel(const float* __restric
   }
 }
 
+// softmax_vjp_kernel for the one-hot upstream vector e_cls, made in registers instead of read: the same operations in the same
+// order, so dz is the one softmax_vjp_kernel gives for that vector, bit for bit (lipasr_mlp_jacobian: one launch per class, no
+// [B][C] vector to upload)
+__global__ __launch_bounds__(256) void softmax_vjp_onehot_kernel(const float* __restrict__ z, int cls, int B, int C, int on_logits,
+                                                                  float* __restrict__ prob, float* __restrict__ dz) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float* zr = z + (size_t)b * C;
+  float mx = zr[0];
+  for (int c = 1; c < C; ++c) mx = fmaxf(mx, zr[c]);
+  float se = 0.0f;
+  for (int c = 0; c < C; ++c) se += expf(zr[c] - mx);
+  const float inv = 1.0f / se;
+  float dot = 0.0f;
+  for (int c = 0; c < C; ++c) dot = fmaf(expf(zr[c] - mx) * inv, c == cls ? 1.0f : 0.0f, dot);
+  for (int c = 0; c < C; ++c) {
+    const float pc = expf(zr[c] - mx) * inv;
+    const float vc = c == cls ? 1.0f : 0.0f;
+    if (prob) prob[(size_t)b * C + c] = pc;
+    dz[(size_t)b * C + c] = on_logits ? vc : pc * (vc - dot);
+  }
+}
+
 // softmax + categorical cross-entropy from logits, one thread per row.
 //   prob (optional), dz = (p - y) * inv_batch (optional), loss_rows = -sum y log_softmax(z) (optional),
 //   correct_rows = [argmax p == argmax y] (optional), onehot_out = one-hot argmax z (optional)
@@ -559,9 +582,9 @@ static int forward_infer(lipasr_mlp* m, const float* params, const float* bnstat
 }
 
 // inference-mode backward to the input from dz at the logits (in m->ws + offDzLast).
-// final_mode 0: store dx; 1: fused sign step on x_adv.
+// final_mode 0: store dx; 1: fused sign step on x_adv.  ld_dx: floats between the rows of dx (0: the input width, rows packed).
 static int backward_infer(lipasr_mlp* m, const float* params, const float* bnstate, int batch, float* dx, float* x_adv,
-                          const float* x0, float alpha, float eps, hipStream_t st, float g0 = 1.0f) {
+                          const float* x0, float alpha, float eps, hipStream_t st, float g0 = 1.0f, int ld_dx = 0) {
   const float* gin = m->ws + m->offDzLast;
   float* pp[2] = {m->ws + m->offG0, m->ws + m->offG1};
   int cur = 0;
@@ -583,7 +606,7 @@ static int backward_infer(lipasr_mlp* m, const float* params, const float* bnsta
       gin = pp[cur];
       cur ^= 1;
     } else {
-      GemmArgs g = gemm_args(gin, L.n_out, params + L.offW, L.n_out, dx, L.n_in, batch, L.n_in, L.n_out,
+      GemmArgs g = gemm_args(gin, L.n_out, params + L.offW, L.n_out, dx, ld_dx ? ld_dx : L.n_in, batch, L.n_in, L.n_out,
                              x_adv ? EPI_SIGNSTEP : EPI_STORE);
       g.x_adv = x_adv;
       g.x0 = x0;
@@ -975,6 +998,37 @@ int lipasr_mlp_output_vjp(lipasr_mlp_t m, const float* params, const float* bnst
                      probs_out, m->ws + m->offDzLast);
   LP_LAUNCH_CHECK();
   return backward_infer(m, params, bnstate, batch, dx, nullptr, nullptr, 0.0f, 0.0f, st);
+}
+
+// The whole Jacobian from ONE forward: backward_infer only reads what forward_infer(keep_a) left (the post-ReLU activations) and
+// writes the two ping-pong gradient buffers and dx, so the C backward chains follow one another on the same saved state.  The last
+// dX GEMM stores class c's rows straight into the caller's layout (ldc = stride_b): n_layers (1 + C) GEMM launches and C small ones.
+int lipasr_mlp_jacobian(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, int on_logits, int batch,
+                        float* probs_out, float* jac, long stride_b, long stride_c, lipasr_stream_t stream) {
+  int rc = check_batch("lipasr_mlp_jacobian", m, batch);
+  if (rc != LIPASR_OK) return rc;
+  LP_CHECK_ARG(params && x && jac, "lipasr_mlp_jacobian: null argument");
+  LP_CHECK_ARG(m->n_state == 0 || bnstate, "lipasr_mlp_jacobian: bnstate is null");
+  const int C = m->L[m->n_layers - 1].n_out;
+  const long n = m->L[0].n_in;
+  LP_CHECK_ARG(C <= 32, "lipasr_mlp_jacobian: %d classes; at most 32 are supported", C);
+  // [B][C][n] (rows of a sample together) or class-major [C][B][n], padded or not; nothing else is known not to overlap
+  LP_CHECK_ARG((stride_c >= n && stride_b >= (long)C * stride_c) || (stride_b >= n && stride_c >= (long)batch * stride_b),
+               "lipasr_mlp_jacobian: strides (%ld, %ld) are neither [batch][classes][%ld] nor [classes][batch][%ld]", stride_b, stride_c,
+               n, n);
+  LP_CHECK_ARG(stride_b <= 0x7fffffffL, "lipasr_mlp_jacobian: stride_b %ld does not fit a leading dimension", stride_b);
+  hipStream_t st = S(stream);
+  float* lg = m->ws + m->offLogits;
+  rc = forward_infer(m, params, bnstate, x, batch, true, lg, st);
+  if (rc != LIPASR_OK) return rc;
+  for (int c = 0; c < C; ++c) {
+    hipLaunchKernelGGL(softmax_vjp_onehot_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, lg, c, batch, C, on_logits ? 1 : 0,
+                       c == 0 ? probs_out : (float*)nullptr, m->ws + m->offDzLast);
+    LP_LAUNCH_CHECK();
+    rc = backward_infer(m, params, bnstate, batch, jac + (size_t)c * stride_c, nullptr, nullptr, 0.0f, 0.0f, st, 1.0f, (int)stride_b);
+    if (rc != LIPASR_OK) return rc;
+  }
+  return LIPASR_OK;
 }
 
 int lipasr_mlp_set_gemm_tiles(lipasr_mlp_t m, int lds_min_tiles) {

@@ -101,6 +101,8 @@ PROTOTYPES = {
     "lipasr_mlp_set_cu_budget": (i32, [c_h, i32]),
     "lipasr_mlp_exchange_errors": (i32, [c_h, C.POINTER(C.c_int)]),
     "lipasr_mlp_output_vjp": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, c_f, c_f, c_s]),
+    "lipasr_mlp_jacobian": (i32, [c_h, c_f, c_f, c_f, i32, i32, c_f, c_f, C.c_long, C.c_long, c_s]),
+    "lipasr_jacobian_sigma": (i32, [c_h, c_f, i32, i32, i32, C.c_long, C.c_long, c_f, c_f, c_f, c_s]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -152,7 +154,8 @@ PROTOTYPES = {
 # lipasr_version() that added it.  Callers ask has() and otherwise make the calls the entry point stands for.
 SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create": 570, "lipasr_dolphin_destroy": 570,
          "lipasr_dolphin_bandpass": 570, "lipasr_dolphin_generate": 570, "lipasr_dolphin_record": 570,
-         "lipasr_dolphin_generate_recorded": 570, "lipasr_dolphin_table": 570}
+         "lipasr_dolphin_generate_recorded": 570, "lipasr_dolphin_table": 570, "lipasr_mlp_jacobian": 580,
+         "lipasr_jacobian_sigma": 580}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 

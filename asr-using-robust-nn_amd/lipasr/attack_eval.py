@@ -11,6 +11,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     "[F]GSM/Carlini[L2]/Carlini[Linf]/[P]GD/[J]SMA"        kind="fgsm" | "l2" | "linf" | "pgd" | "jsma"   (:494)
     (no prompt: ART's norm keyword of FGM / PGD)           --norm inf | 1 | 2 (default inf, the reference's)
     (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
+    (no prompt: the Lipschitz read-outs, global and local) attack="lipschitz": lipschitz_report over="mfcc" | "audio"
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from . import attacks as A
+from .extract_features_construct_dataset import get_lipschitz_constrained, get_local_lipschitz, get_norms, get_upper_lipschitz
 from .keras import CategoricalCrossentropy, load_model, to_categorical
 
 # the grids the reference hard-codes
@@ -104,10 +106,31 @@ def _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels,
         raise ValueError(f"domain={domain!r}: '22k' or 'input'")
     test_filenames = list(test_filenames[:limit] if limit else test_filenames)
     labels = test_labels[:limit] if limit else test_labels
-    if standardize == "before":
-        train_data, val_data, _ = A.standardize_dataset(train_data, val_data, test_data)
     n_classes = labels.shape[1]
     grid = list(AUDIO_SIGMAS if grid is None else grid)[:points]
+    work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
+    acc = {name: [] for name in models}
+    for item in grid:
+        for name, model in models.items():
+            pred = np.zeros((len(test_filenames), n_classes))
+            for sr, n, items, lens in work:
+                clf, x, lt = _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, lens)
+                idx = [i for i, _ in items]
+                cls = A.FastGradientMethod if kind == "fgsm" else A.ProjectedGradientDescent
+                adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x, None, lengths=lt) if item != 0 else x
+                pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
+            a = accuracy(pred, labels)
+            acc[name].append(a)
+            print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
+    return grid, {k: np.asarray(v) for k, v in acc.items()}
+
+
+def _audio_work(models, train_data, val_data, test_data, standardize, test_filenames):
+    """What the sweeps and read-outs over the audio of ``test_filenames`` share -> (work, scaler, bmax): the files grouped into
+    batches [(rate, row length, [(file index, samples)], per-clip lengths or None)], and the StandardScaler fitted on (train, val,
+    the files' clean MFCCs)."""
+    if standardize == "before":
+        train_data, val_data, _ = A.standardize_dataset(train_data, val_data, test_data)
     groups = A._files_to_batches(test_filenames)
     # A rate whose files differ in length goes through ONE extractor and one WaveformClassifier per model, the clips side by
     # side with lengths= (16 kHz and 8 kHz: the rates whose plans take per-clip lengths); rows are padded to the longest clip
@@ -142,28 +165,21 @@ def _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels,
             clean[idx] = torch.cat([ex(w[s:s + ex.batch_max], 44, n_valid=lt[s:s + ex.batch_max])
                                     for s in range(0, w.shape[0], ex.batch_max)]).cpu().numpy()
     sc = A.StandardScaler().fit(np.concatenate([np.asarray(train_data), np.asarray(val_data), clean]))
-    acc = {name: [] for name in models}
-    for item in grid:
-        for name, model in models.items():
-            pred = np.zeros((len(test_filenames), n_classes))
-            for sr, n, items, lens in work:
-                if lens is None:
-                    w, lt = A._to_dev(np.stack([x for _, x in items])), None
-                    ex = A._extractor(int(sr), int(n), min(w.shape[0], model._max_batch))
-                else:
-                    w, lt = _padded_rows(items, n, lens)
-                    ex = A._extractor(int(sr), int(n), min(w.shape[0], bmax))
-                cut = lambda s: None if lt is None else lt[s:s + ex.batch_max]
-                clf = A.WaveformClassifier(model, n_classes, extractor=ex, mean=sc.mean_, scale=sc.scale_, domain=domain)
-                x = torch.cat([ex.resample(w[s:s + ex.batch_max], n_valid=cut(s)) for s in range(0, w.shape[0], ex.batch_max)]) if domain == "22k" else w
-                idx = [i for i, _ in items]
-                cls = A.FastGradientMethod if kind == "fgsm" else A.ProjectedGradientDescent
-                adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x, None, lengths=lt) if item != 0 else x
-                pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
-            a = accuracy(pred, labels)
-            acc[name].append(a)
-            print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
-    return grid, {k: np.asarray(v) for k, v in acc.items()}
+    return work, sc, bmax
+
+
+def _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, lens):
+    """One batch of _audio_work on the device -> (WaveformClassifier over the batch's extractor, its rows in ``domain``, lengths)."""
+    if lens is None:
+        w, lt = A._to_dev(np.stack([x for _, x in items])), None
+        ex = A._extractor(int(sr), int(n), min(w.shape[0], model._max_batch))
+    else:
+        w, lt = _padded_rows(items, n, lens)
+        ex = A._extractor(int(sr), int(n), min(w.shape[0], bmax))
+    cut = lambda s: None if lt is None else lt[s:s + ex.batch_max]
+    clf = A.WaveformClassifier(model, n_classes, extractor=ex, mean=sc.mean_, scale=sc.scale_, domain=domain)
+    x = torch.cat([ex.resample(w[s:s + ex.batch_max], n_valid=cut(s)) for s in range(0, w.shape[0], ex.batch_max)]) if domain == "22k" else w
+    return clf, x, lt
 
 
 def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="fgsm", standardize="before", grid=None,
@@ -275,6 +291,52 @@ def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_fil
     return grid, {k: np.asarray(v) for k, v in acc.items()}
 
 
+def lipschitz_report(models, train_data, val_data, test_data, over="mfcc", standardize="before", test_filenames=None, domain="22k",
+                     limit=None):
+    """Per model: the reference's global read-outs -- get_upper_lipschitz(get_norms(model)) and get_lipschitz_constrained(model) --
+    next to what the model does at the test rows: max / mean / median of the local Lipschitz constant of its logits
+    (get_local_lipschitz).  over="mfcc": with respect to the MFCC rows of ``test_data``, taken where white_box_sweep attacks them:
+    standardised first with standardize="before"; with standardize="after" the rows as they are, which is the point that sweep
+    perturbs but NOT an input the deployed pipeline feeds the model (it standardises afterwards), so that figure describes the
+    sweep's setting, not the pipeline;
+    over="audio": with respect to the audio of ``test_filenames``, the 22 050 Hz signal (domain="22k") or the file's own samples
+    (domain="input"), files grouped and features standardised as white_box_sweep(over="audio") does.  limit: the first N rows /
+    files.  Returns {model name: {"upper", "constrained", "max", "mean", "median", "local": the per-row float64 array}}."""
+    if over == "audio":
+        if test_filenames is None:
+            raise ValueError("the read-out over audio needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+        if domain not in ("22k", "input"):
+            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
+    elif over == "mfcc":
+        if standardize == "before":
+            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
+        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
+    else:
+        raise ValueError("over must be 'audio' or 'mfcc'")
+    out = {}
+    for name, model in models.items():
+        if over == "mfcc":
+            clf = A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(x.shape[1],),
+                                           loss_object=CategoricalCrossentropy())
+            local = get_local_lipschitz(clf, x)
+        else:
+            local = np.zeros(len(test_filenames))
+            for sr, n, items, lens in work:
+                clf, rows, lt = _audio_rows(model, model._n_classes, sc, domain, bmax, sr, n, items, lens)
+                local[[i for i, _ in items]] = get_local_lipschitz(clf, rows, lengths=lt)
+        r = {"upper": float(get_upper_lipschitz(get_norms(model))), "constrained": float(get_lipschitz_constrained(model)),
+             "max": float(local.max()), "mean": float(local.mean()), "median": float(np.median(local)), "local": local}
+        out[name] = r
+        tag = "" if name == "constrained" else " " + name
+        print(f"Upper Lipschitz bound{tag}: {r['upper']}")
+        print(f"Lipschitz constant with the BatchNorm correction{tag}: {r['constrained']}")
+        print(f"Local Lipschitz constant over {len(local)} test {'rows' if over == 'mfcc' else 'files'}{tag}: "
+              f"max {r['max']} mean {r['mean']} median {r['median']}")
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="attacks.py's evaluation menu as flags")
     ap.add_argument("--path", default="processed_google_dataset/")
@@ -282,7 +344,7 @@ def main(argv=None):
     ap.add_argument("--constrained", default="bin/models_constrained/model_constrained_Rho01_dropout01.h5")
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
-    ap.add_argument("--attack", choices=["black", "white", "dolphin"], default="black")
+    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz"], default="black")
     ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points")
@@ -300,6 +362,10 @@ def main(argv=None):
             labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)  # :298-304
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
+    if args.attack == "lipschitz":
+        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
+        return lipschitz_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
+                                test_filenames=names)
     if args.attack == "dolphin":
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
         labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)

@@ -89,6 +89,11 @@ class TensorFlowV2Classifier:
         if model._n_classes != self.nb_classes or model._widths[0] != self.input_shape[0]:
             raise ValueError("nb_classes / input_shape do not match the model")
 
+    @property
+    def batch_limit(self):
+        """Rows one native call takes (the model's max_batch)."""
+        return self.model._max_batch
+
     def predict(self, x, batch_size=128):
         return self.model.predict(x)
 
@@ -113,6 +118,22 @@ class TensorFlowV2Classifier:
             pb = None if probs_out is None else probs_out[s:s + bs]
             N.check(N.lib.lipasr_mlp_output_vjp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), N.ptr(vb), 1 if on_logits else 0,
                                                 xb.shape[0], N.ptr(pb), N.ptr(ob), N.stream_ptr()))
+        return out
+
+    def jacobian_device(self, xt, on_logits=True, probs_out=None):
+        """d out_c / dx for every class on a device tensor [B, features] -> [B, classes, features] (lipasr_mlp_jacobian: ONE forward
+        pass per batch, then one backward chain per class; row c is what ``output_vjp_device`` gives for the one-hot vector e_c).
+        probs_out: optional [B, classes] tensor that receives softmax(f(x))."""
+        m = self.model
+        xt = xt.contiguous()
+        c, n = self.nb_classes, xt.shape[1]
+        out = torch.empty(xt.shape[0], c, n, device=xt.device)
+        bs = m._max_batch
+        for s in range(0, xt.shape[0], bs):
+            xb, ob = xt[s:s + bs], out[s:s + bs]
+            pb = None if probs_out is None else probs_out[s:s + bs]
+            N.check(N.lib.lipasr_mlp_jacobian(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), 1 if on_logits else 0, xb.shape[0],
+                                              N.ptr(pb), N.ptr(ob), c * n, n, N.stream_ptr()))
         return out
 
     def class_gradient(self, x, label=None):
@@ -171,6 +192,11 @@ class WaveformClassifier:
         self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
         self._bs = min(model._max_batch, self.extractor.batch_max)
 
+    @property
+    def batch_limit(self):
+        """Rows one native call takes (the smaller of the model's and the extractor's)."""
+        return self._bs
+
     def _check(self, xt):
         if xt.dim() != 2 or xt.shape[1] != self.n:
             raise ValueError(f"waveforms must be [B, {self.n}] for domain {self.domain!r}, got {tuple(xt.shape)}")
@@ -226,13 +252,60 @@ class WaveformClassifier:
             f = self.features_device(xb, lb)
             gf = torch.empty_like(f)
             N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yb), xb.shape[0], N.ptr(gf), N.stream_ptr()))
-            if ex.short_window:
-                ex.vjp_short(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
-            elif lb is None:
-                ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
-            else:
-                ex.vjp_ragged(xb, gf, lb, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+            self._features_vjp(xb, gf, lb, ob)
         return out
+
+    def _features_vjp(self, xb, gf, lb, ob):
+        """The feature cotangent ``gf`` carried back to the rows ``xb`` whose features this extractor has just computed (its last
+        call on the current stream), into ``ob``: the backward pass that matches the extractor and ``lb``."""
+        ex = self.extractor
+        if ex.short_window:
+            ex.vjp_short(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+        elif lb is None:
+            ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+        else:
+            ex.vjp_ragged(xb, gf, lb, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
+
+    def output_vjp_device(self, xt, vt, on_logits=False, lengths=None):
+        """sum_c v[b, c] d out_c / dx on device tensors ([B, n], [B, classes]) -> [B, n]: TensorFlowV2Classifier.output_vjp_device
+        with the MFCC stage in front (extraction, lipasr_mlp_output_vjp, the backward pass of the extraction)."""
+        self._check(xt)
+        m = self.model
+        xt, vt = xt.contiguous(), vt.contiguous()
+        out = torch.empty_like(xt)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        for s in range(0, xt.shape[0], self._bs):
+            xb, vb, ob = xt[s:s + self._bs], vt[s:s + self._bs], out[s:s + self._bs]
+            lb = None if lt is None else lt[s:s + self._bs]
+            f = self.features_device(xb, lb)
+            gf = torch.empty_like(f)
+            N.check(N.lib.lipasr_mlp_output_vjp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(vb), 1 if on_logits else 0,
+                                                xb.shape[0], None, N.ptr(gf), N.stream_ptr()))
+            self._features_vjp(xb, gf, lb, ob)
+        return out
+
+    def jacobian_device(self, xt, on_logits=True, lengths=None):
+        """d out_c / dx for every class on a device tensor [B, n] -> a [B, classes, n] view of class-major storage.  Per batch: ONE
+        extraction, ONE lipasr_mlp_jacobian into [classes][B][features] (the MFCC backward takes contiguous [B, features]
+        cotangents), then one backward pass of the MFCC stage per class on the intermediates the extraction left: the backward
+        chain only reads them, so they serve every class.  Row c carries the bits of ``output_vjp_device`` with the one-hot e_c."""
+        self._check(xt)
+        m = self.model
+        xt = xt.contiguous()
+        b_all, c = xt.shape[0], self.nb_classes
+        lt = self.lengths_device(lengths, b_all)
+        out = torch.empty(c, b_all, self.n, device=xt.device)
+        for s in range(0, b_all, self._bs):
+            xb = xt[s:s + self._bs]
+            lb = None if lt is None else lt[s:s + self._bs]
+            f = self.features_device(xb, lb)
+            b, nf = f.shape
+            jf = torch.empty(c, b, nf, device=xt.device)
+            N.check(N.lib.lipasr_mlp_jacobian(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), 1 if on_logits else 0, b, None,
+                                              N.ptr(jf), nf, b * nf, N.stream_ptr()))
+            for k in range(c):
+                self._features_vjp(xb, jf[k], lb, out[k, s:s + b])
+        return out.permute(1, 0, 2)
 
     def loss_gradient(self, x, y, lengths=None):
         return self.loss_gradient_device(_to_dev(x), _to_dev(y), lengths=lengths).cpu().numpy()

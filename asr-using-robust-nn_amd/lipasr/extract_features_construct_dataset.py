@@ -7,6 +7,8 @@
 * ``mfcc(waveforms, sr_in)`` is the batched tensor entry the GPU pipeline uses.
 * ``get_norms`` / ``get_upper_lipschitz`` / ``get_lipschitz_constrained`` are the Lipschitz
   read-outs, computed by the K3 kernels instead of host SVDs.
+* ``jacobian_sigma`` / ``get_local_lipschitz`` (ours: the reference has no such read-out) measure how much of those
+  bounds a model uses at given inputs: the spectral norm of its Jacobian per row.
 """
 from __future__ import annotations
 
@@ -358,6 +360,67 @@ def get_lipschitz_constrained(model):
     cst = float(sig.item())
     correction = float(np.prod([float(f.item()) for f in factors])) if factors else 1.0
     return cst / correction
+
+
+# The read-outs above are global bounds taken from the weights.  The two below measure what the network does at given inputs:
+# sigma_b = ||J_b||_2, J_b[c][k] = d out_c(x_b) / d x_b[k] in inference mode ("Local Lipschitz read-out").
+JACOBIAN_CHUNK_BYTES = 256 << 20  # get_local_lipschitz keeps one chunk's Jacobian under this
+
+
+def jacobian_sigma(jac, return_vectors=False):
+    """Spectral norm of every [classes, n] slice of a float32 device tensor [B, classes, n] (lipasr_jacobian_sigma; any strides
+    along the first two dimensions, e.g. a permuted view of class-major storage; classes <= 32) -> sigma [B] on the device.
+    return_vectors=True: (sigma, u [B, classes], v [B, n]), the unit left and right singular vectors, the component of u of
+    largest magnitude positive; v is the input direction along which the output moves fastest.  A slice of zeros gives 0 and zero
+    vectors, a slice with a NaN or inf gives sigma = NaN for that sample alone."""
+    if not torch.is_tensor(jac) or not jac.is_cuda or jac.dtype != torch.float32 or jac.dim() != 3:
+        raise ValueError("jac must be a float32 device tensor [B, classes, n]")
+    b, c, n = jac.shape
+    if n > 1 and jac.stride(2) != 1:
+        raise ValueError("jac must be contiguous along its last dimension")
+    h = N.get_handle(jac.device.index)
+    sigma = torch.empty(b, device=jac.device)
+    u = torch.empty(b, c, device=jac.device) if return_vectors else None
+    v = torch.empty(b, n, device=jac.device) if return_vectors else None
+    N.check(N.lib.lipasr_jacobian_sigma(h.h, N.ptr(jac), b, c, n, jac.stride(0), jac.stride(1), N.ptr(sigma), N.ptr(u), N.ptr(v),
+                                        N.stream_ptr()))
+    return (sigma, u, v) if return_vectors else sigma
+
+
+def get_local_lipschitz(estimator, x, on_logits=True, lengths=None, return_vectors=False):
+    """The local Lipschitz constant of ``estimator`` at every row of ``x``: the largest singular value of the Jacobian of its logits
+    (on_logits=True) or of its softmax probabilities w.r.t. the row -> float64 NumPy [B]; return_vectors=True: (sigma, u [B,
+    classes], v [B, n]).  ``estimator``: anything with ``jacobian_device(xt, on_logits=)`` and ``nb_classes`` --
+    attacks.TensorFlowV2Classifier (rows of MFCC features) or attacks.WaveformClassifier (rows of audio; ``lengths`` as there, and
+    passed on only when given).  Rows go through in chunks of the estimator's ``batch_limit`` (where it has one), cut further so
+    that one chunk's Jacobian stays under JACOBIAN_CHUNK_BYTES."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    xt = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(device=dev, dtype=torch.float32).contiguous()
+    if xt.dim() != 2:
+        raise ValueError(f"x must be [B, n], got {tuple(xt.shape)}")
+    b, n = xt.shape
+    c = int(estimator.nb_classes)
+    chunk = max(1, JACOBIAN_CHUNK_BYTES // max(1, 4 * c * n))
+    limit = getattr(estimator, "batch_limit", None)
+    if limit:
+        chunk = min(chunk, int(limit))
+    lt = None
+    if lengths is not None:
+        lt = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths).astype(np.int32))
+        lt = lt.to(device=dev, dtype=torch.int32).contiguous()
+    sig, us, vs = [], [], []
+    for s in range(0, b, chunk):
+        kw = {} if lt is None else {"lengths": lt[s:s + chunk]}
+        jac = estimator.jacobian_device(xt[s:s + chunk], on_logits=on_logits, **kw)
+        r = jacobian_sigma(jac, return_vectors)
+        if return_vectors:
+            sig.append(r[0]); us.append(r[1]); vs.append(r[2])
+        else:
+            sig.append(r)
+    cat = lambda parts, shape: (torch.cat(parts).double().cpu().numpy() if parts else np.zeros(shape))
+    if return_vectors:
+        return cat(sig, (0,)), cat(us, (0, c)), cat(vs, (0, n))
+    return cat(sig, (0,))
 
 
 # ------------------------------------------------------------------------------------------------ dataset construction

@@ -11,8 +11,8 @@ import argparse
 import numpy as np
 
 from .Constraints import customConstraint, norm_constraint, norm_constraint_FISTA, simple_norm_constraint  # noqa: F401
-from .attacks import standardize_dataset
-from .extract_features_construct_dataset import get_lipschitz_constrained, get_norms, mfcc
+from .attacks import TensorFlowV2Classifier, standardize_dataset
+from .extract_features_construct_dataset import get_lipschitz_constrained, get_local_lipschitz, get_norms, mfcc
 from .keras import (BatchNormalization, Callback, CategoricalCrossentropy, Dataset, Dense, Dropout, EarlyStopping, Input, Model,
                     ModelCheckpoint, NonNeg, TensorBoard, load_model, to_categorical)
 from .synth import synth_clips_fast
@@ -27,7 +27,13 @@ def tensorboard_callback():
 
 
 class lip_stats_callback(Callback):
-    """train_constraints.py:52-60: per-layer spectral norms and the network Lipschitz constant each epoch."""
+    """train_constraints.py:52-60: per-layer spectral norms and the network Lipschitz constant each epoch.
+    probe= (ours; default None: the reference's output, unchanged): a small array of standardised rows [k, n_in]; the largest
+    local Lipschitz constant of the logits over those rows (get_local_lipschitz) is logged as well."""
+
+    def __init__(self, probe=None):
+        super().__init__()
+        self.probe = None if probe is None else np.asarray(probe, dtype=np.float32)
 
     def on_epoch_begin(self, epoch, logs=None):
         lip_cst = get_lipschitz_constrained(self.model)
@@ -36,6 +42,10 @@ class lip_stats_callback(Callback):
         for layer, norm in zip(dense, norms):
             print(f"The norm for layer {layer} is : {norm}")
         print(f"The Lipschitz constant on epoch {epoch} is {lip_cst}")
+        if self.probe is not None:
+            clf = TensorFlowV2Classifier(model=self.model, nb_classes=self.model._n_classes, input_shape=(self.probe.shape[1],))
+            local = get_local_lipschitz(clf, self.probe)
+            print(f"The largest local Lipschitz constant over {len(local)} probe rows on epoch {epoch} is {local.max()}")
 
 
 def get_model(n_in=880, n_classes=10, **kw):

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 570.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 580.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -22,6 +22,8 @@
  * 560: lipasr_mlp_adam_project_product_signal (the optimizer step that also raises a lipasr_flag_wait counter when it starts).
  * 570: the DolphinAttack chain (ultrasonic AM generator and microphone model): lipasr_dolphin_create / _destroy / _bandpass /
  * _generate / _record / _generate_recorded and the host-only lipasr_dolphin_table.
+ * 580: the local Lipschitz read-out: lipasr_mlp_jacobian (every class gradient from one forward pass) and lipasr_jacobian_sigma
+ * (spectral norm and singular vectors of a stack of class gradients, per sample).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -379,6 +381,34 @@ int lipasr_mlp_input_grad(lipasr_mlp_t m, const float* params, const float* bnst
 int lipasr_mlp_output_vjp(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x,
                           const float* v, int on_logits, int batch, float* probs_out, float* dx,
                           lipasr_stream_t stream);
+
+/* (ours: the reference has no such read-out)  The Jacobian of the model output in inference mode,
+ *     J_b[c][k] = d out_c(x_b) / d x_b[k],   jac[b * stride_b + c * stride_c + k]   (strides in floats),
+ * out = the logits (on_logits = 1) or the softmax probabilities (on_logits = 0), the two meanings lipasr_mlp_output_vjp has;
+ * C = classes, 1 <= C <= 32 (more: LIPASR_EINVAL), n = the input width.  Row c carries what lipasr_mlp_output_vjp gives for the
+ * one-hot vector e_c, from ONE forward pass instead of C: n_layers (1 + C) GEMM launches.  Both [batch][C][n] (stride_c >= n,
+ * stride_b >= C stride_c) and class-major [C][batch][n] (stride_b >= n, stride_c >= batch stride_b) are accepted; other strides
+ * are LIPASR_EINVAL.  probs_out (device [batch][classes], may be NULL) receives softmax(f(x)). */
+int lipasr_mlp_jacobian(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, int on_logits,
+                        int batch, float* probs_out /* may be NULL */, float* jac, long stride_b, long stride_c,
+                        lipasr_stream_t stream);
+
+/* (ours)  The local Lipschitz constant: per sample b the spectral norm of the classes x n matrix J_b laid out as above (any
+ * non-negative strides; 1 <= classes <= 32),
+ *     sigma[b] = ||J_b||_2 (the largest singular value),  u[b][.] its left singular vector [classes],  v[b][.] the right one [n]:
+ * v_b is the direction in input space along which the output moves fastest.  Conventions:
+ *   - ||u|| = ||v|| = 1; the sign is fixed so that the component of u of largest magnitude is positive (lowest index on a tie);
+ *   - J_b identically zero: sigma = 0, u = 0, v = 0; nothing is ever non-finite for finite input;
+ *   - a NaN or inf anywhere in J_b: sigma[b] = NaN for that sample only (its u, v are written, with zeros);
+ *   - when the two largest singular values coincide, u, v are some unit pair with J v = sigma u;
+ *   - a column of J_b whose entries are all zero has v exactly 0 (a ragged clip's padding stays out of the direction);
+ *   - J_b 2^k gives sigma 2^k and the same u, v (the kernel works on J_b scaled by a power of two, so that the ~1e-30
+ *     Jacobians of a saturated softmax do not underflow when squared).
+ * u and v may be NULL.  One launch, one workgroup per sample, no workspace, no atomics: two runs give the same bits.
+ * batch == 0 or n == 0 return LIPASR_OK (n == 0: sigma and u are zeroed). */
+int lipasr_jacobian_sigma(lipasr_handle_t h, const float* jac, int batch, int classes, int n, long stride_b, long stride_c,
+                          float* sigma /* [batch] */, float* u /* [batch][classes] or NULL */,
+                          float* v /* [batch][n] or NULL */, lipasr_stream_t stream);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
