@@ -42,6 +42,7 @@ int device_cus();
 
 struct MfccPlan;
 struct DolphinPlan;
+struct PsyPlan;
 
 }  // namespace lipasr
 
@@ -61,6 +62,7 @@ struct lipasr_ctx {
   lipasr::MfccPlan* mfcc = nullptr;               // the handle's default MFCC plan (lipasr_mfcc_plan); also in mfcc_plans
   std::vector<lipasr::MfccPlan*> mfcc_plans;      // every MFCC plan made on this handle and still alive
   std::vector<lipasr::DolphinPlan*> dolphin_plans;  // every DolphinAttack plan made on this handle and still alive
+  std::vector<lipasr::PsyPlan*> psy_plans;          // every psychoacoustic-masker plan made on this handle and still alive
 };
 
 namespace lipasr {

@@ -137,6 +137,14 @@ PROTOTYPES = {
     "lipasr_dolphin_record": (i32, [c_h, c_f, c_f, i32, f32, f32, c_f, c_s]),
     "lipasr_dolphin_generate_recorded": (i32, [c_h, c_f, c_f, i32, f32, f32, c_f, c_s]),
     "lipasr_dolphin_table": (i32, [i32, i32, C.POINTER(C.c_double), i32]),
+    "lipasr_psy_create": (i32, [c_h, i32, i32, i32, i32, C.POINTER(c_h)]),
+    "lipasr_psy_destroy": (i32, [c_h]),
+    "lipasr_psy_psd": (i32, [c_h, c_f, i32, i32, c_f, c_f, c_s]),
+    "lipasr_psy_threshold": (i32, [c_h, c_f, i32, i32, c_f, c_f, c_s]),
+    "lipasr_psy_prepare": (i32, [c_h, c_f, i32, i32, c_f, c_f, c_s]),
+    "lipasr_psy_loss_grad": (i32, [c_h, c_f, i32, i32, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_psy_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, f32, i32, f32, f32, c_s]),
+    "lipasr_psy_table": (i32, [i32, i32, C.POINTER(C.c_double), i32]),
     "lipasr_add_noise_f32": (i32, [c_h, c_f, i32, i32, i32, f32, f32, u64, c_s]),
     "lipasr_debug_set": (i32, [c_h, i32, i32]),
     "lipasr_debug_gemm_mode": (i32, [i32]),
@@ -155,7 +163,9 @@ PROTOTYPES = {
 SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create": 570, "lipasr_dolphin_destroy": 570,
          "lipasr_dolphin_bandpass": 570, "lipasr_dolphin_generate": 570, "lipasr_dolphin_record": 570,
          "lipasr_dolphin_generate_recorded": 570, "lipasr_dolphin_table": 570, "lipasr_mlp_jacobian": 580,
-         "lipasr_jacobian_sigma": 580}
+         "lipasr_jacobian_sigma": 580, "lipasr_psy_create": 590, "lipasr_psy_destroy": 590, "lipasr_psy_psd": 590,
+         "lipasr_psy_threshold": 590, "lipasr_psy_prepare": 590, "lipasr_psy_loss_grad": 590, "lipasr_psy_step": 590,
+         "lipasr_psy_table": 590}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -352,6 +362,16 @@ def dolphin_table(which: int, sr_in: int = 16000):
     n = check(lib.lipasr_dolphin_table(which, sr_in, None, 0))
     out = np.zeros(n, dtype=np.float64)
     check(lib.lipasr_dolphin_table(which, sr_in, out.ctypes.data_as(C.POINTER(C.c_double)), n))
+    return out
+
+
+def psy_table(which: int, sample_rate: int = 16000):
+    """Host-only fp64 tables of the psychoacoustic masker (0 f, 1 bark, 2 ATH in dB, 3 shift; [1025] each) as numpy float64."""
+    import numpy as np
+
+    n = check(lib.lipasr_psy_table(which, sample_rate, None, 0))
+    out = np.zeros(n, dtype=np.float64)
+    check(lib.lipasr_psy_table(which, sample_rate, out.ctypes.data_as(C.POINTER(C.c_double)), n))
     return out
 
 

@@ -291,6 +291,47 @@ def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_fil
     return grid, {k: np.asarray(v) for k, v in acc.items()}
 
 
+def imperceptible_report(models, train_data, val_data, test_data, test_labels, test_filenames, eps, learning_rate_1, learning_rate_2,
+                         domain="22k", standardize="before", limit=None, seed=0, **attack_kw):
+    """ImperceptibleASR (lipasr.attacks) over the audio of ``test_filenames``, targets from random_targets(test_labels): per model
+    the targeted success rate, the mean masking loss L_theta after stage 1 and after stage 2 -- how far the perturbation's spectrum
+    stands above what the clip itself masks -- and the mean perturbation SNR in dB.  Files are grouped by (rate, length); features
+    are standardised as white_box_sweep(over="audio") does.  ``eps`` and the learning rates are amplitudes and have no defaults.
+    Returns {model name: {"success", "loss_theta_1", "loss_theta_2", "snr_db", "rows": per-file arrays}}."""
+    if test_filenames is None:
+        raise ValueError("attacks over audio need test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+    if domain not in ("22k", "input"):
+        raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+    test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+    labels = np.asarray(test_labels[:limit] if limit else test_labels)
+    n_classes = labels.shape[1]
+    targets = A.random_targets(labels, n_classes, rng=np.random.RandomState(seed)).astype(np.float32)
+    _, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
+    groups = A._files_to_batches(test_filenames)
+    out = {}
+    for name, model in models.items():
+        rows = {k: np.zeros(len(test_filenames)) for k in ("success", "loss_theta_1", "loss_theta_2", "snr_db")}
+        for (sr, n), items in groups.items():
+            clf, x, _ = _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, None)
+            idx = [i for i, _ in items]
+            atk = A.ImperceptibleASR(clf, eps=eps, learning_rate_1=learning_rate_1, learning_rate_2=learning_rate_2, **attack_kw)
+            adv = atk.generate_device(x, A._to_dev(targets[idx]))
+            atk.masker.close()
+            hit = clf.predict_device(adv, logits=True).argmax(dim=1).cpu().numpy() == targets[idx].argmax(axis=1)
+            noise = (adv - x).double().pow(2).sum(dim=1)
+            snr = 10.0 * torch.log10(x.double().pow(2).sum(dim=1) / noise)
+            rows["success"][idx], rows["snr_db"][idx] = hit, snr.cpu().numpy()
+            rows["loss_theta_1"][idx], rows["loss_theta_2"][idx] = atk.last_loss_theta_1, atk.last_loss_theta
+        r = {k: float(np.mean(v[np.isfinite(v)])) if np.isfinite(v).any() else float("nan") for k, v in rows.items()}
+        r["rows"] = rows
+        out[name] = r
+        tag = "" if name == "constrained" else " " + name
+        print(f"Targeted success rate of the imperceptible attack{tag}: {r['success'] * 100}% over {len(test_filenames)} files")
+        print(f"Mean masking loss L_theta{tag}: {r['loss_theta_1']} after stage 1, {r['loss_theta_2']} after stage 2")
+        print(f"Mean perturbation SNR{tag}: {r['snr_db']} dB")
+    return out
+
+
 def lipschitz_report(models, train_data, val_data, test_data, over="mfcc", standardize="before", test_filenames=None, domain="22k",
                      limit=None):
     """Per model: the reference's global read-outs -- get_upper_lipschitz(get_norms(model)) and get_lipschitz_constrained(model) --
@@ -345,10 +386,15 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma|imperceptible")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
-    ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points")
+    ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
     ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword")
+    ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
+    ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
+    ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
+    ap.add_argument("--max-iter-1", type=int, default=1000)
+    ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
     import os
 
@@ -370,6 +416,16 @@ def main(argv=None):
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
         labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
         return dolphin_sweep(models, train_data, val_data, test_data, labels, names, standardize=args.standardize, points=args.points)
+    if args.kind == "imperceptible":
+        if args.over != "audio":
+            raise ValueError("--kind imperceptible perturbs audio: give --over audio")
+        if args.eps is None or args.learning_rate_1 is None or args.learning_rate_2 is None:
+            raise ValueError("--kind imperceptible needs --eps, --learning-rate-1 and --learning-rate-2 (amplitudes; there are no defaults)")
+        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
+        labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
+        return imperceptible_report(models, train_data, val_data, test_data, labels, names, args.eps, args.learning_rate_1,
+                                    args.learning_rate_2, standardize=args.standardize, limit=args.points, max_iter_1=args.max_iter_1,
+                                    max_iter_2=args.max_iter_2)
     kw = {}
     if args.over == "audio":
         kw.update(over="audio", test_filenames=np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist())

@@ -835,6 +835,154 @@ class ProjectedGradientDescent(_SignAttack):
                                                  self.eps_step, self.eps, N.stream_ptr()))
 
 
+class ImperceptibleASR:
+    """ART ``ImperceptibleASR`` (Qin et al. 2019) over a WaveformClassifier, in either domain: a targeted attack in two stages.
+    Stage 1 finds an adversarial perturbation inside an L-inf ball that shrinks while the attack succeeds (sign steps of
+    ``learning_rate_1`` down CE(f(x0 + delta), y)); stage 2 pushes the perturbation's power spectrum under the clip's own
+    masking threshold (plain gradient steps of ``learning_rate_2`` along g_net + alpha_u g_theta, L_theta and g_theta from
+    ``PsychoacousticMasker.loss_gradient_device``), with alpha_u raised while the row stays adversarial and lowered while it is not.
+    ``eps`` and the learning rates are amplitudes of this estimator's waveform and have no defaults (ART's are 16-bit sample
+    units tuned for another model).  g_net is the gradient of each row's OWN cross-entropy (lipasr_mlp_input_grad's batch mean
+    undone), so a row's path does not depend on the batch it runs in.
+
+    A row's stage-1 result is x0 + delta at its last successful check (every ``num_iter_decrease_eps`` iterations), or x0 + its
+    last delta if it never succeeded; |delta_u| <= ``last_eps[u]``, the ball that result was found in, and stage 2 stays inside it.
+    Stage 2 keeps, per row, the adversarial iterate with the lowest L_theta seen at its checks (multiples of
+    ``num_iter_increase_alpha`` / ``num_iter_decrease_alpha``), never one with a higher L_theta than the stage-1 result; it stops
+    once every row has L_theta < ``loss_theta_min`` -- looked at only at multiples of ``num_iter_increase_alpha``, the one point
+    where the loop returns to the host.  Afterwards: ``last_success`` (bool [B]), ``last_loss_theta_1`` / ``last_loss_theta``
+    (L_theta after stage 1 / of the returned rows), ``last_eps``, ``last_stage1`` and ``last_iterate`` (device tensors)."""
+
+    ALPHA_FLOOR = 0.0005
+
+    def __init__(self, estimator, masker=None, *, eps, learning_rate_1, learning_rate_2, max_iter_1=1000, max_iter_2=4000,
+                 loss_theta_min=0.05, decrease_factor_eps=0.8, num_iter_decrease_eps=10, alpha=0.05, increase_factor_alpha=1.2,
+                 num_iter_increase_alpha=20, decrease_factor_alpha=0.8, num_iter_decrease_alpha=50, batch_size=32):
+        from .psychoacoustic import PsychoacousticMasker
+
+        if not isinstance(estimator, WaveformClassifier):
+            raise TypeError("ImperceptibleASR runs over audio: the estimator must be a WaveformClassifier")
+        if estimator.extractor.short_window:
+            raise ValueError("ImperceptibleASR: the masker is built for the 2048 / 512 framing, not a short-window extractor")
+        sr = 22050 if estimator.domain == "22k" else int(estimator.extractor.sr_in)
+        self.estimator = estimator
+        self.masker = masker if masker is not None else PsychoacousticMasker(sample_rate=sr, device=estimator.extractor.device)
+        if not isinstance(self.masker, PsychoacousticMasker):
+            raise TypeError("masker must be a lipasr.psychoacoustic.PsychoacousticMasker")
+        for name, v in (("eps", eps), ("learning_rate_1", learning_rate_1), ("learning_rate_2", learning_rate_2)):
+            if not (float(v) > 0):
+                raise ValueError(f"{name}={v!r} must be positive")
+        for name, v in (("max_iter_1", max_iter_1), ("max_iter_2", max_iter_2)):
+            if int(v) < 0:
+                raise ValueError(f"{name}={v!r} must not be negative")
+        for name, v in (("num_iter_decrease_eps", num_iter_decrease_eps), ("num_iter_increase_alpha", num_iter_increase_alpha),
+                        ("num_iter_decrease_alpha", num_iter_decrease_alpha), ("batch_size", batch_size)):
+            if int(v) < 1:
+                raise ValueError(f"{name}={v!r} must be at least 1")
+        self.eps, self.learning_rate_1, self.learning_rate_2 = float(eps), float(learning_rate_1), float(learning_rate_2)
+        self.max_iter_1, self.max_iter_2, self.loss_theta_min = int(max_iter_1), int(max_iter_2), float(loss_theta_min)
+        self.decrease_factor_eps, self.num_iter_decrease_eps = float(decrease_factor_eps), int(num_iter_decrease_eps)
+        self.alpha, self.increase_factor_alpha, self.num_iter_increase_alpha = float(alpha), float(increase_factor_alpha), int(num_iter_increase_alpha)
+        self.decrease_factor_alpha, self.num_iter_decrease_alpha = float(decrease_factor_alpha), int(num_iter_decrease_alpha)
+        self.batch_size = int(batch_size)
+        self.targeted = True
+        self.last_success = self.last_loss_theta = self.last_loss_theta_1 = self.last_eps = self.last_stage1 = self.last_iterate = None
+
+    def _hit(self, xa, target):
+        return self.estimator.predict_device(xa, logits=True).argmax(dim=1) == target
+
+    def _stage1(self, x0, yb, target):
+        """-> (result, success, eps of the ball the result lies in)."""
+        est, mk = self.estimator, self.masker
+        b = x0.shape[0]
+        delta, xa, g = torch.zeros_like(x0), x0.clone(), torch.empty_like(x0)
+        eps_u = torch.full((b,), self.eps, device=x0.device)
+        res, eps_res = x0.clone(), eps_u.clone()
+        succ = torch.zeros(b, dtype=torch.bool, device=x0.device)
+        for it in range(1, self.max_iter_1 + 1):
+            est.loss_gradient_device(xa, yb, out=g)
+            mk.step_device(delta, xa, x0, g, None, None, eps_u, self.learning_rate_1, True, est.clip_values)
+            if it % self.num_iter_decrease_eps == 0:
+                ok = self._hit(xa, target)
+                res = torch.where(ok[:, None], xa, res)
+                eps_res = torch.where(ok, eps_u, eps_res)
+                succ |= ok
+                eps_u = torch.where(ok, self.decrease_factor_eps * torch.minimum(eps_u, delta.abs().amax(dim=1)), eps_u)
+        never = ~succ
+        res = torch.where(never[:, None], xa, res)
+        eps_res = torch.where(never, eps_u, eps_res)
+        return res, succ, eps_res
+
+    def _stage2(self, x0, yb, target, x1, succ, eps_u):
+        """-> (result, success, L_theta after stage 1, L_theta of the result, the last iterate)."""
+        est, mk = self.estimator, self.masker
+        b = x0.shape[0]
+        theta, psd_max = mk.prepare_device(x0)
+        xa = x1.clone()
+        delta = xa - x0
+        g, gt = torch.empty_like(x0), torch.empty_like(x0)
+        loss1, _ = mk.loss_gradient_device(delta, theta, psd_max, need_grad=False)
+        best, best_loss, succ = x1.clone(), loss1.clone(), succ.clone()
+        alpha = torch.full((b,), self.alpha, device=x0.device)
+        # lipasr_mlp_input_grad differentiates the batch MEAN: lr (b g + alpha g_theta) = (lr b) (g + (alpha / b) g_theta)
+        alpha_b, lr = alpha / b, self.learning_rate_2 * b
+        inc, dec = self.num_iter_increase_alpha, self.num_iter_decrease_alpha
+        for it in range(1, self.max_iter_2 + 1):
+            est.loss_gradient_device(xa, yb, out=g)
+            mk.loss_gradient_device(delta, theta, psd_max, out=gt)
+            mk.step_device(delta, xa, x0, g, gt, alpha_b, eps_u, lr, False, est.clip_values)
+            if it % inc and it % dec:
+                continue
+            ok = self._hit(xa, target)
+            cur, _ = mk.loss_gradient_device(delta, theta, psd_max, need_grad=False)
+            better = ok & (cur < best_loss)
+            best = torch.where(better[:, None], xa, best)
+            best_loss = torch.where(better, cur, best_loss)
+            succ |= better
+            if it % inc == 0:
+                alpha = torch.where(ok, alpha * self.increase_factor_alpha, alpha)
+            if it % dec == 0:
+                alpha = torch.where(ok, alpha, (alpha * self.decrease_factor_alpha).clamp_min(self.ALPHA_FLOOR))
+            alpha_b = alpha / b
+            if it % inc == 0 and bool((best_loss < self.loss_theta_min).all()):
+                break
+        return best, succ, loss1, best_loss, xa
+
+    def generate_device(self, xt, yt=None, lengths=None):
+        """xt: float32 device tensor [B, n] of clips of ONE length, yt: one-hot targets [B, classes]; returns a NEW tensor."""
+        if lengths is not None:
+            raise ValueError("lengths=: ImperceptibleASR takes clips of one length (the masker has no per-clip lengths)")
+        if yt is None:
+            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
+        est = self.estimator
+        est._check(xt)
+        if tuple(yt.shape) != (xt.shape[0], est.nb_classes):
+            raise ValueError(f"y must be one-hot [{xt.shape[0]}, {est.nb_classes}]")
+        bs = min(self.batch_size, est._bs)
+        out, keep = torch.empty_like(xt), {k: [] for k in ("succ", "l1", "l2", "eps", "x1", "it")}
+        for s in range(0, xt.shape[0], bs):
+            x0 = xt[s:s + bs].contiguous()
+            yb = yt[s:s + bs].to(torch.float32).contiguous()
+            target = yb.argmax(dim=1)
+            x1, succ, eps_u = self._stage1(x0, yb, target)
+            best, succ, l1, l2, last = self._stage2(x0, yb, target, x1, succ, eps_u)
+            out[s:s + bs] = best
+            for k, v in zip(("succ", "l1", "l2", "eps", "x1", "it"), (succ, l1, l2, eps_u, x1, last)):
+                keep[k].append(v)
+        cat = lambda k: torch.cat(keep[k])
+        self.last_success, self.last_loss_theta_1, self.last_loss_theta = cat("succ").cpu().numpy(), cat("l1").cpu().numpy(), cat("l2").cpu().numpy()
+        self.last_eps, self.last_stage1, self.last_iterate = cat("eps").cpu().numpy(), cat("x1"), cat("it")
+        return out
+
+    def generate(self, x, y=None, lengths=None):
+        if lengths is not None:
+            raise ValueError("lengths=: ImperceptibleASR takes clips of one length (the masker has no per-clip lengths)")
+        if y is None:
+            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
+        adv = self.generate_device(_to_dev(x), _to_dev(y))
+        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+
+
 def sign_step(x_adv, x0, g, alpha, eps):
     """Stand-alone K4 on device tensors, in place on x_adv."""
     h = N.get_handle(x_adv.device.index)

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 580.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 590.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -24,6 +24,8 @@
  * _generate / _record / _generate_recorded and the host-only lipasr_dolphin_table.
  * 580: the local Lipschitz read-out: lipasr_mlp_jacobian (every class gradient from one forward pass) and lipasr_jacobian_sigma
  * (spectral norm and singular vectors of a stack of class gradients, per sample).
+ * 590: the psychoacoustic masking threshold and the imperceptible attack's loss: lipasr_psy_create / _destroy / _psd / _threshold /
+ * _prepare / _loss_grad / _step and the host-only lipasr_psy_table.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -69,6 +71,7 @@ typedef struct lipasr_ctx* lipasr_handle_t;
 typedef struct lipasr_mlp* lipasr_mlp_t;
 typedef struct lipasr_mfcc* lipasr_mfcc_t;
 typedef struct lipasr_dolphin* lipasr_dolphin_t;
+typedef struct lipasr_psy* lipasr_psy_t;
 typedef void* lipasr_stream_t; /* hipStream_t */
 
 /* ------------------------------------------------------------------ core */
@@ -646,6 +649,54 @@ int lipasr_dolphin_generate_recorded(lipasr_dolphin_t p, const float* wav, const
  * 2 h_dn[241], 3 each section's state-transition matrix to the power 64 [10][4] (the carry of the chunked scan).  Returns the
  * element count (negative = error); out may be NULL to query the size. */
 int lipasr_dolphin_table(int which, int sr_in, double* out, int cap);
+
+/* ------------------------------------------------------------------ psychoacoustic masking threshold, imperceptible attack
+ * What ART's PsychoacousticMasker and the second stage of its ImperceptibleASR compute ("Speaker recognition/attacks.py":17
+ * imports both and uses neither on a waveform).  Window N = 2048, hop 512, periodic Hann w, no padding: frame t is
+ * x[512 t .. 512 t + 2048), T = 1 + (n - 2048) / 512 frames, K = 1025 bins, X[k,t] the DFT of w . frame t.
+ * Tables (host, fp64; sr = the plan's sample_rate):
+ *   f_k = k sr / 2048,  bark_k = 13 atan(0.00076 f) + 3.5 atan((f / 7500)^2),  shift_k = -6.025 - 0.275 bark_k,
+ *   ATH_k = 3.64 q^-0.8 - 6.5 exp(-0.6 (q - 3.3)^2) + 0.001 q^4 - 12, q = f / 1000, for 20 <= f <= 20000, -inf outside.
+ * PSD:  p[k,t] = max(-200, 20 log10 |sqrt(8/3) X[k,t] / N|),  psd_max = max over the clip,  psd = 96 - psd_max + p.
+ * Maskers of a frame v = psd[:, t]:
+ *   1. candidates: strict local maxima v[k] > v[k-1], v[k] > v[k+1], 1 <= k <= 1023 (at most 512)
+ *   2. level = 10 log10(10^(v[k-1]/10) + 10^(v[k]/10) + 10^(v[k+1]/10));  3. kept when level > ATH_k
+ *   4. greedy merge, ascending, i_prev = 0: for i = 1 ...: if bark(i) - bark(i_prev) < 0.5 the smaller of the two is dropped --
+ *      level[i_prev] < level[i]: i_prev is dropped and i_prev <- i_prev + 1 (ART's step, kept literally), otherwise (ties too) i
+ *      is dropped -- else i_prev <- i.  bark(i) is the Bark value of masker i's bin; with flag bit 0 it is the Bark table at the
+ *      LIST POSITION i, ART's code as written.  The comparison runs on the fp64 table.
+ *   5. theta[k,t] = 10^(ATH_k/10) + sum_j 10^((level_j + shift_{bin_j} + SF_j(k)) / 10), LINEAR (ART's dB threshold is
+ *      10 log10 theta, possibly -inf), 10^(-inf) = 0, dz = bark_k - bark_{bin_j}, SF = 27 dz for dz <= 0 and
+ *      (-27 + 0.37 max(level_j - 40, 0)) dz above.
+ * Loss of a perturbation delta (same framing):  c = 10^9.6 / 10^(psd_max/10) (8/3) / N^2,  P = c |STFT_delta|^2,
+ *   L = (1 / (K T)) sum_{k,t} max(P - theta, 0) per clip, and its gradient
+ *   g[n] = sum_t shift_{512 t}(w . g_t),  g_t[n] = sum_{k=0}^{1024} 2 G_k Re(X_k e^{2 pi i k n / N}),  G = c [P > theta] / (K T);
+ *   samples past the last frame get exactly 0, and a frame with no bin over theta contributes exactly 0.
+ * Step:  delta <- clamp(delta - lr s(g_net + alpha_u g_theta), +-eps_u), s = sign (use_sign) or the identity; then
+ *   x_adv <- clamp(x0 + delta, clip_lo, clip_hi) and delta <- x_adv - x0.  alpha, eps: device [batch]; g_theta (with alpha) may be NULL.
+ * Arrays: x, delta, g_delta, x_adv, x0, g_net, g_theta [batch][n] float32 (every row of one call has the same n);
+ * psd, theta [batch][T][1025], bins contiguous; psd_max, loss [batch]; n_maskers int [batch][T] or NULL.  lipasr_psy_threshold
+ * takes ANY PSD as input; lipasr_psy_prepare is _psd followed by _threshold with the PSD kept in the plan's workspace.
+ * lipasr_psy_loss_grad with g_delta = NULL computes the loss alone (the same bits).  Everything runs in fp32 (the Bark differences
+ * and c are formed in fp64 and rounded once); every sum runs in a fixed order, without atomics: two runs give the same bits.  No launch
+ * function synchronises or allocates.  Errors: n < 2048 or > n_max, batch > batch_max, n_frames > the plan's, unknown flag bits, a
+ * null array or plan: LIPASR_EINVAL; a plan whose [batch_max][T][1025] tensors pass 2^31 elements: LIPASR_EUNSUPPORTED.  Plans still
+ * alive are freed by lipasr_destroy. */
+int lipasr_psy_create(lipasr_handle_t h, int sample_rate, int n_max, int batch_max, int flags /* bit 0: bark by position */,
+                      lipasr_psy_t* out);
+int lipasr_psy_destroy(lipasr_psy_t p);
+int lipasr_psy_psd(lipasr_psy_t p, const float* x, int n, int batch, float* psd, float* psd_max, lipasr_stream_t stream);
+int lipasr_psy_threshold(lipasr_psy_t p, const float* psd, int n_frames, int batch, float* theta, int* n_maskers_or_null,
+                         lipasr_stream_t stream);
+int lipasr_psy_prepare(lipasr_psy_t p, const float* x, int n, int batch, float* theta, float* psd_max, lipasr_stream_t stream);
+int lipasr_psy_loss_grad(lipasr_psy_t p, const float* delta, int n, int batch, const float* theta, const float* psd_max, float* loss,
+                         float* g_delta_or_null, lipasr_stream_t stream);
+int lipasr_psy_step(lipasr_psy_t p, float* delta, float* x_adv, const float* x0, const float* g_net, const float* g_theta_or_null,
+                    const float* alpha_or_null, const float* eps, int n, int batch, float lr, int use_sign, float clip_lo, float clip_hi,
+                    lipasr_stream_t stream);
+/* Host-only (no GPU needed), fp64 [1025]: which 0 f, 1 bark, 2 ATH in dB (-inf outside its domain), 3 shift.  Returns the element
+ * count (negative = error); out may be NULL to query the size. */
+int lipasr_psy_table(int which, int sample_rate, double* out, int cap);
 
 /* A12 audio-domain noise on device, Philox RNG (attacks.py:73-86, 145-183, 222-245), in place on
  * y [batch][n]:  mode 0: y + N(0, p0)               (add_white_noise, sigma = p0)
