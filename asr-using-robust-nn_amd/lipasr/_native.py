@@ -103,6 +103,7 @@ PROTOTYPES = {
     "lipasr_mlp_output_vjp": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, c_f, c_f, c_s]),
     "lipasr_mlp_jacobian": (i32, [c_h, c_f, c_f, c_f, i32, i32, c_f, c_f, C.c_long, C.c_long, c_s]),
     "lipasr_jacobian_sigma": (i32, [c_h, c_f, i32, i32, i32, C.c_long, C.c_long, c_f, c_f, c_f, c_s]),
+    "lipasr_deepfool_step": (i32, [c_h, c_f, C.c_long, C.c_long, c_f, c_f, c_f, i32, i32, i32, f32, f32, f32, f32, c_f, c_f, c_f, c_f, c_s]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -165,7 +166,7 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_dolphin_generate_recorded": 570, "lipasr_dolphin_table": 570, "lipasr_mlp_jacobian": 580,
          "lipasr_jacobian_sigma": 580, "lipasr_psy_create": 590, "lipasr_psy_destroy": 590, "lipasr_psy_psd": 590,
          "lipasr_psy_threshold": 590, "lipasr_psy_prepare": 590, "lipasr_psy_loss_grad": 590, "lipasr_psy_step": 590,
-         "lipasr_psy_table": 590}
+         "lipasr_psy_table": 590, "lipasr_deepfool_step": 600}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 

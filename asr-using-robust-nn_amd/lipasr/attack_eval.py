@@ -12,6 +12,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: ART's norm keyword of FGM / PGD)           --norm inf | 1 | 2 (default inf, the reference's)
     (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
     (no prompt: the Lipschitz read-outs, global and local) attack="lipschitz": lipschitz_report over="mfcc" | "audio"
+    (no prompt: certified radius next to DeepFool's)       attack="radius": radius_report over="mfcc" | "audio", --norm 2 | inf
 """
 from __future__ import annotations
 
@@ -21,7 +22,8 @@ import numpy as np
 import torch
 
 from . import attacks as A
-from .extract_features_construct_dataset import get_lipschitz_constrained, get_local_lipschitz, get_norms, get_upper_lipschitz
+from .extract_features_construct_dataset import (get_lipschitz_bound, get_lipschitz_constrained, get_local_lipschitz, get_norms,
+                                                  get_robustness_radius, get_upper_lipschitz)
 from .keras import CategoricalCrossentropy, load_model, to_categorical
 
 # the grids the reference hard-codes
@@ -378,6 +380,60 @@ def lipschitz_report(models, train_data, val_data, test_data, over="mfcc", stand
     return out
 
 
+def radius_report(models, train_data, val_data, test_data, over="mfcc", standardize="before", test_filenames=None, domain="22k",
+                  norm=2, limit=None, **deepfool_kw):
+    """Per model: how far the test rows are from the decision boundary (get_robustness_radius) -- the quartiles of the certified
+    radius (rows of MFCC features and norm 2 only), of the distance to the linearised boundary and of the distance DeepFool found,
+    and the share of rows it flipped.  ``over``, ``standardize``, ``test_filenames``, ``domain`` and ``limit`` as in
+    lipschitz_report; ``norm``: 2 or np.inf; deepfool_kw go to attacks.DeepFool.
+    Returns {model name: {"bound": get_lipschitz_bound(model), "margin", "certified" (or None), "linear", "found", "flipped": the
+    per-row arrays, "quartiles": {name: (q25, q50, q75)}, "flipped_share"}}."""
+    if over == "audio":
+        if test_filenames is None:
+            raise ValueError("the read-out over audio needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+        if domain not in ("22k", "input"):
+            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
+    elif over == "mfcc":
+        if standardize == "before":
+            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
+        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
+    else:
+        raise ValueError("over must be 'audio' or 'mfcc'")
+    keys = ("margin", "certified", "linear", "found", "flipped")
+    out = {}
+    for name, model in models.items():
+        if over == "mfcc":
+            clf = A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(x.shape[1],),
+                                           loss_object=CategoricalCrossentropy())
+            r = get_robustness_radius(clf, x, norm=norm, **deepfool_kw)
+        else:
+            r = {k: np.zeros(len(test_filenames), dtype=bool if k == "flipped" else np.float64) for k in keys}
+            r["certified"] = None
+            for sr, n, items, lens in work:
+                clf, rows, lt = _audio_rows(model, model._n_classes, sc, domain, bmax, sr, n, items, lens)
+                part = get_robustness_radius(clf, rows, norm=norm, lengths=lt, **deepfool_kw)
+                for k in ("margin", "linear", "found", "flipped"):
+                    r[k][[i for i, _ in items]] = part[k]
+        r["bound"] = float(get_lipschitz_bound(model))
+        r["quartiles"] = {k: tuple(float(q) for q in np.percentile(r[k], (25, 50, 75))) for k in ("certified", "linear", "found")
+                          if r[k] is not None and len(r[k])}
+        r["flipped_share"] = float(np.mean(r["flipped"])) if len(r["flipped"]) else float("nan")
+        out[name] = r
+        tag = "" if name == "constrained" else " " + name
+        what = f"{len(r['found'])} test {'rows' if over == 'mfcc' else 'files'}"
+        print(f"Lipschitz bound of the logits{tag}: {r['bound']}")
+        for k, label in (("certified", "Certified radius"), ("linear", "Distance to the linearised boundary"), ("found", "Distance DeepFool found")):
+            if k in r["quartiles"]:
+                q = r["quartiles"][k]
+                print(f"{label} over {what}{tag}: quartiles {q[0]} {q[1]} {q[2]}")
+            else:
+                print(f"{label} over {what}{tag}: not given")
+        print(f"Share of {what} DeepFool moved to another class{tag}: {r['flipped_share'] * 100}%")
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="attacks.py's evaluation menu as flags")
     ap.add_argument("--path", default="processed_google_dataset/")
@@ -385,11 +441,11 @@ def main(argv=None):
     ap.add_argument("--constrained", default="bin/models_constrained/model_constrained_Rho01_dropout01.h5")
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
-    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz"], default="black")
+    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius"], default="black")
     ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma|imperceptible")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
-    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword")
+    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; radius: 2 or inf")
     ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
     ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
     ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
@@ -397,6 +453,9 @@ def main(argv=None):
     ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
     import os
+
+    if args.attack == "radius" and args.norm == "1":
+        raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
 
     train_data, _, val_data, _, test_data, test_label = A.load_npy_dataset(args.path)
     n_classes = int(test_label.max()) + 1
@@ -412,6 +471,10 @@ def main(argv=None):
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
         return lipschitz_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
                                 test_filenames=names)
+    if args.attack == "radius":
+        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
+        return radius_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
+                             test_filenames=names, norm=np.inf if args.norm == "inf" else 2, limit=args.points)
     if args.attack == "dolphin":
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
         labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)

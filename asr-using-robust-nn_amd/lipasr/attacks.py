@@ -835,6 +835,152 @@ class ProjectedGradientDescent(_SignAttack):
                                                  self.eps_step, self.eps, N.stream_ptr()))
 
 
+def deepfool_step(jac, out, label, x, norm=2, overshoot=0.02, clip_values=None, allowed=None):
+    """One DeepFool iteration in place on ``x`` (lipasr_deepfool_step; include/lipasr.h fixes the conventions).  Device tensors:
+    jac float32 [B, classes, n] (any strides along the first two dimensions), out float32 [B, classes], label int32 [B],
+    x float32 [B, n] contiguous, allowed int32 [B] (bit k: class k may be the target) or None.
+    -> (dist float32 [B], target int32 [B], state int32 [B]: 1 stepped, 0 already flipped, -1 not finite)."""
+    if not (torch.is_tensor(jac) and jac.is_cuda and jac.dtype == torch.float32 and jac.dim() == 3):
+        raise ValueError("jac must be a float32 device tensor [B, classes, n]")
+    b, c, n = jac.shape
+    if n > 1 and jac.stride(2) != 1:
+        raise ValueError("jac must be contiguous along its last dimension")
+    if tuple(x.shape) != (b, n) or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"x must be a contiguous float32 tensor [{b}, {n}]")
+    if tuple(out.shape) != (b, c) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor [{b}, {c}]")
+    if tuple(label.shape) != (b,) or label.dtype != torch.int32 or (allowed is not None and (tuple(allowed.shape) != (b,) or allowed.dtype != torch.int32)):
+        raise ValueError(f"label (and allowed) must be int32 tensors [{b}]")
+    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    h = N.get_handle(x.device.index)
+    dist = torch.empty(b, device=x.device)
+    target = torch.empty(b, dtype=torch.int32, device=x.device)
+    state = torch.empty(b, dtype=torch.int32, device=x.device)
+    N.check(N.lib.lipasr_deepfool_step(h.h, N.ptr(jac), jac.stride(0), jac.stride(1), N.ptr(out), N.ptr(label), N.ptr(allowed), b, c, n,
+                                       _norm_value(norm), float(overshoot), lo, hi, N.ptr(x), N.ptr(dist), N.ptr(target), N.ptr(state),
+                                       N.stream_ptr()))
+    return dist, target, state
+
+
+class DeepFool:
+    """ART DeepFool(classifier=, max_iter=, epsilon=, nb_grads=, batch_size=, verbose=) (Moosavi-Dezfooli et al. 2016): the
+    minimal-perturbation attack.  The positional and ART keywords mean what they mean in ART, restated from memory of its published
+    implementation (ART is absent: parity unpinned): labels are the estimator's own argmax at ``x``; every iteration moves each row
+    that is still in its class onto the nearest boundary of the classifier linearised at the row; the loop ends when every row has
+    left its class or after ``max_iter`` iterations; ``epsilon`` is the final overshoot, x_adv = x + (1 + epsilon) (x_iter - x),
+    then clipping.  One iteration is: the estimator's outputs, its Jacobian (``jacobian_device``: every class gradient from one
+    forward pass) and ONE lipasr_deepfool_step for the batch; the host looks at the state vector every CHECK_EVERY iterations
+    only, so nothing synchronises per iteration (a row that has left its class is left alone by the kernel).
+
+    Ours, after the ``*``:
+    ``overshoot``: the paper's per-step overshoot, x <- x + (1 + overshoot) r.  ART has none (``overshoot=0`` is its iteration):
+    its step lands exactly ON the boundary of a piecewise-linear network, where the argmax is decided by rounding, and such rows
+    then take zero-length steps until max_iter.  With 0.02 they leave.
+    ``norm``: 2 (ART's) or np.inf (the paper's l_p form with p = inf: the step is |f| / ||w||_1 sign(w)).
+    ``on_logits``: True differentiates the logits, for which the linearisation is exact inside a ReLU piece; False the softmax
+    probabilities, what ART does with a Keras model that ends in softmax (and warns about).
+    ``nb_grads`` < nb_classes: the candidates of a ROW are its own nb_grads largest outputs at x.  ART takes the union of those
+    classes over the whole array, so a row's result there depends on its neighbours; here it does not.
+
+    Estimators: TensorFlowV2Classifier (rows of features, no clipping) and WaveformClassifier in either domain, with ``lengths=``
+    and over a short-window extractor; over audio the kernel clamps to the classifier's ``clip_values``, and with ``lengths=`` the
+    rest of each row comes back as it was.  Rows go through in chunks bounded by the estimator's ``batch_limit`` and by
+    JACOBIAN_CHUNK_BYTES for one chunk's Jacobian; ``batch_size`` is accepted and ignored above that.
+    After a call ``self.last`` holds NumPy arrays [B]: ``iterations`` (steps taken), ``flipped`` (from a final prediction on
+    x_adv), ``target`` (the class of the last step's boundary, -1 without a step) and ``first_dist`` (rho_l of the first step: the
+    distance to the linearised boundary at x)."""
+
+    CHECK_EVERY = 4
+
+    def __init__(self, classifier, max_iter=100, epsilon=1e-6, nb_grads=10, batch_size=1, verbose=True, *, norm=2, overshoot=0.02,
+                 on_logits=True):
+        if not isinstance(classifier, (TensorFlowV2Classifier, WaveformClassifier)):
+            raise TypeError("classifier must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        if int(max_iter) < 0 or int(nb_grads) < 1 or int(batch_size) < 1:
+            raise ValueError("max_iter >= 0, nb_grads >= 1 and batch_size >= 1 are required")
+        if float(epsilon) < 0 or not (0 <= float(overshoot) < math.inf):
+            raise ValueError("epsilon and overshoot must not be negative")
+        self.norm = _norm_value(norm)
+        if self.norm == 1.0:
+            raise ValueError("norm=1: DeepFool runs in norm 2 or np.inf")
+        if classifier.nb_classes > 32:
+            raise ValueError(f"{classifier.nb_classes} classes; 1 to 32 are supported")
+        self.estimator, self._wave = classifier, isinstance(classifier, WaveformClassifier)
+        self.max_iter, self.epsilon, self.nb_grads, self.batch_size = int(max_iter), float(epsilon), int(nb_grads), int(batch_size)
+        self.overshoot, self.on_logits, self.verbose = float(overshoot), bool(on_logits), verbose
+        self.last = None
+
+    def _outputs(self, xa, lt, logits):
+        if self._wave:
+            return self.estimator.predict_device(xa, logits=logits, lengths=lt)
+        return self.estimator.model.predict_device(xa, logits=logits)
+
+    def _chunk(self, x0, lt):
+        """The rows ``x0`` (one chunk) -> (x_adv, iterations, flipped, target, first_dist) on the device."""
+        est = self.estimator
+        b, c = x0.shape[0], est.nb_classes
+        kw = {"lengths": lt} if self._wave else {}
+        clip = est.clip_values if self._wave else None
+        out0 = self._outputs(x0, lt, self.on_logits)
+        classes = torch.arange(c, device=x0.device, dtype=torch.int32)
+        label = torch.where(out0 == out0.max(dim=1, keepdim=True).values, classes[None, :], c).min(dim=1).values.to(torch.int32)
+        allowed = None
+        if self.nb_grads < c:
+            bits = (torch.ones(1, dtype=torch.int64, device=x0.device) << torch.topk(out0, self.nb_grads, dim=1).indices).sum(dim=1)
+            allowed = ((bits + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)  # the same 32 bits
+        xa = x0.clone()
+        iters = torch.zeros(b, dtype=torch.int32, device=x0.device)
+        target = torch.full((b,), -1, dtype=torch.int32, device=x0.device)
+        first = torch.full((b,), math.nan, device=x0.device)
+        for it in range(self.max_iter):
+            out = out0 if it == 0 else self._outputs(xa, lt, self.on_logits)
+            jac = est.jacobian_device(xa, on_logits=self.on_logits, **kw)
+            dist, tgt, state = deepfool_step(jac, out, label, xa, self.norm, self.overshoot, clip, allowed)
+            stepped = state == 1
+            iters += stepped
+            target = torch.where(stepped, tgt, target)
+            if it == 0:
+                first = dist
+            if (it + 1) % self.CHECK_EVERY == 0 and it + 1 < self.max_iter and not bool(stepped.any()):
+                break
+        adv = xa if self.epsilon == 0 else torch.where(xa == x0, x0, x0 + (1.0 + self.epsilon) * (xa - x0))
+        if clip is not None:
+            adv = adv.clamp(*clip)
+        if lt is not None:
+            adv = torch.where(est.clip_mask(lt), adv, x0)
+        final = self._outputs(adv, lt, True)
+        return adv, iters, final.argmax(dim=1) != label, target, first
+
+    def generate_device(self, xt, lengths=None):
+        """x: float32 device tensor [B, n]; returns a NEW device tensor (the input is left untouched).  lengths (WaveformClassifier
+        only): the samples of each row that belong to its clip."""
+        from .extract_features_construct_dataset import JACOBIAN_CHUNK_BYTES
+
+        if lengths is not None and not self._wave:
+            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
+        est = self.estimator
+        xt = xt.to(dtype=torch.float32).contiguous()
+        if xt.dim() != 2 or xt.shape[1] != est.input_shape[0]:
+            raise ValueError(f"x must be [B, {est.input_shape[0]}], got {tuple(xt.shape)}")
+        b, n = xt.shape
+        lt = est.lengths_device(lengths, b) if self._wave else None
+        chunk = min(max(1, JACOBIAN_CHUNK_BYTES // max(1, 4 * est.nb_classes * n)), int(est.batch_limit))
+        parts = [self._chunk(xt[s:s + chunk], None if lt is None else lt[s:s + chunk]) for s in range(0, b, chunk)]
+        if not parts:
+            self.last = dict(iterations=np.zeros(0, dtype=np.int64), flipped=np.zeros(0, dtype=bool), target=np.zeros(0, dtype=np.int64),
+                             first_dist=np.zeros(0))
+            return xt.clone()
+        cat = lambda i: torch.cat([p[i] for p in parts])
+        self.last = dict(iterations=cat(1).cpu().numpy().astype(np.int64), flipped=cat(2).cpu().numpy(),
+                         target=cat(3).cpu().numpy().astype(np.int64), first_dist=cat(4).double().cpu().numpy())
+        return cat(0)
+
+    def generate(self, x, lengths=None):
+        """NumPy in, new NumPy out (the input is left untouched)."""
+        adv = self.generate_device(_to_dev(x), lengths=lengths)
+        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+
+
 class ImperceptibleASR:
     """ART ``ImperceptibleASR`` (Qin et al. 2019) over a WaveformClassifier, in either domain: a targeted attack in two stages.
     Stage 1 finds an adversarial perturbation inside an L-inf ball that shrinks while the attack succeeds (sign steps of

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 590.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 600.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -26,6 +26,7 @@
  * (spectral norm and singular vectors of a stack of class gradients, per sample).
  * 590: the psychoacoustic masking threshold and the imperceptible attack's loss: lipasr_psy_create / _destroy / _psd / _threshold /
  * _prepare / _loss_grad / _step and the host-only lipasr_psy_table.
+ * 600: one DeepFool iteration for a batch, lipasr_deepfool_step.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -412,6 +413,34 @@ int lipasr_mlp_jacobian(lipasr_mlp_t m, const float* params, const float* bnstat
 int lipasr_jacobian_sigma(lipasr_handle_t h, const float* jac, int batch, int classes, int n, long stride_b, long stride_c,
                           float* sigma /* [batch] */, float* u /* [batch][classes] or NULL */,
                           float* v /* [batch][n] or NULL */, lipasr_stream_t stream);
+
+/* (ours: the reference has no minimal-perturbation attack; the iteration is ART's art.attacks.evasion.DeepFool, restated from its
+ * published implementation)  One DeepFool iteration for a batch, in place on x, in one launch.  jac: the class gradients J_b[c][k]
+ * at jac[b * stride_b + c * stride_c + k] (any non-negative strides in floats: [batch][classes][n] or the class-major view, the
+ * layouts lipasr_jacobian_sigma accepts); out: the logits or probabilities at x, whichever jac differentiates; label[b]: the class
+ * the row started in; allowed[b]: bit k set = class k may be the target (NULL = every class).  Per row b, with c = label[b]:
+ *   - any out[b][.] NaN or inf, or label[b] outside [0, classes): state -1, x[b] untouched, dist = NaN, target = -1;
+ *   - argmax out[b] (lowest index on a tie) != c, the row has left its class: state 0, x[b] untouched bit for bit, dist = 0,
+ *     target = that argmax;
+ *   - otherwise, for every k != c with bit k of allowed[b] set:  w_k = J_k - J_c,  f_k = out_k - out_c,
+ *         rho_k = |f_k| / (||w_k||_q + tol),   q = 2 for norm 2, q = 1 for norm inf,   tol = 1e-7 (ART's 10e-8),
+ *     l = argmin rho_k, lowest index on a tie.  A class whose ||w_k|| is NaN or inf (a NaN or inf in J_k or J_c) is never chosen;
+ *     when no class is left (classes == 1, an empty mask, a NaN in row c): state -1, x[b] untouched, dist = NaN, target = -1;
+ *   - the step:  norm 2:  r = |f_l| / (||w_l||_2^2 + tol) w_l;   norm inf:  r = |f_l| / (||w_l||_1 + tol) sign(w_l), sign(0) = 0;
+ *         x[b] <- clamp(x[b] + (1 + overshoot) r, clip_lo, clip_hi)     (-INFINITY / +INFINITY = no clipping),
+ *     dist[b] = rho_l (the distance to the linearised boundary, before the overshoot), target[b] = l, state[b] = 1.
+ *     A column where w_l is exactly 0 keeps the bits of x before clipping: a ragged clip's padding never moves.
+ * overshoot = 0 is ART's iteration; the paper's is 0.02.  norm: 2.0f or +INFINITY, anything else LIPASR_EINVAL; 1 <= classes <= 32,
+ * more is LIPASR_EINVAL; overshoot >= 0 and clip_lo <= clip_hi or LIPASR_EINVAL.  The differences w, their squares (or magnitudes)
+ * and the sums are fp64, lane-serial then a fixed-order tree: ||w_k|| is right to 1e-6 relative for any finite fp32 J (a ~1e-30
+ * Jacobian of a saturated softmax included), and two runs give the same bits.  dist is rounded to fp32 (+inf above its range).
+ * One workgroup per row, no workspace, no atomics, nothing waits on another workgroup.  dist, target and state may be NULL.
+ * batch == 0 returns LIPASR_OK; n == 0 too, with dist (= |f_l| / tol), target and state filled. */
+int lipasr_deepfool_step(lipasr_handle_t h, const float* jac, long stride_b, long stride_c, const float* out /* [batch][classes] */,
+                         const int* label /* [batch] */, const uint32_t* allowed /* [batch] or NULL */, int batch, int classes,
+                         int n, float norm, float overshoot, float clip_lo, float clip_hi, float* x /* [batch][n] */,
+                         float* dist /* [batch] or NULL */, int* target /* [batch] or NULL */, int* state /* [batch] or NULL */,
+                         lipasr_stream_t stream);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
