@@ -122,6 +122,17 @@ struct Philox {
   __host__ __device__ static inline float u01(uint32_t x) { return ((x >> 8) + 1u) * (1.0f / 16777216.0f); }
 };
 
+// Four N(0,1) draws from one Philox block (Box-Muller on two pairs).  add_noise_kernel (mfcc.hip), smooth_expand_kernel and the
+// host table lipasr_smooth_noise_host (smoothing.hip) share it: the device bits are one function, the host's differ by the libm.
+__host__ __device__ __forceinline__ void normal4(uint64_t seed, uint64_t ctr, uint32_t hi0, uint32_t hi1, float (&z)[4]) {
+  uint32_t o[4];
+  Philox::gen(seed, ctr, hi0, hi1, o);
+  const float u0 = Philox::u01(o[0]), u1 = Philox::u01(o[1]), u2 = Philox::u01(o[2]), u3 = Philox::u01(o[3]);
+  const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+  const float t0 = 6.283185307179586f * u1, t1 = 6.283185307179586f * u3;
+  z[0] = r0 * cosf(t0); z[1] = r0 * sinf(t0); z[2] = r1 * cosf(t1); z[3] = r1 * sinf(t1);
+}
+
 // lp_attack.hip: norm 1, 2 or +inf -> code 1, 2 or 0 (else LIPASR_EINVAL with a message naming fn); the Lp step kernel on
 // [rows][n] (any n, any alignment) -- lipasr_mlp_attack_step_lp's second launch
 int lp_norm_code(const char* fn, float norm, int* code);

@@ -28,17 +28,8 @@ void mfcc_plan_free(MfccPlan* p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// A12 audio-domain noise (attacks.py:73-86, 145-183, 222-245), one workgroup per clip
+// A12 audio-domain noise (attacks.py:73-86, 145-183, 222-245), one workgroup per clip (normal4: common.h)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void normal4(uint64_t seed, uint64_t ctr, uint32_t hi0, uint32_t hi1, float (&z)[4]) {
-  uint32_t o[4];
-  Philox::gen(seed, ctr, hi0, hi1, o);
-  const float u0 = Philox::u01(o[0]), u1 = Philox::u01(o[1]), u2 = Philox::u01(o[2]), u3 = Philox::u01(o[3]);
-  const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-  const float t0 = 6.283185307179586f * u1, t1 = 6.283185307179586f * u3;
-  z[0] = r0 * cosf(t0); z[1] = r0 * sinf(t0); z[2] = r1 * cosf(t1); z[3] = r1 * sinf(t1);
-}
-
 __global__ __launch_bounds__(256) void add_noise_kernel(float* __restrict__ y, int n, int mode, float p0, float p1,
                                                          uint64_t seed) {
   __shared__ double red[4];

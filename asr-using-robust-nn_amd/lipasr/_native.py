@@ -104,6 +104,9 @@ PROTOTYPES = {
     "lipasr_mlp_jacobian": (i32, [c_h, c_f, c_f, c_f, i32, i32, c_f, c_f, C.c_long, C.c_long, c_s]),
     "lipasr_jacobian_sigma": (i32, [c_h, c_f, i32, i32, i32, C.c_long, C.c_long, c_f, c_f, c_f, c_s]),
     "lipasr_deepfool_step": (i32, [c_h, c_f, C.c_long, C.c_long, c_f, c_f, c_f, i32, i32, i32, f32, f32, f32, f32, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_smooth_expand": (i32, [c_h, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, f32, u64, f32, f32, c_f, c_s]),
+    "lipasr_smooth_vote": (i32, [c_h, c_f, i32, i32, i32, c_f, c_s]),
+    "lipasr_smooth_noise_host": (i32, [u64, C.c_uint32, C.c_uint32, i32, C.POINTER(f32)]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -166,7 +169,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_dolphin_generate_recorded": 570, "lipasr_dolphin_table": 570, "lipasr_mlp_jacobian": 580,
          "lipasr_jacobian_sigma": 580, "lipasr_psy_create": 590, "lipasr_psy_destroy": 590, "lipasr_psy_psd": 590,
          "lipasr_psy_threshold": 590, "lipasr_psy_prepare": 590, "lipasr_psy_loss_grad": 590, "lipasr_psy_step": 590,
-         "lipasr_psy_table": 590, "lipasr_deepfool_step": 600}
+         "lipasr_psy_table": 590, "lipasr_deepfool_step": 600, "lipasr_smooth_expand": 610,
+         "lipasr_smooth_vote": 610, "lipasr_smooth_noise_host": 610}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -374,6 +378,15 @@ def psy_table(which: int, sample_rate: int = 16000):
     out = np.zeros(n, dtype=np.float64)
     check(lib.lipasr_psy_table(which, sample_rate, out.ctypes.data_as(C.POINTER(C.c_double)), n))
     return out
+
+
+def smooth_noise(seed: int, clip: int, draw: int, n: int):
+    """Host-only: the n standard-normal draws lipasr_smooth_expand adds to clip `clip`, draw `draw` (numpy float32)."""
+    import numpy as np
+
+    out = np.zeros(max(int(n), 1), dtype=np.float32)
+    check(lib.lipasr_smooth_noise_host(int(seed), int(clip), int(draw), int(n), out.ctypes.data_as(C.POINTER(f32))))
+    return out[:int(n)]
 
 
 def debug_table(which: int, sr_in: int = 16000):

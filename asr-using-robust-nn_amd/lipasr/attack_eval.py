@@ -13,6 +13,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
     (no prompt: the Lipschitz read-outs, global and local) attack="lipschitz": lipschitz_report over="mfcc" | "audio"
     (no prompt: certified radius next to DeepFool's)       attack="radius": radius_report over="mfcc" | "audio", --norm 2 | inf
+    (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth": smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
 """
 from __future__ import annotations
 
@@ -434,6 +435,74 @@ def radius_report(models, train_data, val_data, test_data, over="mfcc", standard
     return out
 
 
+SMOOTH_RADII = (0.0, 0.25, 0.5, 0.75, 1.0, 1.5, 2.0, 3.0, 4.0)  # in units of sigma: CERTIFY's radius tops out at sigma Phi^-1(alpha^(1/n))
+
+
+def smooth_report(models, train_data, val_data, test_data, test_labels, sigma, n0=100, n=100_000, alpha=0.001, over="mfcc",
+                  standardize="before", test_filenames=None, domain="22k", limit=None, radii=None, seed=0):
+    """Randomized smoothing (lipasr.smoothing.Smooth.certify: Cohen's CERTIFY with N(0, sigma^2 I)) per model: the certified
+    accuracy at a grid of L2 radii -- the share of test rows whose smoothed class is the label and whose certified radius is at
+    least r -- and the abstention rate.  It certifies the SMOOTHED classifier; next to it, for the constrained model over MFCC rows,
+    the median radius its Lipschitz bound certifies for the base classifier (margin / (sqrt(2) get_lipschitz_bound(model))).
+    ``over``, ``standardize``, ``test_filenames``, ``domain`` and ``limit`` as in radius_report; ``test_labels`` one-hot, row for
+    row with the test rows (over audio: with ``test_filenames``); ``radii``: the grid (default SMOOTH_RADII x sigma).
+    Returns {model name: {"radius", "class", "p_lower": the per-row arrays, "radii", "certified_accuracy" (one per radius),
+    "abstained", "lipschitz_median" (or None)}}."""
+    from .smoothing import Smooth
+
+    if not (float(sigma) >= 0.0 and np.isfinite(float(sigma))):
+        raise ValueError(f"sigma = {sigma}: a finite, non-negative number is required")
+    if over == "audio":
+        if test_filenames is None:
+            raise ValueError("the read-out over audio needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+        if domain not in ("22k", "input"):
+            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
+    elif over == "mfcc":
+        if standardize == "before":
+            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
+        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
+    else:
+        raise ValueError("over must be 'audio' or 'mfcc'")
+    truth = np.asarray(test_labels[:limit] if limit else test_labels).argmax(axis=1)
+    radii = np.asarray([f * float(sigma) for f in SMOOTH_RADII] if radii is None else radii, dtype=np.float64)
+    kw = dict(n0=n0, n=n, alpha=alpha)
+    out = {}
+    for name, model in models.items():
+        lip = None
+        if over == "mfcc":
+            clf = A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(x.shape[1],),
+                                           loss_object=CategoricalCrossentropy())
+            r = Smooth(clf, sigma, seed=seed).certify(x, **kw)
+            if name == "constrained" and len(x) and model._n_classes > 1:
+                top = torch.topk(model.predict_device(A._to_dev(x), logits=True).double(), 2, dim=1).values
+                lip = float(np.median((top[:, 0] - top[:, 1]).cpu().numpy() / (np.sqrt(2.0) * get_lipschitz_bound(model))))
+        else:
+            r = {"radius": np.zeros(len(test_filenames)), "class": np.full(len(test_filenames), -1, dtype=np.int64),
+                 "p_lower": np.zeros(len(test_filenames))}
+            for sr, n_samp, items, lens in work:
+                clf, rows, lt = _audio_rows(model, model._n_classes, sc, domain, bmax, sr, n_samp, items, lens)
+                part = Smooth(clf, sigma, seed=seed).certify(rows, lengths=lt, **kw)
+                for k in r:
+                    r[k][[i for i, _ in items]] = part[k]
+        r = {k: r[k] for k in ("radius", "class", "p_lower")}
+        hit = r["class"] == truth[:len(r["class"])]
+        r["radii"] = radii
+        r["certified_accuracy"] = np.array([float(np.mean(hit & (r["radius"] >= q))) if len(hit) else float("nan") for q in radii])
+        r["abstained"] = float(np.mean(r["class"] < 0)) if len(hit) else float("nan")
+        r["lipschitz_median"] = lip
+        out[name] = r
+        tag = "" if name == "constrained" else " " + name
+        what = f"{len(hit)} test {'rows' if over == 'mfcc' else 'files'}"
+        for q, a in zip(radii, r["certified_accuracy"]):
+            print(f"Certified accuracy of the smoothed classifier (sigma {sigma}) over {what}{tag} at L2 radius {q}: {a * 100}%")
+        print(f"Share of {what} on which the smoothed classifier abstains{tag}: {r['abstained'] * 100}%")
+        if lip is not None:
+            print(f"Median radius the Lipschitz bound certifies for the base classifier over {what}{tag}: {lip}")
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="attacks.py's evaluation menu as flags")
     ap.add_argument("--path", default="processed_google_dataset/")
@@ -441,7 +510,7 @@ def main(argv=None):
     ap.add_argument("--constrained", default="bin/models_constrained/model_constrained_Rho01_dropout01.h5")
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
-    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius"], default="black")
+    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
     ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma|imperceptible")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
@@ -449,6 +518,10 @@ def main(argv=None):
     ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
     ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
     ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
+    ap.add_argument("--sigma", type=float, default=None, help="smooth: standard deviation of the smoothing noise (required)")
+    ap.add_argument("--n0", type=int, default=100, help="smooth: draws that select the class")
+    ap.add_argument("--n", type=int, default=100000, help="smooth: draws that estimate its vote share")
+    ap.add_argument("--alpha", type=float, default=0.001, help="smooth: failure probability of the certificate")
     ap.add_argument("--max-iter-1", type=int, default=1000)
     ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
@@ -456,6 +529,9 @@ def main(argv=None):
 
     if args.attack == "radius" and args.norm == "1":
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
+
+    if args.attack == "smooth" and (args.sigma is None or not 0.0 <= args.sigma < float("inf")):
+        raise ValueError("--attack smooth needs --sigma, the standard deviation of the noise (finite, not negative; there is no default)")
 
     train_data, _, val_data, _, test_data, test_label = A.load_npy_dataset(args.path)
     n_classes = int(test_label.max()) + 1
@@ -475,6 +551,12 @@ def main(argv=None):
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
         return radius_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
                              test_filenames=names, norm=np.inf if args.norm == "inf" else 2, limit=args.points)
+    if args.attack == "smooth":
+        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
+        if names is not None:
+            labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
+        return smooth_report(models, train_data, val_data, test_data, labels, args.sigma, n0=args.n0, n=args.n, alpha=args.alpha,
+                             over=args.over, standardize=args.standardize, test_filenames=names, limit=args.points)
     if args.attack == "dolphin":
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
         labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)

@@ -441,7 +441,7 @@ def get_lipschitz_bound(model):
     return bound
 
 
-def get_robustness_radius(estimator, x, norm=2, lengths=None, **deepfool_kw):
+def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **deepfool_kw):
     """Per row of ``x`` the three numbers  certified radius <= distance to the decision boundary <= distance DeepFool found,  as a
     dict of float64 NumPy arrays [B]:
       margin     min over k != c of z_c - z_k on the logits, c the estimator's own class at the row;
@@ -451,6 +451,13 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, **deepfool_kw):
       linear     the distance to the nearest boundary of the classifier linearised at the row (DeepFool's first rho_l);
       found      ||x_adv - x|| in ``norm`` for attacks.DeepFool(estimator, norm=norm, **deepfool_kw);
       flipped    bool: x_adv is classified differently.  Where it is False, ``found`` bounds nothing.
+    ``smoothing``: None (default: the dict above, nothing else), or dict(sigma=, n0=100, n=100_000, alpha=0.001, seed=0,
+    clip_values=None) -- randomized smoothing (lipasr.smoothing.Smooth.certify) then adds
+      smoothed_radius  the L2 radius sigma Phi^-1(p_lower) within which the SMOOTHED classifier g(x) = argmax_c P(f(x + N(0,
+                       sigma^2 I)) = c) keeps its class, with probability 1 - alpha over the draws; 0 where it abstains;
+      smoothed_class   int64: the class of g at the row, -1 where it abstains.
+    It certifies the smoothed classifier, not the base one whose margin, ``certified`` and ``found`` stand next to it; over audio
+    and for a model without a useful Lipschitz bound it is the only certified entry.  It is an L2 radius whatever ``norm`` is.
     ``estimator``: attacks.TensorFlowV2Classifier or attacks.WaveformClassifier (``lengths`` as there)."""
     from . import attacks as A
 
@@ -476,8 +483,18 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, **deepfool_kw):
     certified = None
     if not wave and attack.norm == 2.0:
         certified = margin / (np.sqrt(2.0) * get_lipschitz_bound(estimator.model))
-    return {"margin": margin, "certified": certified, "linear": attack.last["first_dist"], "found": found,
-            "flipped": attack.last["flipped"]}
+    res = {"margin": margin, "certified": certified, "linear": attack.last["first_dist"], "found": found,
+           "flipped": attack.last["flipped"]}
+    if smoothing is not None:
+        from .smoothing import Smooth
+
+        kw = dict(smoothing)
+        if "sigma" not in kw:
+            raise ValueError("smoothing= needs sigma")
+        sm = Smooth(estimator, kw.pop("sigma"), seed=kw.pop("seed", 0), clip_values=kw.pop("clip_values", None))
+        cert = sm.certify(xt, lengths=lengths, **kw)
+        res["smoothed_radius"], res["smoothed_class"] = cert["radius"], cert["class"]
+    return res
 
 
 # ------------------------------------------------------------------------------------------------ dataset construction

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 600.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 610.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -27,6 +27,8 @@
  * 590: the psychoacoustic masking threshold and the imperceptible attack's loss: lipasr_psy_create / _destroy / _psd / _threshold /
  * _prepare / _loss_grad / _step and the host-only lipasr_psy_table.
  * 600: one DeepFool iteration for a batch, lipasr_deepfool_step.
+ * 610: randomized smoothing: lipasr_smooth_expand (noisy copies of every row), lipasr_smooth_vote (argmax histogram per clip) and
+ * the host-only lipasr_smooth_noise_host.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -441,6 +443,38 @@ int lipasr_deepfool_step(lipasr_handle_t h, const float* jac, long stride_b, lon
                          int n, float norm, float overshoot, float clip_lo, float clip_hi, float* x /* [batch][n] */,
                          float* dist /* [batch] or NULL */, int* target /* [batch] or NULL */, int* state /* [batch] or NULL */,
                          lipasr_stream_t stream);
+
+/* (ours: the reference sweeps add_white_noise over sigmas, attacks.py:73-86, 335-339; CERTIFY and PREDICT of Cohen, Rosenfeld,
+ * Kolter 2019 turn the same draws into a guarantee per clip)  The noisy copies of randomized smoothing, written once, in one launch.
+ * Row b * draws + j of out, element k, with nv = min(max(n_valid[b], 0), n) (n_valid NULL: nv = n):
+ *   - k < nv:   out = clamp(fmaf(sigma, z, x[b][k]), clip_lo, clip_hi)   (-INFINITY / +INFINITY = no clipping),
+ *               z = normal4(seed, k >> 2, clip0 + b, draw0 + j)[k & 3]: the Philox4x32-10 block with key seed and counter
+ *               (k >> 2 low, k >> 2 high = 0, clip0 + b, draw0 + j), Box-Muller on its two pairs;
+ *   - k >= nv:  the bits of x[b][k], untouched and unclamped: a ragged clip's padding never moves.
+ * The draw is a pure function of (seed, clip index, draw index, element): it depends on neither batch nor draws nor on where a
+ * chunk starts, so chunks of any size reproduce one big call bit for bit.  clip0 = 0, draw0 = 0, draws = 1 are the counters of
+ * lipasr_add_noise_f32 mode 0: one draw is the reference's white-noise attack (to the rounding of one fused multiply-add).
+ * sigma = 0 returns x in value.  A NaN in x stays a NaN.  x and out must not overlap.
+ * sigma < 0 or non-finite, clip_lo > clip_hi, a negative size, or more than 2^31 - 1 output rows: LIPASR_EINVAL; batch, draws or
+ * n equal to 0: LIPASR_OK with nothing written; null pointers are refused before the device is touched.
+ * Any n, any alignment of x and out (float4 where a row starts on 16 bytes, scalars otherwise; the values do not depend on it).
+ * One workgroup per output row, no workspace, no atomics: two runs give the same bits. */
+int lipasr_smooth_expand(lipasr_handle_t h, const float* x /* [batch][n] */, const int* n_valid /* [batch] or NULL */, int batch,
+                         int n, int draws, uint32_t clip0, uint32_t draw0, float sigma, uint64_t seed, float clip_lo, float clip_hi,
+                         float* out /* [batch * draws][n] */, lipasr_stream_t stream);
+
+/* The votes of randomized smoothing: per clip b, the histogram of the argmax over rows b * draws .. b * draws + draws - 1 of logits
+ * [batch * draws][classes], ADDED to counts[b][0 .. classes] (int32, [batch][classes + 1]): the caller zeroes counts, and calls
+ * accumulate across chunks.  Per row: the largest entry wins, the lowest index on a tie, +inf is a maximum like any other (a row of
+ * -inf votes for class 0); a row with any NaN goes to bin `classes` and to no class.  One launch, one workgroup per clip, which
+ * alone touches counts[b][.]; per-wave counts by ballot and popcount, summed through LDS in a fixed order; no global atomics: two
+ * runs give the same bits.  1 <= classes <= 32, otherwise LIPASR_EINVAL; batch == 0 or draws == 0 return LIPASR_OK. */
+int lipasr_smooth_vote(lipasr_handle_t h, const float* logits, int batch, int draws, int classes,
+                       int* counts /* [batch][classes + 1] */, lipasr_stream_t stream);
+
+/* Host-only (no GPU needed): z_out[k] = normal4(seed, k >> 2, clip, draw)[k & 3] for k = 0 .. n - 1, the draws lipasr_smooth_expand
+ * adds to clip `clip`, draw `draw` (the host's logf / sinf / cosf: equal to the device's to a few units in the last place). */
+int lipasr_smooth_noise_host(uint64_t seed, uint32_t clip, uint32_t draw, int n, float* z_out /* host [n] */);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
