@@ -107,6 +107,9 @@ PROTOTYPES = {
     "lipasr_smooth_expand": (i32, [c_h, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, f32, u64, f32, f32, c_f, c_s]),
     "lipasr_smooth_vote": (i32, [c_h, c_f, i32, i32, i32, c_f, c_s]),
     "lipasr_smooth_noise_host": (i32, [u64, C.c_uint32, C.c_uint32, i32, C.POINTER(f32)]),
+    "lipasr_genetic_breed": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, C.c_uint32, f32, f32, f32, f32, c_f, c_s]),
+    "lipasr_genetic_breed_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, C.c_uint32, f32, f32, f32, f32, c_f]),
+    "lipasr_genetic_select": (i32, [c_h, c_f, c_f, i32, i32, i32, i32, f32, C.c_uint32, C.c_uint32, u64, c_f, c_f, c_f, c_f, c_s]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -170,7 +173,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_jacobian_sigma": 580, "lipasr_psy_create": 590, "lipasr_psy_destroy": 590, "lipasr_psy_psd": 590,
          "lipasr_psy_threshold": 590, "lipasr_psy_prepare": 590, "lipasr_psy_loss_grad": 590, "lipasr_psy_step": 590,
          "lipasr_psy_table": 590, "lipasr_deepfool_step": 600, "lipasr_smooth_expand": 610,
-         "lipasr_smooth_vote": 610, "lipasr_smooth_noise_host": 610}
+         "lipasr_smooth_vote": 610, "lipasr_smooth_noise_host": 610, "lipasr_genetic_breed": 620,
+         "lipasr_genetic_breed_host": 620, "lipasr_genetic_select": 620}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -387,6 +391,37 @@ def smooth_noise(seed: int, clip: int, draw: int, n: int):
     out = np.zeros(max(int(n), 1), dtype=np.float32)
     check(lib.lipasr_smooth_noise_host(int(seed), int(clip), int(draw), int(n), out.ctypes.data_as(C.POINTER(f32))))
     return out[:int(n)]
+
+
+def genetic_breed_host(x0, pop, generation, seed, mutate_thresh, step, eps, *, pop_in=None, parents=None, n_valid=None, clip0=0,
+                       clip_lo=-float("inf"), clip_hi=float("inf"), out=None):
+    """Host-only: lipasr_genetic_breed_host on NumPy arrays (x0 float32 [B, n], pop_in float32 [B, pop, n] and parents int32
+    [B, pop, 2] or neither, n_valid int32 [B] or None) -> float32 [B, pop, n]: the bits lipasr_genetic_breed writes on the device."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float32)
+    b, n = x0.shape
+    pop = int(pop)
+    keep = [x0]
+
+    def arr(a, dtype, shape):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != shape:
+            raise ValueError(f"expected shape {shape}, got {a.shape}")
+        keep.append(a)
+        return C.c_void_p(a.ctypes.data)
+
+    if out is None:
+        out = np.zeros((b, max(pop, 0), n), dtype=np.float32)
+    elif out.dtype != np.float32 or out.shape != (b, pop, n) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a contiguous float32 array ({b}, {pop}, {n})")
+    check(lib.lipasr_genetic_breed_host(C.c_void_p(x0.ctypes.data), arr(n_valid, np.int32, (b,)), arr(pop_in, np.float32, (b, pop, n)),
+                                        arr(parents, np.int32, (b, pop, 2)), b, pop, n, int(clip0), int(generation), int(seed),
+                                        int(mutate_thresh), float(step), float(eps), float(clip_lo), float(clip_hi),
+                                        C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def debug_table(which: int, sr_in: int = 16000):

@@ -13,7 +13,8 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
     (no prompt: the Lipschitz read-outs, global and local) attack="lipschitz": lipschitz_report over="mfcc" | "audio"
     (no prompt: certified radius next to DeepFool's)       attack="radius": radius_report over="mfcc" | "audio", --norm 2 | inf
-    (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth": smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
+    (no prompt: the genetic query-only attack)             attack="black", kind="genetic": genetic_sweep over="mfcc" | "audio"
+    (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth":smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
 """
 from __future__ import annotations
 
@@ -231,6 +232,74 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
         return A.standardize_dataset(train_data, val_data, adv)[2] if standardize == "after" else adv
 
     return _sweep(clfs, grid, make, labels, "adversarial")
+
+
+# ours (the reference has no query-only attack): L-inf radii for lipasr.attacks.GeneticAttack.  Over MFCC rows the grid is the
+# white-box FGSM one (:497-499), so that the curve lies over white_box_sweep's; over audio a short list of amplitudes out of AUDIO_SIGMAS
+GENETIC_AUDIO_EPS = [0.002, 0.004, 0.01, 0.02, 0.05]
+
+
+def genetic_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
+                  domain="22k", grid=None, points=None, limit=None, **attack_kw):
+    """The genetic black-box attack (lipasr.attacks.GeneticAttack: scores only, no gradient) against its L-inf radius eps, untargeted,
+    from each model's own predictions: per model and eps the accuracy on the attacked rows and the mean number of queries the
+    successful clips took.  over="mfcc": the rows of ``test_data`` (standardize as in white_box_sweep; the default grid is its FGSM
+    grid); over="audio": the audio of ``test_filenames`` through WaveformClassifier, prepared as in white_box_sweep(over="audio")
+    (default grid GENETIC_AUDIO_EPS, amplitudes; iterates stay in [-1, 1]).  ``attack_kw``: GeneticAttack's keywords (pop_size,
+    max_iter, mutation_p, ...).  A query-only attack that ends BELOW the gradient attacks' accuracy at the same eps says that the
+    gradients are masked.  Returns (grid, {model name: accuracies}, {model name: mean queries of the successful clips, nan if none})."""
+    if over not in ("audio", "mfcc"):
+        raise ValueError("over must be 'audio' or 'mfcc'")
+    acc, queries = {name: [] for name in models}, {name: [] for name in models}
+
+    def report(name, item, a, atk_stats):
+        ok, q = atk_stats
+        mean_q = float(np.mean(q[ok])) if ok.any() else float("nan")
+        acc[name].append(a)
+        queries[name].append(mean_q)
+        tag = "" if name == "constrained" else " " + name
+        print(f"Accuracy on genetic black-box {'audio ' if over == 'audio' else ''}test examples{tag}: {a * 100}% ({item}); "
+              f"{int(ok.sum())} of {len(ok)} clips succeeded, mean queries of those: {mean_q}")
+
+    if over == "audio":
+        if test_filenames is None:
+            raise ValueError("attacks over audio need test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+        if domain not in ("22k", "input"):
+            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
+        labels = test_labels[:limit] if limit else test_labels
+        n_classes = labels.shape[1]
+        grid = list(GENETIC_AUDIO_EPS if grid is None else grid)[:points]
+        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
+        for item in grid:
+            for name, model in models.items():
+                pred = np.zeros((len(test_filenames), n_classes))
+                ok, q = np.zeros(len(test_filenames), dtype=bool), np.zeros(len(test_filenames), dtype=np.int64)
+                for sr, n, items, lens in work:
+                    clf, x, lt = _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, lens)
+                    idx = [i for i, _ in items]
+                    atk = A.GeneticAttack(clf, item, **attack_kw)
+                    adv = atk.generate_device(x, None, lengths=lt)
+                    pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
+                    ok[idx], q[idx] = atk.success_.cpu().numpy(), atk.queries_.cpu().numpy()
+                report(name, item, accuracy(pred, labels), (ok, q))
+    else:
+        if standardize == "before":
+            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
+        n_classes, n_in = test_labels.shape[1], test_data.shape[1]
+        default = np.linspace(1, 30, 50) if standardize == "after" else np.linspace(0.01, 0.3, 10)  # white_box_sweep's FGSM grid
+        grid = list(default if grid is None else grid)[:points]
+        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
+        labels = test_labels[:limit] if limit else test_labels
+        for item in grid:
+            for name, model in models.items():
+                clf = A.TensorFlowV2Classifier(model=model, nb_classes=n_classes, input_shape=(n_in,), loss_object=CategoricalCrossentropy())
+                atk = A.GeneticAttack(clf, item, **attack_kw)
+                adv = atk.generate(x)
+                if standardize == "after":
+                    adv = A.standardize_dataset(train_data, val_data, adv)[2]
+                report(name, item, accuracy(model.predict(adv), labels), (atk.success_.cpu().numpy(), atk.queries_.cpu().numpy()))
+    return grid, {k: np.asarray(v) for k, v in acc.items()}, {k: np.asarray(v) for k, v in queries.items()}
 
 
 def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, grid=DOLPHIN_CARRIER_LEVELS, a1=1.0, a2=0.5,
@@ -511,7 +580,9 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr; white: fgsm|l2|linf|pgd|jsma|imperceptible")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic; white: fgsm|l2|linf|pgd|jsma|imperceptible")
+    ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
+    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's)")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
     ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; radius: 2 or inf")
@@ -541,6 +612,10 @@ def main(argv=None):
         names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
         if names is not None:
             labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)  # :298-304
+        if args.kind == "genetic":
+            kw = {k: v for k, v in (("pop_size", args.pop_size), ("max_iter", args.max_iter)) if v is not None}
+            return genetic_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
+                                 test_filenames=names, points=args.points, **kw)
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
     if args.attack == "lipschitz":

@@ -14,7 +14,8 @@ each clip and the rest of the row comes back untouched.  Over a short-window ext
 441, hop 220) the gradient goes through lipasr_mfcc_plan_vjp_short.
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
-models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.
+models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.  ``GeneticAttack`` (lipasr/genetic.py,
+ours) is the one black-box attack that looks at the model's answer: a genetic algorithm over score queries.
 """
 from __future__ import annotations
 
@@ -1274,3 +1275,6 @@ def load_npy_dataset(path):
 
     return (ld("train_data.npy"), ld("train_label.npy"), ld("dev_data.npy"), ld("dev_label.npy"), ld("test_data.npy"),
             ld("test_label.npy"))
+
+
+from .genetic import GeneticAttack  # noqa: E402  (the genetic black-box attack: scores only; lipasr/genetic.py)

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 610.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 620.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -29,6 +29,8 @@
  * 600: one DeepFool iteration for a batch, lipasr_deepfool_step.
  * 610: randomized smoothing: lipasr_smooth_expand (noisy copies of every row), lipasr_smooth_vote (argmax histogram per clip) and
  * the host-only lipasr_smooth_noise_host.
+ * 620: the genetic black-box attack: lipasr_genetic_breed (one generation's children), lipasr_genetic_select (fitness, elite and
+ * parent draws per clip) and the host-only lipasr_genetic_breed_host.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -475,6 +477,62 @@ int lipasr_smooth_vote(lipasr_handle_t h, const float* logits, int batch, int dr
 /* Host-only (no GPU needed): z_out[k] = normal4(seed, k >> 2, clip, draw)[k & 3] for k = 0 .. n - 1, the draws lipasr_smooth_expand
  * adds to clip `clip`, draw `draw` (the host's logf / sinf / cosf: equal to the device's to a few units in the last place). */
 int lipasr_smooth_noise_host(uint64_t seed, uint32_t clip, uint32_t draw, int n, float* z_out /* host [n] */);
+
+/* (ours: the reference's black-box side is three noise sweeps, attacks.py:73-86, 145-294, none of which looks at the model's answer;
+ * this is the genetic algorithm of Alzantot, Balaji, Srivastava 2018, which needs scores only)  One generation's children, written
+ * once, in one launch.  Row b * pop + p of pop_out is child p of clip b; gen(seed; lo, hi0, hi1) below is the Philox4x32-10 block
+ * with key seed and counter (lo low word, lo high word, hi0, hi1).
+ *   - parents (a, c) = parents[b][p], both indices into the clip's members in pop_in (an index outside [0, pop) is clamped into it);
+ *     c < 0: the child is member a of pop_in, copied verbatim (no draw, no clamp): the elite, and clips that are finished.
+ *     pop_in == NULL (then parents must be NULL too): both parents are x0[b] -- the initial population.
+ *   - per quad q = k >> 2 one block o = gen(seed; q, clip0 + b, generation * 256 + p); word e serves element k = 4 q + e:
+ *     bit 0 picks the parent (0: a, 1: c), and the element mutates iff (o[e] >> 8) < mutate_thresh -- the caller passes
+ *     round(p_mut * 2^24), so the decision is integer-exact (0: never, 2^24: always; more is LIPASR_EINVAL);
+ *   - a mutating element takes child = fmaf(step, v, picked), v = 2 u01(m[e]) - 1 in (-1, 1] (exact in fp32),
+ *     m = gen(seed; q | 1 << 63, clip0 + b, generation * 256 + p), u01(w) = ((w >> 8) + 1) / 2^24;
+ *   - then, for k < nv = min(max(n_valid[b], 0), n) (n_valid NULL: nv = n): clamp to [x0 - eps, x0 + eps] (the two bounds rounded
+ *     to fp32), then to [clip_lo, clip_hi] (-INFINITY / +INFINITY: no clamp); k >= nv: the bits of x0[b][k], whatever the parents
+ *     hold -- of a copied child as well.  A NaN stays a NaN.
+ * The draws are a pure function of (seed, clip index, generation, member, element): chunks of any size at any clip0 reproduce one
+ * big call bit for bit, and lipasr_genetic_breed_host gives the same bits on the host (one shared inline function, no libm but a
+ * fused multiply-add).  Any n, any alignment of x0, pop_in and pop_out (float4 where a row starts on 16 bytes, scalars otherwise;
+ * the values do not depend on it).  One workgroup per output row, no workspace, no atomics.
+ * 2 <= pop <= 64, generation < 2^24, step and eps finite and >= 0, clip_lo <= clip_hi, batch * pop <= 2^31 - 1, pop_out overlapping
+ * neither pop_in nor x0, or LIPASR_EINVAL; batch or n equal to 0: LIPASR_OK with nothing written; null pointers are refused before
+ * the device is touched. */
+int lipasr_genetic_breed(lipasr_handle_t h, const float* x0 /* [batch][n] */, const int* n_valid /* [batch] or NULL */,
+                         const float* pop_in /* [batch][pop][n] or NULL */, const int* parents /* [batch][pop][2] or NULL */,
+                         int batch, int pop, int n, uint32_t clip0, uint32_t generation, uint64_t seed, uint32_t mutate_thresh,
+                         float step, float eps, float clip_lo, float clip_hi, float* pop_out /* [batch][pop][n] */,
+                         lipasr_stream_t stream);
+
+/* Host-only (no GPU needed): lipasr_genetic_breed on host arrays, the same inline function in a plain loop -- the CPU-side pin of the
+ * counters above.  Same checks, same bits. */
+int lipasr_genetic_breed_host(const float* x0, const int* n_valid, const float* pop_in, const int* parents, int batch, int pop, int n,
+                              uint32_t clip0, uint32_t generation, uint64_t seed, uint32_t mutate_thresh, float step, float eps,
+                              float clip_lo, float clip_hi, float* pop_out);
+
+/* The selection of one generation: per clip b, from rows b * pop .. b * pop + pop - 1 of logits [batch * pop][classes] and the class
+ * y = labels[b]:
+ *   - fitness[b][p] = max_{c != y} z_c - z_y (targeted: z_y - max_{c != y} z_c), the difference taken in fp64 and rounded once;
+ *     -inf for a row with any NaN, for a NaN difference (inf - inf), for a label outside [0, classes) and, untargeted, for
+ *     classes = 1;
+ *   - best[b] = the argmax of the fitness, the lowest index on a tie;
+ *   - done[b] is sticky: a clip that arrives with done[b] != 0 keeps its best and its done; otherwise, where fitness[best] > 0,
+ *     done[b] = generation + 1 -- with one select per generation, counted from 0, the number of populations evaluated up to and
+ *     including the one that succeeded.  A clip that is done (on arrival or now) gets parents[p] = (p, -1) for every p, which
+ *     freezes its population under lipasr_genetic_breed; so does a clip none of whose members has a fitness above -inf;
+ *   - every other clip: w_p = expf((fit_p - max) / temperature) (the argument in fp64, 0 for fit_p = -inf), the inclusive sums of w in
+ *     index order in fp64 by a wave scan of fixed order; child 0 gets (best, -1), the elite; child p >= 1 draws u_a, u_c =
+ *     u01 of words 0 and 1 of gen(seed; p | 1 << 62, clip0 + b, generation * 256), and each parent is the first index whose
+ *     inclusive sum is >= u * total (a member of weight 0 is never drawn).
+ * One wavefront per clip, lane p owns member p; no global atomics, no other workgroup touches a clip's outputs: two runs give the
+ * same bits.  1 <= classes <= 32, 2 <= pop <= 64, temperature finite and > 0, generation < 2^24, or LIPASR_EINVAL; batch == 0
+ * returns LIPASR_OK. */
+int lipasr_genetic_select(lipasr_handle_t h, const float* logits, const int* labels /* [batch] */, int batch, int pop, int classes,
+                          int targeted, float temperature, uint32_t clip0, uint32_t generation, uint64_t seed,
+                          float* fitness /* [batch][pop] */, int* best /* [batch] */, int* done /* [batch] */,
+                          int* parents /* [batch][pop][2] */, lipasr_stream_t stream);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
