@@ -45,13 +45,18 @@ def accuracy(predictions, labels_onehot):
     return float(np.sum(np.argmax(predictions, axis=1) == np.argmax(labels_onehot, axis=1)) / len(labels_onehot))
 
 
+def _tag(name):
+    """What a printed line says after its subject: nothing for the constrained model, the name of any other."""
+    return "" if name == "constrained" else " " + name
+
+
 def _sweep(models, grid, make_data, labels, what):
     acc = {name: [] for name in models}
     for item in grid:
         for name, model in models.items():
             a = accuracy(model.predict(make_data(name, model, item)), labels)
             acc[name].append(a)
-            print(f"Accuracy on {what} test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
+            print(f"Accuracy on {what} test examples{_tag(name)}: {a * 100}% ({item})")
     return list(grid), {k: np.asarray(v) for k, v in acc.items()}
 
 
@@ -99,42 +104,10 @@ def _padded_rows(items, n_pad, lens):
     return A._to_dev(w), torch.as_tensor(lens).to(A._dev())
 
 
-def _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels, kind, standardize, test_filenames, domain, grid,
-                           points, limit, attack_kw):
-    """FGSM / PGD over the audio of ``test_filenames``; see white_box_sweep."""
-    if kind not in ("fgsm", "pgd"):
-        raise ValueError(f"over='audio' runs kind 'fgsm' and 'pgd', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
-    if test_filenames is None:
-        raise ValueError("attacks over audio need test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
-    if domain not in ("22k", "input"):
-        raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-    test_filenames = list(test_filenames[:limit] if limit else test_filenames)
-    labels = test_labels[:limit] if limit else test_labels
-    n_classes = labels.shape[1]
-    grid = list(AUDIO_SIGMAS if grid is None else grid)[:points]
-    work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
-    acc = {name: [] for name in models}
-    for item in grid:
-        for name, model in models.items():
-            pred = np.zeros((len(test_filenames), n_classes))
-            for sr, n, items, lens in work:
-                clf, x, lt = _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, lens)
-                idx = [i for i, _ in items]
-                cls = A.FastGradientMethod if kind == "fgsm" else A.ProjectedGradientDescent
-                adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x, None, lengths=lt) if item != 0 else x
-                pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
-            a = accuracy(pred, labels)
-            acc[name].append(a)
-            print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
-    return grid, {k: np.asarray(v) for k, v in acc.items()}
-
-
-def _audio_work(models, train_data, val_data, test_data, standardize, test_filenames):
+def _audio_work(models, train_data, val_data, test_filenames):
     """What the sweeps and read-outs over the audio of ``test_filenames`` share -> (work, scaler, bmax): the files grouped into
     batches [(rate, row length, [(file index, samples)], per-clip lengths or None)], and the StandardScaler fitted on (train, val,
-    the files' clean MFCCs)."""
-    if standardize == "before":
-        train_data, val_data, _ = A.standardize_dataset(train_data, val_data, test_data)
+    the files' clean MFCCs); train and val as _TestRows hands them on."""
     groups = A._files_to_batches(test_filenames)
     # A rate whose files differ in length goes through ONE extractor and one WaveformClassifier per model, the clips side by
     # side with lengths= (16 kHz and 8 kHz: the rates whose plans take per-clip lengths); rows are padded to the longest clip
@@ -186,6 +159,53 @@ def _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, lens):
     return clf, x, lt
 
 
+class _TestRows:
+    """What a sweep or read-out runs over, prepared once.  The arguments are refused in one order -- over="audio" without
+    ``test_filenames``, then ``domain``, then ``over`` -- before anything touches a device; ``limit`` keeps the first N rows / files;
+    standardize="before" standardises (train, val, test) once.  Afterwards: ``train_data`` / ``val_data`` (standardised if "before"),
+    ``n`` rows or files, ``what`` ("rows" | "files"), ``x`` (over="mfcc": the float32 NumPy rows) or ``filenames``, ``scaler`` and
+    ``bmax`` (over="audio": _audio_work's), and ``batches(model)``."""
+
+    def __init__(self, models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit):
+        if over == "audio":
+            if test_filenames is None:
+                raise ValueError("over='audio' needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
+            if domain not in ("22k", "input"):
+                raise ValueError(f"domain={domain!r}: '22k' or 'input'")
+        elif over != "mfcc":
+            raise ValueError("over must be 'audio' or 'mfcc'")
+        self.over, self.domain, self.limit, self.what = over, domain, limit, "files" if over == "audio" else "rows"
+        if standardize == "before":
+            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
+        self.train_data, self.val_data = train_data, val_data
+        if over == "audio":
+            self.filenames = list(self.limited(test_filenames))
+            self._work, self.scaler, self.bmax = _audio_work(models, train_data, val_data, self.filenames)
+            self.n = len(self.filenames)
+        else:
+            self.x = np.asarray(self.limited(test_data), dtype=np.float32)
+            self.n = len(self.x)
+
+    def limited(self, rows):
+        """The first ``limit`` of ``rows`` (labels, names: anything that goes row for row with the test set)."""
+        return rows[:self.limit] if self.limit else rows
+
+    def classifier(self, model):
+        """over="mfcc": the model as the reference wraps it (:500-504)."""
+        return A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(self.x.shape[1],),
+                                        loss_object=CategoricalCrossentropy())
+
+    def batches(self, model):
+        """Yields (estimator, x, lengths, idx): ``x`` are the rows ``idx`` of the test set as ``estimator`` takes them.  over="mfcc":
+        one batch, every row, as NumPy, no lengths; over="audio": one batch per entry of _audio_work, on the device."""
+        if self.over == "mfcc":
+            yield self.classifier(model), self.x, None, slice(None)
+            return
+        for sr, n, items, lens in self._work:
+            clf, x, lt = _audio_rows(model, model._n_classes, self.scaler, self.domain, self.bmax, sr, n, items, lens)
+            yield clf, x, lt, [i for i, _ in items]
+
+
 def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="fgsm", standardize="before", grid=None,
                     points=None, limit=None, over="mfcc", test_filenames=None, domain="22k", **attack_kw):
     """attacks.py:493-693.  The models are wrapped as TensorFlowV2Classifier(model=, nb_classes=, input_shape=,
@@ -196,16 +216,8 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
     the curve over black_box_sweep(over="audio", kind="simple").  Features are standardized with the statistics of (train, val,
     clean test MFCCs), fused into the extraction: the statistics black_box_sweep(over="audio") derives at sigma = 0, so the two
     sweeps agree at strength 0."""
-    if over == "audio":
-        return _white_box_audio_sweep(models, train_data, val_data, test_data, test_labels, kind, standardize, test_filenames, domain,
-                                      grid, points, limit, attack_kw)
-    if over != "mfcc":
-        raise ValueError("over must be 'audio' or 'mfcc'")
-    if standardize == "before":
-        train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
-    n_classes, n_in = test_labels.shape[1], test_data.shape[1]
-    clfs = {name: A.TensorFlowV2Classifier(model=m, nb_classes=n_classes, input_shape=(n_in,), loss_object=CategoricalCrossentropy())
-            for name, m in models.items()}
+    if over == "audio" and kind not in ("fgsm", "pgd"):
+        raise ValueError(f"over='audio' runs kind 'fgsm' and 'pgd', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
     if kind == "fgsm":
         default = np.linspace(1, 30, 50) if standardize == "after" else np.linspace(0.01, 0.3, 10)  # :497-499
         build = lambda clf, item: A.FastGradientMethod(estimator=clf, eps=item, **attack_kw)
@@ -223,13 +235,27 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
         build = lambda clf, item: A.CarliniL2Method(classifier=clf, confidence=item, **attack_kw)
     else:
         raise ValueError(f"unknown white-box attack {kind!r}")
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
+    labels = rows.limited(test_labels)
+    if over == "audio":
+        grid = list(AUDIO_SIGMAS if grid is None else grid)[:points]
+        acc = {name: [] for name in models}
+        for item in grid:
+            for name, model in models.items():
+                pred = np.zeros((rows.n, labels.shape[1]))
+                for clf, x, lt, idx in rows.batches(model):
+                    adv = build(clf, item).generate_device(x, None, lengths=lt) if item != 0 else x
+                    pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
+                a = accuracy(pred, labels)
+                acc[name].append(a)
+                print(f"Accuracy on adversarial audio test examples{_tag(name)}: {a * 100}% ({item})")
+        return grid, {k: np.asarray(v) for k, v in acc.items()}
     grid = list(default if grid is None else grid)[:points]
-    x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
-    labels = test_labels[:limit] if limit else test_labels
+    clfs = {name: rows.classifier(m) for name, m in models.items()}
 
     def make(name, clf, item):
-        adv = build(clf, item).generate(x=x)
-        return A.standardize_dataset(train_data, val_data, adv)[2] if standardize == "after" else adv
+        adv = build(clf, item).generate(x=rows.x)
+        return A.standardize_dataset(rows.train_data, rows.val_data, adv)[2] if standardize == "after" else adv
 
     return _sweep(clfs, grid, make, labels, "adversarial")
 
@@ -248,57 +274,35 @@ def genetic_sweep(models, train_data, val_data, test_data, test_labels, over="mf
     (default grid GENETIC_AUDIO_EPS, amplitudes; iterates stay in [-1, 1]).  ``attack_kw``: GeneticAttack's keywords (pop_size,
     max_iter, mutation_p, ...).  A query-only attack that ends BELOW the gradient attacks' accuracy at the same eps says that the
     gradients are masked.  Returns (grid, {model name: accuracies}, {model name: mean queries of the successful clips, nan if none})."""
-    if over not in ("audio", "mfcc"):
-        raise ValueError("over must be 'audio' or 'mfcc'")
-    acc, queries = {name: [] for name in models}, {name: [] for name in models}
-
-    def report(name, item, a, atk_stats):
-        ok, q = atk_stats
-        mean_q = float(np.mean(q[ok])) if ok.any() else float("nan")
-        acc[name].append(a)
-        queries[name].append(mean_q)
-        tag = "" if name == "constrained" else " " + name
-        print(f"Accuracy on genetic black-box {'audio ' if over == 'audio' else ''}test examples{tag}: {a * 100}% ({item}); "
-              f"{int(ok.sum())} of {len(ok)} clips succeeded, mean queries of those: {mean_q}")
-
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
+    labels = rows.limited(test_labels)
     if over == "audio":
-        if test_filenames is None:
-            raise ValueError("attacks over audio need test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
-        if domain not in ("22k", "input"):
-            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
-        labels = test_labels[:limit] if limit else test_labels
-        n_classes = labels.shape[1]
-        grid = list(GENETIC_AUDIO_EPS if grid is None else grid)[:points]
-        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
-        for item in grid:
-            for name, model in models.items():
-                pred = np.zeros((len(test_filenames), n_classes))
-                ok, q = np.zeros(len(test_filenames), dtype=bool), np.zeros(len(test_filenames), dtype=np.int64)
-                for sr, n, items, lens in work:
-                    clf, x, lt = _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, lens)
-                    idx = [i for i, _ in items]
-                    atk = A.GeneticAttack(clf, item, **attack_kw)
+        default = GENETIC_AUDIO_EPS
+    else:
+        default = np.linspace(1, 30, 50) if standardize == "after" else np.linspace(0.01, 0.3, 10)  # white_box_sweep's FGSM grid
+    grid = list(default if grid is None else grid)[:points]
+    acc, queries = {name: [] for name in models}, {name: [] for name in models}
+    for item in grid:
+        for name, model in models.items():
+            pred = np.zeros((rows.n, labels.shape[1]))
+            ok, q = np.zeros(rows.n, dtype=bool), np.zeros(rows.n, dtype=np.int64)
+            for clf, x, lt, idx in rows.batches(model):
+                atk = A.GeneticAttack(clf, item, **attack_kw)
+                if over == "audio":
                     adv = atk.generate_device(x, None, lengths=lt)
                     pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
-                    ok[idx], q[idx] = atk.success_.cpu().numpy(), atk.queries_.cpu().numpy()
-                report(name, item, accuracy(pred, labels), (ok, q))
-    else:
-        if standardize == "before":
-            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
-        n_classes, n_in = test_labels.shape[1], test_data.shape[1]
-        default = np.linspace(1, 30, 50) if standardize == "after" else np.linspace(0.01, 0.3, 10)  # white_box_sweep's FGSM grid
-        grid = list(default if grid is None else grid)[:points]
-        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
-        labels = test_labels[:limit] if limit else test_labels
-        for item in grid:
-            for name, model in models.items():
-                clf = A.TensorFlowV2Classifier(model=model, nb_classes=n_classes, input_shape=(n_in,), loss_object=CategoricalCrossentropy())
-                atk = A.GeneticAttack(clf, item, **attack_kw)
-                adv = atk.generate(x)
-                if standardize == "after":
-                    adv = A.standardize_dataset(train_data, val_data, adv)[2]
-                report(name, item, accuracy(model.predict(adv), labels), (atk.success_.cpu().numpy(), atk.queries_.cpu().numpy()))
+                else:  # NumPy rows in and out, standardised where the deployed pipeline does it, classified by the model itself
+                    adv = atk.generate(x)
+                    if standardize == "after":
+                        adv = A.standardize_dataset(rows.train_data, rows.val_data, adv)[2]
+                    pred[idx] = model.predict(adv)
+                ok[idx], q[idx] = atk.success_.cpu().numpy(), atk.queries_.cpu().numpy()
+            a = accuracy(pred, labels)
+            mean_q = float(np.mean(q[ok])) if ok.any() else float("nan")
+            acc[name].append(a)
+            queries[name].append(mean_q)
+            print(f"Accuracy on genetic black-box {'audio ' if over == 'audio' else ''}test examples{_tag(name)}: {a * 100}% ({item}); "
+                  f"{int(ok.sum())} of {len(ok)} clips succeeded, mean queries of those: {mean_q}")
     return grid, {k: np.asarray(v) for k, v in acc.items()}, {k: np.asarray(v) for k, v in queries.items()}
 
 
@@ -359,7 +363,7 @@ def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_fil
         for name, model in models.items():
             a = accuracy(model.predict(x), labels)
             acc[name].append(a)
-            print(f"Accuracy on DolphinAttack recordings{'' if name == 'constrained' else ' ' + name}: {a * 100}% (carrier level {item})")
+            print(f"Accuracy on DolphinAttack recordings{_tag(name)}: {a * 100}% (carrier level {item})")
     return grid, {k: np.asarray(v) for k, v in acc.items()}
 
 
@@ -370,21 +374,16 @@ def imperceptible_report(models, train_data, val_data, test_data, test_labels, t
     stands above what the clip itself masks -- and the mean perturbation SNR in dB.  Files are grouped by (rate, length); features
     are standardised as white_box_sweep(over="audio") does.  ``eps`` and the learning rates are amplitudes and have no defaults.
     Returns {model name: {"success", "loss_theta_1", "loss_theta_2", "snr_db", "rows": per-file arrays}}."""
-    if test_filenames is None:
-        raise ValueError("attacks over audio need test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
-    if domain not in ("22k", "input"):
-        raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-    test_filenames = list(test_filenames[:limit] if limit else test_filenames)
-    labels = np.asarray(test_labels[:limit] if limit else test_labels)
+    prep = _TestRows(models, train_data, val_data, test_data, "audio", standardize, test_filenames, domain, limit)
+    labels = np.asarray(prep.limited(test_labels))
     n_classes = labels.shape[1]
     targets = A.random_targets(labels, n_classes, rng=np.random.RandomState(seed)).astype(np.float32)
-    _, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
-    groups = A._files_to_batches(test_filenames)
+    groups = A._files_to_batches(prep.filenames)  # by (rate, length) and without lengths: the masker takes clips of one length
     out = {}
     for name, model in models.items():
-        rows = {k: np.zeros(len(test_filenames)) for k in ("success", "loss_theta_1", "loss_theta_2", "snr_db")}
+        rows = {k: np.zeros(prep.n) for k in ("success", "loss_theta_1", "loss_theta_2", "snr_db")}
         for (sr, n), items in groups.items():
-            clf, x, _ = _audio_rows(model, n_classes, sc, domain, bmax, sr, n, items, None)
+            clf, x, _ = _audio_rows(model, n_classes, prep.scaler, domain, prep.bmax, sr, n, items, None)
             idx = [i for i, _ in items]
             atk = A.ImperceptibleASR(clf, eps=eps, learning_rate_1=learning_rate_1, learning_rate_2=learning_rate_2, **attack_kw)
             adv = atk.generate_device(x, A._to_dev(targets[idx]))
@@ -397,8 +396,8 @@ def imperceptible_report(models, train_data, val_data, test_data, test_labels, t
         r = {k: float(np.mean(v[np.isfinite(v)])) if np.isfinite(v).any() else float("nan") for k, v in rows.items()}
         r["rows"] = rows
         out[name] = r
-        tag = "" if name == "constrained" else " " + name
-        print(f"Targeted success rate of the imperceptible attack{tag}: {r['success'] * 100}% over {len(test_filenames)} files")
+        tag = _tag(name)
+        print(f"Targeted success rate of the imperceptible attack{tag}: {r['success'] * 100}% over {prep.n} files")
         print(f"Mean masking loss L_theta{tag}: {r['loss_theta_1']} after stage 1, {r['loss_theta_2']} after stage 2")
         print(f"Mean perturbation SNR{tag}: {r['snr_db']} dB")
     return out
@@ -415,37 +414,19 @@ def lipschitz_report(models, train_data, val_data, test_data, over="mfcc", stand
     over="audio": with respect to the audio of ``test_filenames``, the 22 050 Hz signal (domain="22k") or the file's own samples
     (domain="input"), files grouped and features standardised as white_box_sweep(over="audio") does.  limit: the first N rows /
     files.  Returns {model name: {"upper", "constrained", "max", "mean", "median", "local": the per-row float64 array}}."""
-    if over == "audio":
-        if test_filenames is None:
-            raise ValueError("the read-out over audio needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
-        if domain not in ("22k", "input"):
-            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
-        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
-    elif over == "mfcc":
-        if standardize == "before":
-            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
-        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
-    else:
-        raise ValueError("over must be 'audio' or 'mfcc'")
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
     out = {}
     for name, model in models.items():
-        if over == "mfcc":
-            clf = A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(x.shape[1],),
-                                           loss_object=CategoricalCrossentropy())
-            local = get_local_lipschitz(clf, x)
-        else:
-            local = np.zeros(len(test_filenames))
-            for sr, n, items, lens in work:
-                clf, rows, lt = _audio_rows(model, model._n_classes, sc, domain, bmax, sr, n, items, lens)
-                local[[i for i, _ in items]] = get_local_lipschitz(clf, rows, lengths=lt)
+        local = np.zeros(rows.n)
+        for clf, x, lt, idx in rows.batches(model):
+            local[idx] = get_local_lipschitz(clf, x, lengths=lt)
         r = {"upper": float(get_upper_lipschitz(get_norms(model))), "constrained": float(get_lipschitz_constrained(model)),
              "max": float(local.max()), "mean": float(local.mean()), "median": float(np.median(local)), "local": local}
         out[name] = r
-        tag = "" if name == "constrained" else " " + name
+        tag = _tag(name)
         print(f"Upper Lipschitz bound{tag}: {r['upper']}")
         print(f"Lipschitz constant with the BatchNorm correction{tag}: {r['constrained']}")
-        print(f"Local Lipschitz constant over {len(local)} test {'rows' if over == 'mfcc' else 'files'}{tag}: "
+        print(f"Local Lipschitz constant over {len(local)} test {rows.what}{tag}: "
               f"max {r['max']} mean {r['mean']} median {r['median']}")
     return out
 
@@ -458,41 +439,25 @@ def radius_report(models, train_data, val_data, test_data, over="mfcc", standard
     lipschitz_report; ``norm``: 2 or np.inf; deepfool_kw go to attacks.DeepFool.
     Returns {model name: {"bound": get_lipschitz_bound(model), "margin", "certified" (or None), "linear", "found", "flipped": the
     per-row arrays, "quartiles": {name: (q25, q50, q75)}, "flipped_share"}}."""
-    if over == "audio":
-        if test_filenames is None:
-            raise ValueError("the read-out over audio needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
-        if domain not in ("22k", "input"):
-            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
-        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
-    elif over == "mfcc":
-        if standardize == "before":
-            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
-        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
-    else:
-        raise ValueError("over must be 'audio' or 'mfcc'")
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
     keys = ("margin", "certified", "linear", "found", "flipped")
     out = {}
     for name, model in models.items():
-        if over == "mfcc":
-            clf = A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(x.shape[1],),
-                                           loss_object=CategoricalCrossentropy())
-            r = get_robustness_radius(clf, x, norm=norm, **deepfool_kw)
-        else:
-            r = {k: np.zeros(len(test_filenames), dtype=bool if k == "flipped" else np.float64) for k in keys}
-            r["certified"] = None
-            for sr, n, items, lens in work:
-                clf, rows, lt = _audio_rows(model, model._n_classes, sc, domain, bmax, sr, n, items, lens)
-                part = get_robustness_radius(clf, rows, norm=norm, lengths=lt, **deepfool_kw)
-                for k in ("margin", "linear", "found", "flipped"):
-                    r[k][[i for i, _ in items]] = part[k]
+        r = {k: np.zeros(rows.n, dtype=bool if k == "flipped" else np.float64) for k in keys}
+        for clf, x, lt, idx in rows.batches(model):
+            part = get_robustness_radius(clf, x, norm=norm, lengths=lt, **deepfool_kw)
+            for k in keys:
+                if part[k] is None:  # no certified radius over audio, nor in norm inf
+                    r[k] = None
+                else:
+                    r[k][idx] = part[k]
         r["bound"] = float(get_lipschitz_bound(model))
         r["quartiles"] = {k: tuple(float(q) for q in np.percentile(r[k], (25, 50, 75))) for k in ("certified", "linear", "found")
                           if r[k] is not None and len(r[k])}
         r["flipped_share"] = float(np.mean(r["flipped"])) if len(r["flipped"]) else float("nan")
         out[name] = r
-        tag = "" if name == "constrained" else " " + name
-        what = f"{len(r['found'])} test {'rows' if over == 'mfcc' else 'files'}"
+        tag = _tag(name)
+        what = f"{len(r['found'])} test {rows.what}"
         print(f"Lipschitz bound of the logits{tag}: {r['bound']}")
         for k, label in (("certified", "Certified radius"), ("linear", "Distance to the linearised boundary"), ("found", "Distance DeepFool found")):
             if k in r["quartiles"]:
@@ -521,55 +486,43 @@ def smooth_report(models, train_data, val_data, test_data, test_labels, sigma, n
 
     if not (float(sigma) >= 0.0 and np.isfinite(float(sigma))):
         raise ValueError(f"sigma = {sigma}: a finite, non-negative number is required")
-    if over == "audio":
-        if test_filenames is None:
-            raise ValueError("the read-out over audio needs test_filenames (test_dataset_to_add_noise/test_filenames.npy)")
-        if domain not in ("22k", "input"):
-            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-        test_filenames = list(test_filenames[:limit] if limit else test_filenames)
-        work, sc, bmax = _audio_work(models, train_data, val_data, test_data, standardize, test_filenames)
-    elif over == "mfcc":
-        if standardize == "before":
-            train_data, val_data, test_data = A.standardize_dataset(train_data, val_data, test_data)
-        x = np.asarray(test_data[:limit] if limit else test_data, dtype=np.float32)
-    else:
-        raise ValueError("over must be 'audio' or 'mfcc'")
-    truth = np.asarray(test_labels[:limit] if limit else test_labels).argmax(axis=1)
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
+    truth = np.asarray(rows.limited(test_labels)).argmax(axis=1)
     radii = np.asarray([f * float(sigma) for f in SMOOTH_RADII] if radii is None else radii, dtype=np.float64)
     kw = dict(n0=n0, n=n, alpha=alpha)
     out = {}
     for name, model in models.items():
+        r = {"radius": np.zeros(rows.n), "class": np.full(rows.n, -1, dtype=np.int64), "p_lower": np.zeros(rows.n)}
+        for clf, x, lt, idx in rows.batches(model):
+            part = Smooth(clf, sigma, seed=seed).certify(x, lengths=lt, **kw)
+            for k in r:
+                r[k][idx] = part[k]
         lip = None
-        if over == "mfcc":
-            clf = A.TensorFlowV2Classifier(model=model, nb_classes=model._n_classes, input_shape=(x.shape[1],),
-                                           loss_object=CategoricalCrossentropy())
-            r = Smooth(clf, sigma, seed=seed).certify(x, **kw)
-            if name == "constrained" and len(x) and model._n_classes > 1:
-                top = torch.topk(model.predict_device(A._to_dev(x), logits=True).double(), 2, dim=1).values
-                lip = float(np.median((top[:, 0] - top[:, 1]).cpu().numpy() / (np.sqrt(2.0) * get_lipschitz_bound(model))))
-        else:
-            r = {"radius": np.zeros(len(test_filenames)), "class": np.full(len(test_filenames), -1, dtype=np.int64),
-                 "p_lower": np.zeros(len(test_filenames))}
-            for sr, n_samp, items, lens in work:
-                clf, rows, lt = _audio_rows(model, model._n_classes, sc, domain, bmax, sr, n_samp, items, lens)
-                part = Smooth(clf, sigma, seed=seed).certify(rows, lengths=lt, **kw)
-                for k in r:
-                    r[k][[i for i, _ in items]] = part[k]
-        r = {k: r[k] for k in ("radius", "class", "p_lower")}
+        if over == "mfcc" and name == "constrained" and rows.n and model._n_classes > 1:
+            top = torch.topk(model.predict_device(A._to_dev(rows.x), logits=True).double(), 2, dim=1).values
+            lip = float(np.median((top[:, 0] - top[:, 1]).cpu().numpy() / (np.sqrt(2.0) * get_lipschitz_bound(model))))
         hit = r["class"] == truth[:len(r["class"])]
         r["radii"] = radii
         r["certified_accuracy"] = np.array([float(np.mean(hit & (r["radius"] >= q))) if len(hit) else float("nan") for q in radii])
         r["abstained"] = float(np.mean(r["class"] < 0)) if len(hit) else float("nan")
         r["lipschitz_median"] = lip
         out[name] = r
-        tag = "" if name == "constrained" else " " + name
-        what = f"{len(hit)} test {'rows' if over == 'mfcc' else 'files'}"
+        tag = _tag(name)
+        what = f"{len(hit)} test {rows.what}"
         for q, a in zip(radii, r["certified_accuracy"]):
             print(f"Certified accuracy of the smoothed classifier (sigma {sigma}) over {what}{tag} at L2 radius {q}: {a * 100}%")
         print(f"Share of {what} on which the smoothed classifier abstains{tag}: {r['abstained'] * 100}%")
         if lip is not None:
             print(f"Median radius the Lipschitz bound certifies for the base classifier over {what}{tag}: {lip}")
     return out
+
+
+def _noise_files(noise_dir, n_classes):
+    """The files the dataset construction set aside for the audio attacks (:298-304) -> (file names, their one-hot labels)."""
+    import os
+
+    return (np.load(os.path.join(noise_dir, "test_filenames.npy")).tolist(),
+            to_categorical(np.load(os.path.join(noise_dir, "test_label.npy")), n_classes))
 
 
 def main(argv=None):
@@ -596,8 +549,6 @@ def main(argv=None):
     ap.add_argument("--max-iter-1", type=int, default=1000)
     ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
-    import os
-
     if args.attack == "radius" and args.norm == "1":
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
 
@@ -608,10 +559,10 @@ def main(argv=None):
     n_classes = int(test_label.max()) + 1
     labels = to_categorical(test_label, n_classes)
     models = {"constrained": load_model(args.constrained), "unconstrained": load_model(args.unconstrained)}
+    names = None
+    if args.over == "audio" or args.attack == "dolphin":
+        names, labels = _noise_files(args.noise_dir, n_classes)
     if args.attack == "black":
-        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
-        if names is not None:
-            labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)  # :298-304
         if args.kind == "genetic":
             kw = {k: v for k, v in (("pop_size", args.pop_size), ("max_iter", args.max_iter)) if v is not None}
             return genetic_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
@@ -619,37 +570,27 @@ def main(argv=None):
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
     if args.attack == "lipschitz":
-        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
         return lipschitz_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
                                 test_filenames=names)
     if args.attack == "radius":
-        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
         return radius_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
                              test_filenames=names, norm=np.inf if args.norm == "inf" else 2, limit=args.points)
     if args.attack == "smooth":
-        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist() if args.over == "audio" else None
-        if names is not None:
-            labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
         return smooth_report(models, train_data, val_data, test_data, labels, args.sigma, n0=args.n0, n=args.n, alpha=args.alpha,
                              over=args.over, standardize=args.standardize, test_filenames=names, limit=args.points)
     if args.attack == "dolphin":
-        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
-        labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
         return dolphin_sweep(models, train_data, val_data, test_data, labels, names, standardize=args.standardize, points=args.points)
     if args.kind == "imperceptible":
         if args.over != "audio":
             raise ValueError("--kind imperceptible perturbs audio: give --over audio")
         if args.eps is None or args.learning_rate_1 is None or args.learning_rate_2 is None:
             raise ValueError("--kind imperceptible needs --eps, --learning-rate-1 and --learning-rate-2 (amplitudes; there are no defaults)")
-        names = np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist()
-        labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
         return imperceptible_report(models, train_data, val_data, test_data, labels, names, args.eps, args.learning_rate_1,
                                     args.learning_rate_2, standardize=args.standardize, limit=args.points, max_iter_1=args.max_iter_1,
                                     max_iter_2=args.max_iter_2)
     kw = {}
     if args.over == "audio":
-        kw.update(over="audio", test_filenames=np.load(os.path.join(args.noise_dir, "test_filenames.npy")).tolist())
-        labels = to_categorical(np.load(os.path.join(args.noise_dir, "test_label.npy")), n_classes)
+        kw.update(over="audio", test_filenames=names)
     if args.norm != "inf":
         if args.kind not in ("fgsm", "pgd"):
             raise ValueError("--norm applies to --kind fgsm and pgd")

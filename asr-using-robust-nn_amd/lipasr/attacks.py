@@ -7,6 +7,9 @@ predictions, no clip_values).  Each PGD iteration is ONE native call: inference 
 backward to the input and the sign step fused into the last backward GEMM's epilogue (K4).  ART's other
 ``norm`` (1, 2), ``targeted`` and ``num_random_init`` keywords run the same call in its Lp form
 (lipasr_mlp_attack_step_lp: the step is a second launch) and a native random start (lipasr_lp_ball_init).
+The estimators live in lipasr/estimators.py (re-exported here under the same names); an attack asks its estimator for everything
+that depends on what the rows are -- shape, lengths, predictions, own labels, gradients.  The one choice made here is FGM / PGD's:
+over rows of features they run the fused native iteration, over audio the estimator's gradient and a step launch.
 ``WaveformClassifier`` puts the MFCC stage in front of the model: the same two attacks then perturb the AUDIO (eps in
 amplitude units), the gradient reaching the samples through the native backward pass of K1 (lipasr_mfcc_plan_vjp).  With
 ``lengths=`` a batch holds clips of different lengths, one per row (lipasr_mfcc_plan_vjp_ragged): the perturbation stays inside
@@ -25,17 +28,10 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .extract_features_construct_dataset import MfccExtractor, read_wav, _extractor
-from .keras import Model, to_categorical
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_dev(x):
-    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    return t.to(device=_dev(), dtype=torch.float32).contiguous()
+from .estimators import TensorFlowV2Classifier, WaveformClassifier, _as_given, _dev, _Estimator, _to_dev
+from .extract_features_construct_dataset import read_wav, _extractor
+from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack: scores only; lipasr/genetic.py)
+from .keras import to_categorical
 
 
 # ------------------------------------------------------------------------------------------------ A2
@@ -75,241 +71,6 @@ def standardize_dataset(train_data, val_data, test_data):
     if torch.is_tensor(train_data):
         return res
     return tuple(r.cpu().numpy() for r in res)
-
-
-# ------------------------------------------------------------------------------------------------ A9 / A10
-class TensorFlowV2Classifier:
-    """ART estimator wrapper (attacks.py:500-504): ``predict`` and ``loss_gradient`` over a lipasr Model."""
-
-    def __init__(self, model, nb_classes, input_shape, loss_object=None, clip_values=None):
-        if not isinstance(model, Model):
-            raise TypeError("model must be a lipasr.keras.Model")
-        if clip_values is not None:
-            raise NotImplementedError("the reference passes no clip_values")
-        self.model, self.nb_classes, self.input_shape = model, int(nb_classes), tuple(input_shape)
-        if model._n_classes != self.nb_classes or model._widths[0] != self.input_shape[0]:
-            raise ValueError("nb_classes / input_shape do not match the model")
-
-    @property
-    def batch_limit(self):
-        """Rows one native call takes (the model's max_batch)."""
-        return self.model._max_batch
-
-    def predict(self, x, batch_size=128):
-        return self.model.predict(x)
-
-    def loss_gradient(self, x, y):
-        """d mean CE(f(x), y) / dx in inference mode, NumPy in / NumPy out."""
-        m = self.model
-        xt, yt = _to_dev(x), _to_dev(y)
-        out = torch.empty_like(xt)
-        bs = m._max_batch
-        for s in range(0, xt.shape[0], bs):
-            xb, yb, ob = xt[s:s + bs], yt[s:s + bs], out[s:s + bs]
-            N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), N.ptr(yb), xb.shape[0], N.ptr(ob), N.stream_ptr()))
-        return out.cpu().numpy()
-
-    def output_vjp_device(self, xt, vt, on_logits=False, probs_out=None):
-        """sum_c v[b, c] d out_c / dx on device tensors ([B, features], [B, classes]) -> [B, features]."""
-        m = self.model
-        out = torch.empty_like(xt)
-        bs = m._max_batch
-        for s in range(0, xt.shape[0], bs):
-            xb, vb, ob = xt[s:s + bs], vt[s:s + bs], out[s:s + bs]
-            pb = None if probs_out is None else probs_out[s:s + bs]
-            N.check(N.lib.lipasr_mlp_output_vjp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), N.ptr(vb), 1 if on_logits else 0,
-                                                xb.shape[0], N.ptr(pb), N.ptr(ob), N.stream_ptr()))
-        return out
-
-    def jacobian_device(self, xt, on_logits=True, probs_out=None):
-        """d out_c / dx for every class on a device tensor [B, features] -> [B, classes, features] (lipasr_mlp_jacobian: ONE forward
-        pass per batch, then one backward chain per class; row c is what ``output_vjp_device`` gives for the one-hot vector e_c).
-        probs_out: optional [B, classes] tensor that receives softmax(f(x))."""
-        m = self.model
-        xt = xt.contiguous()
-        c, n = self.nb_classes, xt.shape[1]
-        out = torch.empty(xt.shape[0], c, n, device=xt.device)
-        bs = m._max_batch
-        for s in range(0, xt.shape[0], bs):
-            xb, ob = xt[s:s + bs], out[s:s + bs]
-            pb = None if probs_out is None else probs_out[s:s + bs]
-            N.check(N.lib.lipasr_mlp_jacobian(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), 1 if on_logits else 0, xb.shape[0],
-                                              N.ptr(pb), N.ptr(ob), c * n, n, N.stream_ptr()))
-        return out
-
-    def class_gradient(self, x, label=None):
-        """ART class_gradient: gradients of the model OUTPUT (softmax probabilities) w.r.t. x.
-        label None -> [B, nb_classes, features]; int or int array [B] -> [B, 1, features]."""
-        xt = _to_dev(x)
-        b = xt.shape[0]
-        if label is None:
-            cols = []
-            for c in range(self.nb_classes):
-                v = torch.zeros(b, self.nb_classes, device=xt.device)
-                v[:, c] = 1.0
-                cols.append(self.output_vjp_device(xt, v))
-            return torch.stack(cols, dim=1).cpu().numpy()
-        lab = torch.as_tensor(np.broadcast_to(np.asarray(label), (b,)).astype(np.int64), device=xt.device)
-        v = torch.zeros(b, self.nb_classes, device=xt.device)
-        v[torch.arange(b, device=xt.device), lab] = 1.0
-        return self.output_vjp_device(xt, v)[:, None, :].cpu().numpy()
-
-
-class WaveformClassifier:
-    """Estimator over audio: waveform -> MFCC (K1) -> optional StandardScaler affine -> model.  ``loss_gradient`` follows
-    TensorFlowV2Classifier.loss_gradient's convention (lipasr_mlp_input_grad: d mean CE / d features in inference mode) and
-    carries it to the samples with the backward pass of the MFCC stage (MfccExtractor.vjp).
-    domain="22k" (default): the input is the 22 050 Hz signal [B, extractor.n_y], what the reference's audio noise attacks
-    perturb (librosa.load's output, attacks.py:108-114), so that black-box and white-box audio curves share an amplitude axis;
-    domain="input": the file's samples [B, n_samp] at ``sr_in``.  ``mean`` / ``scale``: [20 * utterance_length] statistics
-    fused into the extraction (both or neither).  ``clip_values``: the attacks clamp their iterates to it.
-    ``lengths`` (features_device, predict*, loss_gradient*): int32 device tensor or array [B], the samples of each row that belong
-    to its clip, counted at ``sr_in`` for EITHER domain (a 22 050 Hz row holds its clip in its first ceil(n * 22050 / sr_in)
-    positions): clips of different lengths in one batch, each treated as if it were alone; the rest of a row is ignored and its
-    gradient is exactly 0.  None: every row is a whole clip, and every call is the one made without the keyword.
-    A short-window extractor (``MfccExtractor(..., n_fft=441, hop=220)``, the Speaker-recognition features) sends the gradient
-    through ``MfccExtractor.vjp_short``; it has no per-clip lengths (``lengths=`` raises ValueError)."""
-
-    def __init__(self, model, nb_classes, extractor=None, sr_in=16000, n_samp=16000, utterance_length=44, mean=None, scale=None,
-                 domain="22k", clip_values=(-1.0, 1.0)):
-        if not isinstance(model, Model):
-            raise TypeError("model must be a lipasr.keras.Model")
-        if domain not in ("22k", "input"):
-            raise ValueError(f"domain={domain!r}: '22k' or 'input'")
-        if (mean is None) != (scale is None):
-            raise ValueError("give both mean and scale or neither")
-        self.model, self.nb_classes, self.utterance_length, self.domain = model, int(nb_classes), int(utterance_length), domain
-        self.extractor = extractor if extractor is not None else MfccExtractor(sr_in, n_samp, batch_max=model._max_batch, device=model._device)
-        self.n = self.extractor.n_y if domain == "22k" else self.extractor.n_samp
-        self.input_shape = (self.n,)
-        n_feat = 20 * self.utterance_length
-        if model._n_classes != self.nb_classes or model._widths[0] != n_feat:
-            raise ValueError("nb_classes / utterance_length do not match the model")
-        dev = self.extractor.device
-        as64 = lambda v: None if v is None else torch.as_tensor(v).to(device=dev, dtype=torch.float64).contiguous().reshape(-1)
-        self.mean, self.scale = as64(mean), as64(scale)
-        if self.mean is not None and (self.mean.numel() != n_feat or self.scale.numel() != n_feat):
-            raise ValueError(f"mean and scale must have {n_feat} elements")
-        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
-        self._bs = min(model._max_batch, self.extractor.batch_max)
-
-    @property
-    def batch_limit(self):
-        """Rows one native call takes (the smaller of the model's and the extractor's)."""
-        return self._bs
-
-    def _check(self, xt):
-        if xt.dim() != 2 or xt.shape[1] != self.n:
-            raise ValueError(f"waveforms must be [B, {self.n}] for domain {self.domain!r}, got {tuple(xt.shape)}")
-
-    def lengths_device(self, lengths, b):
-        """``lengths`` as the int32 device tensor [b] the extractor takes (None stays None)."""
-        if lengths is None:
-            return None
-        if self.extractor.short_window:
-            raise ValueError("lengths=: a short-window extractor takes rows of one length (there is no per-clip-length short-window path)")
-        t = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths).astype(np.int32))
-        t = t.to(device=self.extractor.device, dtype=torch.int32).contiguous()
-        if tuple(t.shape) != (b,):
-            raise ValueError(f"lengths must hold one sample count per row ([{b}]), got {tuple(t.shape)}")
-        return t
-
-    def clip_mask(self, lt):
-        """bool [B, n]: the positions of each row inside its clip -- [0, n) samples (domain "input"), or the [0, ceil(n * 22050 /
-        sr_in)) positions the kernels derive from it (domain "22k", the same float64 expression as clip_lengths)."""
-        ex = self.extractor
-        n = lt.clamp(0, ex.n_samp)
-        if self.domain == "22k":
-            n = torch.ceil(n.to(torch.float64) * (22050.0 / float(ex.sr_in))).to(torch.int32)
-        return torch.arange(self.n, device=lt.device, dtype=torch.int32)[None, :] < n[:, None]
-
-    def features_device(self, xt, lengths=None):
-        """[B <= batch_max, n] device tensor -> standardised features [B, 20 * utterance_length]."""
-        if lengths is not None:
-            lengths = self.lengths_device(lengths, xt.shape[0])
-        if self.domain == "22k":
-            return self.extractor.from_22k(xt, self.utterance_length, self.mean, self.scale, n_valid=lengths)
-        return self.extractor(xt, self.utterance_length, self.mean, self.scale, n_valid=lengths)
-
-    def predict_device(self, xt, logits=False, lengths=None):
-        self._check(xt)
-        lt = self.lengths_device(lengths, xt.shape[0])
-        return torch.cat([self.model.predict_device(self.features_device(xt[s:s + self._bs].contiguous(),
-                                                                         None if lt is None else lt[s:s + self._bs]), logits=logits)
-                          for s in range(0, xt.shape[0], self._bs)])
-
-    def predict(self, x, batch_size=128, lengths=None):
-        return self.predict_device(_to_dev(x), lengths=lengths).cpu().numpy()
-
-    def loss_gradient_device(self, xt, yt, out=None, lengths=None):
-        """d mean CE(f(features(x)), y) / dx on device tensors ([B, n], one-hot [B, classes]) -> [B, n]."""
-        self._check(xt)
-        m, ex = self.model, self.extractor
-        out = torch.empty_like(xt) if out is None else out
-        lt = self.lengths_device(lengths, xt.shape[0])
-        for s in range(0, xt.shape[0], self._bs):
-            xb, yb, ob = xt[s:s + self._bs], yt[s:s + self._bs], out[s:s + self._bs]
-            lb = None if lt is None else lt[s:s + self._bs]
-            f = self.features_device(xb, lb)
-            gf = torch.empty_like(f)
-            N.check(N.lib.lipasr_mlp_input_grad(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(yb), xb.shape[0], N.ptr(gf), N.stream_ptr()))
-            self._features_vjp(xb, gf, lb, ob)
-        return out
-
-    def _features_vjp(self, xb, gf, lb, ob):
-        """The feature cotangent ``gf`` carried back to the rows ``xb`` whose features this extractor has just computed (its last
-        call on the current stream), into ``ob``: the backward pass that matches the extractor and ``lb``."""
-        ex = self.extractor
-        if ex.short_window:
-            ex.vjp_short(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
-        elif lb is None:
-            ex.vjp(xb, gf, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
-        else:
-            ex.vjp_ragged(xb, gf, lb, self.utterance_length, self.scale, domain=self.domain, reuse_forward=True, out=ob)
-
-    def output_vjp_device(self, xt, vt, on_logits=False, lengths=None):
-        """sum_c v[b, c] d out_c / dx on device tensors ([B, n], [B, classes]) -> [B, n]: TensorFlowV2Classifier.output_vjp_device
-        with the MFCC stage in front (extraction, lipasr_mlp_output_vjp, the backward pass of the extraction)."""
-        self._check(xt)
-        m = self.model
-        xt, vt = xt.contiguous(), vt.contiguous()
-        out = torch.empty_like(xt)
-        lt = self.lengths_device(lengths, xt.shape[0])
-        for s in range(0, xt.shape[0], self._bs):
-            xb, vb, ob = xt[s:s + self._bs], vt[s:s + self._bs], out[s:s + self._bs]
-            lb = None if lt is None else lt[s:s + self._bs]
-            f = self.features_device(xb, lb)
-            gf = torch.empty_like(f)
-            N.check(N.lib.lipasr_mlp_output_vjp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), N.ptr(vb), 1 if on_logits else 0,
-                                                xb.shape[0], None, N.ptr(gf), N.stream_ptr()))
-            self._features_vjp(xb, gf, lb, ob)
-        return out
-
-    def jacobian_device(self, xt, on_logits=True, lengths=None):
-        """d out_c / dx for every class on a device tensor [B, n] -> a [B, classes, n] view of class-major storage.  Per batch: ONE
-        extraction, ONE lipasr_mlp_jacobian into [classes][B][features] (the MFCC backward takes contiguous [B, features]
-        cotangents), then one backward pass of the MFCC stage per class on the intermediates the extraction left: the backward
-        chain only reads them, so they serve every class.  Row c carries the bits of ``output_vjp_device`` with the one-hot e_c."""
-        self._check(xt)
-        m = self.model
-        xt = xt.contiguous()
-        b_all, c = xt.shape[0], self.nb_classes
-        lt = self.lengths_device(lengths, b_all)
-        out = torch.empty(c, b_all, self.n, device=xt.device)
-        for s in range(0, b_all, self._bs):
-            xb = xt[s:s + self._bs]
-            lb = None if lt is None else lt[s:s + self._bs]
-            f = self.features_device(xb, lb)
-            b, nf = f.shape
-            jf = torch.empty(c, b, nf, device=xt.device)
-            N.check(N.lib.lipasr_mlp_jacobian(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(f), 1 if on_logits else 0, b, None,
-                                              N.ptr(jf), nf, b * nf, N.stream_ptr()))
-            for k in range(c):
-                self._features_vjp(xb, jf[k], lb, out[k, s:s + b])
-        return out.permute(1, 0, 2)
-
-    def loss_gradient(self, x, y, lengths=None):
-        return self.loss_gradient_device(_to_dev(x), _to_dev(y), lengths=lengths).cpu().numpy()
 
 
 def random_targets(labels, nb_classes, rng=None):
@@ -374,7 +135,7 @@ class SaliencyMapMethod:
                 cur = m.predict_device(batch.contiguous()).argmax(dim=1)
                 active = torch.nonzero((cur != tgt) & (all_feat.sum(dim=1) / nf <= self.gamma))[:, 0]
                 it += 1
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        return _as_given(adv, x)
 
 
 _TANH_SMOOTHER = 0.999999
@@ -422,15 +183,7 @@ class _Carlini:
         return self.estimator.output_vjp_device(xa.contiguous(), v)
 
     def _labels(self, xt, y):
-        if y is not None:
-            return _to_dev(y)
-        m = self.estimator.model
-        yb = torch.empty(xt.shape[0], m._n_classes, device=xt.device)
-        bs = m._max_batch
-        for s in range(0, xt.shape[0], bs):
-            N.check(N.lib.lipasr_mlp_own_labels(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xt[s:s + bs]), xt[s:s + bs].shape[0],
-                                                N.ptr(yb[s:s + bs]), N.stream_ptr()))
-        return yb
+        return _to_dev(y) if y is not None else self.estimator.own_labels_device(xt)
 
     def _line_search(self, n, active, loss, pert, lr, evaluate):
         """ART's halving / doubling search on the per-sample learning rate; evaluate(sel, step) -> loss of the trial
@@ -544,7 +297,7 @@ class CarliniL2Method(_Carlini):
                 nd = fail & ~c_double
                 c_cur[nd] = c_cur[nd] + (c_cur - c_lower)[nd] / 2
             adv[s0:s0 + bs] = best_adv
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        return _as_given(adv, x)
 
 
 class CarliniLInfMethod(_Carlini):
@@ -591,7 +344,7 @@ class CarliniLInfMethod(_Carlini):
                 z = self._predict(xa)
                 loss = self._margin(z, yb)
             adv[s0:s0 + bs] = xa
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        return _as_given(adv, x)
 
 
 _NORMS = {np.inf: math.inf, "inf": math.inf, 1: 1.0, 2: 2.0}
@@ -617,11 +370,13 @@ class _SignAttack:
     def __init__(self, estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init):
         if not isinstance(estimator, (TensorFlowV2Classifier, WaveformClassifier)):
             raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
-        self._wave = isinstance(estimator, WaveformClassifier)
+        # the rows are the model's own inputs: the fused native iteration applies (the one choice this class makes by estimator)
+        self._fused = isinstance(estimator, TensorFlowV2Classifier)
         self.norm = _norm_value(norm)
         if int(num_random_init) < 0:
             raise ValueError("num_random_init must be >= 0")
         self.estimator, self.eps, self.eps_step = estimator, float(eps), float(eps_step)
+        self._default_eps = self.eps  # the ball of the reference's call (FastGradientMethod: none)
         self.max_iter, self.batch_size = int(max_iter), int(batch_size)
         self.targeted, self.num_random_init = bool(targeted), int(num_random_init)
         # random starts: Philox key (seed, restart, first row of the batch) and a device counter that moves with every generate()
@@ -633,22 +388,16 @@ class _SignAttack:
     def _default_path(self):
         return math.isinf(self.norm) and not self.targeted and self.num_random_init == 0
 
-    def _labels(self, m, xb, y):
-        if y is not None:
-            return y
-        yb = torch.empty(xb.shape[0], m._n_classes, device=xb.device)
-        N.check(N.lib.lipasr_mlp_own_labels(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), xb.shape[0], N.ptr(yb), N.stream_ptr()))
-        return yb
-
-    def _step(self, m, xa, x0, yb, alpha, eps):
-        """One native iteration in place on xa."""
+    def _step(self, xa, x0, yb):
+        """One native iteration over rows of features, in place on xa."""
+        m = self.estimator.model
         if self._default_path:
             N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
-                                                 alpha, eps, N.stream_ptr()))
+                                                 self.eps_step, self._default_eps, N.stream_ptr()))
         else:
-            a = -alpha if self.targeted else alpha  # ART: gradient x (1 - 2 targeted)
+            a = -self.eps_step if self.targeted else self.eps_step  # ART: gradient x (1 - 2 targeted)
             N.check(N.lib.lipasr_mlp_attack_step_lp(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb),
-                                                    xa.shape[0], self.norm, a, eps, N.stream_ptr()))
+                                                    xa.shape[0], self.norm, a, self.eps, N.stream_ptr()))
 
     def _random_init(self, xa, x0, restart, row0):
         """xa <- x0 + one draw of ART's random_sphere(rows, n, eps, norm) for restart ``restart`` of the rows starting at
@@ -664,18 +413,13 @@ class _SignAttack:
         else:
             xa.copy_(x0)
 
-    def _success(self, m, x0, yb, xa):
-        """ART compute_success_array: argmax at xa == target (targeted) or != the clean prediction (untargeted)."""
-        pa = m.predict_device(xa.contiguous(), logits=True).argmax(dim=1)
+    def _success(self, est, x0, yb, xa, lens):
+        """ART compute_success_array: argmax at xa == target (targeted) or != the clean prediction (untargeted).  The rows are
+        whole row slices of contiguous tensors, as the estimator takes them."""
+        pa = est.predict_device(xa, logits=True, lengths=lens).argmax(dim=1)
         if self.targeted:
             return pa == yb.argmax(dim=1)
-        return pa != m.predict_device(x0.contiguous(), logits=True).argmax(dim=1)
-
-    def _targets(self, m, xt, yt):
-        if self.targeted and yt is None:
-            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-        bs = min(self.batch_size, m._max_batch)
-        return torch.cat([self._labels(m, xt[s:s + bs], None if yt is None else yt[s:s + bs]) for s in range(0, xt.shape[0], bs)])
+        return pa != est.predict_device(x0, logits=True, lengths=lens).argmax(dim=1)
 
     # ---- over audio (WaveformClassifier): features -> lipasr_mlp_input_grad -> MFCC backward -> lipasr_lp_step -> clamp, all on
     # the device; every keyword keeps its meaning, eps and eps_step are amplitudes
@@ -703,48 +447,26 @@ class _SignAttack:
                                          N.stream_ptr()))
             self._wave_clamp(est, xa, x0, mask)
 
-    def _wave_success(self, est, x0, yb, xa, lens=None):
-        pa = est.predict_device(xa, logits=True, lengths=lens).argmax(dim=1)
-        if self.targeted:
-            return pa == yb.argmax(dim=1)
-        return pa != est.predict_device(x0, logits=True, lengths=lens).argmax(dim=1)
-
-    # ---- the restart driver.  A row backend is batch(s) -> (attack, success) for the rows starting at s: attack(xa, restart) does
+    # ---- the restart driver.  The row backend is batch(s) -> (attack, success) for the rows starting at s: attack(xa, restart) does
     # "start, then max_iter iterations" in place on xa, success(xa) is ART's compute_success_array on those rows.
-    def _feature_rows(self, xt, yt):
-        m = self.estimator.model
-        y_all = self._targets(m, xt, yt)
-        bs = min(self.batch_size, m._max_batch)
-
-        def batch(s):
-            x0, yb = xt[s:s + bs], y_all[s:s + bs]
-
-            def attack(xa, restart):
-                self._start(xa, x0, restart, s)
-                for _ in range(self.max_iter):
-                    self._step(m, xa, x0, yb, self.eps_step, self.eps)
-            return attack, lambda xa: self._success(m, x0, yb, xa)
-        return bs, batch
-
-    def _wave_rows(self, xt, yt, lengths):
+    def _rows(self, xt, yt, lt, bs):
         est = self.estimator
-        est._check(xt)
-        if self.targeted and yt is None:
-            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-        bs = min(self.batch_size, est._bs)
-        lt = est.lengths_device(lengths, xt.shape[0])
+        y_all = yt if yt is not None else est.own_labels_device(xt, lengths=lt, batch=bs)
         mask_all = None if lt is None else est.clip_mask(lt)
         cut = lambda t, s: None if t is None else t[s:s + bs]
-        y_all = yt if yt is not None else torch.cat([self._labels(est.model, est.features_device(xt[s:s + bs].contiguous(), cut(lt, s)), None)
-                                                      for s in range(0, xt.shape[0], bs)])
-        g = torch.empty(bs, xt.shape[1], device=xt.device)
+        g = None if self._fused else torch.empty(bs, xt.shape[1], device=xt.device)
 
         def batch(s):
-            x0, yb = xt[s:s + bs].contiguous(), y_all[s:s + bs]
-            gb, lb, mb = g[:x0.shape[0]], cut(lt, s), cut(mask_all, s)
-            return (lambda xa, restart: self._wave_attack_rows(est, xa, x0, yb, restart, s, gb, lb, mb),
-                    lambda xa: self._wave_success(est, x0, yb, xa, lb))
-        return bs, batch
+            x0, yb, lb = xt[s:s + bs], y_all[s:s + bs], cut(lt, s)
+
+            def attack(xa, restart):
+                if not self._fused:
+                    return self._wave_attack_rows(est, xa, x0, yb, restart, s, g[:x0.shape[0]], lb, cut(mask_all, s))
+                self._start(xa, x0, restart, s)
+                for _ in range(self.max_iter):
+                    self._step(xa, x0, yb)
+            return attack, lambda xa: self._success(est, x0, yb, xa, lb)
+        return batch
 
     def _generate_restarts(self, xt, bs, batch):
         rows = range(0, xt.shape[0], bs)
@@ -778,31 +500,33 @@ class _SignAttack:
         """x: float32 device tensor; returns a NEW device tensor (the input is left untouched).  lengths (WaveformClassifier only):
         the samples of each row that belong to its clip, as WaveformClassifier takes them; every keyword keeps its meaning per row,
         the perturbation stays inside the clip and the rest of each row is returned as it came."""
-        if lengths is not None and not self._wave:
-            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
-        m = self.estimator.model
-        if self._default_path and not self._wave:  # the reference's call: exactly the launches of round 5
+        est = self.estimator
+        lt = est.lengths_device(lengths, len(xt))  # first: rows of features take none, whatever else is wrong
+        xt = est.rows_device(xt)
+        if self.targeted and yt is None:
+            raise ValueError("Target labels `y` need to be provided for a targeted attack.")
+        bs = min(self.batch_size, est.batch_limit)
+        if self._default_path and self._fused:  # the reference's call: labels, then max_iter fused launches, per batch
             adv = xt.clone()
-            bs = min(self.batch_size, m._max_batch)
             for s in range(0, xt.shape[0], bs):
                 x0 = xt[s:s + bs]
                 xa = adv[s:s + bs]
-                yb = self._labels(m, x0, None if yt is None else yt[s:s + bs])
-                self._run(m, xa, x0, yb)
+                yb = est.own_labels_device(x0, batch=bs) if yt is None else yt[s:s + bs]
+                for _ in range(self.max_iter):
+                    self._step(xa, x0, yb)
             return adv
         if self._draws is None:
             self._draws = torch.zeros(1, dtype=torch.int32, device=xt.device)
-        adv = self._generate_restarts(xt, *(self._wave_rows(xt, yt, lengths) if self._wave else self._feature_rows(xt, yt)))
+        adv = self._generate_restarts(xt, bs, self._rows(xt, yt, lt, bs))
         self._draws += 1  # the next generate() draws fresh random starts
         return adv
 
     def generate(self, x, y=None, lengths=None):
-        if lengths is not None and not self._wave:
-            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
+        lt = self.estimator.lengths_device(lengths, len(x))
         xt = _to_dev(x)
         yt = None if y is None else _to_dev(y)
-        adv = self.generate_device(xt, yt, lengths)
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        adv = self.generate_device(xt, yt, lt)
+        return _as_given(adv, x)
 
 
 class FastGradientMethod(_SignAttack):
@@ -814,10 +538,7 @@ class FastGradientMethod(_SignAttack):
 
     def __init__(self, estimator, eps=0.3, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps, 1, batch_size, norm, targeted, num_random_init)
-
-    def _run(self, m, xa, x0, yb):
-        N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
-                                             self.eps, math.inf, N.stream_ptr()))
+        self._default_eps = math.inf  # the reference's call is one step of eps from x0: alpha = eps, and no ball to project on
 
 
 class ProjectedGradientDescent(_SignAttack):
@@ -829,11 +550,6 @@ class ProjectedGradientDescent(_SignAttack):
 
     def __init__(self, estimator, eps=0.3, eps_step=0.1, max_iter=100, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init)
-
-    def _run(self, m, xa, x0, yb):
-        for _ in range(self.max_iter):
-            N.check(N.lib.lipasr_mlp_attack_step(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xa), N.ptr(x0), N.ptr(yb), xa.shape[0],
-                                                 self.eps_step, self.eps, N.stream_ptr()))
 
 
 def deepfool_step(jac, out, label, x, norm=2, overshoot=0.02, clip_values=None, allowed=None):
@@ -895,7 +611,7 @@ class DeepFool:
 
     def __init__(self, classifier, max_iter=100, epsilon=1e-6, nb_grads=10, batch_size=1, verbose=True, *, norm=2, overshoot=0.02,
                  on_logits=True):
-        if not isinstance(classifier, (TensorFlowV2Classifier, WaveformClassifier)):
+        if not isinstance(classifier, _Estimator):
             raise TypeError("classifier must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
         if int(max_iter) < 0 or int(nb_grads) < 1 or int(batch_size) < 1:
             raise ValueError("max_iter >= 0, nb_grads >= 1 and batch_size >= 1 are required")
@@ -906,23 +622,17 @@ class DeepFool:
             raise ValueError("norm=1: DeepFool runs in norm 2 or np.inf")
         if classifier.nb_classes > 32:
             raise ValueError(f"{classifier.nb_classes} classes; 1 to 32 are supported")
-        self.estimator, self._wave = classifier, isinstance(classifier, WaveformClassifier)
+        self.estimator = classifier
         self.max_iter, self.epsilon, self.nb_grads, self.batch_size = int(max_iter), float(epsilon), int(nb_grads), int(batch_size)
         self.overshoot, self.on_logits, self.verbose = float(overshoot), bool(on_logits), verbose
         self.last = None
-
-    def _outputs(self, xa, lt, logits):
-        if self._wave:
-            return self.estimator.predict_device(xa, logits=logits, lengths=lt)
-        return self.estimator.model.predict_device(xa, logits=logits)
 
     def _chunk(self, x0, lt):
         """The rows ``x0`` (one chunk) -> (x_adv, iterations, flipped, target, first_dist) on the device."""
         est = self.estimator
         b, c = x0.shape[0], est.nb_classes
-        kw = {"lengths": lt} if self._wave else {}
-        clip = est.clip_values if self._wave else None
-        out0 = self._outputs(x0, lt, self.on_logits)
+        clip = est.clip_values
+        out0 = est.predict_device(x0, logits=self.on_logits, lengths=lt)
         classes = torch.arange(c, device=x0.device, dtype=torch.int32)
         label = torch.where(out0 == out0.max(dim=1, keepdim=True).values, classes[None, :], c).min(dim=1).values.to(torch.int32)
         allowed = None
@@ -934,8 +644,8 @@ class DeepFool:
         target = torch.full((b,), -1, dtype=torch.int32, device=x0.device)
         first = torch.full((b,), math.nan, device=x0.device)
         for it in range(self.max_iter):
-            out = out0 if it == 0 else self._outputs(xa, lt, self.on_logits)
-            jac = est.jacobian_device(xa, on_logits=self.on_logits, **kw)
+            out = out0 if it == 0 else est.predict_device(xa, logits=self.on_logits, lengths=lt)
+            jac = est.jacobian_device(xa, on_logits=self.on_logits, lengths=lt)
             dist, tgt, state = deepfool_step(jac, out, label, xa, self.norm, self.overshoot, clip, allowed)
             stepped = state == 1
             iters += stepped
@@ -949,7 +659,7 @@ class DeepFool:
             adv = adv.clamp(*clip)
         if lt is not None:
             adv = torch.where(est.clip_mask(lt), adv, x0)
-        final = self._outputs(adv, lt, True)
+        final = est.predict_device(adv, logits=True, lengths=lt)
         return adv, iters, final.argmax(dim=1) != label, target, first
 
     def generate_device(self, xt, lengths=None):
@@ -957,14 +667,10 @@ class DeepFool:
         only): the samples of each row that belong to its clip."""
         from .extract_features_construct_dataset import JACOBIAN_CHUNK_BYTES
 
-        if lengths is not None and not self._wave:
-            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
         est = self.estimator
-        xt = xt.to(dtype=torch.float32).contiguous()
-        if xt.dim() != 2 or xt.shape[1] != est.input_shape[0]:
-            raise ValueError(f"x must be [B, {est.input_shape[0]}], got {tuple(xt.shape)}")
+        xt = est.rows_device(xt)
         b, n = xt.shape
-        lt = est.lengths_device(lengths, b) if self._wave else None
+        lt = est.lengths_device(lengths, b)
         chunk = min(max(1, JACOBIAN_CHUNK_BYTES // max(1, 4 * est.nb_classes * n)), int(est.batch_limit))
         parts = [self._chunk(xt[s:s + chunk], None if lt is None else lt[s:s + chunk]) for s in range(0, b, chunk)]
         if not parts:
@@ -979,7 +685,7 @@ class DeepFool:
     def generate(self, x, lengths=None):
         """NumPy in, new NumPy out (the input is left untouched)."""
         adv = self.generate_device(_to_dev(x), lengths=lengths)
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        return _as_given(adv, x)
 
 
 class ImperceptibleASR:
@@ -1102,10 +808,10 @@ class ImperceptibleASR:
         if yt is None:
             raise ValueError("Target labels `y` need to be provided for a targeted attack.")
         est = self.estimator
-        est._check(xt)
+        xt = est.rows_device(xt)
         if tuple(yt.shape) != (xt.shape[0], est.nb_classes):
             raise ValueError(f"y must be one-hot [{xt.shape[0]}, {est.nb_classes}]")
-        bs = min(self.batch_size, est._bs)
+        bs = min(self.batch_size, est.batch_limit)
         out, keep = torch.empty_like(xt), {k: [] for k in ("succ", "l1", "l2", "eps", "x1", "it")}
         for s in range(0, xt.shape[0], bs):
             x0 = xt[s:s + bs].contiguous()
@@ -1127,7 +833,7 @@ class ImperceptibleASR:
         if y is None:
             raise ValueError("Target labels `y` need to be provided for a targeted attack.")
         adv = self.generate_device(_to_dev(x), _to_dev(y))
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        return _as_given(adv, x)
 
 
 def sign_step(x_adv, x0, g, alpha, eps):
@@ -1275,6 +981,3 @@ def load_npy_dataset(path):
 
     return (ld("train_data.npy"), ld("train_label.npy"), ld("dev_data.npy"), ld("dev_label.npy"), ld("test_data.npy"),
             ld("test_label.npy"))
-
-
-from .genetic import GeneticAttack  # noqa: E402  (the genetic black-box attack: scores only; lipasr/genetic.py)

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import estimators as E  # the module, not its names: it imports this one for the extractor
 from .keras import Model
 
 STANDARD_UTTERANCE_LENGTH = 44  # reference :18
@@ -391,27 +392,20 @@ def jacobian_sigma(jac, return_vectors=False):
 def get_local_lipschitz(estimator, x, on_logits=True, lengths=None, return_vectors=False):
     """The local Lipschitz constant of ``estimator`` at every row of ``x``: the largest singular value of the Jacobian of its logits
     (on_logits=True) or of its softmax probabilities w.r.t. the row -> float64 NumPy [B]; return_vectors=True: (sigma, u [B,
-    classes], v [B, n]).  ``estimator``: anything with ``jacobian_device(xt, on_logits=)`` and ``nb_classes`` --
-    attacks.TensorFlowV2Classifier (rows of MFCC features) or attacks.WaveformClassifier (rows of audio; ``lengths`` as there, and
-    passed on only when given).  Rows go through in chunks of the estimator's ``batch_limit`` (where it has one), cut further so
-    that one chunk's Jacobian stays under JACOBIAN_CHUNK_BYTES."""
-    dev = torch.device("cuda", torch.cuda.current_device())
-    xt = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(device=dev, dtype=torch.float32).contiguous()
+    classes], v [B, n]).  ``estimator``: a TensorFlowV2Classifier (rows of MFCC features) or a WaveformClassifier (rows of audio;
+    ``lengths`` as there) of lipasr.estimators -- or anything with ``jacobian_device(xt, on_logits=)`` and ``nb_classes``, which is
+    why ``lengths`` is passed on only when given and ``batch_limit`` used only where there is one.  Rows go through in chunks of
+    the batch limit, cut further so that one chunk's Jacobian stays under JACOBIAN_CHUNK_BYTES."""
+    xt = E._to_dev(x)
     if xt.dim() != 2:
         raise ValueError(f"x must be [B, n], got {tuple(xt.shape)}")
     b, n = xt.shape
     c = int(estimator.nb_classes)
     chunk = max(1, JACOBIAN_CHUNK_BYTES // max(1, 4 * c * n))
-    limit = getattr(estimator, "batch_limit", None)
-    if limit:
-        chunk = min(chunk, int(limit))
-    lt = None
-    if lengths is not None:
-        lt = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths).astype(np.int32))
-        lt = lt.to(device=dev, dtype=torch.int32).contiguous()
+    chunk = min(chunk, int(getattr(estimator, "batch_limit", None) or chunk))
     sig, us, vs = [], [], []
     for s in range(0, b, chunk):
-        kw = {} if lt is None else {"lengths": lt[s:s + chunk]}
+        kw = {} if lengths is None else {"lengths": lengths[s:s + chunk]}
         jac = estimator.jacobian_device(xt[s:s + chunk], on_logits=on_logits, **kw)
         r = jacobian_sigma(jac, return_vectors)
         if return_vectors:
@@ -458,19 +452,15 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **
       smoothed_class   int64: the class of g at the row, -1 where it abstains.
     It certifies the smoothed classifier, not the base one whose margin, ``certified`` and ``found`` stand next to it; over audio
     and for a model without a useful Lipschitz bound it is the only certified entry.  It is an L2 radius whatever ``norm`` is.
-    ``estimator``: attacks.TensorFlowV2Classifier or attacks.WaveformClassifier (``lengths`` as there)."""
-    from . import attacks as A
+    ``estimator``: a TensorFlowV2Classifier or WaveformClassifier of lipasr.estimators (``lengths`` as there)."""
+    from .attacks import DeepFool  # attacks imports this module
 
-    dev = torch.device("cuda", torch.cuda.current_device())
-    xt = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(device=dev, dtype=torch.float32).contiguous()
-    wave = isinstance(estimator, A.WaveformClassifier)
-    attack = A.DeepFool(estimator, norm=norm, **deepfool_kw)
+    xt = E._to_dev(x)
+    attack = DeepFool(estimator, norm=norm, **deepfool_kw)
     if xt.shape[0] == 0:
-        z = torch.zeros(0, estimator.nb_classes, device=dev)
-    elif wave:
-        z = estimator.predict_device(xt, logits=True, lengths=lengths)
+        z = torch.zeros(0, estimator.nb_classes, device=xt.device)
     else:
-        z = estimator.model.predict_device(xt, logits=True)
+        z = estimator.predict_device(xt, logits=True, lengths=lengths)
     z = z.double()
     if z.shape[1] > 1:
         top = torch.topk(z, 2, dim=1).values
@@ -481,7 +471,8 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **
     d = (adv - xt).double()
     found = (d.pow(2).sum(dim=1).sqrt() if attack.norm == 2.0 else d.abs().amax(dim=1)).cpu().numpy()
     certified = None
-    if not wave and attack.norm == 2.0:
+    # the model's bound speaks about the estimator where its rows are the model's own inputs: no extraction stage in front
+    if getattr(estimator, "extractor", None) is None and attack.norm == 2.0:
         certified = margin / (np.sqrt(2.0) * get_lipschitz_bound(estimator.model))
     res = {"margin": margin, "certified": certified, "linear": attack.last["first_dist"], "found": found,
            "flipped": attack.last["flipped"]}

@@ -1,5 +1,5 @@
 """The genetic black-box attack of Alzantot, Balaji and Srivastava (2018, "Did you hear that? Adversarial examples against
-automatic speech recognition") over the estimators of lipasr.attacks: it queries scores only, never a gradient.
+automatic speech recognition") over the estimators of lipasr.estimators: it queries scores only, never a gradient.
 
 Why it is here: a query-only attack that beats the gradient attacks at the same eps says that the gradients are masked (Athalye et
 al. 2018; Carlini et al. 2019) -- and a constrained network (NonNeg kernels, a small Lipschitz constant, a saturating softmax) is
@@ -18,9 +18,11 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from . import _native as N
+from .estimators import _as_given, _Estimator, _to_dev
 
 
 def _dev_tensor(t, dtype, shape, what):
@@ -114,11 +116,9 @@ class GeneticAttack:
 
     def __init__(self, estimator, eps, *, pop_size=20, max_iter=500, mutation_p=0.0005, step=None, temperature=0.01, targeted=False,
                  seed=0, clip_values=_UNSET, check_every=10):
-        from . import attacks as A
-
-        if not isinstance(estimator, (A.TensorFlowV2Classifier, A.WaveformClassifier)):
+        if not isinstance(estimator, _Estimator):
             raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
-        self.estimator, self._wave = estimator, isinstance(estimator, A.WaveformClassifier)
+        self.estimator = estimator
         self.eps = float(eps)
         self.step = self.eps if step is None else float(step)
         if not (0.0 <= self.eps < math.inf and 0.0 <= self.step < math.inf):
@@ -138,23 +138,17 @@ class GeneticAttack:
             raise ValueError(f"temperature = {temperature}: a finite, positive number is required")
         self.targeted, self.seed = bool(targeted), int(seed) & 0xFFFFFFFFFFFFFFFF
         if clip_values is GeneticAttack._UNSET:
-            clip_values = getattr(estimator, "clip_values", None)
+            clip_values = estimator.clip_values
         if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
             raise ValueError(f"clip_values = {clip_values}")
         self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
         self.success_ = self.queries_ = self.fitness_ = None
 
-    def _predict(self, rows, lt):
-        est = self.estimator
-        if self._wave:
-            return est.predict_device(rows, logits=True, lengths=lt)
-        return est.model.predict_device(rows, logits=True)
-
     def _labels(self, xt, yt, lt):
         if yt is None:
             if self.targeted:
                 raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-            return self._predict(xt, lt).argmax(dim=1).to(torch.int32).contiguous()
+            return self.estimator.predict_device(xt, logits=True, lengths=lt).argmax(dim=1).to(torch.int32).contiguous()
         yt = yt.to(xt.device)
         lab = yt.argmax(dim=1) if yt.dim() == 2 else yt
         if tuple(lab.shape) != (xt.shape[0],):
@@ -166,17 +160,11 @@ class GeneticAttack:
         device tensor: per clip member ``best`` of the last population evaluated -- the adversarial one where the clip is done,
         the fittest otherwise."""
         est, P = self.estimator, self.pop_size
-        if lengths is not None and not self._wave:
-            raise ValueError("lengths= is for attacks over audio: the estimator must be a WaveformClassifier")
-        xt = xt.to(dtype=torch.float32).contiguous()
-        if xt.dim() != 2 or xt.shape[1] != est.input_shape[0]:
-            raise ValueError(f"x must be [B, {est.input_shape[0]}], got {tuple(xt.shape)}")
+        xt = est.rows_device(xt)
         b, n = xt.shape
         dev = xt.device
-        lt = pos = None
-        if lengths is not None:
-            lt = est.lengths_device(lengths, b)
-            pos = est.clip_mask(lt).sum(dim=1).to(torch.int32).contiguous()
+        lt = est.lengths_device(lengths, b)
+        pos = None if lt is None else est.clip_mask(lt).sum(dim=1).to(torch.int32).contiguous()
         labels = self._labels(xt, yt, lt)
         adv = xt.clone()
         self.success_ = torch.zeros(b, dtype=torch.bool, device=dev)
@@ -201,8 +189,8 @@ class GeneticAttack:
             nxt = bufs[1][:bb * P]
             evaluated = 0
             for g in range(self.max_iter):
-                genetic_select(self._predict(cur, lrep), lab, P, g, self.seed, self.temperature, targeted=self.targeted, clip0=s,
-                               fitness=fitness, best=best, done=done, parents=parents)
+                genetic_select(est.predict_device(cur, logits=True, lengths=lrep), lab, P, g, self.seed, self.temperature,
+                               targeted=self.targeted, clip0=s, fitness=fitness, best=best, done=done, parents=parents)
                 evaluated = g + 1
                 if evaluated == self.max_iter or (evaluated % self.check_every == 0 and bool((done != 0).all())):
                     break
@@ -217,11 +205,6 @@ class GeneticAttack:
         return adv
 
     def generate(self, x, y=None, lengths=None):
-        import numpy as np
-
-        from .attacks import _to_dev
-
         xt = _to_dev(x)
         yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
-        adv = self.generate_device(xt, yt, lengths)
-        return adv if torch.is_tensor(x) else adv.cpu().numpy().astype(np.asarray(x).dtype, copy=False)
+        return _as_given(self.generate_device(xt, yt, lengths), x)

@@ -20,6 +20,7 @@ import ctypes as C
 import torch
 
 from . import _native as N
+from .attacks import _norm_value
 from .extract_features_construct_dataset import MfccExtractor
 from .parallel import DataParallel
 
@@ -52,8 +53,6 @@ class TrainPipeline:
         synchronised beforehand (bench.py) may pass False."""
         self.sync_inputs = bool(sync_inputs)
         if pgd:
-            from .attacks import _norm_value
-
             self._pgd_norm = _norm_value(pgd.get("norm", float("inf")))
             rinit = int(pgd.get("num_random_init", 0))
             if rinit not in (0, 1):

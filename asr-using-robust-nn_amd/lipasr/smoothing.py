@@ -1,4 +1,4 @@
-"""Randomized smoothing (Cohen, Rosenfeld, Kolter 2019, algorithms CERTIFY and PREDICT) over the estimators of lipasr.attacks.
+"""Randomized smoothing (Cohen, Rosenfeld, Kolter 2019, algorithms CERTIFY and PREDICT) over the estimators of lipasr.estimators.
 
 The smoothed classifier g(x) = argmax_c P(f(x + N(0, sigma^2 I)) = c) of ANY base classifier f does not change within the L2 radius
 sigma Phi^-1(p_A) of x, p_A a lower bound of the vote share of its majority class.  The reference's black-box experiment
@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .estimators import _Estimator
 
 _PHI_INV = NormalDist().inv_cdf
 
@@ -152,9 +153,7 @@ class Smooth:
     holds for that composition.  None (default): no clamp."""
 
     def __init__(self, estimator, sigma, *, seed=0, clip_values=None):
-        from . import attacks as A
-
-        if not isinstance(estimator, (A.TensorFlowV2Classifier, A.WaveformClassifier)):
+        if not isinstance(estimator, _Estimator):
             raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
         if not (0.0 <= float(sigma) < math.inf):
             raise ValueError(f"sigma = {sigma}: a finite, non-negative number is required")
@@ -162,41 +161,23 @@ class Smooth:
             raise ValueError(f"{estimator.nb_classes} classes; 1 to 32 are supported")
         if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
             raise ValueError(f"clip_values = {clip_values}")
-        self.estimator, self._wave = estimator, isinstance(estimator, A.WaveformClassifier)
+        self.estimator = estimator
         self.sigma, self.seed = float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF
         self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
 
     # ---- device
-    def _rows(self, x):
-        from .attacks import _to_dev
-
-        xt = _to_dev(x)
-        if xt.dim() != 2 or xt.shape[1] != self.estimator.input_shape[0]:
-            raise ValueError(f"x must be [B, {self.estimator.input_shape[0]}], got {tuple(xt.shape)}")
-        return xt
-
-    def _lengths(self, lengths, b):
-        """-> (lengths as the estimator takes them, the valid positions per row for the expand kernel), both int32 [b] or None."""
-        if lengths is None:
-            return None, None
-        if not self._wave:
-            raise ValueError("lengths= is for smoothing over audio: the estimator must be a WaveformClassifier")
-        lt = self.estimator.lengths_device(lengths, b)
-        return lt, self.estimator.clip_mask(lt).sum(dim=1).to(torch.int32).contiguous()
-
     def counts_device(self, xt, n, *, draw0=0, lengths=None):
         """The votes of draws [draw0, draw0 + n) for every row of the float32 device tensor ``xt`` [B, features or samples] ->
         int32 device tensor [B, classes + 1] (last bin: noisy rows whose logits held a NaN).  Chunks of at most
         ``estimator.batch_limit`` noisy rows: expand, predict_device(..., logits=True), vote; nothing synchronises."""
         est = self.estimator
-        xt = xt.to(dtype=torch.float32).contiguous()
-        if xt.dim() != 2 or xt.shape[1] != est.input_shape[0]:
-            raise ValueError(f"x must be [B, {est.input_shape[0]}], got {tuple(xt.shape)}")
+        xt = est.rows_device(xt)
         n, draw0 = int(n), int(draw0)
         if n < 0 or draw0 < 0 or draw0 + n > 0xFFFFFFFF:
             raise ValueError(f"draws [{draw0}, {draw0 + n}) are outside the 32-bit counter")
         b, c = xt.shape[0], est.nb_classes
-        lt, pos = self._lengths(lengths, b)
+        lt = est.lengths_device(lengths, b)  # as the estimator takes them; pos: the valid positions per row for the expand kernel
+        pos = None if lt is None else est.clip_mask(lt).sum(dim=1).to(torch.int32).contiguous()
         counts = torch.zeros(b, c + 1, dtype=torch.int32, device=xt.device)
         if b == 0 or n == 0:
             return counts
@@ -211,10 +192,7 @@ class Smooth:
                 d = min(d_chunk, n - j0)
                 noisy = smooth_expand(xb, d, self.sigma, self.seed, clip0=s, draw0=draw0 + j0, n_valid=None if pos is None else pos[s:s + bb],
                                       clip_values=self.clip_values, out=buf[:bb * d])
-                if self._wave:
-                    z = est.predict_device(noisy, logits=True, lengths=None if lt is None else lt[s:s + bb].repeat_interleave(d))
-                else:
-                    z = est.model.predict_device(noisy, logits=True)
+                z = est.predict_device(noisy, logits=True, lengths=None if lt is None else lt[s:s + bb].repeat_interleave(d))
                 smooth_vote(z, bb, counts[s:s + bb])
         return counts
 
@@ -229,7 +207,7 @@ class Smooth:
         n0, n, alpha = int(n0), int(n), float(alpha)
         if n0 < 1 or n < 1 or not (0.0 < alpha < 1.0):
             raise ValueError(f"certify: n0 = {n0}, n = {n}, alpha = {alpha}")
-        xt = self._rows(x)
+        xt = self.estimator.rows_device(x)
         c = self.estimator.nb_classes
         sel = self.counts_device(xt, n0, draw0=0, lengths=lengths).cpu().numpy().astype(np.int64)
         est = self.counts_device(xt, n, draw0=n0, lengths=lengths).cpu().numpy().astype(np.int64)
@@ -247,7 +225,7 @@ class Smooth:
         n, alpha = int(n), float(alpha)
         if n < 1 or not (0.0 < alpha < 1.0):
             raise ValueError(f"predict: n = {n}, alpha = {alpha}")
-        xt = self._rows(x)
+        xt = self.estimator.rows_device(x)
         c = self.estimator.nb_classes
         counts = self.counts_device(xt, n, lengths=lengths).cpu().numpy().astype(np.int64)[:, :c]
         out = np.full(xt.shape[0], -1, dtype=np.int64)

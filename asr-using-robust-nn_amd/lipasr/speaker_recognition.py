@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import attacks as A
+from .attack_eval import AUDIO_SIGMAS, _tag, accuracy
 from .Constraints import customConstraint, norm_constraint, norm_constraint_FISTA, simple_norm_constraint  # noqa: F401
 from .extract_features_construct_dataset import (  # noqa: F401  (re-exported: the Speaker-recognition copy has the same read-outs)
     N_MFCC,
@@ -129,12 +131,10 @@ def load_audio_dataset_and_labels(filenames, labels):
 def waveform_classifier(model, mean=None, scale=None, batch_max=None, clip_values=(-1, 1)):
     """``attacks.WaveformClassifier`` over [B, 22050] windows: window -> 441/220 MFCC (2020) -> optional StandardScaler affine ->
     the 20-speaker model.  FastGradientMethod / ProjectedGradientDescent with this estimator perturb the audio of the windows."""
-    from .attacks import WaveformClassifier
-
     if not isinstance(model, Model):
         raise TypeError("model must be a lipasr.keras.Model")
     ex = WindowMfcc(batch_max=model._max_batch if batch_max is None else batch_max, device=model._device)
-    return WaveformClassifier(model, N_SPEAKERS, extractor=ex._ex, utterance_length=N_FRAMES, mean=mean, scale=scale, domain="22k",
+    return A.WaveformClassifier(model, N_SPEAKERS, extractor=ex._ex, utterance_length=N_FRAMES, mean=mean, scale=scale, domain="22k",
                               clip_values=clip_values)
 
 
@@ -144,9 +144,6 @@ def white_box_audio_sweep(models, train_data, val_data, test_filenames, test_lab
     1-s windows of ``test_filenames`` (load_audio_dataset_and_labels' slicing, ``test_labels`` [files] class indices repeated per
     window).  Features are standardised with the statistics of (train, val, the clean window MFCCs), fused into the extraction;
     eps is an amplitude, iterates stay in [-1, 1]; grid point 0 is the clean accuracy.  -> (grid, {name: accuracies})."""
-    from . import attacks as A
-    from .attack_eval import AUDIO_SIGMAS, accuracy
-
     if kind not in ("fgsm", "pgd"):
         raise ValueError(f"white-box attacks over audio are fgsm and pgd, not {kind!r}")
     files = list(test_filenames[:limit] if limit else test_filenames)
@@ -172,7 +169,7 @@ def white_box_audio_sweep(models, train_data, val_data, test_filenames, test_lab
             adv = cls(estimator=clf, eps=item, **attack_kw).generate_device(x) if item != 0 else x
             a = accuracy(clf.predict_device(adv).cpu().numpy(), onehot)
             acc[name].append(a)
-            print(f"Accuracy on adversarial audio test examples{'' if name == 'constrained' else ' ' + name}: {a * 100}% ({item})")
+            print(f"Accuracy on adversarial audio test examples{_tag(name)}: {a * 100}% ({item})")
     for clf in clfs.values():
         clf.extractor.close()
     return grid, {k: np.asarray(v) for k, v in acc.items()}

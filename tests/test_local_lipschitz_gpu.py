@@ -530,6 +530,44 @@ def test_local_lipschitz_of_a_bare_estimator(cuda):
     np.testing.assert_array_equal(get_local_lipschitz(Bare(), x), get_local_lipschitz(clf, x))
 
 
+def test_shared_surface_on_a_feature_estimator(cuda):
+    """The device-side surface of lipasr.estimators on a TensorFlowV2Classifier: 7 rows through a model that takes 4 at a time.
+    Every comparison is bit for bit -- the surface only routes to calls that existed before it."""
+    from lipasr import _native as N
+    from lipasr.attacks import TensorFlowV2Classifier
+
+    spec = [P.LayerSpec(36, 16, True, 0.0, False), P.LayerSpec(16, 5, False, 0.0, False)]
+    m = build_model(spec, max_batch=4)
+    load_params(m, R.setup_params(spec, 2))
+    clf = TensorFlowV2Classifier(model=m, nb_classes=5, input_shape=(36,))
+    assert clf.clip_values is None and clf.batch_limit == 4 and clf.input_shape == (36,) and clf.nb_classes == 5 and clf.model is m
+    rng = np.random.default_rng(4)
+    x_np = rng.standard_normal((7, 36)).astype(np.float32)
+    y_np = G.onehot(rng.integers(0, 5, 7), 5).astype(np.float32)
+    x, y = clf.rows_device(x_np), dev(y_np)
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (7, 36)
+    with pytest.raises(ValueError):
+        clf.rows_device(x_np[:, :35])
+    assert torch.equal(clf.predict_device(x, logits=True), m.predict_device(x, logits=True))
+    assert clf.lengths_device(None, 7) is None
+    refusal = "lengths= is for attacks over audio: the estimator must be a WaveformClassifier"
+    for call in (lambda: clf.predict_device(x, lengths=[36] * 7), lambda: clf.jacobian_device(x, lengths=[36] * 7),
+                 lambda: clf.loss_gradient_device(x, y, lengths=[36] * 7), lambda: clf.lengths_device([36] * 7, 7)):
+        with pytest.raises(ValueError, match=refusal):
+            call()
+    want = torch.empty(7, 5, device="cuda")
+    for s in range(0, 7, 3):
+        x0 = x[s:s + 3]
+        N.check(N.lib.lipasr_mlp_own_labels(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(x0), x0.shape[0], N.ptr(want[s:s + 3]), N.stream_ptr()))
+    assert torch.equal(clf.own_labels_device(x, batch=3), want)
+    assert torch.equal(clf.own_labels_device(x, batch=64), clf.own_labels_device(x))  # never more than batch_limit rows a call
+    assert bool((want.sum(dim=1) == 1).all()) and bool(((want == 0) | (want == 1)).all())
+    g = clf.loss_gradient_device(x, y)
+    assert g.cpu().numpy().tobytes() == clf.loss_gradient(x_np, y_np).tobytes() and float(g.abs().max()) > 0
+    out = torch.empty_like(x)
+    assert clf.loss_gradient_device(x, y, out=out) is out and torch.equal(out, g)
+
+
 # =================================================================================================
 # 6. lipschitz_report
 # =================================================================================================

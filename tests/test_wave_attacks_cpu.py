@@ -96,3 +96,31 @@ def test_keyword_validation():
         E.white_box_sweep({}, None, None, None, None, kind="fgsm", over="audio")  # no file names
     with pytest.raises(ValueError):
         E.white_box_sweep({}, None, None, None, None, kind="fgsm", over="video")
+
+
+def test_sweeps_and_reports_refuse_bad_arguments_in_one_order():
+    """The preparation the sweeps and read-outs share: over="audio" without file names, then ``domain``, then ``over`` -- each
+    refused before anything touches a device or the data (there is no device here and the data are None).  white_box_sweep looks
+    at ``kind`` before all of them."""
+    from lipasr import attack_eval as E
+
+    calls = {"lipschitz_report": lambda **kw: E.lipschitz_report({}, None, None, None, **kw),
+             "radius_report": lambda **kw: E.radius_report({}, None, None, None, **kw),
+             "smooth_report": lambda **kw: E.smooth_report({}, None, None, None, None, 0.1, **kw),
+             "genetic_sweep": lambda **kw: E.genetic_sweep({}, None, None, None, None, **kw),
+             "white_box_sweep": lambda **kw: E.white_box_sweep({}, None, None, None, None, kind="fgsm", **kw)}
+    for name, call in calls.items():
+        with pytest.raises(ValueError, match="test_filenames"):
+            call(over="audio", domain="44k")  # no file names AND a bad domain: the file names come first
+        with pytest.raises(ValueError, match="domain="):
+            call(over="audio", test_filenames=["a.wav"], domain="44k")
+        with pytest.raises(ValueError, match="over must be"):
+            call(over="video", domain="44k")
+        with pytest.raises(ValueError, match="over must be"):
+            call(over="video", test_filenames=["a.wav"])
+    with pytest.raises(ValueError, match="kind"):
+        E.white_box_sweep({}, None, None, None, None, kind="jsma", over="audio", domain="44k")  # kind before file names and domain
+    with pytest.raises(ValueError, match="unknown white-box attack"):
+        E.white_box_sweep({}, None, None, None, None, kind="deepfool", over="video")  # and before over
+    with pytest.raises(ValueError, match="sigma"):
+        E.smooth_report({}, None, None, None, None, -1.0, over="video")  # smooth_report's own argument first
