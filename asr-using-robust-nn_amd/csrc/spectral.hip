@@ -812,6 +812,11 @@ static int carve_scratch(lipasr_ctx* h, int R, int max_width, ChainScratch* cs) 
   return LIPASR_OK;
 }
 
+// Test hook (lipasr_debug_k3_launches): launches since load per K3 kernel, counted on the host where the launch happens.
+enum K3Kernel { K3_CHAIN_STEP_12 = 0, K3_CHAIN_STEP_20, K3_CHAIN_STEP_32, K3_CHAIN_HEAD, K3_PRODUCT_SIGMA, K3_SCALE_LAYERS, K3_SIGMA_SCALE_LAYERS,
+                K3_PI_U, K3_PI_V, K3_PI_FINISH, K3_SV_CLIP, K3_FROBENIUS, K3_BN_CORRECTION, K3_KERNELS };
+static long g_k3_launches[K3_KERNELS] = {};
+
 static int g_chain_head = -1;  // lipasr_debug_chain_head: -1 the two leading steps when legal, 0 none, n > 0 at most n (<= 3)
 
 // Launches the chain; on return the Gram partials are in cs.gram (n_part blocks).
@@ -866,6 +871,7 @@ static int launch_chain(lipasr_ctx* h, const float* const* Ws, const int* rows, 
       const size_t lds = lds_f * sizeof(float);
       LP_DYN_LDS(chain_head_kernel, lds);
       hipLaunchKernelGGL(chain_head_kernel, dim3(blocks), dim3(512), lds, st, a);
+      ++g_k3_launches[K3_CHAIN_HEAD];
       LP_LAUNCH_CHECK();
       pin = cs->P[cur];
       p_mode = 0;
@@ -895,6 +901,7 @@ static int launch_chain(lipasr_ctx* h, const float* const* Ws, const int* rows, 
     LP_DYN_LDS(chain_step_kernel<RM>, lds);                                                                   \
     hipLaunchKernelGGL(chain_step_kernel<RM>, dim3(blocks), dim3(256), lds, st, pin, p_mode, Wk, n_rows, n_in, R, \
                        cs->P[cur], emit, cs->gram);                                                           \
+    ++g_k3_launches[K3_CHAIN_STEP_##RM];                                                                      \
   }
     if (R <= 12) LP_CHAIN(12) else if (R <= 20) LP_CHAIN(20) else LP_CHAIN(32)
 #undef LP_CHAIN
@@ -945,16 +952,20 @@ static int run_power_iteration(lipasr_ctx* h, PiArgs& a, int warm, int iters, hi
   int cold = warm ? 0 : 1;
   for (int it = 0; it < iters; ++it) {
     hipLaunchKernelGGL(pi_u_kernel, dim3(nbu), dim3(256), 0, st, a, cold);
+    ++g_k3_launches[K3_PI_U];
     LP_LAUNCH_CHECK();
     cold = 0;
     hipLaunchKernelGGL(pi_v_kernel, dim3(nbv), dim3(256), 0, st, a);
+    ++g_k3_launches[K3_PI_V];
     LP_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(pi_u_kernel, dim3(nbu), dim3(256), 0, st, a, cold);
+  ++g_k3_launches[K3_PI_U];
   LP_LAUNCH_CHECK();
   if (cold) {
     // iters == 0 on a cold start: still leave a defined warm-start vector behind
     hipLaunchKernelGGL(pi_v_kernel, dim3(nbv), dim3(256), 0, st, a);
+    ++g_k3_launches[K3_PI_V];
     LP_LAUNCH_CHECK();
   }
   return LIPASR_OK;
@@ -1145,6 +1156,8 @@ using namespace lipasr;
 
 extern "C" {
 
+long lipasr_debug_k3_launches(int kernel) { return (kernel >= 0 && kernel < K3_KERNELS) ? g_k3_launches[kernel] : -1; }
+
 int lipasr_debug_chain_head(int n) {
   g_chain_head = n < 0 ? -1 : (n > kHeadMax ? kHeadMax : n);
   return LIPASR_OK;
@@ -1161,6 +1174,7 @@ int lipasr_sigma_max(lipasr_handle_t h, const float* W, int rows, int cols, floa
   rc = run_power_iteration(h, a, warm, iters, S(stream));
   if (rc != LIPASR_OK) return rc;
   hipLaunchKernelGGL(pi_finish_kernel, dim3(1, 1), dim3(256), 0, S(stream), a, 0.0, 0, sigma_out);
+  ++g_k3_launches[K3_PI_FINISH];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -1180,6 +1194,7 @@ int lipasr_project_per_layer(lipasr_handle_t h, float* const* Ws, const int* row
   if (rc != LIPASR_OK) return rc;
   const double c = pow((double)rho, 1.0 / (double)n_layers);  // np.power(rho, 1/self.m), Constraints.py:25
   hipLaunchKernelGGL(pi_finish_kernel, dim3(64, n_layers), dim3(256), 0, S(stream), a, c, 1, sigmas_out);
+  ++g_k3_launches[K3_PI_FINISH];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -1239,6 +1254,7 @@ int lipasr::project_product_bump(lipasr_handle_t h, float* const* Ws, const int*
     }
     hipLaunchKernelGGL(sigma_scale_layers_kernel, dim3(lp.wg_start[n_layers]), dim3(kSslThreads), lds, S(stream), p_final, n0, R, (double)rho, oa, lp, cs.scales,
                        norms_out, cs.sigma, bump);
+    ++g_k3_launches[K3_SIGMA_SCALE_LAYERS];
     LP_LAUNCH_CHECK();
     return LIPASR_OK;
   }
@@ -1246,12 +1262,14 @@ int lipasr::project_product_bump(lipasr_handle_t h, float* const* Ws, const int*
   if (rc != LIPASR_OK) return rc;
   hipLaunchKernelGGL(product_sigma_kernel, dim3(1), dim3(kSigmaThreads), 0, S(stream), cs.gram, n_part, cols[n_layers - 1],
                      (double)rho, oa, cs.scales, norms_out, cs.sigma, bump);
+  ++g_k3_launches[K3_PRODUCT_SIGMA];
   LP_LAUNCH_CHECK();
   if (n_order > 0) {
     LayerPtrs lp;
     lp.n_layers = n_layers;
     for (int l = 0; l < n_layers; ++l) { lp.W[l] = Ws[l]; lp.rows[l] = rows[l]; lp.cols[l] = cols[l]; }
     hipLaunchKernelGGL(scale_layers_kernel, dim3(64, n_layers), dim3(256), 0, S(stream), lp, cs.scales);
+    ++g_k3_launches[K3_SCALE_LAYERS];
     LP_LAUNCH_CHECK();
   }
   return LIPASR_OK;
@@ -1273,6 +1291,7 @@ int lipasr_product_norm(lipasr_handle_t h, const float* const* Ws, const int* ro
   oa.n_order = 0;
   hipLaunchKernelGGL(product_sigma_kernel, dim3(1), dim3(kSigmaThreads), 0, S(stream), cs.gram, n_part, cols[n_layers - 1], 1.0,
                      oa, (float*)nullptr, (float*)nullptr, sigma_out, (int*)nullptr);
+  ++g_k3_launches[K3_PRODUCT_SIGMA];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -1284,6 +1303,7 @@ int lipasr_frobenius_project(lipasr_handle_t h, float* W, size_t n, float rho, l
   hipLaunchKernelGGL(sumsq_clamped_kernel, dim3(nb), dim3(256), 0, S(stream), W, n, part);
   LP_LAUNCH_CHECK();
   hipLaunchKernelGGL(frob_scale_kernel, dim3(nb), dim3(256), 0, S(stream), W, n, part, nb, (double)rho);
+  ++g_k3_launches[K3_FROBENIUS];  // the pair counts once
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -1292,6 +1312,7 @@ int lipasr_bn_correction(lipasr_handle_t h, const float* gamma, const float* var
                          lipasr_stream_t stream) {
   LP_CHECK_ARG(h && gamma && var && out && n > 0, "lipasr_bn_correction: bad argument");
   hipLaunchKernelGGL(bn_correction_kernel, dim3(1), dim3(256), 0, S(stream), gamma, var, n, out);
+  ++g_k3_launches[K3_BN_CORRECTION];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -1303,6 +1324,7 @@ int lipasr_sv_clip(lipasr_handle_t h, const float* X, int R, int n, float hi, fl
   LP_CHECK_ARG(R >= 1 && R <= kMaxR && n >= 1, "lipasr_sv_clip: needs 1 <= R <= 32 rows and n >= 1 columns");
   LP_CHECK_ARG(hi >= 0.0f, "lipasr_sv_clip: negative clipping level");
   hipLaunchKernelGGL(sv_clip_kernel, dim3(1), dim3(256), 0, S(stream), X, R, n, (double)hi, out, svals_out);
+  ++g_k3_launches[K3_SV_CLIP];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 620.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 630.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -31,6 +31,7 @@
  * the host-only lipasr_smooth_noise_host.
  * 620: the genetic black-box attack: lipasr_genetic_breed (one generation's children), lipasr_genetic_select (fitness, elite and
  * parent draws per clip) and the host-only lipasr_genetic_breed_host.
+ * 630: test hook of the K3 projections: lipasr_debug_k3_launches (launch counters per kernel).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -864,6 +865,13 @@ long lipasr_debug_group_launches(int family, int arith, int variant);
  * the plain product with bf16 operands (arith 1).  The scales are read in mode 2 only (powers of two). */
 int lipasr_debug_gemm(lipasr_handle_t h, int arith, int transA, int transB, int M, int N, int K, const float* A, int lda,
                       const float* B, int ldb, float* C, int ldc, float scale_a, float scale_b, lipasr_stream_t stream);
+
+/* Test hook: launches since the library was loaded of one K3 kernel (csrc/spectral.hip), counted on the host where the launch
+ * happens.  kernel: 0 / 1 / 2 chain_step_kernel<12> / <20> / <32> (at most 12 / 20 / 32 classes), 3 chain_head_kernel, 4 product_sigma_kernel,
+ * 5 scale_layers_kernel, 6 sigma_scale_layers_kernel, 7 pi_u_kernel, 8 pi_v_kernel, 9 pi_finish_kernel, 10 sv_clip_kernel,
+ * 11 the Frobenius pair (sumsq_clamped_kernel + frob_scale_kernel: one count per pair), 12 bn_correction_kernel.  Returns -1 for an
+ * unknown id, so a test can enumerate the kernels from the library. */
+long lipasr_debug_k3_launches(int kernel);
 
 /* Profiling knob: how many of the leading (small) steps of the product chain W_m^T ... W_1^T run as ONE launch
  * (chain_head_kernel, fp32 matrix instructions): -1 = automatic (the first two steps, when their panels have <= 256 columns

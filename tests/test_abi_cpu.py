@@ -31,6 +31,15 @@ def test_library_exports_every_declared_symbol():
     assert N.lib.lipasr_version() >= 200
 
 
+def test_k3_launch_counters_without_gpu():
+    """lipasr_debug_k3_launches (version 630): host-side counters, readable without a GPU; -1 for an id that does not exist."""
+    assert N.lib.lipasr_version() >= 630 and N.has("lipasr_debug_k3_launches")
+    assert N.lib.lipasr_debug_k3_launches(0) >= 0
+    assert N.lib.lipasr_debug_k3_launches(-1) == -1 and N.lib.lipasr_debug_k3_launches(1000) == -1
+    known = [k for k in range(64) if N.lib.lipasr_debug_k3_launches(k) >= 0]
+    assert known == list(range(len(known))) and len(known) == 13  # the ids documented in include/lipasr.h, without gaps
+
+
 def test_error_convention_without_gpu():
     assert N.lib.lipasr_create(0, None) == N.EINVAL
     assert "out is null" in N.last_error()

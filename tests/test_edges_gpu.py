@@ -87,14 +87,17 @@ def test_projection_on_degenerate_stacks(cuda):
     from test_spectral_gpu import FakeModel
 
     for ws in ([np.abs(np.random.default_rng(0).standard_normal((7, 3))).astype(np.float32)],
-               [np.abs(np.random.default_rng(1).standard_normal((9, 5))).astype(np.float32), np.abs(np.random.default_rng(2).standard_normal((5, 1))).astype(np.float32)]):
+               [np.abs(np.random.default_rng(1).standard_normal((9, 5))).astype(np.float32), np.abs(np.random.default_rng(2).standard_normal((5, 1))).astype(np.float32)],
+               [np.abs(np.random.default_rng(3).standard_normal((9, 5))).astype(np.float32), np.zeros((5, 4), np.float32), np.abs(np.random.default_rng(4).standard_normal((4, 3))).astype(np.float32)]):
         model = FakeModel([w.copy() for w in ws])
         cb = simple_norm_constraint(rho=0.7, affected_layers_indices=[])
         cb.set_model(model)
         cb.on_batch_end(0)
         want, _ = R.simple_norm_constraint_pass(ws, 0.7, [])
         for l, r in zip([l for l in model.layers if "dense" in l.name], want):
+            assert np.isfinite(l.w).all()
             assert rel_err(l.w, r) < 2e-5
+        assert float(cb.last_norms.max().item()) == 0.0 or all(w.any() for w in ws)  # the zero kernel: every norm of the pass is 0
 
 
 @pytest.mark.parametrize("L", [1, 45, 100, 200])
