@@ -15,6 +15,8 @@ namespace lipasr {
 
 using namespace tables;
 
+long g_k1_launches[K1_KERNELS] = {};
+
 void mfcc_plan_free(MfccPlan* p) {
   if (!p) return;
   void* ptrs[] = {p->d_hbandh, p->d_groups, p->d_dft, p->d_mel_wlo, p->d_mel_whi, p->d_mel_pstart, p->d_mel_plen, p->d_hband, p->d_lo, p->d_h, p->d_noff, p->d_hann, p->d_tw, p->d_mel_start, p->d_mel_len, p->d_mel_off,
@@ -715,6 +717,20 @@ int lipasr_mfcc_plan_resample_vjp(lipasr_mfcc_t p, const float* g_y, int batch, 
 int lipasr_mfcc_plan_profile_begin(lipasr_mfcc_t p, int max_calls) { return plan_profile_begin(p, max_calls); }
 int lipasr_mfcc_plan_profile_end(lipasr_mfcc_t p, float* avg_ms3, int* n_calls) { return plan_profile_end(p, avg_ms3, n_calls); }
 int lipasr_mfcc_plan_set(lipasr_mfcc_t p, int key, int value) { return plan_set(p, key, value); }
+
+// ---------------------------------------------------------------- test hooks of the forward pass
+long lipasr_debug_k1_launches(int kernel) { return (kernel >= 0 && kernel < K1_KERNELS) ? g_k1_launches[kernel] : -1; }
+
+int lipasr_debug_mfcc_stage(lipasr_mfcc_t p, int which, int batch, float* out, lipasr_stream_t stream) {
+  LP_CHECK_ARG(p != nullptr && out != nullptr, "lipasr_debug_mfcc_stage: null argument");
+  LP_CHECK_ARG(batch >= 1 && batch <= p->batch_max, "lipasr_debug_mfcc_stage: batch %d outside [1, %d]", batch, p->batch_max);
+  LP_CHECK_ARG(which >= 0 && which <= 2, "lipasr_debug_mfcc_stage: unknown stage %d (0 dB tile, 1 frame maxima, 2 resampled signal)", which);
+  const float* src = which == 0 ? p->d_db : which == 1 ? p->d_fmax : p->d_y;
+  const size_t row = which == 0 ? (size_t)p->n_frames * 128 : which == 1 ? (size_t)p->n_frames : (size_t)p->n_y;
+  DeviceGuard g(p->ctx->device);
+  LP_HIP(hipMemcpyAsync(out, src, (size_t)batch * row * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+  return LIPASR_OK;
+}
 
 // ---------------------------------------------------------------- the handle's default plan (round-1/2 entry points)
 int lipasr_mfcc_plan(lipasr_handle_t h, int sr_in, int n_samp, int batch_max) {

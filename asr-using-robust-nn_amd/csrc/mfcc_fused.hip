@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     lds_barrier();
     const float* rs = reinterpret_cast<const float*>(rsum);
     const float sacc = rs[2 * m + sel] + ((m > 0) ? rs[2 * (128 + m - 1) + sel] : 0.0f);
-    const float dbv = 10.0f * log10f(fmaxf(1e-10f, sacc));  // librosa.power_to_db(ref=1, amin=1e-10)
+    const float dbv = power_to_db(sacc);  // librosa.power_to_db(ref=1, amin=1e-10)
     const int f = sel ? f1 : f0;
     if (f < fe) st.db[((size_t)u * st.n_frames + f) * 128 + m] = dbv;
     const float wm = wave_max(dbv);
@@ -325,9 +325,11 @@ int launch_fused(const MfccPlan* p, const void* wav, int fmt, const int* n_valid
   if (fmt) {
     LP_DYN_LDS(mfcc_fused_kernel<true>, lds);
     hipLaunchKernelGGL(mfcc_fused_kernel<true>, dim3(p->n_groups, batch), dim3(256), lds, st, a);
+    ++g_k1_launches[K1_FUSED_I16];
   } else {
     LP_DYN_LDS(mfcc_fused_kernel<false>, lds);
     hipLaunchKernelGGL(mfcc_fused_kernel<false>, dim3(p->n_groups, batch), dim3(256), lds, st, a);
+    ++g_k1_launches[K1_FUSED_F32];
   }
   LP_LAUNCH_CHECK();
   return LIPASR_OK;

@@ -126,6 +126,13 @@ struct MfccPath {
 // that is already at 22 050 Hz
 MfccPath pick_mfcc_path(const MfccPlan* p, const void* wav, int fmt, bool ragged);
 
+// Test hook (lipasr_debug_k1_launches): launches since load per K1 forward kernel instance, counted on the host where the launch
+// happens.  The ids are part of the ABI (include/lipasr.h); K1_RESAMPLE_H2 + i is entry i of launch_resample's kerns[] table.
+enum K1Kernel { K1_RESAMPLE_H2 = 0, K1_RESAMPLE_PERSIST = 4, K1_RESAMPLE_MFMA, K1_RESAMPLE_REG128, K1_RESAMPLE_GENERIC, K1_COPY_PAD,
+                K1_CLEAR_TAIL, K1_STFT_BDFT, K1_STFT_BDFT_DCT, K1_STFT_MEL2, K1_STFT_MEL, K1_DFT_MEL, K1_DCT, K1_FUSED_F32, K1_FUSED_I16,
+                K1_KERNELS };
+extern long g_k1_launches[K1_KERNELS];  // mfcc.hip
+
 // rows of n_samp samples can be read four at a time: float4 (fmt 0) / short4 (fmt 1) aligned, a multiple of 4 samples long
 inline bool rows_vec4(const MfccPlan* p, const void* wav, int fmt) {
   return (reinterpret_cast<uintptr_t>(wav) & (fmt ? 7 : 15)) == 0 && (p->n_samp & 3) == 0;

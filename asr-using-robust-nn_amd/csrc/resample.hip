@@ -472,6 +472,7 @@ __global__ __launch_bounds__(256) void clear_tail_kernel(float* __restrict__ y, 
 
 int launch_clear_tail(const MfccPlan* p, const int* n_valid, int batch, float* y, hipStream_t st) {
   hipLaunchKernelGGL(clear_tail_kernel, dim3(32, batch), dim3(256), 0, st, y, p->n_y, n_valid, p->n_samp, p->sr_in);
+  ++g_k1_launches[K1_CLEAR_TAIL];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -545,11 +546,13 @@ int launch_resample(const MfccPlan* p, MfccPath::Resampler kind, const void* wav
       using kern_t = void (*)(const void*, const int*, int, int, int, float*, int, int, int, int, int, int, int, const uint4*, const int*, int, int);
       static const kern_t kerns[4] = {resample_persist_h2_kernel<false, false>, resample_persist_h2_kernel<true, false>,
                                       resample_persist_h2_kernel<false, true>, resample_persist_h2_kernel<true, true>};
-      const kern_t kern = kerns[(fmt ? 1 : 0) + (n_valid ? 2 : 0)];
+      const int inst = (fmt ? 1 : 0) + (n_valid ? 2 : 0);
+      const kern_t kern = kerns[inst];
       LP_DYN_LDS(kern, ldsh);
       hipLaunchKernelGGL(kern, dim3(wgs), dim3(64 * kRpMaxWaves), ldsh, st, wav_any, n_valid,
                          p->sr_in, p->n_samp, batch, y, p->n_valid, p->n_y, p->up, p->down, p->left, nq, tiles,
                          reinterpret_cast<const uint4*>(p->d_hbandh), p->d_lo, p->n_ptiles, (p->stage_mask >> SM_H2_SHIFT) & SM_H2_BITS);
+      ++g_k1_launches[K1_RESAMPLE_H2 + inst];
       break;
     }
     case MfccPath::RS_PERSIST_F32: {
@@ -558,6 +561,7 @@ int launch_resample(const MfccPlan* p, MfccPath::Resampler kind, const void* wav
       LP_DYN_LDS(resample_persist_kernel, lds);
       hipLaunchKernelGGL(resample_persist_kernel, dim3(wgs), dim3(64 * p->n_ptiles), lds, st, wav, p->n_samp, batch, y,
                          p->n_valid, p->n_y, p->up, p->down, p->left, nq, tiles, p->d_hband, p->d_lo);
+      ++g_k1_launches[K1_RESAMPLE_PERSIST];
       break;
     }
     case MfccPath::RS_MFMA: {
@@ -565,6 +569,7 @@ int launch_resample(const MfccPlan* p, MfccPath::Resampler kind, const void* wav
       LP_DYN_LDS(resample_mfma_kernel, lds);
       hipLaunchKernelGGL(resample_mfma_kernel, dim3(nq, (batch + 31) / 32), dim3(64 * kRsWaves), lds, st, wav,
                          p->n_samp, batch, y, p->n_valid, p->n_y, p->up, p->down, p->left, p->n_ptiles, p->d_hband, p->d_lo, p->stage_mask);
+      ++g_k1_launches[K1_RESAMPLE_MFMA];
       break;
     }
     case MfccPath::RS_REG128: {
@@ -572,16 +577,19 @@ int launch_resample(const MfccPlan* p, MfccPath::Resampler kind, const void* wav
       const size_t lds = (size_t)(kRsQBlocks * p->down + 128) * sizeof(float);
       hipLaunchKernelGGL(resample_reg128_kernel, dim3(nb, batch), dim3(448), lds, st, wav, p->n_samp, y, p->n_valid,
                          p->n_y, p->up, p->down, p->left, p->d_h, p->d_noff);
+      ++g_k1_launches[K1_RESAMPLE_REG128];
       break;
     }
     case MfccPath::RS_GENERIC: {
       const size_t lds = (size_t)(p->down + p->taps) * sizeof(float);
       hipLaunchKernelGGL(resample_generic_kernel, dim3(nq, batch), dim3(256), lds, st, wav, p->n_samp, y, p->n_valid,
                          p->n_y, p->up, p->down, p->left, p->taps, p->d_h, p->d_noff);
+      ++g_k1_launches[K1_RESAMPLE_GENERIC];
       break;
     }
     case MfccPath::RS_COPY:
       hipLaunchKernelGGL(copy_pad_kernel, dim3(32, batch), dim3(256), 0, st, wav, p->n_samp, y, p->n_y);
+      ++g_k1_launches[K1_COPY_PAD];
       break;
     case MfccPath::RS_NONE:
       set_error("launch_resample: no resampler was chosen");

@@ -33,6 +33,10 @@ __device__ __forceinline__ void clip_lengths(int n, int sr_in, int* n_vy, int* n
   *n_frames = (*n_y >= 2) ? 1 + *n_y / tables::kHop : 0;
 }
 
+// librosa.power_to_db(ref=1, amin=1e-10) of one mel power.  A power at or below amin is EXACTLY -100 dB, as 10 log10 of the float32
+// amin is in the reference; the device's log10f(1e-10f) is one unit in the last place off (-100.00001).
+__device__ __forceinline__ float power_to_db(float p) { return p > 1e-10f ? 10.0f * log10f(p) : -100.0f; }
+
 // np.pad(y, 1024, mode='reflect') index: position j relative to y[0], any j, n >= 2
 __device__ __forceinline__ int reflect_index(int j, int n) {
   if ((unsigned)j < (unsigned)n) return j;  // interior frames never reflect

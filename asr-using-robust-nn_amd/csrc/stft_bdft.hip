@@ -27,7 +27,7 @@
 // bins are wave-uniform lane masks in SGPRs); the scan values go to a wave-private staging slot (the ring slot this
 // wavefront overwrites next) and lane l sums the <= 6 segment ends of mel l and mel l + 64.  Two LDS-only barriers per
 // iteration (stft_mel2_kernel: eleven per frame quad).
-#include "stft.h"
+#include "mfcc_plan.h"
 
 namespace lipasr {
 
@@ -321,7 +321,7 @@ __device__ __forceinline__ float bd_frame_finish(const BdftArgs& a, float* __res
   if (lane == 0) stg[kBdDummy] = 0.0f;
   const float m0 = ((stg[mp[0] & 0xffff] + stg[mp[0] >> 16]) + stg[mp[1] & 0xffff]) + ((stg[mp[1] >> 16] + stg[mp[2] & 0xffff]) + stg[mp[2] >> 16]);
   const float m1 = ((stg[mp[3] & 0xffff] + stg[mp[3] >> 16]) + stg[mp[4] & 0xffff]) + ((stg[mp[4] >> 16] + stg[mp[5] & 0xffff]) + stg[mp[5] >> 16]);
-  const float d0 = 10.0f * log10f(fmaxf(1e-10f, m0)), d1 = 10.0f * log10f(fmaxf(1e-10f, m1));
+  const float d0 = power_to_db(m0), d1 = power_to_db(m1);
   float* dbp = a.st.db + ((size_t)u * a.st.n_frames + f) * 128;
   dbp[lane] = d0;
   dbp[lane + 64] = d1;
@@ -619,6 +619,7 @@ int launch_stft_bdft(const StftArgs& st, const BdftTables& t, int batch, int seg
   const size_t lds = (size_t)kBdLdsFloats * sizeof(float);
   LP_DYN_LDS(stft_bdft_kernel, lds);
   hipLaunchKernelGGL(stft_bdft_kernel, dim3((st.n_frames + seg_frames - 1) / seg_frames, batch), dim3(256), lds, stream, a);
+  ++g_k1_launches[a.out ? K1_STFT_BDFT_DCT : K1_STFT_BDFT];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }

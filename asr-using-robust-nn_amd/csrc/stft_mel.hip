@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void stft_mel_kernel(StftArgs a) {
   } else {
     s = sel ? T[m].y : T[m].x;
   }
-  const float dbv = 10.0f * log10f(fmaxf(1e-10f, s));  // librosa.power_to_db(ref=1, amin=1e-10)
+  const float dbv = power_to_db(s);  // librosa.power_to_db(ref=1, amin=1e-10)
   const int f = sel ? f1 : f0;
   if (f < a.n_frames) a.db[((size_t)u * a.n_frames + f) * 128 + m] = dbv;
   const float wm = wave_max(dbv);
@@ -389,8 +389,8 @@ __device__ __forceinline__ void stft2_quad(const StftArgs& a, float4* __restrict
   float4 sum = rsum[0][m];
   if (m > 0) { const float4 h2 = rsum[1][m - 1]; sum.x += h2.x; sum.y += h2.y; sum.z += h2.z; sum.w += h2.w; }
   const float se = pr ? sum.y : sum.x, so = pr ? sum.w : sum.z;  // even / odd frame of the pair
-  dbe = 10.0f * log10f(fmaxf(1e-10f, se));
-  dbo = 10.0f * log10f(fmaxf(1e-10f, so));
+  dbe = power_to_db(se);
+  dbo = power_to_db(so);
   const int fe = f0 + 2 * pr, fo = fe + 1;
   if (fe < n_frames) a.db[((size_t)u * a.n_frames + fe) * 128 + m] = dbe;
   if (fo < n_frames) a.db[((size_t)u * a.n_frames + fo) * 128 + m] = dbo;
@@ -551,7 +551,7 @@ __global__ __launch_bounds__(64 * kDftMaxTiles) __attribute__((amdgpu_waves_per_
       const float* w = a.mel_w + a.mel_off[m];
       float sacc = 0.0f;
       for (int j = 0; j < ln; ++j) sacc = fmaf(w[j], pr[st + j], sacc);
-      dbv[hmel] = 10.0f * log10f(fmaxf(1e-10f, sacc));  // librosa.power_to_db(ref=1, amin=1e-10)
+      dbv[hmel] = power_to_db(sacc);  // librosa.power_to_db(ref=1, amin=1e-10)
     }
     float* dst = a.db + ((size_t)clip * a.n_frames + frame) * 128;
     dst[lane] = dbv[0];
@@ -668,6 +668,7 @@ int launch_dct(const MfccPlan* p, int batch, int L, const double* am, const doub
   const size_t lds = (size_t)128 * (chunk + 1) * sizeof(float);
   hipLaunchKernelGGL(dct_kernel, dim3(batch, (L + chunk - 1) / chunk), dim3(128), lds, st, p->d_db, p->d_fmax, p->n_frames, L, chunk,
                      reinterpret_cast<const float4*>(p->d_dct), am, as, out, n_valid, p->n_samp, p->sr_in);
+  ++g_k1_launches[K1_DCT];
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -697,6 +698,7 @@ int launch_from_22k(const MfccPlan* p, MfccPath::Stft kind, const float* y, cons
       const size_t dl = (size_t)(n_a > n_p ? n_a : n_p) * sizeof(float);
       LP_DYN_LDS(dft_mel_kernel, dl);
       hipLaunchKernelGGL(dft_mel_kernel, dim3((d.total_rows + kDftRows - 1) / kDftRows), dim3(64 * p->dft_tiles), dl, st, d);
+      ++g_k1_launches[K1_DFT_MEL];
       break;
     }
     case MfccPath::ST_BDFT: {
@@ -714,9 +716,11 @@ int launch_from_22k(const MfccPlan* p, MfccPath::Stft kind, const float* y, cons
     }
     case MfccPath::ST_STOCKHAM4:
       hipLaunchKernelGGL(stft_mel2_kernel, dim3((p->n_frames + 3) / 4, batch), dim3(256), 0, st, a);
+      ++g_k1_launches[K1_STFT_MEL2];
       break;
     case MfccPath::ST_STOCKHAM2:
       hipLaunchKernelGGL(stft_mel_kernel, dim3((p->n_frames + 1) / 2, batch), dim3(256), 0, st, a);
+      ++g_k1_launches[K1_STFT_MEL];
       break;
   }
   LP_LAUNCH_CHECK();

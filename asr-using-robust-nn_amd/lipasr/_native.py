@@ -159,6 +159,8 @@ PROTOTYPES = {
     "lipasr_debug_gemm_launches": (C.c_long, [i32, i32, i32, i32, i32, i32]),
     "lipasr_debug_group_launches": (C.c_long, [i32, i32, i32]),
     "lipasr_debug_k3_launches": (C.c_long, [i32]),
+    "lipasr_debug_k1_launches": (C.c_long, [i32]),
+    "lipasr_debug_mfcc_stage": (i32, [c_h, i32, i32, c_f, c_s]),
     "lipasr_debug_gemm": (i32, [c_h, i32, i32, i32, i32, i32, i32, c_f, i32, c_f, i32, c_f, i32, f32, f32, c_s]),
     "lipasr_flag_signal": (i32, [c_h, C.c_void_p, i32, c_s]),
     "lipasr_flag_wait": (i32, [c_h, C.c_void_p, i32, i32, C.c_void_p, c_s]),
@@ -175,7 +177,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_psy_threshold": 590, "lipasr_psy_prepare": 590, "lipasr_psy_loss_grad": 590, "lipasr_psy_step": 590,
          "lipasr_psy_table": 590, "lipasr_deepfool_step": 600, "lipasr_smooth_expand": 610,
          "lipasr_smooth_vote": 610, "lipasr_smooth_noise_host": 610, "lipasr_genetic_breed": 620,
-         "lipasr_genetic_breed_host": 620, "lipasr_genetic_select": 620, "lipasr_debug_k3_launches": 630}
+         "lipasr_genetic_breed_host": 620, "lipasr_genetic_select": 620, "lipasr_debug_k3_launches": 630,
+         "lipasr_debug_k1_launches": 640, "lipasr_debug_mfcc_stage": 640}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 630.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 640.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -32,6 +32,8 @@
  * 620: the genetic black-box attack: lipasr_genetic_breed (one generation's children), lipasr_genetic_select (fitness, elite and
  * parent draws per clip) and the host-only lipasr_genetic_breed_host.
  * 630: test hook of the K3 projections: lipasr_debug_k3_launches (launch counters per kernel).
+ * 640: test hooks of the MFCC forward pass: lipasr_debug_k1_launches (launch counters per kernel instance) and
+ * lipasr_debug_mfcc_stage (the dB tile, the frame maxima or the resampled signal a plan's last forward call left behind).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -570,7 +572,8 @@ int lipasr_mfcc_plan(lipasr_handle_t h, int sr_in, int n_samp, int batch_max);
  * 1 <= hop <= n_fft selects the short-window path, where the windowed real DFT is an fp32 MFMA
  * contraction -- the Speaker-recognition features (Speaker recognition/
  * extract_features_construct_dataset.py:224-226: win_length=441, n_fft=441, hop_length=220 on
- * 1-s windows at 22 050 Hz -> 20 x 101 = 2020).  Other values: LIPASR_EUNSUPPORTED. */
+ * 1-s windows at 22 050 Hz -> 20 x 101 = 2020).  Other values: LIPASR_EUNSUPPORTED.  The short-window path reflects once: a clip
+ * with n_y <= n_fft / 2 is LIPASR_EINVAL ("clip shorter than the reflect padding"). */
 int lipasr_mfcc_plan_ex(lipasr_handle_t h, int sr_in, int n_samp, int batch_max, int n_fft, int hop);
 /* resampled length int(ceil(n_samp*22050/sr_in)) and frame count 1 + n_y/hop for a plan */
 int lipasr_mfcc_dims(lipasr_handle_t h, int* n_y, int* n_frames);
@@ -872,6 +875,23 @@ int lipasr_debug_gemm(lipasr_handle_t h, int arith, int transA, int transB, int 
  * 11 the Frobenius pair (sumsq_clamped_kernel + frob_scale_kernel: one count per pair), 12 bn_correction_kernel.  Returns -1 for an
  * unknown id, so a test can enumerate the kernels from the library. */
 long lipasr_debug_k3_launches(int kernel);
+
+/* Test hook: launches since the library was loaded of one kernel instance of the MFCC forward pass (K1), counted on the host where
+ * the launch happens.  kernel: 0 / 1 / 2 / 3 resample_persist_h2_kernel for float32 rows / int16 rows / float32 rows with per-clip
+ * lengths / int16 rows with per-clip lengths, 4 resample_persist_kernel, 5 resample_mfma_kernel, 6 resample_reg128_kernel,
+ * 7 resample_generic_kernel, 8 copy_pad_kernel, 9 clear_tail_kernel, 10 stft_bdft_kernel without its DCT epilogue, 11 stft_bdft_kernel
+ * with it (plan key 4), 12 stft_mel2_kernel, 13 stft_mel_kernel, 14 dft_mel_kernel, 15 dct_kernel, 16 mfcc_fused_kernel for float32
+ * rows, 17 mfcc_fused_kernel for int16 rows.  The backward pass re-running the forward counts too.  Returns -1 for an unknown id,
+ * so a test can enumerate the instances from the library. */
+long lipasr_debug_k1_launches(int kernel);
+
+/* Test hook: ONE asynchronous device-to-device copy, on `stream`, of an intermediate that the plan's last forward call left in the
+ * plan, into out (device).  which 0: the dB tile [batch][n_frames][128], 10 log10 max(1e-10, mel) BEFORE the top_db floor; which 1:
+ * the frame maxima [batch][n_frames] (the maximum over the 128 mels of each row of the tile); which 2: the resampled signal
+ * [batch][n_y] that lipasr_mfcc_extract left behind on the three-kernel path (the fused kernel writes none).  Rows and frames are
+ * laid out for the plan's n_frames / n_y; with per-clip lengths the frames past a clip's own count hold whatever an earlier call
+ * left.  LIPASR_EINVAL for a null argument, a batch outside [1, batch_max] or another `which`.  No synchronisation, no allocation. */
+int lipasr_debug_mfcc_stage(lipasr_mfcc_t p, int which, int batch, float* out, lipasr_stream_t stream);
 
 /* Profiling knob: how many of the leading (small) steps of the product chain W_m^T ... W_1^T run as ONE launch
  * (chain_head_kernel, fp32 matrix instructions): -1 = automatic (the first two steps, when their panels have <= 256 columns

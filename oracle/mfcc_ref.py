@@ -55,7 +55,7 @@ def kaiser_best_half_window():
     return (taper * sinc_win).astype(np.float64), num_bits
 
 
-def resample_kaiser_best(x: np.ndarray, sr_orig: int, sr_new: int, time_mode: str = "accumulate") -> np.ndarray:
+def resample_kaiser_best(x: np.ndarray, sr_orig: int, sr_new: int, time_mode: str = "accumulate", dtype=np.float32) -> np.ndarray:
     """resampy.resample(x, sr_orig, sr_new, filter='kaiser_best') for 1-D x, vectorised.
 
     ``time_mode='accumulate'`` follows resampy 0.2.x (time_register += 1/ratio in
@@ -63,11 +63,12 @@ def resample_kaiser_best(x: np.ndarray, sr_orig: int, sr_new: int, time_mode: st
     summed in float64 and rounded once to float32 (the reference rounds the
     running sum to float32 after every tap; the difference is ~1e-7 relative).
     Samples outside [0, n) are treated as absent, exactly like the tap-count
-    clamps ``i_max`` / ``k_max`` of resampy's loop.
+    clamps ``i_max`` / ``k_max`` of resampy's loop.  ``dtype=np.float64`` leaves out that final rounding (the float64
+    reference of the stage tests).
     """
     x = np.asarray(x)
     if sr_orig == sr_new:
-        return x.astype(np.float32, copy=True)
+        return x.astype(dtype, copy=True)
     n_orig = x.shape[0]
     sample_ratio = float(sr_new) / float(sr_orig)
     n_out = int(n_orig * sample_ratio)
@@ -121,7 +122,7 @@ def resample_kaiser_best(x: np.ndarray, sr_orig: int, sr_new: int, time_mode: st
     xi = n[:, None] + taps[None, :] + 1
     xv = xd[np.where(valid, xi, 0)]
     y += np.sum(np.where(valid, w * xv, 0.0), axis=1)
-    return y.astype(np.float32)
+    return y.astype(dtype)
 
 
 def resample_kaiser_best_loop(x, sr_orig, sr_new):
@@ -316,14 +317,17 @@ def fix_frames(m: np.ndarray, utterance_length: int) -> np.ndarray:
     return np.pad(m, ((0, 0), (0, utterance_length - m.shape[1])), mode="constant", constant_values=0)
 
 
-def librosa_load_resample(x: np.ndarray, sr_in: int, fast: bool = False) -> np.ndarray:
+def librosa_load_resample(x: np.ndarray, sr_in: int, fast: bool = False, dtype=np.float32) -> np.ndarray:
     """librosa.load's resampling step: resampy.resample then librosa.resample's
     ``util.fix_length(y_hat, int(np.ceil(n * ratio)))`` (resampy yields int(n * ratio) samples; when
-    n * ratio is not an integer librosa appends one zero sample)."""
+    n * ratio is not an integer librosa appends one zero sample).  ``dtype=np.float64``: the same samples before their
+    rounding to float32."""
     x = np.asarray(x, dtype=np.float32)
+    if fast and dtype != np.float32:
+        raise ValueError("librosa_load_resample: the fast form rounds to float32; dtype=np.float64 needs fast=False")
     if sr_in == SR_TARGET:
-        return x.copy()
-    y = resample_kaiser_best_fast(x, sr_in, SR_TARGET) if (fast and sr_in < SR_TARGET) else resample_kaiser_best(x, sr_in, SR_TARGET)
+        return x.astype(dtype)
+    y = resample_kaiser_best_fast(x, sr_in, SR_TARGET) if (fast and sr_in < SR_TARGET) else resample_kaiser_best(x, sr_in, SR_TARGET, dtype=dtype)
     n_fixed = int(np.ceil(x.shape[0] * (float(SR_TARGET) / float(sr_in))))
     if len(y) < n_fixed:
         y = np.pad(y, (0, n_fixed - len(y)))

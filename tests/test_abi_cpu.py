@@ -40,6 +40,20 @@ def test_k3_launch_counters_without_gpu():
     assert known == list(range(len(known))) and len(known) == 13  # the ids documented in include/lipasr.h, without gaps
 
 
+def test_k1_launch_counters_and_stage_hook_without_gpu():
+    """lipasr_debug_k1_launches and lipasr_debug_mfcc_stage (version 640): both exported; the counters are host-side and readable
+    without a GPU, -1 for an id that does not exist, and the known ids are exactly 0..17 as include/lipasr.h lists them; the copy
+    hook refuses a null plan before it touches a device."""
+    assert N.lib.lipasr_version() >= 640 and N.has("lipasr_debug_k1_launches") and N.has("lipasr_debug_mfcc_stage")
+    assert hasattr(N.lib, "lipasr_debug_k1_launches") and hasattr(N.lib, "lipasr_debug_mfcc_stage")
+    assert N.lib.lipasr_debug_k1_launches(0) >= 0
+    assert N.lib.lipasr_debug_k1_launches(-1) == -1 and N.lib.lipasr_debug_k1_launches(18) == -1 and N.lib.lipasr_debug_k1_launches(1000) == -1
+    known = [k for k in range(64) if N.lib.lipasr_debug_k1_launches(k) >= 0]
+    assert known == list(range(18))
+    assert N.lib.lipasr_debug_mfcc_stage(None, 0, 1, None, None) == N.EINVAL
+    assert "null argument" in N.last_error()
+
+
 def test_error_convention_without_gpu():
     assert N.lib.lipasr_create(0, None) == N.EINVAL
     assert "out is null" in N.last_error()
