@@ -110,6 +110,10 @@ PROTOTYPES = {
     "lipasr_genetic_breed": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, C.c_uint32, f32, f32, f32, f32, c_f, c_s]),
     "lipasr_genetic_breed_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, C.c_uint32, f32, f32, f32, f32, c_f]),
     "lipasr_genetic_select": (i32, [c_h, c_f, c_f, i32, i32, i32, i32, f32, C.c_uint32, C.c_uint32, u64, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_apgd_loss": (i32, [c_h, c_f, c_f, i32, i32, i32, i32, c_f, c_f, c_f, c_s]),
+    "lipasr_apgd_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, f32, f32,
+                               f32, f32, f32, f32, f32, i32, i32, c_s]),
+    "lipasr_debug_apgd_path": (i32, [i32, i32]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -178,7 +182,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_psy_table": 590, "lipasr_deepfool_step": 600, "lipasr_smooth_expand": 610,
          "lipasr_smooth_vote": 610, "lipasr_smooth_noise_host": 610, "lipasr_genetic_breed": 620,
          "lipasr_genetic_breed_host": 620, "lipasr_genetic_select": 620, "lipasr_debug_k3_launches": 630,
-         "lipasr_debug_k1_launches": 640, "lipasr_debug_mfcc_stage": 640}
+         "lipasr_debug_k1_launches": 640, "lipasr_debug_mfcc_stage": 640, "lipasr_apgd_loss": 650, "lipasr_apgd_step": 650,
+         "lipasr_debug_apgd_path": 650}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 

@@ -13,6 +13,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
     (no prompt: the Lipschitz read-outs, global and local) attack="lipschitz": lipschitz_report over="mfcc" | "audio"
     (no prompt: certified radius next to DeepFool's)       attack="radius": radius_report over="mfcc" | "audio", --norm 2 | inf
+    (no prompt: Auto-PGD, per-row step control, CE or DLR) attack="white", kind="apgd", --loss ce | dlr, --norm inf | 2, over="mfcc" | "audio"
     (no prompt: the genetic query-only attack)             attack="black", kind="genetic": genetic_sweep over="mfcc" | "audio"
     (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth":smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
 """
@@ -210,20 +211,24 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
                     points=None, limit=None, over="mfcc", test_filenames=None, domain="22k", **attack_kw):
     """attacks.py:493-693.  The models are wrapped as TensorFlowV2Classifier(model=, nb_classes=, input_shape=,
     loss_object=) (:500-504) and attacked with ART's constructor keywords; JSMA runs on the first 100 test rows (:552).
-    over="audio" (kind fgsm | pgd): the attack perturbs the audio of ``test_filenames`` through WaveformClassifier -- the 22 050 Hz
+    kind="apgd" (ours): lipasr.attacks.AutoProjectedGradientDescent on PGD's grid, ``attack_kw`` its keywords.
+    over="audio" (kind fgsm | pgd | apgd): the attack perturbs the audio of ``test_filenames`` through WaveformClassifier -- the 22 050 Hz
     signal (domain="22k", what the black-box audio noise perturbs) or the file's own samples (domain="input"); eps is an
     amplitude, iterates stay in [-1, 1].  The reference has no such sweep, so the default grid is OURS: AUDIO_SIGMAS, which lays
     the curve over black_box_sweep(over="audio", kind="simple").  Features are standardized with the statistics of (train, val,
     clean test MFCCs), fused into the extraction: the statistics black_box_sweep(over="audio") derives at sigma = 0, so the two
     sweeps agree at strength 0."""
-    if over == "audio" and kind not in ("fgsm", "pgd"):
-        raise ValueError(f"over='audio' runs kind 'fgsm' and 'pgd', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
+    if over == "audio" and kind not in ("fgsm", "pgd", "apgd"):
+        raise ValueError(f"over='audio' runs kind 'fgsm', 'pgd' and 'apgd', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
     if kind == "fgsm":
         default = np.linspace(1, 30, 50) if standardize == "after" else np.linspace(0.01, 0.3, 10)  # :497-499
         build = lambda clf, item: A.FastGradientMethod(estimator=clf, eps=item, **attack_kw)
     elif kind == "pgd":
         default = np.linspace(1, 30, 50)                                                             # :648
         build = lambda clf, item: A.ProjectedGradientDescent(estimator=clf, eps=item, **attack_kw)
+    elif kind == "apgd":  # ours: Auto-PGD (attack_kw: norm, loss_type, max_iter, nb_random_init, ...) on PGD's grid
+        default = np.linspace(1, 30, 50)
+        build = lambda clf, item: A.AutoProjectedGradientDescent(estimator=clf, eps=item, **attack_kw)
     elif kind == "jsma":
         default, limit = [10], (100 if limit is None else limit)                                     # :539, :552
         build = lambda clf, item: A.SaliencyMapMethod(classifier=clf, theta=item, gamma=0.1, **attack_kw)
@@ -533,12 +538,13 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic; white: fgsm|l2|linf|pgd|jsma|imperceptible")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic; white: fgsm|l2|linf|pgd|apgd|jsma|imperceptible")
     ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
-    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's)")
+    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); white apgd: iterations (default: 100)")
+    ap.add_argument("--loss", choices=["ce", "dlr"], default="ce", help="white apgd: cross-entropy or the Difference-of-Logits-Ratio loss")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
-    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; radius: 2 or inf")
+    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; white apgd and radius: 2 or inf")
     ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
     ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
     ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
@@ -551,6 +557,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.attack == "radius" and args.norm == "1":
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
+    if args.attack == "white" and args.kind == "apgd" and args.norm == "1":
+        raise ValueError("--kind apgd runs in --norm inf or 2")
 
     if args.attack == "smooth" and (args.sigma is None or not 0.0 <= args.sigma < float("inf")):
         raise ValueError("--attack smooth needs --sigma, the standard deviation of the noise (finite, not negative; there is no default)")
@@ -592,9 +600,13 @@ def main(argv=None):
     if args.over == "audio":
         kw.update(over="audio", test_filenames=names)
     if args.norm != "inf":
-        if args.kind not in ("fgsm", "pgd"):
-            raise ValueError("--norm applies to --kind fgsm and pgd")
+        if args.kind not in ("fgsm", "pgd", "apgd"):
+            raise ValueError("--norm applies to --kind fgsm, pgd and apgd")
         kw["norm"] = int(args.norm)
+    if args.kind == "apgd":
+        kw["loss_type"] = {"ce": "cross_entropy", "dlr": "difference_logits_ratio"}[args.loss]
+        if args.max_iter is not None:
+            kw["max_iter"] = args.max_iter
     return white_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, standardize=args.standardize,
                            points=args.points, **kw)
 

@@ -7,6 +7,8 @@ predictions, no clip_values).  Each PGD iteration is ONE native call: inference 
 backward to the input and the sign step fused into the last backward GEMM's epilogue (K4).  ART's other
 ``norm`` (1, 2), ``targeted`` and ``num_random_init`` keywords run the same call in its Lp form
 (lipasr_mlp_attack_step_lp: the step is a second launch) and a native random start (lipasr_lp_ball_init).
+``AutoProjectedGradientDescent`` (ART's name; Croce & Hein 2020) is PGD whose step size every row halves for itself, with the
+cross-entropy or the DLR loss: per iteration the estimator's forward and backward pass and two launches of ours (lipasr/apgd.py).
 The estimators live in lipasr/estimators.py (re-exported here under the same names); an attack asks its estimator for everything
 that depends on what the rows are -- shape, lengths, predictions, own labels, gradients.  The one choice made here is FGM / PGD's:
 over rows of features they run the fused native iteration, over audio the estimator's gradient and a step launch.
@@ -550,6 +552,158 @@ class ProjectedGradientDescent(_SignAttack):
 
     def __init__(self, estimator, eps=0.3, eps_step=0.1, max_iter=100, batch_size=32, norm=np.inf, targeted=False, num_random_init=0):
         super().__init__(estimator, eps, eps_step, max_iter, batch_size, norm, targeted, num_random_init)
+
+
+class AutoProjectedGradientDescent:
+    """ART AutoProjectedGradientDescent(estimator=, norm=, eps=, eps_step=, max_iter=, targeted=, nb_random_init=, batch_size=,
+    loss_type=) (Croce & Hein 2020, Auto-PGD): projected gradient ascent with momentum whose step size every input halves for
+    itself when its own loss stops improving, restarting from its own best point.  ``norm``: np.inf or 2 (1 is refused);
+    ``eps_step``: the first step size, None: the paper's 2 eps; ``loss_type``: "cross_entropy" or "difference_logits_ratio" (the
+    scale-invariant DLR loss, untargeted, at least 3 classes); ``targeted``: y holds the class to reach (required then);
+    y=None: the model's own labels.  After the ``*``, ours: ``clip_values`` (default: the estimator's; a TensorFlowV2Classifier has
+    none) and ``seed`` (of the random starts).
+
+    Over a TensorFlowV2Classifier (rows of features) or a WaveformClassifier (audio, with ``lengths=`` as PGD takes them: the
+    perturbation stays inside each clip and the rest of the row comes back bit for bit).  Per batch of min(batch_size,
+    estimator.batch_limit) rows and restart: the start is x0 (nb_random_init == 0) or a lipasr_lp_ball_init draw keyed by (seed,
+    restart, first row of the batch), clamped and masked as PGD's; then max_iter times predict_device(logits=True) -> apgd_loss ->
+    output_vjp_device(on_logits=True) -> apgd_step, the checkpoints from ``apgd_checkpoints(max_iter)``; then one last forward pass
+    and an apgd_step with LAST.  Two launches of ours per iteration besides the estimator's two passes; nothing returns to the host
+    inside a restart.  Every one of the max(1, nb_random_init) restarts runs all rows of the batch (a draw stays a function of the
+    row index); a batch whose rows are all fooled skips its remaining restarts; a fooled row keeps the first restart that fooled it,
+    any other row the restart with the highest best loss.
+
+    generate / generate_device return a NEW array: per row the most recent misclassified iterate where there is one, else the
+    iterate of highest loss.  Afterwards ``success_`` (bool), ``loss_`` (float32: the best loss of the run the row's result comes
+    from) and ``halvings_`` (int32: how often that run halved the row's step), device tensors [B].
+
+    Where this differs from ART (restated from memory of its published implementation; ART is absent: parity unpinned): ART keeps
+    ONE step size and one mean loss per batch; this class keeps them per row, as the paper and its authors' code do, so a row's
+    result does not depend on its neighbours.  Condition 1 counts an iteration as improving when its loss exceeds the PREVIOUS
+    iterate's, as the paper words it.  After a restart from the best point the momentum term is zero for one step."""
+
+    _UNSET = object()
+
+    def __init__(self, estimator, norm=np.inf, eps=0.3, eps_step=None, max_iter=100, targeted=False, nb_random_init=5, batch_size=32,
+                 loss_type="cross_entropy", *, clip_values=_UNSET, seed=0):
+        from .apgd import _loss_code, apgd_checkpoints
+
+        if not isinstance(estimator, (TensorFlowV2Classifier, WaveformClassifier)):
+            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        self.norm = _norm_value(norm)
+        if self.norm == 1.0:
+            raise ValueError("norm=1: Auto-PGD runs in norm 2 or np.inf")
+        self.estimator, self.eps = estimator, float(eps)
+        self.eps_step = 2.0 * self.eps if eps_step is None else float(eps_step)
+        if not (0.0 <= self.eps < math.inf and 0.0 <= self.eps_step < math.inf):
+            raise ValueError(f"eps = {eps}, eps_step = {eps_step}: finite, non-negative numbers are required")
+        self.max_iter, self.batch_size, self.nb_random_init = int(max_iter), int(batch_size), int(nb_random_init)
+        if self.max_iter < 1 or self.batch_size < 1 or self.nb_random_init < 0:
+            raise ValueError("max_iter >= 1, batch_size >= 1 and nb_random_init >= 0 are required")
+        self.targeted, self.loss_type = bool(targeted), loss_type
+        self._loss = _loss_code(loss_type)
+        if not 1 <= estimator.nb_classes <= 32:
+            raise ValueError(f"{estimator.nb_classes} classes; 1 to 32 are supported")
+        if self._loss == 1 and self.targeted:
+            raise ValueError("loss_type='difference_logits_ratio' is untargeted only")
+        if self._loss == 1 and estimator.nb_classes < 3:
+            raise ValueError(f"loss_type='difference_logits_ratio' needs at least 3 classes, the estimator has {estimator.nb_classes}")
+        if clip_values is AutoProjectedGradientDescent._UNSET:
+            clip_values = estimator.clip_values
+        if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
+            raise ValueError(f"clip_values = {clip_values}")
+        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self.seed = (0xA9D0000000000000 + int(seed)) & 0xFFFFFFFFFFFFFFFF
+        self._ckpt = {}
+        prev = 0
+        for w in apgd_checkpoints(self.max_iter):
+            self._ckpt[w], prev = w - prev, w
+        self.success_ = self.loss_ = self.halvings_ = None
+
+    def _labels(self, xt, yt, lt, bs):
+        if yt is None:
+            if self.targeted:
+                raise ValueError("Target labels `y` need to be provided for a targeted attack.")
+            yt = self.estimator.own_labels_device(xt, lengths=lt, batch=bs)
+        yt = yt.to(xt.device)
+        lab = yt.argmax(dim=1) if yt.dim() == 2 else yt
+        if tuple(lab.shape) != (xt.shape[0],):
+            raise ValueError(f"y must be one-hot [B, classes] or class indices [B], got {tuple(yt.shape)}")
+        return lab.to(torch.int32).contiguous()
+
+    def _start(self, x, x0, restart, row0, mask):
+        if self.nb_random_init == 0:
+            x.copy_(x0)
+            return
+        key = (self.seed + 0x9E3779B97F4A7C15 * (restart + 1) + 0xBF58476D1CE4E5B9 * row0) & 0xFFFFFFFFFFFFFFFF  # as _SignAttack's
+        h = N.get_handle(x.device.index)
+        N.check(N.lib.lipasr_lp_ball_init(h.h, N.ptr(x), N.ptr(x0), x.shape[0], x.shape[1], self.norm, self.eps, key, None, 0,
+                                          N.stream_ptr()))
+        inside = x if self.clip_values is None else x.clamp(*self.clip_values)
+        x.copy_(inside if mask is None else torch.where(mask, inside, x0))
+
+    def _run(self, x0, lab, lb, mask, nv, restart, row0):
+        """One restart over the rows x0 -> (x_best, x_adv, state)."""
+        from .apgd import apgd_loss, apgd_state, apgd_step
+
+        est = self.estimator
+        b, dev = x0.shape[0], x0.device
+        x = torch.empty_like(x0)
+        self._start(x, x0, restart, row0, mask)
+        x_prev, x_best, g_best, x_adv = x0.clone(), x0.clone(), torch.zeros_like(x0), x0.clone()
+        f, hit = torch.empty(b, device=dev), torch.empty(b, dtype=torch.int32, device=dev)
+        dz = torch.empty(b, est.nb_classes, device=dev)
+        state = apgd_state(b, dev)
+        kw = dict(norm=self.norm, eps=self.eps, eta0=self.eps_step, clip_values=self.clip_values, n_valid=nv)
+        g = None
+        for k in range(self.max_iter):
+            apgd_loss(est.predict_device(x, logits=True, lengths=lb), lab, self._loss, self.targeted, f=f, dz=dz, hit=hit)
+            g = est.output_vjp_device(x, dz, on_logits=True, lengths=lb)
+            apgd_step(x, x_prev, x0, g, x_best, g_best, x_adv, f, hit, state, first=k == 0, ckpt_len=self._ckpt.get(k, 0), **kw)
+        apgd_loss(est.predict_device(x, logits=True, lengths=lb), lab, self._loss, self.targeted, f=f, dz=dz, hit=hit)
+        apgd_step(x, x_prev, x0, g, x_best, g_best, x_adv, f, hit, state, last=True, **kw)
+        return x_best, x_adv, state
+
+    def generate_device(self, xt, yt=None, lengths=None):
+        """xt: float32 device tensor [B, features or samples]; yt: one-hot [B, classes], class indices [B] or None; returns a NEW
+        device tensor (the input is left untouched)."""
+        est = self.estimator
+        lt = est.lengths_device(lengths, len(xt))
+        xt = est.rows_device(xt)
+        b, dev = xt.shape[0], xt.device
+        bs = min(self.batch_size, int(est.batch_limit))
+        lab_all = self._labels(xt, yt, lt, bs)
+        mask_all = None if lt is None else est.clip_mask(lt)
+        adv = xt.clone()
+        self.success_ = torch.zeros(b, dtype=torch.bool, device=dev)
+        self.loss_ = torch.full((b,), -math.inf, device=dev)
+        self.halvings_ = torch.zeros(b, dtype=torch.int32, device=dev)
+        if b == 0 or xt.shape[1] == 0:
+            return adv
+        for s in range(0, b, bs):
+            x0 = xt[s:s + bs]
+            lb = None if lt is None else lt[s:s + bs]
+            mask = None if mask_all is None else mask_all[s:s + bs]
+            nv = None if mask is None else mask.sum(dim=1).to(torch.int32).contiguous()
+            done = torch.zeros(x0.shape[0], dtype=torch.bool, device=dev)
+            for r in range(max(1, self.nb_random_init)):
+                if r > 0 and bool(done.all()):
+                    break
+                x_best, x_adv, st = self._run(x0, lab_all[s:s + bs], lb, mask, nv, r, s)
+                fooled = st["fooled"] != 0
+                take = fooled | (st["f_best"] > self.loss_[s:s + bs]) if r > 0 else torch.ones_like(done)
+                take = take & ~done
+                adv[s:s + bs] = torch.where(take[:, None], torch.where(fooled[:, None], x_adv, x_best), adv[s:s + bs])
+                self.loss_[s:s + bs] = torch.where(take, st["f_best"], self.loss_[s:s + bs])
+                self.halvings_[s:s + bs] = torch.where(take, st["halvings"], self.halvings_[s:s + bs])
+                done = done | fooled
+            self.success_[s:s + bs] = done
+        return adv
+
+    def generate(self, x, y=None, lengths=None):
+        xt = _to_dev(x)
+        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
+        return _as_given(self.generate_device(xt, yt, lengths), x)
 
 
 def deepfool_step(jac, out, label, x, norm=2, overshoot=0.02, clip_values=None, allowed=None):

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 640.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 650.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -34,6 +34,8 @@
  * 630: test hook of the K3 projections: lipasr_debug_k3_launches (launch counters per kernel).
  * 640: test hooks of the MFCC forward pass: lipasr_debug_k1_launches (launch counters per kernel instance) and
  * lipasr_debug_mfcc_stage (the dB tile, the frame maxima or the resampled signal a plan's last forward call left behind).
+ * 650: Auto-PGD: lipasr_apgd_loss (cross-entropy or DLR with its gradient at the logits), lipasr_apgd_step (one iteration with a
+ * step size, best point and checkpoint decisions per row) and the host-only lipasr_debug_apgd_path.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -536,6 +538,74 @@ int lipasr_genetic_select(lipasr_handle_t h, const float* logits, const int* lab
                           int targeted, float temperature, uint32_t clip0, uint32_t generation, uint64_t seed,
                           float* fitness /* [batch][pop] */, int* best /* [batch] */, int* done /* [batch] */,
                           int* parents /* [batch][pop][2] */, lipasr_stream_t stream);
+
+/* (ours: the reference's strongest first-order attack is fixed-step PGD on the cross-entropy; this is Auto-PGD of Croce & Hein 2020,
+ * "Reliable evaluation of adversarial robustness with an ensemble of diverse parameter-free attacks", ART's
+ * AutoProjectedGradientDescent)  The objective to MAXIMISE and its gradient at the logits, per row of logits [batch][classes], in one
+ * launch; y = labels[b].  The arithmetic is fp64 on the fp32 logits, rounded once.
+ *   - loss_type 0, cross-entropy.  Untargeted: f = logsumexp(z) - z_y, dz = softmax(z) - e_y.  Targeted (the label is the target):
+ *     f = -(logsumexp(z) - z_t), dz = e_t - softmax(z).  (logsumexp as m + log1p(sum_{c != argmax} exp(z_c - m)) and the entry at the
+ *     label as -+ sum_{c != y} softmax_c: neither cancels.)
+ *   - loss_type 1, the Difference-of-Logits-Ratio, untargeted only, classes >= 3.  pi sorts z in descending order, the lowest index
+ *     first on ties; o = argmax_{i != y} z_i (the lowest index on a tie).  D = z_pi1 - z_pi3 + 1e-12, N = z_y - z_o, f = -N / D;
+ *     dz gets -1/D at y, +1/D at o, +N/D^2 added at pi1 and -N/D^2 added at pi3; the contributions add where indices coincide.
+ *     With targeted != 0, or fewer than 3 classes: LIPASR_EINVAL.
+ *   - hit[b] = 1 if argmax z (the lowest index on a tie) != y when untargeted, == t when targeted; else 0.
+ *   - a NaN or +-inf anywhere in a row, or a label outside [0, classes): f = NaN, dz = 0 and hit = 0 for that row only; nothing is
+ *     read out of bounds.
+ * 1 <= classes <= 32, loss_type 0 or 1, or LIPASR_EINVAL; batch == 0 returns LIPASR_OK; null pointers are refused before the device
+ * is touched.  One thread per row, every sum over the classes in index order: two runs give the same bits.  No atomics, no
+ * workspace. */
+int lipasr_apgd_loss(lipasr_handle_t h, const float* logits /* [batch][classes] */, const int* labels /* [batch] */, int batch,
+                     int classes, int loss_type, int targeted, float* f /* [batch] */, float* dz /* [batch][classes] */,
+                     int* hit /* [batch] */, lipasr_stream_t stream);
+
+#define LIPASR_APGD_FIRST 1 /* flags bit 0: the first iteration of a run (the state is initialised, a = 1) */
+#define LIPASR_APGD_LAST  2 /* flags bit 1: bookkeeping only, after the last forward pass */
+/* One Auto-PGD iteration for every row, in place, in one launch.  Row arrays [rows][n], float32: x (in/out, the iterate x_k), x_prev
+ * (in/out, the previous iterate), x0 (in, the clean row), g (in, the gradient of f at x; NaN entries count as 0), x_best and g_best
+ * (in/out, the best point and its gradient), x_adv (in/out, the most recent iterate that hit).  Per row: f and hit at x (from
+ * lipasr_apgd_loss), n_valid or NULL (as lipasr_genetic_breed takes it: nv = min(max(n_valid, 0), n), NULL: nv = n), and the state
+ * eta, f_best, f_prev, f_best_ckpt (float32), improved, reduced_last, fooled, halvings (int32).  Scalars: norm (2.0f or +INFINITY,
+ * anything else LIPASR_EINVAL), eps (finite, >= 0), eta0 (finite, >= 0), clip_lo <= clip_hi (-INFINITY / +INFINITY: none), momentum
+ * and rho (in [0, 1]; the paper's are 0.75 and 0.75), flags (LIPASR_APGD_FIRST | LIPASR_APGD_LAST) and ckpt_len (0: this iteration
+ * is no checkpoint; otherwise the number of iterations since the previous checkpoint; never together with FIRST).
+ * Per row, in this order:
+ *   1. Bookkeeping at x.  With FIRST: eta = eta0, f_best = f_prev = f_best_ckpt = f, improved = reduced_last = fooled = halvings = 0,
+ *      x_best <- x, g_best <- g (the state arrays and x_prev are not read).  Otherwise: if f > f_prev then improved++; then
+ *      f_prev = f; if f > f_best then f_best = f, x_best <- x, g_best <- g.  A NaN f compares false everywhere; at FIRST it is
+ *      stored as -inf.  In both cases hit sets fooled = 1 (sticky) and x_adv <- x.
+ *   2. LAST: stop here; nothing else is written.
+ *   3. Checkpoint (ckpt_len > 0).  Condition 1: improved < rho * ckpt_len (the product in fp64).  Condition 2: reduced_last == 0 &&
+ *      f_best_ckpt == f_best.  If either holds: eta /= 2 and halvings++, the step below starts from (x_best, g_best) with
+ *      x_prev := x_best -- the paper's Algorithm 1 leaves the momentum term after a restart open; here it is zero on that step --
+ *      and reduced_last = 1.  If neither holds: reduced_last = 0, and the step starts from (x, g).  In either case improved = 0 and
+ *      f_best_ckpt = f_best.
+ *   4. The step from (xc, gc, xp): d = sign(gc) (inf; sign(0) = 0) or gc / (||gc||_2 + 1e-7) (2; a non-finite norm gives d = 0, as
+ *      lipasr_lp_step does);  z = P(xc + eta d);  x_new = P(xc + a (z - xc) + (1 - a)(xc - xp)), a = 1 on FIRST and momentum
+ *      otherwise;  P(v): u = clamp(v, clip_lo, clip_hi), then x0 + clamp(u - x0, -eps, eps) (inf) or
+ *      x0 + (u - x0) min(1, eps / (||u - x0||_2 + 1e-7)) (2).  With x0 inside the clip range the result is inside both the ball and
+ *      the range.  Then x_prev <- xc and x <- x_new.  The element-wise arithmetic and the norms are fp64 on the fp32 inputs and
+ *      x_new is rounded once, so P returns the bits of a point that already is x0 +- eps.
+ *   5. Padding.  Columns k >= nv take no part in any norm, and in every array written (x, x_prev, and x_best, g_best, x_adv where
+ *      step 1 copies) they hold the bits of x0[k]: a ragged clip's padding never moves.  A row with nv == 0 only does step 1.
+ * Any n, any alignment: a thread owns the same elements whatever the alignment (float4 loads where n is a multiple of 4 and all
+ * seven row arrays sit on 16 bytes, scalars otherwise), so the values do not depend on it.  One wavefront per row with the step's
+ * four row arrays in registers up to n = 2 048, one workgroup per row with the row held once in registers up to n = 22 528 (the
+ * three dependent norms through LDS), a re-reading form of the same arithmetic beyond; lipasr_debug_apgd_path names the instance.
+ * Every reduction runs in a fixed order: two runs give the same bits.  No atomics, no workspace, nothing waits on another
+ * workgroup.  rows == 0 or n == 0 return LIPASR_OK; null pointers (n_valid excepted) are refused before the device is touched; two
+ * arrays that overlap, one of them written, are LIPASR_EINVAL. */
+int lipasr_apgd_step(lipasr_handle_t h, float* x, float* x_prev, const float* x0, const float* g, float* x_best, float* g_best,
+                     float* x_adv, const float* f /* [rows] */, const int* hit /* [rows] */, const int* n_valid /* [rows] or NULL */,
+                     float* eta, float* f_best, float* f_prev, float* f_best_ckpt, int* improved, int* reduced_last, int* fooled,
+                     int* halvings, int rows, int n, float norm, float eps, float eta0, float clip_lo, float clip_hi, float momentum,
+                     float rho, int flags, int ckpt_len, lipasr_stream_t stream);
+/* Host-only (no GPU needed): the instance lipasr_apgd_step takes for rows of n floats.  Bits 0-2: 0 .. 3 a wavefront per row with
+ * 1 / 2 / 4 / 8 quads per lane (n <= 256, 512, 1 024, 2 048); 4 .. 6 a workgroup per row with 4 / 8 / 11 quads per thread
+ * (n <= 8 192, 16 384, 22 528); 7 the re-reading fallback.  Bit 3: float4 loads (aligned != 0: every row array on 16 bytes, and n a
+ * multiple of 4); it changes the loads inside an instance, never the instance.  n <= 0: -1. */
+int lipasr_debug_apgd_path(int n, int aligned);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
