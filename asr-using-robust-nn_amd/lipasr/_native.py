@@ -114,6 +114,12 @@ PROTOTYPES = {
     "lipasr_apgd_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, f32, f32,
                                f32, f32, f32, f32, f32, i32, i32, c_s]),
     "lipasr_debug_apgd_path": (i32, [i32, i32]),
+    "lipasr_square_init": (i32, [c_h, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, f32, f32, f32, c_f, c_f, c_f, c_s]),
+    "lipasr_square_step": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_uint32, i32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 i32, u64, f32, f32, f32, c_f, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_square_init_host": (i32, [c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, f32, f32, f32, c_f, c_f, c_f]),
+    "lipasr_square_step_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_uint32, i32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      i32, u64, f32, f32, f32, c_f, c_f, c_f, c_f, c_f]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -183,7 +189,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_smooth_vote": 610, "lipasr_smooth_noise_host": 610, "lipasr_genetic_breed": 620,
          "lipasr_genetic_breed_host": 620, "lipasr_genetic_select": 620, "lipasr_debug_k3_launches": 630,
          "lipasr_debug_k1_launches": 640, "lipasr_debug_mfcc_stage": 640, "lipasr_apgd_loss": 650, "lipasr_apgd_step": 650,
-         "lipasr_debug_apgd_path": 650}
+         "lipasr_debug_apgd_path": 650, "lipasr_square_init": 660, "lipasr_square_step": 660, "lipasr_square_init_host": 660,
+         "lipasr_square_step_host": 660}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -431,6 +438,65 @@ def genetic_breed_host(x0, pop, generation, seed, mutate_thresh, step, eps, *, p
                                         int(mutate_thresh), float(step), float(eps), float(clip_lo), float(clip_hi),
                                         C.c_void_p(out.ctypes.data)))
     return out
+
+
+SQUARE_LAST = 1
+
+
+def _host_array(a, dtype, shape, what):
+    import numpy as np
+
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == tuple(shape) and a.flags.c_contiguous and a.flags.writeable):
+        raise ValueError(f"{what} must be a contiguous writeable {np.dtype(dtype).name} array {tuple(shape)}")
+    return C.c_void_p(a.ctypes.data)
+
+
+def square_init_host(x0, height, width, restart, seed, eps, *, n_valid=None, clip0=0, clip_lo=-float("inf"), clip_hi=float("inf"),
+                     x_best=None, x_cand=None, win=None):
+    """Host-only: lipasr_square_init_host on NumPy arrays (x0 float32 [B, height * width], n_valid int32 [B] or None)
+    -> (x_best, x_cand float32 [B, n], win int32 [B, 4]): the bits lipasr_square_init writes on the device."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float32)
+    b, n = x0.shape
+    height, width = int(height), int(width)
+    if height * width != n:
+        raise ValueError(f"{height} x {width} is not the row length {n}")
+    nv = None if n_valid is None else np.ascontiguousarray(n_valid, dtype=np.int32).reshape(b)
+    x_best = np.zeros((b, n), dtype=np.float32) if x_best is None else x_best
+    x_cand = np.zeros((b, n), dtype=np.float32) if x_cand is None else x_cand
+    win = np.zeros((b, 4), dtype=np.int32) if win is None else win
+    check(lib.lipasr_square_init_host(C.c_void_p(x0.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data), b, height, width,
+                                      int(clip0), int(restart), int(seed) & 0xFFFFFFFFFFFFFFFF, float(eps), float(clip_lo),
+                                      float(clip_hi), _host_array(x_best, np.float32, (b, n), "x_best"),
+                                      _host_array(x_cand, np.float32, (b, n), "x_cand"), _host_array(win, np.int32, (b, 4), "win")))
+    return x_best, x_cand, win
+
+
+def square_step_host(logits, labels, x0, height, width, win_h, win_w, p_q, restart, it, seed, eps, *, x_best, x_cand, loss_best, done,
+                     win, n_valid=None, targeted=False, last=False, clip0=0, clip_lo=-float("inf"), clip_hi=float("inf")):
+    """Host-only: lipasr_square_step_host on NumPy arrays, in place on x_best, x_cand float32 [B, n], loss_best float32 [B], done
+    int32 [B] and win int32 [B, 4]; logits float32 [B, classes], labels int32 [B]: the bits lipasr_square_step writes."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float32)
+    b, n = x0.shape
+    height, width = int(height), int(width)
+    if height * width != n:
+        raise ValueError(f"{height} x {width} is not the row length {n}")
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    if logits.ndim != 2 or logits.shape[0] != b:
+        raise ValueError(f"logits must be [{b}, classes], got {logits.shape}")
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(b)
+    nv = None if n_valid is None else np.ascontiguousarray(n_valid, dtype=np.int32).reshape(b)
+    check(lib.lipasr_square_step_host(C.c_void_p(logits.ctypes.data), C.c_void_p(labels.ctypes.data), C.c_void_p(x0.ctypes.data),
+                                      None if nv is None else C.c_void_p(nv.ctypes.data), b, logits.shape[1], height, width, int(win_h),
+                                      int(win_w), int(p_q), 1 if targeted else 0, int(clip0), int(restart), int(it),
+                                      SQUARE_LAST if last else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, float(eps), float(clip_lo),
+                                      float(clip_hi), _host_array(x_best, np.float32, (b, n), "x_best"),
+                                      _host_array(x_cand, np.float32, (b, n), "x_cand"),
+                                      _host_array(loss_best, np.float32, (b,), "loss_best"), _host_array(done, np.int32, (b,), "done"),
+                                      _host_array(win, np.int32, (b, 4), "win")))
 
 
 def debug_table(which: int, sr_in: int = 16000):

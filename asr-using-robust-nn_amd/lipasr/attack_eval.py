@@ -15,6 +15,8 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: certified radius next to DeepFool's)       attack="radius": radius_report over="mfcc" | "audio", --norm 2 | inf
     (no prompt: Auto-PGD, per-row step control, CE or DLR) attack="white", kind="apgd", --loss ce | dlr, --norm inf | 2, over="mfcc" | "audio"
     (no prompt: the genetic query-only attack)             attack="black", kind="genetic": genetic_sweep over="mfcc" | "audio"
+    (no prompt: Square Attack, one score query per step)   attack="black", kind="square": square_sweep over="mfcc" | "audio"
+    (no prompt: the AutoAttack ensemble, robust accuracy)  attack="white", kind="auto", --norm inf | 2, over="mfcc" | "audio"
     (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth":smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
 """
 from __future__ import annotations
@@ -212,14 +214,16 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
     """attacks.py:493-693.  The models are wrapped as TensorFlowV2Classifier(model=, nb_classes=, input_shape=,
     loss_object=) (:500-504) and attacked with ART's constructor keywords; JSMA runs on the first 100 test rows (:552).
     kind="apgd" (ours): lipasr.attacks.AutoProjectedGradientDescent on PGD's grid, ``attack_kw`` its keywords.
-    over="audio" (kind fgsm | pgd | apgd): the attack perturbs the audio of ``test_filenames`` through WaveformClassifier -- the 22 050 Hz
+    kind="auto" (ours): lipasr.attacks.AutoAttack on PGD's grid (the first step size 2 eps, the paper's, unless ``attack_kw`` gives
+    eps_step; MFCC rows are SquareAttack's 20 x frames picture, audio rows a strip): the accuracy that survives all its members.
+    over="audio" (kind fgsm | pgd | apgd | auto): the attack perturbs the audio of ``test_filenames`` through WaveformClassifier -- the 22 050 Hz
     signal (domain="22k", what the black-box audio noise perturbs) or the file's own samples (domain="input"); eps is an
     amplitude, iterates stay in [-1, 1].  The reference has no such sweep, so the default grid is OURS: AUDIO_SIGMAS, which lays
     the curve over black_box_sweep(over="audio", kind="simple").  Features are standardized with the statistics of (train, val,
     clean test MFCCs), fused into the extraction: the statistics black_box_sweep(over="audio") derives at sigma = 0, so the two
     sweeps agree at strength 0."""
-    if over == "audio" and kind not in ("fgsm", "pgd", "apgd"):
-        raise ValueError(f"over='audio' runs kind 'fgsm', 'pgd' and 'apgd', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
+    if over == "audio" and kind not in ("fgsm", "pgd", "apgd", "auto"):
+        raise ValueError(f"over='audio' runs kind 'fgsm', 'pgd', 'apgd' and 'auto', not {kind!r} (C&W and JSMA perturb the MFCC vector only)")
     if kind == "fgsm":
         default = np.linspace(1, 30, 50) if standardize == "after" else np.linspace(0.01, 0.3, 10)  # :497-499
         build = lambda clf, item: A.FastGradientMethod(estimator=clf, eps=item, **attack_kw)
@@ -229,6 +233,9 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
     elif kind == "apgd":  # ours: Auto-PGD (attack_kw: norm, loss_type, max_iter, nb_random_init, ...) on PGD's grid
         default = np.linspace(1, 30, 50)
         build = lambda clf, item: A.AutoProjectedGradientDescent(estimator=clf, eps=item, **attack_kw)
+    elif kind == "auto":  # ours: the AutoAttack ensemble (attack_kw: norm, eps_step, attacks, batch_size, seed) on PGD's grid
+        default = np.linspace(1, 30, 50)
+        build = lambda clf, item: A.AutoAttack(clf, eps=item, **{"eps_step": 2.0 * item, "shape": _picture(clf, over), **attack_kw})
     elif kind == "jsma":
         default, limit = [10], (100 if limit is None else limit)                                     # :539, :552
         build = lambda clf, item: A.SaliencyMapMethod(classifier=clf, theta=item, gamma=0.1, **attack_kw)
@@ -270,15 +277,14 @@ def white_box_sweep(models, train_data, val_data, test_data, test_labels, kind="
 GENETIC_AUDIO_EPS = [0.002, 0.004, 0.01, 0.02, 0.05]
 
 
-def genetic_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
-                  domain="22k", grid=None, points=None, limit=None, **attack_kw):
-    """The genetic black-box attack (lipasr.attacks.GeneticAttack: scores only, no gradient) against its L-inf radius eps, untargeted,
-    from each model's own predictions: per model and eps the accuracy on the attacked rows and the mean number of queries the
-    successful clips took.  over="mfcc": the rows of ``test_data`` (standardize as in white_box_sweep; the default grid is its FGSM
-    grid); over="audio": the audio of ``test_filenames`` through WaveformClassifier, prepared as in white_box_sweep(over="audio")
-    (default grid GENETIC_AUDIO_EPS, amplitudes; iterates stay in [-1, 1]).  ``attack_kw``: GeneticAttack's keywords (pop_size,
-    max_iter, mutation_p, ...).  A query-only attack that ends BELOW the gradient attacks' accuracy at the same eps says that the
-    gradients are masked.  Returns (grid, {model name: accuracies}, {model name: mean queries of the successful clips, nan if none})."""
+def _picture(clf, over):
+    """SquareAttack's ``shape`` for the rows of ``clf``: 20 coefficients x frames for MFCC rows, a strip (None) for audio."""
+    return (20, clf.input_shape[0] // 20) if over == "mfcc" else None
+
+
+def _query_sweep(build, what, models, train_data, val_data, test_data, test_labels, over, standardize, test_filenames, domain, grid,
+                 points, limit):
+    """What genetic_sweep and square_sweep share: ``build(clf, eps)`` makes the attack, which leaves success_ and queries_ behind."""
     rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
     labels = rows.limited(test_labels)
     if over == "audio":
@@ -292,7 +298,7 @@ def genetic_sweep(models, train_data, val_data, test_data, test_labels, over="mf
             pred = np.zeros((rows.n, labels.shape[1]))
             ok, q = np.zeros(rows.n, dtype=bool), np.zeros(rows.n, dtype=np.int64)
             for clf, x, lt, idx in rows.batches(model):
-                atk = A.GeneticAttack(clf, item, **attack_kw)
+                atk = build(clf, item)
                 if over == "audio":
                     adv = atk.generate_device(x, None, lengths=lt)
                     pred[idx] = clf.predict_device(adv, lengths=lt).cpu().numpy()
@@ -306,9 +312,32 @@ def genetic_sweep(models, train_data, val_data, test_data, test_labels, over="mf
             mean_q = float(np.mean(q[ok])) if ok.any() else float("nan")
             acc[name].append(a)
             queries[name].append(mean_q)
-            print(f"Accuracy on genetic black-box {'audio ' if over == 'audio' else ''}test examples{_tag(name)}: {a * 100}% ({item}); "
+            print(f"Accuracy on {what} black-box {'audio ' if over == 'audio' else ''}test examples{_tag(name)}: {a * 100}% ({item}); "
                   f"{int(ok.sum())} of {len(ok)} clips succeeded, mean queries of those: {mean_q}")
     return grid, {k: np.asarray(v) for k, v in acc.items()}, {k: np.asarray(v) for k, v in queries.items()}
+
+
+def genetic_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
+                  domain="22k", grid=None, points=None, limit=None, **attack_kw):
+    """The genetic black-box attack (lipasr.attacks.GeneticAttack: scores only, no gradient) against its L-inf radius eps, untargeted,
+    from each model's own predictions: per model and eps the accuracy on the attacked rows and the mean number of queries the
+    successful clips took.  over="mfcc": the rows of ``test_data`` (standardize as in white_box_sweep; the default grid is its FGSM
+    grid); over="audio": the audio of ``test_filenames`` through WaveformClassifier, prepared as in white_box_sweep(over="audio")
+    (default grid GENETIC_AUDIO_EPS, amplitudes; iterates stay in [-1, 1]).  ``attack_kw``: GeneticAttack's keywords (pop_size,
+    max_iter, mutation_p, ...).  A query-only attack that ends BELOW the gradient attacks' accuracy at the same eps says that the
+    gradients are masked.  Returns (grid, {model name: accuracies}, {model name: mean queries of the successful clips, nan if none})."""
+    return _query_sweep(lambda clf, item: A.GeneticAttack(clf, item, **attack_kw), "genetic", models, train_data, val_data, test_data,
+                        test_labels, over, standardize, test_filenames, domain, grid, points, limit)
+
+
+def square_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
+                 domain="22k", grid=None, points=None, limit=None, **attack_kw):
+    """Square Attack (lipasr.attacks.SquareAttack: one score query per iteration, no gradient) against its L-inf radius eps, as
+    genetic_sweep runs GeneticAttack: the same rows, the same grids, the same return triple with the mean queries of the successful
+    clips.  MFCC rows are 20 x frames pictures, audio rows strips with their lengths.  ``attack_kw``: SquareAttack's keywords
+    (max_iter, p_init, nb_restarts, ...)."""
+    return _query_sweep(lambda clf, item: A.SquareAttack(clf, eps=item, **{"shape": _picture(clf, over), **attack_kw}), "square", models,
+                        train_data, val_data, test_data, test_labels, over, standardize, test_filenames, domain, grid, points, limit)
 
 
 def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, grid=DOLPHIN_CARRIER_LEVELS, a1=1.0, a2=0.5,
@@ -538,13 +567,13 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic; white: fgsm|l2|linf|pgd|apgd|jsma|imperceptible")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square; white: fgsm|l2|linf|pgd|apgd|auto|jsma|imperceptible")
     ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
-    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); white apgd: iterations (default: 100)")
+    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); black square: queries per clip (default: SquareAttack's); white apgd: iterations (default: 100)")
     ap.add_argument("--loss", choices=["ce", "dlr"], default="ce", help="white apgd: cross-entropy or the Difference-of-Logits-Ratio loss")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
-    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; white apgd and radius: 2 or inf")
+    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; white apgd, auto and radius: 2 or inf")
     ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
     ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
     ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
@@ -557,8 +586,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.attack == "radius" and args.norm == "1":
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
-    if args.attack == "white" and args.kind == "apgd" and args.norm == "1":
-        raise ValueError("--kind apgd runs in --norm inf or 2")
+    if args.attack == "white" and args.kind in ("apgd", "auto") and args.norm == "1":
+        raise ValueError(f"--kind {args.kind} runs in --norm inf or 2")
 
     if args.attack == "smooth" and (args.sigma is None or not 0.0 <= args.sigma < float("inf")):
         raise ValueError("--attack smooth needs --sigma, the standard deviation of the noise (finite, not negative; there is no default)")
@@ -575,6 +604,10 @@ def main(argv=None):
             kw = {k: v for k, v in (("pop_size", args.pop_size), ("max_iter", args.max_iter)) if v is not None}
             return genetic_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
                                  test_filenames=names, points=args.points, **kw)
+        if args.kind == "square":
+            kw = {} if args.max_iter is None else dict(max_iter=args.max_iter)
+            return square_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
+                                test_filenames=names, points=args.points, **kw)
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
     if args.attack == "lipschitz":
@@ -600,8 +633,8 @@ def main(argv=None):
     if args.over == "audio":
         kw.update(over="audio", test_filenames=names)
     if args.norm != "inf":
-        if args.kind not in ("fgsm", "pgd", "apgd"):
-            raise ValueError("--norm applies to --kind fgsm, pgd and apgd")
+        if args.kind not in ("fgsm", "pgd", "apgd", "auto"):
+            raise ValueError("--norm applies to --kind fgsm, pgd, apgd and auto")
         kw["norm"] = int(args.norm)
     if args.kind == "apgd":
         kw["loss_type"] = {"ce": "cross_entropy", "dlr": "difference_logits_ratio"}[args.loss]

@@ -20,7 +20,10 @@ each clip and the rest of the row comes back untouched.  Over a short-window ext
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.  ``GeneticAttack`` (lipasr/genetic.py,
-ours) is the one black-box attack that looks at the model's answer: a genetic algorithm over score queries.
+ours) and ``SquareAttack`` (lipasr/square.py; ART's name, Andriushchenko et al. 2020) are the black-box attacks that look at the
+model's answer: a genetic algorithm with pop_size score queries per generation, and a random search with one per iteration.
+``AutoAttack`` (ART's name) runs Auto-PGD with both losses, DeepFool and SquareAttack in turn over the rows that are still
+classified correctly and reports the accuracy that survives all of them.
 """
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ from .estimators import TensorFlowV2Classifier, WaveformClassifier, _as_given, _
 from .extract_features_construct_dataset import read_wav, _extractor
 from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack: scores only; lipasr/genetic.py)
 from .keras import to_categorical
+from .square import SquareAttack  # noqa: F401  (Square Attack: one score query per iteration; lipasr/square.py)
 
 
 # ------------------------------------------------------------------------------------------------ A2
@@ -840,6 +844,118 @@ class DeepFool:
         """NumPy in, new NumPy out (the input is left untouched)."""
         adv = self.generate_device(_to_dev(x), lengths=lengths)
         return _as_given(adv, x)
+
+
+def within_ball_device(adv, x, eps, norm, valid=None):
+    """bool [B]: the perturbation of each row lies in the eps ball -- norm inf: per element eps plus one unit in the last place of
+    the fp32 number |x| + eps; norm 2: eps (1 + 1e-6) + 1e-7; in fp64.  ``valid`` bool [B, n]: only those positions count."""
+    d = adv.double() - x.double()
+    if valid is not None:
+        d = torch.where(valid, d, torch.zeros_like(d))
+    e = float(np.float32(eps))
+    if float(norm) == 2.0:
+        return (d * d).sum(dim=1).sqrt() <= e * (1 + 1e-6) + 1e-7
+    t = (x.double().abs() + float(eps)).float()
+    room = e + (torch.nextafter(t, torch.full_like(t, math.inf)).double() - t.double())
+    return (d.abs() <= room).all(dim=1)
+
+
+class AutoAttack:
+    """ART AutoAttack(estimator=, norm=, eps=, eps_step=, attacks=, batch_size=) (Croce & Hein 2020): an ensemble whose answer is
+    the accuracy that survives every member.  ``attacks=None`` builds the list from this module's own classes at this ``eps``,
+    ``norm`` and ``seed``: AutoProjectedGradientDescent with loss_type="cross_entropy", AutoProjectedGradientDescent with
+    "difference_logits_ratio" (LEFT OUT below 3 classes, where that loss is undefined), DeepFool(norm=norm) and SquareAttack
+    (LEFT OUT under norm=2: only its L-inf form is built).  ART's list is the same four with its own classes (restated from memory
+    of its published implementation; ART is absent: parity unpinned).  ``norm``: np.inf or 2.  Ours, after the ``*``: ``seed`` (every
+    member's), ``shape`` (SquareAttack's picture of a row; None: a strip) and ``targeted``: True is refused -- ART's form with one
+    run per target class is not built.
+
+    generate_device: labels are ``yt``, or the estimator's own predictions.  A row is ROBUST while the estimator's argmax equals
+    its label; rows misclassified when clean are returned bit for bit.  Each attack in turn runs only on the rows that are still
+    robust (gathering that subset, with its ``lengths``, is the one synchronisation per attack; a member's random draws are keyed
+    by a row's position in the subset).  A row counts as broken only if the estimator's argmax at the result differs from the label
+    AND the result lies in the ball (``within_ball_device``; only the clip's own samples count under ``lengths``) -- DeepFool's
+    unbounded result passes or fails this check like any other.  A broken row keeps the first result that broke it; a row no attack
+    broke is returned clean.  Afterwards: ``success_`` bool [B] (broken), ``broken_by_`` int32 [B] (the index into ``attacks``, -1
+    never broken, -2 misclassified when clean) as device tensors and ``robust_accuracy_``, the share of all rows still robust."""
+
+    def __init__(self, estimator, norm=np.inf, eps=0.3, eps_step=0.1, attacks=None, batch_size=32, *, seed=0, shape=None,
+                 targeted=False):
+        if not isinstance(estimator, (TensorFlowV2Classifier, WaveformClassifier)):
+            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        if targeted:
+            raise ValueError("targeted=True: the targeted AutoAttack (one run per target class) is not built")
+        self.norm = _norm_value(norm)
+        if self.norm == 1.0:
+            raise ValueError("norm=1: AutoAttack runs in norm 2 or np.inf")
+        self.estimator, self.eps, self.eps_step = estimator, float(eps), float(eps_step)
+        if not (0.0 <= self.eps < math.inf and 0.0 <= self.eps_step < math.inf):
+            raise ValueError(f"eps = {eps}, eps_step = {eps_step}: finite, non-negative numbers are required")
+        self.batch_size, self.seed, self.targeted = int(batch_size), int(seed), False
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size = {batch_size}")
+        if attacks is None:
+            kw = dict(norm=norm, eps=self.eps, eps_step=self.eps_step, batch_size=self.batch_size, seed=self.seed)
+            attacks = [AutoProjectedGradientDescent(estimator, loss_type="cross_entropy", **kw)]
+            if estimator.nb_classes >= 3:
+                attacks.append(AutoProjectedGradientDescent(estimator, loss_type="difference_logits_ratio", **kw))
+            attacks.append(DeepFool(estimator, batch_size=self.batch_size, verbose=False, norm=norm))
+            if self.norm == math.inf:
+                attacks.append(SquareAttack(estimator, norm=np.inf, eps=self.eps, batch_size=self.batch_size, shape=shape, seed=self.seed))
+        self.attacks = list(attacks)
+        for a in self.attacks:
+            if not callable(getattr(a, "generate_device", None)):
+                raise TypeError(f"{type(a).__name__} has no generate_device")
+        self.success_ = self.broken_by_ = self.robust_accuracy_ = None
+
+    @staticmethod
+    def _attack(attack, xs, ys, ls):
+        import inspect
+
+        takes = inspect.signature(attack.generate_device).parameters
+        kw = {} if ls is None else dict(lengths=ls)
+        return attack.generate_device(xs, ys, **kw) if "yt" in takes else attack.generate_device(xs, **kw)
+
+    def generate_device(self, xt, yt=None, lengths=None):
+        """xt: float32 device tensor [B, features or samples]; yt: one-hot [B, classes], class indices [B] or None; returns a NEW
+        device tensor (the input is left untouched)."""
+        est = self.estimator
+        lt = est.lengths_device(lengths, len(xt))
+        xt = est.rows_device(xt)
+        b, dev = xt.shape[0], xt.device
+        pred = est.predict_device(xt, logits=True, lengths=lt).argmax(dim=1) if b else torch.zeros(0, dtype=torch.int64, device=dev)
+        if yt is None:
+            labels = pred
+        else:
+            yt = yt.to(dev)
+            labels = (yt.argmax(dim=1) if yt.dim() == 2 else yt).long()
+            if tuple(labels.shape) != (b,):
+                raise ValueError(f"y must be one-hot [B, classes] or class indices [B], got {tuple(yt.shape)}")
+        robust = pred == labels
+        adv = xt.clone()
+        self.broken_by_ = torch.where(robust, -1, -2).to(torch.int32)
+        mask_all = None if lt is None else est.clip_mask(lt)
+        for i, attack in enumerate(self.attacks):
+            idx = robust.nonzero()[:, 0]
+            if idx.numel() == 0:
+                break
+            xs, ys = xt[idx].contiguous(), labels[idx]
+            ls = None if lt is None else lt[idx].contiguous()
+            cand = self._attack(attack, xs, ys, ls)
+            moved = est.predict_device(cand, logits=True, lengths=ls).argmax(dim=1) != ys
+            ok = moved & within_ball_device(cand, xs, self.eps, self.norm, None if mask_all is None else mask_all[idx])
+            hit = idx[ok]
+            adv[hit] = cand[ok]
+            self.broken_by_[hit] = i
+            robust[hit] = False
+        self.success_ = self.broken_by_ >= 0
+        self.robust_accuracy_ = float(robust.double().mean()) if b else 1.0
+        return adv
+
+    def generate(self, x, y=None, lengths=None):
+        xt = _to_dev(x)
+        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
+        return _as_given(self.generate_device(xt, yt, lengths), x)
 
 
 class ImperceptibleASR:

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 650.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 660.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -36,6 +36,8 @@
  * lipasr_debug_mfcc_stage (the dB tile, the frame maxima or the resampled signal a plan's last forward call left behind).
  * 650: Auto-PGD: lipasr_apgd_loss (cross-entropy or DLR with its gradient at the logits), lipasr_apgd_step (one iteration with a
  * step size, best point and checkpoint decisions per row) and the host-only lipasr_debug_apgd_path.
+ * 660: Square Attack: lipasr_square_init (the stripe start), lipasr_square_step (one query's bookkeeping and the next proposal) and
+ * the host-only lipasr_square_init_host / lipasr_square_step_host.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -606,6 +608,65 @@ int lipasr_apgd_step(lipasr_handle_t h, float* x, float* x_prev, const float* x0
  * (n <= 8 192, 16 384, 22 528); 7 the re-reading fallback.  Bit 3: float4 loads (aligned != 0: every row array on 16 bytes, and n a
  * multiple of 4); it changes the loads inside an instance, never the instance.  n <= 0: -1. */
 int lipasr_debug_apgd_path(int n, int aligned);
+
+/* (ours: the reference has no score-based search; this is Square Attack of Andriushchenko, Croce, Flammarion, Hein 2020, "Square
+ * Attack: a query-efficient black-box adversarial attack via random search", the L-inf form, ART's SquareAttack, restated from the
+ * paper and from memory of ART: parity unpinned)  A random search over sign patterns, one query per iteration.
+ * Row geometry.  A row is height x width, n = height * width, element (r, c) at r * width + c (MFCC rows: height the coefficient axis,
+ * width the frame axis).  n_valid goes with height == 1 only (a non-NULL n_valid with height > 1 is LIPASR_EINVAL): nv =
+ * min(max(n_valid[b], 0), n) as lipasr_genetic_breed takes it, NULL: nv = n; elements k >= nv carry the bits of x0 in every buffer at
+ * all times.
+ * Perturbed value.  Every perturbed element is v(s) = min(max(fl(x0 + s eps), clip_lo), clip_hi) with s = +1 or -1 (-INFINITY /
+ * +INFINITY: no clamp; a NaN stays a NaN).
+ * gen(seed; lo, hi0, hi1) is the Philox4x32-10 block with key seed and counter (lo low word, lo high word, hi0, hi1).
+ *
+ * lipasr_square_init writes the paper's vertical-stripe start into x_best AND x_cand: column c gets one sign for all its rows, bit
+ * c & 31 of word (c >> 5) & 3 of gen(seed; (c >> 7) | 1 << 62, clip0 + b, restart << 24) (1: s = -1), and win[b] = (0, 0, 0, 0).
+ * restart < 256, eps finite and >= 0, clip_lo <= clip_hi, height * width <= 2^31 - 1, or LIPASR_EINVAL. */
+int lipasr_square_init(lipasr_handle_t h, const float* x0 /* [batch][height * width] */, const int* n_valid /* [batch] or NULL */,
+                       int batch, int height, int width, uint32_t clip0, uint32_t restart, uint64_t seed, float eps, float clip_lo,
+                       float clip_hi, float* x_best, float* x_cand, int* win /* [batch][4] */, lipasr_stream_t stream);
+
+#define LIPASR_SQUARE_LAST 1 /* flags bit 0: the last query of a run: bookkeeping only, no new proposal */
+/* One launch per query: finishes proposal `it` and writes proposal it + 1.  logits [batch][classes] are the model's outputs at
+ * x_cand; y = labels[b].  Per row, in this order:
+ *   1. loss = z_y - max_{c != y} z_c in fp32, one subtraction (targeted: its negative, y the class to reach); classes == 1: +inf; a
+ *      NaN anywhere in the row: NaN; a label outside [0, classes): +inf.
+ *   2. it == 0 (the stripe start; win is empty): loss_best = loss, a NaN stored as +INFINITY.  it > 0: where the row was not done on
+ *      arrival and loss < loss_best (strict; a NaN never wins), the elements inside win[b] = (r, c, h, w) are copied from x_cand to
+ *      x_best and loss_best = loss; otherwise the same elements are copied back from x_best to x_cand.  Only the window is touched:
+ *      a step moves O(window) bytes, not O(n).
+ *   3. done[b] is sticky: a row that arrives with done == 0 and now has loss_best < 0 gets done = it + 1, the number of queries it
+ *      took, the start counted as query 1.
+ *   4. A row that is done, a row with nv == 0, and every row under LIPASR_SQUARE_LAST gets no new proposal: win[b] = (0, 0, 0, 0)
+ *      and x_cand equals x_best bit for bit.  Every other row draws proposal it + 1 from o = gen(seed; 0, clip0 + b,
+ *      restart << 24 | (it + 1)): the window is win_h x win_w when n_valid == NULL, and 1 x clamp((nv * p_q + 2^23) >> 24, 1, nv)
+ *      with n_valid, p_q = round(p * 2^24); its corner is uniform over the positions that keep it inside the row, or inside
+ *      [0, nv): r = (o[0] * (height - h + 1)) >> 32, c = (o[1] * (width - w + 1)) >> 32 in 64-bit integers (with n_valid: nv for
+ *      width); bit 0 of o[2] is the sign of the whole window (1: s = -1).  x_cand gets v(s) inside the window, win[b] its
+ *      (r, c, h, w).
+ * Everything is integer arithmetic, one fp32 add, two clamps and one fp32 subtract: draws and values are a pure function of (seed,
+ * row index, restart, iteration), chunks of any size at any clip0 reproduce one big call bit for bit, and the host twins below give
+ * the same bits.  One workgroup per row, no workspace, no atomics; any n, any alignment of the row buffers (scalar accesses: the
+ * values never depend on it).
+ * it < 2^24, restart < 256, 1 <= classes <= 32, 1 <= win_h <= height, 1 <= win_w <= width, p_q <= 2^24, flags within
+ * LIPASR_SQUARE_LAST, eps finite and >= 0, clip_lo <= clip_hi, x_best overlapping neither x_cand nor x0 (nor x_cand x0), or
+ * LIPASR_EINVAL; batch == 0 or n == 0: LIPASR_OK with nothing written; null pointers (n_valid excepted) are refused before the device
+ * is touched. */
+int lipasr_square_step(lipasr_handle_t h, const float* logits /* [batch][classes] */, const int* labels /* [batch] */,
+                       const float* x0, const int* n_valid /* [batch] or NULL */, int batch, int classes, int height, int width,
+                       int win_h, int win_w, uint32_t p_q, int targeted, uint32_t clip0, uint32_t restart, uint32_t it, int flags,
+                       uint64_t seed, float eps, float clip_lo, float clip_hi, float* x_best, float* x_cand,
+                       float* loss_best /* [batch] */, int* done /* [batch] */, int* win /* [batch][4] */, lipasr_stream_t stream);
+
+/* Host-only (no GPU needed): the two calls above on host arrays, the same inline functions in plain loops -- the CPU-side pin of the
+ * counters.  Same checks, same bits. */
+int lipasr_square_init_host(const float* x0, const int* n_valid, int batch, int height, int width, uint32_t clip0, uint32_t restart,
+                            uint64_t seed, float eps, float clip_lo, float clip_hi, float* x_best, float* x_cand, int* win);
+int lipasr_square_step_host(const float* logits, const int* labels, const float* x0, const int* n_valid, int batch, int classes,
+                            int height, int width, int win_h, int win_w, uint32_t p_q, int targeted, uint32_t clip0, uint32_t restart,
+                            uint32_t it, int flags, uint64_t seed, float eps, float clip_lo, float clip_hi, float* x_best, float* x_cand,
+                            float* loss_best, int* done, int* win);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
