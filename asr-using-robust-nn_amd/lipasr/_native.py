@@ -120,6 +120,17 @@ PROTOTYPES = {
     "lipasr_square_init_host": (i32, [c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, f32, f32, f32, c_f, c_f, c_f]),
     "lipasr_square_step_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_uint32, i32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       i32, u64, f32, f32, f32, c_f, c_f, c_f, c_f, c_f]),
+    "lipasr_hsj_expand": (i32, [c_h, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, C.c_uint32, u64, f32, f32, f32, c_f, c_s]),
+    "lipasr_hsj_accumulate": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f, c_f, c_s]),
+    "lipasr_hsj_direction": (i32, [c_h, c_f, c_f, c_f, i32, i32, f32, c_f, c_s]),
+    "lipasr_hsj_search": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_uint32, C.c_uint32, u64, f32,
+                                f32, i32, f32, f32, c_f, c_f, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_hsj_expand_host": (i32, [c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, C.c_uint32, u64, f32, f32, f32, c_f]),
+    "lipasr_hsj_accumulate_host": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f, c_f]),
+    "lipasr_hsj_direction_host": (i32, [c_f, c_f, c_f, i32, i32, f32, c_f]),
+    "lipasr_hsj_search_host": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_uint32, C.c_uint32, u64, f32, f32,
+                                     i32, f32, f32, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "lipasr_debug_hsj_path": (i32, [i32, i32]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -190,7 +201,9 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_genetic_breed_host": 620, "lipasr_genetic_select": 620, "lipasr_debug_k3_launches": 630,
          "lipasr_debug_k1_launches": 640, "lipasr_debug_mfcc_stage": 640, "lipasr_apgd_loss": 650, "lipasr_apgd_step": 650,
          "lipasr_debug_apgd_path": 650, "lipasr_square_init": 660, "lipasr_square_step": 660, "lipasr_square_init_host": 660,
-         "lipasr_square_step_host": 660}
+         "lipasr_square_step_host": 660, "lipasr_hsj_expand": 670, "lipasr_hsj_accumulate": 670, "lipasr_hsj_direction": 670,
+         "lipasr_hsj_search": 670, "lipasr_hsj_expand_host": 670, "lipasr_hsj_accumulate_host": 670, "lipasr_hsj_direction_host": 670,
+         "lipasr_hsj_search_host": 670, "lipasr_debug_hsj_path": 670}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -497,6 +510,105 @@ def square_step_host(logits, labels, x0, height, width, win_h, win_w, p_q, resta
                                       _host_array(x_cand, np.float32, (b, n), "x_cand"),
                                       _host_array(loss_best, np.float32, (b,), "loss_best"), _host_array(done, np.int32, (b,), "done"),
                                       _host_array(win, np.int32, (b, 4), "win")))
+
+
+HSJ_START, HSJ_HALVE, HSJ_BISECT = 0, 1, 2
+HSJ_FIRST, HSJ_LAST = 1, 2
+# columns of lipasr_hsj_search's fstate and istate
+HSJ_F = {"lo": 0, "hi": 1, "mid": 2, "thresh": 3, "eps": 4, "dist": 5, "dist_best": 6, "dist_far": 7}
+HSJ_I = {"active": 0, "found": 1, "ok": 2, "moved": 3, "halvings": 4, "queries": 5}
+
+
+def _host_in(a, dtype, shape, what):
+    import numpy as np
+
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what} must be {tuple(shape)}, got {a.shape}")
+    return a
+
+
+def _norm_f(norm):
+    return float("inf") if norm in ("inf", float("inf")) else float(norm)
+
+
+def hsj_expand_host(x, delta, draws, it, seed, norm, *, n_valid=None, clip0=0, draw0=0, clip_lo=-float("inf"), clip_hi=float("inf"),
+                    out=None):
+    """Host-only: lipasr_hsj_expand_host on NumPy arrays (x float32 [B, n], delta float32 [B]) -> float32 [B * draws, n]."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    b, n = x.shape
+    delta = _host_in(delta, np.float32, (b,), "delta")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    out = np.zeros((b * int(draws), n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_hsj_expand_host(C.c_void_p(x.ctypes.data), C.c_void_p(delta.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data),
+                                     b, n, int(draws), int(clip0), int(it), int(draw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _norm_f(norm),
+                                     float(clip_lo), float(clip_hi), _host_array(out, np.float32, (b * int(draws), n), "out")))
+    return out
+
+
+def hsj_accumulate_host(logits, labels, p, x, *, sums, counts, n_valid=None, targeted=False):
+    """Host-only: lipasr_hsj_accumulate_host, in place on sums float64 [B, 2, n] and counts int32 [B, 2]."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    b, n = x.shape
+    p = np.ascontiguousarray(p, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != n or (b and p.shape[0] % b):
+        raise ValueError(f"p must be [{b} * draws, {n}], got {p.shape}")
+    draws = p.shape[0] // b if b else 0
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    if logits.ndim != 2 or logits.shape[0] != p.shape[0]:
+        raise ValueError(f"logits must be [{p.shape[0]}, classes], got {logits.shape}")
+    labels = _host_in(labels, np.int32, (b,), "labels")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    check(lib.lipasr_hsj_accumulate_host(C.c_void_p(logits.ctypes.data), C.c_void_p(labels.ctypes.data), C.c_void_p(p.ctypes.data),
+                                         C.c_void_p(x.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data), b, logits.shape[1], n,
+                                         draws, 1 if targeted else 0, _host_array(sums, np.float64, (b, 2, n), "sums"),
+                                         _host_array(counts, np.int32, (b, 2), "counts")))
+
+
+def hsj_direction_host(sums, counts, norm, *, n_valid=None, u=None):
+    """Host-only: lipasr_hsj_direction_host (sums float64 [B, 2, n], counts int32 [B, 2]) -> u float32 [B, n]."""
+    import numpy as np
+
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    b, _, n = sums.shape
+    counts = _host_in(counts, np.int32, (b, 2), "counts")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    u = np.zeros((b, n), dtype=np.float32) if u is None else u
+    check(lib.lipasr_hsj_direction_host(C.c_void_p(sums.ctypes.data), C.c_void_p(counts.ctypes.data),
+                                        None if nv is None else C.c_void_p(nv.ctypes.data), b, n, _norm_f(norm),
+                                        _host_array(u, np.float32, (b, n), "u")))
+    return u
+
+
+def hsj_search_host(logits, labels, x0, mode, flags, seed, norm, *, x_cand, x_far, x_adv, x_best, fstate, istate, start_lo, start_hi,
+                    theta, u=None, n_valid=None, targeted=False, clip0=0, draw=0, step_scale=1.0, max_halvings=25,
+                    clip_lo=-float("inf"), clip_hi=float("inf"), classes=None):
+    """Host-only: lipasr_hsj_search_host on NumPy arrays, in place on x_cand, x_far, x_adv, x_best float32 [B, n], fstate float32
+    [B, 8] and istate int32 [B, 8]; logits float32 [B, classes] or None (under HSJ_FIRST, then ``classes`` says how many)."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float32)
+    b, n = x0.shape
+    if logits is not None:
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        if logits.ndim != 2 or logits.shape[0] != b:
+            raise ValueError(f"logits must be [{b}, classes], got {logits.shape}")
+        classes = logits.shape[1]
+    labels = _host_in(labels, np.int32, (b,), "labels")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    sl, sh, th = (_host_in(a, np.float32, (b,), w) for a, w in ((start_lo, "start_lo"), (start_hi, "start_hi"), (theta, "theta")))
+    uu = None if u is None else _host_in(u, np.float32, (b, n), "u")
+    vp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    check(lib.lipasr_hsj_search_host(vp(logits), vp(labels), vp(x0), vp(nv), vp(uu), vp(sl), vp(sh), vp(th), b, int(classes or 1), n, int(mode),
+                                     int(flags), 1 if targeted else 0, int(clip0), int(draw), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     _norm_f(norm), float(step_scale), int(max_halvings), float(clip_lo), float(clip_hi),
+                                     _host_array(x_cand, np.float32, (b, n), "x_cand"), _host_array(x_far, np.float32, (b, n), "x_far"),
+                                     _host_array(x_adv, np.float32, (b, n), "x_adv"), _host_array(x_best, np.float32, (b, n), "x_best"),
+                                     _host_array(fstate, np.float32, (b, 8), "fstate"), _host_array(istate, np.int32, (b, 8), "istate")))
 
 
 def debug_table(which: int, sr_in: int = 16000):

@@ -16,6 +16,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: Auto-PGD, per-row step control, CE or DLR) attack="white", kind="apgd", --loss ce | dlr, --norm inf | 2, over="mfcc" | "audio"
     (no prompt: the genetic query-only attack)             attack="black", kind="genetic": genetic_sweep over="mfcc" | "audio"
     (no prompt: Square Attack, one score query per step)   attack="black", kind="square": square_sweep over="mfcc" | "audio"
+    (no prompt: HopSkipJump, the label only, min. norm)    attack="black", kind="hsj", --norm inf | 2: hopskipjump_sweep over="mfcc" | "audio"
     (no prompt: the AutoAttack ensemble, robust accuracy)  attack="white", kind="auto", --norm inf | 2, over="mfcc" | "audio"
     (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth":smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
 """
@@ -340,6 +341,45 @@ def square_sweep(models, train_data, val_data, test_data, test_labels, over="mfc
                         train_data, val_data, test_data, test_labels, over, standardize, test_filenames, domain, grid, points, limit)
 
 
+def hopskipjump_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
+                      domain="22k", norm=np.inf, grid=None, points=None, limit=None, **attack_kw):
+    """HopSkipJump (lipasr.attacks.HopSkipJump: the label only, neither score nor gradient) -- ONE run per model, not one per eps: the
+    attack minimises the distance, and from its ``distance_`` per clip comes the whole curve.  The labels are the true ones, so a
+    row that is wrong when clean has distance 0; accuracy at eps is the share of rows with distance_ > eps (an upper bound on the
+    robust accuracy, as every attack gives), at the points of white_box_sweep's PGD grid (over="audio": AUDIO_SIGMAS, its grid
+    there).  ``norm``: 2 or np.inf, the norm of the distance and of eps; ``attack_kw``: HopSkipJump's keywords (max_iter, max_eval,
+    ...).  Rows are prepared as in square_sweep; standardize="after" is refused (the distance would be one between unstandardised
+    rows that the models never see).  Returns (grid, {model name: accuracies}, {model name: {"median_distance": over the rows with
+    a finite distance, "mean_queries": over all rows}})."""
+    if norm not in (2, 2.0, np.inf):
+        raise ValueError(f"norm = {norm!r}: HopSkipJump runs in norm 2 or inf")
+    if standardize != "before":
+        raise ValueError("hopskipjump_sweep measures distances between the rows the models see: standardize='before'")
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
+    labels = np.asarray(rows.limited(test_labels))
+    grid = list((AUDIO_SIGMAS if over == "audio" else np.linspace(1, 30, 50)) if grid is None else grid)[:points]
+    acc, stats = {}, {}
+    for name, model in models.items():
+        dist, q = np.zeros(rows.n, dtype=np.float64), np.zeros(rows.n, dtype=np.int64)
+        for clf, x, lt, idx in rows.batches(model):
+            atk = A.HopSkipJump(clf, norm=norm, **{"verbose": False, **attack_kw})
+            y = torch.as_tensor(labels[idx])
+            if over == "audio":
+                atk.generate_device(x, y, lengths=lt)
+            else:
+                atk.generate(x, y)
+            dist[idx], q[idx] = atk.distance_.cpu().numpy(), atk.queries_.cpu().numpy()
+        acc[name] = np.asarray([float(np.mean(dist > eps)) if rows.n else float("nan") for eps in grid])
+        finite = dist[np.isfinite(dist)]
+        stats[name] = {"median_distance": float(np.median(finite)) if len(finite) else float("nan"),
+                       "mean_queries": float(np.mean(q)) if rows.n else float("nan")}
+        what = f"HopSkipJump (norm {'inf' if norm == np.inf else 2}) black-box {'audio ' if over == 'audio' else ''}test examples{_tag(name)}"
+        for eps, a in zip(grid, acc[name]):
+            print(f"Accuracy on {what}: {a * 100}% ({eps})")
+        print(f"{what}: median distance {stats[name]['median_distance']}, mean queries {stats[name]['mean_queries']} over {rows.n} {rows.what}")
+    return grid, acc, stats
+
+
 def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, grid=DOLPHIN_CARRIER_LEVELS, a1=1.0, a2=0.5,
                   standardize="before", points=None, limit=None):
     """DolphinAttack (lipasr.dolphin) against the carrier level: every file of ``test_filenames`` (16 kHz) becomes amplitude-
@@ -466,11 +506,12 @@ def lipschitz_report(models, train_data, val_data, test_data, over="mfcc", stand
 
 
 def radius_report(models, train_data, val_data, test_data, over="mfcc", standardize="before", test_filenames=None, domain="22k",
-                  norm=2, limit=None, **deepfool_kw):
+                  norm=2, limit=None, found_by="deepfool", **attack_kw):
     """Per model: how far the test rows are from the decision boundary (get_robustness_radius) -- the quartiles of the certified
     radius (rows of MFCC features and norm 2 only), of the distance to the linearised boundary and of the distance DeepFool found,
     and the share of rows it flipped.  ``over``, ``standardize``, ``test_filenames``, ``domain`` and ``limit`` as in
-    lipschitz_report; ``norm``: 2 or np.inf; deepfool_kw go to attacks.DeepFool.
+    lipschitz_report; ``norm``: 2 or np.inf; attack_kw go to attacks.DeepFool.  found_by="hopskipjump": the found distance and
+    the flipped share are attacks.HopSkipJump's, which sees the label only, and attack_kw are its keywords.
     Returns {model name: {"bound": get_lipschitz_bound(model), "margin", "certified" (or None), "linear", "found", "flipped": the
     per-row arrays, "quartiles": {name: (q25, q50, q75)}, "flipped_share"}}."""
     rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
@@ -479,7 +520,7 @@ def radius_report(models, train_data, val_data, test_data, over="mfcc", standard
     for name, model in models.items():
         r = {k: np.zeros(rows.n, dtype=bool if k == "flipped" else np.float64) for k in keys}
         for clf, x, lt, idx in rows.batches(model):
-            part = get_robustness_radius(clf, x, norm=norm, lengths=lt, **deepfool_kw)
+            part = get_robustness_radius(clf, x, norm=norm, lengths=lt, found_by=found_by, **attack_kw)
             for k in keys:
                 if part[k] is None:  # no certified radius over audio, nor in norm inf
                     r[k] = None
@@ -493,13 +534,13 @@ def radius_report(models, train_data, val_data, test_data, over="mfcc", standard
         tag = _tag(name)
         what = f"{len(r['found'])} test {rows.what}"
         print(f"Lipschitz bound of the logits{tag}: {r['bound']}")
-        for k, label in (("certified", "Certified radius"), ("linear", "Distance to the linearised boundary"), ("found", "Distance DeepFool found")):
+        for k, label in (("certified", "Certified radius"), ("linear", "Distance to the linearised boundary"), ("found", "Distance HopSkipJump found" if found_by == "hopskipjump" else "Distance DeepFool found")):
             if k in r["quartiles"]:
                 q = r["quartiles"][k]
                 print(f"{label} over {what}{tag}: quartiles {q[0]} {q[1]} {q[2]}")
             else:
                 print(f"{label} over {what}{tag}: not given")
-        print(f"Share of {what} DeepFool moved to another class{tag}: {r['flipped_share'] * 100}%")
+        print(f"Share of {what} {'HopSkipJump' if found_by == 'hopskipjump' else 'DeepFool'} moved to another class{tag}: {r['flipped_share'] * 100}%")
     return out
 
 
@@ -567,7 +608,7 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square; white: fgsm|l2|linf|pgd|apgd|auto|jsma|imperceptible")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square|hsj; white: fgsm|l2|linf|pgd|apgd|auto|jsma|imperceptible")
     ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
     ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); black square: queries per clip (default: SquareAttack's); white apgd: iterations (default: 100)")
     ap.add_argument("--loss", choices=["ce", "dlr"], default="ce", help="white apgd: cross-entropy or the Difference-of-Logits-Ratio loss")
@@ -588,6 +629,8 @@ def main(argv=None):
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
     if args.attack == "white" and args.kind in ("apgd", "auto") and args.norm == "1":
         raise ValueError(f"--kind {args.kind} runs in --norm inf or 2")
+    if args.attack == "black" and args.kind == "hsj" and args.norm == "1":
+        raise ValueError("--kind hsj runs in --norm inf or 2")
 
     if args.attack == "smooth" and (args.sigma is None or not 0.0 <= args.sigma < float("inf")):
         raise ValueError("--attack smooth needs --sigma, the standard deviation of the noise (finite, not negative; there is no default)")
@@ -608,6 +651,10 @@ def main(argv=None):
             kw = {} if args.max_iter is None else dict(max_iter=args.max_iter)
             return square_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
                                 test_filenames=names, points=args.points, **kw)
+        if args.kind == "hsj":
+            kw = {} if args.max_iter is None else dict(max_iter=args.max_iter)
+            return hopskipjump_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
+                                     test_filenames=names, norm=np.inf if args.norm == "inf" else 2, points=args.points, **kw)
         return black_box_sweep(models, train_data, val_data, test_data, labels, kind=args.kind, over=args.over,
                                standardize=args.standardize, test_filenames=names, points=args.points)
     if args.attack == "lipschitz":

@@ -22,6 +22,8 @@ Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.  ``GeneticAttack`` (lipasr/genetic.py,
 ours) and ``SquareAttack`` (lipasr/square.py; ART's name, Andriushchenko et al. 2020) are the black-box attacks that look at the
 model's answer: a genetic algorithm with pop_size score queries per generation, and a random search with one per iteration.
+``HopSkipJump`` (lipasr/hopskipjump.py; ART's name, Chen et al. 2020) sees less still, the label alone, and minimises the L2 or
+L-inf distance to the nearest misclassified point it can find.
 ``AutoAttack`` (ART's name) runs Auto-PGD with both losses, DeepFool and SquareAttack in turn over the rows that are still
 classified correctly and reports the accuracy that survives all of them.
 """
@@ -38,6 +40,7 @@ from .extract_features_construct_dataset import read_wav, _extractor
 from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack: scores only; lipasr/genetic.py)
 from .keras import to_categorical
 from .square import SquareAttack  # noqa: F401  (Square Attack: one score query per iteration; lipasr/square.py)
+from .hopskipjump import HopSkipJump  # noqa: F401  (HopSkipJump: decisions only, minimum L2 / L-inf norm; lipasr/hopskipjump.py)
 
 
 # ------------------------------------------------------------------------------------------------ A2

@@ -435,7 +435,7 @@ def get_lipschitz_bound(model):
     return bound
 
 
-def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **deepfool_kw):
+def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, found_by="deepfool", **attack_kw):
     """Per row of ``x`` the three numbers  certified radius <= distance to the decision boundary <= distance DeepFool found,  as a
     dict of float64 NumPy arrays [B]:
       margin     min over k != c of z_c - z_k on the logits, c the estimator's own class at the row;
@@ -443,8 +443,12 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **
                  (z_c - z_k has the Lipschitz constant ||e_c - e_k||_2 L).  Given for rows of features (TensorFlowV2Classifier)
                  and norm 2 only; None over audio (the log of the MFCC stage has no global constant) and for norm inf;
       linear     the distance to the nearest boundary of the classifier linearised at the row (DeepFool's first rho_l);
-      found      ||x_adv - x|| in ``norm`` for attacks.DeepFool(estimator, norm=norm, **deepfool_kw);
+      found      ||x_adv - x|| in ``norm`` for attacks.DeepFool(estimator, norm=norm, **attack_kw);
       flipped    bool: x_adv is classified differently.  Where it is False, ``found`` bounds nothing.
+    ``found_by``: "deepfool" (default), or "hopskipjump": ``found`` and ``flipped`` then come from attacks.HopSkipJump(estimator,
+    norm=norm, **attack_kw) -- its ``distance_`` (+inf without a start) and ``success_`` -- a distance that rests on the label alone,
+    neither on a gradient nor on a score, next to the same margin, certified radius and linearised distance (ONE DeepFool step
+    with its default keywords: ``attack_kw`` are HopSkipJump's then).
     ``smoothing``: None (default: the dict above, nothing else), or dict(sigma=, n0=100, n=100_000, alpha=0.001, seed=0,
     clip_values=None) -- randomized smoothing (lipasr.smoothing.Smooth.certify) then adds
       smoothed_radius  the L2 radius sigma Phi^-1(p_lower) within which the SMOOTHED classifier g(x) = argmax_c P(f(x + N(0,
@@ -455,8 +459,10 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **
     ``estimator``: a TensorFlowV2Classifier or WaveformClassifier of lipasr.estimators (``lengths`` as there)."""
     from .attacks import DeepFool  # attacks imports this module
 
+    if found_by not in ("deepfool", "hopskipjump"):
+        raise ValueError(f"found_by = {found_by!r}: 'deepfool' or 'hopskipjump'")
     xt = E._to_dev(x)
-    attack = DeepFool(estimator, norm=norm, **deepfool_kw)
+    attack = DeepFool(estimator, norm=norm, max_iter=1) if found_by == "hopskipjump" else DeepFool(estimator, norm=norm, **attack_kw)
     if xt.shape[0] == 0:
         z = torch.zeros(0, estimator.nb_classes, device=xt.device)
     else:
@@ -476,6 +482,12 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, **
         certified = margin / (np.sqrt(2.0) * get_lipschitz_bound(estimator.model))
     res = {"margin": margin, "certified": certified, "linear": attack.last["first_dist"], "found": found,
            "flipped": attack.last["flipped"]}
+    if found_by == "hopskipjump":
+        from .attacks import HopSkipJump
+
+        hsj = HopSkipJump(estimator, norm=norm, **attack_kw)
+        hsj.generate_device(xt, lengths=lengths)
+        res["found"], res["flipped"] = hsj.distance_.double().cpu().numpy(), hsj.success_.cpu().numpy()
     if smoothing is not None:
         from .smoothing import Smooth
 

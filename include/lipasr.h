@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 660.  ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 670. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -38,6 +38,8 @@
  * step size, best point and checkpoint decisions per row) and the host-only lipasr_debug_apgd_path.
  * 660: Square Attack: lipasr_square_init (the stripe start), lipasr_square_step (one query's bookkeeping and the next proposal) and
  * the host-only lipasr_square_init_host / lipasr_square_step_host.
+ * 670: HopSkipJump: lipasr_hsj_expand (the perturbed copies), lipasr_hsj_accumulate (the two fp64 sums), lipasr_hsj_direction,
+ * lipasr_hsj_search (one query of the start, the step-size halving or the bisection), their _host twins and lipasr_debug_hsj_path.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -667,6 +669,93 @@ int lipasr_square_step_host(const float* logits, const int* labels, const float*
                             int height, int width, int win_h, int win_w, uint32_t p_q, int targeted, uint32_t clip0, uint32_t restart,
                             uint32_t it, int flags, uint64_t seed, float eps, float clip_lo, float clip_hi, float* x_best, float* x_cand,
                             float* loss_best, int* done, int* win);
+
+/* ------------------------------------------------------------------ HopSkipJump (Chen, Jordan, Wainwright 2020)
+ * The decision-based minimum-norm attack: it asks only "is this point adversarial?".  adversarial(z, y): argmax z != y (targeted:
+ * == y), the lowest index on a tie; a row with a NaN logit or a label outside [0, classes) is NOT adversarial.  norm is 2.0f or
+ * +INFINITY (else LIPASR_EINVAL).  Rows have any length and alignment: float4 where n is a multiple of 4 and every row buffer sits on
+ * 16 bytes, scalars otherwise, never changing a value.  nv = clamp(n_valid[b], 0, n), or n when n_valid == NULL: elements at or beyond
+ * nv keep the bits of the clean row in everything written.  clamp(v) = min(max(v, clip_lo), clip_hi) by comparisons (+-INFINITY: no
+ * clamp).  No atomics, nothing waits on another workgroup, two runs give the same bits.
+ *
+ * lipasr_hsj_expand: row b * draws + j of out is clamp(fmaf(s, r, x[b])) with s = (float)((double)delta[b] / ||r||_2) (0 where the
+ * draw is empty or delta[b] is not finite) and r the draw draw0 + j of iteration `it` of clip clip0 + b: element 4 q + e of r is word
+ * e of the Philox block gen(seed; q | (draw0 + j) << 32, clip0 + b, tag << 28 | it), tag 2 / 3,
+ *   norm inf: (k - 2^23) / 2^23 with k = (word >> 8) + 1, uniform on (-1, 1]; ||r||_2 = sqrt(sum (k - 2^23)^2) / 2^23, the sum in
+ *             64-bit integers (n <= 2^17 or LIPASR_EINVAL): the bits of the host twin;
+ *   norm 2:   normal4 (Box-Muller on the block); ||r||_2 from an fp64 sum.  logf / sinf / cosf differ between device and host.
+ * Chunks of draws (draw0) and of clips (clip0) reproduce one big call bit for bit.  it < 2^24. */
+int lipasr_hsj_expand(lipasr_handle_t h, const float* x /* [batch][n] */, const float* delta /* [batch] */,
+                      const int* n_valid /* [batch] or NULL */, int batch, int n, int draws, uint32_t clip0, uint32_t it, uint32_t draw0,
+                      uint64_t seed, float norm, float clip_lo, float clip_hi, float* out /* [batch * draws][n] */,
+                      lipasr_stream_t stream);
+
+/* logits [batch * draws][classes] are the model's outputs at the rows p [batch * draws][n] that lipasr_hsj_expand wrote around
+ * x [batch][n].  phi_j = +1 where row j is adversarial, -1 otherwise.  Adds, in fp64 and in ascending j,
+ *   sums[b][0][k] += p_j[k] - x[k],   sums[b][1][k] += phi_j (p_j[k] - x[k])        (k < nv; nothing is added beyond),
+ *   counts[b][0] += draws,            counts[b][1] += the number of phi_j = +1,
+ * to a workspace the caller zeroed before the first chunk of an iteration: chunks of draws add up to the bits of one call.
+ * 1 <= classes <= 32, draws <= 16384 per call (phi sits in LDS, one byte per draw), batch <= 65535, or LIPASR_EINVAL. */
+int lipasr_hsj_accumulate(lipasr_handle_t h, const float* logits, const int* labels /* [batch] */, const float* p, const float* x,
+                          const int* n_valid, int batch, int classes, int n, int draws, int targeted,
+                          double* sums /* [batch][2][n] */, int* counts /* [batch][2] */, lipasr_stream_t stream);
+
+/* u [batch][n] from the workspace: with m = (2 counts[b][1] - counts[b][0]) / counts[b][0],
+ *   g_k = fma(-m, sums[b][0][k], sums[b][1][k]); every phi +1: g = sums[b][0]; every phi -1: g = -sums[b][0]; no draws: g = 0;
+ *   norm inf: u = sign(g) with sign(0) = 0 (a NaN: 0); norm 2: u = (float)(g / ||g||_2), the norm in fp64, lane-serial then a
+ *   fixed-order tree, u = 0 where it is 0 or not finite.  u is 0 beyond nv. */
+int lipasr_hsj_direction(lipasr_handle_t h, const double* sums, const int* counts, const int* n_valid, int batch, int n, float norm,
+                         float* u /* [batch][n] */, lipasr_stream_t stream);
+
+#define LIPASR_HSJ_START 0  /* mode: the start draws */
+#define LIPASR_HSJ_HALVE 1  /* mode: the step-size halving */
+#define LIPASR_HSJ_BISECT 2 /* mode: the bisection between x0 and the far point */
+#define LIPASR_HSJ_FIRST 1  /* flags bit 0: opens a phase: no logits are read, the first candidate is written */
+#define LIPASR_HSJ_LAST 2   /* flags bit 1 (START only): the last start draw: a row that is still not adversarial gives up */
+/* One launch per query.  logits [batch][classes] are the model's outputs at x_cand (not read under LIPASR_HSJ_FIRST, may be NULL
+ * then).  A row's scalars: fstate[b] = (lo, hi, mid, thresh, eps, dist, dist_best, dist_far), istate[b] = (active, found, ok, moved,
+ * halvings, queries, 0, 0).  A row that is not active is left alone (outside FIRST); every active row counts one query per call.
+ *   START | FIRST  reads istate[b][0] (the caller's: attack this row?) and sets everything else: x_adv = x_best = x0, the three
+ *                  distances +inf, active = asked and nv > 0.  x_cand = start draw 0 (active) or x0.
+ *   START          `draw` is the draw the logits belong to.  adversarial: x_far = x_cand, found = ok = 1, done.  Otherwise draw + 1
+ *                  goes to x_cand, or under LAST the row gives up.  Start draw d, element 4 q + e: clamp(fmaf(u01(word e),
+ *                  start_hi[b] - start_lo[b], start_lo[b])) to [start_lo[b], start_hi[b]], gen(seed; q | d << 32, clip0 + b, 1 << 28).
+ *   HALVE | FIRST  active = found, ok = 0, halvings = 0, eps = dist * step_scale; x_cand = clamp(fmaf(eps, u, x_adv)).
+ *   HALVE          adversarial: x_far = x_cand, ok = 1, done.  Otherwise halvings += 1; at max_halvings the row is done with ok = 0;
+ *                  else eps *= 0.5 and x_cand is written again.
+ *   BISECT | FIRST active = ok, moved = 0, lo = 0; norm 2: hi = 1, thresh = theta[b]; norm inf: dist_far = ||x_far - x0||_inf,
+ *                  hi = dist_far, thresh = min(dist_far * theta[b], theta[b]).  Then as below from "finished?".
+ *   BISECT         adversarial: hi = mid, moved = 1; otherwise lo = mid.  Finished (hi - lo <= thresh, or 0.5 (lo + hi) no longer
+ *                  strictly inside): x_adv = P(hi) where moved, else the bits of x_far; dist = ||x_adv - x0|| in the attack's
+ *                  norm (norm 2: fp64 sum, rounded once); where dist < dist_best, x_best = x_adv and dist_best = dist; done.
+ *                  Otherwise mid = 0.5 (lo + hi) and x_cand = P(mid).  P(a) = clamp(fmaf(a, x_far, fmaf(-a, x0, x0))) for norm 2
+ *                  and clamp(min(max(x_far, x0 - a), x0 + a)) for norm inf: x_adv is written by the function that wrote the
+ *                  candidate the model called adversarial, with the same a.
+ * 1 <= classes <= 32, max_halvings >= 1, step_scale finite and >= 0, clip_lo <= clip_hi, the row buffers not overlapping, or
+ * LIPASR_EINVAL; batch == 0 or n == 0: LIPASR_OK with nothing written. */
+int lipasr_hsj_search(lipasr_handle_t h, const float* logits, const int* labels, const float* x0, const int* n_valid,
+                      const float* u /* [batch][n]; HALVE */, const float* start_lo /* [batch] */, const float* start_hi /* [batch] */,
+                      const float* theta /* [batch] */, int batch, int classes, int n, int mode, int flags, int targeted,
+                      uint32_t clip0, uint32_t draw, uint64_t seed, float norm, float step_scale, int max_halvings, float clip_lo,
+                      float clip_hi, float* x_cand, float* x_far, float* x_adv, float* x_best, float* fstate /* [batch][8] */,
+                      int* istate /* [batch][8] */, lipasr_stream_t stream);
+
+/* Host-only (no GPU needed): the four calls above on host arrays, from the same inline functions in plain loops.  Same checks; the
+ * same bits except where fp64 sums run in another order (the L2 norms) or the libm differs (the L2 draws). */
+int lipasr_hsj_expand_host(const float* x, const float* delta, const int* n_valid, int batch, int n, int draws, uint32_t clip0,
+                           uint32_t it, uint32_t draw0, uint64_t seed, float norm, float clip_lo, float clip_hi, float* out);
+int lipasr_hsj_accumulate_host(const float* logits, const int* labels, const float* p, const float* x, const int* n_valid, int batch,
+                               int classes, int n, int draws, int targeted, double* sums, int* counts);
+int lipasr_hsj_direction_host(const double* sums, const int* counts, const int* n_valid, int batch, int n, float norm, float* u);
+int lipasr_hsj_search_host(const float* logits, const int* labels, const float* x0, const int* n_valid, const float* u,
+                           const float* start_lo, const float* start_hi, const float* theta, int batch, int classes, int n, int mode,
+                           int flags, int targeted, uint32_t clip0, uint32_t draw, uint64_t seed, float norm, float step_scale,
+                           int max_halvings, float clip_lo, float clip_hi, float* x_cand, float* x_far, float* x_adv, float* x_best,
+                           float* fstate, int* istate);
+/* Host-only: the instance lipasr_hsj_expand takes for rows of n elements -- the quads a thread holds (1, 2, 4, 8 in
+ * workgroups of 256 threads up to n = 8 192; 4, 6 plus 32 in workgroups of 1 024 threads up to n = 24 576; 0: the draw is generated
+ * twice) -- plus 64 where float4 accesses are taken. */
+int lipasr_debug_hsj_path(int n, int aligned);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
