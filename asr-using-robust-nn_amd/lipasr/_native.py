@@ -131,6 +131,10 @@ PROTOTYPES = {
     "lipasr_hsj_search_host": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_uint32, C.c_uint32, u64, f32, f32,
                                      i32, f32, f32, c_f, c_f, c_f, c_f, c_f, c_f]),
     "lipasr_debug_hsj_path": (i32, [i32, i32]),
+    "lipasr_room_apply": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, c_f, c_s]),
+    "lipasr_room_vjp": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, f32, c_f, c_s]),
+    "lipasr_room_apply_host": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
+    "lipasr_room_vjp_host": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, f32, c_f]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -203,7 +207,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_debug_apgd_path": 650, "lipasr_square_init": 660, "lipasr_square_step": 660, "lipasr_square_init_host": 660,
          "lipasr_square_step_host": 660, "lipasr_hsj_expand": 670, "lipasr_hsj_accumulate": 670, "lipasr_hsj_direction": 670,
          "lipasr_hsj_search": 670, "lipasr_hsj_expand_host": 670, "lipasr_hsj_accumulate_host": 670, "lipasr_hsj_direction_host": 670,
-         "lipasr_hsj_search_host": 670, "lipasr_debug_hsj_path": 670}
+         "lipasr_hsj_search_host": 670, "lipasr_debug_hsj_path": 670, "lipasr_room_apply": 680, "lipasr_room_vjp": 680,
+         "lipasr_room_apply_host": 680, "lipasr_room_vjp_host": 680}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -609,6 +614,39 @@ def hsj_search_host(logits, labels, x0, mode, flags, seed, norm, *, x_cand, x_fa
                                      _host_array(x_cand, np.float32, (b, n), "x_cand"), _host_array(x_far, np.float32, (b, n), "x_far"),
                                      _host_array(x_adv, np.float32, (b, n), "x_adv"), _host_array(x_best, np.float32, (b, n), "x_best"),
                                      _host_array(fstate, np.float32, (b, 8), "fstate"), _host_array(istate, np.int32, (b, 8), "istate")))
+
+
+def room_apply_host(x, rirs, *, n_valid=None, out=None):
+    """Host-only: lipasr_room_apply_host on NumPy arrays (x float32 [B, n], rirs float32 [R, taps]) -> float32 [B * R, n]."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rirs = np.ascontiguousarray(rirs, dtype=np.float32)
+    if x.ndim != 2 or rirs.ndim != 2:
+        raise ValueError("x must be [B, n] and rirs [R, taps]")
+    (b, n), (r, taps) = x.shape, rirs.shape
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    out = np.zeros((b * r, n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_room_apply_host(C.c_void_p(x.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data),
+                                     C.c_void_p(rirs.ctypes.data), taps, r, b, n, _host_array(out, np.float32, (b * r, n), "out")))
+    return out
+
+
+def room_vjp_host(g, rirs, *, n_valid=None, scale=1.0, out=None):
+    """Host-only: lipasr_room_vjp_host on NumPy arrays (g float32 [B * R, n], rirs float32 [R, taps]) -> float32 [B, n]."""
+    import numpy as np
+
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    rirs = np.ascontiguousarray(rirs, dtype=np.float32)
+    if g.ndim != 2 or rirs.ndim != 2 or rirs.shape[0] == 0 or g.shape[0] % rirs.shape[0]:
+        raise ValueError("g must be [B * R, n] and rirs [R, taps]")
+    (rows, n), (r, taps) = g.shape, rirs.shape
+    b = rows // r
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    out = np.zeros((b, n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_room_vjp_host(C.c_void_p(g.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data),
+                                   C.c_void_p(rirs.ctypes.data), taps, r, b, n, float(scale), _host_array(out, np.float32, (b, n), "out")))
+    return out
 
 
 def debug_table(which: int, sr_in: int = 16000):

@@ -19,6 +19,8 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: HopSkipJump, the label only, min. norm)    attack="black", kind="hsj", --norm inf | 2: hopskipjump_sweep over="mfcc" | "audio"
     (no prompt: the AutoAttack ensemble, robust accuracy)  attack="white", kind="auto", --norm inf | 2, over="mfcc" | "audio"
     (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth":smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
+    (no prompt: the attack played in a room, EOT)          attack="white" | "black", over="audio", --room R [--room-taps --room-t60 LO HI --room-seed]:
+                                                           over_the_air_sweep, kind="fgsm" | "pgd" | "apgd" | "auto" | "genetic" | "square"
 """
 from __future__ import annotations
 
@@ -380,6 +382,72 @@ def hopskipjump_sweep(models, train_data, val_data, test_data, test_labels, over
     return grid, acc, stats
 
 
+OVER_THE_AIR_KINDS = ("fgsm", "pgd", "apgd", "auto", "genetic", "square")
+
+
+def over_the_air_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, kind="pgd", rooms=4, room_taps=2048,
+                       room_t60=(0.15, 0.5), room_seed=0, domain="22k", standardize="before", grid=None, points=None, limit=None,
+                       **attack_kw):
+    """What is left of an attack over audio once it is PLAYED: two disjoint banks of ``rooms`` synthetic room impulse responses
+    each (lipasr.room.synthetic_rirs, one draw of 2 x rooms split in halves: an attack bank A and a held-out bank B), and per model
+    and grid point three accuracies, each the share of (clip, room of B) pairs the model still gets right:
+        "clean"   the clean clips through B
+        "dry"     adversarial clips made without the room (the attack of white_box_sweep / the query sweeps) through B
+        "air"     adversarial clips made through A (the same attack over OverTheAirClassifier: expectation over A) through B
+    ``kind``: one of OVER_THE_AIR_KINDS -- the attacks that optimise within a radius eps; the labels they push away from are each
+    model's own on the dry clip.  Files, lengths and standardisation as in white_box_sweep(over="audio"); the default grid is
+    AUDIO_SIGMAS for the gradient attacks and GENETIC_AUDIO_EPS for the query attacks.  The responses are drawn at the rate of the
+    rows (22 050 Hz for domain="22k").  Returns (grid, {model name: {"clean" | "dry" | "air": accuracies}})."""
+    from .room import RoomChannel, synthetic_rirs
+
+    builders = {"fgsm": lambda clf, e: A.FastGradientMethod(estimator=clf, eps=e, **attack_kw),
+                "pgd": lambda clf, e: A.ProjectedGradientDescent(estimator=clf, eps=e, **attack_kw),
+                "apgd": lambda clf, e: A.AutoProjectedGradientDescent(estimator=clf, eps=e, **attack_kw),
+                "auto": lambda clf, e: A.AutoAttack(clf, eps=e, **{"eps_step": 2.0 * e, "shape": None, **attack_kw}),
+                "genetic": lambda clf, e: A.GeneticAttack(clf, e, **attack_kw),
+                "square": lambda clf, e: A.SquareAttack(clf, eps=e, **{"shape": None, **attack_kw})}
+    if kind not in builders:
+        raise ValueError(f"a room takes an attack that optimises within a radius -- {', '.join(OVER_THE_AIR_KINDS)} -- not {kind!r}")
+    rooms = int(rooms)
+    if rooms < 1:
+        raise ValueError(f"rooms = {rooms}: at least one room per bank")
+    rows = _TestRows(models, train_data, val_data, test_data, "audio", standardize, test_filenames, domain, limit)
+    truth = np.asarray(rows.limited(test_labels)).argmax(axis=1)
+    grid = list((GENETIC_AUDIO_EPS if kind in ("genetic", "square") else AUDIO_SIGMAS) if grid is None else grid)[:points]
+    banks = {}  # rate of the rows -> (A, B)
+
+    def channels(rate):
+        if rate not in banks:
+            h = synthetic_rirs(2 * rooms, sr=rate, taps=room_taps, t60=room_t60, seed=room_seed)
+            banks[rate] = (RoomChannel(h[:rooms]), RoomChannel(h[rooms:]))
+        return banks[rate]
+
+    acc = {name: {k: [] for k in ("clean", "dry", "air")} for name in models}
+    for item in grid:
+        for name, model in models.items():
+            hits = {k: np.zeros((rows.n, rooms), dtype=bool) for k in ("clean", "dry", "air")}
+            for (sr, _, _, _), (clf, x, lt, idx) in zip(rows._work, rows.batches(model)):
+                bank_a, bank_b = channels(22050 if domain == "22k" else int(sr))
+                through_a, through_b = A.OverTheAirClassifier(clf, bank_a), A.OverTheAirClassifier(clf, bank_b)
+                made = {"clean": x,
+                        "dry": build_or_keep(builders[kind], clf, item, x, lt),
+                        "air": build_or_keep(builders[kind], through_a, item, x, lt)}
+                for k, rows_k in made.items():
+                    heard = through_b.predict_each_device(rows_k, lengths=lt, logits=True).argmax(dim=2).cpu().numpy()
+                    hits[k][idx] = heard == truth[idx][:, None]
+            for k, label in (("clean", "clean audio"), ("dry", "adversarial audio made without the room"),
+                             ("air", "adversarial audio made through the attack rooms")):
+                a = float(hits[k].mean()) if rows.n else float("nan")
+                acc[name][k].append(a)
+                print(f"Accuracy through {rooms} held-out rooms on {label}{_tag(name)}: {a * 100}% ({item})")
+    return grid, {name: {k: np.asarray(v) for k, v in d.items()} for name, d in acc.items()}
+
+
+def build_or_keep(build, clf, item, x, lt):
+    """The attack ``build(clf, item)`` on the rows ``x``, or the rows themselves at strength 0."""
+    return build(clf, item).generate_device(x, None, lengths=lt) if item != 0 else x
+
+
 def dolphin_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, grid=DOLPHIN_CARRIER_LEVELS, a1=1.0, a2=0.5,
                   standardize="before", points=None, limit=None):
     """DolphinAttack (lipasr.dolphin) against the carrier level: every file of ``test_filenames`` (16 kHz) becomes amplitude-
@@ -622,6 +690,10 @@ def main(argv=None):
     ap.add_argument("--n0", type=int, default=100, help="smooth: draws that select the class")
     ap.add_argument("--n", type=int, default=100000, help="smooth: draws that estimate its vote share")
     ap.add_argument("--alpha", type=float, default=0.001, help="smooth: failure probability of the certificate")
+    ap.add_argument("--room", type=int, default=None, help="white|black over audio: rooms per bank -- the attack is also made through R synthetic rooms and all is heard through R others")
+    ap.add_argument("--room-taps", type=int, default=2048, help="--room: samples of each room impulse response")
+    ap.add_argument("--room-t60", type=float, nargs=2, default=(0.15, 0.5), metavar=("LO", "HI"), help="--room: range of the reverberation time in seconds")
+    ap.add_argument("--room-seed", type=int, default=0, help="--room: seed of the two banks")
     ap.add_argument("--max-iter-1", type=int, default=1000)
     ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
@@ -642,6 +714,20 @@ def main(argv=None):
     names = None
     if args.over == "audio" or args.attack == "dolphin":
         names, labels = _noise_files(args.noise_dir, n_classes)
+    if args.room is not None:
+        if args.attack not in ("white", "black") or args.over != "audio":
+            raise ValueError("--room goes with --attack white or black and --over audio")
+        kw = {k: v for k, v in (("pop_size", args.pop_size if args.kind == "genetic" else None),
+                                ("max_iter", args.max_iter if args.kind in ("genetic", "square", "apgd") else None)) if v is not None}
+        if args.norm != "inf":
+            if args.kind not in ("fgsm", "pgd", "apgd", "auto"):
+                raise ValueError("--norm applies to --kind fgsm, pgd, apgd and auto")
+            kw["norm"] = int(args.norm)
+        if args.kind == "apgd":
+            kw["loss_type"] = {"ce": "cross_entropy", "dlr": "difference_logits_ratio"}[args.loss]
+        return over_the_air_sweep(models, train_data, val_data, test_data, labels, names, kind=args.kind, rooms=args.room,
+                                  room_taps=args.room_taps, room_t60=tuple(args.room_t60), room_seed=args.room_seed,
+                                  standardize=args.standardize, points=args.points, **kw)
     if args.attack == "black":
         if args.kind == "genetic":
             kw = {k: v for k, v in (("pop_size", args.pop_size), ("max_iter", args.max_iter)) if v is not None}

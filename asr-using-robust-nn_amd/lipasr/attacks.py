@@ -17,6 +17,8 @@ amplitude units), the gradient reaching the samples through the native backward 
 ``lengths=`` a batch holds clips of different lengths, one per row (lipasr_mfcc_plan_vjp_ragged): the perturbation stays inside
 each clip and the rest of the row comes back untouched.  Over a short-window extractor (Speaker recognition: n_fft = win_length =
 441, hop 220) the gradient goes through lipasr_mfcc_plan_vjp_short.
+``OverTheAirClassifier`` puts a bank of room impulse responses (lipasr/room.py) in front of a WaveformClassifier and answers with
+the expectation over the rooms: every attack over audio, white-box or black-box, then optimises the example that is PLAYED.
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.  ``GeneticAttack`` (lipasr/genetic.py,
@@ -35,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .estimators import TensorFlowV2Classifier, WaveformClassifier, _as_given, _dev, _Estimator, _to_dev
+from .estimators import OverTheAirClassifier, TensorFlowV2Classifier, WaveformClassifier, _as_given, _dev, _Estimator, _to_dev
 from .extract_features_construct_dataset import read_wav, _extractor
 from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack: scores only; lipasr/genetic.py)
 from .keras import to_categorical

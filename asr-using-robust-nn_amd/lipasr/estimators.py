@@ -1,8 +1,10 @@
 """The estimators the attacks and read-outs run over, and the one device-side surface they share.
 
 ``TensorFlowV2Classifier`` (ART's wrapper, attacks.py:500-504) takes rows of MFCC features, the model's own inputs;
-``WaveformClassifier`` (ours) puts the MFCC stage in front of the model and takes rows of audio.  Both answer the same calls on
-device tensors, so that an attack asks its estimator and never what kind of estimator it holds:
+``WaveformClassifier`` (ours) puts the MFCC stage in front of the model and takes rows of audio; ``OverTheAirClassifier`` (ours) puts
+a bank of room impulse responses (lipasr.room.RoomChannel) in front of a WaveformClassifier and answers with the expectation over
+the rooms, so that every attack over audio has an over-the-air form.  All answer the same calls on device tensors, so that an attack
+asks its estimator and never what kind of estimator it holds:
 
     model, nb_classes, input_shape, batch_limit, clip_values (None: no clamp -- always on a TensorFlowV2Classifier)
     rows_device(x)                                  x as the float32 device tensor [B, input_shape[0]]
@@ -13,6 +15,7 @@ device tensors, so that an attack asks its estimator and never what kind of esti
     loss_gradient_device(xt, yt, out=None, lengths=None)
     output_vjp_device(xt, vt, on_logits=False, ..., lengths=None)
     jacobian_device(xt, on_logits=True, ..., lengths=None)
+    predict_each_device(xt, lengths=None, logits=False)   OverTheAirClassifier only: [B, R, classes], every room on its own
 
 ``lipasr.attacks`` re-exports every name of this module.
 """
@@ -224,14 +227,18 @@ class WaveformClassifier(_Estimator):
             raise ValueError(f"lengths must hold one sample count per row ([{b}]), got {tuple(t.shape)}")
         return t
 
-    def clip_mask(self, lt):
-        """bool [B, n]: the positions of each row inside its clip -- [0, n) samples (domain "input"), or the [0, ceil(n * 22050 /
-        sr_in)) positions the kernels derive from it (domain "22k", the same float64 expression as clip_lengths)."""
+    def clip_positions(self, lt):
+        """int32 [B]: the positions of each row that belong to its clip -- its samples (domain "input"), or the ceil(n * 22050 /
+        sr_in) positions the kernels derive from them (domain "22k", the same float64 expression as clip_lengths)."""
         ex = self.extractor
         n = lt.clamp(0, ex.n_samp)
         if self.domain == "22k":
             n = torch.ceil(n.to(torch.float64) * (22050.0 / float(ex.sr_in))).to(torch.int32)
-        return torch.arange(self.n, device=lt.device, dtype=torch.int32)[None, :] < n[:, None]
+        return n
+
+    def clip_mask(self, lt):
+        """bool [B, n]: the positions of each row inside its clip, [0, clip_positions)."""
+        return torch.arange(self.n, device=lt.device, dtype=torch.int32)[None, :] < self.clip_positions(lt)[:, None]
 
     def features_device(self, xt, lengths=None):
         """[B <= batch_max, n] device tensor -> standardised features [B, 20 * utterance_length]."""
@@ -318,4 +325,95 @@ class WaveformClassifier(_Estimator):
                                               N.ptr(jf), nf, b * nf, N.stream_ptr()))
             for k in range(c):
                 self._features_vjp(xb, jf[k], lb, out[k, s:s + b])
+        return out.permute(1, 0, 2)
+
+
+class OverTheAirClassifier(WaveformClassifier):
+    """A WaveformClassifier heard through rooms: every clip goes through each of the R room impulse responses of a
+    lipasr.room.RoomChannel before the MFCC stage, and the estimator answers with the expectation over the rooms (expectation over
+    transformations, the robustness half of Qin et al. 2019).  It shares the base's model, extractor, statistics, domain and
+    ``clip_values`` and takes the same rows, so any attack over audio runs on it unchanged; the responses are applied to the rows
+    as they come, so their sample rate has to be the rows' (22 050 Hz in domain "22k"): that is the caller's business.
+    ``lengths`` keep the base's meaning (samples at ``sr_in``); the channel cuts the reverberant tail at the clip's end, so they hold
+    behind it too, and the gradient stays exactly 0 beyond each clip.
+        predict_device        the mean over the rooms of the base's probabilities (or logits)
+        predict_each_device   [B, R, classes], every room on its own: the evaluation read-out
+        loss_gradient_device  d mean_{b, j} CE / dx: the base's gradient at the B R expanded rows (its mean over a chunk's rows already
+                              averages over the rooms) carried back through the channel and summed over the rooms
+        output_vjp_device, jacobian_device   the mean over the rooms of the base's
+        own_labels_device     the base's: the prediction on the DRY clip, which is what was said
+    One native call of the base takes c R rows, so ``batch_limit`` is the base's divided by R (in clips)."""
+
+    def __init__(self, base, channel):
+        from .room import RoomChannel
+
+        if not isinstance(base, WaveformClassifier) or isinstance(base, OverTheAirClassifier):
+            raise TypeError("base must be a WaveformClassifier (and not itself an OverTheAirClassifier)")
+        if not isinstance(channel, RoomChannel):
+            raise TypeError("channel must be a lipasr.room.RoomChannel")
+        if channel.count > base.batch_limit:
+            raise ValueError(f"a bank of {channel.count} rooms does not fit the base's batch_limit {base.batch_limit}")
+        if channel.device != base.extractor.device:
+            raise ValueError(f"the channel is on {channel.device}, the base on {base.extractor.device}")
+        _Estimator.__init__(self, base.model, base.nb_classes)
+        self.base, self.channel = base, channel
+        self.utterance_length, self.domain, self.extractor = base.utterance_length, base.domain, base.extractor
+        self.n, self.input_shape, self.mean, self.scale, self.clip_values = base.n, base.input_shape, base.mean, base.scale, base.clip_values
+        self._bs = base.batch_limit // channel.count
+
+    def _chunks(self, xt, lt):
+        """Per chunk of batch_limit clips: (slice, the c R rows behind the channel, their lengths for the base, the channel's n_valid)."""
+        r = self.channel.count
+        for s in range(0, xt.shape[0], self._bs):
+            sl = slice(s, s + self._bs)
+            lb = None if lt is None else lt[sl]
+            nv = None if lb is None else self.clip_positions(lb).contiguous()
+            yield sl, self.channel.apply(xt[sl], nv), None if lb is None else lb.repeat_interleave(r), nv
+
+    def predict_each_device(self, xt, lengths=None, logits=False):
+        """[B, n] -> [B, R, classes]: the base's probabilities (or logits) for every clip through every room."""
+        xt = self.rows_device(xt)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        r = self.channel.count
+        return torch.cat([self.base.predict_device(rows, logits=logits, lengths=lr).view(-1, r, self.nb_classes)
+                          for _, rows, lr, _ in self._chunks(xt, lt)])
+
+    def predict_device(self, xt, logits=False, lengths=None):
+        return self.predict_each_device(xt, lengths=lengths, logits=logits).mean(dim=1)
+
+    def loss_gradient_device(self, xt, yt, out=None, lengths=None):
+        """d mean_{b, j} CE(f(features(h_j * x_b)), y_b) / dx on device tensors ([B, n], one-hot [B, classes]) -> [B, n]."""
+        xt = self.rows_device(xt)
+        out = torch.empty_like(xt) if out is None else out
+        lt = self.lengths_device(lengths, xt.shape[0])
+        r = self.channel.count
+        for sl, rows, lr, nv in self._chunks(xt, lt):
+            g = self.base.loss_gradient_device(rows, yt[sl].repeat_interleave(r, dim=0), lengths=lr)
+            self.channel.vjp(g, nv, scale=1.0, out=out[sl])
+        return out
+
+    def output_vjp_device(self, xt, vt, on_logits=False, lengths=None):
+        """sum_c v[b, c] d out_c / dx for the mean output over the rooms: [B, n], [B, classes] -> [B, n]."""
+        xt = self.rows_device(xt)
+        out = torch.empty_like(xt)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        r = self.channel.count
+        for sl, rows, lr, nv in self._chunks(xt, lt):
+            g = self.base.output_vjp_device(rows, vt[sl].repeat_interleave(r, dim=0), on_logits=on_logits, lengths=lr)
+            self.channel.vjp(g, nv, scale=1.0 / r, out=out[sl])
+        return out
+
+    def jacobian_device(self, xt, on_logits=True, lengths=None):
+        """d out_c / dx of the mean output over the rooms for every class: [B, n] -> a [B, classes, n] view of class-major storage.
+        Per chunk ONE Jacobian of the base at the c R rows, then one pass of the channel's adjoint per class: row c carries the bits
+        of ``output_vjp_device`` with the one-hot e_c."""
+        xt = self.rows_device(xt)
+        b_all, c = xt.shape[0], self.nb_classes
+        lt = self.lengths_device(lengths, b_all)
+        r = self.channel.count
+        out = torch.empty(c, b_all, self.n, device=xt.device)
+        for sl, rows, lr, nv in self._chunks(xt, lt):
+            jf = self.base.jacobian_device(rows, on_logits=on_logits, lengths=lr).permute(1, 0, 2)  # the base's own storage: [classes][c R][n]
+            for k in range(c):
+                self.channel.vjp(jf[k], nv, scale=1.0 / r, out=out[k, sl])
         return out.permute(1, 0, 2)

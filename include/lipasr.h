@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 670. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 680. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -40,6 +40,8 @@
  * the host-only lipasr_square_init_host / lipasr_square_step_host.
  * 670: HopSkipJump: lipasr_hsj_expand (the perturbed copies), lipasr_hsj_accumulate (the two fp64 sums), lipasr_hsj_direction,
  * lipasr_hsj_search (one query of the start, the step-size halving or the bisection), their _host twins and lipasr_debug_hsj_path.
+ * 680: the over-the-air channel: lipasr_room_apply (every clip through every room impulse response of a bank), lipasr_room_vjp (its
+ * exact adjoint, summed over the rooms) and their _host twins.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -756,6 +758,33 @@ int lipasr_hsj_search_host(const float* logits, const int* labels, const float* 
  * workgroups of 256 threads up to n = 8 192; 4, 6 plus 32 in workgroups of 1 024 threads up to n = 24 576; 0: the draw is generated
  * twice) -- plus 64 where float4 accesses are taken. */
 int lipasr_debug_hsj_path(int n, int aligned);
+
+/* The over-the-air channel (lipasr/room.py, OverTheAirClassifier): a bank of room impulse responses rirs [rir_count][taps] (device)
+ * between the loudspeaker and the microphone, as a batched FIR.  x is [clips][n]; out and g are [clips * rir_count][n], row
+ * b * rir_count + j being clip b through room j.  n_valid [clips] (or NULL: n for every clip) holds POSITIONS IN THE ROW, not
+ * samples at the file's rate; values are clamped to [0, n]; nv_b below is the clamped value.
+ *   lipasr_room_apply:  out[b * R + j][t] = sum_{k = 0}^{min(t, taps - 1)} rirs[j][k] * x[b][t - k]   for t < nv_b, 0 for nv_b <= t < n.
+ *   lipasr_room_vjp:    gx[b][s] = scale * sum_j sum_{k < taps, s + k < nv_b} rirs[j][k] * g[b * R + j][s + k]   for s < nv_b, 0 beyond:
+ *                       the exact adjoint of lipasr_room_apply with the rooms summed in the same launch.
+ * The response is causal, as long as its input and CUT at the end of the clip: the reverberant tail past nv_b is dropped, so that a
+ * clip's length means the same thing on both sides of the channel (an MFCC stage behind it takes the same lengths).  x and g are
+ * read only below nv_b.  Arithmetic: exact fp32 (v_mfma_f32_32x32x2_f32, one fma chain per output element, by room and then by
+ * signal position upwards); no atomics, no workspace, one launch, nothing allocated or synchronised, so two runs give the same bits
+ * and a clip's rows have the bits they would have if the clip were launched alone.  The signals are taken as finite: the zeros of
+ * the banded operand are multiplied, not skipped.  Any n up to 2^30, any taps in [1, 8192], any alignment of every pointer (all
+ * accesses are single floats).  LIPASR_OK without a launch when clips, rir_count or n is 0; LIPASR_EINVAL for taps outside
+ * [1, 8192], a null pointer (n_valid excepted), a non-finite scale, or an output that overlaps an input -- all before the device is
+ * touched. */
+int lipasr_room_apply(const float* x, const int* n_valid, const float* rirs, int taps, int rir_count, int clips, int n, float* out,
+                      lipasr_stream_t stream);
+int lipasr_room_vjp(const float* g, const int* n_valid, const float* rirs, int taps, int rir_count, int clips, int n, float scale,
+                    float* gx, lipasr_stream_t stream);
+/* Host-only (no GPU needed): the same formulas on host arrays in plain loops, the fp32 accumulator taking the taps in (j, k)
+ * order, each tap the exact product added and rounded to fp32.  Same checks. */
+int lipasr_room_apply_host(const float* x, const int* n_valid, const float* rirs, int taps, int rir_count, int clips, int n,
+                           float* out);
+int lipasr_room_vjp_host(const float* g, const int* n_valid, const float* rirs, int taps, int rir_count, int clips, int n,
+                         float scale, float* gx);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
