@@ -6,9 +6,7 @@
 //   run.  Cross-entropy in the forms that do not cancel: logsumexp = m + log1p(sum_{c != argmax} exp(z_c - m)), and the
 //   gradient at the label is -(sum_{c != y} p_c), not p_y - 1.
 //
-// apgd_step_kernel<T, NQ>: T threads per row.  A thread owns the quads q = t, t + T, ... of its row (elements 4q .. 4q + 3), whatever
-//   the alignment: float4 loads where n is a multiple of 4 and every base sits on 16 bytes, four scalars otherwise, the same
-//   element-to-thread map in both, so the alignment never changes a value.
+// apgd_step_kernel<T, NQ>: T threads per row.  A thread owns the quads q = t, t + T, ... of its row (row.h states the row contract).
 //     T = 64,  NQ = 1, 2, 4, 8   one wavefront per row, four rows per block, the four row arrays of the step (the start point, its
 //                                gradient, the previous iterate, the clean row) in registers, as lp_step_kernel holds its three:
 //                                n <= 2 048, the 880 and 2 020 feature rows (NQ 4 and 8).  No LDS, no barrier.
@@ -25,6 +23,7 @@
 //   the fp32 inputs and rounded once, so that a projection of a point that is already a corner of the ball returns its bits.
 //   No atomics, no workspace, nothing waits on another workgroup.  Nothing about its speed has been measured.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -99,44 +98,6 @@ struct ApgdArgs {
   float eps, eta0, lo, hi, momentum, rho;
 };
 
-// the sum of v over the T threads of a row, the same bits in every thread: xor butterfly per wavefront, then (T > 64) one double
-// per wavefront in LDS, added by every thread in index order
-template <int T>
-__device__ __forceinline__ double apgd_row_sum(double v, double* red) {
-  v = wave_sum_d(v);
-  if constexpr (T > 64) {
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = 0.0;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) v += red[w];
-    __syncthreads();
-  }
-  return v;
-}
-
-__device__ __forceinline__ void apgd_ld4(const float* __restrict__ p, int k0, int n, bool vec, float (&v)[4]) {
-  if (vec) {  // n is a multiple of 4 and p sits on 16 bytes: the quad is whole
-    const float4 t = *reinterpret_cast<const float4*>(p + k0);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (k0 + e < n) ? p[k0 + e] : 0.0f;
-  }
-}
-
-__device__ __forceinline__ void apgd_st4(float* __restrict__ p, int k0, int n, bool vec, const float (&v)[4]) {
-  if (vec) {
-    *reinterpret_cast<float4*>(p + k0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (k0 + e < n) p[k0 + e] = v[e];
-  }
-}
-
-__device__ __forceinline__ double apgd_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 template <int T, int NQ>
 __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a) {
   __shared__ double red[T == 64 ? 1 : T / 64];
@@ -144,9 +105,9 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
   const int row = T == 64 ? (int)(blockIdx.x * 4 + (threadIdx.x >> 6)) : (int)blockIdx.x;
   if (row >= a.rows) return;  // uniform over the row's threads; a T = 64 block never meets a barrier
   const int n = a.n;
-  const bool vec = a.vec != 0;
+  const bool vec = a.vec != 0;  // n is a multiple of 4 and every base sits on 16 bytes: each quad is whole
   const size_t base = (size_t)row * n;
-  const int nv = a.n_valid ? min(max(a.n_valid[row], 0), n) : n;
+  const int nv = row_valid(a.n_valid, row, n);
   const int quads = (n + 3) >> 2;
   const bool first = (a.flags & 1) != 0, last = (a.flags & 2) != 0;
 
@@ -177,18 +138,18 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
     for (int q = t; q < quads; q += T) {
       const int k0 = 4 * q;
       float xv[4], cv[4];
-      apgd_ld4(a.x0 + base, k0, n, vec, cv);
-      apgd_ld4(a.x + base, k0, n, vec, xv);
+      ld4(a.x0 + base, k0, n, vec, cv);
+      ld4(a.x + base, k0, n, vec, xv);
 #pragma unroll
       for (int e = 0; e < 4; ++e) xv[e] = (k0 + e < nv) ? xv[e] : cv[e];
-      if (hitr) apgd_st4(a.x_adv + base, k0, n, vec, xv);
+      if (hitr) st4(a.x_adv + base, k0, n, vec, xv);
       if (upd_best) {
-        apgd_st4(a.x_best + base, k0, n, vec, xv);
+        st4(a.x_best + base, k0, n, vec, xv);
         float gv[4];
-        apgd_ld4(a.g + base, k0, n, vec, gv);
+        ld4(a.g + base, k0, n, vec, gv);
 #pragma unroll
         for (int e = 0; e < 4; ++e) gv[e] = (k0 + e < nv) ? gv[e] : cv[e];
-        apgd_st4(a.g_best + base, k0, n, vec, gv);
+        st4(a.g_best + base, k0, n, vec, gv);
       }
     }
   }
@@ -225,14 +186,14 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
   auto fetch = [&](int s, int q) {
     if (q < quads) {
       const int k0 = 4 * q;
-      apgd_ld4(xs, k0, n, vec, XC[s]);
-      apgd_ld4(gs, k0, n, vec, GC[s]);
-      apgd_ld4(a.x0 + base, k0, n, vec, X0[s]);
+      ld4(xs, k0, n, vec, XC[s]);
+      ld4(gs, k0, n, vec, GC[s]);
+      ld4(a.x0 + base, k0, n, vec, X0[s]);
       if (no_mom) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) XP[s][e] = XC[s][e];
       } else {
-        apgd_ld4(a.x_prev + base, k0, n, vec, XP[s]);
+        ld4(a.x_prev + base, k0, n, vec, XP[s]);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) GC[s][e] = GC[s][e] != GC[s][e] ? 0.0f : GC[s][e];  // NaN -> 0
@@ -266,14 +227,14 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
       for (int e = 0; e < 4; ++e)
         if (4 * q + e < nv) s += (double)GC[sl][e] * (double)GC[sl][e];
     });
-    const double nrm = sqrt(apgd_row_sum<T>(s, red));
+    const double nrm = sqrt(block_sum_d<T>(s, red));
     kdir = isfinite(nrm) ? 1.0 / (nrm + kApgdTol) : 0.0;
   }
   // u = clamp(xc + eta d) - x0, the argument of the first projection
   auto dl1 = [&](int sl, int e) {
     const float gq = GC[sl][e];
     const double d = l2 ? (isfinite(gq) ? (double)gq * kdir : 0.0) : (gq > 0.0f ? 1.0 : (gq < 0.0f ? -1.0 : 0.0));
-    return apgd_clamp((double)XC[sl][e] + etad * d, lo, hi) - (double)X0[sl][e];
+    return clampf((double)XC[sl][e] + etad * d, lo, hi) - (double)X0[sl][e];
   };
   double fz = 1.0;
   if (l2) {
@@ -283,14 +244,14 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
       for (int e = 0; e < 4; ++e)
         if (4 * q + e < nv) { const double dl = dl1(sl, e); s += dl * dl; }
     });
-    fz = fmin(1.0, epsd / (sqrt(apgd_row_sum<T>(s, red)) + kApgdTol));
+    fz = fmin(1.0, epsd / (sqrt(block_sum_d<T>(s, red)) + kApgdTol));
   }
   // the argument of the second projection: clamp(xc + a (z - xc) + (1 - a)(xc - xp)) - x0
   auto dl2 = [&](int sl, int e) {
     const double dl = dl1(sl, e), c = (double)X0[sl][e], xc = (double)XC[sl][e];
-    const double z = c + (l2 ? dl * fz : apgd_clamp(dl, -epsd, epsd));
+    const double z = c + (l2 ? dl * fz : clampf(dl, -epsd, epsd));
     const double v = xc + am * (z - xc) + bm * (xc - (double)XP[sl][e]);
-    return apgd_clamp(v, lo, hi) - c;
+    return clampf(v, lo, hi) - c;
   };
   double fv = 1.0;
   if (l2) {
@@ -300,7 +261,7 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
       for (int e = 0; e < 4; ++e)
         if (4 * q + e < nv) { const double dl = dl2(sl, e); s += dl * dl; }
     });
-    fv = fmin(1.0, epsd / (sqrt(apgd_row_sum<T>(s, red)) + kApgdTol));
+    fv = fmin(1.0, epsd / (sqrt(block_sum_d<T>(s, red)) + kApgdTol));
   }
   for_quads([&](int sl, int q) {
     if (q >= quads) return;
@@ -310,11 +271,11 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void apgd_step_kernel(ApgdArgs a
     for (int e = 0; e < 4; ++e) {
       const bool in = k0 + e < nv;
       const double dl = dl2(sl, e), c = (double)X0[sl][e];
-      xn[e] = in ? (float)(c + (l2 ? dl * fv : apgd_clamp(dl, -epsd, epsd))) : X0[sl][e];
+      xn[e] = in ? (float)(c + (l2 ? dl * fv : clampf(dl, -epsd, epsd))) : X0[sl][e];
       xo[e] = in ? XC[sl][e] : X0[sl][e];
     }
-    apgd_st4(a.x_prev + base, k0, n, vec, xo);
-    apgd_st4(a.x + base, k0, n, vec, xn);
+    st4(a.x_prev + base, k0, n, vec, xo);
+    st4(a.x + base, k0, n, vec, xn);
   });
 }
 
@@ -397,9 +358,8 @@ int lipasr_apgd_step(lipasr_handle_t h, float* x, float* x_prev, const float* x0
   constexpr int ns = (int)(sizeof(sp) / sizeof(sp[0]));
   for (int i = 0; i < ns; ++i)
     for (int j = i + 1; j < ns; ++j) {
-      if (!(sp[i].written || sp[j].written) || sp[i].bytes == 0 || sp[j].bytes == 0) continue;
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(sp[i].p), b0 = reinterpret_cast<uintptr_t>(sp[j].p);
-      LP_CHECK_ARG(a0 + sp[i].bytes <= b0 || b0 + sp[j].bytes <= a0, "%s: %s overlaps %s", fn, sp[i].name, sp[j].name);
+      if (!(sp[i].written || sp[j].written)) continue;
+      LP_CHECK_ARG(!spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes), "%s: %s overlaps %s", fn, sp[i].name, sp[j].name);
     }
   ApgdArgs a;
   a.x = x; a.x_prev = x_prev; a.x0 = x0; a.g = g; a.x_best = x_best; a.g_best = g_best; a.x_adv = x_adv;

@@ -21,6 +21,7 @@
 //           ragged clip's padding) keeps the bits of x.
 // VEC = 4 needs n, both strides and the bases of jac and x multiples of 16 bytes; anything else takes VEC = 1.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -43,16 +44,6 @@ struct DeepfoolArgs {
   int* target;  // or null
   int* state;   // or null
 };
-
-template <int VEC>
-__device__ __forceinline__ void df_ld(const float* __restrict__ p, int i, float (&x)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = reinterpret_cast<const float4*>(p)[i];
-    x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-  } else {
-    x[0] = p[i];
-  }
-}
 
 __device__ __forceinline__ void df_result(const DeepfoolArgs& a, size_t b, float dist, int target, int state) {
   if (a.dist) a.dist[b] = dist;
@@ -100,13 +91,13 @@ __global__ __launch_bounds__(kDfThreads) void deepfool_step_kernel(DeepfoolArgs 
   for (int k = 0; k < kDfMaxC; ++k) acc[k] = 0.0;
   for (int i = tid; i < nv; i += kDfThreads) {
     float jc[VEC];
-    df_ld<VEC>(Jc, i, jc);
+    ldv<VEC>(Jc, i, jc);
 #pragma unroll
     for (int g = 0; g < kDfMaxC; g += kDfGroup) {
       if (g < C) {  // uniform
         float jk[kDfGroup][VEC];
 #pragma unroll
-        for (int r = 0; r < kDfGroup; ++r) df_ld<VEC>(J + (size_t)min(g + r, C - 1) * a.stride_c, i, jk[r]);
+        for (int r = 0; r < kDfGroup; ++r) ldv<VEC>(J + (size_t)min(g + r, C - 1) * a.stride_c, i, jk[r]);
 #pragma unroll
         for (int r = 0; r < kDfGroup; ++r)
 #pragma unroll
@@ -153,22 +144,16 @@ __global__ __launch_bounds__(kDfThreads) void deepfool_step_kernel(DeepfoolArgs 
   const float lo = a.lo, hi = a.hi;
   for (int i = tid; i < nv; i += kDfThreads) {
     float jl[VEC], jc[VEC], x[VEC];
-    df_ld<VEC>(Jl, i, jl);
-    df_ld<VEC>(Jc, i, jc);
-    df_ld<VEC>(xr, i, x);
+    ldv<VEC>(Jl, i, jl);
+    ldv<VEC>(Jc, i, jc);
+    ldv<VEC>(xr, i, x);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       const double w = (double)jl[e] - (double)jc[e];
       const float d = (NORM == 2) ? (float)(step * w) : (w > 0.0 ? stepf : (w < 0.0 ? -stepf : 0.0f));
-      float v = (d == 0.0f) ? x[e] : x[e] + d;  // (x + 0 would turn a -0 into +0)
-      v = v < lo ? lo : (v > hi ? hi : v);
-      x[e] = v;
+      x[e] = clampf((d == 0.0f) ? x[e] : x[e] + d, lo, hi);  // (x + 0 would turn a -0 into +0)
     }
-    if constexpr (VEC == 4) {
-      reinterpret_cast<float4*>(xr)[i] = make_float4(x[0], x[1], x[2], x[3]);
-    } else {
-      xr[i] = x[0];
-    }
+    stv<VEC>(xr, i, x);
   }
 }
 

@@ -8,9 +8,8 @@
 //   where an element of the quad mutates, and clamps to the eps ball and to the clip range.  A quad that lies wholly in the
 //   padding is a copy of x0 without a draw or a parent load; a child with parents (a, -1) is a copy of member a.
 //   The counter holds the clip, the generation and the member, never the row's position in the call, so a chunk of any size at
-//   any start draws what one big call would.  Loads and stores are float4 where the row (of x0, of either parent, of the child)
-//   starts on 16 bytes, four scalars per lane otherwise; the last, partial quad of a row is scalar.  The quads stay keyed by the
-//   element index, not by the address, so the alignment never changes a value.
+//   any start draws what one big call would.  The quads move as row.h says, `whole` judged per array (x0, either parent, the
+//   child): the row starts on 16 bytes and the quad is not the partial last one.
 //   16 bytes move per element (two parents, x0, the child) against ten Philox rounds per four elements.  Measured on the
 //   MI355X at 1024 rows x 22 050 (profiles/genetic_timing.txt): 75 us with two parents, 4.8 TB/s of those nominal bytes (x0 and
 //   the parents are shared between children, so part of the reads are cache hits), and 59 us for the initial population, which
@@ -23,6 +22,7 @@
 //   every run), and per child two inverse-CDF draws from one Philox block against the sums in LDS.  No global atomics; no other
 //   workgroup touches the clip's outputs.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -47,23 +47,12 @@ __host__ __device__ __forceinline__ void genetic_quad(uint64_t seed, uint64_t q,
       t = fmaf(step, v, t);
     }
     const float l = x[e] - eps, h = x[e] + eps;
-    t = t < l ? l : (t > h ? h : t);
-    t = t < lo ? lo : (t > hi ? hi : t);
+    t = clampf(clampf(t, l, h), lo, hi);
     out[e] = e < nvq ? t : x[e];
   }
 }
 
 __host__ __device__ __forceinline__ int genetic_index(int i, int P) { return i < 0 ? 0 : (i >= P ? P - 1 : i); }
-
-__device__ __forceinline__ void ga_load4(const float* __restrict__ r, bool vec, int k0, int n, float (&v)[4]) {
-  if (vec && k0 + 4 <= n) {
-    const float4 t = *reinterpret_cast<const float4*>(r + k0);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (k0 + e < n) ? r[k0 + e] : 0.0f;
-  }
-}
 
 __global__ __launch_bounds__(kGaThreads) void genetic_breed_kernel(const float* __restrict__ x0, const int* __restrict__ n_valid,
                                                                     const float* __restrict__ pop_in, const int* __restrict__ parents,
@@ -84,8 +73,7 @@ __global__ __launch_bounds__(kGaThreads) void genetic_breed_kernel(const float* 
     copy = ic < 0;
     cr = copy ? ar : pop_in + ((size_t)b * P + genetic_index(ic, P)) * (size_t)n;
   }
-  int nv = n;
-  if (n_valid) nv = min(max(n_valid[b], 0), n);
+  const int nv = row_valid(n_valid, b, n);
   const bool xvec = (reinterpret_cast<uintptr_t>(xr) & 15) == 0, avec = (reinterpret_cast<uintptr_t>(ar) & 15) == 0,
              cvec = (reinterpret_cast<uintptr_t>(cr) & 15) == 0, ovec = (reinterpret_cast<uintptr_t>(orow) & 15) == 0;
   const bool same = ar == cr;
@@ -93,15 +81,16 @@ __global__ __launch_bounds__(kGaThreads) void genetic_breed_kernel(const float* 
   const int quads = (n + 3) >> 2;
   for (int q = tid; q < quads; q += kGaThreads) {
     const int k0 = q * 4;
+    const bool full = k0 + 4 <= n;
     float x[4], v[4];
-    ga_load4(xr, xvec, k0, n, x);
+    ld4(xr, k0, n, xvec && full, x);
     if (k0 >= nv) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = x[e];
     } else {
       const int nvq = min(nv - k0, 4);
       float a[4];
-      ga_load4(ar, avec, k0, n, a);
+      ld4(ar, k0, n, avec && full, a);
       if (copy) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = e < nvq ? a[e] : x[e];
@@ -109,17 +98,11 @@ __global__ __launch_bounds__(kGaThreads) void genetic_breed_kernel(const float* 
         genetic_quad(seed, (uint64_t)q, clip, key, thresh, step, eps, lo, hi, nvq, a, a, x, v);
       } else {
         float c[4];
-        ga_load4(cr, cvec, k0, n, c);
+        ld4(cr, k0, n, cvec && full, c);
         genetic_quad(seed, (uint64_t)q, clip, key, thresh, step, eps, lo, hi, nvq, a, c, x, v);
       }
     }
-    if (ovec && k0 + 4 <= n) {
-      *reinterpret_cast<float4*>(orow + k0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (k0 + e < n) orow[k0 + e] = v[e];
-    }
+    st4(orow, k0, n, ovec && full, v);
   }
 }
 
@@ -214,10 +197,9 @@ static int genetic_breed_pointers(const char* fn, const float* x0, const float* 
   LP_CHECK_ARG(x0 != nullptr && pop_out != nullptr, "%s: x0 or pop_out is null", fn);
   LP_CHECK_ARG((pop_in == nullptr) == (parents == nullptr), "%s: pop_in and parents go together (both or neither)", fn);
   LP_CHECK_ARG((long long)B * P <= 0x7fffffffLL, "%s: %d x %d rows in one call", fn, B, P);
-  const uintptr_t o0 = reinterpret_cast<uintptr_t>(pop_out), bytes = (uintptr_t)B * P * n * sizeof(float);
-  const uintptr_t i0 = reinterpret_cast<uintptr_t>(pop_in), x00 = reinterpret_cast<uintptr_t>(x0);
-  LP_CHECK_ARG(pop_in == nullptr || o0 + bytes <= i0 || i0 + bytes <= o0, "%s: pop_out overlaps pop_in", fn);
-  LP_CHECK_ARG(o0 + bytes <= x00 || x00 + (uintptr_t)B * n * sizeof(float) <= o0, "%s: pop_out overlaps x0", fn);
+  const size_t bytes = (size_t)B * P * n * sizeof(float);
+  LP_CHECK_ARG(pop_in == nullptr || !spans_overlap(pop_out, bytes, pop_in, bytes), "%s: pop_out overlaps pop_in", fn);
+  LP_CHECK_ARG(!spans_overlap(pop_out, bytes, x0, (size_t)B * n * sizeof(float)), "%s: pop_out overlaps x0", fn);
   return LIPASR_OK;
 }
 
@@ -250,7 +232,7 @@ int lipasr_genetic_breed_host(const float* x0, const int* n_valid, const float* 
   if (int rc = genetic_breed_pointers(fn, x0, pop_in, parents, batch, pop, n, pop_out)) return rc;
   for (int b = 0; b < batch; ++b) {
     const float* xr = x0 + (size_t)b * n;
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     for (int p = 0; p < pop; ++p) {
       const size_t row = (size_t)b * pop + p;
       float* orow = pop_out + row * (size_t)n;

@@ -15,10 +15,11 @@
 // hsj_direction_kernel: ONE workgroup per row: g from the two sums and the two counts, u = sign(g) or g / ||g||_2 (fp64).
 // hsj_search_kernel: ONE workgroup per row, one launch per query: the row's scalars (8 floats, 8 ints) are read by every thread,
 //   hsj_decide() -- shared with the host twin -- says what moves, and the threads move it quad by quad.
-//   float4 where n is a multiple of 4 and every base sits on 16 bytes, scalars otherwise: the same element-to-thread map.
+//   The quads move as row.h says; `vec` is its `whole`: n a multiple of 4 and every base of the call on 16 bytes.
 //   No atomics, nothing waits on another workgroup, two runs give the same bits.  Every a * b + c that a comparison of bits depends
 //   on is an explicit fmaf / fma, and contraction is off for the whole file, so host and device round alike.
 #include "common.h"
+#include "row.h"
 
 #pragma clang fp contract(off)
 
@@ -32,7 +33,6 @@ constexpr int kHsjMaxDraws = 16384;  // phi in LDS, one byte per draw
 constexpr uint32_t kHsjTagStart = 1u << 28, kHsjTagL2 = 2u << 28, kHsjTagLinf = 3u << 28;
 
 __host__ __device__ __forceinline__ bool hsj_finite(float v) { return fabsf(v) < INFINITY; }
-__host__ __device__ __forceinline__ float hsj_clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // argmax != y (targeted: == y), the lowest index on a tie; a NaN anywhere or a label outside [0, classes): not adversarial
 __host__ __device__ __forceinline__ bool hsj_adv(const float* __restrict__ z, int classes, int y, int targeted) {
@@ -71,7 +71,7 @@ __host__ __device__ __forceinline__ float hsj_scale(int l2, double ss, uint64_t 
   if (!(nrm > 0.0) || !(nrm < (double)INFINITY) || !hsj_finite(delta)) return 0.0f;
   return (float)((double)delta / nrm);
 }
-__host__ __device__ __forceinline__ float hsj_point(float s, float r, float x, float lo, float hi) { return hsj_clampf(fmaf(s, r, x), lo, hi); }
+__host__ __device__ __forceinline__ float hsj_point(float s, float r, float x, float lo, float hi) { return clampf(fmaf(s, r, x), lo, hi); }
 
 // the start draws: uniform in [sl, sh]
 __host__ __device__ __forceinline__ void hsj_start4(uint64_t seed, uint32_t clip, uint32_t draw, int q, float (&u)[4]) {
@@ -80,7 +80,7 @@ __host__ __device__ __forceinline__ void hsj_start4(uint64_t seed, uint32_t clip
 #pragma unroll
   for (int e = 0; e < 4; ++e) u[e] = Philox::u01(o[e]);
 }
-__host__ __device__ __forceinline__ float hsj_start_value(float u, float sl, float sh) { return hsj_clampf(fmaf(u, sh - sl, sl), sl, sh); }
+__host__ __device__ __forceinline__ float hsj_start_value(float u, float sl, float sh) { return clampf(fmaf(u, sh - sl, sl), sl, sh); }
 
 // the two projections of the bisection: the blend (L2) and the box (L-inf) between x0 and the far point
 __host__ __device__ __forceinline__ float hsj_proj(int l2, float a, float x0, float xf, float lo, float hi) {
@@ -91,7 +91,7 @@ __host__ __device__ __forceinline__ float hsj_proj(int l2, float a, float x0, fl
     const float l = x0 - a, h = x0 + a;
     v = xf < l ? l : (xf > h ? h : xf);
   }
-  return hsj_clampf(v, lo, hi);
+  return clampf(v, lo, hi);
 }
 
 // g_k from the two sums: sum_j (phi_j - m)(p_j - x) = s1 - m s0
@@ -194,40 +194,8 @@ __host__ __device__ __forceinline__ HsjOps hsj_decide(HsjRow& r, int mode, int f
   return o;
 }
 
-// ---- device helpers
-__device__ __forceinline__ void hsj_ld4(const float* __restrict__ p, int k0, int n, bool vec, float (&v)[4]) {
-  if (vec) {
-    const float4 t = *reinterpret_cast<const float4*>(p + k0);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (k0 + e < n) ? p[k0 + e] : 0.0f;
-  }
-}
-__device__ __forceinline__ void hsj_st4(float* __restrict__ p, int k0, int n, bool vec, const float (&v)[4]) {
-  if (vec) {
-    *reinterpret_cast<float4*>(p + k0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (k0 + e < n) p[k0 + e] = v[e];
-  }
-}
-
-// sums / maxima over the threads of a row, the same bits in every thread: butterfly per wavefront, one value per wavefront in LDS, added
-// (or compared) by every thread in index order.  Two barriers: the LDS slots may be used again at once.
-template <int T = kHsjThreads>
-__device__ __forceinline__ double hsj_block_sum_d(double v, double* red) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = 0.0;
-#pragma unroll
-  for (int w = 0; w < T / 64; ++w) v += red[w];
-  __syncthreads();
-  return v;
-}
-template <int T = kHsjThreads>
+// ---- device helpers: block_sum_d (row.h) for 64-bit integers and for a maximum
+template <int T>
 __device__ __forceinline__ uint64_t hsj_block_sum_u(uint64_t v, uint64_t* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -269,7 +237,7 @@ __global__ __launch_bounds__(T) void hsj_expand_kernel(HsjExpandArgs a) {
   const int tid = threadIdx.x, n = a.n;
   const int b = (int)(blockIdx.x / (unsigned)a.draws), j = (int)(blockIdx.x % (unsigned)a.draws);
   const uint32_t clip = a.clip0 + (uint32_t)b, draw = a.draw0 + (uint32_t)j;
-  const int nv = a.n_valid ? min(max(a.n_valid[b], 0), n) : n;
+  const int nv = row_valid(a.n_valid, b, n);
   const int quads = (n + 3) >> 2;
   const bool vec = a.vec != 0;
   const float* __restrict__ xr = a.x + (size_t)b * n;
@@ -300,7 +268,7 @@ __global__ __launch_bounds__(T) void hsj_expand_kernel(HsjExpandArgs a) {
       if constexpr (NQ > 0) D[s][e] = r[e];
     }
   }
-  if (a.l2) ss = hsj_block_sum_d<T>(ss, red_d); else si = hsj_block_sum_u<T>(si, red_u);
+  if (a.l2) ss = block_sum_d<T>(ss, red_d); else si = hsj_block_sum_u<T>(si, red_u);
   const float sc = hsj_scale(a.l2, ss, si, a.delta[b]);
 #pragma unroll(R)
   for (int s = 0; s < nj; ++s) {
@@ -313,10 +281,10 @@ __global__ __launch_bounds__(T) void hsj_expand_kernel(HsjExpandArgs a) {
     } else {
       gen(q, r);
     }
-    hsj_ld4(xr, 4 * q, n, vec, xv);
+    ld4(xr, 4 * q, n, vec, xv);
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (4 * q + e < nv) ? hsj_point(sc, r[e], xv[e], a.lo, a.hi) : xv[e];
-    hsj_st4(outr, 4 * q, n, vec, o);
+    st4(outr, 4 * q, n, vec, o);
   }
 }
 
@@ -361,11 +329,11 @@ __global__ __launch_bounds__(kHsjAccThreads) void hsj_accumulate_kernel(const fl
   const int q = blockIdx.x * kHsjAccThreads + tid;
   if (q >= quads) return;
   const int k0 = 4 * q;
-  const int nv = n_valid ? min(max(n_valid[b], 0), n) : n;
+  const int nv = row_valid(n_valid, b, n);
   double* __restrict__ s0 = sums + ((size_t)b * 2) * n;
   double* __restrict__ s1 = s0 + n;
   float xv[4];
-  hsj_ld4(x + (size_t)b * n, k0, n, vec, xv);
+  ld4(x + (size_t)b * n, k0, n, vec, xv);
   double a0[4], a1[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -376,7 +344,7 @@ __global__ __launch_bounds__(kHsjAccThreads) void hsj_accumulate_kernel(const fl
 #pragma unroll 4
   for (int j = 0; j < draws; ++j) {
     float pv[4];
-    hsj_ld4(pr + (size_t)j * n, k0, n, vec, pv);
+    ld4(pr + (size_t)j * n, k0, n, vec, pv);
     const bool plus = phi[j] != 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -397,7 +365,7 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_direction_kernel(const double
   __shared__ double red[kHsjThreads / 64];
   const int tid = threadIdx.x, b = blockIdx.x;
   const bool vec = vec_ != 0;
-  const int nv = n_valid ? min(max(n_valid[b], 0), n) : n;
+  const int nv = row_valid(n_valid, b, n);
   const int total = counts[(size_t)b * 2], pos = counts[(size_t)b * 2 + 1];
   const double* __restrict__ s0 = sums + ((size_t)b * 2) * n;
   const double* __restrict__ s1 = s0 + n;
@@ -411,7 +379,7 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_direction_kernel(const double
         const int k = 4 * q + e;
         if (k < nv) { const double g = hsj_g(s0[k], s1[k], total, pos); ss += g * g; }
       }
-    nrm = sqrt(hsj_block_sum_d(ss, red));
+    nrm = sqrt(block_sum_d<kHsjThreads>(ss, red));
   }
   for (int q = tid; q < quads; q += kHsjThreads) {
     float o[4];
@@ -421,7 +389,7 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_direction_kernel(const double
       o[e] = 0.0f;
       if (k < nv) { const double g = hsj_g(s0[k], s1[k], total, pos); o[e] = l2 ? hsj_unit(g, nrm) : hsj_sign(g); }
     }
-    hsj_st4(u + (size_t)b * n, 4 * q, n, vec, o);
+    st4(u + (size_t)b * n, 4 * q, n, vec, o);
   }
 }
 
@@ -443,7 +411,7 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
   const bool vec = a.vec != 0;
   const int l2 = a.l2;
   const size_t base = (size_t)b * n;
-  const int nv = a.n_valid ? min(max(a.n_valid[b], 0), n) : n;
+  const int nv = row_valid(a.n_valid, b, n);
   const int quads = (n + 3) >> 2;
   HsjRow r;
   hsj_load_row(a.fstate + (size_t)b * 8, a.istate + (size_t)b * 8, r);
@@ -455,8 +423,8 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
     float m = 0.0f;
     for (int q = tid; q < quads; q += kHsjThreads) {
       float c[4], f[4];
-      hsj_ld4(x0, 4 * q, n, vec, c);
-      hsj_ld4(a.x_far + base, 4 * q, n, vec, f);
+      ld4(x0, 4 * q, n, vec, c);
+      ld4(a.x_far + base, 4 * q, n, vec, f);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (4 * q + e < nv) m = fmaxf(m, fabsf(f[e] - c[e]));
@@ -472,15 +440,15 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
     for (int q = tid; q < quads; q += kHsjThreads) {
       const int k0 = 4 * q;
       float c[4];
-      hsj_ld4(x0, k0, n, vec, c);
+      ld4(x0, k0, n, vec, c);
       if (op.init_rows) {
-        hsj_st4(a.x_adv + base, k0, n, vec, c);
-        hsj_st4(a.x_best + base, k0, n, vec, c);
+        st4(a.x_adv + base, k0, n, vec, c);
+        st4(a.x_best + base, k0, n, vec, c);
       }
       if (op.far_from_cand) {
         float t[4];
-        hsj_ld4(a.x_cand + base, k0, n, vec, t);
-        hsj_st4(a.x_far + base, k0, n, vec, t);
+        ld4(a.x_cand + base, k0, n, vec, t);
+        st4(a.x_far + base, k0, n, vec, t);
       }
       float o[4];
       if (op.cand == 1) {
@@ -490,20 +458,20 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
         for (int e = 0; e < 4; ++e) o[e] = (k0 + e < nv) ? hsj_start_value(uu[e], sl, sh) : c[e];
       } else if (op.cand == 2) {
         float xa[4], uu[4];
-        hsj_ld4(a.x_adv + base, k0, n, vec, xa);
-        hsj_ld4(a.u + base, k0, n, vec, uu);
+        ld4(a.x_adv + base, k0, n, vec, xa);
+        ld4(a.u + base, k0, n, vec, uu);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (k0 + e < nv) ? hsj_point(r.eps, uu[e], xa[e], a.lo, a.hi) : c[e];
       } else if (op.cand == 3) {
         float f[4];
-        hsj_ld4(a.x_far + base, k0, n, vec, f);
+        ld4(a.x_far + base, k0, n, vec, f);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (k0 + e < nv) ? hsj_proj(l2, r.mid, c[e], f[e], a.lo, a.hi) : c[e];
       } else if (op.cand == 4) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = c[e];
       }
-      if (op.cand != 0) hsj_st4(a.x_cand + base, k0, n, vec, o);
+      if (op.cand != 0) st4(a.x_cand + base, k0, n, vec, o);
     }
   }
   if (op.finish) {  // uniform over the row
@@ -511,16 +479,16 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
     float mx = 0.0f;
     auto value = [&](int k0, const float (&c)[4], float (&o)[4]) {
       float f[4];
-      hsj_ld4(a.x_far + base, k0, n, vec, f);
+      ld4(a.x_far + base, k0, n, vec, f);
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (k0 + e < nv) ? (r.moved ? hsj_proj(l2, r.hi, c[e], f[e], a.lo, a.hi) : f[e]) : c[e];
     };
     for (int q = tid; q < quads; q += kHsjThreads) {
       const int k0 = 4 * q;
       float c[4], o[4];
-      hsj_ld4(x0, k0, n, vec, c);
+      ld4(x0, k0, n, vec, c);
       value(k0, c, o);
-      hsj_st4(a.x_adv + base, k0, n, vec, o);
+      st4(a.x_adv + base, k0, n, vec, o);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (k0 + e < nv) {
@@ -528,15 +496,15 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
           else mx = fmaxf(mx, fabsf(o[e] - c[e]));
         }
     }
-    r.dist = l2 ? (float)sqrt(hsj_block_sum_d(ss, red_d)) : hsj_block_max(mx, red_f);
+    r.dist = l2 ? (float)sqrt(block_sum_d<kHsjThreads>(ss, red_d)) : hsj_block_max(mx, red_f);
     if (r.dist < r.dist_best) {
       r.dist_best = r.dist;
       for (int q = tid; q < quads; q += kHsjThreads) {
         const int k0 = 4 * q;
         float c[4], o[4];
-        hsj_ld4(x0, k0, n, vec, c);
+        ld4(x0, k0, n, vec, c);
         value(k0, c, o);
-        hsj_st4(a.x_best + base, k0, n, vec, o);
+        st4(a.x_best + base, k0, n, vec, o);
       }
     }
   }
@@ -544,11 +512,6 @@ __global__ __launch_bounds__(kHsjThreads) void hsj_search_kernel(HsjSearchArgs a
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ checks
-static bool hsj_overlap(const void* a, size_t ab, const void* b, size_t bb) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return ab != 0 && bb != 0 && !(p + ab <= q || q + bb <= p);
-}
-
 static int hsj_norm(const char* fn, float norm, int* l2) {
   LP_CHECK_ARG(norm == 2.0f || (std::isinf(norm) && norm > 0.0f), "%s: norm=%g; 2 and inf are supported", fn, (double)norm);
   *l2 = norm == 2.0f ? 1 : 0;
@@ -565,7 +528,7 @@ static int hsj_expand_check(const char* fn, const float* x, const float* delta, 
   LP_CHECK_ARG(lo <= hi, "%s: clip range [%g, %g]", fn, (double)lo, (double)hi);
   if (batch == 0 || n == 0 || draws == 0) return LIPASR_OK;
   LP_CHECK_ARG(x != nullptr && delta != nullptr && out != nullptr, "%s: a null pointer", fn);
-  LP_CHECK_ARG(!hsj_overlap(x, (size_t)batch * n * 4, out, (size_t)batch * draws * n * 4), "%s: out overlaps x", fn);
+  LP_CHECK_ARG(!spans_overlap(x, (size_t)batch * n * 4, out, (size_t)batch * draws * n * 4), "%s: out overlaps x", fn);
   return LIPASR_OK;
 }
 
@@ -579,7 +542,7 @@ static int hsj_acc_check(const char* fn, const float* logits, const int* labels,
   if (batch == 0 || n == 0 || draws == 0) return LIPASR_OK;
   LP_CHECK_ARG(logits && labels && p && x && sums && counts, "%s: a null pointer", fn);
   const size_t sb = (size_t)batch * 2 * n * sizeof(double);
-  LP_CHECK_ARG(!hsj_overlap(sums, sb, p, (size_t)batch * draws * n * 4) && !hsj_overlap(sums, sb, x, (size_t)batch * n * 4),
+  LP_CHECK_ARG(!spans_overlap(sums, sb, p, (size_t)batch * draws * n * 4) && !spans_overlap(sums, sb, x, (size_t)batch * n * 4),
                "%s: sums overlaps an input", fn);
   return LIPASR_OK;
 }
@@ -589,7 +552,7 @@ static int hsj_dir_check(const char* fn, const double* sums, const int* counts, 
   LP_CHECK_ARG(batch >= 0 && n >= 0, "%s: bad shape %d x %d", fn, batch, n);
   if (batch == 0 || n == 0) return LIPASR_OK;
   LP_CHECK_ARG(sums && counts && u, "%s: a null pointer", fn);
-  LP_CHECK_ARG(!hsj_overlap(sums, (size_t)batch * 2 * n * 8, u, (size_t)batch * n * 4), "%s: u overlaps sums", fn);
+  LP_CHECK_ARG(!spans_overlap(sums, (size_t)batch * 2 * n * 8, u, (size_t)batch * n * 4), "%s: u overlaps sums", fn);
   return LIPASR_OK;
 }
 
@@ -612,7 +575,7 @@ static int hsj_search_check(const char* fn, const HsjSearchArgs& a, float norm, 
   const char* names[6] = {"x0", "x_cand", "x_far", "x_adv", "x_best", "u"};
   for (int i = 0; i < 6; ++i)
     for (int j = i + 1; j < 6; ++j)
-      LP_CHECK_ARG(rows[i] == nullptr || rows[j] == nullptr || !hsj_overlap(rows[i], rb, rows[j], rb), "%s: %s overlaps %s", fn, names[i],
+      LP_CHECK_ARG(rows[i] == nullptr || rows[j] == nullptr || !spans_overlap(rows[i], rb, rows[j], rb), "%s: %s overlaps %s", fn, names[i],
                    names[j]);
   return LIPASR_OK;
 }
@@ -665,7 +628,7 @@ int lipasr_hsj_expand_host(const float* x, const float* delta, const int* n_vali
   const int quads = (n + 3) >> 2;
   std::vector<float> r((size_t)quads * 4);
   for (int b = 0; b < batch; ++b) {
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     for (int j = 0; j < draws; ++j) {
       double ss = 0.0;
       uint64_t si = 0;
@@ -708,7 +671,7 @@ int lipasr_hsj_accumulate_host(const float* logits, const int* labels, const flo
   if (int rc = hsj_acc_check(fn, logits, labels, p, x, batch, classes, n, draws, sums, counts)) return rc;
   if (batch == 0 || n == 0 || draws == 0) return LIPASR_OK;
   for (int b = 0; b < batch; ++b) {
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     double* s0 = sums + ((size_t)b * 2) * n;
     double* s1 = s0 + n;
     int pos = 0;
@@ -747,7 +710,7 @@ int lipasr_hsj_direction_host(const double* sums, const int* counts, const int* 
   if (int rc = hsj_dir_check(fn, sums, counts, batch, n, norm, u, &l2)) return rc;
   if (batch == 0 || n == 0) return LIPASR_OK;
   for (int b = 0; b < batch; ++b) {
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     const int total = counts[(size_t)b * 2], pos = counts[(size_t)b * 2 + 1];
     const double* s0 = sums + ((size_t)b * 2) * n;
     const double* s1 = s0 + n;
@@ -813,7 +776,7 @@ int lipasr_hsj_search_host(const float* logits, const int* labels, const float* 
   const bool first = (flags & LIPASR_HSJ_FIRST) != 0;
   for (int b = 0; b < batch; ++b) {
     const size_t base = (size_t)b * n;
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     HsjRow r;
     hsj_load_row(fstate + (size_t)b * 8, istate + (size_t)b * 8, r);
     const bool adv = first ? false : hsj_adv(logits + (size_t)b * classes, classes, labels[b], targeted ? 1 : 0);

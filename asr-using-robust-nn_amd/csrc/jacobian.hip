@@ -24,6 +24,7 @@
 // take 107 us -- far from the read's cost: with one workgroup per sample the time is the latency of three dependent passes and of
 // the barriers of the Jacobi sweeps.  VEC = 4 needs n, both strides and the bases multiples of 16 bytes; anything else takes VEC = 1.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -42,16 +43,6 @@ struct JacSigmaArgs {
   float* v;      // [batch][n] or null
 };
 
-template <int VEC>
-__device__ __forceinline__ void jac_ld(const float* __restrict__ p, int i, float (&x)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = reinterpret_cast<const float4*>(p)[i];
-    x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-  } else {
-    x[0] = p[i];
-  }
-}
-
 // rows [a0, a0 + RB) against rows [b0, b0 + RB) (DIAG: the same rows, upper triangle) of J 2^ex; rows >= C count as zero and are
 // not read.  Wave w leaves its sums in part[w][a][b].
 template <int RB, bool DIAG, int VEC>
@@ -67,7 +58,7 @@ __device__ __forceinline__ void gram_block(const float* __restrict__ J, long str
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
       if (a0 + r < C) {  // uniform
-        jac_ld<VEC>(J + (size_t)(a0 + r) * stride_c, i, xa[r]);
+        ldv<VEC>(J + (size_t)(a0 + r) * stride_c, i, xa[r]);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) xa[r][e] = ldexpf(xa[r][e], ex);
       } else {
@@ -79,7 +70,7 @@ __device__ __forceinline__ void gram_block(const float* __restrict__ J, long str
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
         if (b0 + r < C) {
-          jac_ld<VEC>(J + (size_t)(b0 + r) * stride_c, i, xb[r]);
+          ldv<VEC>(J + (size_t)(b0 + r) * stride_c, i, xb[r]);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) xb[r][e] = ldexpf(xb[r][e], ex);
         } else {
@@ -134,7 +125,7 @@ __global__ __launch_bounds__(kJacThreads) void jacobian_sigma_kernel(JacSigmaArg
     const float* row = J + (size_t)c * a.stride_c;
     for (int i = tid; i < nv; i += kJacThreads) {
       float x[VEC];
-      jac_ld<VEC>(row, i, x);
+      ldv<VEC>(row, i, x);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const float m = fabsf(x[e]);
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(kJacThreads) void jacobian_sigma_kernel(JacSigmaArg
     for (int e = 0; e < VEC; ++e) s[e] = 0.0f;
     for (int c = 0; c < C; ++c) {
       float x[VEC];
-      jac_ld<VEC>(J + (size_t)c * a.stride_c, i, x);
+      ldv<VEC>(J + (size_t)c * a.stride_c, i, x);
       const float uc = uf[c];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) s[e] = fmaf(uc, ldexpf(x[e], ex), s[e]);

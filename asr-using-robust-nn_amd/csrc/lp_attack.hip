@@ -15,6 +15,7 @@
 // golden ratio, counter = (element group, row, *counter_dev).  Counter-based, so the two passes the L1 / L2 draws need (the
 // row's norm, then the scaled write) regenerate the same numbers instead of holding them.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -24,25 +25,6 @@ constexpr double kLpTol = 1e-7;  // ART's tol = 10e-8 (fast_gradient.py, project
 
 // norm codes: 0 = inf, 1 = L1, 2 = L2
 __device__ __forceinline__ float sign_nan0(float v) { return (v > 0.0f) ? 1.0f : ((v < 0.0f) ? -1.0f : 0.0f); }
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* __restrict__ p, size_t i, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = reinterpret_cast<const float4*>(p)[i];
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[i];
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void stv(float* __restrict__ p, size_t i, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    reinterpret_cast<float4*>(p)[i] = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    p[i] = v[0];
-  }
-}
 
 // ART's direction: sign(g) (norm inf) or g / (||g||_p + tol); a row whose ||g||_p is not finite (an inf entry) takes no step
 __device__ __forceinline__ float dir_scale(double s, int norm) {

@@ -16,6 +16,7 @@
 // fixed order: by room, then by position upwards.  Loads and stores are single floats (coalesced along time): any alignment.
 // Nothing here allocates, synchronises or waits on another workgroup.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(64 * kRoomWaves) void room_kernel(const float* __re
   if (tid < 32) {
     const int c = c0 + tid;
     int v = 0;
-    if (c < clips) v = n_valid ? min(max(n_valid[c], 0), n) : n;
+    if (c < clips) v = row_valid(n_valid, c, n);
     nvs[tid] = v;
   }
   __syncthreads();
@@ -131,11 +132,6 @@ __global__ __launch_bounds__(64 * kRoomWaves) void room_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ checks
-static bool room_overlap(const void* a, size_t ab, const void* b, size_t bb) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return ab != 0 && bb != 0 && !(p + ab <= q || q + bb <= p);
-}
-
 // sig: the [clips][n] side (x or gx); rows: the [clips * R][n] side (out or g); dst: the one of the two that is written
 static int room_check(const char* fn, const float* sig, const float* rows, const float* rirs, int taps, int R, int clips, int n,
                       const float* dst, float scale) {
@@ -149,7 +145,7 @@ static int room_check(const char* fn, const float* sig, const float* rows, const
   const size_t sb = (size_t)clips * n * 4, rb = (size_t)clips * R * n * 4, hb = (size_t)R * taps * 4;
   const void* other = dst == sig ? (const void*)rows : (const void*)sig;
   const size_t db = dst == sig ? sb : rb, ob = dst == sig ? rb : sb;
-  LP_CHECK_ARG(!room_overlap(dst, db, other, ob) && !room_overlap(dst, db, rirs, hb), "%s: the output overlaps an input", fn);
+  LP_CHECK_ARG(!spans_overlap(dst, db, other, ob) && !spans_overlap(dst, db, rirs, hb), "%s: the output overlaps an input", fn);
   return LIPASR_OK;
 }
 
@@ -197,7 +193,7 @@ int lipasr_room_apply_host(const float* x, const int* n_valid, const float* rirs
   const char* fn = "lipasr_room_apply_host";
   if (int rc = room_check(fn, x, out, rirs, taps, rir_count, clips, n, out, 1.0f)) return rc;
   for (int b = 0; b < clips; ++b) {
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     const float* xr = x + (size_t)b * n;
     for (int j = 0; j < rir_count; ++j) {
       const float* hj = rirs + (size_t)j * taps;
@@ -216,7 +212,7 @@ int lipasr_room_vjp_host(const float* g, const int* n_valid, const float* rirs, 
   const char* fn = "lipasr_room_vjp_host";
   if (int rc = room_check(fn, gx, g, rirs, taps, rir_count, clips, n, gx, scale)) return rc;
   for (int b = 0; b < clips; ++b) {
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), n) : n;
+    const int nv = row_valid(n_valid, b, n);
     float* o = gx + (size_t)b * n;
     // o[s] takes its taps in (j, k) order; the loop over s is the inner one only so that it vectorises
     for (int s = 0; s < n; ++s) o[s] = 0.0f;

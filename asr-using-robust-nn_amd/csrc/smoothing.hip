@@ -6,9 +6,8 @@
 //   normal4, out = clamp(fmaf(sigma, z, x)) on the elements below the clip's valid length, the bits of x on the others.  A quad
 //   that lies wholly in the padding is copied without a draw.  The counter holds the clip and the draw, never the row's position
 //   in the call, so a chunk of any size at any start draws what one big call would.
-//   Loads and stores are float4 where the row of x (of out) starts on 16 bytes, four scalars per lane otherwise; the last, partial
-//   quad of a row is scalar.  x and out are told apart: an aligned x with an odd out still loads float4.  The quads stay keyed by
-//   the element index, not by the address, so the alignment never changes a value.
+//   The quads move as row.h says, `whole` judged per array: x and out are told apart, so an aligned x with an odd out still
+//   loads float4.
 //   The kernel is bound by vector-instruction issue, not by HBM: ten Philox rounds (20 v_mul_hi/lo pairs) plus two logf, two
 //   sqrtf and two sincosf per 32 bytes moved.  Nothing here chases the memory roofline.
 //
@@ -18,6 +17,7 @@
 //   order, and thread c adds the sum to counts[b][c], which no other workgroup touches: no global atomics, the same bits on
 //   every run, and calls accumulate.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -33,8 +33,7 @@ __global__ __launch_bounds__(kSmThreads) void smooth_expand_kernel(const float* 
   const int tid = threadIdx.x;
   const float* __restrict__ xr = x + (size_t)b * n;
   float* __restrict__ orow = out + row * (size_t)n;
-  int nv = n;
-  if (n_valid) nv = min(max(n_valid[b], 0), n);
+  const int nv = row_valid(n_valid, b, n);
   const bool xvec = (reinterpret_cast<uintptr_t>(xr) & 15) == 0, ovec = (reinterpret_cast<uintptr_t>(orow) & 15) == 0;  // uniform
   const uint32_t clip = clip0 + (uint32_t)b, draw = draw0 + (uint32_t)j;
   const int quads = (n + 3) >> 2;
@@ -42,31 +41,16 @@ __global__ __launch_bounds__(kSmThreads) void smooth_expand_kernel(const float* 
     const int k0 = q * 4;
     const bool full = k0 + 4 <= n;
     float v[4];
-    if (full && xvec) {
-      const float4 t = *reinterpret_cast<const float4*>(xr + k0);
-      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (k0 + e < n) ? xr[k0 + e] : 0.0f;
-    }
+    ld4(xr, k0, n, full && xvec, v);
     if (k0 < nv) {
       float z[4];
       normal4(seed, (uint64_t)q, clip, draw, z);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (k0 + e < nv) {
-          const float t = fmaf(sigma, z[e], v[e]);
-          v[e] = t < lo ? lo : (t > hi ? hi : t);
-        }
+        if (k0 + e < nv) v[e] = clampf(fmaf(sigma, z[e], v[e]), lo, hi);
       }
     }
-    if (full && ovec) {
-      *reinterpret_cast<float4*>(orow + k0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (k0 + e < n) orow[k0 + e] = v[e];
-    }
+    st4(orow, k0, n, full && ovec, v);
   }
 }
 

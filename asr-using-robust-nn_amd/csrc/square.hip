@@ -18,6 +18,7 @@
 //   Everything is integer arithmetic, one fp32 add, two clamps and one fp32 subtract, in functions the host twins share: the same
 //   bits on both sides.  The row's other n - h w elements are never touched, whatever the alignment.
 #include "common.h"
+#include "row.h"
 
 namespace lipasr {
 
@@ -26,8 +27,7 @@ constexpr int kSqMaxC = 32;
 
 // min(max(fl(x + s eps), lo), hi); se = +-eps.  A NaN compares false twice and stays.
 __host__ __device__ __forceinline__ float square_value(float x, float se, float lo, float hi) {
-  const float t = x + se;
-  return t < lo ? lo : (t > hi ? hi : t);
+  return clampf(x + se, lo, hi);
 }
 
 // the sign bit of column c at the stripe start: 1 = minus
@@ -106,8 +106,7 @@ __global__ __launch_bounds__(kSqThreads) void square_init_kernel(const float* __
                                                                   int* __restrict__ win) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const size_t base = (size_t)b * height * width;
-  int nv = width;  // n_valid comes with height == 1 only
-  if (n_valid) nv = min(max(n_valid[b], 0), width);
+  const int nv = row_valid(n_valid, b, width);  // n_valid comes with height == 1 only
   if (tid < 4) win[(size_t)b * 4 + tid] = 0;
   for (int c = tid; c < width; c += kSqThreads) {
     uint32_t o[4];
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(kSqThreads) void square_step_kernel(const float* __
   const size_t base = (size_t)b * height * width;
   int* __restrict__ wb = win + (size_t)b * 4;
   const int pr = wb[0], pc = wb[1], ph = wb[2], pw = wb[3];
-  const int nvr = n_valid ? min(max(n_valid[b], 0), width) : -1;
+  const int nvr = n_valid ? row_valid(n_valid, b, width) : -1;
   const float loss = square_margin(logits + (size_t)b * classes, classes, labels[b], targeted);
   const SquareRow d = square_decide(loss, loss_best[b], done[b], it, nvr, flags);  // uniform
   __syncthreads();  // every wave has read the row's state
@@ -169,11 +168,6 @@ __global__ __launch_bounds__(kSqThreads) void square_step_kernel(const float* __
   if (tid < 4) wb[tid] = nw[tid];
 }
 
-static bool square_overlap(const void* a, const void* b, size_t bytes) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return !(p + bytes <= q || q + bytes <= p);
-}
-
 // the checks the device entry points and their host twins share
 static int square_check(const char* fn, const int* n_valid, int B, int height, int width, uint32_t restart, float eps, float lo,
                         float hi) {
@@ -201,9 +195,9 @@ static int square_step_check(const char* fn, const int* n_valid, int B, int clas
 static int square_pointers(const char* fn, const float* x0, const float* x_best, const float* x_cand, const int* win, int B, int n) {
   LP_CHECK_ARG(x0 != nullptr && x_best != nullptr && x_cand != nullptr && win != nullptr, "%s: a null pointer", fn);
   const size_t bytes = (size_t)B * n * sizeof(float);
-  LP_CHECK_ARG(!square_overlap(x_best, x_cand, bytes), "%s: x_best overlaps x_cand", fn);
-  LP_CHECK_ARG(!square_overlap(x_best, x0, bytes), "%s: x_best overlaps x0", fn);
-  LP_CHECK_ARG(!square_overlap(x_cand, x0, bytes), "%s: x_cand overlaps x0", fn);
+  LP_CHECK_ARG(!spans_overlap(x_best, bytes, x_cand, bytes), "%s: x_best overlaps x_cand", fn);
+  LP_CHECK_ARG(!spans_overlap(x_best, bytes, x0, bytes), "%s: x_best overlaps x0", fn);
+  LP_CHECK_ARG(!spans_overlap(x_cand, bytes, x0, bytes), "%s: x_cand overlaps x0", fn);
   return LIPASR_OK;
 }
 
@@ -235,7 +229,7 @@ int lipasr_square_init_host(const float* x0, const int* n_valid, int batch, int 
   if (int rc = square_pointers(fn, x0, x_best, x_cand, win, batch, height * width)) return rc;
   for (int b = 0; b < batch; ++b) {
     const size_t base = (size_t)b * height * width;
-    const int nv = n_valid ? std::min(std::max(n_valid[b], 0), width) : width;
+    const int nv = row_valid(n_valid, b, width);
     for (int e = 0; e < 4; ++e) win[(size_t)b * 4 + e] = 0;
     for (int c = 0; c < width; ++c) {
       uint32_t o[4];
@@ -283,7 +277,7 @@ int lipasr_square_step_host(const float* logits, const int* labels, const float*
   for (int b = 0; b < batch; ++b) {
     const size_t base = (size_t)b * height * width;
     int* wb = win + (size_t)b * 4;
-    const int nvr = n_valid ? std::min(std::max(n_valid[b], 0), width) : -1;
+    const int nvr = n_valid ? row_valid(n_valid, b, width) : -1;
     const float loss = square_margin(logits + (size_t)b * classes, classes, labels[b], targeted ? 1 : 0);
     const SquareRow d = square_decide(loss, loss_best[b], done[b], it, nvr, flags);
     loss_best[b] = d.loss_best;

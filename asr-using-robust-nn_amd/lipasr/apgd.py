@@ -14,7 +14,7 @@ import math
 import torch
 
 from . import _native as N
-from .genetic import _dev_tensor
+from ._rows import _dev_tensor, clip_pair, rows2d
 
 LOSS_TYPES = {"cross_entropy": 0, "difference_logits_ratio": 1}
 FIRST, LAST = 1, 2
@@ -55,9 +55,7 @@ def apgd_state(rows, device):
 def apgd_loss(logits, labels, loss_type="cross_entropy", targeted=False, *, f=None, dz=None, hit=None):
     """lipasr_apgd_loss on device tensors: logits float32 [B, C], labels int32 [B] -> (f float32 [B], dz float32 [B, C], hit int32
     [B]); ``f``, ``dz``, ``hit``: tensors to write into."""
-    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()):
-        raise ValueError("logits must be a contiguous float32 device tensor [B, classes]")
-    b, c = logits.shape
+    b, c = rows2d(logits, "logits", "[B, classes]")
     code = _loss_code(loss_type)
     _dev_tensor(labels, torch.int32, (b,), "labels")
     f = torch.empty(b, device=logits.device) if f is None else _dev_tensor(f, torch.float32, (b,), "f")
@@ -73,9 +71,7 @@ def apgd_step(x, x_prev, x0, g, x_best, g_best, x_adv, f, hit, state, *, norm, e
               first=False, last=False, ckpt_len=0, n_valid=None):
     """lipasr_apgd_step on device tensors, in place: the seven row arrays float32 [rows, n], f float32 [rows] and hit int32 [rows]
     at x, ``state`` the dict of ``apgd_state``, n_valid int32 [rows] or None.  Returns x."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
-        raise ValueError("x must be a contiguous float32 device tensor [rows, n]")
-    rows, n = x.shape
+    rows, n = rows2d(x, "x", "[rows, n]")
     for t, what in ((x_prev, "x_prev"), (x0, "x0"), (g, "g"), (x_best, "x_best"), (g_best, "g_best"), (x_adv, "x_adv")):
         _dev_tensor(t, torch.float32, (rows, n), what)
     _dev_tensor(f, torch.float32, (rows,), "f")
@@ -89,7 +85,7 @@ def apgd_step(x, x_prev, x0, g, x_best, g_best, x_adv, f, hit, state, *, norm, e
     nrm = float(norm)
     if not (nrm == 2.0 or nrm == math.inf):
         raise ValueError(f"norm = {norm!r}: 2 and inf are supported")
-    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    lo, hi = clip_pair(clip_values)
     flags = (FIRST if first else 0) | (LAST if last else 0)
     h = N.get_handle(x.device.index)
     N.check(N.lib.lipasr_apgd_step(h.h, N.ptr(x), N.ptr(x_prev), N.ptr(x0), N.ptr(g), N.ptr(x_best), N.ptr(g_best), N.ptr(x_adv), N.ptr(f),

@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._rows import check_estimator, clip_pair, generate_host, labels_device, resolve_clip_values
 from .estimators import OverTheAirClassifier, TensorFlowV2Classifier, WaveformClassifier, _as_given, _dev, _Estimator, _to_dev
 from .extract_features_construct_dataset import read_wav, _extractor
 from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack: scores only; lipasr/genetic.py)
@@ -597,8 +598,7 @@ class AutoProjectedGradientDescent:
                  loss_type="cross_entropy", *, clip_values=_UNSET, seed=0):
         from .apgd import _loss_code, apgd_checkpoints
 
-        if not isinstance(estimator, (TensorFlowV2Classifier, WaveformClassifier)):
-            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        check_estimator(estimator, (TensorFlowV2Classifier, WaveformClassifier))
         self.norm = _norm_value(norm)
         if self.norm == 1.0:
             raise ValueError("norm=1: Auto-PGD runs in norm 2 or np.inf")
@@ -611,34 +611,17 @@ class AutoProjectedGradientDescent:
             raise ValueError("max_iter >= 1, batch_size >= 1 and nb_random_init >= 0 are required")
         self.targeted, self.loss_type = bool(targeted), loss_type
         self._loss = _loss_code(loss_type)
-        if not 1 <= estimator.nb_classes <= 32:
-            raise ValueError(f"{estimator.nb_classes} classes; 1 to 32 are supported")
         if self._loss == 1 and self.targeted:
             raise ValueError("loss_type='difference_logits_ratio' is untargeted only")
         if self._loss == 1 and estimator.nb_classes < 3:
             raise ValueError(f"loss_type='difference_logits_ratio' needs at least 3 classes, the estimator has {estimator.nb_classes}")
-        if clip_values is AutoProjectedGradientDescent._UNSET:
-            clip_values = estimator.clip_values
-        if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
-            raise ValueError(f"clip_values = {clip_values}")
-        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self.clip_values = resolve_clip_values(estimator, clip_values, AutoProjectedGradientDescent._UNSET)
         self.seed = (0xA9D0000000000000 + int(seed)) & 0xFFFFFFFFFFFFFFFF
         self._ckpt = {}
         prev = 0
         for w in apgd_checkpoints(self.max_iter):
             self._ckpt[w], prev = w - prev, w
         self.success_ = self.loss_ = self.halvings_ = None
-
-    def _labels(self, xt, yt, lt, bs):
-        if yt is None:
-            if self.targeted:
-                raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-            yt = self.estimator.own_labels_device(xt, lengths=lt, batch=bs)
-        yt = yt.to(xt.device)
-        lab = yt.argmax(dim=1) if yt.dim() == 2 else yt
-        if tuple(lab.shape) != (xt.shape[0],):
-            raise ValueError(f"y must be one-hot [B, classes] or class indices [B], got {tuple(yt.shape)}")
-        return lab.to(torch.int32).contiguous()
 
     def _start(self, x, x0, restart, row0, mask):
         if self.nb_random_init == 0:
@@ -681,7 +664,7 @@ class AutoProjectedGradientDescent:
         xt = est.rows_device(xt)
         b, dev = xt.shape[0], xt.device
         bs = min(self.batch_size, int(est.batch_limit))
-        lab_all = self._labels(xt, yt, lt, bs)
+        lab_all = labels_device(xt, yt, self.targeted, lambda: est.own_labels_device(xt, lengths=lt, batch=bs))
         mask_all = None if lt is None else est.clip_mask(lt)
         adv = xt.clone()
         self.success_ = torch.zeros(b, dtype=torch.bool, device=dev)
@@ -710,9 +693,7 @@ class AutoProjectedGradientDescent:
         return adv
 
     def generate(self, x, y=None, lengths=None):
-        xt = _to_dev(x)
-        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
-        return _as_given(self.generate_device(xt, yt, lengths), x)
+        return generate_host(self, x, y, lengths)
 
 
 def deepfool_step(jac, out, label, x, norm=2, overshoot=0.02, clip_values=None, allowed=None):
@@ -731,7 +712,7 @@ def deepfool_step(jac, out, label, x, norm=2, overshoot=0.02, clip_values=None, 
         raise ValueError(f"out must be a contiguous float32 tensor [{b}, {c}]")
     if tuple(label.shape) != (b,) or label.dtype != torch.int32 or (allowed is not None and (tuple(allowed.shape) != (b,) or allowed.dtype != torch.int32)):
         raise ValueError(f"label (and allowed) must be int32 tensors [{b}]")
-    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x.device.index)
     dist = torch.empty(b, device=x.device)
     target = torch.empty(b, dtype=torch.int32, device=x.device)
@@ -958,9 +939,7 @@ class AutoAttack:
         return adv
 
     def generate(self, x, y=None, lengths=None):
-        xt = _to_dev(x)
-        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
-        return _as_given(self.generate_device(xt, yt, lengths), x)
+        return generate_host(self, x, y, lengths)
 
 
 class ImperceptibleASR:

@@ -18,17 +18,10 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
 import torch
 
 from . import _native as N
-from .estimators import _as_given, _Estimator, _to_dev
-
-
-def _dev_tensor(t, dtype, shape, what):
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        raise ValueError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} device tensor {list(shape)}")
-    return t
+from ._rows import _dev_tensor, check_estimator, clip_pair, generate_host, labels_device, resolve_clip_values, rows2d
 
 
 def mutate_threshold(mutation_p):
@@ -44,9 +37,7 @@ def genetic_breed(x0, pop, generation, seed, mutate_thresh, step, eps, *, pop_in
     """lipasr_genetic_breed on device tensors: x0 float32 [B, n]; pop_in float32 [B * pop, n] with parents int32 [B, pop, 2], or
     neither (the initial population); n_valid int32 [B] or None -> float32 [B * pop, n], row b * pop + p child p of clip
     ``clip0 + b``."""
-    if not (torch.is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float32 and x0.dim() == 2 and x0.is_contiguous()):
-        raise ValueError("x0 must be a contiguous float32 device tensor [B, n]")
-    b, n = x0.shape
+    b, n = rows2d(x0, "x0")
     pop, generation = int(pop), int(generation)
     if not 0 <= generation < 1 << 24:
         raise ValueError(f"generation = {generation}: 0 to 2^24 - 1")
@@ -62,7 +53,7 @@ def genetic_breed(x0, pop, generation, seed, mutate_thresh, step, eps, *, pop_in
         out = torch.empty(b * max(pop, 0), n, device=x0.device)
     else:
         _dev_tensor(out, torch.float32, (b * pop, n), "out")
-    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x0.device.index)
     N.check(N.lib.lipasr_genetic_breed(h.h, N.ptr(x0), N.ptr(n_valid), N.ptr(pop_in), N.ptr(parents), b, pop, n, int(clip0), generation,
                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(mutate_thresh), float(step), float(eps), lo, hi, N.ptr(out),
@@ -73,9 +64,7 @@ def genetic_breed(x0, pop, generation, seed, mutate_thresh, step, eps, *, pop_in
 def genetic_select(logits, labels, pop, generation, seed, temperature, *, targeted=False, clip0=0, fitness, best, done, parents):
     """lipasr_genetic_select on device tensors: logits float32 [B * pop, C], labels int32 [B]; writes fitness float32 [B, pop], best
     int32 [B], done int32 [B] (sticky; generation + 1 where the clip succeeds) and parents int32 [B, pop, 2]."""
-    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()):
-        raise ValueError("logits must be a contiguous float32 device tensor [B * pop, classes]")
-    rows, c = logits.shape
+    rows, c = rows2d(logits, "logits", "[B * pop, classes]")
     pop, generation = int(pop), int(generation)
     if pop < 1 or rows % pop:
         raise ValueError(f"{rows} rows of logits are no multiple of pop = {pop}")
@@ -116,8 +105,7 @@ class GeneticAttack:
 
     def __init__(self, estimator, eps, *, pop_size=20, max_iter=500, mutation_p=0.0005, step=None, temperature=0.01, targeted=False,
                  seed=0, clip_values=_UNSET, check_every=10):
-        if not isinstance(estimator, _Estimator):
-            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        check_estimator(estimator)
         self.estimator = estimator
         self.eps = float(eps)
         self.step = self.eps if step is None else float(step)
@@ -130,30 +118,13 @@ class GeneticAttack:
             raise ValueError(f"max_iter = {max_iter}: 1 to 2^24")
         if self.check_every < 1:
             raise ValueError(f"check_every = {check_every}")
-        if not 1 <= estimator.nb_classes <= 32:
-            raise ValueError(f"{estimator.nb_classes} classes; 1 to 32 are supported")
         self.mutation_p, self._thresh = float(mutation_p), mutate_threshold(mutation_p)
         self.temperature = float(temperature)
         if not 0.0 < self.temperature < math.inf:
             raise ValueError(f"temperature = {temperature}: a finite, positive number is required")
         self.targeted, self.seed = bool(targeted), int(seed) & 0xFFFFFFFFFFFFFFFF
-        if clip_values is GeneticAttack._UNSET:
-            clip_values = estimator.clip_values
-        if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
-            raise ValueError(f"clip_values = {clip_values}")
-        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self.clip_values = resolve_clip_values(estimator, clip_values, GeneticAttack._UNSET)
         self.success_ = self.queries_ = self.fitness_ = None
-
-    def _labels(self, xt, yt, lt):
-        if yt is None:
-            if self.targeted:
-                raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-            return self.estimator.predict_device(xt, logits=True, lengths=lt).argmax(dim=1).to(torch.int32).contiguous()
-        yt = yt.to(xt.device)
-        lab = yt.argmax(dim=1) if yt.dim() == 2 else yt
-        if tuple(lab.shape) != (xt.shape[0],):
-            raise ValueError(f"y must be one-hot [B, classes] or class indices [B], got {tuple(yt.shape)}")
-        return lab.to(torch.int32).contiguous()
 
     def generate_device(self, xt, yt=None, lengths=None):
         """xt: float32 device tensor [B, features or samples]; yt: one-hot [B, classes] or class indices [B] or None; returns a NEW
@@ -165,7 +136,7 @@ class GeneticAttack:
         dev = xt.device
         lt = est.lengths_device(lengths, b)
         pos = None if lt is None else est.clip_mask(lt).sum(dim=1).to(torch.int32).contiguous()
-        labels = self._labels(xt, yt, lt)
+        labels = labels_device(xt, yt, self.targeted, lambda: est.predict_device(xt, logits=True, lengths=lt).argmax(dim=1))
         adv = xt.clone()
         self.success_ = torch.zeros(b, dtype=torch.bool, device=dev)
         self.queries_ = torch.zeros(b, dtype=torch.int64, device=dev)
@@ -205,6 +176,4 @@ class GeneticAttack:
         return adv
 
     def generate(self, x, y=None, lengths=None):
-        xt = _to_dev(x)
-        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
-        return _as_given(self.generate_device(xt, yt, lengths), x)
+        return generate_host(self, x, y, lengths)

@@ -24,23 +24,12 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .estimators import _as_given, _Estimator, _to_dev
-from .genetic import _dev_tensor
+from ._rows import _dev_tensor, check_estimator, clip_pair, generate_host, labels_device, resolve_clip_values, rows2d
 
 START, HALVE, BISECT = N.HSJ_START, N.HSJ_HALVE, N.HSJ_BISECT
 FIRST, LAST = N.HSJ_FIRST, N.HSJ_LAST
 F, I = N.HSJ_F, N.HSJ_I
 MAX_DRAWS = 16384  # per lipasr_hsj_accumulate call
-
-
-def _rows(x, what="x"):
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
-        raise ValueError(f"{what} must be a contiguous float32 device tensor [B, n]")
-    return x.shape
-
-
-def _clip(clip_values):
-    return (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
 
 
 def _norm(norm):
@@ -54,7 +43,7 @@ def _norm(norm):
 def hsj_expand(x, delta, draws, it, seed, norm, *, out, n_valid=None, clip0=0, draw0=0, clip_values=None):
     """lipasr_hsj_expand on device tensors: x float32 [B, n], delta float32 [B] -> out float32 [B * draws, n], row b * draws + j the
     copy ``draw0 + j`` of clip ``clip0 + b`` at iteration ``it``."""
-    b, n = _rows(x)
+    b, n = rows2d(x, "x")
     draws = int(draws)
     _dev_tensor(delta, torch.float32, (b,), "delta")
     _dev_tensor(out, torch.float32, (b * draws, n), "out")
@@ -62,7 +51,7 @@ def hsj_expand(x, delta, draws, it, seed, norm, *, out, n_valid=None, clip0=0, d
         _dev_tensor(n_valid, torch.int32, (b,), "n_valid")
     if not 0 <= int(it) < 1 << 24:
         raise ValueError(f"it = {it}: 0 to 2^24 - 1")
-    lo, hi = _clip(clip_values)
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x.device.index)
     N.check(N.lib.lipasr_hsj_expand(h.h, N.ptr(x), N.ptr(delta), N.ptr(n_valid), b, n, draws, int(clip0), int(it), int(draw0),
                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _norm(norm), lo, hi, N.ptr(out), N.stream_ptr()))
@@ -72,8 +61,8 @@ def hsj_expand(x, delta, draws, it, seed, norm, *, out, n_valid=None, clip0=0, d
 def hsj_accumulate(logits, labels, p, x, *, sums, counts, n_valid=None, targeted=False):
     """lipasr_hsj_accumulate on device tensors, in place on sums float64 [B, 2, n] and counts int32 [B, 2]: logits float32
     [B * draws, classes] at the rows p float32 [B * draws, n] around x float32 [B, n]; labels int32 [B]."""
-    b, n = _rows(x)
-    _rows(p, "p")
+    b, n = rows2d(x, "x")
+    rows2d(p, "p")
     if p.shape[1] != n or (b and p.shape[0] % b):
         raise ValueError(f"p must be [{b} * draws, {n}], got {tuple(p.shape)}")
     draws = p.shape[0] // b if b else 0
@@ -110,7 +99,7 @@ def hsj_search(logits, labels, x0, mode, flags, seed, norm, *, x_cand, x_far, x_
     """lipasr_hsj_search on device tensors, in place: logits float32 [B, classes] at x_cand (None under FIRST, then ``classes`` says
     how many), labels int32 [B], the five row buffers float32 [B, n], fstate float32 [B, 8] and istate int32 [B, 8] (columns:
     lipasr._native.HSJ_F, HSJ_I), start_lo, start_hi, theta float32 [B]."""
-    b, n = _rows(x0, "x0")
+    b, n = rows2d(x0, "x0")
     if logits is not None:
         if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
                 and logits.shape[0] == b):
@@ -129,7 +118,7 @@ def hsj_search(logits, labels, x0, mode, flags, seed, norm, *, x_cand, x_far, x_
         _dev_tensor(t, torch.float32, (b,), what)
     if n_valid is not None:
         _dev_tensor(n_valid, torch.int32, (b,), "n_valid")
-    lo, hi = _clip(clip_values)
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x0.device.index)
     N.check(N.lib.lipasr_hsj_search(h.h, N.ptr(logits), N.ptr(labels), N.ptr(x0), N.ptr(n_valid), N.ptr(u), N.ptr(start_lo), N.ptr(start_hi),
                                     N.ptr(theta), b, int(classes or 1), n, int(mode), int(flags), 1 if targeted else 0, int(clip0), int(draw),
@@ -177,8 +166,7 @@ class HopSkipJump:
 
     def __init__(self, classifier, batch_size=64, targeted=False, norm=2, max_iter=50, max_eval=10000, init_eval=100, init_size=100,
                  verbose=True, *, seed=0, clip_values=_UNSET, gamma=0.01, max_halvings=25, check_every=4):
-        if not isinstance(classifier, _Estimator):
-            raise TypeError("classifier must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        check_estimator(classifier, what="classifier")
         self.estimator = classifier
         self.norm = _norm(norm)
         self.batch_size, self.targeted, self.verbose = int(batch_size), bool(targeted), bool(verbose)
@@ -192,30 +180,13 @@ class HopSkipJump:
             raise ValueError(f"max_eval = {max_eval}, init_eval = {init_eval}, init_size = {init_size}: at least 1")
         if not 0.0 < self.gamma < math.inf:
             raise ValueError(f"gamma = {gamma}: a positive number is required")
-        if not 1 <= classifier.nb_classes <= 32:
-            raise ValueError(f"{classifier.nb_classes} classes; 1 to 32 are supported")
         self.seed = (0x48534A0000000000 + int(seed)) & 0xFFFFFFFFFFFFFFFF
-        if clip_values is HopSkipJump._UNSET:
-            clip_values = classifier.clip_values
-        if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
-            raise ValueError(f"clip_values = {clip_values}")
-        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self.clip_values = resolve_clip_values(classifier, clip_values, HopSkipJump._UNSET)
         self.success_ = self.distance_ = self.queries_ = self.start_distance_ = None
 
     def evals(self, t):
         """E of iteration ``t``: min(int(init_eval sqrt(t)), max_eval)."""
         return min(int(self.init_eval * math.sqrt(t)), self.max_eval)
-
-    def _labels(self, xt, yt, clean):
-        if yt is None:
-            if self.targeted:
-                raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-            return clean.argmax(dim=1).to(torch.int32).contiguous()
-        yt = yt.to(xt.device)
-        lab = yt.argmax(dim=1) if yt.dim() == 2 else yt
-        if tuple(lab.shape) != (xt.shape[0],):
-            raise ValueError(f"y must be one-hot [B, classes] or class indices [B], got {tuple(yt.shape)}")
-        return lab.to(torch.int32).contiguous()
 
     def _phase(self, mode, limit, predict, kw, **first):
         """One phase of lipasr_hsj_search: FIRST, then one query per call until no row is active."""
@@ -249,7 +220,7 @@ class HopSkipJump:
         predict_all = lambda rows, ls: torch.cat([est.predict_device(rows[s:s + cb], logits=True, lengths=None if ls is None else ls[s:s + cb])
                                                   for s in range(0, b, cb)])
         clean = predict_all(xt, lt)
-        labels = self._labels(xt, yt, clean)
+        labels = labels_device(xt, yt, self.targeted, lambda: clean.argmax(dim=1))
         already = adversarial_device(clean, labels, self.targeted)
         init = None
         if x_adv_init is not None:
@@ -340,6 +311,4 @@ class HopSkipJump:
         return adv
 
     def generate(self, x, y=None, x_adv_init=None, lengths=None):
-        xt = _to_dev(x)
-        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
-        return _as_given(self.generate_device(xt, yt, x_adv_init, lengths), x)
+        return generate_host(self, x, y, x_adv_init, lengths)

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._rows import clip_pair, rows2d
 from .estimators import _Estimator
 
 _PHI_INV = NormalDist().inv_cdf
@@ -109,9 +110,7 @@ def smooth_expand(x, draws, sigma, seed=0, *, clip0=0, draw0=0, n_valid=None, cl
     """lipasr_smooth_expand on device tensors (include/lipasr.h fixes the conventions): x float32 [B, n] contiguous along its rows,
     n_valid int32 [B] or None -> float32 [B * draws, n], row b * draws + j the copy of row b with draw ``draw0 + j`` of clip
     ``clip0 + b`` added below n_valid[b]."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
-        raise ValueError("x must be a contiguous float32 device tensor [B, n]")
-    b, n = x.shape
+    b, n = rows2d(x, "x")
     draws = int(draws)
     if n_valid is not None and (tuple(n_valid.shape) != (b,) or n_valid.dtype != torch.int32 or not n_valid.is_contiguous()):
         raise ValueError(f"n_valid must be a contiguous int32 tensor [{b}]")
@@ -119,7 +118,7 @@ def smooth_expand(x, draws, sigma, seed=0, *, clip0=0, draw0=0, n_valid=None, cl
         out = torch.empty(b * max(draws, 0), n, device=x.device)
     elif tuple(out.shape) != (b * draws, n) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float32 tensor [{b * draws}, {n}]")
-    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x.device.index)
     N.check(N.lib.lipasr_smooth_expand(h.h, N.ptr(x), N.ptr(n_valid), b, n, draws, int(clip0), int(draw0), float(sigma), int(seed), lo, hi,
                                        N.ptr(out), N.stream_ptr()))
@@ -129,9 +128,7 @@ def smooth_expand(x, draws, sigma, seed=0, *, clip0=0, draw0=0, n_valid=None, cl
 def smooth_vote(logits, batch, counts):
     """lipasr_smooth_vote: float32 logits [batch * draws, classes] -> the argmax histogram of every clip ADDED to the int32
     ``counts`` [batch, classes + 1] (last bin: rows with a NaN)."""
-    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()):
-        raise ValueError("logits must be a contiguous float32 device tensor [batch * draws, classes]")
-    rows, c = logits.shape
+    rows, c = rows2d(logits, "logits", "[batch * draws, classes]")
     batch = int(batch)
     if batch < 0 or (batch == 0 and rows) or (batch and rows % batch):
         raise ValueError(f"{rows} rows of logits are no multiple of batch = {batch}")

@@ -21,8 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .estimators import _as_given, _Estimator, _to_dev
-from .genetic import _dev_tensor
+from ._rows import _dev_tensor, check_estimator, clip_pair, generate_host, labels_device, resolve_clip_values, rows2d
 
 LAST = N.SQUARE_LAST
 SCHEDULE = (10, 50, 200, 500, 1000, 2000, 4000, 6000, 8000)  # of a run rescaled to 10 000 iterations
@@ -54,9 +53,7 @@ def square_p_q(p):
 
 
 def _rows(x0, height, width):
-    if not (torch.is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float32 and x0.dim() == 2 and x0.is_contiguous()):
-        raise ValueError("x0 must be a contiguous float32 device tensor [B, n]")
-    b, n = x0.shape
+    b, n = rows2d(x0, "x0")
     height, width = int(height), int(width)
     if height < 0 or width < 0 or height * width != n:
         raise ValueError(f"shape = ({height}, {width}) does not multiply to the row length {n}")
@@ -74,7 +71,7 @@ def square_init(x0, height, width, restart, seed, eps, *, x_best, x_cand, win, n
         _dev_tensor(n_valid, torch.int32, (b,), "n_valid")
     if not 0 <= int(restart) < 256:
         raise ValueError(f"restart = {restart}: 0 to 255")
-    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x0.device.index)
     N.check(N.lib.lipasr_square_init(h.h, N.ptr(x0), N.ptr(n_valid), b, height, width, int(clip0), int(restart),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, float(eps), lo, hi, N.ptr(x_best), N.ptr(x_cand), N.ptr(win),
@@ -104,7 +101,7 @@ def square_step(logits, labels, x0, height, width, win_h, win_w, p_q, restart, i
         raise ValueError(f"restart = {restart}: 0 to 255")
     if not 0 <= int(p_q) <= 1 << 24:
         raise ValueError(f"p_q = {p_q}: 0 to 2^24")
-    lo, hi = (-math.inf, math.inf) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+    lo, hi = clip_pair(clip_values)
     h = N.get_handle(x0.device.index)
     N.check(N.lib.lipasr_square_step(h.h, N.ptr(logits), N.ptr(labels), N.ptr(x0), N.ptr(n_valid), b, logits.shape[1], height, width,
                                      int(win_h), int(win_w), int(p_q), 1 if targeted else 0, int(clip0), int(restart), int(it),
@@ -152,8 +149,7 @@ class SquareAttack:
 
     def __init__(self, estimator, norm=np.inf, max_iter=100, eps=0.3, p_init=0.8, nb_restarts=1, batch_size=128, *, shape=None,
                  targeted=False, seed=0, clip_values=_UNSET, p_schedule=square_p, check_every=10):
-        if not isinstance(estimator, _Estimator):
-            raise TypeError("estimator must be a lipasr TensorFlowV2Classifier or WaveformClassifier")
+        check_estimator(estimator)
         if norm not in (np.inf, "inf", math.inf):
             raise ValueError(f"norm = {norm!r}: only np.inf is built -- the L2 Square Attack redistributes mass between windows and is "
                              "out of scope")
@@ -171,8 +167,6 @@ class SquareAttack:
             raise ValueError(f"nb_restarts = {nb_restarts}: 1 to 256")
         if self.batch_size < 1 or self.check_every < 1:
             raise ValueError(f"batch_size = {batch_size}, check_every = {check_every}: at least 1")
-        if not 1 <= estimator.nb_classes <= 32:
-            raise ValueError(f"{estimator.nb_classes} classes; 1 to 32 are supported")
         if shape is not None:
             if len(tuple(shape)) != 2:
                 raise ValueError(f"shape = {shape!r}: (height, width) is required")
@@ -185,23 +179,8 @@ class SquareAttack:
         self.p_schedule = p_schedule
         self.targeted = bool(targeted)
         self.seed = (0x5CA2E00000000000 + int(seed)) & 0xFFFFFFFFFFFFFFFF
-        if clip_values is SquareAttack._UNSET:
-            clip_values = estimator.clip_values
-        if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
-            raise ValueError(f"clip_values = {clip_values}")
-        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self.clip_values = resolve_clip_values(estimator, clip_values, SquareAttack._UNSET)
         self.success_ = self.queries_ = self.loss_ = None
-
-    def _labels(self, xt, yt, clean):
-        if yt is None:
-            if self.targeted:
-                raise ValueError("Target labels `y` need to be provided for a targeted attack.")
-            return clean.argmax(dim=1).to(torch.int32).contiguous()
-        yt = yt.to(xt.device)
-        lab = yt.argmax(dim=1) if yt.dim() == 2 else yt
-        if tuple(lab.shape) != (xt.shape[0],):
-            raise ValueError(f"y must be one-hot [B, classes] or class indices [B], got {tuple(yt.shape)}")
-        return lab.to(torch.int32).contiguous()
 
     def window(self, it, height, width):
         """(win_h, win_w, p_q) of proposal ``it``."""
@@ -229,7 +208,7 @@ class SquareAttack:
             return adv
         clean = torch.cat([est.predict_device(xt[s:s + bs], logits=True, lengths=None if lt is None else lt[s:s + bs])
                            for s in range(0, b, bs)])
-        labels = self._labels(xt, yt, clean)
+        labels = labels_device(xt, yt, self.targeted, lambda: clean.argmax(dim=1))
         margin = margin_device(clean, labels, self.targeted)
         already = margin < 0
         self.loss_ = torch.where(already, margin, self.loss_)
@@ -271,6 +250,4 @@ class SquareAttack:
         return adv
 
     def generate(self, x, y=None, lengths=None):
-        xt = _to_dev(x)
-        yt = None if y is None else (y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y)))
-        return _as_given(self.generate_device(xt, yt, lengths), x)
+        return generate_host(self, x, y, lengths)

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from apgd_ref import within_ball as _within_ball
 from smoothing_ref import linear_case, linear_classify, philox4x32  # noqa: F401
 
 AMBIGUITY = 1e-5  # of the total weight: the issue's definition of an ambiguous draw
@@ -156,9 +157,7 @@ def attack(classify, x, labels, eps, pop=20, max_iter=500, mutation_p=0.0005, st
 
 def within_ball(adv, x, eps):
     """|adv - x| <= eps plus one unit in the last place of the bound: the ball's bounds are the fp32 numbers x -+ eps."""
-    adv, x = np.asarray(adv, dtype=np.float32), np.asarray(x, dtype=np.float32)
-    room = float(np.float32(eps)) + np.spacing(np.abs(x) + np.float32(eps)).astype(np.float64)
-    return bool((np.abs(adv.astype(np.float64) - x.astype(np.float64)) <= room).all())
+    return _within_ball(np.asarray(adv, dtype=np.float32), np.asarray(x, dtype=np.float32), float(np.float32(eps)), np.inf)
 
 
 # ---- the linear two-class case, restated for L-inf: six rows at (almost) the same distance from the boundary

@@ -1,7 +1,7 @@
 """Oracle of HopSkipJump (lipasr_hsj_expand / _accumulate / _direction / _search, their host twins, lipasr.hopskipjump.HopSkipJump):
 a NumPy restatement.  TEST INFRASTRUCTURE for tests/test_hsj_*: nothing here is used by the library.
 
-    philox_np     Philox4x32-10 on uint64 arrays (pinned against square_ref.philox, Python integers, by test_hsj_cpu)
+    philox_np     philox_ref's, re-exported (pinned against philox, Python integers, by test_hsj_cpu)
     fmaf32 / fma64   a * b + c rounded once: float32 through round-to-odd in float64, float64 through an exact product and fsum
     adversarial   the decision on one row of logits
     draw          one draw r (before scaling): L-inf exact, L2 Box-Muller in float64 or float32
@@ -16,10 +16,8 @@ import math
 
 import numpy as np
 
-from square_ref import philox  # noqa: F401  (Python integers: the pin of philox_np)
+from philox_ref import nv as _nv, philox, philox_np  # noqa: F401  (re-exported under the names the tests import)
 
-M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-MASK = np.uint64(0xFFFFFFFF)
 TAG_START, TAG_L2, TAG_LINF = 1 << 28, 2 << 28, 3 << 28
 START, HALVE, BISECT = 0, 1, 2
 FIRST, LAST = 1, 2
@@ -27,17 +25,6 @@ F = {"lo": 0, "hi": 1, "mid": 2, "thresh": 3, "eps": 4, "dist": 5, "dist_best": 
 I = {"active": 0, "found": 1, "ok": 2, "moved": 3, "halvings": 4, "queries": 5}
 f32 = np.float32
 INF = f32(np.inf)
-
-
-def philox_np(seed, lo, hi, hi0, hi1):
-    """Blocks with key ``seed`` and counters (lo, hi, hi0, hi1), each a 32-bit value or array -> uint64 array [4, ...]."""
-    c = [np.asarray(v, dtype=np.uint64) & MASK for v in np.broadcast_arrays(lo, hi, hi0, hi1)]
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(M0) * c[0], np.uint64(M1) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & MASK, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & MASK]
-        k0, k1 = (k0 + np.uint64(W0)) & MASK, (k1 + np.uint64(W1)) & MASK
-    return np.stack(c)
 
 
 def _two_sum(a, b):
@@ -90,10 +77,6 @@ def adversarial(z, y, targeted=False):
         return False
     p = int(np.argmax(z))  # the first maximum
     return p == y if targeted else p != y
-
-
-def _nv(n_valid, b, n):
-    return n if n_valid is None else min(max(int(n_valid[b]), 0), n)
 
 
 def draw(l2, seed, clip, it, j, n, nv, dtype=np.float64):

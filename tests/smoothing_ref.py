@@ -1,7 +1,7 @@
 """Oracle of randomized smoothing (lipasr_smooth_expand, lipasr_smooth_vote, lipasr_smooth_noise_host, lipasr.smoothing.Smooth): a
 float64 restatement.  TEST INFRASTRUCTURE for tests/test_smoothing_*: nothing here is used by the library.
 
-    philox4x32      Philox4x32-10 (Salmon et al. 2011) on NumPy integers: key = seed, counter = (ctr low, ctr high, hi0, hi1)
+    philox4x32      philox_ref.philox_np: key = seed, counter = (ctr low, ctr high, hi0, hi1)
     normal          the Box-Muller of normal4 on one block per four elements, counter (k >> 2, 0, clip, draw): the uniforms are the
                     kernel's ((x >> 8) + 1) / 2^24, exact in both precisions; log, sqrt, cos and sin are float64 and 2 pi is exact
     expand          clamp(x + sigma z) below n_valid, x behind it                       (include/lipasr.h, lipasr_smooth_expand)
@@ -13,25 +13,13 @@ from __future__ import annotations
 
 import numpy as np
 
-M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-MASK = 0xFFFFFFFF
+from philox_ref import MASK, philox_np
 
 
 def philox4x32(seed, ctr, hi0, hi1):
-    """ctr: uint64 array [m] -> uint64 array [4, m] of 32-bit words."""
+    """ctr: uint64 array [m] -> uint64 array [4, m] of 32-bit words (philox_ref.philox_np with the counter's two halves)."""
     ctr = np.asarray(ctr, dtype=np.uint64)
-    mask = np.uint64(MASK)
-    c0, c1 = ctr & mask, ctr >> np.uint64(32)
-    c2 = np.full_like(ctr, int(hi0) & MASK)
-    c3 = np.full_like(ctr, int(hi1) & MASK)
-    k0, k1 = int(seed) & MASK, (int(seed) >> 32) & MASK
-    for _ in range(10):
-        p0, p1 = np.uint64(M0) * c0, np.uint64(M1) * c2  # 32 x 32 bits: no overflow in 64
-        n0 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0)
-        n2 = (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1)
-        c1, c3, c0, c2 = p1 & mask, p0 & mask, n0, n2
-        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
-    return np.stack([c0, c1, c2, c3])
+    return philox_np(int(seed), ctr, ctr >> np.uint64(32), int(hi0) & MASK, int(hi1) & MASK)
 
 
 def normal(seed, clip, draw, n):

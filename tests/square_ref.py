@@ -1,7 +1,7 @@
 """Oracle of Square Attack (lipasr_square_init, lipasr_square_step, their host twins, lipasr.square.SquareAttack): a NumPy
 restatement.  TEST INFRASTRUCTURE for tests/test_square_* and tests/test_autoattack_gpu.py: nothing here is used by the library.
 
-    philox        Philox4x32-10 on Python integers only (one block)
+    philox        philox_ref's, re-exported
     init          the vertical-stripe start (include/lipasr.h, lipasr_square_init)
     margin        the loss of one row of logits, in float32
     draw          proposal it + 1 of a row: window and sign
@@ -18,21 +18,10 @@ import math
 
 import numpy as np
 
-MASK = 0xFFFFFFFF
-M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+from philox_ref import MASK, nv as _row_nv, philox  # noqa: F401  (philox: re-exported under the name the tests import)
+
 STRIPE_TAG = 1 << 62
 SCHEDULE = (10, 50, 200, 500, 1000, 2000, 4000, 6000, 8000)
-
-
-def philox(seed, ctr_lo, hi0, hi1):
-    """One block: key ``seed`` (64 bits), counter (ctr_lo low word, ctr_lo high word, hi0, hi1) -> four 32-bit words."""
-    c = [ctr_lo & MASK, (ctr_lo >> 32) & MASK, hi0 & MASK, hi1 & MASK]
-    k0, k1 = seed & MASK, (seed >> 32) & MASK
-    for _ in range(10):
-        p0, p1 = M0 * c[0], M1 * c[2]
-        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & MASK, (p0 >> 32) ^ c[3] ^ k1, p0 & MASK]
-        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
-    return c
 
 
 def value(x, minus, eps, lo=-np.inf, hi=np.inf):
@@ -45,7 +34,7 @@ def value(x, minus, eps, lo=-np.inf, hi=np.inf):
 
 
 def _nv(n_valid, b, n):
-    return None if n_valid is None else min(max(int(n_valid[b]), 0), n)
+    return None if n_valid is None else _row_nv(n_valid, b, n)  # None: no lengths, as the kernel's -1
 
 
 def stripe_signs(seed, clip, restart, width):

@@ -113,6 +113,21 @@ def test_refusals_without_a_device():
     assert step(*_step_args(arrays=[None] * 18, rows=0)) == N.OK and step(*_step_args(arrays=[None] * 18, n=0)) == N.OK
 
 
+def test_step_names_the_arrays_that_overlap():
+    """A written array that shares a byte with any other is refused by name, the earlier argument first; made-up pointers."""
+    import lipasr._native as N
+
+    step = N.lib.lipasr_apgd_step
+    names = ["x", "x_prev", "x0", "g", "x_best", "g_best", "x_adv", "f", "hit", "n_valid", "eta", "f_best", "f_prev", "f_best_ckpt",
+             "improved", "reduced_last", "fooled", "halvings"]
+    row_bytes, state_bytes = 2 * 16 * 4, 2 * 4
+    for i, j, shift in ((0, 4, 64), (0, 1, row_bytes - 4), (2, 6, 0), (3, 5, -4), (7, 10, 4), (9, 10, 0), (11, 12, 0), (8, 17, state_bytes - 4)):
+        arrays = [C.c_void_p(4096 * (k + 1)) for k in range(18)]
+        arrays[j] = C.c_void_p(4096 * (i + 1) + shift)
+        assert step(*_step_args(arrays=arrays)) == N.EINVAL
+        assert N.last_error() == f"lipasr_apgd_step: {names[i]} overlaps {names[j]}", (i, j, N.last_error())
+
+
 def test_checkpoints():
     from lipasr.apgd import apgd_checkpoints
 

@@ -19,6 +19,7 @@ import torch
 
 from helpers import build_model, dev, load_params
 from oracle import mlp_ref as P
+from philox_ref import philox_np
 
 gpu = pytest.mark.gpu
 
@@ -30,24 +31,13 @@ KNOB_NO_RING, KNOB_NO_X1 = 32, 512
 # ---------------------------------------------------------------------------------------------
 # the generator and the mask rule, restated
 # ---------------------------------------------------------------------------------------------
-M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 MASK32 = np.uint64(0xFFFFFFFF)
 
 
 def philox4x32_10(ctr, key):
     """ctr: four uint32 arrays (or scalars) of one shape, key: (k0, k1) -> the four uint32 outputs."""
-    c = [np.asarray(x, dtype=np.uint64) & MASK32 for x in ctr]
-    c = list(np.broadcast_arrays(*c))
-    k0, k1 = np.uint64(key[0] & 0xFFFFFFFF), np.uint64(key[1] & 0xFFFFFFFF)
-    for _ in range(10):
-        p0 = np.uint64(M0) * c[0]
-        p1 = np.uint64(M1) * c[2]
-        n0 = (p1 >> np.uint64(32)) ^ c[1] ^ k0
-        n2 = (p0 >> np.uint64(32)) ^ c[3] ^ k1
-        c = [n0, p1 & MASK32, n2, p0 & MASK32]
-        k0 = (k0 + np.uint64(W0)) & MASK32
-        k1 = (k1 + np.uint64(W1)) & MASK32
-    return [x.astype(np.uint32) for x in c]
+    seed = (int(key[0]) & 0xFFFFFFFF) | ((int(key[1]) & 0xFFFFFFFF) << 32)
+    return [x.astype(np.uint32) for x in philox_np(seed, *ctr)]
 
 
 def dropout_mask(seed, layer, step, rows, cols, rate):

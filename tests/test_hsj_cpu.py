@@ -367,6 +367,37 @@ def test_abi_refusals_and_surface():
         HopSkipJump(object())
 
 
+def test_overlap_refusals_name_what_overlaps():
+    """Every host twin refuses a written span that overlaps another, by one element here, and says which: views of one buffer."""
+    N = _N()
+    x, delta = rows(2, 8, 0), np.ones(2, dtype=np.float32)
+    p = N.hsj_expand_host(x, delta, 3, 1, 0, 2)
+    z, lab = logits_for(2, 3, 4, [0, 1], 0), np.array([0, 1], dtype=np.int32)
+    _, counts = workspace(2, 8)
+    st = R.new_state(2, 8, [1, 1])
+    search = lambda **kw: N.hsj_search_host(z[:2], lab, x, R.BISECT, 0, 0, 2,
+                                            **{**dict(x_cand=st["x_cand"], x_far=st["x_far"], x_adv=st["x_adv"], x_best=st["x_best"],
+                                                      fstate=st["f"], istate=st["i"], start_lo=-delta, start_hi=delta, theta=delta,
+                                                      u=np.zeros((2, 8), dtype=np.float32)), **kw})
+    big = np.zeros(64, dtype=np.float64)
+    f32 = lambda a, b, shape: big[a:b].view(np.float32).reshape(shape)
+    inside = f32(0, 8, (2, 8))
+    for bad, msg in ((lambda: N.hsj_expand_host(inside, delta, 3, 1, 0, 2, out=f32(7, 31, (6, 8))), "lipasr_hsj_expand_host: out overlaps x"),
+                     (lambda: N.hsj_accumulate_host(z, lab, f32(31, 55, (6, 8)), x, sums=big[:32].reshape(2, 2, 8), counts=counts),
+                      "lipasr_hsj_accumulate_host: sums overlaps an input"),
+                     (lambda: N.hsj_accumulate_host(z, lab, p, f32(31, 39, (2, 8)), sums=big[:32].reshape(2, 2, 8), counts=counts),
+                      "lipasr_hsj_accumulate_host: sums overlaps an input"),
+                     (lambda: N.hsj_direction_host(big[:32].reshape(2, 2, 8), counts, 2, u=f32(31, 39, (2, 8))),
+                      "lipasr_hsj_direction_host: u overlaps sums"),
+                     (lambda: search(x_far=st["x_cand"]), "lipasr_hsj_search_host: x_cand overlaps x_far"),
+                     (lambda: search(x_best=st["x_adv"]), "lipasr_hsj_search_host: x_adv overlaps x_best"),
+                     (lambda: search(x_cand=x), "lipasr_hsj_search_host: x0 overlaps x_cand"),
+                     (lambda: search(u=st["x_best"]), "lipasr_hsj_search_host: x_best overlaps u")):
+        with pytest.raises(ValueError) as e:
+            bad()
+        assert msg in str(e.value), (msg, str(e.value))
+
+
 # ------------------------------------------------------------------------------------------------------------- the linear model
 def linear_model(n=36, seed=0):
     """sign(w x + b) as the two-layer, two-class network relu((w, -w) x + (b, -b)) -> identity: (W1 [n, 2], b1, W2, b2), w, b."""
