@@ -16,6 +16,7 @@ namespace lipasr {
 using namespace tables;
 
 long g_k1_launches[K1_KERNELS] = {};
+long g_k1_vjp_launches[K1V_KERNELS] = {};
 
 void mfcc_plan_free(MfccPlan* p) {
   if (!p) return;
@@ -535,17 +536,25 @@ static int plan_vjp(MfccPlan* p, const VjpCall& c, hipStream_t st) {
     return LIPASR_EUNSUPPORTED;
   }
   if ((rc = c.entry == VJ_SHORT ? vjp_short_prepare(fn, p) : vjp_prepare(fn, p)) != LIPASR_OK) return rc;
-  // when the caller's forward may be reused: the plan's intermediates are that forward only if it ran with the stage mask's
-  // profiling switches off (they do not reach dft_mel_kernel) and, for the one-length entry, in the three-kernel form (the fused
-  // resample -> STFT kernel leaves no d_y; the ragged entry has refused that case above)
-  const bool reuse = (c.flags & 1) && (c.entry == VJ_SHORT || !(p->stage_mask & (SM_SKIP_FFT | SM_SKIP_MEL))) &&
-                     !(c.entry == VJ_ONE_LENGTH && domain == 0 && prefers_fused(p));
+  // What of the caller's forward is reused (flags bit 0).
+  // d_y, the resampled signal: whenever the forward left one -- the one-length entry's fused resample -> STFT kernel leaves none
+  // (the ragged entry has refused that case above).  It does not depend on the STFT kernel.
+  // d_db / d_fmax, the tile: only where stft_mel2_kernel (or, on short-window plans, dft_mel_kernel) made it, which is also the
+  // kernel the backward pass runs for itself.  The other 2048/512 kernels lose, on a quiet frame next to a loud one, digits that the
+  // features never see (tolerance 2e-2) but that Gmel = Gdb (10 / ln 10) / mel magnifies: stft_bdft_kernel applies the Hann window
+  // in the frequency domain, 0.5 X[k] - 0.25 (X[k-1] + X[k+1]) of the rectangular-window spectrum, and a burst under the tail of a
+  // window cancels a large spectrum down to a small one that keeps the large one's 2^-22 (measured: mel powers 49 and 86 x further
+  // from float64 than a float32 evaluation, 3 .. 4 x on other frames); stft_mel_kernel sends two frames of any loudness through one
+  // transform.  stft_mel2_kernel windows in the time domain and scales every frame by itself.  Same bits either way.
+  const MfccPath::Stft stft = p->dft ? MfccPath::ST_DFT : MfccPath::ST_STOCKHAM4;
+  const bool reuse_y = (c.flags & 1) && !(c.entry == VJ_ONE_LENGTH && prefers_fused(p));
+  const bool reuse_tile = (c.flags & 1) && path.stft == stft && (domain == 1 || reuse_y);
   const float* y = static_cast<const float*>(c.sig);
   if (domain == 0) {
-    if (!reuse && (rc = launch_resample(p, path.resampler, c.sig, c.fmt, nv, batch, p->d_y, st)) != LIPASR_OK) return rc;
+    if (!reuse_y && (rc = launch_resample(p, path.resampler, c.sig, c.fmt, nv, batch, p->d_y, st)) != LIPASR_OK) return rc;
     y = p->d_y;
   }
-  if (!reuse && (rc = launch_from_22k(p, path.stft, y, nv, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
+  if (!reuse_tile && (rc = launch_from_22k(p, stft, y, nv, batch, L, nullptr, nullptr, nullptr, st, nullptr, true)) != LIPASR_OK) return rc;
   MfccVjpArgs a;
   a.y = y; a.n_y = p->n_y; a.n_frames = p->n_frames; a.batch = batch; a.L = L;
   a.db = p->d_db; a.fmax = p->d_fmax; a.g_feat = c.g_feat; a.aff_scale = c.scale; a.dct_rows = p->d_dct_rows;
@@ -729,6 +738,32 @@ int lipasr_debug_mfcc_stage(lipasr_mfcc_t p, int which, int batch, float* out, l
   const size_t row = which == 0 ? (size_t)p->n_frames * 128 : which == 1 ? (size_t)p->n_frames : (size_t)p->n_y;
   DeviceGuard g(p->ctx->device);
   LP_HIP(hipMemcpyAsync(out, src, (size_t)batch * row * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+  return LIPASR_OK;
+}
+
+// ---------------------------------------------------------------- test hooks of the backward pass
+long lipasr_debug_k1_vjp_launches(int kernel) { return (kernel >= 0 && kernel < K1V_KERNELS) ? g_k1_vjp_launches[kernel] : -1; }
+
+int lipasr_debug_mfcc_vjp_stage(lipasr_mfcc_t p, int which, int batch, float* out, lipasr_stream_t stream) {
+  LP_CHECK_ARG(p != nullptr && out != nullptr, "lipasr_debug_mfcc_vjp_stage: null argument");
+  LP_CHECK_ARG(batch >= 1 && batch <= p->batch_max, "lipasr_debug_mfcc_vjp_stage: batch %d outside [1, %d]", batch, p->batch_max);
+  LP_CHECK_ARG(which >= 0 && which <= 1, "lipasr_debug_mfcc_vjp_stage: unknown stage %d (0 Gmel, 1 g_y of a domain-0 call)", which);
+  LP_CHECK_ARG(p->vj_ready && p->d_gmel && p->d_gy, "lipasr_debug_mfcc_vjp_stage: the plan has run no backward pass yet (no workspaces)");
+  const float* src = which == 0 ? p->d_gmel : p->d_gy;
+  const size_t row = which == 0 ? (size_t)p->n_frames * 128 : (size_t)p->n_y;
+  DeviceGuard g(p->ctx->device);
+  LP_HIP(hipMemcpyAsync(out, src, (size_t)batch * row * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+  return LIPASR_OK;
+}
+
+int lipasr_debug_mfcc_stage_put(lipasr_mfcc_t p, int which, int batch, const float* in, lipasr_stream_t stream) {
+  LP_CHECK_ARG(p != nullptr && in != nullptr, "lipasr_debug_mfcc_stage_put: null argument");
+  LP_CHECK_ARG(batch >= 1 && batch <= p->batch_max, "lipasr_debug_mfcc_stage_put: batch %d outside [1, %d]", batch, p->batch_max);
+  LP_CHECK_ARG(which >= 0 && which <= 1, "lipasr_debug_mfcc_stage_put: unknown stage %d (0 dB tile, 1 frame maxima)", which);
+  float* dst = which == 0 ? p->d_db : p->d_fmax;
+  const size_t row = which == 0 ? (size_t)p->n_frames * 128 : (size_t)p->n_frames;
+  DeviceGuard g(p->ctx->device);
+  LP_HIP(hipMemcpyAsync(dst, in, (size_t)batch * row * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
   return LIPASR_OK;
 }
 

@@ -132,6 +132,11 @@ enum K1Kernel { K1_RESAMPLE_H2 = 0, K1_RESAMPLE_PERSIST = 4, K1_RESAMPLE_MFMA, K
                 K1_CLEAR_TAIL, K1_STFT_BDFT, K1_STFT_BDFT_DCT, K1_STFT_MEL2, K1_STFT_MEL, K1_DFT_MEL, K1_DCT, K1_FUSED_F32, K1_FUSED_I16,
                 K1_KERNELS };
 extern long g_k1_launches[K1_KERNELS];  // mfcc.hip
+// The same for the backward pass (lipasr_debug_k1_vjp_launches): one id per kernel instance of mfcc_vjp.h, mfcc_vjp.hip and
+// mfcc_vjp_short.hip, in the order include/lipasr.h lists them.
+enum K1VjpKernel { K1V_DB = 0, K1V_DB_RAGGED, K1V_STFT, K1V_STFT_RAGGED, K1V_FOLD, K1V_FOLD_RAGGED, K1V_RESAMPLE_Q8, K1V_RESAMPLE_Q1,
+                   K1V_RESAMPLE_Q8_RAGGED, K1V_RESAMPLE_Q1_RAGGED, K1V_COPY_CUT, K1V_DFT, K1V_DFT_FOLD, K1V_KERNELS };
+extern long g_k1_vjp_launches[K1V_KERNELS];  // mfcc.hip
 
 // rows of n_samp samples can be read four at a time: float4 (fmt 0) / short4 (fmt 1) aligned, a multiple of 4 samples long
 inline bool rows_vec4(const MfccPlan* p, const void* wav, int fmt) {

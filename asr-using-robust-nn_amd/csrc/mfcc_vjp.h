@@ -6,7 +6,8 @@
 //                             elements handed to the clip maximum (first maximum in (frame, mel) order), Gmel = Gdb (10/ln 10)/mel
 //                             with mel = 10^(dB/10) recomputed from the stored dB.
 //   2. stft_vjp_kernel        one workgroup per (clip, group of 8 frames).  Frames go in pairs through ONE complex FFT as in
-//                             stft_mel_kernel (frame a + i frame b, separated by conjugate symmetry); Z = 2 GP X of both frames
+//                             stft_mel_kernel (frame a + i frame b, separated by conjugate symmetry), each frame first brought to
+//                             a peak in [1, 2) by a power of two that its cotangent takes back; Z = 2 GP X of both frames
 //                             is made Hermitian (H[k] = Z[k]/2, H[N-k] = conj Z[k]/2, the real bins 0 and N/2 whole), packed
 //                             again as Ha + i Hb and sent through the SAME four Stockham passes on conjugated data, which
 //                             returns the two real frame gradients in the real and (negated) imaginary part.  They are
@@ -56,10 +57,19 @@ __device__ __forceinline__ float vj_gdbc(const float* __restrict__ Ds, const flo
   return gd;
 }
 
-// d dB / d mel = (10 / ln 10) / mel, mel = 10^(dB/10); amin = 1e-10 pins dB at -100 (no gradient)
+// d dB / d mel = (10 / ln 10) / mel, mel = 10^(dB/10); amin = 1e-10 pins dB at -100 (no gradient).  The exponent -d/10 is formed
+// with its rounding made good: p = fl(-0.1f d) is off by up to half a unit of a number near 10 and 0.1f by 1.5e-8 of itself, and
+// exp10 magnifies both by ln 10 |d| / 10 -- 22 units of the result at d = -95 (measured against float64).  e is the exact
+// remainder of the product plus (0.1f - 0.1) d, and 10^(p + e) = 10^p (1 + ln 10 e) to second order in e < 1e-6.
 __device__ __forceinline__ float vj_db_to_mel(float gdb, float d) {
-  return (d > -100.0f) ? gdb * (4.3429448190325175f * exp10f(-0.1f * d)) : 0.0f;
+  if (!(d > -100.0f)) return 0.0f;
+  const float p = -0.1f * d;
+  const float e = fmaf(-0.1f, d, -p) + 1.4901161e-9f * d;
+  return gdb * (4.3429448190325175f * (exp10f(p) * fmaf(2.3025851f, e, 1.0f)));
 }
+
+// the power of two that brings a frame of peak m into [1, 2) (1 for a zero frame; frames below 2^-60 are pinned at -100 dB anyway)
+__device__ __forceinline__ int vj_peak_exp(float m) { return m > 0.0f ? min(max(ilogbf(m), -60), 60) : 0; }
 
 template <bool RAGGED>
 using VjArgs = typename std::conditional<RAGGED, MfccVjpRaggedArgs, MfccVjpArgs>::type;
@@ -131,6 +141,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   __shared__ __attribute__((aligned(16))) float2 buf[kFftLds];
   __shared__ float ola[kVjSeg];
   __shared__ float gms[2][kNMels];
+  __shared__ float pk[2][4];
   const int tid = threadIdx.x, g = blockIdx.x, u = blockIdx.y;
   const int Ts = a.n_frames;  // row stride of gmel
   int T = Ts, n_y = a.n_y, n_vy = a.n_y;
@@ -172,6 +183,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       const float w = a.hann[tid + 256 * e];
       x0[e] = {w * s0, w * s1};
     }
+    // The two frames share one transform, whose rounding error is 2^-24 of the LARGER of the two spectra: a quiet frame paired with
+    // a loud one (it may lie 80 dB below it and still be above the floor) would take the loud frame's noise into its X, and its
+    // cotangent ~ 1 / |X|^2 magnifies it (measured: g_y 73 x further from float64 than a float32 evaluation frame by frame).  Each
+    // frame is brought to a peak in [1, 2) by a power of two before the transform -- exact -- and its cotangent takes the factor
+    // back.  Frames of one binade keep the bits they had.
+    float sca, scb;
+    {
+      float ma = 0.0f, mb = 0.0f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { ma = fmaxf(ma, fabsf(x0[e].re)); mb = fmaxf(mb, fabsf(x0[e].im)); }
+      ma = wave_max(ma);
+      mb = wave_max(mb);
+      if ((tid & 63) == 0) { pk[0][tid >> 6] = ma; pk[1][tid >> 6] = mb; }
+      __syncthreads();
+      const int ea = vj_peak_exp(fmaxf(fmaxf(pk[0][0], pk[0][1]), fmaxf(pk[0][2], pk[0][3])));
+      const int eb = vj_peak_exp(fmaxf(fmaxf(pk[1][0], pk[1][1]), fmaxf(pk[1][2], pk[1][3])));
+      const float na = ldexpf(1.0f, -ea), nb = ldexpf(1.0f, -eb);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { x0[e].re *= na; x0[e].im *= nb; }
+      sca = ldexpf(1.0f, ea);
+      scb = ldexpf(1.0f, eb);
+    }
     fft_pass<8, 1>(buf, 1, tid, a.tw, x0);
     __syncthreads();
     fft_pass<8, 1>(buf, 8, tid, a.tw);
@@ -201,8 +234,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const float xbr = 0.5f * (zi - wi), xbi = -0.5f * (zr - wr);
         const int m = a.bin_run[k], m1 = min(m + 1, kNMels - 1);
         const float l1 = a.mel_wlo[k], h1 = (m + 1 < kNMels) ? a.mel_whi[k] : 0.0f;
-        const float ga = l1 * gms[0][m] + h1 * gms[0][m1];
-        const float gb = l1 * gms[1][m] + h1 * gms[1][m1];
+        const float ga = (l1 * gms[0][m] + h1 * gms[0][m1]) * sca;
+        const float gb = (l1 * gms[1][m] + h1 * gms[1][m1]) * scb;
         const float ar = ga * xar, ai = ga * xai, br = gb * xbr, bi = gb * xbi;
         if (k == 0 || k == 1024) {
           buf[padi(k)] = make_float2(2.0f * ar, -2.0f * br);  // real bins: Re Z whole

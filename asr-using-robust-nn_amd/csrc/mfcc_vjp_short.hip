@@ -219,9 +219,11 @@ int launch_short_vjp(const ShortVjpArgs& a, hipStream_t st) {
   k.seg = seg;
   hipLaunchKernelGGL(dft_vjp_kernel, dim3(n_wgs), dim3(64 * a.n_tiles), lds, st, k);
   LP_LAUNCH_CHECK();
+  ++g_k1_vjp_launches[K1V_DFT];
   hipLaunchKernelGGL(dft_vjp_fold_kernel, dim3((a.n_y + 255) / 256, a.batch), dim3(256), 0, st, a.part, n_wgs, seg, a.hop, a.n_fft, a.rpc,
                      a.n_y, a.gy);
   LP_LAUNCH_CHECK();
+  ++g_k1_vjp_launches[K1V_DFT_FOLD];
   return LIPASR_OK;
 }
 

@@ -186,6 +186,9 @@ PROTOTYPES = {
     "lipasr_debug_k3_launches": (C.c_long, [i32]),
     "lipasr_debug_k1_launches": (C.c_long, [i32]),
     "lipasr_debug_mfcc_stage": (i32, [c_h, i32, i32, c_f, c_s]),
+    "lipasr_debug_k1_vjp_launches": (C.c_long, [i32]),
+    "lipasr_debug_mfcc_vjp_stage": (i32, [c_h, i32, i32, c_f, c_s]),
+    "lipasr_debug_mfcc_stage_put": (i32, [c_h, i32, i32, c_f, c_s]),
     "lipasr_debug_gemm": (i32, [c_h, i32, i32, i32, i32, i32, i32, c_f, i32, c_f, i32, c_f, i32, f32, f32, c_s]),
     "lipasr_flag_signal": (i32, [c_h, C.c_void_p, i32, c_s]),
     "lipasr_flag_wait": (i32, [c_h, C.c_void_p, i32, i32, C.c_void_p, c_s]),
@@ -208,7 +211,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_square_step_host": 660, "lipasr_hsj_expand": 670, "lipasr_hsj_accumulate": 670, "lipasr_hsj_direction": 670,
          "lipasr_hsj_search": 670, "lipasr_hsj_expand_host": 670, "lipasr_hsj_accumulate_host": 670, "lipasr_hsj_direction_host": 670,
          "lipasr_hsj_search_host": 670, "lipasr_debug_hsj_path": 670, "lipasr_room_apply": 680, "lipasr_room_vjp": 680,
-         "lipasr_room_apply_host": 680, "lipasr_room_vjp_host": 680}
+         "lipasr_room_apply_host": 680, "lipasr_room_vjp_host": 680, "lipasr_debug_k1_vjp_launches": 690,
+         "lipasr_debug_mfcc_vjp_stage": 690, "lipasr_debug_mfcc_stage_put": 690}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 

@@ -168,7 +168,9 @@ class MfccExtractor:
         """Backward pass (lipasr_mfcc_plan_vjp): the gradient w.r.t. ``sig`` of <features(sig), g_feat>.
         domain="input": sig [B, n_samp] at sr_in (what ``__call__`` takes); domain="22k": sig [B, n_y] (what ``from_22k`` takes).
         scale: the float64 StandardScaler scale the forward applied, or None.  reuse_forward=True: this extractor's last call
-        was the forward on exactly this ``sig`` on the current stream; its intermediates are read, the bits are the same.
+        was the forward on exactly this ``sig`` on the current stream; the resampled signal it left is read, and its dB tile too
+        where stft_mel2_kernel made it (stage-mask bit 256; otherwise that kernel runs again for the backward pass: the default
+        block-DFT tile is not accurate enough to divide by).  The bits are the same either way.
         2048/512 plans, float32 rows of one length: anything else raises LipasrError(EUNSUPPORTED).  Clips of different lengths
         in one launch, int16 rows and clips shorter than the reflect padding: ``vjp_ragged``; short-window extractors: ``vjp_short``."""
         dom, b, out = self._vjp_args(sig, g_feat, utterance_length, scale, domain, out, (torch.float32, torch.int16))
@@ -194,7 +196,7 @@ class MfccExtractor:
         its first ceil(n * 22050 / sr_in) positions.  sig: float32, or int16 PCM for domain="input" (the gradient is float32, with
         respect to pcm / 32768).  The gradient is exactly 0 from each clip's end to the end of its row; a clip may be as short as
         2 resampled samples, and an empty one gets zeros.  reuse_forward=True: this extractor's last call on the current stream was
-        the forward with the same rows and n_valid (``__call__`` / ``from_22k`` with n_valid).  16 kHz and 8 kHz 2048/512 plans with
+        the forward with the same rows and n_valid (``__call__`` / ``from_22k`` with n_valid); what is reused: as in ``vjp``.  16 kHz and 8 kHz 2048/512 plans with
         rows a multiple of 4 samples: anything else raises LipasrError(EUNSUPPORTED)."""
         dom, b, out = self._vjp_args(sig, g_feat, utterance_length, scale, domain, out, (torch.float32, torch.int16))
         N.check(N.lib.lipasr_mfcc_plan_vjp_ragged(self._plan, N.ptr(sig), 1 if sig.dtype == torch.int16 else 0, N.ptr(self._lengths(n_valid, b)),

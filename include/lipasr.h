@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 680. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 690. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -42,6 +42,9 @@
  * lipasr_hsj_search (one query of the start, the step-size halving or the bisection), their _host twins and lipasr_debug_hsj_path.
  * 680: the over-the-air channel: lipasr_room_apply (every clip through every room impulse response of a bank), lipasr_room_vjp (its
  * exact adjoint, summed over the rooms) and their _host twins.
+ * 690: test hooks of the MFCC backward pass: lipasr_debug_k1_vjp_launches (launch counters per kernel instance),
+ * lipasr_debug_mfcc_vjp_stage (Gmel or g_y that a plan's last backward call left behind) and lipasr_debug_mfcc_stage_put (a dB tile
+ * or frame maxima of the caller's INTO the plan, for a backward call with flags bit 0).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -889,7 +892,11 @@ int lipasr_mfcc_plan_from_22k(lipasr_mfcc_t p, const float* y, int batch, int n_
  *   affine_scale: the StandardScaler scale the forward applied (device double [20 L]) or NULL (= 1).
  *   flags bit 0: the caller ran THIS plan's forward (lipasr_mfcc_extract for domain 0, lipasr_mfcc_plan_from_22k for domain 1) on
  *     exactly this signal and batch as the plan's last call, on this stream: the plan's intermediates are read instead of
- *     re-running the forward kernels.  Same bits either way.  bit 1: the rows are int16 PCM, bit 2: the rows have per-clip
+ *     re-running the forward kernels: the resampled signal always, the dB tile and frame maxima where that forward ran the kernel
+ *     the backward pass runs for itself -- stft_mel2_kernel (stage-mask bit 256) or, on short-window plans, dft_mel_kernel.  The
+ *     default block-DFT kernel windows in the frequency domain and loses, on a frame with a loud burst under the tail of its
+ *     window, digits that 1 / mel magnifies here, and stft_mel_kernel (bit 64) sends two frames of any loudness through one
+ *     transform: their tiles are never read, and stft_mel2_kernel runs again inside the call.  Same bits either way.  bit 1: the rows are int16 PCM, bit 2: the rows have per-clip
  *     lengths -- neither has a backward pass: LIPASR_EUNSUPPORTED, as for short-window plans and clips of n_y <= 2048.
  * Every sum runs in a fixed order (no floating-point atomics): two calls give the same bits.  No host synchronisation; the
  * plan's backward workspaces are allocated by the first call (make it outside a graph capture). */
@@ -1141,6 +1148,30 @@ long lipasr_debug_k1_launches(int kernel);
  * laid out for the plan's n_frames / n_y; with per-clip lengths the frames past a clip's own count hold whatever an earlier call
  * left.  LIPASR_EINVAL for a null argument, a batch outside [1, batch_max] or another `which`.  No synchronisation, no allocation. */
 int lipasr_debug_mfcc_stage(lipasr_mfcc_t p, int which, int batch, float* out, lipasr_stream_t stream);
+
+/* Test hook: launches since the library was loaded of one kernel instance of the MFCC backward pass, counted on the host where the
+ * launch happens.  kernel: 0 / 1 mfcc_vjp_db_kernel for one length / with per-clip lengths, 2 / 3 stft_vjp_kernel likewise, 4 / 5
+ * stft_vjp_fold_kernel likewise, 6 resample_vjp_kernel with 8 outputs per thread, 7 with one output per thread (the 8-output window
+ * of g_y exceeds 60 KiB of LDS), 8 / 9 the same two forms with per-clip lengths, 10 copy_cut_kernel (22 050 Hz plans), 11
+ * dft_vjp_kernel, 12 dft_vjp_fold_kernel (short-window plans).  The forward kernels a backward call re-runs count in
+ * lipasr_debug_k1_launches.  Returns -1 for an unknown id, so a test can enumerate the instances from the library. */
+long lipasr_debug_k1_vjp_launches(int kernel);
+
+/* Test hook: ONE asynchronous device-to-device copy, on `stream`, of an intermediate that the plan's last backward call
+ * (lipasr_mfcc_plan_vjp, _vjp_ragged, _vjp_short) left in the plan, into out (device).  which 0: Gmel [batch][n_frames][128], d loss /
+ * d mel power; which 1: g_y [batch][n_y], the gradient at 22 050 Hz of a domain-0 call (a domain-1 call writes g_sig instead and
+ * leaves this array alone).  Rows are laid out for the plan's n_frames / n_y; with per-clip lengths the frames of Gmel past a clip's
+ * own count hold whatever an earlier call left.  LIPASR_EINVAL in the cases of lipasr_debug_mfcc_stage, and while the plan has no
+ * backward workspaces (they are allocated by its first backward call).  No synchronisation, no allocation. */
+int lipasr_debug_mfcc_vjp_stage(lipasr_mfcc_t p, int which, int batch, float* out, lipasr_stream_t stream);
+
+/* Test hook, the opposite direction of lipasr_debug_mfcc_stage: ONE asynchronous device-to-device copy, on `stream`, FROM in (device)
+ * INTO the plan.  which 0: the dB tile [batch][n_frames][128]; which 1: the frame maxima [batch][n_frames] (no other `which`).  A
+ * backward call with flags bit 0 reads these two arrays instead of re-running the forward (2048/512 plans: with stage-mask bit 256
+ * set, see lipasr_mfcc_plan_vjp), so a test can hand step 1 of the chain
+ * (DCT^T, top_db floor, dB -> mel) a tile with exact ties or elements exactly on the floor; the later steps recompute X from the
+ * signal and do not read the tile.  The next forward call overwrites them.  LIPASR_EINVAL as for lipasr_debug_mfcc_stage. */
+int lipasr_debug_mfcc_stage_put(lipasr_mfcc_t p, int which, int batch, const float* in, lipasr_stream_t stream);
 
 /* Profiling knob: how many of the leading (small) steps of the product chain W_m^T ... W_1^T run as ONE launch
  * (chain_head_kernel, fp32 matrix instructions): -1 = automatic (the first two steps, when their panels have <= 256 columns

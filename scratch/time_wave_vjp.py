@@ -41,12 +41,20 @@ r["fwd22"] = timed("forward from_22k (STFT+mel+dB, DCT)", lambda: ex.from_22k(y2
 r["fwd"] = timed("forward extract (resample, STFT+mel+dB, DCT)", lambda: ex(x, L, out=feat))
 r["res"] = timed("forward resample alone", lambda: ex.resample(x, out=y22))
 ex.from_22k(y22, L, out=feat)
-r["vjp22_reuse"] = timed("vjp domain 22k, reuse_forward (db + stft_vjp + fold)", lambda: ex.vjp(y22, g, L, domain="22k", reuse_forward=True, out=out22))
+r["vjp22_reuse"] = timed("vjp domain 22k, reuse_forward (STFT re-run + db + stft_vjp + fold)", lambda: ex.vjp(y22, g, L, domain="22k", reuse_forward=True, out=out22))
 r["vjp22"] = timed("vjp domain 22k, forward re-run", lambda: ex.vjp(y22, g, L, domain="22k", out=out22))
 r["rvjp"] = timed("resample_vjp alone", lambda: ex.resample_vjp(gy, out=outx))
 ex(x, L, out=feat)
-r["vjp0_reuse"] = timed("vjp domain input, reuse_forward (+ resample_vjp)", lambda: ex.vjp(x, g, L, domain="input", reuse_forward=True, out=outx))
+r["vjp0_reuse"] = timed("vjp domain input, reuse_forward (d_y reused; + resample_vjp)", lambda: ex.vjp(x, g, L, domain="input", reuse_forward=True, out=outx))
 r["vjp0"] = timed("vjp domain input, forward re-run", lambda: ex.vjp(x, g, L, domain="input", out=outx))
+# a plan whose forward is stft_mel2_kernel (stage-mask bit 256): the one 2048/512 forward whose tile flags bit 0 reuses
+ex.set(0, 256)
+r["fwd22_m"] = timed("mask 256: forward from_22k (stft_mel2_kernel, DCT)", lambda: ex.from_22k(y22, L, out=feat))
+ex.from_22k(y22, L, out=feat)
+r["vjp22_reuse_m"] = timed("mask 256: vjp domain 22k, reuse_forward (tile reused)", lambda: ex.vjp(y22, g, L, domain="22k", reuse_forward=True, out=out22))
+ex(x, L, out=feat)
+r["vjp0_reuse_m"] = timed("mask 256: vjp domain input, reuse_forward (tile reused)", lambda: ex.vjp(x, g, L, domain="input", reuse_forward=True, out=outx))
+ex.set(0, 0)
 h = N.get_handle(0)
 for dom, x0 in (("22k", y22.clone()), ("input", x.clone())):
     clf = A.WaveformClassifier(m, 10, extractor=ex, utterance_length=L, domain=dom)

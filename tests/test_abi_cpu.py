@@ -54,6 +54,19 @@ def test_k1_launch_counters_and_stage_hook_without_gpu():
     assert "null argument" in N.last_error()
 
 
+def test_k1_backward_hooks_without_gpu():
+    """lipasr_debug_k1_vjp_launches, lipasr_debug_mfcc_vjp_stage and lipasr_debug_mfcc_stage_put (version 690): exported; the counters
+    are host-side, -1 for an id that does not exist, and the known ids are exactly 0..12 as include/lipasr.h lists them; the two copy
+    hooks refuse a null plan before they touch a device."""
+    names = ("lipasr_debug_k1_vjp_launches", "lipasr_debug_mfcc_vjp_stage", "lipasr_debug_mfcc_stage_put")
+    assert N.lib.lipasr_version() >= 690 and all(N.has(n) and hasattr(N.lib, n) and N.SINCE[n] == 690 for n in names)
+    assert N.lib.lipasr_debug_k1_vjp_launches(-1) == -1 and N.lib.lipasr_debug_k1_vjp_launches(13) == -1
+    assert [k for k in range(64) if N.lib.lipasr_debug_k1_vjp_launches(k) >= 0] == list(range(13))
+    for fn in (N.lib.lipasr_debug_mfcc_vjp_stage, N.lib.lipasr_debug_mfcc_stage_put):
+        assert fn(None, 0, 1, None, None) == N.EINVAL
+        assert "null argument" in N.last_error()
+
+
 def test_error_convention_without_gpu():
     assert N.lib.lipasr_create(0, None) == N.EINVAL
     assert "out is null" in N.last_error()
