@@ -135,6 +135,14 @@ PROTOTYPES = {
     "lipasr_room_vjp": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, f32, c_f, c_s]),
     "lipasr_room_apply_host": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
     "lipasr_room_vjp_host": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, f32, c_f]),
+    "lipasr_universal_shifts": (i32, [c_h, i32, i32, C.c_uint32, C.c_uint32, u64, c_f, c_s]),
+    "lipasr_universal_apply": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, i32, f32, f32, c_f, c_s]),
+    "lipasr_universal_reduce": (i32, [c_h, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
+    "lipasr_universal_step": (i32, [c_h, c_f, c_f, i32, i32, f32, f32, f32, c_s]),
+    "lipasr_universal_shifts_host": (i32, [i32, i32, C.c_uint32, C.c_uint32, u64, c_f]),
+    "lipasr_universal_apply_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, f32, f32, c_f]),
+    "lipasr_universal_reduce_host": (i32, [c_f, c_f, c_f, i32, i32, i32, c_f]),
+    "lipasr_universal_step_host": (i32, [c_f, c_f, i32, i32, f32, f32, f32]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -212,7 +220,10 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_hsj_search": 670, "lipasr_hsj_expand_host": 670, "lipasr_hsj_accumulate_host": 670, "lipasr_hsj_direction_host": 670,
          "lipasr_hsj_search_host": 670, "lipasr_debug_hsj_path": 670, "lipasr_room_apply": 680, "lipasr_room_vjp": 680,
          "lipasr_room_apply_host": 680, "lipasr_room_vjp_host": 680, "lipasr_debug_k1_vjp_launches": 690,
-         "lipasr_debug_mfcc_vjp_stage": 690, "lipasr_debug_mfcc_stage_put": 690}
+         "lipasr_debug_mfcc_vjp_stage": 690, "lipasr_debug_mfcc_stage_put": 690, "lipasr_universal_shifts": 700,
+         "lipasr_universal_apply": 700, "lipasr_universal_reduce": 700, "lipasr_universal_step": 700,
+         "lipasr_universal_shifts_host": 700, "lipasr_universal_apply_host": 700, "lipasr_universal_reduce_host": 700,
+         "lipasr_universal_step_host": 700}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -651,6 +662,65 @@ def room_vjp_host(g, rirs, *, n_valid=None, scale=1.0, out=None):
     check(lib.lipasr_room_vjp_host(C.c_void_p(g.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data),
                                    C.c_void_p(rirs.ctypes.data), taps, r, b, n, float(scale), _host_array(out, np.float32, (b, n), "out")))
     return out
+
+
+UNIVERSAL_GROUP = 64  # LIPASR_UNIVERSAL_GROUP: the rows one slab of lipasr_universal_reduce's sums holds
+
+
+def _vp(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def universal_shifts_host(batch, P, it, seed, *, clip0=0, out=None):
+    """Host-only: lipasr_universal_shifts_host -> int32 [batch], the shifts of rows clip0 .. clip0 + batch - 1 at iteration ``it``."""
+    import numpy as np
+
+    batch = int(batch)
+    out = np.zeros(max(batch, 0), dtype=np.int32) if out is None else out
+    check(lib.lipasr_universal_shifts_host(batch, int(P), int(clip0), int(it), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           _host_array(out, np.int32, (max(batch, 0),), "out")))
+    return out
+
+
+def universal_apply_host(x, noise, *, offs=None, n_valid=None, clip_lo=-float("inf"), clip_hi=float("inf"), out=None):
+    """Host-only: lipasr_universal_apply_host on NumPy arrays (x float32 [B, n], noise float32 [P]) -> float32 [B, n]."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    b, n = x.shape
+    noise = np.ascontiguousarray(noise, dtype=np.float32).reshape(-1)
+    of = None if offs is None else _host_in(offs, np.int32, (b,), "offs")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    out = np.zeros((b, n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_universal_apply_host(_vp(x), _vp(noise), _vp(of), _vp(nv), b, n, noise.shape[0], float(clip_lo), float(clip_hi),
+                                          _host_array(out, np.float32, (b, n), "out")))
+    return out
+
+
+def universal_reduce_host(g, P, *, offs=None, n_valid=None, sums=None):
+    """Host-only: lipasr_universal_reduce_host on NumPy arrays (g float32 [B, n]) -> float64 [ceil(B / 64), P]."""
+    import numpy as np
+
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    b, n = g.shape
+    P = int(P)
+    groups = (b + UNIVERSAL_GROUP - 1) // UNIVERSAL_GROUP
+    of = None if offs is None else _host_in(offs, np.int32, (b,), "offs")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    sums = np.zeros((groups, max(P, 0)), dtype=np.float64) if sums is None else sums
+    check(lib.lipasr_universal_reduce_host(_vp(g), _vp(of), _vp(nv), b, n, P, _host_array(sums, np.float64, (groups, max(P, 0)), "sums")))
+    return sums
+
+
+def universal_step_host(noise, sums, norm, alpha, eps):
+    """Host-only: lipasr_universal_step_host, in place on noise float32 [P]; sums float64 [groups, P]."""
+    import numpy as np
+
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    groups, P = sums.shape
+    check(lib.lipasr_universal_step_host(_host_array(noise, np.float32, (P,), "noise"), _vp(sums), groups, P, _norm_f(norm), float(alpha),
+                                         float(eps)))
+    return noise
 
 
 def debug_table(which: int, sr_in: int = 16000):

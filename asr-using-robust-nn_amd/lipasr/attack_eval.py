@@ -21,6 +21,8 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: randomized smoothing, CERTIFY per clip)    attack="smooth":smooth_report over="mfcc" | "audio", --sigma S [--n0 --n --alpha]
     (no prompt: the attack played in a room, EOT)          attack="white" | "black", over="audio", --room R [--room-taps --room-t60 LO HI --room-seed]:
                                                            over_the_air_sweep, kind="fgsm" | "pgd" | "apgd" | "auto" | "genetic" | "square"
+    (no prompt: one noise vector for every clip)           attack="white", kind="universal", --norm inf | 2, over="mfcc" | "audio" [--shift --length P
+                                                           --max-iter E --room R]: universal_sweep, fitted on one half, heard on the other
 """
 from __future__ import annotations
 
@@ -443,6 +445,76 @@ def over_the_air_sweep(models, train_data, val_data, test_data, test_labels, tes
     return grid, {name: {k: np.asarray(v) for k, v in d.items()} for name, d in acc.items()}
 
 
+def universal_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
+                    domain="22k", norm=np.inf, rooms=None, room_taps=2048, room_t60=(0.15, 0.5), room_seed=0, grid=None, points=None,
+                    limit=None, **attack_kw):
+    """ONE perturbation for every clip (lipasr.attacks.UniversalPerturbation) against its radius eps.  Per model and eps the noise
+    is FITTED on the first half of the test rows (over="audio": of every batch of files that share a rate and a row length, since a
+    noise vector has one period) from the model's own predictions, and the accuracy is that of the SECOND half with that noise
+    added -- rows the fit never saw: the generalisation that makes the perturbation universal.  Next to it: the fooling rate on the
+    fitting half.  Rows, standardisation (standardize="before" only: the noise lives on the rows the models see) and grids as in
+    white_box_sweep: its FGSM grid (norm inf) or PGD grid (norm 2) over MFCC rows, AUDIO_SIGMAS without the 0 over audio.
+    ``rooms`` (over="audio"): the fit runs through a bank of that many synthetic rooms (OverTheAirClassifier) and the held-out
+    half is heard through a disjoint bank, as over_the_air_sweep does.  ``attack_kw``: UniversalPerturbation's keywords (max_iter,
+    length, random_shift, eps_step, delta, ...).  Returns (grid, {model name: held-out accuracies}, {model name: fooling rates
+    of the fitting half})."""
+    if norm not in (2, 2.0, np.inf):
+        raise ValueError(f"norm = {norm!r}: UniversalPerturbation runs in norm 2 or inf")
+    if standardize != "before":
+        raise ValueError("universal_sweep fits the noise on the rows the models see: standardize='before'")
+    if rooms is not None and over != "audio":
+        raise ValueError("rooms= goes with over='audio'")
+    rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
+    truth = np.asarray(rows.limited(test_labels)).argmax(axis=1)
+    if over == "audio":
+        default = AUDIO_SIGMAS[1:]
+    else:
+        default = np.linspace(0.01, 0.3, 10) if norm == np.inf else np.linspace(1, 30, 50)
+    grid = list(default if grid is None else grid)[:points]
+    banks = {}
+
+    def through(clf, sr):
+        """(the estimator the noise is fitted over, the one the held-out rows are heard through)"""
+        if rooms is None:
+            return clf, clf
+        from .room import RoomChannel, synthetic_rirs
+
+        rate = 22050 if domain == "22k" else int(sr)
+        if rate not in banks:
+            h = synthetic_rirs(2 * int(rooms), sr=rate, taps=room_taps, t60=room_t60, seed=room_seed)
+            banks[rate] = (RoomChannel(h[:int(rooms)]), RoomChannel(h[int(rooms):]))
+        return A.OverTheAirClassifier(clf, banks[rate][0]), A.OverTheAirClassifier(clf, banks[rate][1])
+
+    acc, fooled = {name: [] for name in models}, {name: [] for name in models}
+    for item in grid:
+        for name, model in models.items():
+            hits, seen, rate_sum, fitted = 0, 0, 0.0, 0
+            rates = [sr for sr, _, _, _ in rows._work] if over == "audio" else [None]
+            for sr, (clf, x, lt, idx) in zip(rates, rows.batches(model)):
+                xt = clf.rows_device(x)
+                half = xt.shape[0] // 2
+                if half == 0:
+                    continue
+                idx = np.arange(rows.n)[idx]
+                cut = lambda t, s: None if t is None else t[s]
+                fit_clf, hear_clf = through(clf, sr)
+                atk = A.UniversalPerturbation(fit_clf, eps=item, norm=norm, **attack_kw)
+                atk.generate_device(xt[:half].contiguous(), None, lengths=cut(lt, slice(0, half)))
+                held = atk.apply(xt[half:].contiguous(), lengths=cut(lt, slice(half, None)))
+                pred = hear_clf.predict_device(held, logits=True, lengths=cut(lt, slice(half, None))).argmax(dim=1).cpu().numpy()
+                hits += int((pred == truth[idx[half:]]).sum())
+                seen += len(pred)
+                rate_sum += atk.fooling_rate * half
+                fitted += half
+            a = hits / seen if seen else float("nan")
+            f = rate_sum / fitted if fitted else float("nan")
+            acc[name].append(a)
+            fooled[name].append(f)
+            print(f"Accuracy on held-out {'audio ' if over == 'audio' else ''}test examples under a universal perturbation{_tag(name)}: "
+                  f"{a * 100}% ({item}); fooling rate on the {fitted} fitting {rows.what}: {f * 100}%")
+    return grid, {k: np.asarray(v) for k, v in acc.items()}, {k: np.asarray(v) for k, v in fooled.items()}
+
+
 def build_or_keep(build, clf, item, x, lt):
     """The attack ``build(clf, item)`` on the rows ``x``, or the rows themselves at strength 0."""
     return build(clf, item).generate_device(x, None, lengths=lt) if item != 0 else x
@@ -676,13 +748,13 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square|hsj; white: fgsm|l2|linf|pgd|apgd|auto|jsma|imperceptible")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square|hsj; white: fgsm|l2|linf|pgd|apgd|auto|universal|jsma|imperceptible")
     ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
-    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); black square: queries per clip (default: SquareAttack's); white apgd: iterations (default: 100)")
+    ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); black square: queries per clip (default: SquareAttack's); white apgd: iterations (default: 100); white universal: passes over the fitting rows at most (default: UniversalPerturbation's)")
     ap.add_argument("--loss", choices=["ce", "dlr"], default="ce", help="white apgd: cross-entropy or the Difference-of-Logits-Ratio loss")
     ap.add_argument("--over", choices=["audio", "mfcc"], default="mfcc")
     ap.add_argument("--points", type=int, default=None, help="keep only the first N grid points (white imperceptible: the first N files)")
-    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; white apgd, auto and radius: 2 or inf")
+    ap.add_argument("--norm", choices=["inf", "1", "2"], default="inf", help="white fgsm|pgd: ART's norm keyword; white apgd, auto, universal and radius: 2 or inf")
     ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
     ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
     ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
@@ -694,12 +766,17 @@ def main(argv=None):
     ap.add_argument("--room-taps", type=int, default=2048, help="--room: samples of each room impulse response")
     ap.add_argument("--room-t60", type=float, nargs=2, default=(0.15, 0.5), metavar=("LO", "HI"), help="--room: range of the reverberation time in seconds")
     ap.add_argument("--room-seed", type=int, default=0, help="--room: seed of the two banks")
+    ap.add_argument("--shift", action="store_true", help="white universal: every clip meets the noise at a random offset")
+    ap.add_argument("--length", type=int, default=None, help="white universal: the period of the noise in positions of a row (default: the row width)")
     ap.add_argument("--max-iter-1", type=int, default=1000)
     ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
     if args.attack == "radius" and args.norm == "1":
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
-    if args.attack == "white" and args.kind in ("apgd", "auto") and args.norm == "1":
+    universal = args.attack == "white" and args.kind == "universal"
+    if (args.shift or args.length is not None) and not universal:
+        raise ValueError("--shift and --length go with --kind universal")
+    if args.attack == "white" and args.kind in ("apgd", "auto", "universal") and args.norm == "1":
         raise ValueError(f"--kind {args.kind} runs in --norm inf or 2")
     if args.attack == "black" and args.kind == "hsj" and args.norm == "1":
         raise ValueError("--kind hsj runs in --norm inf or 2")
@@ -714,6 +791,13 @@ def main(argv=None):
     names = None
     if args.over == "audio" or args.attack == "dolphin":
         names, labels = _noise_files(args.noise_dir, n_classes)
+    if universal:
+        if args.room is not None and args.over != "audio":
+            raise ValueError("--room goes with --attack white or black and --over audio")
+        kw = {k: v for k, v in (("max_iter", args.max_iter), ("length", args.length)) if v is not None}
+        return universal_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
+                               test_filenames=names, norm=np.inf if args.norm == "inf" else 2, rooms=args.room, room_taps=args.room_taps,
+                               room_t60=tuple(args.room_t60), room_seed=args.room_seed, points=args.points, random_shift=args.shift, **kw)
     if args.room is not None:
         if args.attack not in ("white", "black") or args.over != "audio":
             raise ValueError("--room goes with --attack white or black and --over audio")

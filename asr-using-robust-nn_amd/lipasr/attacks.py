@@ -28,6 +28,8 @@ model's answer: a genetic algorithm with pop_size score queries per generation, 
 L-inf distance to the nearest misclassified point it can find.
 ``AutoAttack`` (ART's name) runs Auto-PGD with both losses, DeepFool and SquareAttack in turn over the rows that are still
 classified correctly and reports the accuracy that survives all of them.
+``UniversalPerturbation`` (lipasr/universal.py; ART's name, Moosavi-Dezfooli et al. 2017) fits ONE noise vector for every row --
+the only attack here whose kernels sum across the rows of a batch -- and applies it to rows it never saw.
 """
 from __future__ import annotations
 
@@ -44,6 +46,7 @@ from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack:
 from .keras import to_categorical
 from .square import SquareAttack  # noqa: F401  (Square Attack: one score query per iteration; lipasr/square.py)
 from .hopskipjump import HopSkipJump  # noqa: F401  (HopSkipJump: decisions only, minimum L2 / L-inf norm; lipasr/hopskipjump.py)
+from .universal import UniversalPerturbation  # noqa: F401  (one noise vector for every row; lipasr/universal.py)
 
 
 # ------------------------------------------------------------------------------------------------ A2

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 690. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 700. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -45,6 +45,9 @@
  * 690: test hooks of the MFCC backward pass: lipasr_debug_k1_vjp_launches (launch counters per kernel instance),
  * lipasr_debug_mfcc_vjp_stage (Gmel or g_y that a plan's last backward call left behind) and lipasr_debug_mfcc_stage_put (a dB tile
  * or frame maxima of the caller's INTO the plan, for a backward call with flags bit 0).
+ * 700: universal adversarial perturbations: lipasr_universal_shifts (a shift per row), lipasr_universal_apply (one noise vector on
+ * every row), lipasr_universal_reduce (the gradient rows summed back onto the noise, in fp64 and in a fixed order),
+ * lipasr_universal_step (the step and projection of the noise) and their _host twins.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -788,6 +791,64 @@ int lipasr_room_apply_host(const float* x, const int* n_valid, const float* rirs
                            float* out);
 int lipasr_room_vjp_host(const float* g, const int* n_valid, const float* rirs, int taps, int rir_count, int clips, int n,
                          float scale, float* gx);
+
+/* Universal adversarial perturbations (lipasr/universal.py, attacks.UniversalPerturbation; ART's UniversalPerturbation in its
+ * minibatch form): ONE perturbation `noise`, float32 [P], shared by every row of a batch.  Its period P >= 1 may equal the row
+ * width n, be shorter (the snippet loops) or longer (a row sees a window of it).  offs [batch] (int32, or NULL: all zero) is a
+ * shift per row: position k of row b is paired with noise[(k + offs[b]) mod P].  0 <= offs[b] < P is the caller's promise; the
+ * kernels reduce ((offs[b] % P) + P) % P all the same, so that no value indexes outside noise.  n_valid [batch] (or NULL: n) holds
+ * POSITIONS IN THE ROW, clamped to [0, n]; nv_b below is the clamped value.  Limits: batch <= 65535, n <= 2^17, P <= 2^17, else
+ * LIPASR_EINVAL.  Every entry point refuses a null pointer (offs and n_valid excepted) before the device is touched, returns
+ * LIPASR_OK with nothing written when batch, n or P is 0 (lipasr_universal_step: groups or P), allocates nothing and synchronises
+ * nothing.  No atomics anywhere: two runs give the same bits. */
+#define LIPASR_UNIVERSAL_GROUP 64 /* the rows whose sum one slab of lipasr_universal_reduce's output holds */
+
+/* The shifts of rows clip0 .. clip0 + batch - 1 at iteration `it`, one launch: o = Philox4x32-10 with key `seed` and the counter
+ * words (clip0 + b, 0, it, 0x554E4956), offs_out[b] = (uint64(o[0]) * P) >> 32, in [0, P).  A pure function of (seed, clip0 + b,
+ * it, P): chunks at any clip0 reproduce one big call bit for bit. */
+int lipasr_universal_shifts(lipasr_handle_t h, int batch, int P, uint32_t clip0, uint32_t it, uint64_t seed, int* offs_out /* [batch] */,
+                            lipasr_stream_t stream);
+
+/* out[b][k] = clamp(x[b][k] + noise[(k + offs[b]) mod P], clip_lo, clip_hi) for k < nv_b -- one fp32 add, then
+ * v < lo ? lo : (v > hi ? hi : v), so that a NaN stays -- and the bits of x[b][k] for k >= nv_b.  One launch; every access is a single
+ * float, consecutive lanes consecutive positions: any n, any alignment, one instance, so no value depends on the alignment.  out must overlap neither x nor noise, and clip_lo <= clip_hi, else LIPASR_EINVAL. */
+int lipasr_universal_apply(lipasr_handle_t h, const float* x /* [batch][n] */, const float* noise /* [P] */, const int* offs,
+                           const int* n_valid, int batch, int n, int P, float clip_lo, float clip_hi, float* out /* [batch][n] */,
+                           lipasr_stream_t stream);
+
+/* The adjoint of the broadcast, and the hot path: the gradient rows g [batch][n] summed back onto the period.  sums is
+ * double [G][P], G = ceil(batch / LIPASR_UNIVERSAL_GROUP); it is WRITTEN, not added to (no memset).  sums[grp][p] is the fp64
+ * sum, started at +0.0, of (double)g[b][k] over the rows b of group grp in ascending b and, within a row, over the positions
+ * k < nv_b with (k + offs[b]) mod P == p in ascending k; a NaN entry counts as 0 (as in lipasr_lp_step).  Pure fp64 additions in
+ * an order that is a function of (batch, P) alone -- never of the grid, the CU count or the alignment -- so the result is the
+ * same bits on every run, the bits of the host twin and of a float64 loop in the stated order, and minibatches cut at multiples
+ * of LIPASR_UNIVERSAL_GROUP give the slabs of one big call.  One launch of G x ceil(P / 256) independent workgroups: a lane owns one
+ * period position and reads every row of its group as coalesced dwords from (p - offs[b]) mod P in strides of P.  sums must not
+ * overlap g. */
+int lipasr_universal_reduce(lipasr_handle_t h, const float* g /* [batch][n] */, const int* offs, const int* n_valid, int batch, int n,
+                            int P, double* sums /* [G][P] */, lipasr_stream_t stream);
+
+/* One step of the noise, in place.  G[p] = sum over grp of sums[grp][p], in ascending grp, in fp64.  `norm` is 2.0f or +INFINITY,
+ * else LIPASR_EINVAL; alpha finite (a negative alpha descends: the targeted attack); eps >= 0, +inf: no projection.
+ *   inf: noise[p] = clamp(noise[p] + alpha * sign(G[p]), -eps, eps), sign(0) = sign(NaN) = 0: the product is +-alpha or +-0 exactly,
+ *        so this is all fp32 and exact.  Element-wise, ceil(P / 256) workgroups.
+ *   2:   N = sqrt(sum_p G[p]^2) in fp64; d'[p] = noise[p] + (alpha * G[p]) / (N + 1e-7) in fp64, or noise[p] where N is not finite
+ *        (such a call takes no step and only projects); M = sqrt(sum_p d'[p]^2); r = eps / (M + 1e-7);
+ *        noise[p] = (float)(d'[p] * (r < 1 ? r : 1)), the factor being 1 under eps = +inf.  ONE launch of ONE workgroup of 1024
+ *        threads: thread t adds its terms p = t, t + 1024, ... in ascending order into one fp64 partial, and the partials meet
+ *        in block_sum_d's order (a butterfly per wavefront, then the 16 wavefronts in index order).  A second launch would cost
+ *        more than the three passes one workgroup makes over P <= 2^17 positions whose partials sit in L2.
+ * groups <= ceil(65535 / LIPASR_UNIVERSAL_GROUP); noise must not overlap sums. */
+int lipasr_universal_step(lipasr_handle_t h, float* noise /* [P] */, const double* sums /* [groups][P] */, int groups, int P, float norm,
+                          float alpha, float eps, lipasr_stream_t stream);
+
+/* Host-only (no GPU needed): the same inline functions in plain loops, the same checks.  The same bits as the device entry
+ * points everywhere except the norm-2 sums of lipasr_universal_step, which the host adds in ascending p. */
+int lipasr_universal_shifts_host(int batch, int P, uint32_t clip0, uint32_t it, uint64_t seed, int* offs_out);
+int lipasr_universal_apply_host(const float* x, const float* noise, const int* offs, const int* n_valid, int batch, int n, int P,
+                                float clip_lo, float clip_hi, float* out);
+int lipasr_universal_reduce_host(const float* g, const int* offs, const int* n_valid, int batch, int n, int P, double* sums);
+int lipasr_universal_step_host(float* noise, const double* sums, int groups, int P, float norm, float alpha, float eps);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
