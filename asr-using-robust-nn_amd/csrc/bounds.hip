@@ -1,0 +1,1022 @@
+// Certified robustness of the dense classifier by bound propagation (lipasr/bounds.py): interval bounds (IBP) forward through the
+// layers, one backward linear-relaxation pass (CROWN-IBP) for the margins z_y - z_k.  DESIGN.md, "Bound propagation", derives every
+// constant below.
+//
+//   bounds_prep_kernel   1 launch   the input box [x - eps_b, x + eps_b] /\ [clip_lo, clip_hi] rounded outward, the row's NaN flag,
+//                                   and (norm 2) the column norms of W_1
+//   bounds_layer_kernel  L - 1      one hidden layer: a 32 x 128 tile of (W c, |W| r, |W| |c|) from ONE read of W on
+//                                   v_mfma_f32_32x32x2_f32, three accumulators per wavefront (48 accumulator registers), |W| and |c|
+//                                   formed in registers, the next chunk's loads in flight during the MFMAs; epilogue: bias, widening, store (lo_z, hi_z, S), ReLU, BatchNorm affine with
+//                                   the sign of s, outward rounding, store the next (lo, hi)
+//   bounds_head_kernel   1          Lambda_L[b][k] = W_L[y_b] - W_L[k], the IBP margins, and the relaxation of layer L - 1
+//   bounds_back_kernel   L - 1      Lambda_{l-1} = Lambda_l W_l^T for M = batch x classes rows on the same tile; epilogue: layer
+//                                   l - 1's BatchNorm and ReLU relaxation from row b = m / C's bounds, the constant and the slack of
+//                                   the row's 32 columns as ONE partial each (a butterfly over the 32 lanes: fixed order, no atomics)
+//   bounds_tail_kernel   1          the input reduction, the partials in index order, margin_crown and slack
+//
+// Forward L + 1 launches, backward L (none when margin_crown is null).  Every sum has one order that depends on the shapes alone:
+// the MFMA is an fmaf chain in ascending k, a row's constant is the butterfly of each 32-column tile, then the tiles in ascending
+// order, then the stages top-down.  The host twin runs the same inline functions in those orders, so host and device give the
+// same values (a zero may differ in sign: the padded k steps of a tile turn a -0 accumulator into +0).
+// Rows are independent everywhere, so a NaN stays in its row; the flag of bounds_prep_kernel makes such a row's margins NaN.
+// Loads and stores are single floats, guarded: any width, any batch, any alignment.  Nothing allocates or synchronises.
+#include "common.h"
+#include "row.h"
+#include "mlp.h"
+
+// host and device must round alike, and a product that is rounded before its sum is what the error bounds below assume
+#pragma clang fp contract(off)
+
+namespace lipasr {
+
+typedef float bd_f32x16 __attribute__((ext_vector_type(16)));
+
+long g_bounds_launches[5] = {};
+enum { BD_PREP = 0, BD_LAYER = 1, BD_HEAD = 2, BD_BACK = 3, BD_TAIL = 4 };
+
+constexpr int kBdMaxWidth = 4096;                  // (width + 2) 2^-53 <= kBdD / 2 and gamma_{width + 1} << 1
+constexpr double kBdU = 5.9604644775390625e-08;    // 2^-24, the unit roundoff of fp32
+constexpr double kBdTiny = 1.401298464324817e-45;  // 2^-149, the smallest fp32 subnormal
+constexpr double kBdD = 9.094947017729282e-13;     // 2^-40: covers every fp64 rounding of a sum of <= 4096 + 2 terms
+
+#define BD_HD __host__ __device__ __forceinline__
+
+BD_HD unsigned bd_bits(float f) { return __builtin_bit_cast(unsigned, f); }
+BD_HD float bd_float(unsigned u) { return __builtin_bit_cast(float, u); }
+// the next fp32 above / below; a NaN and the infinity on that side stay
+BD_HD float bd_step_up(float f) {
+  if (f != f || f == INFINITY) return f;
+  if (f == 0.0f) return bd_float(1u);
+  const unsigned u = bd_bits(f);
+  return bd_float(f > 0.0f ? u + 1u : u - 1u);
+}
+BD_HD float bd_step_dn(float f) {
+  if (f != f || f == -INFINITY) return f;
+  if (f == 0.0f) return bd_float(0x80000001u);
+  const unsigned u = bd_bits(f);
+  return bd_float(f > 0.0f ? u - 1u : u + 1u);
+}
+// the largest fp32 <= v / the smallest fp32 >= v
+BD_HD float bd_dn(double v) {
+  const float f = (float)v;
+  return (double)f > v ? bd_step_dn(f) : f;
+}
+BD_HD float bd_up(double v) {
+  const float f = (float)v;
+  return (double)f < v ? bd_step_up(f) : f;
+}
+BD_HD double bd_max(double a, double b) { return a < b ? b : a; }
+BD_HD double bd_gamma(int n) { return n * kBdU / (1.0 - n * kBdU); }
+// what an fmaf chain of K products plus the bias can be off by, given S >= sum of the magnitudes: two chains meet in one bound
+BD_HD double bd_widen(int K, double S) { return bd_gamma(K + 1) * S + 2.0 * (K + 1) * kBdTiny; }
+
+// h = s relu(z) + t in inference mode; tm bounds the magnitudes t was made of
+struct BdAff { double s, t, tm; };
+BD_HD BdAff bd_aff(const float* gamma, const float* beta, const float* mmean, const float* mvar, int j) {
+  if (!gamma) return BdAff{1.0, 0.0, 0.0};
+  const double s = (double)gamma[j] / sqrt((double)mvar[j] + (double)kBnEps);
+  const double sm = s * (double)mmean[j];
+  return BdAff{s, (double)beta[j] - sm, fabs((double)beta[j]) + fabs(sm)};
+}
+
+// the input box of one element: [x - eps, x + eps] /\ [clip_lo, clip_hi], rounded outward (exact at eps = 0)
+BD_HD void bd_input_box(float x, float eps, float clip_lo, float clip_hi, float& lo, float& hi) {
+  if (eps == 0.0f) {
+    lo = hi = x;
+  } else {
+    const double d = kBdD * (fabs((double)x) + (double)eps);
+    lo = bd_dn((double)x - (double)eps - d);
+    hi = bd_up((double)x + (double)eps + d);
+  }
+  if (lo < clip_lo) lo = clip_lo;
+  if (hi > clip_hi) hi = clip_hi;
+}
+
+// centre and radius with [c - r, c + r] a superset of [lo, hi]
+BD_HD void bd_mid_rad(float lo, float hi, float& c, float& r) {
+  if (lo == hi) { c = lo; r = 0.0f; return; }
+  const double dl = lo, dh = hi;
+  c = (float)(0.5 * (dl + dh));
+  const double dc = c;
+  r = bd_up(bd_max(dh - dc, dc - dl) + kBdD * (fabs(dl) + fabs(dh)));
+  if (r < 0.0f) r = 0.0f;  // an empty box (the clip box does not meet the ball)
+}
+// norm 2, first layer: the centre stays x, the radius covers the box on both sides
+BD_HD void bd_sym_rad(float x, float lo, float hi, float& c, float& r) {
+  c = x;
+  if (lo == hi && lo == x) { r = 0.0f; return; }
+  const double dx = x;
+  r = bd_up(bd_max((double)hi - dx, dx - (double)lo) + kBdD * (fabs((double)lo) + fabs((double)hi) + fabs(dx)));
+  if (r < 0.0f) r = 0.0f;
+}
+
+// one pre-activation box from the three sums of a column: ac = fl(W c), ar = fl(|W| r), as = fl(|W| |c|)
+BD_HD void bd_z_box(float ac, float ar, float as, float bias, int K, bool l2, float eps, float colnorm, float& zlo, float& zhi,
+                    float& S) {
+  const double g = bd_gamma(K + 1);
+  S = bd_up((((double)as + (double)ar) * (1.0 + 2.0 * g) + fabs((double)bias) + 2.0 * (K + 1) * kBdTiny) * (1.0 + kBdD));
+  const double w = bd_widen(K, (double)S);
+  double rad = ar;
+  if (l2) {
+    const double r2 = (double)eps * (double)colnorm * (1.0 + kBdD);
+    if (r2 < rad) rad = r2;
+  }
+  const double zc = (double)ac + (double)bias;
+  zlo = bd_dn(zc - rad - w);
+  zhi = bd_up(zc + rad + w);
+}
+
+// ReLU, then the affine map with lo and hi swapped where s < 0, rounded outward.  v < 0 ? 0 : v keeps a NaN.
+BD_HD void bd_post_box(float zlo, float zhi, const BdAff& a, float& hlo, float& hhi) {
+  const double alo = zlo < 0.0f ? 0.0 : (double)zlo, ahi = zhi < 0.0f ? 0.0 : (double)zhi;
+  const double d = kBdD * (fabs(a.s) * ahi + a.tm);
+  const double vlo = a.s >= 0.0 ? a.s * alo + a.t : a.s * ahi + a.t;
+  const double vhi = a.s >= 0.0 ? a.s * ahi + a.t : a.s * alo + a.t;
+  hlo = bd_dn(vlo - d);
+  hhi = bd_up(vhi + d);
+}
+
+// Lambda on h_j = s relu(z_j) + t becomes nu on z_j: dc goes to the row's constant, ds to its slack.
+//   lam       the coefficient as stored (fp32); kin: the K of the product that made it (0: none), whose subnormal term sits here
+//   zlo, zhi  the pre-activation box of the row, S its sum of magnitudes, bias the b_j of z_j = (W h)_j + b_j; kout: the K of the
+//             product nu goes into
+BD_HD void bd_relax(float lam, const BdAff& a, float zlo, float zhi, float S, float bias, int kin, int kout, float& nu, double& dc,
+                    double& ds) {
+  const double p = (double)lam * a.s;
+  const double ahi = zhi < 0.0f ? 0.0 : (double)zhi;
+  const double Z = bd_max(fabs((double)zlo), fabs((double)zhi));
+  double slope, icpt = 0.0;
+  if (zhi <= 0.0f) {
+    slope = 0.0;
+  } else if (zlo >= 0.0f) {
+    slope = 1.0;
+  } else if (p < 0.0) {
+    // the upper line: any slope >= hi / (hi - lo) lies above relu on [lo, hi]
+    slope = (double)zhi / ((double)zhi - (double)zlo) * (1.0 + kBdD);
+    icpt = -(p * slope * (double)zlo) * (1.0 + kBdD);  // <= 0, rounded away from 0
+  } else {
+    slope = zhi >= -zlo ? 1.0 : 0.0;
+  }
+  nu = (float)(p * slope);
+  const double lt = (double)lam * a.t, nb = (double)nu * (double)bias;
+  dc = lt + icpt + nb;
+  ds = kBdD * (fabs(lt) + fabs((double)lam) * a.tm + fabs(icpt) + fabs(nb))  // fp64 roundings of t and of the three terms
+       + (2.0 * kBdU * fabs((double)nu) + kBdTiny) * Z                        // nu is the real p * slope rounded to fp32
+       + bd_gamma(kout + 1) * fabs((double)nu) * (double)S;                   // the product nu W that follows
+  if (kin) ds = ds + (kin + 1) * kBdTiny * (fabs(a.s) * ahi + a.tm) * (1.0 + kBdD);  // subnormal steps of the product before
+}
+
+// min over the input set of a . v, term by term: box form, and (norm 2) the ball form around x
+struct BdRed { double boxmin, dot, sq, mag; };
+BD_HD void bd_red_add(BdRed& r, double a, float lo, float hi, bool l2, float x) {
+  const double pl = a * (double)lo, ph = a * (double)hi;
+  r.boxmin = pl < ph ? pl : ph;
+  double mx = bd_max(fabs((double)lo), fabs((double)hi));
+  r.dot = 0.0;
+  r.sq = 0.0;
+  if (l2) {
+    r.dot = a * (double)x;
+    r.sq = a * a;
+    mx = bd_max(mx, fabs((double)x));
+  }
+  r.mag = fabs(a) * mx;
+}
+BD_HD double bd_red_finish(const BdRed& r, bool l2, float eps) {
+  double v = r.boxmin;
+  if (l2) {
+    const double v2 = r.dot - (double)eps * sqrt(r.sq) * (1.0 + kBdD);
+    if (v2 > v) v = v2;
+  }
+  return v - kBdD * r.mag;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- the plan
+struct BdShape {
+  int L = 0;
+  int n[LIPASR_MAX_LAYERS + 1] = {};
+  bool bn[LIPASR_MAX_LAYERS] = {};
+  size_t offW[LIPASR_MAX_LAYERS] = {}, offb[LIPASR_MAX_LAYERS] = {}, offg[LIPASR_MAX_LAYERS] = {}, offbe[LIPASR_MAX_LAYERS] = {};
+  size_t offmm[LIPASR_MAX_LAYERS] = {}, offmv[LIPASR_MAX_LAYERS] = {};
+  size_t n_params = 0, n_state = 0;
+};
+
+static size_t bd_align4(size_t v) { return (v + 3) & ~(size_t)3; }
+
+// the workspace, in floats from a 16-byte boundary.  The lo family is one span [lo0 | zlo_1 | hlo_1 | zlo_2 | ...], the hi family
+// likewise: layer_lo / layer_hi are one copy each.
+struct BdPlan {
+  size_t fam = 0;                      // floats of one family
+  size_t offLo = 0, offHi = 0;         // the families
+  size_t z[LIPASR_MAX_LAYERS] = {}, h[LIPASR_MAX_LAYERS] = {};  // offsets inside a family, hidden layers 0 .. L - 2
+  size_t offS[LIPASR_MAX_LAYERS] = {};
+  size_t offNorm = 0, offFlag = 0, offLam[2] = {}, offAcc = 0, offPart[LIPASR_MAX_LAYERS] = {};
+  int tiles[LIPASR_MAX_LAYERS] = {};   // partial columns of back stage l (the product with W_l, l = 1 .. L - 2): 4 ceil(n_l / 128)
+  size_t total = 0;                    // with the slack of the alignment
+};
+
+static BdPlan bd_plan(const BdShape& sh, int batch) {
+  BdPlan p;
+  const size_t B = batch, C = sh.n[sh.L], M = B * C;
+  size_t f = 0;
+  f += B * sh.n[0];
+  for (int l = 0; l + 1 < sh.L; ++l) {
+    p.z[l] = f; f += B * sh.n[l + 1];
+    p.h[l] = f; f += B * sh.n[l + 1];
+  }
+  p.fam = f;
+  size_t o = 0;
+  p.offLo = o; o = bd_align4(o + f);
+  p.offHi = o; o = bd_align4(o + f);
+  int maxw = sh.n[0];
+  for (int l = 0; l + 1 < sh.L; ++l) {
+    p.offS[l] = o; o = bd_align4(o + B * sh.n[l + 1]);
+    maxw = std::max(maxw, sh.n[l + 1]);
+  }
+  p.offNorm = o; o = bd_align4(o + (sh.L > 1 ? sh.n[1] : 0));
+  p.offFlag = o; o = bd_align4(o + B);
+  p.offLam[0] = o; o = bd_align4(o + M * maxw);
+  p.offLam[1] = o; o = bd_align4(o + M * maxw);
+  p.offAcc = o; o = bd_align4(o + 2 * 2 * M);  // doubles: [M][2]
+  for (int l = 1; l + 1 < sh.L; ++l) {
+    p.tiles[l] = 4 * ((sh.n[l] + 127) / 128);
+    p.offPart[l] = o; o = bd_align4(o + 2 * 2 * M * p.tiles[l]);  // doubles: [M][tiles][2]
+  }
+  p.total = o + 4;
+  return p;
+}
+
+static float* bd_base(float* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15); }
+
+// the partial sums of the back stages, as the tail reads them
+struct BdStages {
+  int count;
+  int tiles[LIPASR_MAX_LAYERS];
+  const double* part[LIPASR_MAX_LAYERS];
+};
+
+// -------------------------------------------------------------------------------------------------------------------- kernels
+constexpr int kBdThreads = 256;
+constexpr int kBdNormSlices = kBdThreads / 32;
+
+__device__ __forceinline__ double bd_sum32(double v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the same order on the host: v[0] of 32 terms
+static inline double bd_sum32_host(double (&v)[32]) {
+  for (int o = 16; o > 0; o >>= 1)
+    for (int i = 0; i < o; ++i) v[i] = v[i] + v[i + o];
+  return v[0];
+}
+
+// blocks [0, batch): one row's input box and flag.  blocks from batch on (norm 2): 32 column norms of W_1 each, a column's squares
+// in 8 interleaved fp64 partial sums (thread slice s takes i = s, s + 8, ...) that meet in index order.
+__global__ __launch_bounds__(kBdThreads) void bounds_prep_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                                 const int* __restrict__ y, int batch, int n0, int classes,
+                                                                 float clip_lo, float clip_hi, float* __restrict__ lo0,
+                                                                 float* __restrict__ hi0, int* __restrict__ flag,
+                                                                 const float* __restrict__ W1, int n1, float* __restrict__ colnorm) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < batch) {
+    const int b = blockIdx.x;
+    const float e = eps[b];
+    int bad = !(e >= 0.0f) || y[b] < 0 || y[b] >= classes;
+    for (int i = tid; i < n0; i += kBdThreads) {
+      const float v = x[(size_t)b * n0 + i];
+      bad |= v != v;
+      float lo, hi;
+      bd_input_box(v, e, clip_lo, clip_hi, lo, hi);
+      lo0[(size_t)b * n0 + i] = lo;
+      hi0[(size_t)b * n0 + i] = hi;
+    }
+    bad = __syncthreads_or(bad);
+    if (tid == 0) flag[b] = bad;
+  } else {
+    __shared__ double parts[kBdNormSlices][32];
+    const int jl = tid & 31, sl = tid >> 5;
+    const int j = ((int)blockIdx.x - batch) * 32 + jl;
+    double acc = 0.0;
+    if (j < n1) {
+      for (int i = sl; i < n0; i += kBdNormSlices) {
+        const double w = W1[(size_t)i * n1 + j];
+        acc = acc + w * w;
+      }
+    }
+    parts[sl][jl] = acc;
+    __syncthreads();
+    if (sl == 0 && j < n1) {
+      double tot = parts[0][jl];
+      for (int q = 1; q < kBdNormSlices; ++q) tot = tot + parts[q][jl];
+      colnorm[j] = bd_up(sqrt(tot) * (1.0 + kBdD));
+    }
+  }
+}
+
+// z = W h + b over a box of h: rows b0 .. b0 + 31 (blockIdx.x), columns n0 .. n0 + 127 (blockIdx.y), a wavefront per 32 columns.
+// x != null: the first layer under norm 2 (centre x, radius min(|W| r, eps ||W_j||_2)).
+__global__ __launch_bounds__(kBdThreads) void bounds_layer_kernel(const float* __restrict__ lo, const float* __restrict__ hi,
+                                                                  const float* __restrict__ x, const float* __restrict__ eps,
+                                                                  const float* __restrict__ colnorm, const float* __restrict__ W,
+                                                                  const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, const float* __restrict__ mmean,
+                                                                  const float* __restrict__ mvar, int batch, int K, int N,
+                                                                  float* __restrict__ zlo, float* __restrict__ zhi,
+                                                                  float* __restrict__ Sout, float* __restrict__ hlo,
+                                                                  float* __restrict__ hhi) {
+  __shared__ float cs[32 * 33], rs[32 * 33], wsm[32 * 128];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  const int b0 = blockIdx.x * 32, n0 = blockIdx.y * 128;
+  bd_f32x16 acc_c, acc_r, acc_s;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc_c[e] = acc_r[e] = acc_s[e] = 0.0f;
+  // the next chunk's 28 loads per thread are in flight while the current one feeds 48 MFMAs per wavefront; an element past the
+  // batch or past K is the point box 0, whose centre and radius are 0
+  float lreg[4], hreg[4], xreg[4], wreg[16];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+      const int b = b0 + row, k = k0 + kk;
+      const bool in = b < batch && k < K;
+      const size_t at = (size_t)b * K + k;
+      lreg[q] = in ? lo[at] : 0.0f;
+      hreg[q] = in ? hi[at] : 0.0f;
+      xreg[q] = (in && x) ? x[at] : 0.0f;
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = tid + kBdThreads * q, kk = idx >> 7, col = idx & 127;
+      const int k = k0 + kk, j = n0 + col;
+      wreg[q] = (k < K && j < N) ? W[(size_t)k * N + j] : 0.0f;
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += 32) {
+    __syncthreads();  // the previous chunk is read
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+      float c, r;
+      if (x) bd_sym_rad(xreg[q], lreg[q], hreg[q], c, r);
+      else bd_mid_rad(lreg[q], hreg[q], c, r);
+      cs[row * 33 + kk] = c;
+      rs[row * 33 + kk] = r;
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) wsm[tid + kBdThreads * q] = wreg[q];
+    __syncthreads();
+    if (k0 + 32 < K) fetch(k0 + 32);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float c = cs[li * 33 + 2 * s + h], r = rs[li * 33 + 2 * s + h];
+      const float w = wsm[(2 * s + h) * 128 + wave * 32 + li], aw = fabsf(w);
+      acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(c, w, acc_c, 0, 0, 0);
+      acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(r, aw, acc_r, 0, 0, 0);
+      acc_s = __builtin_amdgcn_mfma_f32_32x32x2f32(fabsf(c), aw, acc_s, 0, 0, 0);
+    }
+  }
+  const int j = n0 + wave * 32 + li;
+  if (j >= N) return;
+  const BdAff a = bd_aff(gamma, beta, mmean, mvar, j);
+  const float bj = bias[j];
+  const float cn = x ? colnorm[j] : 0.0f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int b = b0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    if (b >= batch) continue;
+    const size_t at = (size_t)b * N + j;
+    float l, u, S, pl, pu;
+    bd_z_box(acc_c[e], acc_r[e], acc_s[e], bj, K, x != nullptr, x ? eps[b] : 0.0f, cn, l, u, S);
+    zlo[at] = l;
+    zhi[at] = u;
+    Sout[at] = S;
+    bd_post_box(l, u, a, pl, pu);
+    hlo[at] = pl;
+    hhi[at] = pu;
+  }
+}
+
+// 32 lanes per row m = b C + k: Lambda_L, the IBP margin, and (hidden layers) the relaxation of the last hidden layer.
+// hidden: lo / hi = the box of h_{L-1}, x = null.  One layer: lo / hi = the input box, x and eps and l2 as the caller gave them.
+__global__ __launch_bounds__(kBdThreads) void bounds_head_kernel(const float* __restrict__ WL, const float* __restrict__ bL,
+                                                                 const int* __restrict__ y, const int* __restrict__ flag, int M, int C,
+                                                                 int nh, const float* __restrict__ lo, const float* __restrict__ hi,
+                                                                 const float* __restrict__ x, const float* __restrict__ eps, int l2,
+                                                                 int hidden, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, const float* __restrict__ mmean,
+                                                                 const float* __restrict__ mvar, const float* __restrict__ zlo,
+                                                                 const float* __restrict__ zhi, const float* __restrict__ S,
+                                                                 const float* __restrict__ bias, float* __restrict__ lam_out,
+                                                                 double* __restrict__ rowacc,
+                                                                 float* __restrict__ margin_ibp) {
+  const int li = threadIdx.x & 31;
+  const int m = blockIdx.x * (kBdThreads / 32) + (threadIdx.x >> 5);
+  if (m >= M) return;  // whole 32-lane groups leave; the butterflies below stay inside a group
+  const int b = m / C, k = m % C;
+  const int bad = flag[b];
+  const int yb = bad ? 0 : y[b];
+  const float e = eps[b];
+  double csum = 0.0, ssum = 0.0;
+  BdRed tot{0.0, 0.0, 0.0, 0.0};
+  for (int j0 = 0; j0 < nh; j0 += 32) {
+    const int j = j0 + li;
+    double dc = 0.0, ds = 0.0;
+    BdRed r{0.0, 0.0, 0.0, 0.0};
+    if (j < nh) {
+      const size_t at = (size_t)b * nh + j;
+      const double d = (double)WL[(size_t)j * C + yb] - (double)WL[(size_t)j * C + k];
+      const float lam = k == yb ? 0.0f : (float)d;
+      const float l = lo[at], u = hi[at];
+      bd_red_add(r, d, l, u, l2 != 0, x ? x[at] : 0.0f);
+      // lam is the real difference rounded to fp32
+      const double H = bd_max(bd_max(fabs((double)l), fabs((double)u)), x ? fabs((double)x[at]) : 0.0);
+      ds = 2.0 * kBdU * fabs((double)lam) * H;
+      float nu = lam;
+      if (hidden) {
+        double rc, rs;
+        bd_relax(lam, bd_aff(gamma, beta, mmean, mvar, j), zlo[at], zhi[at], S[at], bias[j], 0, nh, nu, rc, rs);
+        dc = rc;
+        ds = ds + rs;
+      }
+      lam_out[(size_t)m * nh + j] = nu;
+    }
+    csum = csum + bd_sum32(dc);
+    ssum = ssum + bd_sum32(ds);
+    tot.boxmin = tot.boxmin + bd_sum32(r.boxmin);
+    tot.dot = tot.dot + bd_sum32(r.dot);
+    tot.sq = tot.sq + bd_sum32(r.sq);
+    tot.mag = tot.mag + bd_sum32(r.mag);
+  }
+  if (li == 0) {
+    const double c0 = (double)bL[yb] - (double)bL[k];
+    rowacc[2 * (size_t)m] = csum + c0;
+    rowacc[2 * (size_t)m + 1] = ssum + kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(csum));
+    const double v = bd_red_finish(tot, l2 != 0, e) + c0 - kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(tot.boxmin));
+    margin_ibp[m] = bad ? NAN : (k == yb ? INFINITY : bd_dn(v));
+  }
+}
+
+// out[m][i] = sum_j A[m][j] W[i][j]: rows m0 .. m0 + 31 (blockIdx.x), columns i0 .. i0 + 127 (blockIdx.y).  relax: the epilogue
+// applies the layer below (its BatchNorm parameters and the z box and S of row m / C) and writes one partial per row and wavefront.
+__global__ __launch_bounds__(kBdThreads) void bounds_back_kernel(const float* __restrict__ A, const float* __restrict__ W, int M, int K,
+                                                                 int N, int C, int relax, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, const float* __restrict__ mmean,
+                                                                 const float* __restrict__ mvar, const float* __restrict__ zlo,
+                                                                 const float* __restrict__ zhi, const float* __restrict__ S,
+                                                                 const float* __restrict__ bias, float* __restrict__ out,
+                                                                 double* __restrict__ part, int tiles) {
+  __shared__ float as[32 * 33], wt[128 * 33];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  const int m0 = blockIdx.x * 32, i0 = blockIdx.y * 128;
+  bd_f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+  float areg[4], wreg[16];  // the next chunk, in flight while the current one feeds the MFMAs
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+      const int m = m0 + row, k = k0 + kk;
+      areg[q] = (m < M && k < K) ? A[(size_t)m * K + k] : 0.0f;
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = tid + kBdThreads * q, il = idx >> 5, kk = idx & 31;
+      const int i = i0 + il, k = k0 + kk;
+      wreg[q] = (i < N && k < K) ? W[(size_t)i * K + k] : 0.0f;
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += 32) {
+    __syncthreads();  // the previous chunk is read
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q;
+      as[(idx >> 5) * 33 + (idx & 31)] = areg[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = tid + kBdThreads * q;
+      wt[(idx >> 5) * 33 + (idx & 31)] = wreg[q];
+    }
+    __syncthreads();
+    if (k0 + 32 < K) fetch(k0 + 32);
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[li * 33 + 2 * s + h], wt[(wave * 32 + li) * 33 + 2 * s + h], acc, 0, 0, 0);
+  }
+  const int i = i0 + wave * 32 + li;
+  const bool col = i < N;
+  BdAff a{1.0, 0.0, 0.0};
+  if (relax && col) a = bd_aff(gamma, beta, mmean, mvar, i);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;  // the same for the 32 lanes of a half
+    const bool ok = col && m < M;
+    float nu = acc[e];
+    double dc = 0.0, ds = 0.0;
+    if (relax && ok) {
+      const size_t at = (size_t)(m / C) * N + i;
+      bd_relax(acc[e], a, zlo[at], zhi[at], S[at], bias[i], K, N, nu, dc, ds);
+    }
+    if (ok) out[(size_t)m * N + i] = nu;
+    if (relax) {
+      dc = bd_sum32(dc);
+      ds = bd_sum32(ds);
+      if (li == 0 && m < M) {
+        double* p = part + 2 * ((size_t)m * tiles + (blockIdx.y * 4 + wave));
+        p[0] = dc;
+        p[1] = ds;
+      }
+    }
+  }
+}
+
+// 32 lanes per row m: the input reduction of Lambda_0, the constants and slacks in their fixed order, the two outputs.
+__global__ __launch_bounds__(kBdThreads) void bounds_tail_kernel(const float* __restrict__ lam0, const int* __restrict__ y,
+                                                                 const int* __restrict__ flag, int M, int C, int n0, int kin,
+                                                                 const float* __restrict__ lo0, const float* __restrict__ hi0,
+                                                                 const float* __restrict__ x, const float* __restrict__ eps, int l2,
+                                                                 const double* __restrict__ rowacc, BdStages st,
+                                                                 float* __restrict__ margin_crown, float* __restrict__ slack) {
+  const int li = threadIdx.x & 31;
+  const int m = blockIdx.x * (kBdThreads / 32) + (threadIdx.x >> 5);
+  if (m >= M) return;
+  const int b = m / C, k = m % C;
+  const int bad = flag[b];
+  const int yb = bad ? 0 : y[b];
+  double ssum = 0.0;
+  BdRed tot{0.0, 0.0, 0.0, 0.0};
+  for (int j0 = 0; j0 < n0; j0 += 32) {
+    const int j = j0 + li;
+    double ds = 0.0;
+    BdRed r{0.0, 0.0, 0.0, 0.0};
+    if (j < n0) {
+      const size_t at = (size_t)b * n0 + j;
+      const float l = lo0[at], u = hi0[at];
+      bd_red_add(r, (double)lam0[(size_t)m * n0 + j], l, u, l2 != 0, x[at]);
+      if (kin) ds = (kin + 1) * kBdTiny * bd_max(fabs((double)l), fabs((double)u));
+    }
+    ssum = ssum + bd_sum32(ds);
+    tot.boxmin = tot.boxmin + bd_sum32(r.boxmin);
+    tot.dot = tot.dot + bd_sum32(r.dot);
+    tot.sq = tot.sq + bd_sum32(r.sq);
+    tot.mag = tot.mag + bd_sum32(r.mag);
+  }
+  if (li != 0) return;
+  double c = rowacc[2 * (size_t)m], s = rowacc[2 * (size_t)m + 1] + ssum, cm = fabs(c);
+  for (int g = 0; g < st.count; ++g) {
+    const double* p = st.part[g] + 2 * (size_t)m * st.tiles[g];
+    for (int t = 0; t < st.tiles[g]; ++t) {
+      c = c + p[2 * t];
+      cm = cm + fabs(p[2 * t]);
+      s = s + p[2 * t + 1];
+    }
+  }
+  const double red = bd_red_finish(tot, l2 != 0, eps[b]);
+  s = (s + kBdD * (cm + fabs(red))) * (1.0 + kBdD);
+  const bool unused = k == yb;
+  margin_crown[m] = bad ? NAN : (unused ? INFINITY : bd_dn(red + c - s));
+  if (slack) slack[m] = bad ? NAN : (unused ? 0.0f : bd_up(s));
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host twin
+static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, const float* bnstate, const float* x, const float* eps,
+                    bool l2, float clip_lo, float clip_hi, const int* y, int batch, float* ws, float* margin_ibp, float* margin_crown,
+                    float* slack) {
+  const int L = sh.L, C = sh.n[L], n0 = sh.n[0], M = batch * C;
+  float* lo = ws + pl.offLo;
+  float* hi = ws + pl.offHi;
+  int* flag = reinterpret_cast<int*>(ws + pl.offFlag);
+  float* colnorm = ws + pl.offNorm;
+  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
+    g = be = mm = mv = nullptr;
+    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
+  };
+  // prep
+  for (int b = 0; b < batch; ++b) {
+    int bad = !(eps[b] >= 0.0f) || y[b] < 0 || y[b] >= C;
+    for (int i = 0; i < n0; ++i) {
+      const float v = x[(size_t)b * n0 + i];
+      bad |= v != v;
+      bd_input_box(v, eps[b], clip_lo, clip_hi, lo[(size_t)b * n0 + i], hi[(size_t)b * n0 + i]);
+    }
+    flag[b] = bad;
+  }
+  if (l2 && L > 1) {
+    const float* W1 = params + sh.offW[0];
+    const int n1 = sh.n[1];
+    for (int j = 0; j < n1; ++j) {
+      double part[kBdNormSlices] = {};
+      for (int i = 0; i < n0; ++i) {
+        const double w = W1[(size_t)i * n1 + j];
+        part[i % kBdNormSlices] = part[i % kBdNormSlices] + w * w;
+      }
+      double tot = part[0];
+      for (int q = 1; q < kBdNormSlices; ++q) tot = tot + part[q];
+      colnorm[j] = bd_up(sqrt(tot) * (1.0 + kBdD));
+    }
+  }
+  // hidden layers
+  std::vector<float> c, r, ac, ar, as;
+  for (int l = 0; l + 1 < L; ++l) {
+    const int K = sh.n[l], N = sh.n[l + 1];
+    const float* W = params + sh.offW[l];
+    const float* bias = params + sh.offb[l];
+    const float *g, *be, *mm, *mv;
+    bnp(l, g, be, mm, mv);
+    const float* ilo = l == 0 ? lo : lo + pl.h[l - 1];
+    const float* ihi = l == 0 ? hi : hi + pl.h[l - 1];
+    const bool first2 = l2 && l == 0;
+    c.assign(K, 0.0f); r.assign(K, 0.0f);
+    for (int b = 0; b < batch; ++b) {
+      for (int k = 0; k < K; ++k) {
+        const size_t at = (size_t)b * K + k;
+        if (first2) bd_sym_rad(x[at], ilo[at], ihi[at], c[k], r[k]);
+        else bd_mid_rad(ilo[at], ihi[at], c[k], r[k]);
+      }
+      ac.assign(N, 0.0f); ar.assign(N, 0.0f); as.assign(N, 0.0f);
+      for (int k = 0; k < K; ++k) {
+        const float ck = c[k], rk = r[k], ak = std::fabs(ck);
+        const float* wr = W + (size_t)k * N;
+        for (int j = 0; j < N; ++j) {
+          const float w = wr[j], aw = std::fabs(w);
+          ac[j] = std::fmaf(ck, w, ac[j]);
+          ar[j] = std::fmaf(rk, aw, ar[j]);
+          as[j] = std::fmaf(ak, aw, as[j]);
+        }
+      }
+      for (int j = 0; j < N; ++j) {
+        const size_t at = (size_t)b * N + j;
+        float zl, zu, S;
+        bd_z_box(ac[j], ar[j], as[j], bias[j], K, first2, first2 ? eps[b] : 0.0f, first2 ? colnorm[j] : 0.0f, zl, zu, S);
+        lo[pl.z[l] + at] = zl;
+        hi[pl.z[l] + at] = zu;
+        ws[pl.offS[l] + at] = S;
+        bd_post_box(zl, zu, bd_aff(g, be, mm, mv, j), lo[pl.h[l] + at], hi[pl.h[l] + at]);
+      }
+    }
+  }
+  // head
+  const bool hidden = L > 1;
+  const int nh = sh.n[L - 1];
+  const float* WL = params + sh.offW[L - 1];
+  const float* bL = params + sh.offb[L - 1];
+  const float* hl = hidden ? lo + pl.h[L - 2] : lo;
+  const float* hu = hidden ? hi + pl.h[L - 2] : hi;
+  const bool hl2 = l2 && !hidden;
+  double* rowacc = reinterpret_cast<double*>(ws + pl.offAcc);
+  float* lam = ws + pl.offLam[0];
+  const float *g, *be, *mm, *mv;
+  if (hidden) bnp(L - 2, g, be, mm, mv);
+  double vc[32], vs[32], v0[32], v1[32], v2[32], v3[32];
+  for (int m = 0; m < M; ++m) {
+    const int b = m / C, k = m % C, bad = flag[b], yb = bad ? 0 : y[b];
+    double csum = 0.0, ssum = 0.0;
+    BdRed tot{0.0, 0.0, 0.0, 0.0};
+    for (int j0 = 0; j0 < nh; j0 += 32) {
+      for (int q = 0; q < 32; ++q) {
+        const int j = j0 + q;
+        double dc = 0.0, ds = 0.0;
+        BdRed rr{0.0, 0.0, 0.0, 0.0};
+        if (j < nh) {
+          const size_t at = (size_t)b * nh + j;
+          const double d = (double)WL[(size_t)j * C + yb] - (double)WL[(size_t)j * C + k];
+          const float la = k == yb ? 0.0f : (float)d;
+          const float l = hl[at], u = hu[at];
+          bd_red_add(rr, d, l, u, hl2, hidden ? 0.0f : x[at]);
+          const double H = bd_max(bd_max(fabs((double)l), fabs((double)u)), hidden ? 0.0 : fabs((double)x[at]));
+          ds = 2.0 * kBdU * fabs((double)la) * H;
+          float nu = la;
+          if (hidden) {
+            double rc, rs;
+            bd_relax(la, bd_aff(g, be, mm, mv, j), lo[pl.z[L - 2] + at], hi[pl.z[L - 2] + at], ws[pl.offS[L - 2] + at],
+                     params[sh.offb[L - 2] + j], 0, nh, nu, rc, rs);
+            dc = rc;
+            ds = ds + rs;
+          }
+          lam[(size_t)m * nh + j] = nu;
+        }
+        vc[q] = dc; vs[q] = ds; v0[q] = rr.boxmin; v1[q] = rr.dot; v2[q] = rr.sq; v3[q] = rr.mag;
+      }
+      csum = csum + bd_sum32_host(vc);
+      ssum = ssum + bd_sum32_host(vs);
+      tot.boxmin = tot.boxmin + bd_sum32_host(v0);
+      tot.dot = tot.dot + bd_sum32_host(v1);
+      tot.sq = tot.sq + bd_sum32_host(v2);
+      tot.mag = tot.mag + bd_sum32_host(v3);
+    }
+    const double c0 = (double)bL[yb] - (double)bL[k];
+    rowacc[2 * (size_t)m] = csum + c0;
+    rowacc[2 * (size_t)m + 1] = ssum + kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(csum));
+    const double v = bd_red_finish(tot, hl2, eps[b]) + c0 - kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(tot.boxmin));
+    margin_ibp[m] = bad ? NAN : (k == yb ? INFINITY : bd_dn(v));
+  }
+  if (!margin_crown) return;
+  // back
+  int cur = 0;
+  std::vector<float> acc;
+  for (int l = L - 2; l >= 0; --l) {
+    const int K = sh.n[l + 1], N = sh.n[l];
+    const float* W = params + sh.offW[l];
+    const float* A = ws + pl.offLam[cur];
+    float* out = ws + pl.offLam[cur ^ 1];
+    const bool relax = l > 0;
+    if (relax) bnp(l - 1, g, be, mm, mv);
+    double* part = relax ? reinterpret_cast<double*>(ws + pl.offPart[l]) : nullptr;
+    const int tiles = pl.tiles[l];
+    for (int m = 0; m < M; ++m) {
+      acc.assign(N, 0.0f);
+      for (int k = 0; k < K; ++k) {
+        const float a = A[(size_t)m * K + k];
+        for (int i = 0; i < N; ++i) acc[i] = std::fmaf(a, W[(size_t)i * K + k], acc[i]);
+      }
+      if (!relax) {
+        for (int i = 0; i < N; ++i) out[(size_t)m * N + i] = acc[i];
+        continue;
+      }
+      for (int t = 0; t < tiles; ++t) {
+        for (int q = 0; q < 32; ++q) {
+          const int i = 32 * t + q;
+          double dc = 0.0, ds = 0.0;
+          if (i < N) {
+            const size_t at = (size_t)(m / C) * N + i;
+            float nu;
+            bd_relax(acc[i], bd_aff(g, be, mm, mv, i), lo[pl.z[l - 1] + at], hi[pl.z[l - 1] + at], ws[pl.offS[l - 1] + at],
+                     params[sh.offb[l - 1] + i], K, N, nu, dc, ds);
+            out[(size_t)m * N + i] = nu;
+          }
+          vc[q] = dc; vs[q] = ds;
+        }
+        part[2 * ((size_t)m * tiles + t)] = bd_sum32_host(vc);
+        part[2 * ((size_t)m * tiles + t) + 1] = bd_sum32_host(vs);
+      }
+    }
+    cur ^= 1;
+  }
+  // tail
+  const float* lam0 = ws + pl.offLam[cur];
+  const int kin = hidden ? sh.n[1] : 0;
+  for (int m = 0; m < M; ++m) {
+    const int b = m / C, k = m % C, bad = flag[b], yb = bad ? 0 : y[b];
+    double ssum = 0.0;
+    BdRed tot{0.0, 0.0, 0.0, 0.0};
+    for (int j0 = 0; j0 < n0; j0 += 32) {
+      for (int q = 0; q < 32; ++q) {
+        const int j = j0 + q;
+        double ds = 0.0;
+        BdRed rr{0.0, 0.0, 0.0, 0.0};
+        if (j < n0) {
+          const size_t at = (size_t)b * n0 + j;
+          bd_red_add(rr, (double)lam0[(size_t)m * n0 + j], lo[at], hi[at], l2, x[at]);
+          if (kin) ds = (kin + 1) * kBdTiny * bd_max(fabs((double)lo[at]), fabs((double)hi[at]));
+        }
+        vs[q] = ds; v0[q] = rr.boxmin; v1[q] = rr.dot; v2[q] = rr.sq; v3[q] = rr.mag;
+      }
+      ssum = ssum + bd_sum32_host(vs);
+      tot.boxmin = tot.boxmin + bd_sum32_host(v0);
+      tot.dot = tot.dot + bd_sum32_host(v1);
+      tot.sq = tot.sq + bd_sum32_host(v2);
+      tot.mag = tot.mag + bd_sum32_host(v3);
+    }
+    double cc = rowacc[2 * (size_t)m], s = rowacc[2 * (size_t)m + 1] + ssum, cm = fabs(cc);
+    for (int l = L - 2; l >= 1; --l) {
+      const double* p = reinterpret_cast<const double*>(ws + pl.offPart[l]) + 2 * (size_t)m * pl.tiles[l];
+      for (int t = 0; t < pl.tiles[l]; ++t) {
+        cc = cc + p[2 * t];
+        cm = cm + fabs(p[2 * t]);
+        s = s + p[2 * t + 1];
+      }
+    }
+    const double red = bd_red_finish(tot, l2, eps[b]);
+    s = (s + kBdD * (cm + fabs(red))) * (1.0 + kBdD);
+    const bool unused = k == yb;
+    margin_crown[m] = bad ? NAN : (unused ? INFINITY : bd_dn(red + cc - s));
+    if (slack) slack[m] = bad ? NAN : (unused ? 0.0f : bd_up(s));
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------------- checks
+static int bd_shape_from(const char* fn, int n_layers, const int* widths, const int* bn, BdShape* sh) {
+  LP_CHECK_ARG(widths != nullptr, "%s: null argument", fn);
+  LP_CHECK_ARG(n_layers >= 1 && n_layers <= LIPASR_MAX_LAYERS, "%s: n_layers=%d outside [1,%d]", fn, n_layers, LIPASR_MAX_LAYERS);
+  for (int l = 0; l <= n_layers; ++l)
+    LP_CHECK_ARG(widths[l] >= 1 && widths[l] <= kBdMaxWidth, "%s: widths[%d]=%d outside [1,%d]", fn, l, widths[l], kBdMaxWidth);
+  LP_CHECK_ARG(widths[n_layers] <= 32, "%s: %d classes; at most 32 are supported", fn, widths[n_layers]);
+  sh->L = n_layers;
+  size_t po = 0, so = 0;
+  for (int l = 0; l < n_layers; ++l) {
+    const size_t ni = widths[l], no = widths[l + 1];
+    sh->n[l] = widths[l];
+    sh->bn[l] = l + 1 < n_layers && bn && bn[l];
+    // the flat layout of lipasr_mlp_create
+    sh->offW[l] = po; po = bd_align4(po + ni * no);
+    sh->offb[l] = po; po = bd_align4(po + no);
+    if (sh->bn[l]) {
+      sh->offg[l] = po; po = bd_align4(po + no);
+      sh->offbe[l] = po; po = bd_align4(po + no);
+      sh->offmm[l] = so; so = bd_align4(so + no);
+      sh->offmv[l] = so; so = bd_align4(so + no);
+    }
+  }
+  sh->n[n_layers] = widths[n_layers];
+  sh->n_params = po;
+  sh->n_state = so;
+  return LIPASR_OK;
+}
+
+static int bd_shape_of(const char* fn, lipasr_mlp_t m, BdShape* sh) {
+  LP_CHECK_ARG(m != nullptr, "%s: null argument", fn);
+  sh->L = m->n_layers;
+  for (int l = 0; l < m->n_layers; ++l) {
+    const MlpLayer& P = m->L[l];
+    sh->n[l] = P.n_in;
+    sh->n[l + 1] = P.n_out;
+    sh->bn[l] = P.bn;
+    sh->offW[l] = P.offW; sh->offb[l] = P.offb; sh->offg[l] = P.offg; sh->offbe[l] = P.offbe;
+    sh->offmm[l] = P.offmm; sh->offmv[l] = P.offmv;
+  }
+  sh->n_params = m->n_params;
+  sh->n_state = m->n_state;
+  for (int l = 0; l <= sh->L; ++l)
+    LP_CHECK_ARG(sh->n[l] <= kBdMaxWidth, "%s: a layer of %d units; at most %d are supported", fn, sh->n[l], kBdMaxWidth);
+  LP_CHECK_ARG(sh->n[sh->L] <= 32, "%s: %d classes; at most 32 are supported", fn, sh->n[sh->L]);
+  return LIPASR_OK;
+}
+
+static int bd_check(const char* fn, const BdShape& sh, const BdPlan& pl, const float* params, const float* bnstate, const float* x,
+                    const float* eps, float norm, float clip_lo, float clip_hi, const int* y, int batch, const float* ws,
+                    size_t ws_floats, const float* margin_ibp, const float* margin_crown, const float* slack, const float* layer_lo,
+                    const float* layer_hi, bool* l2) {
+  LP_CHECK_ARG(params && x && eps && y && ws && margin_ibp, "%s: null argument", fn);
+  LP_CHECK_ARG(sh.n_state == 0 || bnstate, "%s: bnstate is null", fn);
+  LP_CHECK_ARG(norm == 2.0f || norm == INFINITY, "%s: norm %g; inf and 2 are supported", fn, (double)norm);
+  LP_CHECK_ARG(!(clip_lo != clip_lo) && !(clip_hi != clip_hi) && clip_lo <= clip_hi, "%s: clip box [%g, %g]", fn, (double)clip_lo,
+               (double)clip_hi);
+  LP_CHECK_ARG(!slack || margin_crown, "%s: the slack is that of margin_crown, which is null", fn);
+  LP_CHECK_ARG(ws_floats >= pl.total, "%s: workspace of %zu floats; %zu are needed", fn, ws_floats, pl.total);
+  *l2 = norm == 2.0f;
+  const size_t B = batch, C = sh.n[sh.L];
+  struct Span { const void* p; size_t bytes; bool written; };
+  const Span sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {x, B * sh.n[0] * 4, false},
+                     {eps, B * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true}, {margin_ibp, B * C * 4, true},
+                     {margin_crown, margin_crown ? B * C * 4 : 0, true}, {slack, slack ? B * C * 4 : 0, true},
+                     {layer_lo, layer_lo ? pl.fam * 4 : 0, true}, {layer_hi, layer_hi ? pl.fam * 4 : 0, true}};
+  const int ns = sizeof(sp) / sizeof(sp[0]);
+  for (int i = 0; i < ns; ++i)
+    for (int j = i + 1; j < ns; ++j)
+      LP_CHECK_ARG(!((sp[i].written || sp[j].written) && sp[i].p && sp[j].p && spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes)),
+                   "%s: an output or the workspace overlaps another argument", fn);
+  return LIPASR_OK;
+}
+
+}  // namespace lipasr
+
+using namespace lipasr;
+
+extern "C" {
+
+long lipasr_debug_bounds_launches(int kernel) { return (kernel >= 0 && kernel < 5) ? g_bounds_launches[kernel] : -1; }
+
+int lipasr_mlp_bounds_workspace(lipasr_mlp_t m, int batch, size_t* floats) {
+  const char* fn = "lipasr_mlp_bounds_workspace";
+  BdShape sh;
+  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
+  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
+  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  *floats = bd_plan(sh, batch).total;
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_bounds_workspace_host(int n_layers, const int* widths, int batch, size_t* floats) {
+  const char* fn = "lipasr_mlp_bounds_workspace_host";
+  BdShape sh;
+  if (int rc = bd_shape_from(fn, n_layers, widths, nullptr, &sh)) return rc;
+  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
+  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  *floats = bd_plan(sh, batch).total;
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, const float* eps, float norm,
+                      float clip_lo, float clip_hi, const int* y, int batch, float* workspace, size_t workspace_floats,
+                      float* margin_ibp, float* margin_crown, float* slack, float* layer_lo, float* layer_hi, lipasr_stream_t stream) {
+  const char* fn = "lipasr_mlp_bounds";
+  BdShape sh;
+  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
+  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  const BdPlan pl = bd_plan(sh, batch);
+  bool l2 = false;
+  if (int rc = bd_check(fn, sh, pl, params, bnstate, x, eps, norm, clip_lo, clip_hi, y, batch, workspace, workspace_floats, margin_ibp,
+                        margin_crown, slack, layer_lo, layer_hi, &l2))
+    return rc;
+  DeviceGuard guard(m->ctx->device);
+  hipStream_t st = S(stream);
+  float* ws = bd_base(workspace);
+  const int L = sh.L, C = sh.n[L], n0 = sh.n[0], M = batch * C;
+  float* lo = ws + pl.offLo;
+  float* hi = ws + pl.offHi;
+  int* flag = reinterpret_cast<int*>(ws + pl.offFlag);
+  float* colnorm = ws + pl.offNorm;
+  const bool hidden = L > 1;
+  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
+    g = be = mm = mv = nullptr;
+    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
+  };
+  const float *g, *be, *mm, *mv;
+  {
+    const bool norms = l2 && hidden;
+    const int n1 = hidden ? sh.n[1] : 0;
+    const unsigned blocks = (unsigned)batch + (norms ? (unsigned)((n1 + 31) / 32) : 0u);
+    hipLaunchKernelGGL(bounds_prep_kernel, dim3(blocks), dim3(kBdThreads), 0, st, x, eps, y, batch, n0, C, clip_lo, clip_hi, lo, hi, flag,
+                       params + sh.offW[0], n1, colnorm);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_launches[BD_PREP];
+  }
+  for (int l = 0; l + 1 < L; ++l) {
+    const int K = sh.n[l], N = sh.n[l + 1];
+    bnp(l, g, be, mm, mv);
+    const bool first2 = l2 && l == 0;
+    hipLaunchKernelGGL(bounds_layer_kernel, dim3((batch + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st,
+                       l == 0 ? lo : lo + pl.h[l - 1], l == 0 ? hi : hi + pl.h[l - 1], first2 ? x : nullptr, eps, colnorm,
+                       params + sh.offW[l], params + sh.offb[l], g, be, mm, mv, batch, K, N, lo + pl.z[l], hi + pl.z[l],
+                       ws + pl.offS[l], lo + pl.h[l], hi + pl.h[l]);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_launches[BD_LAYER];
+  }
+  double* rowacc = reinterpret_cast<double*>(ws + pl.offAcc);
+  const unsigned rowblocks = (unsigned)((M + kBdThreads / 32 - 1) / (kBdThreads / 32));
+  {
+    const int nh = sh.n[L - 1];
+    g = be = mm = mv = nullptr;
+    if (hidden) bnp(L - 2, g, be, mm, mv);
+    hipLaunchKernelGGL(bounds_head_kernel, dim3(rowblocks), dim3(kBdThreads), 0, st, params + sh.offW[L - 1], params + sh.offb[L - 1], y,
+                       flag, M, C, nh, hidden ? lo + pl.h[L - 2] : lo, hidden ? hi + pl.h[L - 2] : hi, hidden ? nullptr : x, eps,
+                       (l2 && !hidden) ? 1 : 0, hidden ? 1 : 0, g, be, mm, mv, hidden ? lo + pl.z[L - 2] : nullptr,
+                       hidden ? hi + pl.z[L - 2] : nullptr, hidden ? ws + pl.offS[L - 2] : nullptr,
+                       hidden ? params + sh.offb[L - 2] : nullptr, ws + pl.offLam[0], rowacc,
+                       margin_ibp);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_launches[BD_HEAD];
+  }
+  if (margin_crown) {
+    int cur = 0;
+    BdStages stg;
+    stg.count = 0;
+    for (int l = L - 2; l >= 0; --l) {
+      const int K = sh.n[l + 1], N = sh.n[l];
+      const bool relax = l > 0;
+      g = be = mm = mv = nullptr;
+      if (relax) bnp(l - 1, g, be, mm, mv);
+      double* part = relax ? reinterpret_cast<double*>(ws + pl.offPart[l]) : nullptr;
+      hipLaunchKernelGGL(bounds_back_kernel, dim3((M + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, ws + pl.offLam[cur],
+                         params + sh.offW[l], M, K, N, C, relax ? 1 : 0, g, be, mm, mv, relax ? lo + pl.z[l - 1] : nullptr,
+                         relax ? hi + pl.z[l - 1] : nullptr, relax ? ws + pl.offS[l - 1] : nullptr,
+                         relax ? params + sh.offb[l - 1] : nullptr, ws + pl.offLam[cur ^ 1], part,
+                         pl.tiles[l]);
+      LP_LAUNCH_CHECK();
+      ++g_bounds_launches[BD_BACK];
+      if (relax) {
+        stg.tiles[stg.count] = pl.tiles[l];
+        stg.part[stg.count] = part;
+        ++stg.count;
+      }
+      cur ^= 1;
+    }
+    hipLaunchKernelGGL(bounds_tail_kernel, dim3(rowblocks), dim3(kBdThreads), 0, st, ws + pl.offLam[cur], y, flag, M, C, n0,
+                       hidden ? sh.n[1] : 0, lo, hi, x, eps, l2 ? 1 : 0, rowacc, stg, margin_crown, slack);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_launches[BD_TAIL];
+  }
+  if (layer_lo) LP_HIP(hipMemcpyAsync(layer_lo, lo, pl.fam * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (layer_hi) LP_HIP(hipMemcpyAsync(layer_hi, hi, pl.fam * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_bounds_host(int n_layers, const int* widths, const int* bn, const float* params, const float* bnstate, const float* x,
+                           const float* eps, float norm, float clip_lo, float clip_hi, const int* y, int batch, float* workspace,
+                           size_t workspace_floats, float* margin_ibp, float* margin_crown, float* slack, float* layer_lo,
+                           float* layer_hi) {
+  const char* fn = "lipasr_mlp_bounds_host";
+  BdShape sh;
+  if (int rc = bd_shape_from(fn, n_layers, widths, bn, &sh)) return rc;
+  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  const BdPlan pl = bd_plan(sh, batch);
+  bool l2 = false;
+  if (int rc = bd_check(fn, sh, pl, params, bnstate, x, eps, norm, clip_lo, clip_hi, y, batch, workspace, workspace_floats, margin_ibp,
+                        margin_crown, slack, layer_lo, layer_hi, &l2))
+    return rc;
+  // the host can look at what the device entry point only flags: eps and y are refused here
+  for (int b = 0; b < batch; ++b) {
+    LP_CHECK_ARG(eps[b] >= 0.0f, "%s: eps[%d] = %g", fn, b, (double)eps[b]);
+    LP_CHECK_ARG(y[b] >= 0 && y[b] < sh.n[sh.L], "%s: y[%d] = %d outside [0,%d)", fn, b, y[b], sh.n[sh.L]);
+  }
+  float* ws = bd_base(workspace);
+  bd_host(sh, pl, params, bnstate, x, eps, l2, clip_lo, clip_hi, y, batch, ws, margin_ibp, margin_crown, slack);
+  if (layer_lo) std::memcpy(layer_lo, ws + pl.offLo, pl.fam * sizeof(float));
+  if (layer_hi) std::memcpy(layer_hi, ws + pl.offHi, pl.fam * sizeof(float));
+  return LIPASR_OK;
+}
+
+}  // extern "C"

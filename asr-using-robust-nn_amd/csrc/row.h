@@ -1,4 +1,4 @@
-// The row contract of the attack kernels (apgd, hsj, genetic, square, smoothing, room, deepfool, lp_attack, jacobian, universal), stated once.
+// The row contract of the attack kernels (apgd, hsj, genetic, square, smoothing, room, deepfool, lp_attack, jacobian, universal, bounds), stated once.
 //
 // A row of n floats is owned quad by quad: quad q is the elements 4q .. 4q + 3, whichever thread takes it.  A quad moves as one
 // float4 where it is whole and its base sits on 16 bytes (the caller says so: `whole`), as four guarded scalars otherwise; the

@@ -143,6 +143,11 @@ PROTOTYPES = {
     "lipasr_universal_apply_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, f32, f32, c_f]),
     "lipasr_universal_reduce_host": (i32, [c_f, c_f, c_f, i32, i32, i32, c_f]),
     "lipasr_universal_step_host": (i32, [c_f, c_f, i32, i32, f32, f32, f32]),
+    "lipasr_mlp_bounds_workspace": (i32, [c_h, i32, C.POINTER(sz)]),
+    "lipasr_mlp_bounds": (i32, [c_h, c_f, c_f, c_f, c_f, f32, f32, f32, c_f, i32, c_f, sz, c_f, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_mlp_bounds_workspace_host": (i32, [i32, PI, i32, C.POINTER(sz)]),
+    "lipasr_mlp_bounds_host": (i32, [i32, PI, PI, c_f, c_f, c_f, c_f, f32, f32, f32, c_f, i32, c_f, sz, c_f, c_f, c_f, c_f, c_f]),
+    "lipasr_debug_bounds_launches": (C.c_long, [i32]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -223,7 +228,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_debug_mfcc_vjp_stage": 690, "lipasr_debug_mfcc_stage_put": 690, "lipasr_universal_shifts": 700,
          "lipasr_universal_apply": 700, "lipasr_universal_reduce": 700, "lipasr_universal_step": 700,
          "lipasr_universal_shifts_host": 700, "lipasr_universal_apply_host": 700, "lipasr_universal_reduce_host": 700,
-         "lipasr_universal_step_host": 700}
+         "lipasr_universal_step_host": 700, "lipasr_mlp_bounds_workspace": 710, "lipasr_mlp_bounds": 710,
+         "lipasr_mlp_bounds_workspace_host": 710, "lipasr_mlp_bounds_host": 710, "lipasr_debug_bounds_launches": 710}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -730,4 +736,78 @@ def debug_table(which: int, sr_in: int = 16000):
     n = check(lib.lipasr_debug_table(which, sr_in, None, 0))
     out = np.zeros(n, dtype=np.float32)
     check(lib.lipasr_debug_table(which, sr_in, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return out
+
+
+BOUNDS_KERNELS = ("prep", "layer", "head", "back", "tail")  # ids of lipasr_debug_bounds_launches
+
+
+def bounds_layout(widths, bn=None):
+    """Offsets (in floats) of lipasr_mlp_create's flat layout for a model given by its widths: per layer a dict with W, b and (BatchNorm)
+    gamma, beta in params and mean, var in bnstate; then (n_params, n_state)."""
+    a4 = lambda v: (v + 3) & ~3
+    po = so = 0
+    out = []
+    L = len(widths) - 1
+    for l in range(L):
+        ni, no = int(widths[l]), int(widths[l + 1])
+        d = {"W": po}
+        po = a4(po + ni * no)
+        d["b"] = po
+        po = a4(po + no)
+        if bn is not None and l + 1 < L and bn[l]:
+            d["gamma"] = po
+            po = a4(po + no)
+            d["beta"] = po
+            po = a4(po + no)
+            d["mean"] = so
+            so = a4(so + no)
+            d["var"] = so
+            so = a4(so + no)
+        out.append(d)
+    return out, po, so
+
+
+def bounds_split_layers(flat, widths, batch):
+    """layer_lo or layer_hi of lipasr_mlp_bounds as (input box [B, n_0], [(z_l, h_l) for the hidden layers])."""
+    b, o = int(batch), 0
+    box = flat[o:o + b * widths[0]].reshape(b, widths[0])
+    o += b * widths[0]
+    layers = []
+    for n in widths[1:-1]:
+        z = flat[o:o + b * n].reshape(b, n)
+        o += b * n
+        h = flat[o:o + b * n].reshape(b, n)
+        o += b * n
+        layers.append((z, h))
+    return box, layers
+
+
+def mlp_bounds_host(widths, bn, params, bnstate, x, eps, norm, y, *, clip_lo=-float("inf"), clip_hi=float("inf"), crown=True,
+                    ws_offset=0):
+    """Host-only: lipasr_mlp_bounds_host on NumPy arrays -> dict(margin_ibp, margin_crown, slack [B, C]; lo, hi: the flat layer
+    boxes).  ws_offset: floats the workspace starts past a 16-byte boundary."""
+    import numpy as np
+
+    widths = [int(w) for w in widths]
+    L = len(widths) - 1
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    b = x.shape[0]
+    params = np.ascontiguousarray(params, dtype=np.float32)
+    bnstate = None if bnstate is None else np.ascontiguousarray(bnstate, dtype=np.float32)
+    eps = _host_in(eps, np.float32, (b,), "eps")
+    y = _host_in(y, np.int32, (b,), "y")
+    wa, ba = int_array(widths), (None if bn is None else int_array(bn))
+    need = sz()
+    check(lib.lipasr_mlp_bounds_workspace_host(L, wa, b, C.byref(need)))
+    ws = np.zeros(need.value + 8, dtype=np.float32)
+    skip = (-(ws.ctypes.data // 4)) % 4 + int(ws_offset)
+    wsv = ws[skip:skip + need.value]
+    fam = b * (widths[0] + 2 * sum(widths[1:-1]))
+    c = widths[-1]
+    out = {"margin_ibp": np.zeros((b, c), np.float32), "margin_crown": np.zeros((b, c), np.float32) if crown else None,
+           "slack": np.zeros((b, c), np.float32) if crown else None, "lo": np.zeros(fam, np.float32), "hi": np.zeros(fam, np.float32)}
+    check(lib.lipasr_mlp_bounds_host(L, wa, ba, _vp(params), _vp(bnstate), _vp(x), _vp(eps), _norm_f(norm), float(clip_lo), float(clip_hi),
+                                     _vp(y), b, _vp(wsv), need.value, _vp(out["margin_ibp"]), _vp(out["margin_crown"]), _vp(out["slack"]),
+                                     _vp(out["lo"]), _vp(out["hi"])))
     return out

@@ -13,6 +13,7 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
     (no prompt: dolphin_attack.m + a microphone model)     attack="dolphin": accuracy against the carrier level
     (no prompt: the Lipschitz read-outs, global and local) attack="lipschitz": lipschitz_report over="mfcc" | "audio"
     (no prompt: certified radius next to DeepFool's)       attack="radius": radius_report over="mfcc" | "audio", --norm 2 | inf
+    (no prompt: certified accuracy by bound propagation)   attack="certify": certify_report --norm inf | 2, --method ibp | crown-ibp
     (no prompt: Auto-PGD, per-row step control, CE or DLR) attack="white", kind="apgd", --loss ce | dlr, --norm inf | 2, over="mfcc" | "audio"
     (no prompt: the genetic query-only attack)             attack="black", kind="genetic": genetic_sweep over="mfcc" | "audio"
     (no prompt: Square Attack, one score query per step)   attack="black", kind="square": square_sweep over="mfcc" | "audio"
@@ -646,29 +647,32 @@ def lipschitz_report(models, train_data, val_data, test_data, over="mfcc", stand
 
 
 def radius_report(models, train_data, val_data, test_data, over="mfcc", standardize="before", test_filenames=None, domain="22k",
-                  norm=2, limit=None, found_by="deepfool", **attack_kw):
+                  norm=2, limit=None, found_by="deepfool", bounds=None, **attack_kw):
     """Per model: how far the test rows are from the decision boundary (get_robustness_radius) -- the quartiles of the certified
     radius (rows of MFCC features and norm 2 only), of the distance to the linearised boundary and of the distance DeepFool found,
     and the share of rows it flipped.  ``over``, ``standardize``, ``test_filenames``, ``domain`` and ``limit`` as in
     lipschitz_report; ``norm``: 2 or np.inf; attack_kw go to attacks.DeepFool.  found_by="hopskipjump": the found distance and
     the flipped share are attacks.HopSkipJump's, which sees the label only, and attack_kw are its keywords.
+    ``bounds``: None, or get_robustness_radius's dict(eps_max=, steps=, method=): only then is "bound_radius" (bound propagation,
+    rows of MFCC features, in ``norm``) computed, returned and printed.
     Returns {model name: {"bound": get_lipschitz_bound(model), "margin", "certified" (or None), "linear", "found", "flipped": the
     per-row arrays, "quartiles": {name: (q25, q50, q75)}, "flipped_share"}}."""
     rows = _TestRows(models, train_data, val_data, test_data, over, standardize, test_filenames, domain, limit)
-    keys = ("margin", "certified", "linear", "found", "flipped")
+    keys = ("margin", "certified", "linear", "found", "flipped") + (("bound_radius",) if bounds is not None else ())
     out = {}
     for name, model in models.items():
         r = {k: np.zeros(rows.n, dtype=bool if k == "flipped" else np.float64) for k in keys}
         for clf, x, lt, idx in rows.batches(model):
-            part = get_robustness_radius(clf, x, norm=norm, lengths=lt, found_by=found_by, **attack_kw)
+            part = get_robustness_radius(clf, x, norm=norm, lengths=lt, found_by=found_by, **({} if bounds is None else {"bounds": bounds}),
+                                         **attack_kw)
             for k in keys:
                 if part[k] is None:  # no certified radius over audio, nor in norm inf
                     r[k] = None
                 else:
                     r[k][idx] = part[k]
         r["bound"] = float(get_lipschitz_bound(model))
-        r["quartiles"] = {k: tuple(float(q) for q in np.percentile(r[k], (25, 50, 75))) for k in ("certified", "linear", "found")
-                          if r[k] is not None and len(r[k])}
+        r["quartiles"] = {k: tuple(float(q) for q in np.percentile(r[k], (25, 50, 75))) for k in ("certified", "bound_radius", "linear", "found")
+                          if r.get(k) is not None and len(r[k])}
         r["flipped_share"] = float(np.mean(r["flipped"])) if len(r["flipped"]) else float("nan")
         out[name] = r
         tag = _tag(name)
@@ -680,7 +684,45 @@ def radius_report(models, train_data, val_data, test_data, over="mfcc", standard
                 print(f"{label} over {what}{tag}: quartiles {q[0]} {q[1]} {q[2]}")
             else:
                 print(f"{label} over {what}{tag}: not given")
+        if "bound_radius" in r["quartiles"]:
+            q = r["quartiles"]["bound_radius"]
+            print(f"Radius certified by bound propagation over {what}{tag}: quartiles {q[0]} {q[1]} {q[2]}")
         print(f"Share of {what} {'HopSkipJump' if found_by == 'hopskipjump' else 'DeepFool'} moved to another class{tag}: {r['flipped_share'] * 100}%")
+    return out
+
+
+def certify_report(models, train_data, val_data, test_data, test_labels, norm=np.inf, method="crown-ibp", standardize="before",
+                   grid=None, points=None, limit=None, eps_max=None, steps=12):
+    """Bound propagation (lipasr.bounds: IBP / CROWN-IBP) per model over the MFCC test rows: the certified accuracy -- the share of
+    rows classified as their label that NO perturbation within eps (in ``norm``: np.inf or 2) moves to another class -- at every
+    eps of the PGD sweep's grid (white_box_sweep(kind="pgd"); ``grid`` / ``points`` as there), which stands UNDER the accuracy any
+    attack leaves at that eps; the median certified radius of a bisection on [0, eps_max] (default: the grid's largest eps); and,
+    for norm 2, the median radius the Lipschitz bound certifies, next to it.  It certifies the base classifier, deterministically.
+    Returns {model name: {"grid", "certified_accuracy" (one per eps), "bound_radius" (per row), "lipschitz_median" (or None)}}."""
+    from .bounds import certified_accuracy, certified_radius
+
+    rows = _TestRows(models, train_data, val_data, test_data, "mfcc", standardize, None, "22k", limit)
+    labels = np.asarray(rows.limited(test_labels)).argmax(axis=1)
+    grid = [float(e) for e in list(np.linspace(1, 30, 50) if grid is None else grid)[:points]]
+    top = float(max(grid)) if eps_max is None else float(eps_max)
+    out = {}
+    for name, model in models.items():
+        clf = rows.classifier(model)
+        r = {"grid": np.asarray(grid), "certified_accuracy": certified_accuracy(clf, rows.x, labels, grid, norm=norm, method=method),
+             "bound_radius": certified_radius(clf, rows.x, norm=norm, eps_max=top, steps=steps, method=method).double().cpu().numpy(),
+             "lipschitz_median": None}
+        if norm == 2 and rows.n and model._n_classes > 1:
+            z = torch.topk(model.predict_device(A._to_dev(rows.x), logits=True).double(), 2, dim=1).values
+            r["lipschitz_median"] = float(np.median((z[:, 0] - z[:, 1]).cpu().numpy() / (np.sqrt(2.0) * get_lipschitz_bound(model))))
+        out[name] = r
+        tag = _tag(name)
+        what = f"{rows.n} test rows"
+        nn = "inf" if norm == np.inf else "2"
+        for e, a in zip(grid, r["certified_accuracy"]):
+            print(f"Certified accuracy ({method}, norm {nn}) over {what}{tag} at eps {e}: {a * 100}%")
+        print(f"Median radius certified by bound propagation over {what}{tag}: {float(np.median(r['bound_radius'])) if rows.n else float('nan')}")
+        if r["lipschitz_median"] is not None:
+            print(f"Median radius the Lipschitz bound certifies over {what}{tag}: {r['lipschitz_median']}")
     return out
 
 
@@ -747,7 +789,7 @@ def main(argv=None):
     ap.add_argument("--constrained", default="bin/models_constrained/model_constrained_Rho01_dropout01.h5")
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
-    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth"], default="black")
+    ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth", "certify"], default="black")
     ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square|hsj; white: fgsm|l2|linf|pgd|apgd|auto|universal|jsma|imperceptible")
     ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
     ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); black square: queries per clip (default: SquareAttack's); white apgd: iterations (default: 100); white universal: passes over the fitting rows at most (default: UniversalPerturbation's)")
@@ -758,6 +800,8 @@ def main(argv=None):
     ap.add_argument("--eps", type=float, default=None, help="white imperceptible: L-inf radius of stage 1, an amplitude (required)")
     ap.add_argument("--learning-rate-1", type=float, default=None, help="white imperceptible: sign-step size of stage 1 (required)")
     ap.add_argument("--learning-rate-2", type=float, default=None, help="white imperceptible: gradient-step size of stage 2 (required)")
+    ap.add_argument("--method", choices=["ibp", "crown-ibp"], default="crown-ibp", help="certify: interval bounds alone, or with the backward relaxation pass")
+    ap.add_argument("--bounds", action="store_true", help="radius: also the radius bound propagation certifies (MFCC rows)")
     ap.add_argument("--sigma", type=float, default=None, help="smooth: standard deviation of the smoothing noise (required)")
     ap.add_argument("--n0", type=int, default=100, help="smooth: draws that select the class")
     ap.add_argument("--n", type=int, default=100000, help="smooth: draws that estimate its vote share")
@@ -773,6 +817,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.attack == "radius" and args.norm == "1":
         raise ValueError("--attack radius runs DeepFool in --norm 2 or inf")
+    if args.attack == "certify" and (args.norm == "1" or args.over != "mfcc"):
+        raise ValueError("--attack certify propagates bounds over MFCC rows in --norm inf or 2")
     universal = args.attack == "white" and args.kind == "universal"
     if (args.shift or args.length is not None) and not universal:
         raise ValueError("--shift and --length go with --kind universal")
@@ -832,7 +878,11 @@ def main(argv=None):
                                 test_filenames=names)
     if args.attack == "radius":
         return radius_report(models, train_data, val_data, test_data, over=args.over, standardize=args.standardize,
-                             test_filenames=names, norm=np.inf if args.norm == "inf" else 2, limit=args.points)
+                             test_filenames=names, norm=np.inf if args.norm == "inf" else 2, limit=args.points,
+                             **({"bounds": {}} if args.bounds else {}))
+    if args.attack == "certify":
+        return certify_report(models, train_data, val_data, test_data, labels, norm=np.inf if args.norm == "inf" else 2,
+                              method=args.method, standardize=args.standardize, points=args.points)
     if args.attack == "smooth":
         return smooth_report(models, train_data, val_data, test_data, labels, args.sigma, n0=args.n0, n=args.n, alpha=args.alpha,
                              over=args.over, standardize=args.standardize, test_filenames=names, limit=args.points)

@@ -1,0 +1,177 @@
+"""Certified robustness of the dense classifier by bound propagation (ours: the reference has no certificate).
+
+Interval bounds (IBP; Gowal et al. 2018) go forward through the dense layers, one backward linear-relaxation pass gives the
+margins (CROWN-IBP; Zhang et al. 2020): lipasr_mlp_bounds, DESIGN.md "Bound propagation".  What comes out is deterministic and
+speaks about the base classifier itself, in norm inf (the threat model of FGSM, PGD, Auto-PGD, Square and AutoAttack) and norm 2:
+
+    bound_margins       lower bounds of z_y - z_k over  {v : ||v - x_b|| <= eps_b} /\\ clip box,  per row and class
+    certified_radius    per row the largest eps of a bisection at which every margin stayed positive
+    certified_accuracy  the share of rows certified at each eps of a grid: the lower end of the bracket whose upper end an attack gives
+
+The estimator is a TensorFlowV2Classifier (rows of MFCC features; its ``clip_values`` are honoured).  A WaveformClassifier is
+refused: the log of the MFCC stage has no interval form here, as ``certified`` is None over audio in get_robustness_radius.
+The bounds hold for the real-arithmetic function of the fp32 weights: every rounding of the propagation itself is accounted for.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _native as N
+from . import estimators as E
+
+METHODS = ("crown-ibp", "ibp")
+
+
+def _check(estimator, norm, method):
+    if getattr(estimator, "extractor", None) is not None or isinstance(estimator, E.WaveformClassifier):
+        raise TypeError("bound propagation needs rows of features (a TensorFlowV2Classifier): over audio the MFCC stage's log has "
+                        "no interval form here, so nothing can be certified through it")
+    if not isinstance(estimator, E.TensorFlowV2Classifier):
+        raise TypeError("estimator must be a lipasr.estimators.TensorFlowV2Classifier")
+    if method not in METHODS:
+        raise ValueError(f"method = {method!r}: one of {METHODS}")
+    norm = N._norm_f(norm)
+    if norm not in (2.0, float("inf")):
+        raise ValueError(f"norm = {norm!r}: inf or 2")
+    return norm
+
+
+def _clip(estimator, clip_values):
+    cv = estimator.clip_values if clip_values is None else clip_values
+    return (-float("inf"), float("inf")) if cv is None else (float(cv[0]), float(cv[1]))
+
+
+def _eps_device(eps, b, device):
+    if torch.is_tensor(eps):
+        et = eps.to(device=device, dtype=torch.float32).reshape(-1)
+    else:
+        e = np.asarray(eps, dtype=np.float64).reshape(-1)
+        if not (e >= 0).all():  # also refuses a NaN
+            raise ValueError("eps must be >= 0")
+        et = torch.as_tensor(e, dtype=torch.float32, device=device)
+    if et.numel() == 1:
+        et = et.expand(b)
+    if et.numel() != b:
+        raise ValueError(f"eps must be a number or one per row ({b}), got {et.numel()}")
+    return et.contiguous()
+
+
+def _labels_device(estimator, xt, y):
+    if y is None:
+        return estimator.own_labels_device(xt).argmax(dim=1).to(torch.int32).contiguous()
+    yt = y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
+    if yt.dim() == 2:
+        yt = yt.argmax(dim=1)
+    yt = yt.to(device=xt.device, dtype=torch.int32).reshape(-1).contiguous()
+    if yt.numel() != xt.shape[0]:
+        raise ValueError(f"y must hold one class per row ({xt.shape[0]}), got {yt.numel()}")
+    return yt
+
+
+class _Workspace:
+    """The device floats lipasr_mlp_bounds works in, grown on demand and kept for the next chunk."""
+
+    def __init__(self, model):
+        self.model, self.buf = model, None
+
+    def get(self, b):
+        need = N.sz()
+        N.check(N.lib.lipasr_mlp_bounds_workspace(self.model._plan, b, N.C.byref(need)))
+        if self.buf is None or self.buf.numel() < need.value:
+            self.buf = torch.empty(need.value, device="cuda", dtype=torch.float32)
+        return self.buf, need.value
+
+
+def _margins(estimator, xt, et, yt, norm, clip, method, ws, details=False):
+    m = estimator.model
+    b, c = xt.shape[0], estimator.nb_classes
+    ibp = torch.empty(b, c, device=xt.device)
+    crown = torch.empty(b, c, device=xt.device) if method == "crown-ibp" else None
+    slack = torch.empty(b, c, device=xt.device) if (details and crown is not None) else None
+    lo = hi = None
+    if details:
+        fam = m._widths[0] + 2 * sum(m._widths[1:-1])
+        lo, hi = torch.empty(b * fam, device=xt.device), torch.empty(b * fam, device=xt.device)
+    bs = estimator.batch_limit
+    o = 0
+    for s in range(0, b, bs):
+        xb = xt[s:s + bs]
+        n = xb.shape[0]
+        buf, floats = ws.get(n)
+        sl = lambda t: None if t is None else t[s:s + bs]
+        fl = None if lo is None else (lo[o:], hi[o:])
+        N.check(N.lib.lipasr_mlp_bounds(m._plan, N.ptr(m._params), N.ptr(m._bnstate), N.ptr(xb), N.ptr(et[s:s + bs]), norm, clip[0], clip[1],
+                                        N.ptr(yt[s:s + bs]), n, N.ptr(buf), floats, N.ptr(ibp[s:s + bs]), N.ptr(sl(crown)), N.ptr(sl(slack)),
+                                        N.ptr(None if fl is None else fl[0]), N.ptr(None if fl is None else fl[1]), N.stream_ptr()))
+        if details:
+            o += n * fam
+    out = ibp if crown is None else torch.maximum(ibp, crown)
+    if details:
+        return out, {"margin_ibp": ibp, "margin_crown": crown, "slack": slack, "lo": lo, "hi": hi}
+    return out
+
+
+def bound_margins(estimator, x, eps, norm=float("inf"), y=None, method="crown-ibp", clip_values=None, details=False):
+    """Lower bounds [B, classes] (device tensor) of z_y - z_k over the input set of every row: eps a number or one per row, y the
+    class per row (ints or one-hot; default the estimator's own label).  Column y holds +inf, a row with a NaN holds NaN.  method
+    "crown-ibp": max(IBP, CROWN-IBP) per entry; "ibp": the interval bounds alone (no backward pass).  A row is certified at its eps
+    when its smallest entry is > 0.  ``details=True`` also returns what the native call wrote, chunk after chunk of batch_limit rows
+    (margin_ibp, margin_crown, slack, and the flat boxes lo / hi of lipasr_mlp_bounds)."""
+    norm = _check(estimator, norm, method)
+    xt = estimator.rows_device(x)
+    if xt.shape[0] == 0:
+        out = torch.empty(0, estimator.nb_classes, device=xt.device)
+        return (out, {}) if details else out
+    et = _eps_device(eps, xt.shape[0], xt.device)
+    yt = _labels_device(estimator, xt, y)
+    return _margins(estimator, xt, et, yt, norm, _clip(estimator, clip_values), method, _Workspace(estimator.model), details)
+
+
+def certified_radius(estimator, x, norm=float("inf"), y=None, eps_max=1.0, steps=12, method="crown-ibp", clip_values=None):
+    """Per row (device tensor [B], float32) the largest eps the bisection tested at which the row was certified: every row carries
+    its own bracket [lo, hi], starting at [0, eps_max] with the first test at eps_max; each of the ``steps`` steps is ONE
+    lipasr_mlp_bounds call per chunk over the whole batch at the rows' current eps.  0 if no tested eps was certified, and 0 for a
+    row that the classifier does not give the class y (with y=None no row is)."""
+    norm = _check(estimator, norm, method)
+    if not (float(eps_max) > 0 and np.isfinite(eps_max)) or int(steps) < 1:
+        raise ValueError("eps_max must be a positive finite number and steps >= 1")
+    xt = estimator.rows_device(x)
+    b = xt.shape[0]
+    if b == 0:
+        return torch.zeros(0, device=xt.device)
+    yt = _labels_device(estimator, xt, y)
+    right = estimator.own_labels_device(xt).argmax(dim=1).to(torch.int32) == yt
+    clip, ws = _clip(estimator, clip_values), _Workspace(estimator.model)
+    lo = torch.zeros(b, device=xt.device)
+    hi = torch.full((b,), float(eps_max), device=xt.device)
+    best = torch.zeros(b, device=xt.device)
+    eps = hi.clone()
+    for _ in range(int(steps)):
+        mm = _margins(estimator, xt, eps, yt, norm, clip, method, ws).amin(dim=1)
+        cert = (mm > 0) & right
+        best = torch.where(cert, torch.maximum(best, eps), best)
+        lo = torch.where(cert, eps, lo)
+        hi = torch.where(cert, hi, eps)
+        eps = ((lo.double() + hi.double()) / 2).float()
+    return best
+
+
+def certified_accuracy(estimator, x, labels, grid, norm=float("inf"), method="crown-ibp", clip_values=None):
+    """float64 NumPy array, one entry per eps of ``grid``: the share of rows that are classified as ``labels`` (ints or one-hot)
+    and certified at that eps -- no perturbation within eps changes their class.  A lower bound of the robust accuracy at eps,
+    as an attack's accuracy is an upper bound."""
+    norm = _check(estimator, norm, method)
+    xt = estimator.rows_device(x)
+    yt = _labels_device(estimator, xt, labels)
+    grid = [float(e) for e in grid]
+    if xt.shape[0] == 0:
+        return np.full(len(grid), np.nan)
+    right = estimator.own_labels_device(xt).argmax(dim=1).to(torch.int32) == yt
+    clip, ws = _clip(estimator, clip_values), _Workspace(estimator.model)
+    out = []
+    for e in grid:
+        et = _eps_device(e, xt.shape[0], xt.device)
+        mm = _margins(estimator, xt, et, yt, norm, clip, method, ws).amin(dim=1)
+        out.append(float(((mm > 0) & right).double().mean().item()))
+    return np.array(out)

@@ -437,7 +437,7 @@ def get_lipschitz_bound(model):
     return bound
 
 
-def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, found_by="deepfool", **attack_kw):
+def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, found_by="deepfool", bounds=None, **attack_kw):
     """Per row of ``x`` the three numbers  certified radius <= distance to the decision boundary <= distance DeepFool found,  as a
     dict of float64 NumPy arrays [B]:
       margin     min over k != c of z_c - z_k on the logits, c the estimator's own class at the row;
@@ -458,6 +458,11 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, fo
       smoothed_class   int64: the class of g at the row, -1 where it abstains.
     It certifies the smoothed classifier, not the base one whose margin, ``certified`` and ``found`` stand next to it; over audio
     and for a model without a useful Lipschitz bound it is the only certified entry.  It is an L2 radius whatever ``norm`` is.
+    ``bounds``: None (default: nothing is added), or dict(eps_max=1.0, steps=12, method="crown-ibp") -- bound propagation
+    (lipasr.bounds.certified_radius) then adds
+      bound_radius     in the call's ``norm`` (2 or inf): the largest eps of a bisection on [0, eps_max] at which IBP / CROWN-IBP
+                       certify the BASE classifier's own class over the whole ball; deterministic, and the only certified entry
+                       in norm inf.  Rows of features only: a WaveformClassifier is refused, as lipasr.bounds refuses it.
     ``estimator``: a TensorFlowV2Classifier or WaveformClassifier of lipasr.estimators (``lengths`` as there)."""
     from .attacks import DeepFool  # attacks imports this module
 
@@ -499,6 +504,10 @@ def get_robustness_radius(estimator, x, norm=2, lengths=None, smoothing=None, fo
         sm = Smooth(estimator, kw.pop("sigma"), seed=kw.pop("seed", 0), clip_values=kw.pop("clip_values", None))
         cert = sm.certify(xt, lengths=lengths, **kw)
         res["smoothed_radius"], res["smoothed_class"] = cert["radius"], cert["class"]
+    if bounds is not None:
+        from .bounds import certified_radius
+
+        res["bound_radius"] = certified_radius(estimator, xt, norm=norm, **dict(bounds)).double().cpu().numpy()
     return res
 
 

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 700. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 710. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -48,6 +48,8 @@
  * 700: universal adversarial perturbations: lipasr_universal_shifts (a shift per row), lipasr_universal_apply (one noise vector on
  * every row), lipasr_universal_reduce (the gradient rows summed back onto the noise, in fp64 and in a fixed order),
  * lipasr_universal_step (the step and projection of the noise) and their _host twins.
+ * 710: certified robustness by bound propagation (IBP and CROWN-IBP): lipasr_mlp_bounds, lipasr_mlp_bounds_workspace, their _host
+ * twins and the test hook lipasr_debug_bounds_launches.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -849,6 +851,54 @@ int lipasr_universal_apply_host(const float* x, const float* noise, const int* o
                                 float clip_lo, float clip_hi, float* out);
 int lipasr_universal_reduce_host(const float* g, const int* offs, const int* n_valid, int batch, int n, int P, double* sums);
 int lipasr_universal_step_host(float* noise, const double* sums, int groups, int P, float norm, float alpha, float eps);
+
+/* ---------------------------------------------------------------- certified robustness by bound propagation (ours)
+ * The reference has no certificate.  For the classifier in inference mode,
+ *     z_l = W_l h_{l-1} + b_l,  h_l = s_l relu(z_l) + t_l,  s = gamma / sqrt(var + 1e-3f), t = beta - s mean (s = 1, t = 0 without
+ *     BatchNorm),  logits = z_L,
+ * and the input set  { v : ||v - x_b||_p <= eps_b } /\ [clip_lo, clip_hi]^n  (p = norm: +INFINITY or 2.0f, else LIPASR_EINVAL; no clip
+ * box: -INFINITY, +INFINITY), lipasr_mlp_bounds writes lower bounds of the margins  z_L[y_b] - z_L[k]  over the whole set:
+ *   margin_ibp[b][k]    interval bounds (Gowal et al. 2018) through the hidden layers, then the difference row W_L[y_b] - W_L[k] on
+ *                       the last hidden box (not the difference of two logit bounds);
+ *   margin_crown[b][k]  (may be NULL: no backward pass) one backward linear-relaxation pass from that difference row down to the
+ *                       input (CROWN-IBP, Zhang et al. 2020): an unstable ReLU takes the line hi / (hi - lo) (z - lo) where its
+ *                       coefficient is negative and, where it is not, z if hi >= -lo and 0 otherwise; at the input the minimum of
+ *                       the linear function over the box coordinate by coordinate, under norm 2 the larger of that and
+ *                       Lambda . x - eps ||Lambda||_2;
+ *   slack[b][k]         (may be NULL; needs margin_crown) what the backward pass subtracted for fp32 / fp64 rounding.
+ * Column k = y_b holds +INFINITY (slack 0): the smallest entry of a row is its certificate, and the row is certified at eps_b when
+ * max(margin_ibp, margin_crown) > 0 in every column.  The bounds hold for the REAL-arithmetic function of the fp32 parameters:
+ * every fp32 sum is widened by gamma_{K+1} S + 2 (K + 1) 2^-149 (S = the sum of magnitudes, gamma_n = n 2^-24 / (1 - n 2^-24)),
+ * every other step is made in fp64 and rounded outward ("Bound propagation").
+ *   layer_lo / layer_hi (may be NULL): the boxes the forward pass kept, one span each:
+ *       [ input box [batch][n_0] | z_1 [batch][n_1] | h_1 [batch][n_1] | z_2 | h_2 | ... ]  over the hidden layers 1 .. L - 1.
+ *   Under norm 2 the first layer is centred on x with the radius min(|W_1|^T r, eps_b ||W_1[:, j]||_2), r the half-width of the box
+ *   around x; the column norms are taken once per call.
+ *   workspace: device floats, any 4-byte alignment, lipasr_mlp_bounds_workspace(m, batch) of them; the library keeps nothing
+ *   between calls.  Widths <= 4096, classes <= 32, batch * classes <= 2^24: LIPASR_EINVAL otherwise, as for a null argument, a
+ *   workspace that is too small, a clip box with clip_lo > clip_hi or a NaN, and an output or the workspace overlapping anything.
+ * eps and y are device arrays: a row with a negative or NaN eps_b, a y_b outside [0, classes) or a NaN in x gets NaN margins and
+ * touches no other row (the host twin, which can look, refuses the first two with LIPASR_EINVAL).
+ * Launches: forward L + 1 (bounds_prep_kernel, L - 1 bounds_layer_kernel, bounds_head_kernel), backward L (L - 1
+ * bounds_back_kernel, bounds_tail_kernel), L = n_layers; two device-to-device copies for layer_lo / layer_hi.  Every sum runs in
+ * one order that depends on the shapes alone (no atomics): two calls give the same bits. */
+int lipasr_mlp_bounds_workspace(lipasr_mlp_t m, int batch, size_t* floats);
+int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x /* [batch][n_0] */,
+                      const float* eps /* [batch] */, float norm, float clip_lo, float clip_hi, const int* y /* [batch] */, int batch,
+                      float* workspace, size_t workspace_floats, float* margin_ibp /* [batch][classes] */,
+                      float* margin_crown /* may be NULL */, float* slack /* may be NULL */, float* layer_lo /* may be NULL */,
+                      float* layer_hi /* may be NULL */, lipasr_stream_t stream);
+/* Host-only (no GPU needed): the same inline functions in plain loops and in the same orders, the same checks, on a model given
+ * by its widths [n_layers + 1] and BatchNorm flags [n_layers] (NULL: none) with params / bnstate in lipasr_mlp_create's layout.
+ * The same values as the device entry point (a zero may differ in sign). */
+int lipasr_mlp_bounds_workspace_host(int n_layers, const int* widths, int batch, size_t* floats);
+int lipasr_mlp_bounds_host(int n_layers, const int* widths, const int* bn, const float* params, const float* bnstate, const float* x,
+                           const float* eps, float norm, float clip_lo, float clip_hi, const int* y, int batch, float* workspace,
+                           size_t workspace_floats, float* margin_ibp, float* margin_crown, float* slack, float* layer_lo,
+                           float* layer_hi);
+/* Test hook: launches since the library was loaded of 0 bounds_prep_kernel, 1 bounds_layer_kernel, 2 bounds_head_kernel,
+ * 3 bounds_back_kernel, 4 bounds_tail_kernel, counted on the host where the launch happens; -1 for an unknown id. */
+long lipasr_debug_bounds_launches(int kernel);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
