@@ -148,6 +148,12 @@ PROTOTYPES = {
     "lipasr_mlp_bounds_workspace_host": (i32, [i32, PI, i32, C.POINTER(sz)]),
     "lipasr_mlp_bounds_host": (i32, [i32, PI, PI, c_f, c_f, c_f, c_f, f32, f32, f32, c_f, i32, c_f, sz, c_f, c_f, c_f, c_f, c_f]),
     "lipasr_debug_bounds_launches": (C.c_long, [i32]),
+    "lipasr_warp_table_host": (i32, [c_f, c_f]),
+    "lipasr_warp_apply": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
+    "lipasr_warp_param_vjp": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
+    "lipasr_warp_apply_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
+    "lipasr_warp_param_vjp_host": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
+    "lipasr_debug_warp_launches": (C.c_long, [i32]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -229,7 +235,9 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_universal_apply": 700, "lipasr_universal_reduce": 700, "lipasr_universal_step": 700,
          "lipasr_universal_shifts_host": 700, "lipasr_universal_apply_host": 700, "lipasr_universal_reduce_host": 700,
          "lipasr_universal_step_host": 700, "lipasr_mlp_bounds_workspace": 710, "lipasr_mlp_bounds": 710,
-         "lipasr_mlp_bounds_workspace_host": 710, "lipasr_mlp_bounds_host": 710, "lipasr_debug_bounds_launches": 710}
+         "lipasr_mlp_bounds_workspace_host": 710, "lipasr_mlp_bounds_host": 710, "lipasr_debug_bounds_launches": 710, "lipasr_warp_table_host": 720,
+         "lipasr_warp_apply": 720, "lipasr_warp_param_vjp": 720, "lipasr_warp_apply_host": 720, "lipasr_warp_param_vjp_host": 720,
+         "lipasr_debug_warp_launches": 720}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -668,6 +676,55 @@ def room_vjp_host(g, rirs, *, n_valid=None, scale=1.0, out=None):
     check(lib.lipasr_room_vjp_host(C.c_void_p(g.ctypes.data), None if nv is None else C.c_void_p(nv.ctypes.data),
                                    C.c_void_p(rirs.ctypes.data), taps, r, b, n, float(scale), _host_array(out, np.float32, (b, n), "out")))
     return out
+
+
+WARP_Z, WARP_P = 16, 512  # zero crossings per wing and table steps per crossing of the time-warp table
+
+
+def warp_table_host():
+    """Host-only: lipasr_warp_table_host -> (win, delta), float32 [WARP_Z * WARP_P + 1] each."""
+    import numpy as np
+
+    win, delta = (np.zeros(WARP_Z * WARP_P + 1, dtype=np.float32) for _ in range(2))
+    check(lib.lipasr_warp_table_host(C.c_void_p(win.ctypes.data), C.c_void_p(delta.ctypes.data)))
+    return win, delta
+
+
+def _warp_host_args(x, params, K, n_valid, table):
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("x must be [B, n]")
+    b, n = x.shape
+    params = _host_in(params, np.float32, (b * int(K), 3), "params")
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    if table is None:
+        table = np.stack(warp_table_host(), axis=1)
+    table = _host_in(table, np.float32, (WARP_Z * WARP_P + 1, 2), "table")
+    return x, params, nv, table, b, n
+
+
+def warp_apply_host(x, params, K, *, n_valid=None, table=None, out=None):
+    """Host-only: lipasr_warp_apply_host on NumPy arrays (x float32 [B, n], params float32 [B * K, 3]) -> float32 [B * K, n]."""
+    import numpy as np
+
+    x, params, nv, table, b, n = _warp_host_args(x, params, K, n_valid, table)
+    out = np.zeros((b * int(K), n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_warp_apply_host(_vp(x), None if nv is None else _vp(nv), _vp(params), _vp(table), b, int(K), n,
+                                     _host_array(out, np.float32, (b * int(K), n), "out")))
+    return out
+
+
+def warp_param_vjp_host(x, g, params, K, *, n_valid=None, table=None):
+    """Host-only: lipasr_warp_param_vjp_host on NumPy arrays (g float32 [B * K, n]) -> float64 [B * K, 3]."""
+    import numpy as np
+
+    x, params, nv, table, b, n = _warp_host_args(x, params, K, n_valid, table)
+    g = _host_in(g, np.float32, (b * int(K), n), "g")
+    gp = np.zeros((b * int(K), 3), dtype=np.float64)
+    check(lib.lipasr_warp_param_vjp_host(_vp(x), _vp(g), None if nv is None else _vp(nv), _vp(params), _vp(table), b, int(K), n, _vp(gp)))
+    return gp
 
 
 UNIVERSAL_GROUP = 64  # LIPASR_UNIVERSAL_GROUP: the rows one slab of lipasr_universal_reduce's sums holds

@@ -24,6 +24,8 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
                                                            over_the_air_sweep, kind="fgsm" | "pgd" | "apgd" | "auto" | "genetic" | "square"
     (no prompt: one noise vector for every clip)           attack="white", kind="universal", --norm inf | 2, over="mfcc" | "audio" [--shift --length P
                                                            --max-iter E --room R]: universal_sweep, fitted on one half, heard on the other
+    (no prompt: worst-case delay, speed and level)         attack="black" (the grid alone) | "white" (--refine N), kind="warp", over="audio"
+                                                           [--max-shift-ms D ... --max-rate R --max-gain-db G --room R]: time_warp_sweep
 """
 from __future__ import annotations
 
@@ -47,6 +49,8 @@ MIXTURE_P = 0.01                                                                
 # ours (the reference has no such sweep): the constant added to the normalised voice before the carrier multiplies it --
 # dolphin_attack.m's 0.001 first, the DolphinAttack paper's 1 last
 DOLPHIN_CARRIER_LEVELS = [0.001, 0.01, 0.1, 0.3, 1.0]
+# ours: the largest delay either way of time_warp_sweep, in milliseconds (100 ms is the shift augmentation of Speech Commands)
+WARP_SHIFTS_MS = [0, 2, 5, 10, 20, 50, 100]
 
 
 def accuracy(predictions, labels_onehot):
@@ -344,6 +348,55 @@ def square_sweep(models, train_data, val_data, test_data, test_labels, over="mfc
     (max_iter, p_init, nb_restarts, ...)."""
     return _query_sweep(lambda clf, item: A.SquareAttack(clf, eps=item, **{"shape": _picture(clf, over), **attack_kw}), "square", models,
                         train_data, val_data, test_data, test_labels, over, standardize, test_filenames, domain, grid, points, limit)
+
+
+def time_warp_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, max_rate=1.0, max_gain_db=0.0,
+                    counts=(9, 3, 3), refine_steps=0, rooms=None, room_taps=2048, room_t60=(0.15, 0.5), room_seed=0, domain="22k",
+                    standardize="before", grid=None, points=None, limit=None):
+    """The time-warp attack (lipasr.attacks.TimeWarp: the worst of a grid of delays, speeds and levels per clip; refine_steps > 0
+    adds its first-order steps) against the largest delay either way, ``grid`` in MILLISECONDS (default WARP_SHIFTS_MS), with
+    ``max_rate``, ``max_gain_db`` and ``counts`` held fixed: per model and delay one accuracy line.  Audio only -- files, lengths
+    and standardisation as in white_box_sweep(over="audio"); the labels are the true ones, so a clip that is wrong when clean
+    counts as wrong at every delay.  A triple found inside a smaller box lies inside every larger one, so a clip's margin at a
+    delay is the smallest found at any delay of the grid up to it: the accuracies cannot rise with the delay.  ``rooms``: the
+    attack and the read-out run through a bank of that many synthetic rooms (OverTheAirClassifier).  An axis whose box has no
+    width (a delay of 0, max_rate 1, max_gain_db 0) is searched with one candidate, not ``counts`` copies of it.
+    Returns (grid, {model name: accuracies})."""
+    rows = _TestRows(models, train_data, val_data, test_data, "audio", standardize, test_filenames, domain, limit)
+    truth = np.asarray(rows.limited(test_labels)).argmax(axis=1)
+    grid = [float(d) for d in list(WARP_SHIFTS_MS if grid is None else grid)[:points]]
+    if any(d < 0 for d in grid):
+        raise ValueError(f"delays in milliseconds, not negative: {grid}")
+    banks = {}
+
+    def through(clf, rate):
+        if rooms is None:
+            return clf
+        from .room import RoomChannel, synthetic_rirs
+
+        if rate not in banks:
+            banks[rate] = RoomChannel(synthetic_rirs(int(rooms), sr=rate, taps=room_taps, t60=room_t60, seed=room_seed))
+        return A.OverTheAirClassifier(clf, banks[rate])
+
+    acc = {name: [] for name in models}
+    for name, model in models.items():
+        margins = np.full((len(grid), rows.n), np.inf)
+        for (sr, _, _, _), (clf, x, lt, idx) in zip(rows._work, rows.batches(model)):
+            rate = 22050 if domain == "22k" else int(sr)
+            est = through(clf, rate)
+            y = torch.as_tensor(truth[idx])
+            for k, ms in enumerate(grid):
+                used = tuple(c if wide else 1 for c, wide in zip(counts, (ms > 0, max_rate > 1.0, max_gain_db > 0.0)))
+                atk = A.TimeWarp(est, max_shift=ms * 1e-3 * rate, max_rate=max_rate, max_gain_db=max_gain_db, counts=used,
+                                 refine_steps=refine_steps)
+                atk.generate_device(x, y, lengths=lt)
+                margins[k, idx] = atk.margins_.cpu().numpy()
+        for k, ms in enumerate(grid):
+            found = margins[[j for j, other in enumerate(grid) if other <= ms]].min(axis=0)
+            a = float(np.mean(found > 0)) if rows.n else float("nan")
+            acc[name].append(a)
+            print(f"Accuracy on time-warped audio test examples{_tag(name)}: {a * 100}% ({ms} ms)")
+    return grid, {k: np.asarray(v) for k, v in acc.items()}
 
 
 def hopskipjump_sweep(models, train_data, val_data, test_data, test_labels, over="mfcc", standardize="before", test_filenames=None,
@@ -790,7 +843,7 @@ def main(argv=None):
     ap.add_argument("--unconstrained", default="bin/models/baseline.h5")
     ap.add_argument("--standardize", choices=["before", "after"], default="before")
     ap.add_argument("--attack", choices=["black", "white", "dolphin", "lipschitz", "radius", "smooth", "certify"], default="black")
-    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square|hsj; white: fgsm|l2|linf|pgd|apgd|auto|universal|jsma|imperceptible")
+    ap.add_argument("--kind", default="simple", help="black: simple|mixture|snr|genetic|square|hsj|warp; white: fgsm|l2|linf|pgd|apgd|auto|universal|jsma|imperceptible|warp")
     ap.add_argument("--pop-size", type=int, default=None, help="black genetic: members per clip (default: GeneticAttack's)")
     ap.add_argument("--max-iter", type=int, default=None, help="black genetic: generations at most (default: GeneticAttack's); black square: queries per clip (default: SquareAttack's); white apgd: iterations (default: 100); white universal: passes over the fitting rows at most (default: UniversalPerturbation's)")
     ap.add_argument("--loss", choices=["ce", "dlr"], default="ce", help="white apgd: cross-entropy or the Difference-of-Logits-Ratio loss")
@@ -812,6 +865,10 @@ def main(argv=None):
     ap.add_argument("--room-seed", type=int, default=0, help="--room: seed of the two banks")
     ap.add_argument("--shift", action="store_true", help="white universal: every clip meets the noise at a random offset")
     ap.add_argument("--length", type=int, default=None, help="white universal: the period of the noise in positions of a row (default: the row width)")
+    ap.add_argument("--max-shift-ms", type=float, nargs="+", default=None, help="kind warp: the grid of largest delays in milliseconds (default: 0 2 5 10 20 50 100)")
+    ap.add_argument("--max-rate", type=float, default=1.0, help="kind warp: speeds from 1 / R to R (1 to 1.25)")
+    ap.add_argument("--max-gain-db", type=float, default=0.0, help="kind warp: levels from -G to +G dB")
+    ap.add_argument("--refine", type=int, default=0, help="white warp: first-order steps on each clip's triple after the grid")
     ap.add_argument("--max-iter-1", type=int, default=1000)
     ap.add_argument("--max-iter-2", type=int, default=4000)
     args = ap.parse_args(argv)
@@ -827,6 +884,14 @@ def main(argv=None):
     if args.attack == "black" and args.kind == "hsj" and args.norm == "1":
         raise ValueError("--kind hsj runs in --norm inf or 2")
 
+    warp = args.attack in ("black", "white") and args.kind == "warp"
+    if warp and args.over != "audio":
+        raise ValueError("--kind warp resamples audio: give --over audio")
+    if warp and args.attack == "black" and args.refine:
+        raise ValueError("--refine takes gradients: give --attack white")
+    if not warp and (args.max_shift_ms is not None or args.max_rate != 1.0 or args.max_gain_db != 0.0 or args.refine):
+        raise ValueError("--max-shift-ms, --max-rate, --max-gain-db and --refine go with --kind warp")
+
     if args.attack == "smooth" and (args.sigma is None or not 0.0 <= args.sigma < float("inf")):
         raise ValueError("--attack smooth needs --sigma, the standard deviation of the noise (finite, not negative; there is no default)")
 
@@ -837,6 +902,10 @@ def main(argv=None):
     names = None
     if args.over == "audio" or args.attack == "dolphin":
         names, labels = _noise_files(args.noise_dir, n_classes)
+    if warp:
+        return time_warp_sweep(models, train_data, val_data, test_data, labels, names, max_rate=args.max_rate, max_gain_db=args.max_gain_db,
+                               refine_steps=args.refine, rooms=args.room, room_taps=args.room_taps, room_t60=tuple(args.room_t60),
+                               room_seed=args.room_seed, standardize=args.standardize, grid=args.max_shift_ms, points=args.points)
     if universal:
         if args.room is not None and args.over != "audio":
             raise ValueError("--room goes with --attack white or black and --over audio")

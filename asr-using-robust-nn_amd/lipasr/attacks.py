@@ -30,6 +30,8 @@ L-inf distance to the nearest misclassified point it can find.
 classified correctly and reports the accuracy that survives all of them.
 ``UniversalPerturbation`` (lipasr/universal.py; ART's name, Moosavi-Dezfooli et al. 2017) fits ONE noise vector for every row --
 the only attack here whose kernels sum across the rows of a batch -- and applies it to rows it never saw.
+``TimeWarp`` (lipasr/warp.py; ours, ART's ``SpatialTransformation`` is the closest name) is the one threat model here that is not
+additive: the worst of a grid of small delays, speeds and levels per clip, then first-order steps on the three parameters.
 """
 from __future__ import annotations
 
@@ -47,6 +49,7 @@ from .keras import to_categorical
 from .square import SquareAttack  # noqa: F401  (Square Attack: one score query per iteration; lipasr/square.py)
 from .hopskipjump import HopSkipJump  # noqa: F401  (HopSkipJump: decisions only, minimum L2 / L-inf norm; lipasr/hopskipjump.py)
 from .universal import UniversalPerturbation  # noqa: F401  (one noise vector for every row; lipasr/universal.py)
+from .warp import TimeWarp  # noqa: F401  (worst-case shift, speed and gain over audio; lipasr/warp.py)
 
 
 # ------------------------------------------------------------------------------------------------ A2

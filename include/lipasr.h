@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 710. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 720. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -50,6 +50,9 @@
  * lipasr_universal_step (the step and projection of the noise) and their _host twins.
  * 710: certified robustness by bound propagation (IBP and CROWN-IBP): lipasr_mlp_bounds, lipasr_mlp_bounds_workspace, their _host
  * twins and the test hook lipasr_debug_bounds_launches.
+ * 720: the time-warp operator: lipasr_warp_apply (every clip resampled under K triples of shift, rate and gain),
+ * lipasr_warp_param_vjp (the derivative with respect to the three parameters), their _host twins, the host-only
+ * lipasr_warp_table_host and the test hook lipasr_debug_warp_launches.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -899,6 +902,51 @@ int lipasr_mlp_bounds_host(int n_layers, const int* widths, const int* bn, const
 /* Test hook: launches since the library was loaded of 0 bounds_prep_kernel, 1 bounds_layer_kernel, 2 bounds_head_kernel,
  * 3 bounds_back_kernel, 4 bounds_tail_kernel, counted on the host where the launch happens; -1 for an unknown id. */
 long lipasr_debug_bounds_launches(int kernel);
+
+/* The time-warp operator (lipasr/warp.py, attacks.TimeWarp; ours -- ART's SpatialTransformation is the image form): every clip
+ * resampled under K triples (shift in samples, rate, linear gain) by band-limited interpolation, in one launch.  x is [clips][n];
+ * params is float32 [clips * K][3], one triple per OUTPUT row, so every clip may carry its own candidates; out and g are
+ * [clips * K][n], row b * K + j being clip b under its candidate j.  n_valid [clips] (or NULL: n for every clip) holds POSITIONS IN
+ * THE ROW, clamped to [0, n]; nv below is the clamped value.
+ * The interpolation kernel is a Kaiser-windowed sinc, tabulated as resampy tabulates its own: Z = 16 zero crossings per wing, P = 512
+ * table steps per crossing, win[i] = sinc(i / P) kaiser(beta = 8.6) for i = 0 .. Z P, computed in float64 and rounded once to fp32,
+ * with win[0] = 1 and win[k P] = 0 EXACTLY for k = 1 .. Z; delta[i] = fp32(win[i + 1] - win[i]), delta[Z P] = 0
+ * (lipasr_warp_table_host writes both, Z P + 1 floats each).  `table` is the two interleaved, float32 [Z P + 1][2] = (win, delta).
+ * The cutoff is Nyquist and there is no roll-off, so that integer positions reproduce samples exactly; the price is paid near
+ * Nyquist, where 16 crossings are too few: a sine at 0.8 of Nyquist is interpolated to 4e-5 of its amplitude, one at 0.9 to 7e-2,
+ * one at 0.95 to 0.36 ("Time warp").  The 22 050 Hz rows of 16 kHz files hold nothing above 0.73 of Nyquist.  The cutoff
+ * does not follow the rate either: a rate above 1 aliases whatever the clip holds above 1 / rate of Nyquist.
+ *   For t < nv, in fp64:  c = (nv - 1) / 2,  u = c + rate (t - c) - shift,  n0 = floor(u),  f = u - n0   (rate warps about the
+ *   clip's centre; a positive shift delays);  idx = f P, j0 = (int)idx, eta = (float)(idx - j0).
+ *   acc, an fp32 fmaf chain from 0 with every tap weight w = fmaf(eta, delta[j], win[j]): first the left wing i = 0 .. Z - 1, sample
+ *   n0 - i at table index j0 + i P; then the right wing from idx' = (1 - f) P in the same way, k = 0 .. Z - 1, sample n0 + 1 + k.
+ *   A source position outside [0, nv) is absent, as is a table index beyond Z P.
+ *   out[row][t] = gain * acc (one fp32 rounding) for t < nv, 0 for nv <= t < n.
+ * lipasr_warp_param_vjp writes gp, float64 [clips * K][3] (any 4-byte boundary).  With dxu[t] the same chain over the slopes
+ * (delta[j] * P on the left wing, -delta[j] * P on the right; the exact derivative of the table's piecewise-linear form):
+ *   gp[row][0] = sum_t g gain (-dxu),   gp[row][1] = sum_t (g gain dxu) (t - c),   gp[row][2] = sum_t g acc,   all over t < nv,
+ * the products and sums in fp64: thread t mod 512 adds its terms in ascending t, then row.h's block_sum_d (a butterfly per
+ * wavefront, then the 8 wavefronts in index order).
+ * Both: one launch, no workspace, nothing allocated or synchronised, no atomics: two runs give the same bits, and a clip's rows
+ * have the bits they would have if the clip were launched alone.  Any n up to 2^24, any K >= 1, any 4-byte alignment of every
+ * pointer.  LIPASR_OK without a launch when clips, K or n is 0; LIPASR_EINVAL, before the device is touched, for a null pointer
+ * (n_valid excepted), n above 2^24, or an output that overlaps an input.  Signals are taken as finite.  A row whose triple is not
+ * finite, or whose rate lies outside [0.5, 2], is written as NaN over [0, nv) (gp: three NaN) and touches no other row. */
+int lipasr_warp_apply(const float* x /* [clips][n] */, const int* n_valid, const float* params /* [clips * K][3] */,
+                      const float* table /* [Z P + 1][2] */, int clips, int K, int n, float* out /* [clips * K][n] */,
+                      lipasr_stream_t stream);
+int lipasr_warp_param_vjp(const float* x, const float* g /* [clips * K][n] */, const int* n_valid, const float* params,
+                          const float* table, int clips, int K, int n, double* gp /* [clips * K][3] */, lipasr_stream_t stream);
+/* Host-only (no GPU needed): the table, and the same chains in the same order on host arrays (general path only, absent taps left
+ * out where the device multiplies a staged zero): the same bits as the device entry points on finite signals.  Same checks. */
+int lipasr_warp_table_host(float* win /* [Z P + 1] */, float* delta /* [Z P + 1] */);
+int lipasr_warp_apply_host(const float* x, const int* n_valid, const float* params, const float* table, int clips, int K, int n,
+                           float* out);
+int lipasr_warp_param_vjp_host(const float* x, const float* g, const int* n_valid, const float* params, const float* table, int clips,
+                               int K, int n, double* gp);
+/* Test hook: launches since the library was loaded of 0 warp_kernel<false> (apply), 1 warp_kernel<true> (param_vjp), counted on the
+ * host where the launch happens; -1 for an unknown id. */
+long lipasr_debug_warp_launches(int kernel);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
