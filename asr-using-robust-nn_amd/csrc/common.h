@@ -139,8 +139,4 @@ int lp_norm_code(const char* fn, float norm, int* code);
 int lp_step_launch(float* x_adv, const float* x0, const float* g, int rows, int n, int norm, float alpha, float eps,
                    hipStream_t st);
 
-// spectral.hip: lipasr_project_product with an optional device counter bumped by its single-workgroup kernel
-int project_product_bump(lipasr_handle_t h, float* const* Ws, const int* rows, const int* cols, int n_layers, float rho,
-                         const int* order, int n_order, float* norms_out, int* bump, lipasr_stream_t stream);
-
 }  // namespace lipasr

@@ -15,7 +15,7 @@
 //           C > 20 would need 528, more than a lane has, and takes RB = 12 over block pairs (MULTI: rows re-read from L2, 3.4 x at
 //           C = 32; no model of the project has more than 20 classes).
 //   eigen   cyclic Jacobi on G in fp64 in LDS, round-robin (tournament) ordering so that C / 2 disjoint rotations run at once -- the
-//           scheme of sv_clip_kernel (spectral.hip), restated here because that one is written into its kernel's LDS carving.
+//           scheme of sv_clip_kernel (spectral_clip.hip), restated here because that one is written into its kernel's LDS carving.
 //           lambda_max -> sigma = sqrt(lambda_max) 2^-ex, its eigenvector -> u (largest component positive).
 //   v       only when asked: v[k] = (sum_c u[c] J[c][k]) / sigma on the scaled values, a third read.  A column of zeros gives
 //           fmaf(u, 0, +0) = +0 whatever u is: v stays exactly zero past the end of a ragged clip.

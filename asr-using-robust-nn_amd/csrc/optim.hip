@@ -1,6 +1,7 @@
 // K5 (Keras-form Adam + NonNeg over the flat parameter buffer), K4 (stand-alone sign step),
 // A2 (StandardScaler fit / apply) and the plan-level wrappers of the K3 projections.
 #include "mlp.h"
+#include "spectral.h"
 
 namespace lipasr {
 

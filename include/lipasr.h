@@ -1284,7 +1284,7 @@ long lipasr_debug_group_launches(int family, int arith, int variant);
 int lipasr_debug_gemm(lipasr_handle_t h, int arith, int transA, int transB, int M, int N, int K, const float* A, int lda,
                       const float* B, int ldb, float* C, int ldc, float scale_a, float scale_b, lipasr_stream_t stream);
 
-/* Test hook: launches since the library was loaded of one K3 kernel (csrc/spectral.hip), counted on the host where the launch
+/* Test hook: launches since the library was loaded of one K3 kernel (csrc/spectral_*.hip), counted on the host where the launch
  * happens.  kernel: 0 / 1 / 2 chain_step_kernel<12> / <20> / <32> (at most 12 / 20 / 32 classes), 3 chain_head_kernel, 4 product_sigma_kernel,
  * 5 scale_layers_kernel, 6 sigma_scale_layers_kernel, 7 pi_u_kernel, 8 pi_v_kernel, 9 pi_finish_kernel, 10 sv_clip_kernel,
  * 11 the Frobenius pair (sumsq_clamped_kernel + frob_scale_kernel: one count per pair), 12 bn_correction_kernel.  Returns -1 for an

@@ -1,4 +1,4 @@
-"""Every K3 Lipschitz-projection kernel path (csrc/spectral.hip) against float64, and proof of which kernels ran.
+"""Every K3 Lipschitz-projection kernel path (csrc/spectral.hip and spectral_*.hip) against float64, and proof of which kernels ran.
 
 Every case goes through the raw C entry points with ctypes, so that pointers, alignment and iteration counts are the test's:
 
@@ -6,7 +6,7 @@ Every case goes through the raw C entry points with ctypes, so that pointers, al
     "aligned" kernel starts at a multiple of 4 floats, an "unaligned" one at a multiple of 4 plus 1); outputs have a sentinel tail.
     The sentinels must survive: the scaling kernels rewrite the model's weights in place.
   * kernels: every case names the kernels it is meant to run in a module-level table, with the launch counts written out by hand
-    from the selector's rules (launch_chain, project_product_bump, run_power_iteration); lipasr_debug_k3_launches must show that
+    from the selector's rules (launch_chain, sigma_fused_fits, run_power_iteration); lipasr_debug_k3_launches must show that
     exactly those counters moved by exactly those amounts.
   * float64: a product norm against the chain multiplied in float64 and numpy.linalg.svd; whole passes against
     oracle.constraints_ref; clipping against the float64 SVD.
