@@ -22,6 +22,12 @@ struct MlpLayer {
 constexpr float kBnMomentum = 0.99f;  // Keras BatchNormalization defaults (train_constraints.py:68)
 constexpr float kBnEps = 1e-3f;
 
+// Test hook (lipasr_debug_k2_launches): launches since load per kernel of the training step that is not a GEMM, counted on the
+// host where the launch happens.  The ids are part of the ABI (include/lipasr.h): append, never renumber.
+enum K2Kernel { K2_BN_FWD = 0, K2_DROPOUT_FWD, K2_BN_BWD, K2_PART_REDUCE, K2_SOFTMAX_CE, K2_SOFTMAX_VJP, K2_SOFTMAX_VJP_ONEHOT,
+                K2_ADAM_NONNEG, K2_STEP_INC, K2_KERNELS };
+extern long g_k2_launches[K2_KERNELS];  // mlp.hip
+
 }  // namespace lipasr
 
 struct lipasr_mlp {

@@ -5,6 +5,8 @@
 
 namespace lipasr {
 
+long g_k2_launches[K2_KERNELS] = {};
+
 // arithmetic mode of a plan's GEMM + the fp16 range scales of mode 2 by operand kind.  Powers of two (exact): activations and
 // features unscaled (|x| < 65504; BatchNorm outputs are O(1): their low plane is a normal fp16 number down to |x| = 0.12 and loses
 // bits gradually below, on values that weigh little in a sum), kernels x 2^12 (|w| < 16), gradients x 2^8 / 2^floor(log2 g0) where g0 is the
@@ -699,6 +701,7 @@ static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstat
         hipLaunchKernelGGL(part_reduce_kernel, dim3((L.n_out + 255) / 256), dim3(256), 0, st, part,
                            gemm_row_tiles(0, 1, g), L.n_out);
         LP_LAUNCH_CHECK();
+        ++g_k2_launches[K2_PART_REDUCE];
       }
     }
     if (!last && L.bn) ++cur;  // exchange point: the partial sums of a, a^2 are complete
@@ -718,6 +721,7 @@ static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstat
       const dim3 grid((L.n_out + 127) / 128, (batch + kApplyRows - 1) / kApplyRows);
       hipLaunchKernelGGL(bn_apply_fwd_kernel, grid, apply_block, 0, st, b);
       LP_LAUNCH_CHECK();
+      ++g_k2_launches[b.has_bn ? K2_BN_FWD : K2_DROPOUT_FWD];
     }
     hin = (!last && L.offH != L.offA) ? (ws + L.offH) : outp;
   }
@@ -727,6 +731,7 @@ static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstat
                        C, inv_batch, probs ? probs : (ws + m->offProb), ws + m->offDzLast, loss_rows, correct_rows,
                        (float*)nullptr);
     LP_LAUNCH_CHECK();
+    ++g_k2_launches[K2_SOFTMAX_CE];
   }
 
   // ---- backward.  The dX chain runs first, layer by layer (dX GEMM fused with the dropout backward and the
@@ -767,6 +772,7 @@ static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstat
         hipLaunchKernelGGL(part_reduce_kernel, dim3((P.n_out + 255) / 256), dim3(256), 0, st, part,
                            gemm_row_tiles(0, 0, gx), P.n_out);
         LP_LAUNCH_CHECK();
+        ++g_k2_launches[K2_PART_REDUCE];
       }
     }
     if (P.bn) ++cur;  // exchange point: the partial sums of g, g xhat are complete
@@ -783,6 +789,7 @@ static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstat
       const dim3 grid((P.n_out + 127) / 128, (batch + kApplyRows - 1) / kApplyRows);
       hipLaunchKernelGGL(bn_apply_bwd_kernel, grid, apply_block, 0, st, b);
       LP_LAUNCH_CHECK();
+      ++g_k2_launches[K2_BN_BWD];
     }
   }
   // [dW ; db] = [lin ; 1]^T[n_in+1][B] * gin[B][n_out] for every layer: the all-ones row yields the bias gradient
@@ -906,6 +913,7 @@ int lipasr_mlp_predict(lipasr_mlp_t m, const float* params, const float* bnstate
     hipLaunchKernelGGL(softmax_ce_kernel, dim3((batch + 255) / 256), dim3(256), 0, S(stream), lg, (const float*)nullptr,
                        batch, C, 0.0f, probs, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
     LP_LAUNCH_CHECK();
+    ++g_k2_launches[K2_SOFTMAX_CE];
   }
   return LIPASR_OK;
 }
@@ -923,6 +931,7 @@ int lipasr_mlp_own_labels(lipasr_mlp_t m, const float* params, const float* bnst
   hipLaunchKernelGGL(softmax_ce_kernel, dim3((batch + 255) / 256), dim3(256), 0, S(stream), lg, (const float*)nullptr,
                      batch, C, 0.0f, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, y_onehot_out);
   LP_LAUNCH_CHECK();
+  ++g_k2_launches[K2_SOFTMAX_CE];
   return LIPASR_OK;
 }
 
@@ -939,6 +948,7 @@ static int attack_common(lipasr_mlp_t m, const float* params, const float* bnsta
                        1.0f / (float)batch, m->ws + m->offProb, m->ws + m->offDzLast, (float*)nullptr, (float*)nullptr,
                        (float*)nullptr);
     LP_LAUNCH_CHECK();
+    ++g_k2_launches[K2_SOFTMAX_CE];
   }
   return backward_infer(m, params, bnstate, batch, dx, x_adv, x0, alpha, eps, st, 1.0f / (float)batch);
 }
@@ -997,6 +1007,7 @@ int lipasr_mlp_output_vjp(lipasr_mlp_t m, const float* params, const float* bnst
   hipLaunchKernelGGL(softmax_vjp_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, lg, v, batch, C, on_logits ? 1 : 0,
                      probs_out, m->ws + m->offDzLast);
   LP_LAUNCH_CHECK();
+  ++g_k2_launches[K2_SOFTMAX_VJP];
   return backward_infer(m, params, bnstate, batch, dx, nullptr, nullptr, 0.0f, 0.0f, st);
 }
 
@@ -1025,6 +1036,7 @@ int lipasr_mlp_jacobian(lipasr_mlp_t m, const float* params, const float* bnstat
     hipLaunchKernelGGL(softmax_vjp_onehot_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, lg, c, batch, C, on_logits ? 1 : 0,
                        c == 0 ? probs_out : (float*)nullptr, m->ws + m->offDzLast);
     LP_LAUNCH_CHECK();
+    ++g_k2_launches[K2_SOFTMAX_VJP_ONEHOT];
     rc = backward_infer(m, params, bnstate, batch, jac + (size_t)c * stride_c, nullptr, nullptr, 0.0f, 0.0f, st, 1.0f, (int)stride_b);
     if (rc != LIPASR_OK) return rc;
   }
@@ -1073,6 +1085,34 @@ int lipasr_mlp_set_compute(lipasr_mlp_t m, int mode) {
       }
   }
   m->compute_bf16 = mode;
+  return LIPASR_OK;
+}
+
+// ---------------------------------------------------------------- test hooks of the training step's own kernels
+long lipasr_debug_k2_launches(int kernel) { return (kernel >= 0 && kernel < K2_KERNELS) ? g_k2_launches[kernel] : -1; }
+
+int lipasr_debug_mlp_stage(lipasr_mlp_t m, int layer, int which, int batch, float* out, lipasr_stream_t stream) {
+  LP_CHECK_ARG(m != nullptr && out != nullptr, "lipasr_debug_mlp_stage: null argument");
+  LP_CHECK_ARG(layer >= 0 && layer < m->n_layers, "lipasr_debug_mlp_stage: layer %d outside [0, %d)", layer, m->n_layers);
+  LP_CHECK_ARG(batch >= 1 && batch <= m->max_batch, "lipasr_debug_mlp_stage: batch %d outside [1, %d]", batch, m->max_batch);
+  const MlpLayer& L = m->L[layer];
+  const bool last = layer == m->n_layers - 1;
+  const float* src = nullptr;
+  size_t n = (size_t)batch * L.n_out;
+  switch (which) {
+    case 0: if (!last) src = m->ws + L.offA; break;
+    case 1: if (!last) src = m->ws + L.offH; break;
+    case 2: if (!last && L.bn) { src = m->ws + L.offMean; n = 2 * (size_t)L.n_out; } break;
+    case 3: src = m->ws + (last ? m->offDzLast : L.offDz); break;
+    case 4: if (!last && L.bn) src = m->ws + m->offG0; break;
+    case 5: if (last) src = m->ws + m->offLogits; break;
+    case 6: if (last) src = m->ws + m->offProb; break;
+    default: break;
+  }
+  LP_CHECK_ARG(src != nullptr, "lipasr_debug_mlp_stage: layer %d has no stage %d (0 A, 1 H, 2 [mean | rstd], 3 dz, 4 g, 5 logits, 6 probabilities)",
+               layer, which);
+  DeviceGuard g(m->ctx->device);
+  LP_HIP(hipMemcpyAsync(out, src, n * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
   return LIPASR_OK;
 }
 

@@ -12,7 +12,8 @@ struct SegTable {
 };
 
 // One launch over the flat buffers.  t = *step_dev + 1; lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (Keras
-// optimizer_v2.Adam, epsilon outside the square root and not bias-corrected).
+// optimizer_v2.Adam, epsilon outside the square root and not bias-corrected).  NonNeg is Keras' w * (w >= 0): a negative weight
+// becomes 0 and a NaN stays a NaN, so a poisoned step cannot leave healthy-looking weights behind.
 // flag (may be null): a lipasr_flag_wait counter that receives `flag_value` when this kernel STARTS, i.e. when everything the
 // stream ran before it -- the whole forward / backward pass -- has finished (lipasr_mlp_adam_project_product_signal).
 __global__ __launch_bounds__(256) void adam_nonneg_kernel(float* __restrict__ w, const float* __restrict__ g,
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void adam_nonneg_kernel(float* __restrict__ w,
     mv.c = mv.c * b1 + gg * ob1;                     \
     vv.c = vv.c * b2 + (gg * gg) * ob2;              \
     float x = wv.c - lr_t * mv.c / (sqrtf(vv.c) + eps); \
-    wv.c = (nn && !(x >= 0.0f)) ? 0.0f : x;          \
+    wv.c = (nn && x < 0.0f) ? 0.0f : x;              \
   }
     LP_ADAM1(x) LP_ADAM1(y) LP_ADAM1(z) LP_ADAM1(w)
 #undef LP_ADAM1
@@ -160,11 +161,13 @@ static int adam_launch(lipasr_mlp_t m, float* params, const float* grads, float*
   hipLaunchKernelGGL(adam_nonneg_kernel, dim3(blocks), dim3(256), 0, S(stream), params, grads, adam_m, adam_v, n4, segs,
                      step_dev, lr, beta1, beta2, eps, grad_scale, flag, flag_value);
   LP_LAUNCH_CHECK();
+  ++g_k2_launches[K2_ADAM_NONNEG];
   if (bump_step) {
     // a second one-thread launch: a last-workgroup ticket inside the Adam kernel measured 11 us slower (atomics
     // from 1-2 K workgroups on one address) than this 4.6 us launch
     hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, S(stream), step_dev);
     LP_LAUNCH_CHECK();
+    ++g_k2_launches[K2_STEP_INC];
   }
   return LIPASR_OK;
 }

@@ -208,6 +208,8 @@ PROTOTYPES = {
     "lipasr_debug_k1_vjp_launches": (C.c_long, [i32]),
     "lipasr_debug_mfcc_vjp_stage": (i32, [c_h, i32, i32, c_f, c_s]),
     "lipasr_debug_mfcc_stage_put": (i32, [c_h, i32, i32, c_f, c_s]),
+    "lipasr_debug_k2_launches": (C.c_long, [i32]),
+    "lipasr_debug_mlp_stage": (i32, [c_h, i32, i32, i32, c_f, c_s]),
     "lipasr_debug_gemm": (i32, [c_h, i32, i32, i32, i32, i32, i32, c_f, i32, c_f, i32, c_f, i32, f32, f32, c_s]),
     "lipasr_flag_signal": (i32, [c_h, C.c_void_p, i32, c_s]),
     "lipasr_flag_wait": (i32, [c_h, C.c_void_p, i32, i32, C.c_void_p, c_s]),
@@ -237,7 +239,7 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_universal_step_host": 700, "lipasr_mlp_bounds_workspace": 710, "lipasr_mlp_bounds": 710,
          "lipasr_mlp_bounds_workspace_host": 710, "lipasr_mlp_bounds_host": 710, "lipasr_debug_bounds_launches": 710, "lipasr_warp_table_host": 720,
          "lipasr_warp_apply": 720, "lipasr_warp_param_vjp": 720, "lipasr_warp_apply_host": 720, "lipasr_warp_param_vjp_host": 720,
-         "lipasr_debug_warp_launches": 720}
+         "lipasr_debug_warp_launches": 720, "lipasr_debug_k2_launches": 730, "lipasr_debug_mlp_stage": 730}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 

@@ -53,6 +53,9 @@
  * 720: the time-warp operator: lipasr_warp_apply (every clip resampled under K triples of shift, rate and gain),
  * lipasr_warp_param_vjp (the derivative with respect to the three parameters), their _host twins, the host-only
  * lipasr_warp_table_host and the test hook lipasr_debug_warp_launches.
+ * 730: test hooks of the training step's own kernels: lipasr_debug_k2_launches (launch counters per kernel) and
+ * lipasr_debug_mlp_stage (an activation, the saved statistics, a gradient, the logits or the probabilities that a classifier plan's
+ * last call left behind).  The NonNeg clamp of lipasr_mlp_adam_nonneg keeps a NaN weight (it wrote 0 before).
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -1331,6 +1334,28 @@ int lipasr_debug_mfcc_vjp_stage(lipasr_mfcc_t p, int which, int batch, float* ou
  * (DCT^T, top_db floor, dB -> mel) a tile with exact ties or elements exactly on the floor; the later steps recompute X from the
  * signal and do not read the tile.  The next forward call overwrites them.  LIPASR_EINVAL as for lipasr_debug_mfcc_stage. */
 int lipasr_debug_mfcc_stage_put(lipasr_mfcc_t p, int which, int batch, const float* in, lipasr_stream_t stream);
+
+/* Test hook: launches since the library was loaded of one of the training step's own kernels (K2 without the GEMMs, K5), counted on
+ * the host where the launch happens.  kernel: 0 bn_apply_fwd_kernel with BatchNorm, 1 bn_apply_fwd_kernel as dropout only (a layer
+ * with dropout and no BatchNorm), 2 bn_apply_bwd_kernel, 3 part_reduce_kernel (synchronized BatchNorm: lipasr_mlp_train_segment),
+ * 4 softmax_ce_kernel, 5 softmax_vjp_kernel, 6 softmax_vjp_onehot_kernel, 7 adam_nonneg_kernel, 8 step_inc_kernel.  The BatchNorm
+ * and softmax arithmetic that runs inside a GEMM's epilogue (the exchange epilogue, softmax + CE of at most 32 classes) counts in
+ * lipasr_debug_gemm_launches.  Returns -1 for an unknown id, so a test can enumerate the kernels from the library. */
+long lipasr_debug_k2_launches(int kernel);
+
+/* Test hook: ONE asynchronous device-to-device copy, on `stream`, of an intermediate that the plan's last call left in the plan's
+ * workspace, into out (device), rows packed at the layer's width n_out.  which 0: A_l, the post-ReLU output [batch][n_out]; 1: H_l,
+ * after BatchNorm and dropout (A_l itself on a layer with neither); 2: the saved [mean | rstd], [2][n_out], of a training-mode
+ * forward; 3: dz_l, the gradient at the pre-activation (for the last layer: at the logits, whichever call wrote it last); 4: the g
+ * buffer bn_apply_bwd_kernel read for layer l, dh times dropout [batch][n_out], as the last launch-chain backward of that layer
+ * left it; 5: the logits [batch][classes]; 6: the probabilities [batch][classes] the plan kept (a call that was given a `probs` or
+ * `logits` destination of the caller's writes there instead).  0, 1, 2 and 4 exist on hidden layers only, 2 and 4 only with
+ * BatchNorm, 5 and 6 on the last layer only.  g is ONE buffer for all layers: a whole step overwrites it layer by layer (what is
+ * left belongs to the first BatchNorm layer), and the exchange epilogue never writes it -- read it after running only that layer's
+ * segment through lipasr_mlp_train_segment, or on a plan with one BatchNorm layer and lipasr_mlp_set_fuse_bn(plan, 0).
+ * LIPASR_EINVAL for a null argument, a layer out of range, a batch outside [1, max_batch] or a `which` the layer does not have.  No
+ * synchronisation, no allocation. */
+int lipasr_debug_mlp_stage(lipasr_mlp_t m, int layer, int which, int batch, float* out, lipasr_stream_t stream);
 
 /* Profiling knob: how many of the leading (small) steps of the product chain W_m^T ... W_1^T run as ONE launch
  * (chain_head_kernel, fp32 matrix instructions): -1 = automatic (the first two steps, when their panels have <= 256 columns

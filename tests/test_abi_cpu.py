@@ -67,6 +67,25 @@ def test_k1_backward_hooks_without_gpu():
         assert "null argument" in N.last_error()
 
 
+def test_k2_launch_counters_and_stage_hook_without_gpu():
+    """lipasr_debug_k2_launches and lipasr_debug_mlp_stage (version 730): both exported and declared; the counters are host-side and
+    readable without a GPU, -1 for an id that does not exist, and the known ids are exactly 0..8 as include/lipasr.h lists them; the
+    copy hook refuses null arguments before it touches a device."""
+    names = ("lipasr_debug_k2_launches", "lipasr_debug_mlp_stage")
+    assert N.lib.lipasr_version() >= 730 and all(N.has(n) and hasattr(N.lib, n) and N.SINCE[n] == 730 and n in N.PROTOTYPES for n in names)
+    assert all(n in declared_symbols() for n in names)
+    assert N.lib.lipasr_debug_k2_launches(0) >= 0
+    assert N.lib.lipasr_debug_k2_launches(-1) == -1 and N.lib.lipasr_debug_k2_launches(9) == -1 and N.lib.lipasr_debug_k2_launches(1000) == -1
+    assert [k for k in range(64) if N.lib.lipasr_debug_k2_launches(k) >= 0] == list(range(9))
+    assert N.lib.lipasr_debug_mlp_stage(None, 0, 0, 1, None, None) == N.EINVAL
+    assert "null argument" in N.last_error()
+    import ctypes
+
+    dst = ctypes.c_float()
+    assert N.lib.lipasr_debug_mlp_stage(None, 0, 0, 1, ctypes.byref(dst), None) == N.EINVAL  # a null plan with a destination
+    assert "null argument" in N.last_error()
+
+
 def test_error_convention_without_gpu():
     assert N.lib.lipasr_create(0, None) == N.EINVAL
     assert "out is null" in N.last_error()
