@@ -1,5 +1,5 @@
 // The dense classifier's GEMM interface: what a launch is told (GemmArgs, its epilogues and dropout arguments), the grouped
-// launch's argument block, and the host entry points of gemm.hip that the plan (mlp.hip) calls.  The choice of a kernel
+// launch's argument block, and the host entry points of gemm.hip that the plan (mlp_train.hip, mlp_infer.hip) calls.  The choice of a kernel
 // (pick_gemm) and the launchers live in gemm.hip; the tile kernels live in one translation unit per family (gemm_frag.hip,
 // gemm_lds.hip, gemm_ring.hip, gemm_ring_group.hip, gemm_ring2.hip), each of which registers its instances in the GemmTable.
 #pragma once
@@ -86,7 +86,7 @@ struct GemmArgs {
   DropArgs drop;           // EPI_DH_STATS / EPI_DZ_NOBN
   int ones_row;            // AMODE 1 only: row M-1 of op(A) is all ones (bias gradient = column sums of B)
   float* extra_out;        // its output row goes here instead of C
-  // EPI_BIAS_SOFTMAX_CE (what softmax_ce_kernel computes, fused): labels in, the rest optional outputs
+  // EPI_BIAS_SOFTMAX_CE (softmax_ce_kernel's softmax and first argmax, and the cross-entropy, fused): labels in, the rest optional outputs
   const float* y;          // [M][N] one-hot
   float inv_batch;
   float* prob;             // [M][N]

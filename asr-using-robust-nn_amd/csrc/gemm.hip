@@ -6,8 +6,8 @@
 //   gemm_ring.hip        64x64 LDS-DMA ring tile (gemm_ring_tile.h), arithmetic mode 2
 //   gemm_ring_group.hip  128x128 weight-gradient ring tiles and the grouped launch of arithmetic mode 2
 //   gemm_ring2.hip       128x64 exchange ring tile of arithmetic mode 2
-// with the device code they share in gemm_device.h.  The BatchNorm / dropout / softmax-CE kernels and the plan-level forward /
-// backward / predict / attack sequences that call these launchers are mlp.hip.
+// with the device code they share in gemm_device.h.  The plan-level sequences that call these launchers are mlp_train.hip (the
+// training step, with the BatchNorm / dropout kernels) and mlp_infer.hip (predict / attacks / class gradients, with the softmax kernels).
 #include "gemm.h"
 #include <algorithm>
 #include <cstdint>

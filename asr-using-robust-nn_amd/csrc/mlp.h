@@ -1,4 +1,5 @@
-// The dense-classifier plan shared by mlp.hip (forward/backward) and optim.hip (Adam, projections).
+// The dense-classifier plan, shared by mlp.hip (the plan itself), mlp_train.hip (the training step), mlp_infer.hip (predict, attacks,
+// class gradients), optim.hip (Adam, projections) and bounds.hip, and what the three mlp units share among themselves.
 #pragma once
 #include "common.h"
 
@@ -28,6 +29,9 @@ enum K2Kernel { K2_BN_FWD = 0, K2_DROPOUT_FWD, K2_BN_BWD, K2_PART_REDUCE, K2_SOF
                 K2_ADAM_NONNEG, K2_STEP_INC, K2_KERNELS };
 extern long g_k2_launches[K2_KERNELS];  // mlp.hip
 
+// rows of the column partials [2][row tiles][width]: the *_STATS epilogues leave one slab per 32-row tile at the most
+inline int part_row_tiles(int max_batch) { return (max_batch + 31) / 32; }
+
 }  // namespace lipasr
 
 struct lipasr_mlp {
@@ -39,7 +43,7 @@ struct lipasr_mlp {
   size_t n_params = 0, n_state = 0;
   float* ws = nullptr;  // workspace
   size_t ws_floats = 0;
-  size_t offLogits = 0, offProb = 0, offDzLast = 0, offG0 = 0, offG1 = 0, offG2 = 0, offPart = 0;
+  size_t offLogits = 0, offProb = 0, offDzLast = 0, offG0 = 0, offG1 = 0, offPart = 0;
   int compute_bf16 = 0;  // lipasr_mlp_set_compute: 0 exact fp32, 1 GEMM operands rounded to bf16 at the MFMA, 2 fp16 two-plane split (fp32 accumulate)
   float last_inv_batch = 1.0f;  // the loss-gradient bound of the last training forward (mode 2's gradient scale in lipasr_mlp_train_dw0)
   int lds_min_tiles = 0;  // lipasr_mlp_set_gemm_tiles: training GEMMs take the LDS-tiled kernel from this many 64x64 tiles (0 = default)
@@ -58,3 +62,18 @@ struct lipasr_mlp {
   size_t xc_gran_off[2][LIPASR_MAX_LAYERS] = {};  // [forward | backward][layer], in granules
   size_t xc_ctrl_off[2][LIPASR_MAX_LAYERS] = {};  // in 32-bit words
 };
+
+// What mlp.hip defines for mlp_train.hip and mlp_infer.hip; it stays out of the library's exported symbols.
+namespace lipasr {
+struct GemmArgs;  // gemm.h
+enum OperandKind { OP_ACT = 0, OP_WEIGHT = 1, OP_GRAD = 2 };
+#pragma GCC visibility push(hidden)
+int plan_cus(const lipasr_mlp* m);  // the CUs the plan's stream may use
+// arithmetic mode, CU budget and the fp16 range scales of mode 2 by operand kind; g0: bound of the gradient at the logits
+void set_arith(GemmArgs& g, const lipasr_mlp* m, int kind_a, int kind_b, float g0 = 1.0f, bool training = true);
+// an entry point's prologue: "null plan", "batch outside [1, max_batch]" and, for a plan with BatchNorm state, "bnstate is null";
+// check_batch: the first two, for the entry points that take no bnstate
+int check_batch(const char* fn, const lipasr_mlp* m, int batch);
+int check_call(const char* fn, const lipasr_mlp* m, int batch, const float* bnstate);
+#pragma GCC visibility pop
+}  // namespace lipasr

@@ -1,6 +1,6 @@
 """The training step's own kernels stage by stage against float64, and proof of which kernels ran: adam_nonneg_kernel / step_inc_kernel
-(csrc/optim.hip), bn_apply_fwd_kernel / bn_apply_bwd_kernel / part_reduce_kernel and the three softmax forms (csrc/mlp.hip), and the
-second copies of that arithmetic in the GEMM epilogues (EPI_BIAS_RELU_BNX / EPI_DH_BNX, EPI_BIAS_SOFTMAX_CE; csrc/gemm_device.h,
+(csrc/optim.hip), bn_apply_fwd_kernel / bn_apply_bwd_kernel / part_reduce_kernel (csrc/mlp_train.hip) and the three softmax forms
+(csrc/mlp_infer.hip), and the second copies of that arithmetic in the GEMM epilogues (EPI_BIAS_RELU_BNX / EPI_DH_BNX, EPI_BIAS_SOFTMAX_CE; csrc/gemm_device.h,
 gemm_frag.hip).  In the manner of test_mfcc_instances_gpu.py:
 
   * memory: every array the test owns (params, grads, m, v, the step word, x, y, masks, the `part` buffer, every destination of
@@ -39,11 +39,7 @@ pytestmark = pytest.mark.gpu
 (BN_FWD, DROPOUT_FWD, BN_BWD, PART_REDUCE, SOFTMAX_CE, SOFTMAX_VJP, SOFTMAX_VJP_ONEHOT, ADAM, STEP_INC) = range(9)
 K2_NAMES = ("bn_apply_fwd_kernel", "bn_apply_fwd_kernel (dropout only)", "bn_apply_bwd_kernel", "part_reduce_kernel", "softmax_ce_kernel",
             "softmax_vjp_kernel", "softmax_vjp_onehot_kernel", "adam_nonneg_kernel", "step_inc_kernel")
-UNREACHABLE = {
-    "softmax_ce_kernel inside lipasr_mlp_train_fwd_bwd and inside lipasr_mlp_input_grad / _attack_step":
-        "both launch it only for more than 32 classes, and lipasr_mlp_create refuses 33 (test_create_refuses_33_classes); at most 32 "
-        "classes take EPI_BIAS_SOFTMAX_CE",
-}
+UNREACHABLE = {}  # what no case can run -> why (nothing today)
 FRAG4 = 0
 EPI_STATS, EPI_DH_STATS, EPI_DZ_NOBN, EPI_SOFTMAX_CE, EPI_BNX, EPI_DH_BNX = 6, 7, 8, 9, 10, 11
 SEG_W, SEG_B, SEG_GAMMA, SEG_BETA, SEG_MMEAN, SEG_MVAR = range(6)
@@ -584,8 +580,74 @@ def test_synchronized_batchnorm_two_plans_one_process(cuda):
     _held(case, (BN_BWD,), "dgamma of both plans", o["grads0"][og:og + N_].astype(np.float64) + o["grads1"][og:og + N_], dgm, bdg)
 
 
+def test_segments_of_a_plan_with_two_batchnorm_layers_out_of_three(cuda):
+    """Widths (5, 9, 33, 7, 3), BatchNorm on the second and third hidden layer only, no dropout, 7 rows on a plan for 10: the exchange
+    points are forward layer 1 (33 wide), forward layer 2 (7), backward layer 2, backward layer 1 -- five segments, 66, 14, 14, 66
+    floats to exchange and none after the last.  The five segments in order on one plan (caller-owned `part`, stat_batch 7,
+    grad_scale 1, nothing between them: one rank's sum is itself) against ONE lipasr_mlp_train_fwd_bwd on the launch chain of a second,
+    identical plan: the same bits everywhere.  Seven rows are one row tile, part_reduce_kernel over one tile stores (float)(double)x,
+    and the apply kernels read one tile on both paths."""
+    N = _native()
+    widths, bn, B, max_batch = (5, 9, 33, 7, 3), (0, 1, 1, 0), 7, 10
+    rng = np.random.default_rng(20251)
+    tensors, state = {}, {}
+    for l in range(4):
+        tensors[(l, SEG_W)] = 0.4 * rng.standard_normal((widths[l], widths[l + 1]))
+        tensors[(l, SEG_B)] = 0.1 * rng.standard_normal(widths[l + 1])
+        if bn[l]:
+            tensors[(l, SEG_GAMMA)] = 1.0 + 0.1 * rng.standard_normal(widths[l + 1])
+            tensors[(l, SEG_BETA)] = 0.1 * rng.standard_normal(widths[l + 1])
+            state[(l, SEG_MMEAN)] = 0.1 * rng.standard_normal(widths[l + 1])
+            state[(l, SEG_MVAR)] = 1.0 + 0.5 * rng.random(widths[l + 1])
+    x = rng.standard_normal((B, widths[0])).astype(np.float32)
+    y = np.eye(widths[-1], dtype=np.float32)[rng.integers(0, widths[-1], B)]
+    stages = [(l, w) for l in range(3) for w in (0, 1, 3)] + [(1, 2), (2, 2), (3, 3)]
+
+    def run():
+        out = {}
+        for name in ("segments", "chain"):
+            with Mlp(widths, bn, (0, 0, 0, 0), (0, 0, 0, 0), max_batch, fuse=0) as plan:
+                bufs = dict(params=Buf((plan.n_params,), plan.flat(tensors)), bnstate=Buf((plan.n_state,), plan.flat(state, True)), x=Buf(x.shape, x),
+                            y=Buf(y.shape, y), grads=Buf((plan.n_params,)), loss=Buf((B,)), correct=Buf((B,)), probs=None)
+                cfg = N.DropoutCfg()
+                cfg.mode = 0
+                before = _snapshot()
+                if name == "segments":
+                    ns, pf, ex = C.c_int(), N.sz(), N.sz()
+                    N.check(N.lib.lipasr_mlp_train_segments(plan.h, C.byref(ns)))
+                    assert ns.value == 5
+                    sizes = []
+                    for seg in range(5):
+                        N.check(N.lib.lipasr_mlp_train_segment_exchange(plan.h, B, seg, C.byref(ex)))
+                        sizes.append(ex.value)
+                    assert sizes == [66, 14, 14, 66, 0]
+                    N.check(N.lib.lipasr_mlp_part_floats(plan.h, C.byref(pf)))
+                    part = Buf((pf.value,))
+                    for seg in range(5):
+                        _train_call(plan, None, B, cfg, seg=seg, part=part, stat_batch=B, grad_scale=1.0, bufs=bufs)
+                    _assert_moved(before, {PART_REDUCE: 4, BN_FWD: 2, BN_BWD: 2}, "two-of-three segments")
+                    part.read()
+                else:
+                    _train_call(plan, None, B, cfg, bufs=bufs)
+                    _assert_moved(before, {BN_FWD: 2, BN_BWD: 2}, "two-of-three chain")
+                assert plan.errors() == 0
+                for l, w in stages:
+                    out[f"{name}-stage{l}{w}"] = plan.stage(l, w, B)
+                for k, b in (("grads", "grads"), ("state", "bnstate"), ("loss", "loss"), ("correct", "correct")):
+                    out[f"{name}-{k}"] = bufs[b].read()
+                for k in ("params", "x", "y"):
+                    bufs[k].read()
+        return out
+
+    o = _twice(run)
+    for k in [k[len("chain-"):] for k in o if k.startswith("chain-")]:
+        assert _same(o[f"segments-{k}"], o[f"chain-{k}"]), f"{k}: the five segments and the one call differ"
+    assert np.isfinite(o["chain-grads"]).all() and np.abs(o["chain-stage03"]).max() > 0 and np.isfinite(o["chain-loss"]).all()
+    _record("two-of-three segments", (PART_REDUCE,), 0.0, "same bits as the launch chain")
+
+
 # ====================================================================================================== softmax
-SOFTMAX_CASES = [(C_, B) for C_ in (1, 2, 10, 32) for B in (1, 255, 257)]
+SOFTMAX_CASES =[(C_, B) for C_ in (1, 2, 10, 32) for B in (1, 255, 257)]
 
 
 def _identity(plan, C_):
