@@ -154,6 +154,11 @@ PROTOTYPES = {
     "lipasr_warp_apply_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
     "lipasr_warp_param_vjp_host": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
     "lipasr_debug_warp_launches": (C.c_long, [i32]),
+    "lipasr_defence_apply": (i32, [c_f, c_f, PI, PI, PV, i32, i32, i32, c_f, c_s]),
+    "lipasr_defence_vjp": (i32, [c_f, c_f, c_f, PI, PI, PV, i32, i32, i32, c_f, c_s]),
+    "lipasr_defence_apply_host": (i32, [c_f, c_f, PI, PI, PV, i32, i32, i32, c_f]),
+    "lipasr_defence_vjp_host": (i32, [c_f, c_f, c_f, PI, PI, PV, i32, i32, i32, c_f]),
+    "lipasr_debug_defence_launches": (C.c_long, [i32]),
     "lipasr_mlp_attack_step": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, c_s]),
     "lipasr_mlp_attack_step_lp": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, i32, f32, f32, f32, c_s]),
     "lipasr_mlp_own_labels": (i32, [c_h, c_f, c_f, c_f, i32, c_f, c_s]),
@@ -239,7 +244,8 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_universal_step_host": 700, "lipasr_mlp_bounds_workspace": 710, "lipasr_mlp_bounds": 710,
          "lipasr_mlp_bounds_workspace_host": 710, "lipasr_mlp_bounds_host": 710, "lipasr_debug_bounds_launches": 710, "lipasr_warp_table_host": 720,
          "lipasr_warp_apply": 720, "lipasr_warp_param_vjp": 720, "lipasr_warp_apply_host": 720, "lipasr_warp_param_vjp_host": 720,
-         "lipasr_debug_warp_launches": 720, "lipasr_debug_k2_launches": 730, "lipasr_debug_mlp_stage": 730}
+         "lipasr_debug_warp_launches": 720, "lipasr_debug_k2_launches": 730, "lipasr_debug_mlp_stage": 730, "lipasr_defence_apply": 740,
+         "lipasr_defence_vjp": 740, "lipasr_defence_apply_host": 740, "lipasr_defence_vjp_host": 740, "lipasr_debug_defence_launches": 740}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -727,6 +733,51 @@ def warp_param_vjp_host(x, g, params, K, *, n_valid=None, table=None):
     gp = np.zeros((b * int(K), 3), dtype=np.float64)
     check(lib.lipasr_warp_param_vjp_host(_vp(x), _vp(g), None if nv is None else _vp(nv), _vp(params), _vp(table), b, int(K), n, _vp(gp)))
     return gp
+
+
+DEFENCE_MEDIAN, DEFENCE_FIR, DEFENCE_QUANTIZE = 0, 1, 2  # LIPASR_DEFENCE_*
+DEFENCE_MAX_STAGES, DEFENCE_MAX_HALO = 4, 256
+
+
+def defence_chain(stages, taps_ptrs):
+    """The three host arrays of a defence chain (include/lipasr.h, lipasr_defence_apply) from ``stages``, a list of (kind, arg)
+    with kind one of DEFENCE_*, and ``taps_ptrs``, one address (or None) per stage: (kinds, args, taps, count)."""
+    return (int_array([k for k, _ in stages]), int_array([a for _, a in stages]), ptr_array(taps_ptrs), len(stages))
+
+
+def _defence_host_args(x, stages, n_valid):
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("x must be [B, n]")
+    b, n = x.shape
+    nv = None if n_valid is None else _host_in(n_valid, np.int32, (b,), "n_valid")
+    keep = [None if t is None else np.ascontiguousarray(t, dtype=np.float32).reshape(-1) for _, _, t in stages]
+    chain = defence_chain([(k, int(a)) for k, a, _ in stages], [None if t is None else t.ctypes.data for t in keep])
+    return x, nv, keep, chain, b, n
+
+
+def defence_apply_host(x, stages, *, n_valid=None, out=None):
+    """Host-only: lipasr_defence_apply_host on NumPy arrays.  x float32 [B, n]; ``stages``: a list of (kind, arg, taps) with kind
+    one of DEFENCE_*, arg the width, tap count or bits and taps a float32 array for a FIR stage (None otherwise) -> float32 [B, n]."""
+    import numpy as np
+
+    x, nv, keep, (kinds, args, taps, count), b, n = _defence_host_args(x, stages, n_valid)
+    out = np.zeros((b, n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_defence_apply_host(_vp(x), _vp(nv), kinds, args, taps, count, b, n, _host_array(out, np.float32, (b, n), "out")))
+    return out
+
+
+def defence_vjp_host(x, g, stages, *, n_valid=None, out=None):
+    """Host-only: lipasr_defence_vjp_host on NumPy arrays (x and the cotangent g float32 [B, n]) -> float32 [B, n]."""
+    import numpy as np
+
+    x, nv, keep, (kinds, args, taps, count), b, n = _defence_host_args(x, stages, n_valid)
+    g = _host_in(g, np.float32, (b, n), "g")
+    out = np.zeros((b, n), dtype=np.float32) if out is None else out
+    check(lib.lipasr_defence_vjp_host(_vp(x), _vp(g), _vp(nv), kinds, args, taps, count, b, n, _host_array(out, np.float32, (b, n), "out")))
+    return out
 
 
 UNIVERSAL_GROUP = 64  # LIPASR_UNIVERSAL_GROUP: the rows one slab of lipasr_universal_reduce's sums holds

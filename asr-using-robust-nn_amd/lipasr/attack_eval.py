@@ -26,6 +26,8 @@ windows) is left to the caller: every sweep returns ``(grid, {model name: accura
                                                            --max-iter E --room R]: universal_sweep, fitted on one half, heard on the other
     (no prompt: worst-case delay, speed and level)         attack="black" (the grid alone) | "white" (--refine N), kind="warp", over="audio"
                                                            [--max-shift-ms D ... --max-rate R --max-gain-db G --room R]: time_warp_sweep
+    (no prompt: a defence that cleans the input)           attack="white" | "black", over="audio", --defence median:5,lowpass:4000:101,quantize:8
+                                                           [--defence-backward chain | identity --detect-fpr F]: defended_sweep, the kinds of --room
 """
 from __future__ import annotations
 
@@ -441,6 +443,16 @@ def hopskipjump_sweep(models, train_data, val_data, test_data, test_labels, over
 OVER_THE_AIR_KINDS = ("fgsm", "pgd", "apgd", "auto", "genetic", "square")
 
 
+def _radius_attacks(attack_kw):
+    """kind -> build(estimator over audio, eps): the attacks of OVER_THE_AIR_KINDS with ``attack_kw`` as their keywords."""
+    return {"fgsm": lambda clf, e: A.FastGradientMethod(estimator=clf, eps=e, **attack_kw),
+            "pgd": lambda clf, e: A.ProjectedGradientDescent(estimator=clf, eps=e, **attack_kw),
+            "apgd": lambda clf, e: A.AutoProjectedGradientDescent(estimator=clf, eps=e, **attack_kw),
+            "auto": lambda clf, e: A.AutoAttack(clf, eps=e, **{"eps_step": 2.0 * e, "shape": None, **attack_kw}),
+            "genetic": lambda clf, e: A.GeneticAttack(clf, e, **attack_kw),
+            "square": lambda clf, e: A.SquareAttack(clf, eps=e, **{"shape": None, **attack_kw})}
+
+
 def over_the_air_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, kind="pgd", rooms=4, room_taps=2048,
                        room_t60=(0.15, 0.5), room_seed=0, domain="22k", standardize="before", grid=None, points=None, limit=None,
                        **attack_kw):
@@ -456,12 +468,7 @@ def over_the_air_sweep(models, train_data, val_data, test_data, test_labels, tes
     rows (22 050 Hz for domain="22k").  Returns (grid, {model name: {"clean" | "dry" | "air": accuracies}})."""
     from .room import RoomChannel, synthetic_rirs
 
-    builders = {"fgsm": lambda clf, e: A.FastGradientMethod(estimator=clf, eps=e, **attack_kw),
-                "pgd": lambda clf, e: A.ProjectedGradientDescent(estimator=clf, eps=e, **attack_kw),
-                "apgd": lambda clf, e: A.AutoProjectedGradientDescent(estimator=clf, eps=e, **attack_kw),
-                "auto": lambda clf, e: A.AutoAttack(clf, eps=e, **{"eps_step": 2.0 * e, "shape": None, **attack_kw}),
-                "genetic": lambda clf, e: A.GeneticAttack(clf, e, **attack_kw),
-                "square": lambda clf, e: A.SquareAttack(clf, eps=e, **{"shape": None, **attack_kw})}
+    builders = _radius_attacks(attack_kw)
     if kind not in builders:
         raise ValueError(f"a room takes an attack that optimises within a radius -- {', '.join(OVER_THE_AIR_KINDS)} -- not {kind!r}")
     rooms = int(rooms)
@@ -496,6 +503,78 @@ def over_the_air_sweep(models, train_data, val_data, test_data, test_labels, tes
                 a = float(hits[k].mean()) if rows.n else float("nan")
                 acc[name][k].append(a)
                 print(f"Accuracy through {rooms} held-out rooms on {label}{_tag(name)}: {a * 100}% ({item})")
+    return grid, {name: {k: np.asarray(v) for k, v in d.items()} for name, d in acc.items()}
+
+
+def defended_sweep(models, train_data, val_data, test_data, test_labels, test_filenames, defence, kind="pgd", backward="chain",
+                   detect_fpr=0.05, domain="22k", standardize="before", grid=None, points=None, limit=None, **attack_kw):
+    """An input-transformation defence under attack (lipasr.defences, estimators.DefendedClassifier).  ``defence``: the text form
+    lipasr.defences.parse_defence takes, e.g. "median:5,lowpass:4000:101,quantize:8"; its taps are designed at the rate of the rows
+    (22 050 Hz for domain="22k").  Per model and grid point four numbers:
+        "undefended"  accuracy of the model on adversarial clips made against it
+        "static"      accuracy of the DEFENDED model on those same clips: the attacker does not know of the defence
+        "adaptive"    accuracy of the defended model on clips made against itself: the attacker differentiates through the defence
+                      (backward="chain") or takes it as the identity on the way back (backward="identity", BPDA); a query attack
+                      simply queries the defended model
+        "detected"    the share of the static clips that lipasr.defences.TransformationDetector flags at the false-positive rate
+                      ``detect_fpr``.  The threshold is fitted on the clean FIRST half of every batch of files (the split
+                      universal_sweep makes), and the flagged share is that of the static clips of the SECOND halves.
+    ``kind``: one of OVER_THE_AIR_KINDS; the labels the attacks push away from are each estimator's own.  Files, lengths,
+    standardisation and default grids as in over_the_air_sweep.  Returns (grid, {model name: {the four names: values per point}})."""
+    from .defences import AudioDefence, TransformationDetector, parse_defence
+
+    builders = _radius_attacks(attack_kw)
+    if kind not in builders:
+        raise ValueError(f"a defence is put under an attack that optimises within a radius -- {', '.join(OVER_THE_AIR_KINDS)} -- not {kind!r}")
+    if backward not in ("chain", "identity"):
+        raise ValueError(f"backward={backward!r}: 'chain' or 'identity'")
+    if not 0.0 <= float(detect_fpr) <= 1.0:
+        raise ValueError(f"detect_fpr = {detect_fpr}: a share in [0, 1]")
+    parse_defence(defence, 22050)  # a wrong text is refused before anything touches a device
+    rows = _TestRows(models, train_data, val_data, test_data, "audio", standardize, test_filenames, domain, limit)
+    labels = rows.limited(test_labels)
+    truth = np.asarray(labels).argmax(axis=1)
+    grid = list((GENETIC_AUDIO_EPS if kind in ("genetic", "square") else AUDIO_SIGMAS) if grid is None else grid)[:points]
+    chains = {}  # rate of the rows -> AudioDefence
+
+    def chain(rate):
+        if rate not in chains:
+            chains[rate] = AudioDefence(parse_defence(defence, rate))
+        return chains[rate]
+
+    keys = ("undefended", "static", "adaptive", "detected")
+    acc = {name: {k: [] for k in keys} for name in models}
+    for item in grid:
+        for name, model in models.items():
+            hits = {k: np.zeros(rows.n, dtype=bool) for k in keys[:3]}
+            clean_scores, static_scores = [], []
+            for (sr, _, _, _), (clf, x, lt, idx) in zip(rows._work, rows.batches(model)):
+                d = chain(22050 if domain == "22k" else int(sr))
+                defended = A.DefendedClassifier(clf, d, backward=backward)
+                static = build_or_keep(builders[kind], clf, item, x, lt)
+                adaptive = build_or_keep(builders[kind], defended, item, x, lt)
+                for k, est, rows_k in (("undefended", clf, static), ("static", defended, static), ("adaptive", defended, adaptive)):
+                    hits[k][idx] = est.predict_device(rows_k, lengths=lt, logits=True).argmax(dim=1).cpu().numpy() == truth[idx]
+                half = x.shape[0] // 2
+                cut = lambda t, s: None if t is None else t[s]
+                det = TransformationDetector(clf, [d])
+                clean_scores.append(det.scores(x[:half].contiguous(), cut(lt, slice(0, half))).cpu().numpy())
+                static_scores.append(det.scores(static[half:].contiguous(), cut(lt, slice(half, None))).cpu().numpy())
+            clean_scores, static_scores = np.concatenate(clean_scores), np.concatenate(static_scores)
+            if len(clean_scores) and len(static_scores):
+                det.fit_scores(clean_scores, detect_fpr)
+                threshold, rate = det.threshold, float(np.mean(det.flag_scores(static_scores)))
+            else:
+                threshold = rate = float("nan")
+            for k, label in (("undefended", "Accuracy of the undefended model on adversarial audio"),
+                             ("static", "Accuracy of the defended model on adversarial audio made against the undefended one (static)"),
+                             ("adaptive", f"Accuracy of the defended model on adversarial audio made against itself (adaptive, backward {backward})")):
+                a = float(hits[k].mean()) if rows.n else float("nan")
+                acc[name][k].append(a)
+                print(f"{label}{_tag(name)}: {a * 100}% ({item})")
+            acc[name]["detected"].append(rate)
+            print(f"Detector hit rate on the static adversarial audio at false-positive rate {detect_fpr}{_tag(name)}: {rate * 100}% ({item}); "
+                  f"threshold {threshold} from {len(clean_scores)} clean clips, {len(static_scores)} adversarial clips scored")
     return grid, {name: {k: np.asarray(v) for k, v in d.items()} for name, d in acc.items()}
 
 
@@ -863,6 +942,9 @@ def main(argv=None):
     ap.add_argument("--room-taps", type=int, default=2048, help="--room: samples of each room impulse response")
     ap.add_argument("--room-t60", type=float, nargs=2, default=(0.15, 0.5), metavar=("LO", "HI"), help="--room: range of the reverberation time in seconds")
     ap.add_argument("--room-seed", type=int, default=0, help="--room: seed of the two banks")
+    ap.add_argument("--defence", default=None, metavar="SPEC", help="white|black over audio: an input-transformation defence in front of the models, e.g. median:5,lowpass:4000:101,quantize:8 (also bandpass:LO:HI[:TAPS]) -- accuracy undefended, static, adaptive and the detector's hit rate")
+    ap.add_argument("--defence-backward", choices=["chain", "identity"], default="chain", help="--defence: the adaptive attack differentiates through the defence, or takes it as the identity on the way back (BPDA)")
+    ap.add_argument("--detect-fpr", type=float, default=0.05, help="--defence: false-positive rate the detector's threshold is fitted to on the clean half")
     ap.add_argument("--shift", action="store_true", help="white universal: every clip meets the noise at a random offset")
     ap.add_argument("--length", type=int, default=None, help="white universal: the period of the noise in positions of a row (default: the row width)")
     ap.add_argument("--max-shift-ms", type=float, nargs="+", default=None, help="kind warp: the grid of largest delays in milliseconds (default: 0 2 5 10 20 50 100)")
@@ -895,6 +977,16 @@ def main(argv=None):
     if args.attack == "smooth" and (args.sigma is None or not 0.0 <= args.sigma < float("inf")):
         raise ValueError("--attack smooth needs --sigma, the standard deviation of the noise (finite, not negative; there is no default)")
 
+    if args.defence is None and (args.defence_backward != "chain" or args.detect_fpr != 0.05):
+        raise ValueError("--defence-backward and --detect-fpr go with --defence")
+    if args.defence is not None:
+        if args.attack not in ("white", "black") or args.over != "audio" or warp or universal:
+            raise ValueError("--defence goes with --attack white or black and --over audio (kinds " + ", ".join(OVER_THE_AIR_KINDS) + ")")
+        if args.room is not None:
+            raise ValueError("--defence and --room are two sweeps: give one of them")
+        if args.kind not in OVER_THE_AIR_KINDS:
+            raise ValueError(f"--defence takes an attack that optimises within a radius -- {', '.join(OVER_THE_AIR_KINDS)} -- not {args.kind!r}")
+
     train_data, _, val_data, _, test_data, test_label = A.load_npy_dataset(args.path)
     n_classes = int(test_label.max()) + 1
     labels = to_categorical(test_label, n_classes)
@@ -913,7 +1005,7 @@ def main(argv=None):
         return universal_sweep(models, train_data, val_data, test_data, labels, over=args.over, standardize=args.standardize,
                                test_filenames=names, norm=np.inf if args.norm == "inf" else 2, rooms=args.room, room_taps=args.room_taps,
                                room_t60=tuple(args.room_t60), room_seed=args.room_seed, points=args.points, random_shift=args.shift, **kw)
-    if args.room is not None:
+    if args.room is not None or args.defence is not None:
         if args.attack not in ("white", "black") or args.over != "audio":
             raise ValueError("--room goes with --attack white or black and --over audio")
         kw = {k: v for k, v in (("pop_size", args.pop_size if args.kind == "genetic" else None),
@@ -924,6 +1016,10 @@ def main(argv=None):
             kw["norm"] = int(args.norm)
         if args.kind == "apgd":
             kw["loss_type"] = {"ce": "cross_entropy", "dlr": "difference_logits_ratio"}[args.loss]
+        if args.defence is not None:
+            return defended_sweep(models, train_data, val_data, test_data, labels, names, args.defence, kind=args.kind,
+                                  backward=args.defence_backward, detect_fpr=args.detect_fpr, standardize=args.standardize,
+                                  points=args.points, **kw)
         return over_the_air_sweep(models, train_data, val_data, test_data, labels, names, kind=args.kind, rooms=args.room,
                                   room_taps=args.room_taps, room_t60=tuple(args.room_t60), room_seed=args.room_seed,
                                   standardize=args.standardize, points=args.points, **kw)

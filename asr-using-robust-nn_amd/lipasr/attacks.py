@@ -19,6 +19,8 @@ each clip and the rest of the row comes back untouched.  Over a short-window ext
 441, hop 220) the gradient goes through lipasr_mfcc_plan_vjp_short.
 ``OverTheAirClassifier`` puts a bank of room impulse responses (lipasr/room.py) in front of a WaveformClassifier and answers with
 the expectation over the rooms: every attack over audio, white-box or black-box, then optimises the example that is PLAYED.
+``DefendedClassifier`` puts an input-transformation defence (lipasr/defences.py: median, FIR and bit-depth stages) in front of a
+WaveformClassifier: every attack over audio then differentiates through the defence, or takes it as the identity on the way back.
 
 Black-box: ``standardize_dataset`` (A2, fp64-accumulated fit on the device), the audio-domain noise
 models on the device (Philox RNG) and the noisy-audio -> MFCC dataset helpers.  ``GeneticAttack`` (lipasr/genetic.py,
@@ -42,7 +44,7 @@ import torch
 
 from . import _native as N
 from ._rows import check_estimator, clip_pair, generate_host, labels_device, resolve_clip_values
-from .estimators import OverTheAirClassifier, TensorFlowV2Classifier, WaveformClassifier, _as_given, _dev, _Estimator, _to_dev
+from .estimators import DefendedClassifier, OverTheAirClassifier, TensorFlowV2Classifier, WaveformClassifier, _as_given, _dev, _Estimator, _to_dev
 from .extract_features_construct_dataset import read_wav, _extractor
 from .genetic import GeneticAttack  # noqa: F401  (the genetic black-box attack: scores only; lipasr/genetic.py)
 from .keras import to_categorical

@@ -3,7 +3,9 @@
 ``TensorFlowV2Classifier`` (ART's wrapper, attacks.py:500-504) takes rows of MFCC features, the model's own inputs;
 ``WaveformClassifier`` (ours) puts the MFCC stage in front of the model and takes rows of audio; ``OverTheAirClassifier`` (ours) puts
 a bank of room impulse responses (lipasr.room.RoomChannel) in front of a WaveformClassifier and answers with the expectation over
-the rooms, so that every attack over audio has an over-the-air form.  All answer the same calls on device tensors, so that an attack
+the rooms, so that every attack over audio has an over-the-air form; ``DefendedClassifier`` (ours) puts an input-transformation
+defence (lipasr.defences.AudioDefence: median, FIR and bit-depth stages) in front of a WaveformClassifier, so that every attack over
+audio has an adaptive form against it.  All answer the same calls on device tensors, so that an attack
 asks its estimator and never what kind of estimator it holds:
 
     model, nb_classes, input_shape, batch_limit, clip_values (None: no clamp -- always on a TensorFlowV2Classifier)
@@ -416,4 +418,84 @@ class OverTheAirClassifier(WaveformClassifier):
             jf = self.base.jacobian_device(rows, on_logits=on_logits, lengths=lr).permute(1, 0, 2)  # the base's own storage: [classes][c R][n]
             for k in range(c):
                 self.channel.vjp(jf[k], nv, scale=1.0 / r, out=out[k, sl])
+        return out.permute(1, 0, 2)
+
+
+class DefendedClassifier(WaveformClassifier):
+    """A WaveformClassifier behind an input-transformation defence: every clip goes through a lipasr.defences.AudioDefence T (a chain
+    of median, FIR and bit-depth stages, one launch) before the MFCC stage.  It shares the base's model, extractor, statistics,
+    domain and ``clip_values`` and takes the same rows, so any attack over audio runs on it unchanged -- which makes the attack
+    ADAPTIVE: it sees the defence.  FIR taps are applied to the rows as they come, so their sample rate has to be the rows' (22 050 Hz
+    in domain "22k"): that is the caller's business.  ``lengths`` keep the base's meaning (samples at ``sr_in``); the defence keeps
+    every clip's length and writes exactly 0 beyond it, so they hold behind it too, and the gradient stays exactly 0 beyond each clip.
+        predict_device, predict, own_labels_device                  the base's at T(x)
+        loss_gradient_device, output_vjp_device, jacobian_device    the base's at T(x), carried back by ``defence.vjp(x, .)``; the
+                              Jacobian takes one pass of the adjoint per class on ONE forward pass of the base
+    ``backward``: "chain" differentiates through the defence (the median routes to the element it selected, the FIR is its adjoint,
+    the quantiser is straight-through where its clamp was idle); "identity" takes the whole defence as the identity on the way back
+    (BPDA, Athalye, Carlini and Wagner 2018): the base's gradient at T(x), masked to the clip.
+    ``batch_limit`` is the base's.  A DefendedClassifier may be the base of an OverTheAirClassifier: room, then defence, then
+    recogniser, the physical order."""
+
+    def __init__(self, base, defence, backward="chain"):
+        from .defences import AudioDefence
+
+        if not isinstance(base, WaveformClassifier) or isinstance(base, (OverTheAirClassifier, DefendedClassifier)):
+            raise TypeError("base must be a WaveformClassifier (and neither an OverTheAirClassifier nor a DefendedClassifier)")
+        if not isinstance(defence, AudioDefence):
+            raise TypeError("defence must be a lipasr.defences.AudioDefence")
+        if backward not in ("chain", "identity"):
+            raise ValueError(f"backward={backward!r}: 'chain' or 'identity'")
+        if defence.device != base.extractor.device:
+            raise ValueError(f"the defence is on {defence.device}, the base on {base.extractor.device}")
+        _Estimator.__init__(self, base.model, base.nb_classes)
+        self.base, self.defence, self.backward = base, defence, backward
+        self.utterance_length, self.domain, self.extractor = base.utterance_length, base.domain, base.extractor
+        self.n, self.input_shape, self.mean, self.scale, self.clip_values = base.n, base.input_shape, base.mean, base.scale, base.clip_values
+        self._bs = base.batch_limit
+
+    def _n_valid(self, lt):
+        return None if lt is None else self.clip_positions(lt).contiguous()
+
+    def _features(self, xb, lb):
+        return self.base._features(self.defence.apply(xb.contiguous(), self._n_valid(lb)), lb)
+
+    def features_device(self, xt, lengths=None):
+        """[B <= batch_max, n] device tensor -> the standardised features of T(x)."""
+        lt = self.lengths_device(lengths, xt.shape[0])
+        return self._features(xt, lt)
+
+    def predict_device(self, xt, logits=False, lengths=None):
+        xt = self.rows_device(xt)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        return self.base.predict_device(self.defence.apply(xt, self._n_valid(lt)), logits=logits, lengths=lt)
+
+    def loss_gradient_device(self, xt, yt, out=None, lengths=None):
+        """d mean CE(f(features(T(x))), y) / dx on device tensors ([B, n], one-hot [B, classes]) -> [B, n]."""
+        xt = self.rows_device(xt)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        nv = self._n_valid(lt)
+        g = self.base.loss_gradient_device(self.defence.apply(xt, nv), yt, lengths=lt)
+        return self.defence.vjp(xt, g, nv, backward=self.backward, out=out)
+
+    def output_vjp_device(self, xt, vt, on_logits=False, lengths=None):
+        """sum_c v[b, c] d out_c / dx with the defence in front: [B, n], [B, classes] -> [B, n]."""
+        xt = self.rows_device(xt)
+        lt = self.lengths_device(lengths, xt.shape[0])
+        nv = self._n_valid(lt)
+        g = self.base.output_vjp_device(self.defence.apply(xt, nv), vt, on_logits=on_logits, lengths=lt)
+        return self.defence.vjp(xt, g, nv, backward=self.backward)
+
+    def jacobian_device(self, xt, on_logits=True, lengths=None):
+        """d out_c / dx for every class with the defence in front: [B, n] -> a [B, classes, n] view of class-major storage.  ONE
+        Jacobian of the base at T(x), then one pass of the defence's adjoint per class: row c carries the bits of
+        ``output_vjp_device`` with the one-hot e_c."""
+        xt = self.rows_device(xt)
+        b_all, c = xt.shape[0], self.nb_classes
+        lt = self.lengths_device(lengths, b_all)
+        nv = self._n_valid(lt)
+        jf = self.base.jacobian_device(self.defence.apply(xt, nv), on_logits=on_logits, lengths=lt).permute(1, 0, 2)  # the base's own storage: [classes][B][n]
+        out = torch.empty(c, b_all, self.n, device=xt.device)
+        for k in range(c):
+            self.defence.vjp(xt, jf[k], nv, backward=self.backward, out=out[k])
         return out.permute(1, 0, 2)

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 720. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 740. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -56,6 +56,9 @@
  * 730: test hooks of the training step's own kernels: lipasr_debug_k2_launches (launch counters per kernel) and
  * lipasr_debug_mlp_stage (an activation, the saved statistics, a gradient, the logits or the probabilities that a classifier plan's
  * last call left behind).  The NonNeg clamp of lipasr_mlp_adam_nonneg keeps a NaN weight (it wrote 0 before).
+ * 740: input-transformation defences over audio: lipasr_defence_apply (a chain of median, FIR and bit-depth stages in one launch),
+ * lipasr_defence_vjp (the chain's vector-Jacobian product in one launch), their _host twins and the test hook
+ * lipasr_debug_defence_launches.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -950,6 +953,53 @@ int lipasr_warp_param_vjp_host(const float* x, const float* g, const int* n_vali
 /* Test hook: launches since the library was loaded of 0 warp_kernel<false> (apply), 1 warp_kernel<true> (param_vjp), counted on the
  * host where the launch happens; -1 for an unknown id. */
 long lipasr_debug_warp_launches(int kernel);
+
+/* Input-transformation defences over audio (lipasr/defences.py, estimators.DefendedClassifier; ours -- ART's SpatialSmoothing,
+ * FeatureSqueezing and Resample preprocessors are the NumPy forms): a chain of 1 to LIPASR_DEFENCE_MAX_STAGES stages over rows
+ * x [clips][n], in one launch, and the chain's vector-Jacobian product in one launch.  The chain is three HOST arrays of `stages`
+ * entries: kinds (LIPASR_DEFENCE_*), args (the width, the tap count or the bits) and taps (for a FIR stage the DEVICE pointer of
+ * its float32 taps, any 4-byte boundary; ignored for the other kinds, and the array may be NULL when no stage is a FIR).  They
+ * are read before the call returns.  n_valid [clips] (or NULL: n for every clip) holds POSITIONS IN THE ROW, clamped to [0, n];
+ * nv below is the clamped value.  Every stage reads its input as 0 outside [0, nv) and writes exactly 0 there, so the chain is the
+ * composition of its stages, each as if launched alone.
+ *   MEDIAN, odd width k in 3 .. 15, h = (k - 1) / 2:  out[t] = the element of rank h of x[t - h .. t + h].  Elements are ordered by
+ *       (value, position) with values compared as floats: -0 and +0 tie and the position decides; the padding zeros take part as
+ *       elements at their positions.  The output carries the bits of the selected element.
+ *       vjp: gx[s] = sum of g[t] over the t whose selected element is position s, from 0 in ascending t in fp32; the gradient of
+ *       an output that selected a padding zero is dropped.
+ *   FIR, odd tap count <= 255, c = (taps - 1) / 2:  out[t] = sum_k h[k] x[t + c - k] (centred: zero phase for symmetric taps), one
+ *       fmaf chain from 0 in ascending k over every k (an absent sample is a 0 operand).
+ *       vjp, the exact adjoint: gx[s] = sum_k h[k] g[s - c + k], g read as 0 outside [0, nv), the same chain.
+ *   QUANTIZE, bits in 2 .. 16, q = 2^(bits - 1):  out[t] = clamp(rintf(x[t] q), -q, q - 1) / q: exact in fp32 (ties to even).
+ *       vjp: straight-through where the clamp was idle (gx[s] = g[s], its bits), 0 where it acted.
+ * The half-widths of a chain (h, c, 0) may sum to at most LIPASR_DEFENCE_MAX_HALO.  A workgroup owns 1 024 positions of one clip
+ * and keeps every intermediate in LDS; the vjp launch recomputes the forward pass over the halo it needs and reads no saved state.
+ * No element's arithmetic depends on the tiling, the batch or the alignment: two runs give the same bits, a clip's row has the
+ * bits it would have if launched alone, and a chain gives the bits of its stages launched one after the other.
+ * Both: one launch, no workspace, nothing allocated or synchronised, no atomics.  Any n up to 2^30, any clips, any 4-byte
+ * alignment of every pointer.  Signals and taps are taken as finite.  LIPASR_EINVAL, before the device is touched and whatever the
+ * sizes: stages outside 1 .. 4, kinds or args NULL, an unknown kind, an even or out-of-range width, tap count or bits, a FIR stage
+ * without taps, a halo above the limit, a negative size.  Then LIPASR_OK without a launch when clips or n is 0; else LIPASR_EINVAL
+ * for a null x, g, out or gx and for an output that overlaps an input or the taps. */
+#define LIPASR_DEFENCE_MEDIAN 0
+#define LIPASR_DEFENCE_FIR 1
+#define LIPASR_DEFENCE_QUANTIZE 2
+#define LIPASR_DEFENCE_MAX_STAGES 4
+#define LIPASR_DEFENCE_MAX_HALO 256
+int lipasr_defence_apply(const float* x /* [clips][n] */, const int* n_valid, const int* kinds /* host [stages] */,
+                         const int* args /* host [stages] */, const float* const* taps /* host [stages] of device pointers */,
+                         int stages, int clips, int n, float* out /* [clips][n] */, lipasr_stream_t stream);
+int lipasr_defence_vjp(const float* x, const float* g /* [clips][n] */, const int* n_valid, const int* kinds, const int* args,
+                       const float* const* taps, int stages, int clips, int n, float* gx /* [clips][n] */, lipasr_stream_t stream);
+/* Host-only (no GPU needed): the same inline functions over whole rows in plain loops, on host arrays (taps: host pointers).  The
+ * same bits as the device entry points on finite signals.  Same checks. */
+int lipasr_defence_apply_host(const float* x, const int* n_valid, const int* kinds, const int* args, const float* const* taps,
+                              int stages, int clips, int n, float* out);
+int lipasr_defence_vjp_host(const float* x, const float* g, const int* n_valid, const int* kinds, const int* args,
+                            const float* const* taps, int stages, int clips, int n, float* gx);
+/* Test hook: launches since the library was loaded of 0 defence_apply_kernel, 1 defence_vjp_kernel, counted on the host where the
+ * launch happens; -1 for an unknown id. */
+long lipasr_debug_defence_launches(int kernel);
 
 /* One fused FGSM/PGD iteration (attacks.py:506-510, 657-661): inference forward at x_adv, CE
  * gradient, backward to the input, and the K4 sign step applied in place on x_adv inside the last
