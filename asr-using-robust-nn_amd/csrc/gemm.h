@@ -121,6 +121,16 @@ struct GemmArgs {
   float* dbeta;
 };
 
+// ReLU and its backward mask that keep a NaN.  fmaxf returns its other argument and NaN > 0 is false, so a poisoned pre-activation
+// (a NaN input, or inf - inf after an operand left fp16's range in arithmetic mode 2) became 0 in the forward pass and the step
+// went on with a finite loss and finite gradients; Keras' ReLU passes the NaN on, and so does the oracle (a NaN activation times
+// the mask (a > 0) is NaN).  The same bits as fmaxf(t, 0) and (a > 0 ? d : 0) for every other value.
+__device__ __forceinline__ float relu_keep_nan(const float t) {
+  const float a = fmaxf(t, 0.0f);
+  return t != t ? t : a;
+}
+__device__ __forceinline__ float relu_mask_keep_nan(const float a, const float d) { return a > 0.0f ? d : (a != a ? a : 0.0f); }
+
 // mode 2, operands whose size is not known beforehand (gradients): the producer's epilogue leaves max |x| as float bits; the
 // scale 2^(14 - e) with max = f 2^e, f in [0.5, 1), puts the largest value in [2^13, 2^14) -- a factor 4 under fp16's 65504
 // The maximum lives in kAmaxSlots words, one per 64-byte line: 2048 wavefronts folding their maxima into ONE word cost the backward

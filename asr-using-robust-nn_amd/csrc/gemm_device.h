@@ -122,22 +122,22 @@ __device__ __forceinline__ float epilogue_elem(const GemmArgs& g, float dm, int 
     case EPI_BIAS:
       return v + g.bias[gn];
     case EPI_BIAS_RELU:
-      return fmaxf(v + g.bias[gn], 0.0f);
+      return relu_keep_nan(v + g.bias[gn]);
     case EPI_BIAS_RELU_STATS: {
-      const float a = fmaxf(v + g.bias[gn], 0.0f);
+      const float a = relu_keep_nan(v + g.bias[gn]);
       s1 = a;
       s2 = a * a;
       return a;
     }
     case EPI_BIAS_RELU_BN: {
-      const float a = fmaxf(v + g.bias[gn], 0.0f);
+      const float a = relu_keep_nan(v + g.bias[gn]);
       if (g.aux) g.aux[(size_t)gm * g.ldc + gn] = a;
       if (g.gamma) return (a - g.mmean[gn]) / sqrtf(g.mvar[gn] + kBnEps) * g.gamma[gn] + g.beta[gn];
       return a;
     }
     case EPI_DZ_INFER: {
       const float s = g.gamma ? g.gamma[gn] / sqrtf(g.mvar[gn] + kBnEps) : 1.0f;
-      return g.aux[(size_t)gm * g.ldc + gn] > 0.0f ? v * s : 0.0f;
+      return relu_mask_keep_nan(g.aux[(size_t)gm * g.ldc + gn], v * s);
     }
     case EPI_DH_STATS: {
       const size_t e = (size_t)gm * g.ldc + gn;
@@ -149,7 +149,7 @@ __device__ __forceinline__ float epilogue_elem(const GemmArgs& g, float dm, int 
     }
     case EPI_DZ_NOBN: {
       const size_t e = (size_t)gm * g.ldc + gn;
-      return g.aux[e] > 0.0f ? v * dm : 0.0f;
+      return relu_mask_keep_nan(g.aux[e], v * dm);
     }
     case EPI_SIGNSTEP: {
       const size_t i = (size_t)gm * g.ldc + gn;
@@ -348,7 +348,7 @@ __device__ __forceinline__ void bnx_finish(const GemmArgs& g, const int step, co
       } else {
         const float xh = (av[r][e] - mean[e]) * rstd[e];
         const float d = ga[e] * rstd[e] * (val[r][e] - p0[e] * invB - xh * p1[e] * invB);
-        o[e] = av[r][e] > 0.0f ? d : 0.0f;
+        o[e] = relu_mask_keep_nan(av[r][e], d);
         if (gn + e < g.N) omax = fmaxf(omax, fabsf(o[e]));
       }
     }
@@ -422,7 +422,7 @@ __device__ __forceinline__ void bnx_row4(const GemmArgs& g, const int step, cons
   if (g.epi == EPI_BIAS_RELU_BNX) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float a = (rv && gn + e < g.N) ? fmaxf(acc[e] + q.p0[e], 0.0f) : 0.0f;
+      const float a = (rv && gn + e < g.N) ? relu_keep_nan(acc[e] + q.p0[e]) : 0.0f;
       val[e] = a; av[e] = a; s1[e] = a; s2[e] = a * a;
     }
   } else {

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(BnBwdArgs p) {
     for (int e = 0; e < 4; ++e) {
       const float xh = (av[e] - mean[e]) * rstd[e];
       const float d = ga[e] * rstd[e] * (gv[e] - dbt[e] * invB - xh * dg[e] * invB);
-      o[e] = av[e] > 0.0f ? d : 0.0f;
+      o[e] = relu_mask_keep_nan(av[e], d);
       if (c.j + e < c.N) omax = fmaxf(omax, fabsf(o[e]));
     }
     st4(p.dz, ro, c, o);

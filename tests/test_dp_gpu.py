@@ -12,12 +12,15 @@ import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COMPUTE = ("float32", "float16x2")  # the training arithmetics a model with BatchNorm after every hidden layer can take
 
 
 def _spec():
     from oracle import mlp_ref as P
 
-    # no BatchNorm / dropout: per-replica statistics would (by design) differ from a single big batch
+    # no BatchNorm / dropout: per-replica statistics would (by design) differ from a single big batch.  For the same reason the test
+    # on this model runs on exact fp32 only: lipasr_mlp_set_compute refuses the fp16 two-plane mode for a network without BatchNorm
+    # after every hidden layer (EUNSUPPORTED); two ranks against one in that mode are the synchronized-BatchNorm tests below.
     return [P.LayerSpec(880, 256, False, 0.0, True), P.LayerSpec(256, 64, False, 0.0, True), P.LayerSpec(64, 10, False, 0.0, True)]
 
 
@@ -172,8 +175,11 @@ def test_dropout_masks_differ_by_rank(cuda):
     assert not torch.equal(grads[0], grads[1])
 
 
-def test_head_plus_dw0_equals_one_call(cuda):
-    """lipasr_mlp_train_fwd_bwd_head + lipasr_mlp_train_dw0 (the data-parallel pair) against lipasr_mlp_train_fwd_bwd:
+@pytest.mark.parametrize("compute", COMPUTE)
+def test_head_plus_dw0_equals_one_call(cuda, compute):
+    """(On both training arithmetics.  float32: everything past late_floats from the same launches, bit for bit.  float16x2: the
+    group without layer 0 may take another tile, see below -- the bound of fp32 summation order, 2e-6 of the maximum.)
+    lipasr_mlp_train_fwd_bwd_head + lipasr_mlp_train_dw0 (the data-parallel pair) against lipasr_mlp_train_fwd_bwd:
     everything past late_floats bit-identical (the same launches), the first layer's [dW | db] from a different GEMM
     tiling (LDS-tiled 64x64 instead of the grouped split-K kernel): fp32 summation order only."""
     from helpers import build_model, dev, load_params
@@ -184,12 +190,12 @@ def test_head_plus_dw0_equals_one_call(cuda):
     rng = np.random.default_rng(1)
     x = dev(rng.standard_normal((512, 880)))
     y = dev(P.to_categorical(rng.integers(0, 10, 512), 10))
-    m = build_model(spec, max_batch=512)
+    m = build_model(spec, max_batch=512, compute_dtype=compute)
     load_params(m, p)
     m.train_fwd_bwd(x, y, dropout=False)
     whole = m._grads.clone()
     bn = m._bnstate.clone()
-    m2 = build_model(spec, max_batch=512)
+    m2 = build_model(spec, max_batch=512, compute_dtype=compute)
     load_params(m2, p)
     m2._grads.fill_(float("nan"))
     m2.train_fwd_bwd(x, y, dropout=False, defer_dw0=True)
@@ -198,7 +204,8 @@ def test_head_plus_dw0_equals_one_call(cuda):
     assert torch.isnan(m2._grads[:late]).all()           # the head leaves [dW_0 | db_0] alone
     untouched = torch.isnan(m2._grads[late:])            # the alignment pads between segments are never written
     assert int(untouched.sum()) < 32 and float(whole[late:][untouched].abs().max() if untouched.any() else 0.0) == 0.0
-    if getattr(m, "_compute_dtype", "float32") == "float16x2":
+    assert m._compute_dtype == compute and m2._compute_dtype == compute
+    if compute == "float16x2":
         # arithmetic mode 2 chooses the weight-gradient tile by how many 128 x 128 tiles the GROUP makes: with layer 1 in the group
         # they cover 40 % of the chip (128 x 128 split-pass tiles), without it they do not (64 x 64 ring tiles) -- the same sums in
         # another fp32 order, each path bitwise reproducible in itself
@@ -213,14 +220,14 @@ def test_head_plus_dw0_equals_one_call(cuda):
 
 
 # ------------------------------------------------------------------ synchronized BatchNorm (opt-in)
-def _sync_run(dp, sync_bn, steps=4):
+def _sync_run(dp, sync_bn, steps=4, compute="float32"):
     from helpers import build_model, dev, load_params
     from lipasr.pipeline import TrainPipeline
     from oracle import mlp_ref as P
 
     # the reference's constrained model with its five BatchNorm layers, dropout off so that runs are comparable bit for bit
     spec = [P.LayerSpec(s.n_in, s.n_out, s.bn, 0.0, s.nonneg) for s in P.vd_constrained_spec()]
-    m = build_model(spec, max_batch=64)
+    m = build_model(spec, max_batch=64, compute_dtype=compute)
     load_params(m, P.init_params(spec, seed=6, dtype=np.float32, nonneg_init=True))
     rng = np.random.default_rng(17)
     x = dev(rng.standard_normal((64 * steps, 880)))
@@ -234,7 +241,7 @@ def _sync_run(dp, sync_bn, steps=4):
     return m, pipe
 
 
-def _sync_worker(rank, world, port, out_dir):
+def _sync_worker(rank, world, port, out_dir, compute):
     for p in (ROOT, os.path.join(ROOT, "asr-using-robust-nn_amd"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -246,7 +253,7 @@ def _sync_worker(rank, world, port, out_dir):
     dp = DataParallel()
     out = {}
     for sync in (True, False):
-        m, pipe = _sync_run(dp, sync)
+        m, pipe = _sync_run(dp, sync, compute=compute)
         out[sync] = {"params": m._params.cpu(), "bn": m._bnstate.cpu(), "div": dp.max_divergence(m._params), "norms": pipe.norms.cpu()}
         pipe.close()
     torch.save(out, os.path.join(out_dir, f"s{rank}.pt"))
@@ -254,15 +261,18 @@ def _sync_worker(rank, world, port, out_dir):
 
 
 @pytest.mark.timeout(900)
-def test_sync_batchnorm_two_ranks_match_one_rank(cuda, tmp_path):
-    """Opt-in synchronized BatchNorm (lipasr_mlp_train_segment + a SUM all-reduce of the column partial sums between
+@pytest.mark.parametrize("compute", COMPUTE)
+def test_sync_batchnorm_two_ranks_match_one_rank(cuda, tmp_path, compute):
+    """(On both training arithmetics at the same bounds.  What is bit for bit here holds in either: both ranks apply the SAME
+    all-reduced sums and gradients, whatever tiles produced their shares; one rank against two is a bound in both.)
+    Opt-in synchronized BatchNorm (lipasr_mlp_train_segment + a SUM all-reduce of the column partial sums between
     segments): two ranks of 32 rows reproduce the single process's 64-row run of the five-BatchNorm model -- weights AND
     moving statistics -- to fp32 summation order, which per-replica statistics (the default) do not."""
     from lipasr.parallel import DataParallel
 
-    m1, pipe1 = _sync_run(DataParallel(), False)
+    m1, pipe1 = _sync_run(DataParallel(), False, compute=compute)
     ref, ref_bn = m1._params.cpu(), m1._bnstate.cpu()
-    mp.spawn(_sync_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_sync_worker, args=(2, _free_port(), str(tmp_path), compute), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "s0.pt")
     r1 = torch.load(tmp_path / "s1.pt")
     for sync in (True, False):
@@ -282,7 +292,7 @@ def test_sync_batchnorm_two_ranks_match_one_rank(cuda, tmp_path):
 
 
 # ------------------------------------------------------------------ round 4: uneven shards and the PGD inner loop under synchronized BatchNorm
-def _sync_uneven_run(dp, split, pgd, steps=3):
+def _sync_uneven_run(dp, split, pgd, steps=3, compute="float32"):
     """64 rows per step cut into `split` rows per rank (40 | 24 rows are 2 | 1 row tiles of 32: the partial-sum
     buffers of the two ranks have different shapes; they are reduced to [2][width] before the exchange)."""
     from helpers import build_model, dev, load_params
@@ -290,7 +300,7 @@ def _sync_uneven_run(dp, split, pgd, steps=3):
     from oracle import mlp_ref as P
 
     spec = [P.LayerSpec(s.n_in, s.n_out, s.bn, 0.0, s.nonneg) for s in P.vd_constrained_spec()]
-    m = build_model(spec, max_batch=64)
+    m = build_model(spec, max_batch=64, compute_dtype=compute)
     load_params(m, P.init_params(spec, seed=8, dtype=np.float32, nonneg_init=True))
     rng = np.random.default_rng(23)
     x = dev(rng.standard_normal((64 * steps, 880)))
@@ -306,7 +316,7 @@ def _sync_uneven_run(dp, split, pgd, steps=3):
     return m, pipe
 
 
-def _sync_uneven_worker(rank, world, port, out_dir):
+def _sync_uneven_worker(rank, world, port, out_dir, compute):
     for p in (ROOT, os.path.join(ROOT, "asr-using-robust-nn_amd"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -318,7 +328,7 @@ def _sync_uneven_worker(rank, world, port, out_dir):
     dp = DataParallel()
     out = {}
     for pgd in (False, True):
-        m, pipe = _sync_uneven_run(dp, (40, 24), pgd)
+        m, pipe = _sync_uneven_run(dp, (40, 24), pgd, compute=compute)
         out[pgd] = {"params": m._params.cpu(), "bn": m._bnstate.cpu(), "div": dp.max_divergence(m._params)}
         pipe.close()
     torch.save(out, os.path.join(out_dir, f"u{rank}.pt"))
@@ -326,8 +336,11 @@ def _sync_uneven_worker(rank, world, port, out_dir):
 
 
 @pytest.mark.timeout(900)
-def test_sync_batchnorm_uneven_shards_and_pgd(cuda, tmp_path):
-    """Synchronized BatchNorm with shards of 40 and 24 rows (different row-tile counts per rank) and, second, with the PGD
+@pytest.mark.parametrize("compute", COMPUTE)
+def test_sync_batchnorm_uneven_shards_and_pgd(cuda, tmp_path, compute):
+    """(On both training arithmetics at the same bounds; the attack runs on exact fp32 in either.  Bit for bit between the ranks
+    in both: they apply the same all-reduced sums.)
+    Synchronized BatchNorm with shards of 40 and 24 rows (different row-tile counts per rank) and, second, with the PGD
     inner loop in front of the step (it raised NotImplementedError): both reproduce the single-process
     run of the 64-row batch, every piece between two collectives replayed as a HIP graph."""
     import torch.multiprocessing as mp
@@ -335,10 +348,10 @@ def test_sync_batchnorm_uneven_shards_and_pgd(cuda, tmp_path):
 
     ref = {}
     for pgd in (False, True):
-        m1, pipe1 = _sync_uneven_run(DataParallel(), (64,), pgd)
+        m1, pipe1 = _sync_uneven_run(DataParallel(), (64,), pgd, compute=compute)
         ref[pgd] = (m1._params.cpu(), m1._bnstate.cpu())
         pipe1.close()
-    mp.spawn(_sync_uneven_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_sync_uneven_worker, args=(2, _free_port(), str(tmp_path), compute), nprocs=2, join=True)
     r0, r1 = torch.load(os.path.join(tmp_path, "u0.pt")), torch.load(os.path.join(tmp_path, "u1.pt"))
     for pgd in (False, True):
         assert r0[pgd]["div"] == 0.0 and r1[pgd]["div"] == 0.0

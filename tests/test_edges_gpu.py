@@ -39,12 +39,15 @@ def test_mfcc_single_clip_and_full_plan(cuda):
         ex(dev(np.concatenate([waves, waves[:1]])))     # one more than the plan holds
 
 
-@pytest.mark.parametrize("batch", [1, 2, 31, 33])
-def test_classifier_tiny_and_ragged_batches(cuda, batch):
-    """batch 1 makes every BatchNorm variance exactly 0 (rstd = 1/sqrt(eps)); 31 / 33 straddle the 32-row tiles."""
+@pytest.mark.parametrize("batch, compute", [pytest.param(b, c, id=str(b) if c == "float32" else f"{b}-{c}")  # (the fp32 rows keep their ids)
+                                            for b in (1, 2, 31, 33) for c in ("float32", "float16x2")])
+def test_classifier_tiny_and_ragged_batches(cuda, batch, compute):
+    """batch 1 makes every BatchNorm variance exactly 0 (rstd = 1/sqrt(eps)); 31 / 33 straddle the 32-row tiles.  On both training
+    arithmetics at the same bounds: at batch 1 every BatchNorm backward cancels, max |dz| is 0 or at rounding level, and the fp16
+    two-plane mode derives its gradient scale from just that (scale_from_amax falls back to 1 for a maximum that is not > 0)."""
     spec = P.vd_constrained_spec()
     p = P.init_params(spec, seed=2, dtype=np.float32, nonneg_init=True)
-    m = build_model(spec, max_batch=64)
+    m = build_model(spec, max_batch=64, compute_dtype=compute)
     load_params(m, p)
     rng = np.random.default_rng(batch)
     x = rng.standard_normal((batch, 880)).astype(np.float32)

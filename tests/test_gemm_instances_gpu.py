@@ -412,14 +412,17 @@ def _model(spec, max_batch, arith, fuse, tiles, cus, knob):
     return m
 
 
+def open_plan_case(case):
+    """The case's model with its parameters loaded and every knob set -> (model, spec, x, y, masks), the last three on the device."""
+    spec, p, x, y, masks = _problem(case["widths"], case["bn_off"], case["drop"], case["batch"], case["seed"])
+    m = _model(spec, case["batch"], case["arith"], case["fuse"], case["tiles"], case["cus"], case["knob"])
+    load_params(m, p)
+    return m, spec, dev(x), dev(y), [dev(k) if k is not None else None for k in masks]
+
+
 def run_plan_case(case):
     """One training step of the case; returns (tensors the step left, correct rows, the launch counters that moved)."""
-    spec, p, x, y, masks = _problem(case["widths"], case["bn_off"], case["drop"], case["batch"], case["seed"])
-    batch = case["batch"]
-    m = _model(spec, batch, case["arith"], case["fuse"], case["tiles"], case["cus"], case["knob"])
-    load_params(m, p)
-    xt, yt = dev(x), dev(y)
-    mt = [dev(k) if k is not None else None for k in masks]
+    m, spec, xt, yt, mt = open_plan_case(case)
     before = _snapshot()
     if case["form"] == "head+dw0":
         m.train_fwd_bwd(xt, yt, masks=mt, defer_dw0=True)
@@ -429,6 +432,11 @@ def run_plan_case(case):
     errors = m.exchange_errors()  # (synchronises)
     moved = _moved(before, _snapshot())
     assert errors == 0, "an exchange gave up"
+    return step_tensors(m, spec, case["batch"]) + (moved,)
+
+
+def step_tensors(m, spec, batch):
+    """What the model's last training step left -> (tensors by the names of _tensors, correct rows)."""
     got = grads_of(m, spec)
     after = read_params(m, spec)
     t = {"loss_rows": m._loss_rows[:batch].cpu().numpy().astype(np.float64)}
@@ -437,7 +445,7 @@ def run_plan_case(case):
         if s.bn:
             t[f"dgamma{l}"], t[f"dbeta{l}"] = got["dgamma"][l], got["dbeta"][l]
             t[f"mov_mean{l}"], t[f"mov_var{l}"] = after.mov_mean[l], after.mov_var[l]
-    return t, m._correct_rows[:batch].cpu().numpy(), moved
+    return t, m._correct_rows[:batch].cpu().numpy()
 
 
 @gpu

@@ -22,8 +22,10 @@ def _data(n=96, seed=41):
     return x, y
 
 
-def test_l2_adversarial_training_steps_match_the_composed_oracle(cuda):
-    """Three L2 adversarial-training steps at batch 32, dropout off: PGD-20 (eps 0.5, eps_step 0.1, norm 2, the batch's labels,
+@pytest.mark.parametrize("compute", ("float32", "float16x2"))
+def test_l2_adversarial_training_steps_match_the_composed_oracle(cuda, compute):
+    """(On both training arithmetics, at the same bounds: the fp16 two-plane mode claims those of exact fp32; the attack runs on
+    exact fp32 in either.)  Three L2 adversarial-training steps at batch 32, dropout off: PGD-20 (eps 0.5, eps_step 0.1, norm 2, the batch's labels,
     inference-mode network) -> training step on x_adv -> Adam + NonNeg -> simple_norm_constraint, against the same composition
     of the restatement and the oracle (lp_attacks_ref.pgd -> mlp_ref.train_step -> constraints_ref.simple_norm_constraint_pass),
     held to the terms of test_adversarial_training_steps_match_the_composed_oracle.  The oracle takes ITS training step from the
@@ -37,7 +39,7 @@ def test_l2_adversarial_training_steps_match_the_composed_oracle(cuda):
     eps, eps_step, iters = 0.5, 0.1, 20
     runs = []
     for use_graph in (True, False):
-        m = build_model(spec, max_batch=32)
+        m = build_model(spec, max_batch=32, compute_dtype=compute)
         load_params(m, p)
         pipe = TrainPipeline(m, batch=32, rho=0.1, constraint="product", use_graph=use_graph,
                              pgd=dict(eps=eps, eps_step=eps_step, max_iter=iters, norm=2))

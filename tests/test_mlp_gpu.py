@@ -145,11 +145,13 @@ def test_inference_logits_2366_clips(cuda):
     np.testing.assert_allclose(m.predict(x), P.softmax(ref), atol=2e-5)
 
 
-def test_n_train_steps_track_the_oracle(cuda):
-    """5 optimizer steps (fwd, bwd, Adam, NonNeg, BN moving statistics) with injected dropout masks."""
+@pytest.mark.parametrize("compute", ("float32", "float16x2"))
+def test_n_train_steps_track_the_oracle(cuda, compute):
+    """5 optimizer steps (fwd, bwd, Adam, NonNeg, BN moving statistics) with injected dropout masks, on both training arithmetics
+    at the same bounds (the fp16 two-plane mode claims those of exact fp32; its gradient scales are state from step to step)."""
     spec = P.vd_constrained_spec()
     p = _random_state(spec, 3)
-    m = build_model(spec)
+    m = build_model(spec, compute_dtype=compute)
     load_params(m, p)
     p64 = p.astype(np.float64)
     st = P.AdamState()

@@ -156,8 +156,10 @@ def test_pgd_adversarial_training_step(cuda):
     assert int(m._step.item()) == 3
 
 
-def test_adversarial_training_steps_match_the_composed_oracle(cuda):
-    """BASELINE config 5 as a whole: three adversarial-training steps at batch 32, dropout off --
+@pytest.mark.parametrize("compute", ("float32", "float16x2"))
+def test_adversarial_training_steps_match_the_composed_oracle(cuda, compute):
+    """(On both training arithmetics, at the same bounds: the fp16 two-plane mode claims those of exact fp32; extraction and the
+    attack run on exact fp32 in either.)  BASELINE config 5 as a whole: three adversarial-training steps at batch 32, dropout off --
     waveform -> MFCC + standardisation -> PGD-20 (eps 0.5, eps_step 0.1, the update rule of ART's ProjectedGradientDescent,
     attacks.py:647-661, driven from the training loop with the BATCH's labels, inference-mode network) -> training step on x_adv
     -> Adam + NonNeg -> simple_norm_constraint -- against the same composition of the oracle's pieces:
@@ -177,7 +179,7 @@ def test_adversarial_training_steps_match_the_composed_oracle(cuda):
     ref_feats = M.compute_mfcc_batch(waves)
     mean, scale = P.standard_scaler_fit(ref_feats)
     ref_std = (ref_feats - mean) / scale
-    m = build_model(spec, max_batch=32)
+    m = build_model(spec, max_batch=32, compute_dtype=compute)
     load_params(m, p)
     eps, eps_step, iters = 0.5, 0.1, 20
     pipe = TrainPipeline(m, batch=32, rho=0.1, constraint="product", use_graph=True, pgd=dict(eps=eps, eps_step=eps_step, max_iter=iters),
