@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+from . import knobs
+
 _lib = None
 hid_t = C.c_int64
 hsize_t = C.c_ulonglong
@@ -43,7 +45,7 @@ def library():
     if _lib is not None:
         return _lib
     tried = []
-    names = [os.environ.get("LIPASR_HDF5_LIBRARY"), ctypes.util.find_library("hdf5"), ctypes.util.find_library("hdf5_serial")]
+    names = [knobs.get("LIPASR_HDF5_LIBRARY"), ctypes.util.find_library("hdf5"), ctypes.util.find_library("hdf5_serial")]
     lib = None
     for cand in [n for n in names if n] + list(_SEARCH):
         try:

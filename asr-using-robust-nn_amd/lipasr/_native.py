@@ -14,9 +14,11 @@ import os
 # that same copy: two HIP runtimes in one process cannot both own the device ("no ROCm-capable device").
 import torch  # noqa: F401  (plumbing: device memory, streams, process groups)
 
+from . import knobs
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LIPASR_LIBRARY: another build of the same library (A/B timing of kernel changes); never a different backend
-LIB_PATH = os.environ.get("LIPASR_LIBRARY") or os.path.join(_HERE, "liblipasr.so")
+LIB_PATH = knobs.get("LIPASR_LIBRARY") or os.path.join(_HERE, "liblipasr.so")
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -262,10 +264,10 @@ for _name, (_res, _args) in PROTOTYPES.items():
     _fn.argtypes = _args
 
 
-if os.environ.get("LIPASR_CHAIN_HEAD"):  # A/B timing knob (lipasr_debug_chain_head): same product bit for bit
-    lib.lipasr_debug_chain_head(int(os.environ["LIPASR_CHAIN_HEAD"]))
-if os.environ.get("LIPASR_GEMM_MODE"):  # A/B timing knob (lipasr_debug_gemm_mode): never a different backend
-    lib.lipasr_debug_gemm_mode(int(os.environ["LIPASR_GEMM_MODE"]))
+if knobs.get("LIPASR_CHAIN_HEAD") is not None:  # A/B timing knob (lipasr_debug_chain_head): same product bit for bit
+    lib.lipasr_debug_chain_head(knobs.get("LIPASR_CHAIN_HEAD"))
+if knobs.get("LIPASR_GEMM_MODE") is not None:  # A/B timing knob (lipasr_debug_gemm_mode): never a different backend
+    lib.lipasr_debug_gemm_mode(knobs.get("LIPASR_GEMM_MODE"))
 
 
 def last_error() -> str:

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import keras_h5
+from . import keras_h5, knobs
 
 _name_counts = {}
 
@@ -325,9 +325,7 @@ class Model:
         "bfloat16" (GEMM operands rounded to bf16: BASELINE config 2's arithmetic, NOT inside the 1e-3 logit bound)."""
         self._compute_from_env = compute_dtype is None
         if compute_dtype is None:  # (LIPASR_COMPUTE: sweep knob for the test suite and A/B runs)
-            import os as _os
-
-            compute_dtype = _os.environ.get("LIPASR_COMPUTE", "float32")
+            compute_dtype = knobs.get("LIPASR_COMPUTE")
         if compute_dtype not in ("float32", "bfloat16", "float16x2"):
             raise ValueError("compute_dtype must be 'float32', 'float16x2' or 'bfloat16'")
         self._compute_dtype = compute_dtype
@@ -401,12 +399,10 @@ class Model:
                 self._compute_dtype = "float32"  # (the environment's default does not apply to a model without BatchNorm)
             else:
                 N.check(rc)
-        import os as _os
-
-        if _os.environ.get("LIPASR_FUSE_BN", "1") == "0":  # A/B knob: BatchNorm as launches of its own (the round-4 chain)
+        if knobs.get("LIPASR_FUSE_BN") == "0":  # A/B knob: BatchNorm as launches of its own (the round-4 chain)
             N.check(N.lib.lipasr_mlp_set_fuse_bn(plan, 0))
-        if _os.environ.get("LIPASR_GEMM_TILES"):  # A/B knob: 64 x 64 tiles from which a GEMM takes the LDS-tiled / ring kernels (default 224; the pipeline sets 128 on a CU share)
-            N.check(N.lib.lipasr_mlp_set_gemm_tiles(plan, int(_os.environ["LIPASR_GEMM_TILES"])))
+        if knobs.get("LIPASR_GEMM_TILES") is not None:  # A/B knob: 64 x 64 tiles from which a GEMM takes the LDS-tiled / ring kernels (default 224; the pipeline sets 128 on a CU share)
+            N.check(N.lib.lipasr_mlp_set_gemm_tiles(plan, knobs.get("LIPASR_GEMM_TILES")))
         n_params, n_state = N.sz(), N.sz()
         N.check(N.lib.lipasr_mlp_sizes(plan, C.byref(n_params), C.byref(n_state)))
         dev = self._device

@@ -10,8 +10,9 @@ resident waveform pool in place and are launched eagerly (3 launches per step).
 
 Two HIP streams: the MFCC of batch i+1 (VALU/LDS-bound kernels) runs on its own stream while the
 classifier step of batch i (many short MFMA / latency-bound kernels) runs on the training stream; the
-feature and label buffers are double-buffered and hipEvents carry the two dependencies
-(features ready -> train; train done with a buffer -> MFCC may overwrite it).
+feature and label buffers are double-buffered and handoff.py carries the two dependencies
+(features ready -> train; train done with a buffer -> MFCC may overwrite it).  Which CUs and queues
+the two streams get is schedule.py's decision.
 """
 from __future__ import annotations
 
@@ -19,10 +20,16 @@ import ctypes as C
 
 import torch
 
-from . import _native as N
+from . import _native as N, knobs
 from .attacks import _norm_value
 from .extract_features_construct_dataset import MfccExtractor
+from .handoff import EventHandoff, FlagHandoff
 from .parallel import DataParallel
+from .schedule import plan_schedule
+
+
+class _Captured(tuple):
+    """The HIP graphs of a step's pieces, in order; ``rets``: what each piece returned while it was captured."""
 
 
 class TrainPipeline:
@@ -59,7 +66,6 @@ class TrainPipeline:
                 raise ValueError(f"pgd num_random_init={rinit}: 0 or 1 (more restarts inside training are not supported)")
             self._pgd_rinit = rinit == 1
             self._pgd_seed = (0xBA11000000000000 + int(model._seed)) & 0xFFFFFFFFFFFFFFFF  # + the rank, folded in by the kernel
-        self._train_cus = train_cus
         # Data parallel, gradient exchange.  False: two HIP graphs around ONE all-reduce of the whole flat buffer.  True:
         # three graphs around two buckets, everything but [dW_0 | db_0] (44 % of the bytes) reduced beside the dW_0 GEMM.
         # Measured on one MI355X with a one-rank RCCL group (identity collectives, scratch/nccl_one_rank.py): the extra
@@ -78,7 +84,6 @@ class TrainPipeline:
         model._replica_rank = self.dp.rank  # every rank draws its own dropout masks
         self._late = model.late_floats      # [dW_0 | db_0]: the gradient bucket that is ready last
         self.sync_bn = bool(sync_bn) and self.dp.world > 1
-        self.use_graph = (bool(pgd) or self.sync_bn) if use_graph == "auto" else bool(use_graph)
         self.per_layer_iters = per_layer_iters
         self.mean, self.scale = affine if affine is not None else (None, None)
         nf = 20 * self.L
@@ -95,186 +100,83 @@ class TrainPipeline:
         self.v_state = torch.zeros(sum(model._widths[1:]), device=self.dev)
         self._order = N.int_array(list(range(nl)))
         self._warm = False
+        self._n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
+
+        def plan(cus):
+            return plan_schedule(n_cu=self._n_cu, batch=self.batch, compute_dtype=getattr(model, "_compute_dtype", "float32"), pgd=bool(pgd),
+                                 custom_extractor=self._custom_ex, mfcc_cus=cus, train_cus=train_cus, use_graph=use_graph, world=self.dp.world,
+                                 sync_bn=self.sync_bn, constraint=constraint, has_adam_signal=N.has("lipasr_mlp_adam_project_product_signal"))
+
+        sched = plan(mfcc_cus)  # the policy and its measurements: schedule.py
         self._masked_stream = self._masked_train_stream = None  # CU-masked streams this pipeline made (hardware queues of their own)
         self._gemm_tiles_set = False
-        self.stream = torch.cuda.Stream(device=self.dev)       # training stream (equal priorities measured best)
-        self.mfcc_stream = self._make_mfcc_stream(mfcc_cus)   # feature-extraction stream
-        # When the classifier's stream is IDLE (the first step after a drained pipeline, a host-bound caller), the extraction does
-        # not need to keep to its CU share: it runs on an unmasked stream, 0.19 instead of 0.39 ms for 1024 clips -- in a 20-step
-        # timed region that first extraction is 0.02 ms per step (round 4, scratch/fill_probe.py).  LIPASR_WIDE_WHEN_IDLE=0: off.
-        import os as _os
-
-        self._wide_stream = torch.cuda.Stream(device=self.dev) if (self._masked_stream is not None and not self._custom_ex
-                                                                  and _os.environ.get("LIPASR_WIDE_WHEN_IDLE", "1") == "1") else None
-        self._ev_last_mfcc = None     # the extraction plan's scratch is shared: consecutive extractions are ordered, whatever stream they ran on
-        self._last_xs = None
-        self._last_train_ev = None
-        self._n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
-        # The two hand-offs between the streams (features of buffer b ready -> classifier; classifier done with buffer b -> next
-        # extraction into it) are device-side counters (lipasr_flag_signal / lipasr_flag_wait: one-wavefront kernels) instead of
-        # hipEventRecord + hipStreamWaitEvent pairs: 0.405 against 0.409 ms per step (round 4, batch 1024, same box back to back;
-        # config 5 3.84 against 4.05-4.09 ms).  Needs streams that can run at the same time whatever the other one holds: the two
-        # hardware queues of _make_mfcc_stream.  Round 5: a wait that times out REPORTS and keeps
-        # waiting (it used to let the stream run on onto unordered data); the report lands in a pinned host word that step(),
-        # synchronize() and close() read without synchronising anything, so a caller that never calls pipe.synchronize() hears of
-        # it at its next step; and the default is events whenever ranks exchange gradients or BatchNorm sums (a rank sitting in a
-        # collective while a peer checkpoints is a legitimate stall, and the flag kernels have never run beside an RCCL kernel:
-        # no N > 1 run exists).  LIPASR_GPU_FLAGS=1 forces the flags on, 0 forces events (needed under tools that serialise
-        # kernels across streams, e.g. rocprofv3 --pmc: a wait kernel would spin in front of the signal it waits for).
-        self._flags = None
-        self._flag_err = None
-        want_flags = _os.environ.get("LIPASR_GPU_FLAGS", "auto")
-        if want_flags == "auto":
-            want_flags = "1" if (self.dp.world == 1 and not self.sync_bn) else "0"
-        if want_flags == "1" and self._masked_train_stream is not None:
-            self._flags = torch.zeros(2 * self._nbuf, dtype=torch.int32, device=self.dev)  # ready[b] | free[b]
-            self._flag_err = torch.zeros(1, dtype=torch.int32).pin_memory()                # 1: a wait is overdue, 2: a wait gave up
-            self._flag_timeout_ms = int(_os.environ.get("LIPASR_FLAG_TIMEOUT_MS", "30000"))  # what a wait sits out before it reports
-        # "classifier done with buffer b" is true as soon as the step's forward / backward pass is: the eager single-device step
-        # with the product constraint lets its Adam kernel raise free[b] when it starts (lipasr_mlp_adam_project_product_signal)
-        # instead of ending with a one-wavefront signal launch, 2.5-5 us and a launch boundary on the critical stream.  Every
-        # other shape of a step (graphs, data parallel, synchronized BatchNorm, another constraint) keeps the trailing launch.
-        # LIPASR_ADAM_SIGNAL=0: the trailing launch everywhere (A/B timing).
-        self._adam_signal = (self._flags is not None and self.dp.world == 1 and not self.sync_bn and not self.use_graph
-                             and self.constraint == "product" and N.has("lipasr_mlp_adam_project_product_signal")
-                             and _os.environ.get("LIPASR_ADAM_SIGNAL", "1") == "1")
-        self._ev_feat = [torch.cuda.Event() for _ in range(self._nbuf)]   # features of buffer b are ready
-        self._ev_free = [None] * self._nbuf                             # training has finished reading buffer b
+        self.stream = torch.cuda.Stream(device=self.dev)  # training stream (equal priorities measured best)
+        if sched.mfcc_groups is not None:
+            self.mfcc_cus = sched.mfcc_cus  # (without a partition the attribute does not exist)
+            self._masked_stream = self._make_masked_stream(0, sched.mfcc_groups, warn="the MFCC stream shares every CU")
+            if self._masked_stream is None:  # a runtime without CU masking: same results, the shared-CU schedule
+                sched = plan(None)
+            elif hasattr(self.ex, "set"):
+                # the three-kernel path's persistent resampler sizes its grid to one workgroup per CU it may use
+                # (the STFT kernel's fused DCT epilogue, plan key 4, stays off: on a CU share one workgroup per clip holding its 74 kB of
+                # LDS while two of its four wavefronts run the fp32 DCT loses to the separate dct_kernel -- stage 0.400 against 0.388 ms
+                # on 96 CUs, step 0.434 against 0.418 ms, round 4)
+                self.ex.set(1, self.mfcc_cus)
+        self.use_graph = sched.use_graph
+        if sched.classifier_groups is not None:
+            self._masked_train_stream = self._make_masked_stream(*sched.classifier_groups)
+        if self._masked_train_stream is not None:
+            self.stream = torch.cuda.ExternalStream(self._masked_train_stream.value, device=self.dev)
+        confined = sched.classifier == "rest" and self._masked_train_stream is not None
+        self.train_cus = sched.train_cus if confined else self._n_cu  # the CUs the classifier's stream may use
+        if confined:
+            N.check(N.lib.lipasr_mlp_set_gemm_tiles(self.model._plan, sched.gemm_tiles))
+            N.check(N.lib.lipasr_mlp_set_cu_budget(self.model._plan, sched.cu_budget))
+            self._gemm_tiles_set = True  # the pipeline owns these settings: close() puts the model's plan back
+        self.mfcc_stream = (torch.cuda.ExternalStream(self._masked_stream.value, device=self.dev) if self._masked_stream is not None
+                            else torch.cuda.Stream(device=self.dev))  # feature-extraction stream
+        # The schedule's wishes that need a stream of this pipeline's own making: an extraction that may leave its share needs a
+        # share; the flags need streams that can run at the same time whatever the other one holds, i.e. a classifier stream that
+        # owns a hardware queue; and the Adam kernel can only raise a flag that exists.
+        self._wide_stream = torch.cuda.Stream(device=self.dev) if sched.wide and self._masked_stream is not None else None
+        if sched.flags and self._masked_train_stream is not None:
+            self._handoff = FlagHandoff(self.h, self._nbuf, self.dev, knobs.get("LIPASR_FLAG_TIMEOUT_MS"))
+        else:
+            self._handoff = EventHandoff(self._nbuf, self._wide_stream is not None)
+        self._adam_signal = sched.adam_signal and self._flags is not None
         self._i = 0
-        self._graphs = {}
-        self._closed = False
-        self._prof = None
+        self._graphs = {}  # (bsz, b, gb) -> _Captured
+        self._closed = self._failed = False
+        self._prof, self._prof_i = None, 0
         N.register_owner(self)
 
-    def _make_mfcc_stream(self, mfcc_cus):
-        """The MFCC kernels are throughput kernels with thousands of workgroups; the classifier step is a chain of ~30
-        short dependent kernels.  Sharing every CU, the chain's workgroups queue behind MFCC workgroups for LDS and
-        wave slots and the step stretches.  A CU-masked stream keeps the MFCC work on part of the chip: it runs
-        slower there, but it is off the critical path, and the chain finds the other CUs free."""
-        import os
+    _flags = property(lambda self: self._handoff.flags)
+    _flag_err = property(lambda self: self._handoff.err)
+    _flag_timeout_ms = property(lambda self: self._handoff.timeout_ms)
 
-        n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
-        if mfcc_cus == "auto":
-            # measured at per-GPU batch 1024 on MI355X: 0.591 ms per step unmasked, 0.549 / 0.529 / 0.518 / 0.513 / 0.510 /
-            # 0.506 / 0.532 / 0.528 with 240 / 224 / 208 / 192 / 176 / 160 / 144 / 128 CUs for the MFCC stream
-            # (a heavier extractor wants a larger share: the 441/220 Speaker-recognition path measured 0.904 ms unmasked,
-            # 0.865 / 0.826 / 0.811 with 160 / 192 / 224 CUs)
-            # re-measured at the end of round 2 (after the STFT / GEMM changes): batch 1024: 0.540 / 0.505 / 0.489 / 0.520 ms
-            # with 128 / 160 / 192 / 224 CUs; batch 512: 0.340 with 160, 0.349 with 192 -- the MFCC work grows with the
-            # batch, the classifier's kernel chain hardly does, so the larger batch wants the larger share
-            env = os.environ.get("LIPASR_MFCC_CUS")
-            if env is not None:
-                mfcc_cus = int(env)
-            elif self._custom_ex:
-                mfcc_cus = (n_cu * 7) // 8
-            else:
-                # round 3 (resampler on the fp16 matrix instruction, dual-FFT STFT kernel: the MFCC needs 155 us of the
-                # whole chip instead of 240), 200-step runs, classifier stream on every CU: batch 1024: 0.499 / 0.460 / 0.481 /
-                # 0.493 / 0.499 ms with 96 / 128 / 160 / 192 / 224 CUs; batch 512: 0.341 with 128, 0.353 with 160.
-                # With the classifier's stream on the REST of the chip (train_cus="rest", 300-step runs, three repeats within
-                # 0.002): batch 1024: 0.616 / 0.447 / 0.471 ms with 64 / 96 / 128 CUs for the MFCC (0.468 for the best shared
-                # schedule, 0.517 with 96 CUs and the classifier everywhere); batch 512: 0.339 / 0.346 with 64 / 96 (0.347 shared)
-                # PGD adversarial training is the other regime: the classifier's leg is ten times the MFCC's and throughput-bound
-                # on its GEMMs, so it keeps every CU (PGD-20, batch 1024: 4.09 ms with 128 CUs for the MFCC and the classifier
-                # everywhere; 4.14 / 4.25 with 64 / 32; on the rest of the chip only: 4.67 / 5.05 / 5.24 with 32 / 64 / 96)
-                rest = self._train_cus == "rest" or (self._train_cus == "auto" and not self.pgd
-                                                     and os.environ.get("LIPASR_TRAIN_CUS", "rest") == "rest")
-                if rest:
-                    # after the grouped dW GEMM moved to LDS tiles: batch 1024: 0.614 / 0.431 / 0.453 with 64 / 96 / 128;
-                    # batch 2048: 0.871 / 0.679 with 96 / 128; batch 512: 0.337 with 64
-                    mfcc_cus = n_cu // 4 if self.batch <= 768 else ((n_cu * 3) // 8 if self.batch <= 1536 else n_cu // 2)
-                    # round 5: with the classifier's training GEMMs in arithmetic mode 2 (fp16 two-plane split, LDS-DMA ring) its
-                    # leg is 0.36 ms on 160 CUs and 0.37-0.38 on 128, so the extraction gets half the chip: batch 1024
-                    # 0.371 ms per step with 128 | 128 against 0.400 with 96 | 160 (200 steps, same box, interleaved)
-                    if getattr(self.model, "_compute_dtype", "float32") == "float16x2" and 768 < self.batch <= 1536:
-                        mfcc_cus = n_cu // 2
-                else:
-                    mfcc_cus = n_cu // 2
-        if not mfcc_cus or mfcc_cus >= n_cu:
-            # no partition -- but a long dependent chain (the PGD graph: ~440 nodes) still must not sit on a pool stream that may
-            # share a hardware queue with the extraction's pool stream (the cause of round 3's 3x; ADVICE r4: this fix used to
-            # be reachable only through the masked-MFCC branch below)
-            if self.pgd:
-                self._own_queue_train_stream(n_cu)
-            return torch.cuda.Stream(device=self.dev)
-        # Measured on MI355X (scratch/cu_mask_probe.py): mask bits act in groups of 8 consecutive bits -- group g
-        # (bits 8g .. 8g+7) stands for CU g of every XCD, and the group is enabled when any of its bits is set.  So the
-        # share is granted in steps of 8 CUs (one per XCD).
-        # (pairs of settings 32 apart behaved alike -- 240/224, 208/192, 176/160, 144/128 -- so the share is rounded
-        # down to a multiple of 32 CUs, which is what the hardware appears to grant; re-checked in round 3 with the two
-        # disjoint partitions: 13, 14 and 15 groups leave the STFT kernel's time where 12 groups put it, 0.267 ms)
-        n_groups = max(1, n_cu // 8)
-        k = max(4, min((int(mfcc_cus) // 32) * 4, n_groups))
-        words = (n_cu + 31) // 32
+    def _make_masked_stream(self, first, end, warn=None):
+        """A native stream confined to the 8-CU groups first .. end - 1, or None where the runtime cannot mask (after a warning, when
+        ``warn`` says what follows).  Measured on MI355X (scratch/cu_mask_probe.py): mask bits act in groups of 8 consecutive bits --
+        group g (bits 8g .. 8g+7) stands for CU g of every XCD, and the group is enabled when any of its bits is set.  The
+        extraction gets the first groups (an evenly spread choice measured erratic, 0.517 ... 0.78 ms, the prefix smooth), the
+        classifier the others (partitions that share 32 or 64 CUs measured worse: 0.452-0.461 against 0.418 ms) or all."""
+        words = (self._n_cu + 31) // 32
         mask = (C.c_uint32 * words)()
-        # the first k groups: an evenly spread choice of groups measured erratic (0.517 ... 0.78 ms), the prefix smooth
-        for g in range(k):
-            for b in range(8 * g, 8 * g + 8):
-                mask[b // 32] |= 1 << (b % 32)
-        self.mfcc_cus = 8 * k
+        for bit in range(8 * first, min(8 * end, self._n_cu)):
+            mask[bit // 32] |= 1 << (bit % 32)
         st = N.c_s()
-        rc = N.lib.lipasr_stream_create_masked(self.h.h, mask, words, C.byref(st))
-        if rc != N.OK:  # a runtime without CU masking: same results, the shared-CU schedule
+        if N.lib.lipasr_stream_create_masked(self.h.h, mask, words, C.byref(st)) == N.OK:
+            return st
+        if warn:
             import warnings
 
-            warnings.warn(f"lipasr: CU-masked stream unavailable ({N.last_error()}); the MFCC stream shares every CU")
-            if self.pgd:
-                self._own_queue_train_stream(n_cu)
-            return torch.cuda.Stream(device=self.dev)
-        self._masked_stream = st
-        # the three-kernel path's persistent resampler sizes its grid to one workgroup per CU it may use
-        if hasattr(self.ex, "set"):
-            self.ex.set(1, self.mfcc_cus)
-            # (the STFT kernel's fused DCT epilogue, plan key 4, stays off: on a CU share one workgroup per clip holding its 74 kB of
-            # LDS while two of its four wavefronts run the fp32 DCT loses to the separate dct_kernel -- stage 0.400 against 0.388 ms
-            # on 96 CUs, step 0.434 against 0.418 ms, round 4)
-        # the classifier's stream on the CUs the MFCC stream does not use
-        want = self._train_cus if self._train_cus != "auto" else os.environ.get("LIPASR_TRAIN_CUS", "all" if (self._custom_ex or self.pgd) else "rest")
-        if want == "rest" and k < n_groups:
-            mask2 = (C.c_uint32 * words)()
-            for g in range(k, n_groups):  # (partitions that share 32 or 64 CUs measured worse: 0.452-0.461 against 0.418 ms)
-                for b in range(8 * g, 8 * g + 8):
-                    mask2[b // 32] |= 1 << (b % 32)
-            st2 = N.c_s()
-            if N.lib.lipasr_stream_create_masked(self.h.h, mask2, words, C.byref(st2)) == N.OK:
-                self._masked_train_stream = st2
-                self.stream = torch.cuda.ExternalStream(st2.value, device=self.dev)
-                self.train_cus = 8 * (n_groups - k)
-                # on part of the chip the LDS-tiled GEMM pays from fewer tiles on (layer 2 forward, the dX GEMM into layer 2:
-                # 128 tiles): -16 us on the classifier's graph at 160 CUs (PGD, which keeps every CU, loses 8 % with it)
-                N.check(N.lib.lipasr_mlp_set_gemm_tiles(self.model._plan, int(os.environ.get("LIPASR_GEMM_TILES", "128"))))
-                # the fused BatchNorm exchange spins until a column block's workgroups are all resident: tell the plan how many
-                # CUs its stream really has (round 5)
-                N.check(N.lib.lipasr_mlp_set_cu_budget(self.model._plan, self.train_cus))
-                self._gemm_tiles_set = True  # the pipeline owns these settings: close() puts the model's plan back (ADVICE r3)
-        else:
-            self._own_queue_train_stream(n_cu)
-        return torch.cuda.ExternalStream(st.value, device=self.dev)
-
-    def _own_queue_train_stream(self, n_cu):
-        """The classifier keeps every CU (PGD, custom extractor, train_cus="all") -- but NOT on a stream of torch's pool: pool
-        streams are multiplexed over GPU_MAX_HW_QUEUES (4) hardware queues, and once enough streams exist in the process the
-        training stream can land on the queue that carries the MFCC stream's kernels; its 440-node PGD graph then waited
-        behind them node by node: 13.0 ms per step instead of 4.1 as the fifth configuration of one process (round 3's
-        unexplained 3x; round 4: scratch/pgd_fifth_probe.py, gone with GPU_MAX_HW_QUEUES=8).  A stream made with a FULL CU
-        mask owns a hardware queue like the two partition streams do."""
-        import os
-
-        if os.environ.get("LIPASR_TRAIN_OWN_QUEUE", "1") != "1":
-            return
-        words = (n_cu + 31) // 32
-        mask2 = (C.c_uint32 * words)()
-        for b in range(n_cu):
-            mask2[b // 32] |= 1 << (b % 32)
-        st2 = N.c_s()
-        if N.lib.lipasr_stream_create_masked(self.h.h, mask2, words, C.byref(st2)) == N.OK:
-            self._masked_train_stream = st2
-            self.stream = torch.cuda.ExternalStream(st2.value, device=self.dev)
+            warnings.warn(f"lipasr: CU-masked stream unavailable ({N.last_error()}); {warn}")
+        return None
 
     def _check_flags(self):
         """Reads the pinned report word of the device-side waits (no synchronisation).  Raises once per report and clears it,
         so that close() can still drain and release the streams afterwards."""
-        fe = self._flag_err
+        fe = self._handoff.err
         if fe is None:
             return
         code = int(fe[0])
@@ -323,61 +225,63 @@ class TrainPipeline:
             return x
         return self._pgd_loop(bsz, x, self._labels2[b][:bsz])
 
-    def _syncbn_step(self, bsz, b, gb):
-        """Synchronized BatchNorm: [PGD loop] -> segment 0 | all-reduce | segment 1 | ... | gradient all-reduce | update.
-        With graphs every piece between two collectives is one replayed HIP graph (the collectives themselves are eager
-        torch.distributed calls on the stream)."""
-        m = self.model
-        n_seg = m.syncbn_segments()
-        y = self._labels2[b][:bsz]
-        xin = (self.x_adv if self.pgd else self._feats2[b])[:bsz]
-        if not self.use_graph:
-            self._attack_only(bsz, b)
-            for seg in range(n_seg):
-                n = m.syncbn_segment(seg, xin, y, gb, self.dp.world)
-                if n:
-                    self.dp.allreduce_grads(m._part[:n])
-            self.dp.allreduce_grads(m._grads)
-            self._update()
-            return
-        key = (bsz, b, gb, "syncbn")
-        g = self._graphs.get(key)
-        if g is None:
-            counts = []
+    def _shape(self, bsz, b, gb):
+        """The classifier's part of a step, one of four shapes: its pieces (callables that enqueue on the current stream) and the
+        collectives between them, in order.  ("run", piece); ("reduce", t) a blocking all-reduce and ("start", t) an asynchronous
+        one of t(n), n being what the piece before returned, nothing for None; ("wait", None) for the ones started."""
+        m, dp = self.model, self.dp
+        if dp.world == 1:
+            free = self._handoff.free_ptr(b) if self._adam_signal else None  # free[b] goes out with the Adam kernel
+            return [("run", lambda: (self._attack_and_train(bsz, b, gb), self._update(free)))]
+        grads, update = ("reduce", lambda n: m._grads), ("run", self._update)
+        if self.sync_bn:
+            # synchronized BatchNorm: [PGD loop] -> segment 0 | all-reduce | segment 1 | ... | gradient all-reduce | update
+            y = self._labels2[b][:bsz]
+            xin = (self.x_adv if self.pgd else self._feats2[b])[:bsz]
+            sums = ("reduce", lambda n: m._part[:n] if n else None)  # the segment's BatchNorm column sums (none after the last)
+            shape = [("run", lambda: (self._attack_only(bsz, b), m.syncbn_segment(0, xin, y, gb, dp.world))[1]), sums]
+            for seg in range(1, m.syncbn_segments()):
+                shape += [("run", lambda s=seg: m.syncbn_segment(s, xin, y, gb, dp.world)), sums]
+            return shape + [grads, update]
+        if self.overlap_buckets:
+            # two gradient buckets (SURVEY 8e: reduce what is ready while the backward pass still computes):
+            # fwd/bwd without dW_0 -> [everything behind dW_0 | db_0 reduces, 44 % of the bytes] || dW_0 -> [dW_0 | db_0] -> update
+            late = self._late
+            return [("run", lambda: self._attack_and_train(bsz, b, gb, defer_dw0=True)), ("start", lambda n: m._grads[late:]),
+                    ("run", lambda: m.train_dw0((self.x_adv if self.pgd else self._feats2[b])[:bsz])), ("start", lambda n: m._grads[:late]),
+                    ("wait", None), update]
+        return [("run", lambda: self._attack_and_train(bsz, b, gb)), grads, update]
 
-            def first():
-                self._attack_only(bsz, b)
-                counts.append(m.syncbn_segment(0, xin, y, gb, self.dp.world))
-
-            ids = [self._capture(first)]
-            for seg in range(1, n_seg):
-                ids.append(self._capture(lambda s=seg: counts.append(m.syncbn_segment(s, xin, y, gb, self.dp.world))))
-            ids.append(self._capture(self._update))
-            self._sync_counts = getattr(self, "_sync_counts", {})
-            self._sync_counts[key] = counts
-            g = tuple(ids)
-            self._graphs[key] = g
-        counts = self._sync_counts[key]
-        for seg in range(n_seg):
-            N.check(N.lib.lipasr_graph_launch(self.h.h, g[seg], N.stream_ptr()))
-            if counts[seg]:
-                self.dp.allreduce_grads(m._part[:counts[seg]])
-        self.dp.allreduce_grads(m._grads)
-        N.check(N.lib.lipasr_graph_launch(self.h.h, g[n_seg], N.stream_ptr()))
-
-    def _dw0(self, bsz, b):
-        self.model.train_dw0((self.x_adv if self.pgd else self._feats2[b])[:bsz])
-
-    def _reduce_and_update_eager(self, bsz, b):
-        """world > 1, no graphs: head -> [bucket A reduces] || dW_0 -> bucket B -> Adam + projection."""
-        m = self.model
-        late = self._late
-        ha = self.dp.allreduce_async(m._grads[late:])
-        self._dw0(bsz, b)
-        hb = self.dp.allreduce_async(m._grads[:late])
-        ha.wait()
-        hb.wait()
-        self._update()
+    def _run_shape(self, bsz, b, gb):
+        """Walks the step's shape: eager mode calls its pieces, graph mode replays them, each captured once per (bsz, b, gb) --
+        the collectives (eager torch.distributed calls on the stream) sit between the same pieces in both."""
+        shape = self._shape(bsz, b, gb)
+        g = self._graphs.get((bsz, b, gb)) if self.use_graph else None
+        if self.use_graph and g is None:
+            rets = []  # (sync-BN: the segments' reduce counts; a capture runs nothing, so all pieces are captured before the first replay)
+            g = _Captured(self._capture(lambda p=p: rets.append(p())) for kind, p in shape if kind == "run")
+            g.rets = rets
+            self._graphs[(bsz, b, gb)] = g
+        k, ret, started = 0, None, []
+        for kind, arg in shape:
+            if kind == "run":
+                if g is None:
+                    ret = arg()
+                else:
+                    N.check(N.lib.lipasr_graph_launch(self.h.h, g[k], N.stream_ptr()))
+                    ret = g.rets[k]
+                k += 1
+            elif kind == "wait":
+                for handle in started:
+                    handle.wait()
+            else:
+                t = arg(ret)
+                if t is None:
+                    continue
+                if kind == "reduce":
+                    self.dp.allreduce_grads(t)
+                else:
+                    started.append(self.dp.allreduce_async(t))
 
     def _update(self, free_flag=None):
         m = self.model
@@ -446,111 +350,45 @@ class TrainPipeline:
         # temporary handed to step() and freed right after it is not recycled (the caching allocator re-issues a block on
         # the stream it was allocated on) while the MFCC kernels still read it.  (Not record_stream(): the allocator would
         # then record events on the CU-masked stream whenever such a block is freed -- also after close() destroyed it.)
-        caller = torch.cuda.current_stream(self.dev)
+        caller, ho, i = torch.cuda.current_stream(self.dev), self._handoff, self._i
         xs = self.mfcc_stream
-        idle = self.stream.query() if self._flags is not None else (self._last_train_ev is None or self._last_train_ev.query())
-        wide = self._wide_stream is not None and features is None and idle
+        wide = self._wide_stream is not None and features is None and ho.classifier_idle(self.stream)
         if wide:  # nothing runs on the classifier's CUs: this extraction may have them
             xs = self._wide_stream
             self.ex.set(1, self._n_cu)
         if self.sync_inputs:
             xs.wait_stream(caller)
         with torch.cuda.stream(xs):
-            if self._flags is not None:
-                if self._last_xs is not None and self._last_xs is not xs:
-                    xs.wait_stream(self._last_xs)  # the plan's scratch is shared: order this extraction after the last one on the other stream
-                self._last_xs = xs
-            elif self._ev_last_mfcc is not None and self._wide_stream is not None:
-                xs.wait_event(self._ev_last_mfcc)
-            if self._flags is not None:
-                fl = self._flags
-                if self._i > self._nbuf:
-                    N.check(N.lib.lipasr_flag_wait(self.h.h, fl[self._nbuf + b:].data_ptr(), self._i - self._nbuf, self._flag_timeout_ms, self._flag_err.data_ptr(), N.stream_ptr()))
-            elif self._ev_free[b] is not None:
-                xs.wait_event(self._ev_free[b])  # the step that last read this buffer is done
-            if features is not None:
+            ho.order_extraction(xs)
+            ho.wait_free(b, i, xs)                    # 1. the step that last read buffer b is done with it
+            if features is not None:                  # 2. the extraction
                 self._feats2[b][:bsz].copy_(features)
+            elif self._custom_ex:
+                self.ex(waves, self.mean, self.scale, out=self._feats2[b][:bsz])
             else:
-                if self._custom_ex:
-                    self.ex(waves, self.mean, self.scale, out=self._feats2[b][:bsz])
-                else:
-                    self.ex(waves, self.L, self.mean, self.scale, out=self._feats2[b][:bsz])
+                self.ex(waves, self.L, self.mean, self.scale, out=self._feats2[b][:bsz])
             self._labels2[b][:bsz].copy_(y_onehot)
-            if self._flags is not None:
-                N.check(N.lib.lipasr_flag_signal(self.h.h, self._flags[b:].data_ptr(), self._i, N.stream_ptr()))
-            else:
-                self._ev_feat[b].record(xs)
-                self._ev_last_mfcc = self._ev_feat[b]
+            ho.signal_ready(b, i, xs)                 # 3. features and labels of b are ready
         if wide:
             self.ex.set(1, self.mfcc_cus)
         if self.sync_inputs:
-            if self._flags is not None:
-                caller.wait_stream(xs)
-            else:
-                caller.wait_event(self._ev_feat[b])
+            ho.caller_waits(caller, b, xs)
         with torch.cuda.stream(self.stream):
             self._warm_start()
-            if self._flags is not None:
-                N.check(N.lib.lipasr_flag_wait(self.h.h, self._flags[b:].data_ptr(), self._i, self._flag_timeout_ms, self._flag_err.data_ptr(), N.stream_ptr()))
-            else:
-                self.stream.wait_event(self._ev_feat[b])
+            ho.wait_ready(b, i, self.stream)          # 4. the classifier waits for them
             prof = None
-            if getattr(self, "_prof", None) is not None and self._prof_i < len(self._prof):
+            if self._prof is not None and self._prof_i < len(self._prof):
                 prof = self._prof[self._prof_i]
                 self._prof_i += 1
                 prof[0].record(self.stream)
-            if self.sync_bn:
-                self._syncbn_step(bsz, b, gb)
-            elif not self.use_graph:
-                if self.dp.world == 1:
-                    self._attack_and_train(bsz, b, gb)
-                    self._update(self._flags[self._nbuf + b:].data_ptr() if self._adam_signal else None)
-                elif self.overlap_buckets:
-                    self._attack_and_train(bsz, b, gb, defer_dw0=True)
-                    self._reduce_and_update_eager(bsz, b)
-                else:
-                    self._attack_and_train(bsz, b, gb)
-                    self.dp.allreduce_grads(self.model._grads)
-                    self._update()
-            else:
-                g = self._graphs.get((bsz, b, gb))
-                if g is None:
-                    if self.dp.world == 1:
-                        g = (self._capture(lambda: (self._attack_and_train(bsz, b, gb), self._update())),)
-                    elif self.overlap_buckets:
-                        # three graphs around the two gradient buckets (reduce what is ready while the backward
-                        # pass still computes): [attack + fwd/bwd without dW_0] | [dW_0] | [Adam + projection]
-                        g = (self._capture(self._attack_and_train, bsz, b, gb, True), self._capture(self._dw0, bsz, b),
-                             self._capture(self._update))
-                    else:
-                        g = (self._capture(self._attack_and_train, bsz, b, gb), self._capture(self._update))
-                    self._graphs[(bsz, b, gb)] = g
-                N.check(N.lib.lipasr_graph_launch(self.h.h, g[0], N.stream_ptr()))
-                if len(g) == 3:
-                    late = self._late
-                    ha = self.dp.allreduce_async(self.model._grads[late:])   # 44 % of the bytes, beside the dW_0 GEMM
-                    N.check(N.lib.lipasr_graph_launch(self.h.h, g[1], N.stream_ptr()))
-                    hb = self.dp.allreduce_async(self.model._grads[:late])
-                    ha.wait()
-                    hb.wait()
-                    N.check(N.lib.lipasr_graph_launch(self.h.h, g[2], N.stream_ptr()))
-                elif len(g) == 2:
-                    self.dp.allreduce_grads(self.model._grads)
-                    N.check(N.lib.lipasr_graph_launch(self.h.h, g[1], N.stream_ptr()))
+            self._run_shape(bsz, b, gb)               # 5. attack, forward / backward, collectives, update
             if prof is not None:
                 prof[1].record(self.stream)
-            if self._adam_signal:
-                pass  # free[b] went out with the Adam kernel
-            elif self._flags is not None:
-                N.check(N.lib.lipasr_flag_signal(self.h.h, self._flags[self._nbuf + b:].data_ptr(), self._i, N.stream_ptr()))
-            else:
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-                self._ev_free[b] = ev
-                self._last_train_ev = ev
+            if not self._adam_signal:                 # 6. the classifier is done with b (or its Adam kernel said so in 5)
+                ho.signal_free(b, i, self.stream)
 
     def synchronize(self):
-        if getattr(self, "_wide_stream", None) is not None:
+        if self._wide_stream is not None:
             self._wide_stream.synchronize()
         self.mfcc_stream.synchronize()
         self.stream.synchronize()
