@@ -20,26 +20,19 @@
 // same values (a zero may differ in sign: the padded k steps of a tile turn a -0 accumulator into +0).
 // Rows are independent everywhere, so a NaN stays in its row; the flag of bounds_prep_kernel makes such a row's margins NaN.
 // Loads and stores are single floats, guarded: any width, any batch, any alignment.  Nothing allocates or synchronises.
-#include "common.h"
-#include "row.h"
-#include "mlp.h"
+#include "bounds.h"
 
 // host and device must round alike, and a product that is rounded before its sum is what the error bounds below assume
 #pragma clang fp contract(off)
 
 namespace lipasr {
 
-typedef float bd_f32x16 __attribute__((ext_vector_type(16)));
-
 long g_bounds_launches[5] = {};
 enum { BD_PREP = 0, BD_LAYER = 1, BD_HEAD = 2, BD_BACK = 3, BD_TAIL = 4 };
 
-constexpr int kBdMaxWidth = 4096;                  // (width + 2) 2^-53 <= kBdD / 2 and gamma_{width + 1} << 1
 constexpr double kBdU = 5.9604644775390625e-08;    // 2^-24, the unit roundoff of fp32
 constexpr double kBdTiny = 1.401298464324817e-45;  // 2^-149, the smallest fp32 subnormal
 constexpr double kBdD = 9.094947017729282e-13;     // 2^-40: covers every fp64 rounding of a sum of <= 4096 + 2 terms
-
-#define BD_HD __host__ __device__ __forceinline__
 
 BD_HD unsigned bd_bits(float f) { return __builtin_bit_cast(unsigned, f); }
 BD_HD float bd_float(unsigned u) { return __builtin_bit_cast(float, u); }
@@ -69,15 +62,6 @@ BD_HD double bd_max(double a, double b) { return a < b ? b : a; }
 BD_HD double bd_gamma(int n) { return n * kBdU / (1.0 - n * kBdU); }
 // what an fmaf chain of K products plus the bias can be off by, given S >= sum of the magnitudes: two chains meet in one bound
 BD_HD double bd_widen(int K, double S) { return bd_gamma(K + 1) * S + 2.0 * (K + 1) * kBdTiny; }
-
-// h = s relu(z) + t in inference mode; tm bounds the magnitudes t was made of
-struct BdAff { double s, t, tm; };
-BD_HD BdAff bd_aff(const float* gamma, const float* beta, const float* mmean, const float* mvar, int j) {
-  if (!gamma) return BdAff{1.0, 0.0, 0.0};
-  const double s = (double)gamma[j] / sqrt((double)mvar[j] + (double)kBnEps);
-  const double sm = s * (double)mmean[j];
-  return BdAff{s, (double)beta[j] - sm, fabs((double)beta[j]) + fabs(sm)};
-}
 
 // the input box of one element: [x - eps, x + eps] /\ [clip_lo, clip_hi], rounded outward (exact at eps = 0)
 BD_HD void bd_input_box(float x, float eps, float clip_lo, float clip_hi, float& lo, float& hi) {
@@ -191,23 +175,10 @@ BD_HD double bd_red_finish(const BdRed& r, bool l2, float eps) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------- the plan
-struct BdShape {
-  int L = 0;
-  int n[LIPASR_MAX_LAYERS + 1] = {};
-  bool bn[LIPASR_MAX_LAYERS] = {};
-  size_t offW[LIPASR_MAX_LAYERS] = {}, offb[LIPASR_MAX_LAYERS] = {}, offg[LIPASR_MAX_LAYERS] = {}, offbe[LIPASR_MAX_LAYERS] = {};
-  size_t offmm[LIPASR_MAX_LAYERS] = {}, offmv[LIPASR_MAX_LAYERS] = {};
-  size_t n_params = 0, n_state = 0;
-};
-
-static size_t bd_align4(size_t v) { return (v + 3) & ~(size_t)3; }
-
 // the workspace, in floats from a 16-byte boundary.  The lo family is one span [lo0 | zlo_1 | hlo_1 | zlo_2 | ...], the hi family
 // likewise: layer_lo / layer_hi are one copy each.
-struct BdPlan {
-  size_t fam = 0;                      // floats of one family
+struct BdPlan : BdBoxes {              // fam: floats of one family; z / h: offsets inside a family, hidden layers 0 .. L - 2
   size_t offLo = 0, offHi = 0;         // the families
-  size_t z[LIPASR_MAX_LAYERS] = {}, h[LIPASR_MAX_LAYERS] = {};  // offsets inside a family, hidden layers 0 .. L - 2
   size_t offS[LIPASR_MAX_LAYERS] = {};
   size_t offNorm = 0, offFlag = 0, offLam[2] = {}, offAcc = 0, offPart[LIPASR_MAX_LAYERS] = {};
   int tiles[LIPASR_MAX_LAYERS] = {};   // partial columns of back stage l (the product with W_l, l = 1 .. L - 2): 4 ceil(n_l / 128)
@@ -216,14 +187,8 @@ struct BdPlan {
 
 static BdPlan bd_plan(const BdShape& sh, int batch) {
   BdPlan p;
-  const size_t B = batch, C = sh.n[sh.L], M = B * C;
-  size_t f = 0;
-  f += B * sh.n[0];
-  for (int l = 0; l + 1 < sh.L; ++l) {
-    p.z[l] = f; f += B * sh.n[l + 1];
-    p.h[l] = f; f += B * sh.n[l + 1];
-  }
-  p.fam = f;
+  static_cast<BdBoxes&>(p) = bd_boxes(sh, batch);
+  const size_t B = batch, C = sh.n[sh.L], M = B * C, f = p.fam;
   size_t o = 0;
   p.offLo = o; o = bd_align4(o + f);
   p.offHi = o; o = bd_align4(o + f);
@@ -245,8 +210,6 @@ static BdPlan bd_plan(const BdShape& sh, int batch) {
   return p;
 }
 
-static float* bd_base(float* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15); }
-
 // the partial sums of the back stages, as the tail reads them
 struct BdStages {
   int count;
@@ -255,7 +218,6 @@ struct BdStages {
 };
 
 // -------------------------------------------------------------------------------------------------------------------- kernels
-constexpr int kBdThreads = 256;
 constexpr int kBdNormSlices = kBdThreads / 32;
 
 __device__ __forceinline__ double bd_sum32(double v) {
@@ -798,7 +760,7 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
 }
 
 // --------------------------------------------------------------------------------------------------------------------- checks
-static int bd_shape_from(const char* fn, int n_layers, const int* widths, const int* bn, BdShape* sh) {
+int bd_shape_from(const char* fn, int n_layers, const int* widths, const int* bn, BdShape* sh) {
   LP_CHECK_ARG(widths != nullptr, "%s: null argument", fn);
   LP_CHECK_ARG(n_layers >= 1 && n_layers <= LIPASR_MAX_LAYERS, "%s: n_layers=%d outside [1,%d]", fn, n_layers, LIPASR_MAX_LAYERS);
   for (int l = 0; l <= n_layers; ++l)
@@ -826,7 +788,7 @@ static int bd_shape_from(const char* fn, int n_layers, const int* widths, const 
   return LIPASR_OK;
 }
 
-static int bd_shape_of(const char* fn, lipasr_mlp_t m, BdShape* sh) {
+int bd_shape_of(const char* fn, lipasr_mlp_t m, BdShape* sh) {
   LP_CHECK_ARG(m != nullptr, "%s: null argument", fn);
   sh->L = m->n_layers;
   for (int l = 0; l < m->n_layers; ++l) {

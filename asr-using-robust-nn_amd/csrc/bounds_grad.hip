@@ -1,0 +1,680 @@
+// IBP certified training (lipasr/bounds.py, IBPCrossentropy): the backward pass of the interval bounds of bounds.hip with respect
+// to the parameters.  DESIGN.md, "Certified training", derives every line below.  Per row b, from what ONE lipasr_mlp_bounds call
+// wrote (margin_ibp and the boxes layer_lo / layer_hi), under norm inf:
+//
+//   u[b][k] = -margin_ibp[b][k] (k != y_b), u[b][y_b] = 0      loss_rows[b] = logsumexp_k u[b][k]
+//   grads = scale_old grads + scale_new d(sum_b loss_rows[b]) / d params
+//
+//   bg_head_kernel     1 launch   a block per row: softmax of u, loss_rows, d loss / d u, the gradient into the last hidden box
+//                                 through the difference rows W_L[y] - W_L[k] (lo where the difference is > 0, hi otherwise), and
+//                                 the BatchNorm and ReLU gates of layer L - 1: (gc, gr) of that layer and what its column sums need
+//   bg_head_dw_kernel  1          dW_L and db_L: 8 entries a block, the batch in 32 interleaved fp64 slices that meet in index order
+//   bg_colsum_kernel   L - 1      db_l, dgamma_l, dbeta_l of a hidden layer: 8 columns a block, the same 32 slices
+//   bg_wgrad_kernel    L - 1      dW_l = c^T gc + sign(W_l) (r^T gr): a 32 x 128 tile of both products on v_mfma_f32_32x32x2_f32, the
+//                                 batch as the k dimension, c and r formed in registers from lo / hi, the next chunk's loads in flight
+//                                 during the MFMAs; epilogue: the sign of W, the two scales, the store into grads
+//   bg_back_kernel     L - 2      (g_c, g_r) = (gc W_l^T, gr |W_l|^T) from ONE read of W_l on the same tile; epilogue: g_lo, g_hi, layer
+//                                 l - 1's BatchNorm and ReLU gates, (gc, gr) of layer l - 1 and what its column sums need
+//
+// Launches of one call with L layers: 2 for L = 1, 3 (L - 1) + 1 for L >= 2.  Every sum has one order that the shapes fix: the
+// MFMA is an fmaf chain in ascending k, a column sum is 32 interleaved slices in ascending row order that meet in slice order.  No
+// atomics: two calls give the same bits, and the host twin, which runs the same inline functions in those orders, gives the same
+// values (a zero may differ in sign).  exp and log are written out in + * / below for that reason.  Conventions, torch's:
+// relu'(0) = 0, d|w| / dw = 0 at 0, s >= 0 takes the branch that does not swap, a difference of 0 selects hi; the widening and the
+// outward roundings of the forward pass are constants; the input box carries no gradient.  A row whose margins are NaN (or whose
+// label is outside [0, classes)) makes its loss and the whole gradient NaN.
+// Loads and stores are single floats, guarded: any width, any batch, any alignment.  Nothing allocates or synchronises.
+#include "bounds.h"
+
+// host and device must round alike
+#pragma clang fp contract(off)
+
+namespace lipasr {
+
+long g_bounds_grad_launches[4] = {};
+enum { BG_HEAD = 0, BG_WGRAD = 1, BG_BACK = 2, BG_COLSUM = 3 };
+
+// a column sum over the batch: a block takes kBgCols columns, thread slice s of a column the rows s, s + kBgSlices, ...  (8 x 32
+// and not 32 x 8: at batch 1024 a slice is 32 dependent loads, not 128, and a 1024-wide layer is 128 blocks, not 32)
+constexpr int kBgCols = 8;
+constexpr int kBgSlices = kBdThreads / kBgCols;
+
+// exp and log in plain arithmetic: the same bits on the host and on the device.  |error| < 2^-50 relative on the ranges used
+// (exp: x <= 0 after the row's maximum is taken off; log: a sum in [1, 32]).
+BD_HD double bg_pow2(int n) { return __builtin_bit_cast(double, (unsigned long long)(n + 1023) << 52); }
+BD_HD double bg_exp(double x) {
+  if (x != x) return x;
+  if (x < -745.0) return 0.0;
+  if (x > 709.0) return INFINITY;
+  const double kf = x * 1.4426950408889634;
+  const int n = (int)(kf + (kf < 0.0 ? -0.5 : 0.5));
+  const double r = (x - n * 0.693147180369123816490e+00) - n * 1.90821492927058770002e-10;
+  double p = 1.0;
+  for (int k = 13; k >= 1; --k) p = 1.0 + r * p / (double)k;
+  return n < -1000 ? p * bg_pow2(n + 100) * bg_pow2(-100) : p * bg_pow2(n);
+}
+BD_HD double bg_log(double s) {
+  if (!(s > 0.0) || s == INFINITY) return s != s ? s : (s == INFINITY ? s : (s == 0.0 ? -INFINITY : NAN));
+  const unsigned long long bits = __builtin_bit_cast(unsigned long long, s);
+  int e = (int)((bits >> 52) & 0x7ff) - 1023;
+  double m = __builtin_bit_cast(double, (bits & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
+  if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
+  const double f = (m - 1.0) / (m + 1.0), f2 = f * f;
+  double q = 1.0 / 23.0;
+  for (int k = 21; k >= 1; k -= 2) q = q * f2 + 1.0 / (double)k;
+  return e * 0.693147180369123816490e+00 + (2.0 * f * q + e * 1.90821492927058770002e-10);
+}
+
+BD_HD float bg_mix(float old, float v, float scale_old, float scale_new) {
+  return scale_old == 0.0f ? scale_new * v : scale_old * old + scale_new * v;
+}
+BD_HD int bg_label(int y, int C) { return (y >= 0 && y < C) ? y : 0; }
+
+// the gradient (glo, ghi) on the box of h = s relu(z) + t becomes (gc, gr) = (g_zlo + g_zhi, g_zhi - g_zlo) on the box of z, and
+// the terms of d loss / d s and d loss / d t.  A gate multiplies, so that a NaN stays.
+BD_HD void bg_gate(double glo, double ghi, double s, float zlo, float zhi, float& gc, float& gr, float& es, float& et) {
+  const double alo = zlo > 0.0f ? (double)zlo : 0.0, ahi = zhi > 0.0f ? (double)zhi : 0.0;
+  const double ml = zlo > 0.0f ? 1.0 : 0.0, mh = zhi > 0.0f ? 1.0 : 0.0;
+  double gzlo, gzhi, ds;
+  if (s >= 0.0) {
+    gzlo = s * glo * ml;
+    gzhi = s * ghi * mh;
+    ds = glo * alo + ghi * ahi;
+  } else {
+    gzhi = s * glo * mh;
+    gzlo = s * ghi * ml;
+    ds = glo * ahi + ghi * alo;
+  }
+  gc = (float)(gzlo + gzhi);
+  gr = (float)(gzhi - gzlo);
+  es = (float)ds;
+  et = (float)(glo + ghi);
+}
+
+// one column j of a row's head: p[k] the softmax of u, wl = W_L[j][0 .. C).  ty = d loss / d W_L[j][y]
+BD_HD void bg_head_column(const double* p, const float* wl, int C, int yb, float lo, float hi, double& glo, double& ghi, double& ty) {
+  const double wy = wl[yb];
+  glo = ghi = ty = 0.0;
+  for (int k = 0; k < C; ++k) {
+    if (k == yb) continue;
+    const double d = wy - (double)wl[k], q = -p[k];
+    if (d > 0.0) {
+      glo = glo + q * d;
+      ty = ty + q * (double)lo;
+    } else {
+      ghi = ghi + q * d;
+      ty = ty + q * (double)hi;
+    }
+  }
+}
+
+// one term of entry e of [dW_L | db_L] from row b
+BD_HD double bg_head_dw_term(int e, int nh, int C, int b, int yb, const float* WL, const float* coef, const float* ty, const float* lo,
+                             const float* hi) {
+  if (e >= nh * C) return coef[(size_t)b * C + (e - nh * C)];
+  const int j = e / C, k = e % C;
+  if (k == yb) return ty[(size_t)b * nh + j];
+  const double d = (double)WL[(size_t)j * C + yb] - (double)WL[(size_t)j * C + k];
+  return (double)coef[(size_t)b * C + k] * (double)(d > 0.0 ? lo[(size_t)b * nh + j] : hi[(size_t)b * nh + j]);
+}
+
+// dgamma and dbeta of a column from the sums of es and et
+BD_HD void bg_bn_grads(double sum_s, double sum_t, float mmean, float mvar, double& dgamma, double& dbeta) {
+  const double rstd = 1.0 / sqrt((double)mvar + (double)kBnEps);
+  dgamma = (sum_s - (double)mmean * sum_t) * rstd;
+  dbeta = sum_t;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- the plan
+// the workspace, in floats from a 16-byte boundary; z / h / fam: the boxes of layer_lo / layer_hi (bd_boxes)
+struct BgPlan : BdBoxes {
+  size_t offCoef = 0, offTy = 0, offG[2][2] = {}, offE[2][2] = {};
+  size_t total = 0;
+};
+
+static BgPlan bg_plan(const BdShape& sh, int batch) {
+  BgPlan p;
+  static_cast<BdBoxes&>(p) = bd_boxes(sh, batch);
+  const size_t B = batch, C = sh.n[sh.L];
+  size_t maxh = 0;
+  for (int l = 0; l + 1 < sh.L; ++l) maxh = std::max(maxh, (size_t)sh.n[l + 1]);
+  size_t o = 0;
+  p.offCoef = o; o = bd_align4(o + B * C);
+  p.offTy = o; o = bd_align4(o + B * sh.n[sh.L - 1]);
+  for (int s = 0; s < 2; ++s)
+    for (int q = 0; q < 2; ++q) {
+      p.offG[s][q] = o; o = bd_align4(o + B * maxh);
+      p.offE[s][q] = o; o = bd_align4(o + B * maxh);
+    }
+  p.total = o + 4;
+  return p;
+}
+
+// -------------------------------------------------------------------------------------------------------------------- kernels
+// a block per row b
+__global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __restrict__ margin, const int* __restrict__ y,
+                                                             const float* __restrict__ WL, int C, int nh, const float* __restrict__ lo,
+                                                             const float* __restrict__ hi, int hidden, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, const float* __restrict__ mmean,
+                                                             const float* __restrict__ mvar, const float* __restrict__ zlo,
+                                                             const float* __restrict__ zhi, float* __restrict__ loss_rows,
+                                                             float* __restrict__ coef, float* __restrict__ ty_out, float* __restrict__ gc,
+                                                             float* __restrict__ gr, float* __restrict__ es, float* __restrict__ et) {
+  __shared__ double p[32];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int yraw = y[b], yb = bg_label(yraw, C);
+  const bool ok = yraw == yb;
+  if (tid < C) p[tid] = tid == yb ? 0.0 : -(double)margin[(size_t)b * C + tid];
+  __syncthreads();
+  double mx = 0.0;
+  for (int k = 0; k < C; ++k) mx = p[k] > mx ? p[k] : mx;
+  __syncthreads();
+  if (tid < C) p[tid] = ok ? bg_exp(p[tid] - mx) : NAN;
+  __syncthreads();
+  double sum = 0.0;
+  for (int k = 0; k < C; ++k) sum = sum + p[k];
+  __syncthreads();
+  if (tid < C) p[tid] = p[tid] / sum;
+  __syncthreads();
+  if (tid == 0) loss_rows[b] = (float)(mx + bg_log(sum));
+  if (tid < C) {
+    double v = p[tid];
+    if (tid == yb) {
+      v = 0.0;
+      for (int k = 0; k < C; ++k)
+        if (k != yb) v = v - p[k];
+    }
+    coef[(size_t)b * C + tid] = (float)v;
+  }
+  for (int j = tid; j < nh; j += kBdThreads) {
+    const size_t at = (size_t)b * nh + j;
+    double glo, ghi, ty;
+    bg_head_column(p, WL + (size_t)j * C, C, yb, lo[at], hi[at], glo, ghi, ty);
+    ty_out[at] = (float)ty;
+    if (hidden) {
+      float vc, vr, vs, vt;
+      bg_gate(glo, ghi, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[at], zhi[at], vc, vr, vs, vt);
+      gc[at] = vc;
+      gr[at] = vr;
+      if (gamma) {
+        es[at] = vs;
+        et[at] = vt;
+      }
+    }
+  }
+}
+
+// kBgCols entries of [dW_L | db_L] a block
+__global__ __launch_bounds__(kBdThreads) void bg_head_dw_kernel(const float* __restrict__ WL, const int* __restrict__ y,
+                                                                const float* __restrict__ coef, const float* __restrict__ ty,
+                                                                const float* __restrict__ lo, const float* __restrict__ hi, int batch, int C,
+                                                                int nh, float scale_old, float scale_new, float* __restrict__ dW,
+                                                                float* __restrict__ db) {
+  __shared__ double parts[kBgSlices][kBgCols];
+  const int el = threadIdx.x % kBgCols, sl = threadIdx.x / kBgCols;
+  const int e = blockIdx.x * kBgCols + el, E = nh * C + C;
+  double acc = 0.0;
+  if (e < E)
+    for (int b = sl; b < batch; b += kBgSlices) acc = acc + bg_head_dw_term(e, nh, C, b, bg_label(y[b], C), WL, coef, ty, lo, hi);
+  parts[sl][el] = acc;
+  __syncthreads();
+  if (sl == 0 && e < E) {
+    double tot = parts[0][el];
+    for (int q = 1; q < kBgSlices; ++q) tot = tot + parts[q][el];
+    float* out = e < nh * C ? dW + e : db + (e - nh * C);
+    *out = bg_mix(*out, (float)tot, scale_old, scale_new);
+  }
+}
+
+// kBgCols columns of a hidden layer a block: db, and (BatchNorm) dgamma and dbeta
+__global__ __launch_bounds__(kBdThreads) void bg_colsum_kernel(const float* __restrict__ gc, const float* __restrict__ es,
+                                                               const float* __restrict__ et, const float* __restrict__ mmean,
+                                                               const float* __restrict__ mvar, int batch, int N, float scale_old,
+                                                               float scale_new, float* __restrict__ db, float* __restrict__ dgamma,
+                                                               float* __restrict__ dbeta) {
+  __shared__ double parts[3][kBgSlices][kBgCols];
+  const int jl = threadIdx.x % kBgCols, sl = threadIdx.x / kBgCols;
+  const int j = blockIdx.x * kBgCols + jl;
+  double ab = 0.0, as = 0.0, at = 0.0;
+  if (j < N)
+    for (int b = sl; b < batch; b += kBgSlices) {
+      const size_t i = (size_t)b * N + j;
+      ab = ab + (double)gc[i];
+      if (dgamma) {
+        as = as + (double)es[i];
+        at = at + (double)et[i];
+      }
+    }
+  parts[0][sl][jl] = ab;
+  parts[1][sl][jl] = as;
+  parts[2][sl][jl] = at;
+  __syncthreads();
+  if (sl == 0 && j < N) {
+    double tb = parts[0][0][jl], ts = parts[1][0][jl], tt = parts[2][0][jl];
+    for (int q = 1; q < kBgSlices; ++q) {
+      tb = tb + parts[0][q][jl];
+      ts = ts + parts[1][q][jl];
+      tt = tt + parts[2][q][jl];
+    }
+    db[j] = bg_mix(db[j], (float)tb, scale_old, scale_new);
+    if (dgamma) {
+      double dg, dbe;
+      bg_bn_grads(ts, tt, mmean[j], mvar[j], dg, dbe);
+      dgamma[j] = bg_mix(dgamma[j], (float)dg, scale_old, scale_new);
+      dbeta[j] = bg_mix(dbeta[j], (float)dbe, scale_old, scale_new);
+    }
+  }
+}
+
+// dW[i][j] = sum_b c[b][i] gc[b][j] + sign(W[i][j]) sum_b r[b][i] gr[b][j]: rows i0 .. i0 + 31 (blockIdx.x), columns
+// j0 .. j0 + 127 (blockIdx.y), a wavefront per 32 columns, the batch in chunks of 32.
+__global__ __launch_bounds__(kBdThreads) void bg_wgrad_kernel(const float* __restrict__ lo, const float* __restrict__ hi,
+                                                              const float* __restrict__ gc, const float* __restrict__ gr,
+                                                              const float* __restrict__ W, int batch, int K, int N, float scale_old,
+                                                              float scale_new, float* __restrict__ dW) {
+  __shared__ float cs[32 * 33], rs[32 * 33], gcs[32 * 128], grs[32 * 128];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 128;
+  bd_f32x16 acc_c, acc_r;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc_c[e] = acc_r[e] = 0.0f;
+  // a row past the batch, a unit past K and a column past N read as 0
+  float lreg[4], hreg[4], creg[16], rreg[16];
+  auto fetch = [&](int b0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q, bb = idx >> 5, ii = idx & 31;
+      const int b = b0 + bb, i = i0 + ii;
+      const bool in = b < batch && i < K;
+      const size_t at = (size_t)b * K + i;
+      lreg[q] = in ? lo[at] : 0.0f;
+      hreg[q] = in ? hi[at] : 0.0f;
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = tid + kBdThreads * q, bb = idx >> 7, col = idx & 127;
+      const int b = b0 + bb, j = j0 + col;
+      const bool in = b < batch && j < N;
+      const size_t at = (size_t)b * N + j;
+      creg[q] = in ? gc[at] : 0.0f;
+      rreg[q] = in ? gr[at] : 0.0f;
+    }
+  };
+  fetch(0);
+  for (int b0 = 0; b0 < batch; b0 += 32) {
+    __syncthreads();  // the previous chunk is read
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q, bb = idx >> 5, ii = idx & 31;
+      cs[bb * 33 + ii] = 0.5f * (lreg[q] + hreg[q]);
+      rs[bb * 33 + ii] = 0.5f * (hreg[q] - lreg[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      gcs[tid + kBdThreads * q] = creg[q];
+      grs[tid + kBdThreads * q] = rreg[q];
+    }
+    __syncthreads();
+    if (b0 + 32 < batch) fetch(b0 + 32);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const int bb = 2 * s + h;
+      acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(cs[bb * 33 + li], gcs[bb * 128 + wave * 32 + li], acc_c, 0, 0, 0);
+      acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(rs[bb * 33 + li], grs[bb * 128 + wave * 32 + li], acc_r, 0, 0, 0);
+    }
+  }
+  const int j = j0 + wave * 32 + li;
+  if (j >= N) return;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int i = i0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    if (i >= K) continue;
+    const size_t at = (size_t)i * N + j;
+    const float w = W[at];
+    const float sg = w > 0.0f ? 1.0f : (w < 0.0f ? -1.0f : 0.0f);
+    dW[at] = bg_mix(dW[at], acc_c[e] + sg * acc_r[e], scale_old, scale_new);
+  }
+}
+
+// (g_c, g_r)[b][i] = sum_j (gc[b][j] W[i][j], gr[b][j] |W[i][j]|): rows b0 .. b0 + 31 (blockIdx.x), columns i0 .. i0 + 127
+// (blockIdx.y).  The epilogue applies the layer below: its BatchNorm scale and the z box of row b.
+__global__ __launch_bounds__(kBdThreads) void bg_back_kernel(const float* __restrict__ gc, const float* __restrict__ gr,
+                                                             const float* __restrict__ W, int batch, int K, int N,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             const float* __restrict__ mmean, const float* __restrict__ mvar,
+                                                             const float* __restrict__ zlo, const float* __restrict__ zhi,
+                                                             float* __restrict__ gc_out, float* __restrict__ gr_out,
+                                                             float* __restrict__ es, float* __restrict__ et) {
+  __shared__ float a1[32 * 33], a2[32 * 33], wt[128 * 33];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  const int b0 = blockIdx.x * 32, i0 = blockIdx.y * 128;
+  bd_f32x16 acc_c, acc_r;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc_c[e] = acc_r[e] = 0.0f;
+  float creg[4], rreg[4], wreg[16];  // the next chunk, in flight while the current one feeds the MFMAs
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+      const int b = b0 + row, k = k0 + kk;
+      const bool in = b < batch && k < K;
+      const size_t at = (size_t)b * K + k;
+      creg[q] = in ? gc[at] : 0.0f;
+      rreg[q] = in ? gr[at] : 0.0f;
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = tid + kBdThreads * q, il = idx >> 5, kk = idx & 31;
+      const int i = i0 + il, k = k0 + kk;
+      wreg[q] = (i < N && k < K) ? W[(size_t)i * K + k] : 0.0f;
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += 32) {
+    __syncthreads();  // the previous chunk is read
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + kBdThreads * q;
+      a1[(idx >> 5) * 33 + (idx & 31)] = creg[q];
+      a2[(idx >> 5) * 33 + (idx & 31)] = rreg[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = tid + kBdThreads * q;
+      wt[(idx >> 5) * 33 + (idx & 31)] = wreg[q];
+    }
+    __syncthreads();
+    if (k0 + 32 < K) fetch(k0 + 32);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float w = wt[(wave * 32 + li) * 33 + 2 * s + h];
+      acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[li * 33 + 2 * s + h], w, acc_c, 0, 0, 0);
+      acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[li * 33 + 2 * s + h], fabsf(w), acc_r, 0, 0, 0);
+    }
+  }
+  const int i = i0 + wave * 32 + li;
+  if (i >= N) return;
+  const double s = bd_aff(gamma, beta, mmean, mvar, i).s;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int b = b0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    if (b >= batch) continue;
+    const size_t at = (size_t)b * N + i;
+    const double c = acc_c[e], r = acc_r[e];
+    float vc, vr, vs, vt;
+    bg_gate(0.5 * (c - r), 0.5 * (c + r), s, zlo[at], zhi[at], vc, vr, vs, vt);
+    gc_out[at] = vc;
+    gr_out[at] = vr;
+    if (gamma) {
+      es[at] = vs;
+      et[at] = vt;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host twin
+static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, const float* bnstate, const float* margin,
+                    const float* layer_lo, const float* layer_hi, const int* y, int batch, float* ws, float scale_old, float scale_new,
+                    float* grads, float* loss_rows) {
+  const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
+  const bool hidden = L > 1;
+  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
+    g = be = mm = mv = nullptr;
+    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
+  };
+  const float *g = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
+  float* coef = ws + pl.offCoef;
+  float* ty = ws + pl.offTy;
+  const float* WL = params + sh.offW[L - 1];
+  const float* hlo = hidden ? layer_lo + pl.h[L - 2] : layer_lo;
+  const float* hhi = hidden ? layer_hi + pl.h[L - 2] : layer_hi;
+  int cur = 0;
+  // head
+  if (hidden) bnp(L - 2, g, be, mm, mv);
+  for (int b = 0; b < batch; ++b) {
+    double p[32];
+    const int yb = bg_label(y[b], C);
+    const bool ok = yb == y[b];
+    double mx = 0.0, sum = 0.0;
+    for (int k = 0; k < C; ++k) {
+      p[k] = k == yb ? 0.0 : -(double)margin[(size_t)b * C + k];
+      mx = p[k] > mx ? p[k] : mx;
+    }
+    for (int k = 0; k < C; ++k) {
+      p[k] = ok ? bg_exp(p[k] - mx) : NAN;
+      sum = sum + p[k];
+    }
+    for (int k = 0; k < C; ++k) p[k] = p[k] / sum;
+    loss_rows[b] = (float)(mx + bg_log(sum));
+    double vy = 0.0;
+    for (int k = 0; k < C; ++k)
+      if (k != yb) vy = vy - p[k];
+    for (int k = 0; k < C; ++k) coef[(size_t)b * C + k] = (float)(k == yb ? vy : p[k]);
+    for (int j = 0; j < nh; ++j) {
+      const size_t at = (size_t)b * nh + j;
+      double glo, ghi, t;
+      bg_head_column(p, WL + (size_t)j * C, C, yb, hlo[at], hhi[at], glo, ghi, t);
+      ty[at] = (float)t;
+      if (hidden) {
+        float vs, vt;
+        bg_gate(glo, ghi, bd_aff(g, be, mm, mv, j).s, layer_lo[pl.z[L - 2] + at], layer_hi[pl.z[L - 2] + at], ws[pl.offG[cur][0] + at],
+                ws[pl.offG[cur][1] + at], vs, vt);
+        if (g) { ws[pl.offE[cur][0] + at] = vs; ws[pl.offE[cur][1] + at] = vt; }
+      }
+    }
+  }
+  auto sliced = [&](auto term) {
+    double part[kBgSlices] = {};
+    for (int b = 0; b < batch; ++b) part[b % kBgSlices] = part[b % kBgSlices] + term(b);
+    double tot = part[0];
+    for (int q = 1; q < kBgSlices; ++q) tot = tot + part[q];
+    return tot;
+  };
+  for (int e = 0; e < nh * C + C; ++e) {
+    const double tot = sliced([&](int b) { return bg_head_dw_term(e, nh, C, b, bg_label(y[b], C), WL, coef, ty, hlo, hhi); });
+    float* out = e < nh * C ? grads + sh.offW[L - 1] + e : grads + sh.offb[L - 1] + (e - nh * C);
+    *out = bg_mix(*out, (float)tot, scale_old, scale_new);
+  }
+  // hidden layers, top down
+  std::vector<float> accc, accr;
+  for (int l = L - 2; l >= 0; --l) {
+    const int K = sh.n[l], N = sh.n[l + 1];
+    const float* gc = ws + pl.offG[cur][0];
+    const float* gr = ws + pl.offG[cur][1];
+    const float* es = ws + pl.offE[cur][0];
+    const float* et = ws + pl.offE[cur][1];
+    const float* W = params + sh.offW[l];
+    bnp(l, g, be, mm, mv);
+    for (int j = 0; j < N; ++j) {
+      const double tb = sliced([&](int b) { return (double)gc[(size_t)b * N + j]; });
+      float* db = grads + sh.offb[l] + j;
+      *db = bg_mix(*db, (float)tb, scale_old, scale_new);
+      if (g) {
+        const double ts = sliced([&](int b) { return (double)es[(size_t)b * N + j]; });
+        const double tt = sliced([&](int b) { return (double)et[(size_t)b * N + j]; });
+        double dg, dbe;
+        bg_bn_grads(ts, tt, mm[j], mv[j], dg, dbe);
+        float* og = grads + sh.offg[l] + j;
+        float* ob = grads + sh.offbe[l] + j;
+        *og = bg_mix(*og, (float)dg, scale_old, scale_new);
+        *ob = bg_mix(*ob, (float)dbe, scale_old, scale_new);
+      }
+    }
+    const float* ilo = l == 0 ? layer_lo : layer_lo + pl.h[l - 1];
+    const float* ihi = l == 0 ? layer_hi : layer_hi + pl.h[l - 1];
+    for (int i = 0; i < K; ++i) {
+      accc.assign(N, 0.0f); accr.assign(N, 0.0f);
+      for (int b = 0; b < batch; ++b) {
+        const float lo = ilo[(size_t)b * K + i], hi = ihi[(size_t)b * K + i];
+        const float c = 0.5f * (lo + hi), r = 0.5f * (hi - lo);
+        for (int j = 0; j < N; ++j) {
+          accc[j] = std::fmaf(c, gc[(size_t)b * N + j], accc[j]);
+          accr[j] = std::fmaf(r, gr[(size_t)b * N + j], accr[j]);
+        }
+      }
+      for (int j = 0; j < N; ++j) {
+        const size_t at = (size_t)i * N + j;
+        const float w = W[at];
+        const float sg = w > 0.0f ? 1.0f : (w < 0.0f ? -1.0f : 0.0f);
+        float* out = grads + sh.offW[l] + at;
+        *out = bg_mix(*out, accc[j] + sg * accr[j], scale_old, scale_new);
+      }
+    }
+    if (l == 0) break;
+    // back: the gradient into the box of layer l - 1, through its gates
+    bnp(l - 1, g, be, mm, mv);
+    for (int b = 0; b < batch; ++b) {
+      accc.assign(K, 0.0f); accr.assign(K, 0.0f);
+      for (int j = 0; j < N; ++j) {
+        const float vc = gc[(size_t)b * N + j], vr = gr[(size_t)b * N + j];
+        for (int i = 0; i < K; ++i) {
+          const float w = W[(size_t)i * N + j];
+          accc[i] = std::fmaf(vc, w, accc[i]);
+          accr[i] = std::fmaf(vr, std::fabs(w), accr[i]);
+        }
+      }
+      for (int i = 0; i < K; ++i) {
+        const size_t at = (size_t)b * K + i;
+        const double c = accc[i], r = accr[i];
+        float vs, vt;
+        bg_gate(0.5 * (c - r), 0.5 * (c + r), bd_aff(g, be, mm, mv, i).s, layer_lo[pl.z[l - 1] + at], layer_hi[pl.z[l - 1] + at],
+                ws[pl.offG[cur ^ 1][0] + at], ws[pl.offG[cur ^ 1][1] + at], vs, vt);
+        if (g) { ws[pl.offE[cur ^ 1][0] + at] = vs; ws[pl.offE[cur ^ 1][1] + at] = vt; }
+      }
+    }
+    cur ^= 1;
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------------- checks
+static int bg_check(const char* fn, const BdShape& sh, const BgPlan& pl, const float* params, const float* bnstate, const float* margin,
+                    const float* layer_lo, const float* layer_hi, const int* y, int batch, const float* ws, size_t ws_floats,
+                    const float* grads, const float* loss_rows) {
+  LP_CHECK_ARG(params && margin && layer_lo && layer_hi && y && ws && grads && loss_rows, "%s: null argument", fn);
+  LP_CHECK_ARG(sh.n_state == 0 || bnstate, "%s: bnstate is null", fn);
+  LP_CHECK_ARG(ws_floats >= pl.total, "%s: workspace of %zu floats; %zu are needed", fn, ws_floats, pl.total);
+  const size_t B = batch, C = sh.n[sh.L];
+  struct Span { const void* p; size_t bytes; bool written; };
+  const Span sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {margin, B * C * 4, false},
+                     {layer_lo, pl.fam * 4, false}, {layer_hi, pl.fam * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true},
+                     {grads, sh.n_params * 4, true}, {loss_rows, B * 4, true}};
+  const int ns = sizeof(sp) / sizeof(sp[0]);
+  for (int i = 0; i < ns; ++i)
+    for (int j = i + 1; j < ns; ++j)
+      LP_CHECK_ARG(!((sp[i].written || sp[j].written) && sp[i].p && sp[j].p && spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes)),
+                   "%s: an output or the workspace overlaps another argument", fn);
+  return LIPASR_OK;
+}
+
+static int bg_batch_check(const char* fn, const BdShape& sh, int batch) {
+  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  return LIPASR_OK;
+}
+
+}  // namespace lipasr
+
+using namespace lipasr;
+
+extern "C" {
+
+long lipasr_debug_bounds_grad_launches(int kernel) { return (kernel >= 0 && kernel < 4) ? g_bounds_grad_launches[kernel] : -1; }
+
+int lipasr_mlp_bounds_grad_workspace(lipasr_mlp_t m, int batch, size_t* floats) {
+  const char* fn = "lipasr_mlp_bounds_grad_workspace";
+  BdShape sh;
+  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
+  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
+  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
+  *floats = bg_plan(sh, batch).total;
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_bounds_grad_workspace_host(int n_layers, const int* widths, int batch, size_t* floats) {
+  const char* fn = "lipasr_mlp_bounds_grad_workspace_host";
+  BdShape sh;
+  if (int rc = bd_shape_from(fn, n_layers, widths, nullptr, &sh)) return rc;
+  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
+  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
+  *floats = bg_plan(sh, batch).total;
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_bounds_grad(lipasr_mlp_t m, const float* params, const float* bnstate, const float* margin_ibp, const float* layer_lo,
+                           const float* layer_hi, const int* y, int batch, float* workspace, size_t workspace_floats, float scale_old,
+                           float scale_new, float* grads, float* loss_rows, lipasr_stream_t stream) {
+  const char* fn = "lipasr_mlp_bounds_grad";
+  BdShape sh;
+  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
+  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
+  const BgPlan pl = bg_plan(sh, batch);
+  if (int rc = bg_check(fn, sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, workspace, workspace_floats, grads, loss_rows))
+    return rc;
+  DeviceGuard guard(m->ctx->device);
+  hipStream_t st = S(stream);
+  float* ws = bd_base(workspace);
+  const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
+  const bool hidden = L > 1;
+  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
+    g = be = mm = mv = nullptr;
+    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
+  };
+  const float *g = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
+  float* coef = ws + pl.offCoef;
+  float* ty = ws + pl.offTy;
+  const float* WL = params + sh.offW[L - 1];
+  const float* hlo = hidden ? layer_lo + pl.h[L - 2] : layer_lo;
+  const float* hhi = hidden ? layer_hi + pl.h[L - 2] : layer_hi;
+  int cur = 0;
+  if (hidden) bnp(L - 2, g, be, mm, mv);
+  hipLaunchKernelGGL(bg_head_kernel, dim3(batch), dim3(kBdThreads), 0, st, margin_ibp, y, WL, C, nh, hlo, hhi, hidden ? 1 : 0, g, be, mm, mv,
+                     hidden ? layer_lo + pl.z[L - 2] : nullptr, hidden ? layer_hi + pl.z[L - 2] : nullptr, loss_rows, coef, ty,
+                     ws + pl.offG[cur][0], ws + pl.offG[cur][1], ws + pl.offE[cur][0], ws + pl.offE[cur][1]);
+  LP_LAUNCH_CHECK();
+  ++g_bounds_grad_launches[BG_HEAD];
+  hipLaunchKernelGGL(bg_head_dw_kernel, dim3((nh * C + C + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, WL, y, coef, ty, hlo, hhi, batch, C, nh,
+                     scale_old, scale_new, grads + sh.offW[L - 1], grads + sh.offb[L - 1]);
+  LP_LAUNCH_CHECK();
+  ++g_bounds_grad_launches[BG_HEAD];
+  for (int l = L - 2; l >= 0; --l) {
+    const int K = sh.n[l], N = sh.n[l + 1];
+    const float* gc = ws + pl.offG[cur][0];
+    const float* gr = ws + pl.offG[cur][1];
+    bnp(l, g, be, mm, mv);
+    hipLaunchKernelGGL(bg_colsum_kernel, dim3((N + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, gc, ws + pl.offE[cur][0], ws + pl.offE[cur][1], mm, mv,
+                       batch, N, scale_old, scale_new, grads + sh.offb[l], g ? grads + sh.offg[l] : nullptr,
+                       g ? grads + sh.offbe[l] : nullptr);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_grad_launches[BG_COLSUM];
+    hipLaunchKernelGGL(bg_wgrad_kernel, dim3((K + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, l == 0 ? layer_lo : layer_lo + pl.h[l - 1],
+                       l == 0 ? layer_hi : layer_hi + pl.h[l - 1], gc, gr, params + sh.offW[l], batch, K, N, scale_old, scale_new,
+                       grads + sh.offW[l]);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_grad_launches[BG_WGRAD];
+    if (l == 0) break;
+    bnp(l - 1, g, be, mm, mv);
+    hipLaunchKernelGGL(bg_back_kernel, dim3((batch + 31) / 32, (K + 127) / 128), dim3(kBdThreads), 0, st, gc, gr, params + sh.offW[l], batch, N,
+                       K, g, be, mm, mv, layer_lo + pl.z[l - 1], layer_hi + pl.z[l - 1], ws + pl.offG[cur ^ 1][0], ws + pl.offG[cur ^ 1][1],
+                       ws + pl.offE[cur ^ 1][0], ws + pl.offE[cur ^ 1][1]);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_grad_launches[BG_BACK];
+    cur ^= 1;
+  }
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_bounds_grad_host(int n_layers, const int* widths, const int* bn, const float* params, const float* bnstate,
+                                const float* margin_ibp, const float* layer_lo, const float* layer_hi, const int* y, int batch,
+                                float* workspace, size_t workspace_floats, float scale_old, float scale_new, float* grads,
+                                float* loss_rows) {
+  const char* fn = "lipasr_mlp_bounds_grad_host";
+  BdShape sh;
+  if (int rc = bd_shape_from(fn, n_layers, widths, bn, &sh)) return rc;
+  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
+  const BgPlan pl = bg_plan(sh, batch);
+  if (int rc = bg_check(fn, sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, workspace, workspace_floats, grads, loss_rows))
+    return rc;
+  bg_host(sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, bd_base(workspace), scale_old, scale_new, grads, loss_rows);
+  return LIPASR_OK;
+}
+
+}  // extern "C"

@@ -150,6 +150,11 @@ PROTOTYPES = {
     "lipasr_mlp_bounds_workspace_host": (i32, [i32, PI, i32, C.POINTER(sz)]),
     "lipasr_mlp_bounds_host": (i32, [i32, PI, PI, c_f, c_f, c_f, c_f, f32, f32, f32, c_f, i32, c_f, sz, c_f, c_f, c_f, c_f, c_f]),
     "lipasr_debug_bounds_launches": (C.c_long, [i32]),
+    "lipasr_mlp_bounds_grad_workspace": (i32, [c_h, i32, C.POINTER(sz)]),
+    "lipasr_mlp_bounds_grad": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, sz, f32, f32, c_f, c_f, c_s]),
+    "lipasr_mlp_bounds_grad_workspace_host": (i32, [i32, PI, i32, C.POINTER(sz)]),
+    "lipasr_mlp_bounds_grad_host": (i32, [i32, PI, PI, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, sz, f32, f32, c_f, c_f]),
+    "lipasr_debug_bounds_grad_launches": (C.c_long, [i32]),
     "lipasr_warp_table_host": (i32, [c_f, c_f]),
     "lipasr_warp_apply": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
     "lipasr_warp_param_vjp": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
@@ -247,7 +252,9 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_mlp_bounds_workspace_host": 710, "lipasr_mlp_bounds_host": 710, "lipasr_debug_bounds_launches": 710, "lipasr_warp_table_host": 720,
          "lipasr_warp_apply": 720, "lipasr_warp_param_vjp": 720, "lipasr_warp_apply_host": 720, "lipasr_warp_param_vjp_host": 720,
          "lipasr_debug_warp_launches": 720, "lipasr_debug_k2_launches": 730, "lipasr_debug_mlp_stage": 730, "lipasr_defence_apply": 740,
-         "lipasr_defence_vjp": 740, "lipasr_defence_apply_host": 740, "lipasr_defence_vjp_host": 740, "lipasr_debug_defence_launches": 740}
+         "lipasr_defence_vjp": 740, "lipasr_defence_apply_host": 740, "lipasr_defence_vjp_host": 740, "lipasr_debug_defence_launches": 740,
+         "lipasr_mlp_bounds_grad_workspace": 750, "lipasr_mlp_bounds_grad": 750, "lipasr_mlp_bounds_grad_workspace_host": 750,
+         "lipasr_mlp_bounds_grad_host": 750, "lipasr_debug_bounds_grad_launches": 750}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -880,6 +887,11 @@ def bounds_layout(widths, bn=None):
     return out, po, so
 
 
+def bounds_family_floats(widths, batch):
+    """Floats of layer_lo (or layer_hi) of lipasr_mlp_bounds: the input box and (z_l, h_l) of every hidden layer, [batch][n] each."""
+    return int(batch) * (int(widths[0]) + 2 * sum(int(n) for n in widths[1:-1]))
+
+
 def bounds_split_layers(flat, widths, batch):
     """layer_lo or layer_hi of lipasr_mlp_bounds as (input box [B, n_0], [(z_l, h_l) for the hidden layers])."""
     b, o = int(batch), 0
@@ -915,11 +927,49 @@ def mlp_bounds_host(widths, bn, params, bnstate, x, eps, norm, y, *, clip_lo=-fl
     ws = np.zeros(need.value + 8, dtype=np.float32)
     skip = (-(ws.ctypes.data // 4)) % 4 + int(ws_offset)
     wsv = ws[skip:skip + need.value]
-    fam = b * (widths[0] + 2 * sum(widths[1:-1]))
+    fam = bounds_family_floats(widths, b)
     c = widths[-1]
     out = {"margin_ibp": np.zeros((b, c), np.float32), "margin_crown": np.zeros((b, c), np.float32) if crown else None,
            "slack": np.zeros((b, c), np.float32) if crown else None, "lo": np.zeros(fam, np.float32), "hi": np.zeros(fam, np.float32)}
     check(lib.lipasr_mlp_bounds_host(L, wa, ba, _vp(params), _vp(bnstate), _vp(x), _vp(eps), _norm_f(norm), float(clip_lo), float(clip_hi),
                                      _vp(y), b, _vp(wsv), need.value, _vp(out["margin_ibp"]), _vp(out["margin_crown"]), _vp(out["slack"]),
                                      _vp(out["lo"]), _vp(out["hi"])))
+    return out
+
+
+BOUNDS_GRAD_KERNELS = ("head", "wgrad", "back", "colsum")  # ids of lipasr_debug_bounds_grad_launches
+
+
+def bounds_grad_launches(n_layers):
+    """Launches of one lipasr_mlp_bounds_grad call per id of BOUNDS_GRAD_KERNELS, for a model of n_layers Dense layers."""
+    h = int(n_layers) - 1
+    return {"head": 2, "wgrad": h, "back": max(h - 1, 0), "colsum": h}
+
+
+def mlp_bounds_grad_host(widths, bn, params, bnstate, margin_ibp, lo, hi, y, *, scale_old=0.0, scale_new=1.0, grads=None, ws_offset=0):
+    """Host-only: lipasr_mlp_bounds_grad_host on NumPy arrays (margin_ibp, lo, hi as mlp_bounds_host returned them) ->
+    dict(grads [n_params], loss_rows [B]).  grads: the buffer that scale_old applies to (default zeros); it is not changed.
+    ws_offset: floats the workspace starts past a 16-byte boundary."""
+    import numpy as np
+
+    widths = [int(w) for w in widths]
+    L = len(widths) - 1
+    margin_ibp = np.ascontiguousarray(margin_ibp, dtype=np.float32)
+    b = margin_ibp.shape[0]
+    params = np.ascontiguousarray(params, dtype=np.float32)
+    bnstate = None if bnstate is None else np.ascontiguousarray(bnstate, dtype=np.float32)
+    fam = bounds_family_floats(widths, b)
+    lo = _host_in(lo, np.float32, (fam,), "lo")
+    hi = _host_in(hi, np.float32, (fam,), "hi")
+    y = _host_in(y, np.int32, (b,), "y")
+    wa, ba = int_array(widths), (None if bn is None else int_array(bn))
+    need = sz()
+    check(lib.lipasr_mlp_bounds_grad_workspace_host(L, wa, b, C.byref(need)))
+    ws = np.zeros(need.value + 8, dtype=np.float32)
+    skip = (-(ws.ctypes.data // 4)) % 4 + int(ws_offset)
+    wsv = ws[skip:skip + need.value]
+    out = {"grads": np.zeros(params.size, np.float32) if grads is None else np.array(grads, dtype=np.float32, copy=True),
+           "loss_rows": np.zeros(b, np.float32)}
+    check(lib.lipasr_mlp_bounds_grad_host(L, wa, ba, _vp(params), _vp(bnstate), _vp(margin_ibp), _vp(lo), _vp(hi), _vp(y), b, _vp(wsv),
+                                          need.value, float(scale_old), float(scale_new), _vp(out["grads"]), _vp(out["loss_rows"])))
     return out

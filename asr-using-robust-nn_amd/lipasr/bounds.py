@@ -19,8 +19,87 @@ import torch
 
 from . import _native as N
 from . import estimators as E
+from .keras import CategoricalCrossentropy
 
 METHODS = ("crown-ibp", "ibp")
+
+
+class IBPCrossentropy(CategoricalCrossentropy):
+    """IBP certified training (Gowal et al. 2018) as a loss for ``Model.compile``:
+
+        loss = (1 - kappa_t) CE(logits(x), y) + kappa_t CE(worst-case logits over the eps_t-box around x, y)
+
+    The worst-case logits are the interval bounds of lipasr_mlp_bounds (norm inf, the classifier in inference form: running
+    BatchNorm statistics, dropout off), their gradient is lipasr_mlp_bounds_grad ("Certified training").  For
+    ``warmup_steps`` steps the loss is plain cross-entropy; over the next ``ramp_steps`` steps eps_t and kappa_t rise linearly from
+    0 to ``eps`` and ``kappa`` and stay there.  The step counter lives here, on the host: one count per ``train_on_batch``.
+    ``clip_values``: the box the inputs live in (default none), as an estimator's.  ``evaluate`` and ``save`` of the model stay on
+    plain cross-entropy; ``fit`` logs the mixed loss.  Not built: norm 2, data parallel, TrainPipeline."""
+
+    name = "ibp_categorical_crossentropy"
+    certified = True  # Model.train_on_batch hands the step to train_step below
+
+    def __init__(self, eps, kappa=0.5, warmup_steps=0, ramp_steps=1, clip_values=None, norm=float("inf")):
+        if N._norm_f(norm) != float("inf"):
+            raise ValueError(f"norm = {norm!r}: IBP certified training is built for norm inf; norm 2 (the column-norm branch of the "
+                             "first layer) is not built")
+        if not float(eps) >= 0 or not np.isfinite(eps):
+            raise ValueError(f"eps = {eps!r}: a finite number >= 0")
+        if not 0.0 <= float(kappa) <= 1.0:
+            raise ValueError(f"kappa = {kappa!r}: in [0, 1]")
+        if int(warmup_steps) < 0 or int(ramp_steps) < 1:
+            raise ValueError(f"warmup_steps = {warmup_steps!r}, ramp_steps = {ramp_steps!r}: >= 0 and >= 1")
+        self.clip = (-float("inf"), float("inf")) if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        if not self.clip[0] <= self.clip[1]:
+            raise ValueError(f"clip_values = {clip_values!r}: low <= high")
+        self.eps, self.kappa = float(eps), float(kappa)
+        self.warmup_steps, self.ramp_steps = int(warmup_steps), int(ramp_steps)
+        self.step = 0
+
+    def schedule(self, step):
+        """(eps_t, kappa_t) of the ``step``-th call of train_on_batch, counted from 0."""
+        f = min(max((int(step) - self.warmup_steps) / self.ramp_steps, 0.0), 1.0)
+        return self.eps * f, self.kappa * f
+
+    def _buffers(self, model):
+        """The device floats of one certified step, once per model at its max_batch."""
+        buf = getattr(model, "_ibp_buffers", None)
+        if buf is None:
+            b, w, dev = model._max_batch, model._widths, model._device
+            need, need_g = N.sz(), N.sz()
+            N.check(N.lib.lipasr_mlp_bounds_workspace(model._plan, b, N.C.byref(need)))
+            N.check(N.lib.lipasr_mlp_bounds_grad_workspace(model._plan, b, N.C.byref(need_g)))
+            fam = N.bounds_family_floats(w, b)
+            f = lambda n: torch.zeros(n, device=dev)
+            buf = {"ws": f(need.value), "ws_grad": f(need_g.value), "lo": f(fam), "hi": f(fam), "margin": f(b * w[-1]), "eps": f(b),
+                   "rows": f(b)}
+            model._ibp_buffers = buf
+        return buf
+
+    def train_step(self, model, xb, yb, masks=None, dropout=True):
+        """One step of ``model`` under this loss; False when kappa_t is 0 (the caller then makes the plain step's calls).
+        Otherwise: the plain forward and backward pass scaled by 1 - kappa_t, the interval bounds at eps_t on the same parameters,
+        their gradient mixed in at kappa_t / batch, Adam.  Stream-ordered; nothing synchronises."""
+        eps_t, kappa_t = self.schedule(self.step)
+        self.step += 1
+        if kappa_t == 0.0:
+            return False
+        b = xb.shape[0]
+        buf = self._buffers(model)
+        model.train_fwd_bwd(xb, yb, inv_batch=(1.0 - kappa_t) / b, masks=masks, dropout=dropout)
+        yt = yb.argmax(dim=1).to(torch.int32)
+        buf["eps"][:b].fill_(eps_t)
+        args = (model._plan, N.ptr(model._params), N.ptr(model._bnstate))
+        N.check(N.lib.lipasr_mlp_bounds(*args, N.ptr(xb), N.ptr(buf["eps"]), float("inf"), self.clip[0], self.clip[1], N.ptr(yt), b,
+                                        N.ptr(buf["ws"]), buf["ws"].numel(), N.ptr(buf["margin"]), None, None, N.ptr(buf["lo"]),
+                                        N.ptr(buf["hi"]), N.stream_ptr()))
+        N.check(N.lib.lipasr_mlp_bounds_grad(*args, N.ptr(buf["margin"]), N.ptr(buf["lo"]), N.ptr(buf["hi"]), N.ptr(yt), b,
+                                             N.ptr(buf["ws_grad"]), buf["ws_grad"].numel(), 1.0, kappa_t / b, N.ptr(model._grads),
+                                             N.ptr(buf["rows"]), N.stream_ptr()))
+        rows = model._loss_rows[:b]
+        rows.mul_(1.0 - kappa_t).add_(buf["rows"][:b], alpha=kappa_t)  # what fit() logs
+        model.apply_adam()
+        return True
 
 
 def _check(estimator, norm, method):
@@ -91,7 +170,7 @@ def _margins(estimator, xt, et, yt, norm, clip, method, ws, details=False):
     slack = torch.empty(b, c, device=xt.device) if (details and crown is not None) else None
     lo = hi = None
     if details:
-        fam = m._widths[0] + 2 * sum(m._widths[1:-1])
+        fam = N.bounds_family_floats(m._widths, 1)
         lo, hi = torch.empty(b * fam, device=xt.device), torch.empty(b * fam, device=xt.device)
     bs = estimator.batch_limit
     o = 0

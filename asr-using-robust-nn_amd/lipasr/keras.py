@@ -65,6 +65,9 @@ class CategoricalCrossentropy:
     """Marker for the only loss the path uses (train_constraints.py:94); computed from logits in softmax_ce_kernel."""
 
     name = "categorical_crossentropy"
+    # True on a subclass that owns the training step: Model.train_on_batch then calls its
+    # ``train_step(model, xb, yb, masks=, dropout=) -> bool`` (lipasr.bounds.IBPCrossentropy; this module cannot import it)
+    certified = False
 
 
 class _Node:
@@ -470,6 +473,9 @@ class Model:
         if loss is not None and not (isinstance(loss, CategoricalCrossentropy) or loss == "categorical_crossentropy"):
             raise NotImplementedError("only categorical cross-entropy is implemented")
         self._adam = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
+        # kept for train_on_batch: a lipasr.bounds.IBPCrossentropy turns the step into a certified one.  evaluate() and save()
+        # stay on plain cross-entropy: a reloaded model is compiled with the plain loss
+        self._loss = loss
         self._metrics = list(metrics or [])
         self._compiled = True
 
@@ -586,7 +592,15 @@ class Model:
                                                       len(order), N.ptr(norms_out), N.stream_ptr()))
 
     def train_on_batch(self, xb, yb, masks=None, dropout=True):
-        """fwd, bwd, (data-parallel gradient all-reduce), Adam + NonNeg; returns nothing (stream-ordered)."""
+        """fwd, bwd, (data-parallel gradient all-reduce), Adam + NonNeg; returns nothing (stream-ordered).  Compiled with a
+        lipasr.bounds.IBPCrossentropy, the step is a certified one as soon as the loss's schedule gives kappa_t > 0."""
+        ibp = getattr(self, "_loss", None)
+        if getattr(ibp, "certified", False):
+            if self._dp is not None:
+                raise NotImplementedError("IBP certified training (lipasr.bounds.IBPCrossentropy) is not built for a model under "
+                                          "DataParallel")
+            if ibp.train_step(self, xb, yb, masks=masks, dropout=dropout):
+                return
         if self._dp is not None:
             self._dp.train_step(self, xb, yb, masks=masks, dropout=dropout)
             return

@@ -59,6 +59,7 @@ class TrainPipeline:
         were just produced on the caller's stream or are temporaries; a loop over a resident pool that was filled and
         synchronised beforehand (bench.py) may pass False."""
         self.sync_inputs = bool(sync_inputs)
+        self._refuse_certified(model)
         if pgd:
             self._pgd_norm = _norm_value(pgd.get("norm", float("inf")))
             rinit = int(pgd.get("num_random_init", 0))
@@ -330,6 +331,13 @@ class TrainPipeline:
         used[-1][1].synchronize()
         return sum(a.elapsed_time(b) for a, b in used) / len(used)
 
+    @staticmethod
+    def _refuse_certified(model):
+        """Asked when the pipeline is built and again at every step: the model may be compiled anew in between."""
+        if getattr(getattr(model, "_loss", None), "certified", False):
+            raise NotImplementedError("TrainPipeline does not run IBP certified training (lipasr.bounds.IBPCrossentropy): its step "
+                                      "plans hold the plain step only; train with Model.fit / Model.train_on_batch")
+
     def step(self, waves, y_onehot, features=None, global_batch=None):
         """waves: float32 device tensor [b, n_samp] (a view into a resident pool is fine), y_onehot [b, classes].
         features: pre-extracted, already standardised [b, 20*L] features instead of waveforms (BASELINE config 2,
@@ -337,6 +345,7 @@ class TrainPipeline:
         global_batch: data parallel with UNEVEN shards only (e.g. the last partial batch cut by ``shard_bounds``): the
         number of rows all ranks process in this step; default = this rank's rows x world size.
         Asynchronous: ``pipe.feats`` / ``pipe.labels`` / the model's buffers are valid after ``synchronize()``."""
+        self._refuse_certified(self.model)
         bsz = (features if features is not None else waves).shape[0]
         gb = int(global_batch) if global_batch is not None else bsz * self.dp.world
         b = self._i % self._nbuf

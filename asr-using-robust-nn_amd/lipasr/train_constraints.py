@@ -103,8 +103,32 @@ def load_processed_dataset(path="processed_google_dataset/"):
     return (ld("train_data"), ld("train_label")), (ld("dev_data"), ld("dev_label")), (ld("test_data"), ld("test_label"))
 
 
+def add_certified_arguments(ap):
+    """The flags of IBP certified training (lipasr.bounds.IBPCrossentropy); without --certified-eps training is unchanged."""
+    ap.add_argument("--certified-eps", type=float, default=None, help="train on the interval bounds at this norm-inf radius "
+                                                                        "(of the standardised features); default: off")
+    ap.add_argument("--certified-kappa", type=float, default=0.5, help="final weight of the robust cross-entropy")
+    ap.add_argument("--certified-warmup", type=int, default=0, help="steps of plain training before the ramp")
+    ap.add_argument("--certified-ramp", type=int, default=1, help="steps over which eps and kappa rise from 0")
+    return ap
+
+
+def certified_arguments(argv):
+    return add_certified_arguments(argparse.ArgumentParser(add_help=False)).parse_known_args(argv)[0]
+
+
+def certified_loss(args):
+    """The IBPCrossentropy the flags ask for, or None."""
+    if args.certified_eps is None:
+        return None
+    from .bounds import IBPCrossentropy
+
+    return IBPCrossentropy(args.certified_eps, kappa=args.certified_kappa, warmup_steps=args.certified_warmup,
+                           ramp_steps=args.certified_ramp)
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser()
+    ap = add_certified_arguments(argparse.ArgumentParser())
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--rho", type=float, default=0.1)
     ap.add_argument("--small", action="store_true", help="2048/512/512 clips instead of the reference's split sizes")
@@ -123,7 +147,7 @@ def main(argv=None):
     val_dataset = Dataset.from_tensor_slices((val_data, val_label)).shuffle(880, reshuffle_each_iteration=False).batch(512)
 
     model = get_model()
-    model.compile(optimizer="adam", loss=CategoricalCrossentropy(), metrics=["accuracy"])
+    model.compile(optimizer="adam", loss=certified_loss(args) or CategoricalCrossentropy(), metrics=["accuracy"])
     print(model.summary())
     model.fit(train_dataset, epochs=args.epochs, validation_data=val_dataset, verbose=2,
               callbacks=[EarlyStopping(monitor="val_loss", patience=6000, restore_best_weights=False),

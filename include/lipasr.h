@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 740. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 750. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -59,6 +59,8 @@
  * 740: input-transformation defences over audio: lipasr_defence_apply (a chain of median, FIR and bit-depth stages in one launch),
  * lipasr_defence_vjp (the chain's vector-Jacobian product in one launch), their _host twins and the test hook
  * lipasr_debug_defence_launches.
+ * 750: IBP certified training: lipasr_mlp_bounds_grad (the backward pass of the interval bounds with respect to the parameters),
+ * lipasr_mlp_bounds_grad_workspace, their _host twins and the test hook lipasr_debug_bounds_grad_launches.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -908,6 +910,43 @@ int lipasr_mlp_bounds_host(int n_layers, const int* widths, const int* bn, const
 /* Test hook: launches since the library was loaded of 0 bounds_prep_kernel, 1 bounds_layer_kernel, 2 bounds_head_kernel,
  * 3 bounds_back_kernel, 4 bounds_tail_kernel, counted on the host where the launch happens; -1 for an unknown id. */
 long lipasr_debug_bounds_launches(int kernel);
+
+/* IBP certified training (Gowal et al. 2018; lipasr.bounds.IBPCrossentropy): the backward pass of the interval bounds with respect
+ * to the parameters.  From what ONE lipasr_mlp_bounds call under norm +INFINITY wrote for (params, bnstate, y, batch) --
+ * margin_ibp and the boxes layer_lo / layer_hi -- per row b
+ *     u[b][k] = -margin_ibp[b][k] (k != y_b),  u[b][y_b] = 0,   loss_rows[b] = logsumexp_k u[b][k]
+ * (the cross-entropy of the worst-case logits, the last layer elided into the difference rows as lipasr_mlp_bounds does) and
+ *     grads = scale_old * grads + scale_new * d( sum_b loss_rows[b] ) / d params          (scale_old == 0: the old contents of grads are ignored)
+ * over W, b, gamma and beta of every layer in lipasr_mlp_create's flat layout; the pad floats are not touched.  The running
+ * BatchNorm statistics are constants, dropout is off.  Derivative conventions (torch's): relu'(0) = 0; d|w|/dw = 0 at 0; s >= 0
+ * takes the branch that does not swap lo and hi; the difference W_L[j][y] - W_L[j][k] selects lo where it is > 0 and hi otherwise;
+ * the widening and the outward roundings of the forward pass are constants; the input box carries no gradient.  Per hidden layer,
+ * with c = (lo + hi) / 2 and r = (hi - lo) / 2 of its input box, gc = g_zlo + g_zhi, gr = g_zhi - g_zlo:
+ *     dW[i][j] = sum_b c[b][i] gc[b][j] + sign(W[i][j]) sum_b r[b][i] gr[b][j],   db[j] = sum_b gc[b][j],
+ *     g_lo, g_hi = (gc W^T -+ gr |W|^T) / 2, then through h = s relu(z) + t with the gates z_lo > 0 / z_hi > 0.
+ * A row whose margins are NaN, or whose y_b is outside [0, classes), makes loss_rows[b] and the whole gradient NaN.
+ *   workspace: device floats, any 4-byte alignment, lipasr_mlp_bounds_grad_workspace(m, batch) of them; nothing is kept between calls.
+ *   LIPASR_EINVAL for a null argument, a workspace that is too small, grads / loss_rows / the workspace overlapping anything,
+ *   widths > 4096, classes > 32 or batch * classes > 2^24.
+ * Launches: 2 for one layer, else 3 (L - 1) + 1 -- bg_head_kernel, bg_head_dw_kernel (dW_L, db_L), and per hidden layer
+ * bg_colsum_kernel (db, dgamma, dbeta), bg_wgrad_kernel (dW on v_mfma_f32_32x32x2_f32, both scales in its epilogue) and, above the
+ * first, bg_back_kernel (W and |W| from one read, the gates of the layer below in its epilogue).  Every sum runs in one order that
+ * the shapes fix (no atomics): two calls give the same bits.  Nothing allocates or synchronises. */
+int lipasr_mlp_bounds_grad_workspace(lipasr_mlp_t m, int batch, size_t* floats);
+int lipasr_mlp_bounds_grad(lipasr_mlp_t m, const float* params, const float* bnstate, const float* margin_ibp /* [batch][classes] */,
+                           const float* layer_lo, const float* layer_hi, const int* y /* [batch] */, int batch, float* workspace,
+                           size_t workspace_floats, float scale_old, float scale_new, float* grads, float* loss_rows /* [batch] */,
+                           lipasr_stream_t stream);
+/* Host-only twins on widths and BatchNorm flags, as lipasr_mlp_bounds_host: the same inline functions in plain loops and in the
+ * same orders, the same checks, the same values as the device entry point (a zero may differ in sign). */
+int lipasr_mlp_bounds_grad_workspace_host(int n_layers, const int* widths, int batch, size_t* floats);
+int lipasr_mlp_bounds_grad_host(int n_layers, const int* widths, const int* bn, const float* params, const float* bnstate,
+                                const float* margin_ibp, const float* layer_lo, const float* layer_hi, const int* y, int batch,
+                                float* workspace, size_t workspace_floats, float scale_old, float scale_new, float* grads,
+                                float* loss_rows);
+/* Test hook: launches since the library was loaded of 0 the two head kernels, 1 bg_wgrad_kernel, 2 bg_back_kernel,
+ * 3 bg_colsum_kernel, counted on the host where the launch happens; -1 for an unknown id. */
+long lipasr_debug_bounds_grad_launches(int kernel);
 
 /* The time-warp operator (lipasr/warp.py, attacks.TimeWarp; ours -- ART's SpatialTransformation is the image form): every clip
  * resampled under K triples (shift in samples, rate, linear gain) by band-limited interpolation, in one launch.  x is [clips][n];
