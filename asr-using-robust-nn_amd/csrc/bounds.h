@@ -1,5 +1,7 @@
-// What bounds.hip (the interval and CROWN-IBP bounds) and bounds_grad.hip (the backward pass of the interval bounds) share: the
-// classifier's shape in the flat layout of lipasr_mlp_create, the inference-mode BatchNorm affine, the workspace alignment.
+// What bounds.hip (the interval and CROWN-IBP bounds), bounds_grad.hip (the backward pass of the interval bounds) and
+// bounds_crown_grad.hip (the backward pass of the relaxation) share: the classifier's shape in the flat layout of lipasr_mlp_create,
+// the inference-mode BatchNorm affine, the slope of a ReLU line, the workspace alignment, and the two launch sequences that
+// bounds_crown_grad.hip borrows.
 #pragma once
 #include "common.h"
 #include "row.h"
@@ -12,7 +14,27 @@ typedef float bd_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kBdMaxWidth = 4096;                  // (width + 2) 2^-53 <= kBdD / 2 and gamma_{width + 1} << 1
 constexpr int kBdThreads = 256;
 
+constexpr double kBdU = 5.9604644775390625e-08;    // 2^-24, the unit roundoff of fp32
+constexpr double kBdTiny = 1.401298464324817e-45;  // 2^-149, the smallest fp32 subnormal
+constexpr double kBdD = 9.094947017729282e-13;     // 2^-40: covers every fp64 rounding of a sum of <= 4096 + 2 terms
+
 #define BD_HD __host__ __device__ __forceinline__
+
+BD_HD double bd_max(double a, double b) { return a < b ? b : a; }
+
+// the slope of the line that relaxes relu on [zlo, zhi] for a coefficient p on its output; upper: the line is the upper one of an
+// unstable neuron (p < 0), the only one whose slope moves with the box and that has an intercept
+BD_HD double bd_slope(double p, float zlo, float zhi, bool& upper) {
+  upper = false;
+  if (zhi <= 0.0f) return 0.0;
+  if (zlo >= 0.0f) return 1.0;
+  if (p < 0.0) {
+    // any slope >= hi / (hi - lo) lies above relu on [lo, hi]
+    upper = true;
+    return (double)zhi / ((double)zhi - (double)zlo) * (1.0 + kBdD);
+  }
+  return zhi >= -zlo ? 1.0 : 0.0;
+}
 
 // h = s relu(z) + t in inference mode; tm bounds the magnitudes t was made of
 struct BdAff { double s, t, tm; };
@@ -55,5 +77,25 @@ inline float* bd_base(float* ws) { return reinterpret_cast<float*>((reinterpret_
 // the shape from widths and BatchNorm flags (the host twins) / from a classifier plan; both refuse what the kernels do not take
 int bd_shape_from(const char* fn, int n_layers, const int* widths, const int* bn, BdShape* sh);
 int bd_shape_of(const char* fn, lipasr_mlp_t m, BdShape* sh);
+
+// bounds.hip: out[m][i] = sum_j A[m][j] W[i][j] on the tile of bounds_back_kernel, without its relaxation epilogue
+int bd_launch_product(hipStream_t st, const float* A, const float* W, int M, int K, int N, int C, float* out);
+
+// bounds_grad.hip: the sweep of lipasr_mlp_bounds_grad and of its host twin.  mix = null: exactly that call.  Otherwise the margins
+// are (1 - beta) margin + beta margin2, the head's cotangent is weighted by 1 - beta, and inj_lo / inj_hi (laid out as layer_lo /
+// layer_hi are; only the z boxes are read) are added to the gradient on every pre-activation box before it goes down.
+struct BgMixIn {
+  const float* margin2;
+  float beta;
+  const float* inj_lo;
+  const float* inj_hi;
+};
+size_t bg_workspace_floats(const BdShape& sh, int batch);
+int bg_run_device(const BdShape& sh, hipStream_t st, const float* params, const float* bnstate, const float* margin, const float* layer_lo,
+                  const float* layer_hi, const int* y, int batch, float* ws, float scale_old, float scale_new, float* grads, float* loss_rows,
+                  const BgMixIn* mix);
+void bg_run_host(const BdShape& sh, const float* params, const float* bnstate, const float* margin, const float* layer_lo,
+                 const float* layer_hi, const int* y, int batch, float* ws, float scale_old, float scale_new, float* grads, float* loss_rows,
+                 const BgMixIn* mix);
 
 }  // namespace lipasr

@@ -30,10 +30,6 @@ namespace lipasr {
 long g_bounds_launches[5] = {};
 enum { BD_PREP = 0, BD_LAYER = 1, BD_HEAD = 2, BD_BACK = 3, BD_TAIL = 4 };
 
-constexpr double kBdU = 5.9604644775390625e-08;    // 2^-24, the unit roundoff of fp32
-constexpr double kBdTiny = 1.401298464324817e-45;  // 2^-149, the smallest fp32 subnormal
-constexpr double kBdD = 9.094947017729282e-13;     // 2^-40: covers every fp64 rounding of a sum of <= 4096 + 2 terms
-
 BD_HD unsigned bd_bits(float f) { return __builtin_bit_cast(unsigned, f); }
 BD_HD float bd_float(unsigned u) { return __builtin_bit_cast(float, u); }
 // the next fp32 above / below; a NaN and the infinity on that side stay
@@ -58,7 +54,6 @@ BD_HD float bd_up(double v) {
   const float f = (float)v;
   return (double)f < v ? bd_step_up(f) : f;
 }
-BD_HD double bd_max(double a, double b) { return a < b ? b : a; }
 BD_HD double bd_gamma(int n) { return n * kBdU / (1.0 - n * kBdU); }
 // what an fmaf chain of K products plus the bias can be off by, given S >= sum of the magnitudes: two chains meet in one bound
 BD_HD double bd_widen(int K, double S) { return bd_gamma(K + 1) * S + 2.0 * (K + 1) * kBdTiny; }
@@ -129,18 +124,9 @@ BD_HD void bd_relax(float lam, const BdAff& a, float zlo, float zhi, float S, fl
   const double p = (double)lam * a.s;
   const double ahi = zhi < 0.0f ? 0.0 : (double)zhi;
   const double Z = bd_max(fabs((double)zlo), fabs((double)zhi));
-  double slope, icpt = 0.0;
-  if (zhi <= 0.0f) {
-    slope = 0.0;
-  } else if (zlo >= 0.0f) {
-    slope = 1.0;
-  } else if (p < 0.0) {
-    // the upper line: any slope >= hi / (hi - lo) lies above relu on [lo, hi]
-    slope = (double)zhi / ((double)zhi - (double)zlo) * (1.0 + kBdD);
-    icpt = -(p * slope * (double)zlo) * (1.0 + kBdD);  // <= 0, rounded away from 0
-  } else {
-    slope = zhi >= -zlo ? 1.0 : 0.0;
-  }
+  bool upper;
+  const double slope = bd_slope(p, zlo, zhi, upper);
+  const double icpt = upper ? -(p * slope * (double)zlo) * (1.0 + kBdD) : 0.0;  // <= 0, rounded away from 0
   nu = (float)(p * slope);
   const double lt = (double)lam * a.t, nb = (double)nu * (double)bias;
   dc = lt + icpt + nb;
@@ -493,6 +479,14 @@ __global__ __launch_bounds__(kBdThreads) void bounds_back_kernel(const float* __
       }
     }
   }
+}
+
+// the plain product out = A W^T of bounds_back_kernel (no relaxation, no partials), for the chain that bounds_crown_grad.hip keeps
+int bd_launch_product(hipStream_t st, const float* A, const float* W, int M, int K, int N, int C, float* out) {
+  hipLaunchKernelGGL(bounds_back_kernel, dim3((M + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, A, W, M, K, N, C, 0, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, 0);
+  LP_LAUNCH_CHECK();
+  return LIPASR_OK;
 }
 
 // 32 lanes per row m: the input reduction of Lambda_0, the constants and slacks in their fixed order, the two outputs.

@@ -24,7 +24,10 @@
 // outward roundings of the forward pass are constants; the input box carries no gradient.  A row whose margins are NaN (or whose
 // label is outside [0, classes)) makes its loss and the whole gradient NaN.
 // Loads and stores are single floats, guarded: any width, any batch, any alignment.  Nothing allocates or synchronises.
-#include "bounds.h"
+// bounds_crown_grad.hip runs the same sweep through bg_run_device / bg_run_host with a BgMixIn (bounds.h): the margins mixed with
+// margin_crown, the head weighted by 1 - beta, and a gradient on every z box added in bg_gate.  With a null BgMixIn the extra
+// operands are null and every result is what it was without them.
+#include "bounds_grad.h"
 
 // host and device must round alike
 #pragma clang fp contract(off)
@@ -34,45 +37,11 @@ namespace lipasr {
 long g_bounds_grad_launches[4] = {};
 enum { BG_HEAD = 0, BG_WGRAD = 1, BG_BACK = 2, BG_COLSUM = 3 };
 
-// a column sum over the batch: a block takes kBgCols columns, thread slice s of a column the rows s, s + kBgSlices, ...  (8 x 32
-// and not 32 x 8: at batch 1024 a slice is 32 dependent loads, not 128, and a 1024-wide layer is 128 blocks, not 32)
-constexpr int kBgCols = 8;
-constexpr int kBgSlices = kBdThreads / kBgCols;
-
-// exp and log in plain arithmetic: the same bits on the host and on the device.  |error| < 2^-50 relative on the ranges used
-// (exp: x <= 0 after the row's maximum is taken off; log: a sum in [1, 32]).
-BD_HD double bg_pow2(int n) { return __builtin_bit_cast(double, (unsigned long long)(n + 1023) << 52); }
-BD_HD double bg_exp(double x) {
-  if (x != x) return x;
-  if (x < -745.0) return 0.0;
-  if (x > 709.0) return INFINITY;
-  const double kf = x * 1.4426950408889634;
-  const int n = (int)(kf + (kf < 0.0 ? -0.5 : 0.5));
-  const double r = (x - n * 0.693147180369123816490e+00) - n * 1.90821492927058770002e-10;
-  double p = 1.0;
-  for (int k = 13; k >= 1; --k) p = 1.0 + r * p / (double)k;
-  return n < -1000 ? p * bg_pow2(n + 100) * bg_pow2(-100) : p * bg_pow2(n);
-}
-BD_HD double bg_log(double s) {
-  if (!(s > 0.0) || s == INFINITY) return s != s ? s : (s == INFINITY ? s : (s == 0.0 ? -INFINITY : NAN));
-  const unsigned long long bits = __builtin_bit_cast(unsigned long long, s);
-  int e = (int)((bits >> 52) & 0x7ff) - 1023;
-  double m = __builtin_bit_cast(double, (bits & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
-  if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
-  const double f = (m - 1.0) / (m + 1.0), f2 = f * f;
-  double q = 1.0 / 23.0;
-  for (int k = 21; k >= 1; k -= 2) q = q * f2 + 1.0 / (double)k;
-  return e * 0.693147180369123816490e+00 + (2.0 * f * q + e * 1.90821492927058770002e-10);
-}
-
-BD_HD float bg_mix(float old, float v, float scale_old, float scale_new) {
-  return scale_old == 0.0f ? scale_new * v : scale_old * old + scale_new * v;
-}
-BD_HD int bg_label(int y, int C) { return (y >= 0 && y < C) ? y : 0; }
-
 // the gradient (glo, ghi) on the box of h = s relu(z) + t becomes (gc, gr) = (g_zlo + g_zhi, g_zhi - g_zlo) on the box of z, and
 // the terms of d loss / d s and d loss / d t.  A gate multiplies, so that a NaN stays.
-BD_HD void bg_gate(double glo, double ghi, double s, float zlo, float zhi, float& gc, float& gr, float& es, float& et) {
+// inj: (ilo, ihi), the gradient that reaches the z box by another road (the relaxation of bounds_crown_grad.hip), is added.
+BD_HD void bg_gate(double glo, double ghi, double s, float zlo, float zhi, float& gc, float& gr, float& es, float& et, bool inj = false,
+                   double ilo = 0.0, double ihi = 0.0) {
   const double alo = zlo > 0.0f ? (double)zlo : 0.0, ahi = zhi > 0.0f ? (double)zhi : 0.0;
   const double ml = zlo > 0.0f ? 1.0 : 0.0, mh = zhi > 0.0f ? 1.0 : 0.0;
   double gzlo, gzhi, ds;
@@ -84,6 +53,10 @@ BD_HD void bg_gate(double glo, double ghi, double s, float zlo, float zhi, float
     gzhi = s * glo * mh;
     gzlo = s * ghi * ml;
     ds = glo * ahi + ghi * alo;
+  }
+  if (inj) {
+    gzlo = gzlo + ilo;
+    gzhi = gzhi + ihi;
   }
   gc = (float)(gzlo + gzhi);
   gr = (float)(gzhi - gzlo);
@@ -118,13 +91,6 @@ BD_HD double bg_head_dw_term(int e, int nh, int C, int b, int yb, const float* W
   return (double)coef[(size_t)b * C + k] * (double)(d > 0.0 ? lo[(size_t)b * nh + j] : hi[(size_t)b * nh + j]);
 }
 
-// dgamma and dbeta of a column from the sums of es and et
-BD_HD void bg_bn_grads(double sum_s, double sum_t, float mmean, float mvar, double& dgamma, double& dbeta) {
-  const double rstd = 1.0 / sqrt((double)mvar + (double)kBnEps);
-  dgamma = (sum_s - (double)mmean * sum_t) * rstd;
-  dbeta = sum_t;
-}
-
 // ------------------------------------------------------------------------------------------------------------------- the plan
 // the workspace, in floats from a 16-byte boundary; z / h / fam: the boxes of layer_lo / layer_hi (bd_boxes)
 struct BgPlan : BdBoxes {
@@ -152,7 +118,9 @@ static BgPlan bg_plan(const BdShape& sh, int batch) {
 
 // -------------------------------------------------------------------------------------------------------------------- kernels
 // a block per row b
-__global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __restrict__ margin, const int* __restrict__ y,
+__global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __restrict__ margin, const float* __restrict__ margin2, float mixbeta,
+                                                             const float* __restrict__ inj_lo, const float* __restrict__ inj_hi,
+                                                             const int* __restrict__ y,
                                                              const float* __restrict__ WL, int C, int nh, const float* __restrict__ lo,
                                                              const float* __restrict__ hi, int hidden, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ mmean,
@@ -164,7 +132,7 @@ __global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __rest
   const int tid = threadIdx.x, b = blockIdx.x;
   const int yraw = y[b], yb = bg_label(yraw, C);
   const bool ok = yraw == yb;
-  if (tid < C) p[tid] = tid == yb ? 0.0 : -(double)margin[(size_t)b * C + tid];
+  if (tid < C) p[tid] = tid == yb ? 0.0 : bg_u(margin, margin2, mixbeta, (size_t)b * C + tid);
   __syncthreads();
   double mx = 0.0;
   for (int k = 0; k < C; ++k) mx = p[k] > mx ? p[k] : mx;
@@ -177,6 +145,11 @@ __global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __rest
   if (tid < C) p[tid] = p[tid] / sum;
   __syncthreads();
   if (tid == 0) loss_rows[b] = (float)(mx + bg_log(sum));
+  if (margin2) {  // the interval part of the mixed margin carries the weight 1 - beta
+    __syncthreads();
+    if (tid < C) p[tid] = (1.0 - (double)mixbeta) * p[tid];
+    __syncthreads();
+  }
   if (tid < C) {
     double v = p[tid];
     if (tid == yb) {
@@ -193,7 +166,8 @@ __global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __rest
     ty_out[at] = (float)ty;
     if (hidden) {
       float vc, vr, vs, vt;
-      bg_gate(glo, ghi, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[at], zhi[at], vc, vr, vs, vt);
+      if (inj_lo) bg_gate(glo, ghi, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[at], zhi[at], vc, vr, vs, vt, true, inj_lo[at], inj_hi[at]);
+      else bg_gate(glo, ghi, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[at], zhi[at], vc, vr, vs, vt);
       gc[at] = vc;
       gr[at] = vr;
       if (gamma) {
@@ -343,6 +317,7 @@ __global__ __launch_bounds__(kBdThreads) void bg_back_kernel(const float* __rest
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              const float* __restrict__ mmean, const float* __restrict__ mvar,
                                                              const float* __restrict__ zlo, const float* __restrict__ zhi,
+                                                             const float* __restrict__ inj_lo, const float* __restrict__ inj_hi,
                                                              float* __restrict__ gc_out, float* __restrict__ gr_out,
                                                              float* __restrict__ es, float* __restrict__ et) {
   __shared__ float a1[32 * 33], a2[32 * 33], wt[128 * 33];
@@ -402,7 +377,8 @@ __global__ __launch_bounds__(kBdThreads) void bg_back_kernel(const float* __rest
     const size_t at = (size_t)b * N + i;
     const double c = acc_c[e], r = acc_r[e];
     float vc, vr, vs, vt;
-    bg_gate(0.5 * (c - r), 0.5 * (c + r), s, zlo[at], zhi[at], vc, vr, vs, vt);
+    if (inj_lo) bg_gate(0.5 * (c - r), 0.5 * (c + r), s, zlo[at], zhi[at], vc, vr, vs, vt, true, inj_lo[at], inj_hi[at]);
+    else bg_gate(0.5 * (c - r), 0.5 * (c + r), s, zlo[at], zhi[at], vc, vr, vs, vt);
     gc_out[at] = vc;
     gr_out[at] = vr;
     if (gamma) {
@@ -415,7 +391,9 @@ __global__ __launch_bounds__(kBdThreads) void bg_back_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------------------------ host twin
 static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, const float* bnstate, const float* margin,
                     const float* layer_lo, const float* layer_hi, const int* y, int batch, float* ws, float scale_old, float scale_new,
-                    float* grads, float* loss_rows) {
+                    float* grads, float* loss_rows, const BgMixIn* mix) {
+  const float* margin2 = mix ? mix->margin2 : nullptr;
+  const float mixbeta = mix ? mix->beta : 0.0f;
   const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
   const bool hidden = L > 1;
   auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
@@ -437,7 +415,7 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
     const bool ok = yb == y[b];
     double mx = 0.0, sum = 0.0;
     for (int k = 0; k < C; ++k) {
-      p[k] = k == yb ? 0.0 : -(double)margin[(size_t)b * C + k];
+      p[k] = k == yb ? 0.0 : bg_u(margin, margin2, mixbeta, (size_t)b * C + k);
       mx = p[k] > mx ? p[k] : mx;
     }
     for (int k = 0; k < C; ++k) {
@@ -446,6 +424,8 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
     }
     for (int k = 0; k < C; ++k) p[k] = p[k] / sum;
     loss_rows[b] = (float)(mx + bg_log(sum));
+    if (margin2)
+      for (int k = 0; k < C; ++k) p[k] = (1.0 - (double)mixbeta) * p[k];
     double vy = 0.0;
     for (int k = 0; k < C; ++k)
       if (k != yb) vy = vy - p[k];
@@ -458,7 +438,8 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
       if (hidden) {
         float vs, vt;
         bg_gate(glo, ghi, bd_aff(g, be, mm, mv, j).s, layer_lo[pl.z[L - 2] + at], layer_hi[pl.z[L - 2] + at], ws[pl.offG[cur][0] + at],
-                ws[pl.offG[cur][1] + at], vs, vt);
+                ws[pl.offG[cur][1] + at], vs, vt, mix != nullptr, mix ? mix->inj_lo[pl.z[L - 2] + at] : 0.0,
+                mix ? mix->inj_hi[pl.z[L - 2] + at] : 0.0);
         if (g) { ws[pl.offE[cur][0] + at] = vs; ws[pl.offE[cur][1] + at] = vt; }
       }
     }
@@ -538,7 +519,8 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
         const double c = accc[i], r = accr[i];
         float vs, vt;
         bg_gate(0.5 * (c - r), 0.5 * (c + r), bd_aff(g, be, mm, mv, i).s, layer_lo[pl.z[l - 1] + at], layer_hi[pl.z[l - 1] + at],
-                ws[pl.offG[cur ^ 1][0] + at], ws[pl.offG[cur ^ 1][1] + at], vs, vt);
+                ws[pl.offG[cur ^ 1][0] + at], ws[pl.offG[cur ^ 1][1] + at], vs, vt, mix != nullptr, mix ? mix->inj_lo[pl.z[l - 1] + at] : 0.0,
+                mix ? mix->inj_hi[pl.z[l - 1] + at] : 0.0);
         if (g) { ws[pl.offE[cur ^ 1][0] + at] = vs; ws[pl.offE[cur ^ 1][1] + at] = vt; }
       }
     }
@@ -568,6 +550,74 @@ static int bg_check(const char* fn, const BdShape& sh, const BgPlan& pl, const f
 
 static int bg_batch_check(const char* fn, const BdShape& sh, int batch) {
   LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  return LIPASR_OK;
+}
+
+size_t bg_workspace_floats(const BdShape& sh, int batch) { return bg_plan(sh, batch).total; }
+
+void bg_run_host(const BdShape& sh, const float* params, const float* bnstate, const float* margin, const float* layer_lo,
+                 const float* layer_hi, const int* y, int batch, float* ws, float scale_old, float scale_new, float* grads, float* loss_rows,
+                 const BgMixIn* mix) {
+  bg_host(sh, bg_plan(sh, batch), params, bnstate, margin, layer_lo, layer_hi, y, batch, ws, scale_old, scale_new, grads, loss_rows, mix);
+}
+
+int bg_run_device(const BdShape& sh, hipStream_t st, const float* params, const float* bnstate, const float* margin, const float* layer_lo,
+                  const float* layer_hi, const int* y, int batch, float* ws, float scale_old, float scale_new, float* grads, float* loss_rows,
+                  const BgMixIn* mix) {
+  const BgPlan pl = bg_plan(sh, batch);
+  const float* margin2 = mix ? mix->margin2 : nullptr;
+  const float mixbeta = mix ? mix->beta : 0.0f;
+  const float* ilo = mix ? mix->inj_lo : nullptr;
+  const float* ihi = mix ? mix->inj_hi : nullptr;
+  const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
+  const bool hidden = L > 1;
+  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
+    g = be = mm = mv = nullptr;
+    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
+  };
+  const float *g = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
+  float* coef = ws + pl.offCoef;
+  float* ty = ws + pl.offTy;
+  const float* WL = params + sh.offW[L - 1];
+  const float* hlo = hidden ? layer_lo + pl.h[L - 2] : layer_lo;
+  const float* hhi = hidden ? layer_hi + pl.h[L - 2] : layer_hi;
+  int cur = 0;
+  if (hidden) bnp(L - 2, g, be, mm, mv);
+  hipLaunchKernelGGL(bg_head_kernel, dim3(batch), dim3(kBdThreads), 0, st, margin, margin2, mixbeta,
+                     (hidden && ilo) ? ilo + pl.z[L - 2] : nullptr, (hidden && ihi) ? ihi + pl.z[L - 2] : nullptr, y, WL, C, nh, hlo, hhi, hidden ? 1 : 0, g, be, mm, mv,
+                     hidden ? layer_lo + pl.z[L - 2] : nullptr, hidden ? layer_hi + pl.z[L - 2] : nullptr, loss_rows, coef, ty,
+                     ws + pl.offG[cur][0], ws + pl.offG[cur][1], ws + pl.offE[cur][0], ws + pl.offE[cur][1]);
+  LP_LAUNCH_CHECK();
+  ++g_bounds_grad_launches[BG_HEAD];
+  hipLaunchKernelGGL(bg_head_dw_kernel, dim3((nh * C + C + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, WL, y, coef, ty, hlo, hhi, batch, C, nh,
+                     scale_old, scale_new, grads + sh.offW[L - 1], grads + sh.offb[L - 1]);
+  LP_LAUNCH_CHECK();
+  ++g_bounds_grad_launches[BG_HEAD];
+  for (int l = L - 2; l >= 0; --l) {
+    const int K = sh.n[l], N = sh.n[l + 1];
+    const float* gc = ws + pl.offG[cur][0];
+    const float* gr = ws + pl.offG[cur][1];
+    bnp(l, g, be, mm, mv);
+    hipLaunchKernelGGL(bg_colsum_kernel, dim3((N + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, gc, ws + pl.offE[cur][0], ws + pl.offE[cur][1], mm, mv,
+                       batch, N, scale_old, scale_new, grads + sh.offb[l], g ? grads + sh.offg[l] : nullptr,
+                       g ? grads + sh.offbe[l] : nullptr);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_grad_launches[BG_COLSUM];
+    hipLaunchKernelGGL(bg_wgrad_kernel, dim3((K + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, l == 0 ? layer_lo : layer_lo + pl.h[l - 1],
+                       l == 0 ? layer_hi : layer_hi + pl.h[l - 1], gc, gr, params + sh.offW[l], batch, K, N, scale_old, scale_new,
+                       grads + sh.offW[l]);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_grad_launches[BG_WGRAD];
+    if (l == 0) break;
+    bnp(l - 1, g, be, mm, mv);
+    hipLaunchKernelGGL(bg_back_kernel, dim3((batch + 31) / 32, (K + 127) / 128), dim3(kBdThreads), 0, st, gc, gr, params + sh.offW[l], batch, N,
+                       K, g, be, mm, mv, layer_lo + pl.z[l - 1], layer_hi + pl.z[l - 1], ilo ? ilo + pl.z[l - 1] : nullptr,
+                       ihi ? ihi + pl.z[l - 1] : nullptr, ws + pl.offG[cur ^ 1][0], ws + pl.offG[cur ^ 1][1],
+                       ws + pl.offE[cur ^ 1][0], ws + pl.offE[cur ^ 1][1]);
+    LP_LAUNCH_CHECK();
+    ++g_bounds_grad_launches[BG_BACK];
+    cur ^= 1;
+  }
   return LIPASR_OK;
 }
 
@@ -610,56 +660,8 @@ int lipasr_mlp_bounds_grad(lipasr_mlp_t m, const float* params, const float* bns
   if (int rc = bg_check(fn, sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, workspace, workspace_floats, grads, loss_rows))
     return rc;
   DeviceGuard guard(m->ctx->device);
-  hipStream_t st = S(stream);
-  float* ws = bd_base(workspace);
-  const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
-  const bool hidden = L > 1;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
-  const float *g = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
-  float* coef = ws + pl.offCoef;
-  float* ty = ws + pl.offTy;
-  const float* WL = params + sh.offW[L - 1];
-  const float* hlo = hidden ? layer_lo + pl.h[L - 2] : layer_lo;
-  const float* hhi = hidden ? layer_hi + pl.h[L - 2] : layer_hi;
-  int cur = 0;
-  if (hidden) bnp(L - 2, g, be, mm, mv);
-  hipLaunchKernelGGL(bg_head_kernel, dim3(batch), dim3(kBdThreads), 0, st, margin_ibp, y, WL, C, nh, hlo, hhi, hidden ? 1 : 0, g, be, mm, mv,
-                     hidden ? layer_lo + pl.z[L - 2] : nullptr, hidden ? layer_hi + pl.z[L - 2] : nullptr, loss_rows, coef, ty,
-                     ws + pl.offG[cur][0], ws + pl.offG[cur][1], ws + pl.offE[cur][0], ws + pl.offE[cur][1]);
-  LP_LAUNCH_CHECK();
-  ++g_bounds_grad_launches[BG_HEAD];
-  hipLaunchKernelGGL(bg_head_dw_kernel, dim3((nh * C + C + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, WL, y, coef, ty, hlo, hhi, batch, C, nh,
-                     scale_old, scale_new, grads + sh.offW[L - 1], grads + sh.offb[L - 1]);
-  LP_LAUNCH_CHECK();
-  ++g_bounds_grad_launches[BG_HEAD];
-  for (int l = L - 2; l >= 0; --l) {
-    const int K = sh.n[l], N = sh.n[l + 1];
-    const float* gc = ws + pl.offG[cur][0];
-    const float* gr = ws + pl.offG[cur][1];
-    bnp(l, g, be, mm, mv);
-    hipLaunchKernelGGL(bg_colsum_kernel, dim3((N + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, gc, ws + pl.offE[cur][0], ws + pl.offE[cur][1], mm, mv,
-                       batch, N, scale_old, scale_new, grads + sh.offb[l], g ? grads + sh.offg[l] : nullptr,
-                       g ? grads + sh.offbe[l] : nullptr);
-    LP_LAUNCH_CHECK();
-    ++g_bounds_grad_launches[BG_COLSUM];
-    hipLaunchKernelGGL(bg_wgrad_kernel, dim3((K + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, l == 0 ? layer_lo : layer_lo + pl.h[l - 1],
-                       l == 0 ? layer_hi : layer_hi + pl.h[l - 1], gc, gr, params + sh.offW[l], batch, K, N, scale_old, scale_new,
-                       grads + sh.offW[l]);
-    LP_LAUNCH_CHECK();
-    ++g_bounds_grad_launches[BG_WGRAD];
-    if (l == 0) break;
-    bnp(l - 1, g, be, mm, mv);
-    hipLaunchKernelGGL(bg_back_kernel, dim3((batch + 31) / 32, (K + 127) / 128), dim3(kBdThreads), 0, st, gc, gr, params + sh.offW[l], batch, N,
-                       K, g, be, mm, mv, layer_lo + pl.z[l - 1], layer_hi + pl.z[l - 1], ws + pl.offG[cur ^ 1][0], ws + pl.offG[cur ^ 1][1],
-                       ws + pl.offE[cur ^ 1][0], ws + pl.offE[cur ^ 1][1]);
-    LP_LAUNCH_CHECK();
-    ++g_bounds_grad_launches[BG_BACK];
-    cur ^= 1;
-  }
-  return LIPASR_OK;
+  return bg_run_device(sh, S(stream), params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, bd_base(workspace), scale_old, scale_new, grads,
+                       loss_rows, nullptr);
 }
 
 int lipasr_mlp_bounds_grad_host(int n_layers, const int* widths, const int* bn, const float* params, const float* bnstate,
@@ -673,7 +675,7 @@ int lipasr_mlp_bounds_grad_host(int n_layers, const int* widths, const int* bn, 
   const BgPlan pl = bg_plan(sh, batch);
   if (int rc = bg_check(fn, sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, workspace, workspace_floats, grads, loss_rows))
     return rc;
-  bg_host(sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, bd_base(workspace), scale_old, scale_new, grads, loss_rows);
+  bg_host(sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, bd_base(workspace), scale_old, scale_new, grads, loss_rows, nullptr);
   return LIPASR_OK;
 }
 

@@ -155,6 +155,11 @@ PROTOTYPES = {
     "lipasr_mlp_bounds_grad_workspace_host": (i32, [i32, PI, i32, C.POINTER(sz)]),
     "lipasr_mlp_bounds_grad_host": (i32, [i32, PI, PI, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, sz, f32, f32, c_f, c_f]),
     "lipasr_debug_bounds_grad_launches": (C.c_long, [i32]),
+    "lipasr_mlp_bounds_crown_grad_workspace": (i32, [c_h, i32, C.POINTER(sz)]),
+    "lipasr_mlp_bounds_crown_grad": (i32, [c_h, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, f32, c_f, sz, f32, f32, c_f, c_f, c_s]),
+    "lipasr_mlp_bounds_crown_grad_workspace_host": (i32, [i32, PI, i32, C.POINTER(sz)]),
+    "lipasr_mlp_bounds_crown_grad_host": (i32, [i32, PI, PI, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, f32, c_f, sz, f32, f32, c_f, c_f]),
+    "lipasr_debug_bounds_crown_grad_launches": (C.c_long, [i32]),
     "lipasr_warp_table_host": (i32, [c_f, c_f]),
     "lipasr_warp_apply": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
     "lipasr_warp_param_vjp": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_s]),
@@ -254,7 +259,10 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_debug_warp_launches": 720, "lipasr_debug_k2_launches": 730, "lipasr_debug_mlp_stage": 730, "lipasr_defence_apply": 740,
          "lipasr_defence_vjp": 740, "lipasr_defence_apply_host": 740, "lipasr_defence_vjp_host": 740, "lipasr_debug_defence_launches": 740,
          "lipasr_mlp_bounds_grad_workspace": 750, "lipasr_mlp_bounds_grad": 750, "lipasr_mlp_bounds_grad_workspace_host": 750,
-         "lipasr_mlp_bounds_grad_host": 750, "lipasr_debug_bounds_grad_launches": 750}
+         "lipasr_mlp_bounds_grad_host": 750, "lipasr_debug_bounds_grad_launches": 750,
+         "lipasr_mlp_bounds_crown_grad_workspace": 760, "lipasr_mlp_bounds_crown_grad": 760,
+         "lipasr_mlp_bounds_crown_grad_workspace_host": 760, "lipasr_mlp_bounds_crown_grad_host": 760,
+         "lipasr_debug_bounds_crown_grad_launches": 760}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -972,4 +980,47 @@ def mlp_bounds_grad_host(widths, bn, params, bnstate, margin_ibp, lo, hi, y, *, 
            "loss_rows": np.zeros(b, np.float32)}
     check(lib.lipasr_mlp_bounds_grad_host(L, wa, ba, _vp(params), _vp(bnstate), _vp(margin_ibp), _vp(lo), _vp(hi), _vp(y), b, _vp(wsv),
                                           need.value, float(scale_old), float(scale_new), _vp(out["grads"]), _vp(out["loss_rows"])))
+    return out
+
+
+# ids of lipasr_debug_bounds_crown_grad_launches
+BOUNDS_CROWN_GRAD_KERNELS = ("soft", "relax", "product", "adjoint", "wgrad", "wreduce", "colsum", "finish", "head")
+
+
+def bounds_crown_grad_launches(n_layers):
+    """Launches of one lipasr_mlp_bounds_crown_grad call at beta > 0 per id of BOUNDS_CROWN_GRAD_KERNELS, for a model of n_layers
+    Dense layers; the sweep of lipasr_mlp_bounds_grad that follows counts under bounds_grad_launches(n_layers)."""
+    h = int(n_layers) - 1
+    return {"soft": 1, "relax": max(h, 1), "product": h, "adjoint": h, "wgrad": h, "wreduce": h, "colsum": h, "finish": h, "head": 1}
+
+
+def mlp_bounds_crown_grad_host(widths, bn, params, bnstate, margin_ibp, margin_crown, lo, hi, y, beta, *, scale_old=0.0, scale_new=1.0,
+                               grads=None, ws_offset=0):
+    """Host-only: lipasr_mlp_bounds_crown_grad_host on NumPy arrays (margin_ibp, margin_crown, lo, hi as mlp_bounds_host returned
+    them) -> dict(grads [n_params], loss_rows [B]).  grads: the buffer that scale_old applies to (default zeros); it is not
+    changed.  ws_offset: floats the workspace starts past a 16-byte boundary."""
+    import numpy as np
+
+    widths = [int(w) for w in widths]
+    L = len(widths) - 1
+    margin_ibp = np.ascontiguousarray(margin_ibp, dtype=np.float32)
+    b = margin_ibp.shape[0]
+    margin_crown = _host_in(margin_crown, np.float32, (b, widths[-1]), "margin_crown")
+    params = np.ascontiguousarray(params, dtype=np.float32)
+    bnstate = None if bnstate is None else np.ascontiguousarray(bnstate, dtype=np.float32)
+    fam = bounds_family_floats(widths, b)
+    lo = _host_in(lo, np.float32, (fam,), "lo")
+    hi = _host_in(hi, np.float32, (fam,), "hi")
+    y = _host_in(y, np.int32, (b,), "y")
+    wa, ba = int_array(widths), (None if bn is None else int_array(bn))
+    need = sz()
+    check(lib.lipasr_mlp_bounds_crown_grad_workspace_host(L, wa, b, C.byref(need)))
+    ws = np.zeros(need.value + 8, dtype=np.float32)
+    skip = (-(ws.ctypes.data // 4)) % 4 + int(ws_offset)
+    wsv = ws[skip:skip + need.value]
+    out = {"grads": np.zeros(params.size, np.float32) if grads is None else np.array(grads, dtype=np.float32, copy=True),
+           "loss_rows": np.zeros(b, np.float32)}
+    check(lib.lipasr_mlp_bounds_crown_grad_host(L, wa, ba, _vp(params), _vp(bnstate), _vp(margin_ibp), _vp(margin_crown), _vp(lo), _vp(hi),
+                                                _vp(y), b, float(beta), _vp(wsv), need.value, float(scale_old), float(scale_new),
+                                                _vp(out["grads"]), _vp(out["loss_rows"])))
     return out

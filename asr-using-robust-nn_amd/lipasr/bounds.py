@@ -102,6 +102,68 @@ class IBPCrossentropy(CategoricalCrossentropy):
         return True
 
 
+class CrownIBPCrossentropy(IBPCrossentropy):
+    """CROWN-IBP certified training (Zhang et al. 2020) as a loss for ``Model.compile``: IBPCrossentropy with the worst-case logits
+    taken from the mixed margin
+
+        (1 - beta_t) margin_ibp + beta_t margin_crown
+
+    of ONE lipasr_mlp_bounds call; its gradient is lipasr_mlp_bounds_crown_grad ("CROWN-IBP certified training").
+    beta_t goes linearly from ``beta_start`` to ``beta_end`` over the ramp of eps_t and kappa_t; the paper's schedule is 1 -> 0,
+    ``beta_start = beta_end = 1`` trains on the CROWN-IBP margin throughout.  A step at beta_t = 0 makes exactly the calls of
+    IBPCrossentropy, a step at kappa_t = 0 those of the plain step.  Not built: norm 2, data parallel, TrainPipeline."""
+
+    name = "crown_ibp_categorical_crossentropy"
+
+    def __init__(self, eps, kappa=0.5, warmup_steps=0, ramp_steps=1, beta_start=1.0, beta_end=0.0, clip_values=None, norm=float("inf")):
+        super().__init__(eps, kappa=kappa, warmup_steps=warmup_steps, ramp_steps=ramp_steps, clip_values=clip_values, norm=norm)
+        for k, v in (("beta_start", beta_start), ("beta_end", beta_end)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"{k} = {v!r}: in [0, 1]")
+        self.beta_start, self.beta_end = float(beta_start), float(beta_end)
+
+    def beta_schedule(self, step):
+        """beta_t of the ``step``-th call of train_on_batch, counted from 0."""
+        f = min(max((int(step) - self.warmup_steps) / self.ramp_steps, 0.0), 1.0)
+        return self.beta_start + (self.beta_end - self.beta_start) * f
+
+    def _crown_buffers(self, model):
+        buf = self._buffers(model)
+        if "ws_crown" not in buf:
+            b, w, dev = model._max_batch, model._widths, model._device
+            need = N.sz()
+            N.check(N.lib.lipasr_mlp_bounds_crown_grad_workspace(model._plan, b, N.C.byref(need)))
+            buf["ws_crown"] = torch.zeros(need.value, device=dev)
+            buf["margin_crown"] = torch.zeros(b * w[-1], device=dev)
+        return buf
+
+    def train_step(self, model, xb, yb, masks=None, dropout=True):
+        """One step of ``model`` under this loss; False when kappa_t is 0.  Otherwise the plain pass scaled by 1 - kappa_t, the
+        bounds at eps_t with margin_crown, lipasr_mlp_bounds_crown_grad at beta_t mixed in at kappa_t / batch, Adam."""
+        beta_t = self.beta_schedule(self.step)
+        if beta_t == 0.0 or self.schedule(self.step)[1] == 0.0:
+            return super().train_step(model, xb, yb, masks=masks, dropout=dropout)
+        eps_t, kappa_t = self.schedule(self.step)
+        self.step += 1
+        b = xb.shape[0]
+        buf = self._crown_buffers(model)
+        model.train_fwd_bwd(xb, yb, inv_batch=(1.0 - kappa_t) / b, masks=masks, dropout=dropout)
+        yt = yb.argmax(dim=1).to(torch.int32)
+        buf["eps"][:b].fill_(eps_t)
+        args = (model._plan, N.ptr(model._params), N.ptr(model._bnstate))
+        N.check(N.lib.lipasr_mlp_bounds(*args, N.ptr(xb), N.ptr(buf["eps"]), float("inf"), self.clip[0], self.clip[1], N.ptr(yt), b,
+                                        N.ptr(buf["ws"]), buf["ws"].numel(), N.ptr(buf["margin"]), N.ptr(buf["margin_crown"]), None,
+                                        N.ptr(buf["lo"]), N.ptr(buf["hi"]), N.stream_ptr()))
+        N.check(N.lib.lipasr_mlp_bounds_crown_grad(*args, N.ptr(buf["margin"]), N.ptr(buf["margin_crown"]), N.ptr(buf["lo"]),
+                                                   N.ptr(buf["hi"]), N.ptr(yt), b, beta_t, N.ptr(buf["ws_crown"]),
+                                                   buf["ws_crown"].numel(), 1.0, kappa_t / b, N.ptr(model._grads), N.ptr(buf["rows"]),
+                                                   N.stream_ptr()))
+        rows = model._loss_rows[:b]
+        rows.mul_(1.0 - kappa_t).add_(buf["rows"][:b], alpha=kappa_t)  # what fit() logs
+        model.apply_adam()
+        return True
+
+
 def _check(estimator, norm, method):
     if getattr(estimator, "extractor", None) is not None or isinstance(estimator, E.WaveformClassifier):
         raise TypeError("bound propagation needs rows of features (a TensorFlowV2Classifier): over audio the MFCC stage's log has "

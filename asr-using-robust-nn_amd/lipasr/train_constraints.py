@@ -110,6 +110,10 @@ def add_certified_arguments(ap):
     ap.add_argument("--certified-kappa", type=float, default=0.5, help="final weight of the robust cross-entropy")
     ap.add_argument("--certified-warmup", type=int, default=0, help="steps of plain training before the ramp")
     ap.add_argument("--certified-ramp", type=int, default=1, help="steps over which eps and kappa rise from 0")
+    ap.add_argument("--certified-method", choices=("ibp", "crown-ibp"), default="ibp", help="the margins the robust cross-entropy is "
+                    "taken on: the interval bounds (IBPCrossentropy) or their mix with the CROWN-IBP margins (CrownIBPCrossentropy)")
+    ap.add_argument("--certified-beta", type=float, nargs=2, default=(1.0, 0.0), metavar=("START", "END"),
+                    help="crown-ibp: the weight of the CROWN-IBP margin at the start and at the end of the ramp")
     return ap
 
 
@@ -118,11 +122,16 @@ def certified_arguments(argv):
 
 
 def certified_loss(args):
-    """The IBPCrossentropy the flags ask for, or None."""
+    """The IBPCrossentropy or CrownIBPCrossentropy the flags ask for, or None."""
     if args.certified_eps is None:
         return None
     from .bounds import IBPCrossentropy
 
+    if args.certified_method == "crown-ibp":
+        from .bounds import CrownIBPCrossentropy
+
+        return CrownIBPCrossentropy(args.certified_eps, kappa=args.certified_kappa, warmup_steps=args.certified_warmup,
+                                    ramp_steps=args.certified_ramp, beta_start=args.certified_beta[0], beta_end=args.certified_beta[1])
     return IBPCrossentropy(args.certified_eps, kappa=args.certified_kappa, warmup_steps=args.certified_warmup,
                            ramp_steps=args.certified_ramp)
 

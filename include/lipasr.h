@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 750. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 760. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -61,6 +61,8 @@
  * lipasr_debug_defence_launches.
  * 750: IBP certified training: lipasr_mlp_bounds_grad (the backward pass of the interval bounds with respect to the parameters),
  * lipasr_mlp_bounds_grad_workspace, their _host twins and the test hook lipasr_debug_bounds_grad_launches.
+ * 760: CROWN-IBP certified training: lipasr_mlp_bounds_crown_grad (the backward pass of the relaxation with respect to the parameters),
+ * lipasr_mlp_bounds_crown_grad_workspace, their _host twins and the test hook lipasr_debug_bounds_crown_grad_launches.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -947,6 +949,42 @@ int lipasr_mlp_bounds_grad_host(int n_layers, const int* widths, const int* bn, 
 /* Test hook: launches since the library was loaded of 0 the two head kernels, 1 bg_wgrad_kernel, 2 bg_back_kernel,
  * 3 bg_colsum_kernel, counted on the host where the launch happens; -1 for an unknown id. */
 long lipasr_debug_bounds_grad_launches(int kernel);
+
+/* CROWN-IBP certified training (Zhang et al. 2020; lipasr.bounds.CrownIBPCrossentropy): the backward pass of the relaxation with
+ * respect to the parameters.  From what ONE lipasr_mlp_bounds call under norm +INFINITY wrote for (params, bnstate, y, batch) with
+ * margin_crown requested and the boxes kept, per row b and with beta in [0, 1]
+ *     mixed[b][k] = (1 - beta) margin_ibp[b][k] + beta margin_crown[b][k]
+ *     u[b][k] = -mixed[b][k] (k != y_b),  u[b][y_b] = 0,   loss_rows[b] = logsumexp_k u[b][k]
+ *     grads = scale_old * grads + scale_new * d( sum_b loss_rows[b] ) / d params          (scale_old == 0: the old contents of grads are ignored)
+ * in the layout and with the conventions of lipasr_mlp_bounds_grad.  margin_crown is differentiated along the chain
+ * Lambda_l -> nu_l -> Lambda_{l-1} and through the pre-activation boxes that set the upper line of every unstable neuron; further
+ * constants: the slack, the (1 + 2^-40) factors of that line.  Further conventions (torch's): a coefficient p < 0 takes the upper
+ * line, anything else the lower one, whose slope carries no gradient; Lambda_0 > 0 selects lo of the input box, anything else hi.
+ * A row whose margins are NaN, or whose y_b is outside [0, classes), makes loss_rows[b] and the whole gradient NaN.
+ *   workspace: device floats, any 4-byte alignment, lipasr_mlp_bounds_crown_grad_workspace(m, batch) of them -- every level of the
+ *   chain is kept, twice batch * classes * (n_0 + ... + n_{L-1}) floats and more; nothing is kept between calls.
+ *   LIPASR_EINVAL for everything lipasr_mlp_bounds_grad refuses, a null margin_crown, and beta outside [0, 1] or NaN.
+ * Launches with L layers: beta == 0 makes exactly the launches of lipasr_mlp_bounds_grad and writes its bits.  Otherwise 5 for
+ * L = 1 and 10 (L - 1) + 3 for L >= 2: cg_soft_kernel (1), cg_relax_kernel (max(L - 1, 1)), bounds_back_kernel (L - 1),
+ * per hidden layer cg_adjoint_kernel, cg_wgrad_kernel (v_mfma_f32_32x32x2_f32 both; the rows split over blockIdx.z), cg_wreduce_kernel,
+ * cg_colsum_kernel (the column sums, M split over blockIdx.y) and cg_finish_kernel (the injections; db, dgamma, dbeta), cg_head_kernel (1), then the 3 (L - 1) + 1 (2 for L = 1) launches of
+ * lipasr_mlp_bounds_grad's sweep, which takes the mixed margins and the gradient on the boxes.  Every sum runs in one order that
+ * the shapes fix (no atomics): two calls give the same bits.  Nothing allocates or synchronises. */
+int lipasr_mlp_bounds_crown_grad_workspace(lipasr_mlp_t m, int batch, size_t* floats);
+int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const float* bnstate, const float* margin_ibp /* [batch][classes] */,
+                                 const float* margin_crown /* [batch][classes] */, const float* layer_lo, const float* layer_hi,
+                                 const int* y /* [batch] */, int batch, float beta, float* workspace, size_t workspace_floats,
+                                 float scale_old, float scale_new, float* grads, float* loss_rows /* [batch] */, lipasr_stream_t stream);
+/* Host-only twins, as lipasr_mlp_bounds_grad_host: the same values as the device entry point (a zero may differ in sign). */
+int lipasr_mlp_bounds_crown_grad_workspace_host(int n_layers, const int* widths, int batch, size_t* floats);
+int lipasr_mlp_bounds_crown_grad_host(int n_layers, const int* widths, const int* bn, const float* params, const float* bnstate,
+                                      const float* margin_ibp, const float* margin_crown, const float* layer_lo, const float* layer_hi,
+                                      const int* y, int batch, float beta, float* workspace, size_t workspace_floats, float scale_old,
+                                      float scale_new, float* grads, float* loss_rows);
+/* Test hook: launches since the library was loaded of 0 cg_soft_kernel, 1 cg_relax_kernel, 2 bounds_back_kernel (as this call
+ * launches it), 3 cg_adjoint_kernel, 4 cg_wgrad_kernel, 5 cg_wreduce_kernel, 6 cg_colsum_kernel, 7 cg_finish_kernel, 8 cg_head_kernel;
+ * the sweep of lipasr_mlp_bounds_grad counts under lipasr_debug_bounds_grad_launches; -1 for an unknown id. */
+long lipasr_debug_bounds_crown_grad_launches(int kernel);
 
 /* The time-warp operator (lipasr/warp.py, attacks.TimeWarp; ours -- ART's SpatialTransformation is the image form): every clip
  * resampled under K triples (shift in samples, rate, linear gain) by band-limited interpolation, in one launch.  x is [clips][n];
