@@ -49,7 +49,7 @@ using namespace lipasr;
 
 extern "C" {
 
-int lipasr_version(void) { return 760; }  // 760: CROWN-IBP certified training (lipasr_mlp_bounds_crown_grad, lipasr_mlp_bounds_crown_grad_workspace, their _host twins, lipasr_debug_bounds_crown_grad_launches); 750: IBP certified training (lipasr_mlp_bounds_grad, lipasr_mlp_bounds_grad_workspace, their _host twins, lipasr_debug_bounds_grad_launches); 740: input-transformation defences over audio (lipasr_defence_apply, lipasr_defence_vjp, their _host twins, lipasr_debug_defence_launches); 730: test hooks of the training step's own kernels (lipasr_debug_k2_launches, lipasr_debug_mlp_stage); 720: the time-warp operator (lipasr_warp_table_host, lipasr_warp_apply, lipasr_warp_param_vjp, their _host twins, lipasr_debug_warp_launches); 710: certified robustness by bound propagation (lipasr_mlp_bounds, lipasr_mlp_bounds_workspace, their _host twins, lipasr_debug_bounds_launches); 700: universal adversarial perturbations (lipasr_universal_shifts, _apply, _reduce, _step and their _host twins); 690: test hooks of the MFCC backward pass (lipasr_debug_k1_vjp_launches, lipasr_debug_mfcc_vjp_stage, lipasr_debug_mfcc_stage_put); 680: the over-the-air channel (lipasr_room_apply, lipasr_room_vjp and their _host twins); 670: HopSkipJump (lipasr_hsj_expand, _accumulate, _direction, _search, their _host twins, lipasr_debug_hsj_path); 660: Square Attack (lipasr_square_init, lipasr_square_step and their _host twins); 650: Auto-PGD (lipasr_apgd_loss, lipasr_apgd_step, lipasr_debug_apgd_path); 640: test hooks of the MFCC forward pass (lipasr_debug_k1_launches, lipasr_debug_mfcc_stage); 630: launch counters of the K3 projection kernels (lipasr_debug_k3_launches); 620: the genetic black-box attack (lipasr_genetic_breed, lipasr_genetic_select, lipasr_genetic_breed_host); 610: randomized smoothing (lipasr_smooth_expand, lipasr_smooth_vote, lipasr_smooth_noise_host); 600: one DeepFool iteration (lipasr_deepfool_step); 590: the psychoacoustic masking threshold and the imperceptible attack's loss (lipasr_psy_*); 580: the local Lipschitz read-out (lipasr_mlp_jacobian, lipasr_jacobian_sigma); 570: the DolphinAttack chain (lipasr_dolphin_*); 560: lipasr_mlp_adam_project_product_signal; 550: the backward pass of the short-window MFCC plans (lipasr_mfcc_plan_vjp_short); 540: test hooks of the GEMM selector (lipasr_debug_gemm, lipasr_debug_gemm_launches, lipasr_debug_group_launches); 530: per-clip lengths in the MFCC backward pass and the split forward (lipasr_mfcc_plan_*_ragged); 520: the MFCC backward pass (lipasr_mfcc_plan_vjp, lipasr_mfcc_plan_resample_vjp); 510: the Lp attack entry points (round 4 added lipasr_flag_*, lipasr_debug_chain_head; round 5: see include/lipasr.h)
+int lipasr_version(void) { return 770; }  // 770: training for randomized smoothing (lipasr_mlp_train_fwd, lipasr_mlp_train_bwd, lipasr_smooth_loss, lipasr_smooth_loss_host, lipasr_smooth_probit_host, lipasr_debug_smooth_loss_launches); 760: CROWN-IBP certified training (lipasr_mlp_bounds_crown_grad, lipasr_mlp_bounds_crown_grad_workspace, their _host twins, lipasr_debug_bounds_crown_grad_launches); 750: IBP certified training (lipasr_mlp_bounds_grad, lipasr_mlp_bounds_grad_workspace, their _host twins, lipasr_debug_bounds_grad_launches); 740: input-transformation defences over audio (lipasr_defence_apply, lipasr_defence_vjp, their _host twins, lipasr_debug_defence_launches); 730: test hooks of the training step's own kernels (lipasr_debug_k2_launches, lipasr_debug_mlp_stage); 720: the time-warp operator (lipasr_warp_table_host, lipasr_warp_apply, lipasr_warp_param_vjp, their _host twins, lipasr_debug_warp_launches); 710: certified robustness by bound propagation (lipasr_mlp_bounds, lipasr_mlp_bounds_workspace, their _host twins, lipasr_debug_bounds_launches); 700: universal adversarial perturbations (lipasr_universal_shifts, _apply, _reduce, _step and their _host twins); 690: test hooks of the MFCC backward pass (lipasr_debug_k1_vjp_launches, lipasr_debug_mfcc_vjp_stage, lipasr_debug_mfcc_stage_put); 680: the over-the-air channel (lipasr_room_apply, lipasr_room_vjp and their _host twins); 670: HopSkipJump (lipasr_hsj_expand, _accumulate, _direction, _search, their _host twins, lipasr_debug_hsj_path); 660: Square Attack (lipasr_square_init, lipasr_square_step and their _host twins); 650: Auto-PGD (lipasr_apgd_loss, lipasr_apgd_step, lipasr_debug_apgd_path); 640: test hooks of the MFCC forward pass (lipasr_debug_k1_launches, lipasr_debug_mfcc_stage); 630: launch counters of the K3 projection kernels (lipasr_debug_k3_launches); 620: the genetic black-box attack (lipasr_genetic_breed, lipasr_genetic_select, lipasr_genetic_breed_host); 610: randomized smoothing (lipasr_smooth_expand, lipasr_smooth_vote, lipasr_smooth_noise_host); 600: one DeepFool iteration (lipasr_deepfool_step); 590: the psychoacoustic masking threshold and the imperceptible attack's loss (lipasr_psy_*); 580: the local Lipschitz read-out (lipasr_mlp_jacobian, lipasr_jacobian_sigma); 570: the DolphinAttack chain (lipasr_dolphin_*); 560: lipasr_mlp_adam_project_product_signal; 550: the backward pass of the short-window MFCC plans (lipasr_mfcc_plan_vjp_short); 540: test hooks of the GEMM selector (lipasr_debug_gemm, lipasr_debug_gemm_launches, lipasr_debug_group_launches); 530: per-clip lengths in the MFCC backward pass and the split forward (lipasr_mfcc_plan_*_ragged); 520: the MFCC backward pass (lipasr_mfcc_plan_vjp, lipasr_mfcc_plan_resample_vjp); 510: the Lp attack entry points (round 4 added lipasr_flag_*, lipasr_debug_chain_head; round 5: see include/lipasr.h)
 
 const char* lipasr_last_error(void) { return g_err; }
 

@@ -283,12 +283,13 @@ static void set_exchange(GemmArgs& g, const lipasr_mlp* m, int dir, int l, int b
 }
 
 // [dW ; db] of layer l = [lin ; 1]^T[n_in+1][B] * gin[B][n_out]: the all-ones row yields the bias gradient.  g0: the bound of the
-// gradient at the logits the step ran with.  The grouped launch of the step and lipasr_mlp_train_dw0 both take it from here.
-static GemmArgs dw_args(const lipasr_mlp* m, int l, const float* x, float* grads, int batch, float g0) {
+// gradient at the logits the step ran with, dz_last: that gradient itself (the plan's own slot, or the caller's of
+// lipasr_mlp_train_bwd).  The grouped launch of the step and lipasr_mlp_train_dw0 both take it from here.
+static GemmArgs dw_args(const lipasr_mlp* m, int l, const float* x, float* grads, int batch, float g0, const float* dz_last) {
   const MlpLayer& L = m->L[l];
   const bool last = (l == m->n_layers - 1);
   const float* lin = (l == 0) ? x : (m->ws + m->L[l - 1].offH);
-  const float* gin = last ? (m->ws + m->offDzLast) : (m->ws + L.offDz);
+  const float* gin = last ? dz_last : (m->ws + L.offDz);
   GemmArgs g = gemm_args(lin, L.n_in, gin, L.n_out, grads + L.offW, L.n_out, L.n_in + 1, L.n_out, batch, EPI_STORE);
   g.ones_row = 1;
   g.extra_out = grads + L.offb;
@@ -341,9 +342,10 @@ struct Step {
   const float* params;
   float* bnstate;
   const float* x;
-  const float* y_onehot;
+  const float* y_onehot;  // null (lipasr_mlp_train_fwd): the last epilogue writes logits and probabilities only
+  const float* dz_last;   // the gradient at the logits the backward passes read: the plan's slot, or the caller's (lipasr_mlp_train_bwd)
   int batch;
-  float inv_batch;
+  float inv_batch;        // the factor on p - y, and the bound of the gradient at the logits (lipasr_mlp_train_bwd: the caller's dz_bound)
   const lipasr_dropout_cfg* dropout;
   float* grads;
   float* loss_rows;
@@ -467,7 +469,7 @@ static int step_dx_chain(Step& s) {
   for (int l = Lc - 1; l >= 1; --l) {
     const MlpLayer& L = m->L[l];
     const MlpLayer& P = m->L[l - 1];
-    const float* gin = (l == Lc - 1) ? (ws + m->offDzLast) : (ws + L.offDz);
+    const float* gin = (l == Lc - 1) ? s.dz_last : (ws + L.offDz);
     // dh_prev[B][n_in] = gin[B][n_out] * W^T
     const bool bnx = P.bn && !s.segmented() && bnx_fits(m, false, s.batch, L.n_in, L.n_out);
     float* out1 = (P.bn && !bnx) ? (ws + m->offG0) : (ws + P.offDz);
@@ -511,7 +513,7 @@ static int step_weight_grads(Step& s, int dw_mode) {
   if (!s.seg.on()) return LIPASR_OK;
   const int Lc = s.m->n_layers;
   GemmArgs gw[LIPASR_MAX_LAYERS];
-  for (int l = 0; l < Lc; ++l) gw[l] = dw_args(s.m, l, s.x, s.grads, s.batch, s.inv_batch);
+  for (int l = 0; l < Lc; ++l) gw[l] = dw_args(s.m, l, s.x, s.grads, s.batch, s.inv_batch, s.dz_last);
   if (dw_mode == 0 || Lc == 1) return launch_gemm_group_tn(gw, Lc, s.st);
   int rc = launch_gemm_group_tn(gw + 1, Lc - 1, s.st);
   if (rc != LIPASR_OK || dw_mode == 2) return rc;
@@ -527,6 +529,24 @@ struct SegArgs {
   float grad_scale = 1.0f;
 };
 
+// the step's arguments as every entry point fills them; the caller sets what its passes do not need to null
+static Step make_step(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, const float* y_onehot, int batch,
+                      float inv_batch, const lipasr_dropout_cfg* dropout, float* grads, float* loss_rows, float* correct_rows,
+                      float* probs, lipasr_stream_t stream, const SegArgs& sa) {
+  Step s;
+  s.m = m; s.params = params; s.bnstate = bnstate; s.x = x; s.y_onehot = y_onehot;
+  s.dz_last = m->ws + m->offDzLast;
+  s.batch = batch; s.inv_batch = inv_batch; s.dropout = dropout;
+  s.grads = grads; s.loss_rows = loss_rows; s.correct_rows = correct_rows; s.probs = probs;
+  s.st = S(stream);
+  s.part = sa.part_ext ? sa.part_ext : (m->ws + m->offPart);
+  s.bstat = sa.stat_batch > 0 ? sa.stat_batch : batch;
+  s.grad_scale = sa.grad_scale;
+  s.seg.pts = exchange_points(m);
+  s.seg.want = sa.seg;
+  return s;
+}
+
 static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, const float* y_onehot,
                               int batch, float inv_batch, const lipasr_dropout_cfg* dropout, float* grads,
                               float* loss_rows, float* correct_rows, float* probs, lipasr_stream_t stream, int dw_mode,
@@ -537,16 +557,7 @@ static int train_fwd_bwd_impl(lipasr_mlp_t m, const float* params, float* bnstat
   LP_CHECK_ARG(!dropout || (dropout->mode >= 0 && dropout->mode <= 2), "lipasr_mlp_train_fwd_bwd: dropout mode %d",
                dropout ? dropout->mode : 0);
   m->last_inv_batch = inv_batch;
-  Step s;
-  s.m = m; s.params = params; s.bnstate = bnstate; s.x = x; s.y_onehot = y_onehot;
-  s.batch = batch; s.inv_batch = inv_batch; s.dropout = dropout;
-  s.grads = grads; s.loss_rows = loss_rows; s.correct_rows = correct_rows; s.probs = probs;
-  s.st = S(stream);
-  s.part = sa.part_ext ? sa.part_ext : (m->ws + m->offPart);
-  s.bstat = sa.stat_batch > 0 ? sa.stat_batch : batch;
-  s.grad_scale = sa.grad_scale;
-  s.seg.pts = exchange_points(m);
-  s.seg.want = sa.seg;
+  Step s = make_step(m, params, bnstate, x, y_onehot, batch, inv_batch, dropout, grads, loss_rows, correct_rows, probs, stream, sa);
   rc = step_forward(s);
   if (rc == LIPASR_OK) rc = step_dx_chain(s);
   if (rc == LIPASR_OK) rc = step_weight_grads(s, dw_mode);
@@ -578,7 +589,39 @@ int lipasr_mlp_train_dw0(lipasr_mlp_t m, const float* x, int batch, float* grads
   if (rc != LIPASR_OK) return rc;
   LP_CHECK_ARG(x && grads, "lipasr_mlp_train_dw0: null argument");
   if (m->n_layers == 1) return LIPASR_OK;  // a one-layer plan's head already holds every gradient
-  return launch_gemm(1, 1, dw_args(m, 0, x, grads, batch, m->last_inv_batch), S(stream));
+  return launch_gemm(1, 1, dw_args(m, 0, x, grads, batch, m->last_inv_batch, m->ws + m->offDzLast), S(stream));
+}
+
+// The step with the loss gradient supplied from outside: the forward pass alone (the last epilogue runs without labels: logits and
+// probabilities, no loss, no gradient), then the two backward passes reading the caller's gradient at the logits.
+int lipasr_mlp_train_fwd(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, int batch,
+                         const lipasr_dropout_cfg* dropout, float* logits_out, lipasr_stream_t stream) {
+  int rc = check_call("lipasr_mlp_train_fwd", m, batch, bnstate);
+  if (rc != LIPASR_OK) return rc;
+  LP_CHECK_ARG(params && x && logits_out, "lipasr_mlp_train_fwd: null argument");
+  LP_CHECK_ARG(!dropout || (dropout->mode >= 0 && dropout->mode <= 2), "lipasr_mlp_train_fwd: dropout mode %d", dropout ? dropout->mode : 0);
+  Step s = make_step(m, params, bnstate, x, nullptr, batch, 1.0f / (float)batch, dropout, nullptr, nullptr, nullptr, nullptr, stream,
+                     SegArgs());
+  rc = step_forward(s);
+  if (rc != LIPASR_OK) return rc;
+  const size_t n = (size_t)batch * m->L[m->n_layers - 1].n_out;
+  LP_HIP(hipMemcpyAsync(logits_out, m->ws + m->offLogits, n * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+  return LIPASR_OK;
+}
+
+int lipasr_mlp_train_bwd(lipasr_mlp_t m, const float* params, const float* x, const float* dz, int batch, float dz_bound,
+                         const lipasr_dropout_cfg* dropout, float* grads, lipasr_stream_t stream) {
+  int rc = check_batch("lipasr_mlp_train_bwd", m, batch);
+  if (rc != LIPASR_OK) return rc;
+  LP_CHECK_ARG(params && x && dz && grads, "lipasr_mlp_train_bwd: null argument");
+  LP_CHECK_ARG(!dropout || (dropout->mode >= 0 && dropout->mode <= 2), "lipasr_mlp_train_bwd: dropout mode %d", dropout ? dropout->mode : 0);
+  LP_CHECK_ARG(dz_bound > 0.0f && dz_bound < INFINITY, "lipasr_mlp_train_bwd: dz_bound %g (a finite bound > 0 of max |dz|)", (double)dz_bound);
+  m->last_inv_batch = dz_bound;
+  Step s = make_step(m, params, nullptr, x, nullptr, batch, dz_bound, dropout, grads, nullptr, nullptr, nullptr, stream, SegArgs());
+  s.dz_last = dz;
+  rc = step_dx_chain(s);
+  if (rc == LIPASR_OK) rc = step_weight_grads(s, gemm_knobs().split_dw0 ? 1 : 0);
+  return rc;
 }
 
 int lipasr_mlp_train_segments(lipasr_mlp_t m, int* n_segments) {

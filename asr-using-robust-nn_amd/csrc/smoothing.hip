@@ -24,6 +24,7 @@ namespace lipasr {
 constexpr int kSmThreads = 256;
 constexpr int kSmWaves = kSmThreads / 64;
 constexpr int kSmMaxC = 32;
+extern long g_smooth_launches[2];  // smooth_train.hip (lipasr_debug_smooth_loss_launches): id 1 counts smooth_expand_kernel
 
 __global__ __launch_bounds__(kSmThreads) void smooth_expand_kernel(const float* __restrict__ x, const int* __restrict__ n_valid,
                                                                     int n, int draws, uint32_t clip0, uint32_t draw0, float sigma,
@@ -105,6 +106,7 @@ int lipasr_smooth_expand(lipasr_handle_t h, const float* x, const int* n_valid, 
   hipLaunchKernelGGL(smooth_expand_kernel, dim3((unsigned)(batch * draws)), dim3(kSmThreads), 0, S(stream), x, n_valid, n, draws,
                      clip0, draw0, sigma, seed, clip_lo, clip_hi, out);
   LP_LAUNCH_CHECK();
+  ++g_smooth_launches[1];
   return LIPASR_OK;
 }
 

@@ -84,6 +84,8 @@ PROTOTYPES = {
     "lipasr_mlp_train_fwd_bwd": (i32, [c_h, c_f, c_f, c_f, c_f, i32, f32, C.POINTER(DropoutCfg), c_f, c_f, c_f, c_f, c_s]),
     "lipasr_mlp_train_fwd_bwd_head": (i32, [c_h, c_f, c_f, c_f, c_f, i32, f32, C.POINTER(DropoutCfg), c_f, c_f, c_f, c_f, c_s]),
     "lipasr_mlp_train_dw0": (i32, [c_h, c_f, i32, c_f, c_s]),
+    "lipasr_mlp_train_fwd": (i32, [c_h, c_f, c_f, c_f, i32, C.POINTER(DropoutCfg), c_f, c_s]),
+    "lipasr_mlp_train_bwd": (i32, [c_h, c_f, c_f, c_f, i32, f32, C.POINTER(DropoutCfg), c_f, c_s]),
     "lipasr_mlp_grad_split": (i32, [c_h, C.POINTER(sz)]),
     "lipasr_mlp_train_segments": (i32, [c_h, PI]),
     "lipasr_mlp_train_segment_exchange": (i32, [c_h, i32, i32, C.POINTER(sz)]),
@@ -108,6 +110,10 @@ PROTOTYPES = {
     "lipasr_deepfool_step": (i32, [c_h, c_f, C.c_long, C.c_long, c_f, c_f, c_f, i32, i32, i32, f32, f32, f32, f32, c_f, c_f, c_f, c_f, c_s]),
     "lipasr_smooth_expand": (i32, [c_h, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, f32, u64, f32, f32, c_f, c_s]),
     "lipasr_smooth_vote": (i32, [c_h, c_f, i32, i32, i32, c_f, c_s]),
+    "lipasr_smooth_loss": (i32, [c_h, c_f, c_f, i32, i32, i32, f32, f32, f32, f32, f32, c_f, c_f, c_f, c_f, c_s]),
+    "lipasr_smooth_loss_host": (i32, [c_f, c_f, i32, i32, i32, f32, f32, f32, f32, f32, c_f, c_f, c_f, c_f]),
+    "lipasr_smooth_probit_host": (i32, [c_f, i32, c_f]),
+    "lipasr_debug_smooth_loss_launches": (i32, [i32]),
     "lipasr_smooth_noise_host": (i32, [u64, C.c_uint32, C.c_uint32, i32, C.POINTER(f32)]),
     "lipasr_genetic_breed": (i32, [c_h, c_f, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, C.c_uint32, f32, f32, f32, f32, c_f, c_s]),
     "lipasr_genetic_breed_host": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, C.c_uint32, C.c_uint32, u64, C.c_uint32, f32, f32, f32, f32, c_f]),
@@ -262,7 +268,9 @@ SINCE = {"lipasr_mlp_adam_project_product_signal": 560, "lipasr_dolphin_create":
          "lipasr_mlp_bounds_grad_host": 750, "lipasr_debug_bounds_grad_launches": 750,
          "lipasr_mlp_bounds_crown_grad_workspace": 760, "lipasr_mlp_bounds_crown_grad": 760,
          "lipasr_mlp_bounds_crown_grad_workspace_host": 760, "lipasr_mlp_bounds_crown_grad_host": 760,
-         "lipasr_debug_bounds_crown_grad_launches": 760}
+         "lipasr_debug_bounds_crown_grad_launches": 760, "lipasr_mlp_train_fwd": 770, "lipasr_mlp_train_bwd": 770,
+         "lipasr_smooth_loss": 770, "lipasr_smooth_loss_host": 770, "lipasr_smooth_probit_host": 770,
+         "lipasr_debug_smooth_loss_launches": 770}
 lib.lipasr_version.restype = i32
 _VERSION = lib.lipasr_version()
 
@@ -479,6 +487,38 @@ def smooth_noise(seed: int, clip: int, draw: int, n: int):
     out = np.zeros(max(int(n), 1), dtype=np.float32)
     check(lib.lipasr_smooth_noise_host(int(seed), int(clip), int(draw), int(n), out.ctypes.data_as(C.POINTER(f32))))
     return out[:int(n)]
+
+
+SMOOTH_LOSS_KERNELS = ("loss", "expand")  # ids of lipasr_debug_smooth_loss_launches
+
+
+def smooth_probit(q):
+    """Host-only: Phi^-1 of every entry of ``q`` as lipasr_smooth_loss computes it (numpy float64)."""
+    import numpy as np
+
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    out = np.zeros(max(q.size, 1), dtype=np.float64)
+    check(lib.lipasr_smooth_probit_host(q.ctypes.data_as(C.c_void_p), int(q.size), out.ctypes.data_as(C.c_void_p)))
+    return out[:q.size]
+
+
+def smooth_loss_host(logits, label, draws, sigma, lam, gamma, beta, scale):
+    """Host-only: lipasr_smooth_loss_host on NumPy arrays (logits float32 [clips * draws, classes], label int32 [clips]) -> the dict
+    of float32 arrays dz [clips * draws, classes], loss, correct and radius [clips] that lipasr_smooth_loss writes on the device."""
+    import numpy as np
+
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+    rows, classes = logits.shape
+    clips, draws = label.size, int(draws)
+    if rows != clips * draws:
+        raise ValueError(f"{rows} rows of logits are not {clips} clips x {draws} draws")
+    out = {"dz": np.zeros((rows, classes), dtype=np.float32)}
+    out.update({k: np.zeros(max(clips, 1), dtype=np.float32) for k in ("loss", "correct", "radius")})
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib.lipasr_smooth_loss_host(vp(logits), vp(label), clips, draws, classes, float(sigma), float(lam), float(gamma), float(beta),
+                                      float(scale), vp(out["dz"]), vp(out["loss"]), vp(out["correct"]), vp(out["radius"])))
+    return {k: (v if k == "dz" else v[:clips]) for k, v in out.items()}
 
 
 def genetic_breed_host(x0, pop, generation, seed, mutate_thresh, step, eps, *, pop_in=None, parents=None, n_valid=None, clip0=0,

@@ -6,6 +6,10 @@ sigma Phi^-1(p_A) of x, p_A a lower bound of the vote share of its majority clas
 turns the same draws into a guarantee per clip, over MFCC rows and -- where the Lipschitz bound of get_robustness_radius has
 nothing to say -- over audio.
 
+Training FOR smoothing (the reference trains on clean rows only): GaussianCrossentropy (Cohen et al.: cross-entropy on noisy
+copies) and MACERCrossentropy (Zhai et al., ICLR 2020: the certified radius of the soft smoothed classifier, maximised without an
+attack) are losses for ``Model.compile``; DESIGN.md, "Training for smoothing".
+
 Device side, per chunk of at most ``estimator.batch_limit`` noisy rows: lipasr_smooth_expand writes the noisy copies once (Philox
 counters keyed by seed, clip, draw and element, so a clip's draws depend on neither its neighbours nor the chunking), the
 estimator's ``predict_device(..., logits=True)`` classifies them, lipasr_smooth_vote adds the argmax histogram to [B, C + 1]
@@ -23,6 +27,7 @@ import torch
 from . import _native as N
 from ._rows import clip_pair, rows2d
 from .estimators import _Estimator
+from .keras import CategoricalCrossentropy
 
 _PHI_INV = NormalDist().inv_cdf
 
@@ -232,3 +237,139 @@ class Smooth:
             if binom_p_two_sided(n_a, n_b) <= alpha:
                 out[i] = order[0]
         return out
+
+
+# ------------------------------------------------------------------------------------------------ training for smoothing
+def smooth_loss(logits, label, draws, sigma, lam, gamma, beta, scale, dz, loss, correct=None, radius=None):
+    """lipasr_smooth_loss on device tensors (include/lipasr.h fixes the definitions): float32 logits [clips * draws, classes] and
+    int32 label [clips] -> dz [clips * draws, classes], loss [clips] and, where given, correct and radius [clips], all float32."""
+    rows, c = rows2d(logits, "logits", "[clips * draws, classes]")
+    clips, draws = int(label.numel()), int(draws)
+    if label.dtype != torch.int32 or not label.is_contiguous() or rows != clips * draws:
+        raise ValueError(f"label must be a contiguous int32 tensor [clips] with clips * {draws} = {rows} rows of logits")
+    for name, t, shape in (("dz", dz, (rows, c)), ("loss", loss, (clips,)), ("correct", correct, (clips,)), ("radius", radius, (clips,))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor {list(shape)}")
+    h = N.get_handle(logits.device.index)
+    N.check(N.lib.lipasr_smooth_loss(h.h, N.ptr(logits), N.ptr(label), clips, draws, c, float(sigma), float(lam), float(gamma), float(beta),
+                                     float(scale), N.ptr(dz), N.ptr(loss), N.ptr(correct), N.ptr(radius), N.stream_ptr()))
+    return dz
+
+
+class GaussianCrossentropy(CategoricalCrossentropy):
+    """Gaussian-noise training (Cohen, Rosenfeld, Kolter 2019) as a loss for ``Model.compile``: the cross-entropy of ``draws`` noisy
+    copies x + N(0, sigma^2 I) of every row, fresh at every step.  The copies are lipasr_smooth_expand's at clip0 = 0 and draw0 =
+    step * draws -- a pure function of (seed, step, row, draw, element) --, the step is the existing lipasr_mlp_train_fwd_bwd on the
+    clips * draws rows at inv_batch = 1 / (clips * draws), so it runs in every ``compute_dtype``.  ``fit`` logs the mean loss and
+    accuracy of every clip's copies.  ``sigma == 0 and draws == 1`` makes the plain step's calls.  ``clip_values``: (lo, hi) clamps the
+    noisy rows, as ``Smooth``'s.  The step counter lives here, on the host: one count per ``train_on_batch``.  ``evaluate`` and ``save``
+    of the model stay on plain cross-entropy.  Not built: data parallel, TrainPipeline."""
+
+    name = "gaussian_categorical_crossentropy"
+    certified = True  # Model.train_on_batch hands the step to train_step below
+
+    def __init__(self, sigma, draws=1, seed=0, clip_values=None):
+        if not (0.0 <= float(sigma) < math.inf):
+            raise ValueError(f"sigma = {sigma!r}: a finite number >= 0")
+        if not 1 <= int(draws) <= 64 or int(draws) != draws:
+            raise ValueError(f"draws = {draws!r}: an integer in [1, 64]")
+        if clip_values is not None and not float(clip_values[0]) <= float(clip_values[1]):
+            raise ValueError(f"clip_values = {clip_values!r}: low <= high")
+        self.sigma, self.draws, self.seed = float(sigma), int(draws), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.clip_values = None if clip_values is None else (float(clip_values[0]), float(clip_values[1]))
+        self.step = 0
+
+    def _buffers(self, model, width):
+        """The device floats of one step, once per model at its max_batch."""
+        buf = getattr(model, "_smooth_buffers", None)
+        if buf is None:
+            b, dev = model._max_batch, model._device
+            c = model._widths[-1]
+            buf = {"x": torch.zeros(b, width, device=dev), "logits": torch.zeros(b, c, device=dev), "dz": torch.zeros(b, c, device=dev)}
+            model._smooth_buffers = buf
+        return buf
+
+    def _expand(self, model, xb):
+        """The noisy copies of this step's rows [clips * draws, width] (a view of the model's buffer) and their count."""
+        clips = xb.shape[0]
+        rows = clips * self.draws
+        if rows > model._max_batch:
+            raise ValueError(f"{clips} clips x {self.draws} draws = {rows} noisy rows exceed the plan's max_batch {model._max_batch}")
+        if self.step * self.draws + self.draws > 0xFFFFFFFF:
+            raise ValueError(f"step {self.step} x {self.draws} draws is outside the 32-bit draw counter")
+        noisy = self._buffers(model, xb.shape[1])["x"][:rows]
+        smooth_expand(xb, self.draws, self.sigma, self.seed, clip0=0, draw0=self.step * self.draws, clip_values=self.clip_values, out=noisy)
+        return noisy, rows
+
+    def train_step(self, model, xb, yb, masks=None, dropout=True):
+        """One step of ``model`` under this loss; False at sigma == 0 and draws == 1 (the caller then makes the plain step's calls).
+        ``masks``: [clips * draws, width] per layer.  Stream-ordered; nothing synchronises."""
+        if self.sigma == 0.0 and self.draws == 1:
+            self.step += 1
+            return False
+        clips, m = xb.shape[0], self.draws
+        noisy, rows = self._expand(model, xb)
+        self.step += 1
+        model.train_fwd_bwd(noisy, yb.repeat_interleave(m, dim=0), inv_batch=1.0 / rows, masks=masks, dropout=dropout)
+        if m > 1:  # what fit() logs: per clip, the mean over its copies
+            for t in (model._loss_rows, model._correct_rows):
+                t[:clips] = t[:rows].view(clips, m).mean(dim=1)
+        model.apply_adam()
+        return True
+
+
+class MACERCrossentropy(GaussianCrossentropy):
+    """MACER (Zhai et al., ICLR 2020) as a loss for ``Model.compile``: per clip, over ``draws`` noisy copies,
+
+        loss = -log mean_j softmax(z_j)_y + lam_t (sigma / 2) max(0, gamma - xi) [the smoothed soft classifier is right],
+        xi = Phi^-1(q_y) - Phi^-1(max_{c != y} q_c),  q = mean_j softmax(beta z_j)
+
+    (lipasr_smooth_loss; DESIGN.md, "Training for smoothing").  The step: lipasr_smooth_expand, lipasr_mlp_train_fwd,
+    lipasr_smooth_loss at scale 1 / clips, lipasr_mlp_train_bwd, Adam.  lam_t is 0 for the first ``warmup_steps`` steps -- there the
+    loss is the cross-entropy of the smoothed soft classifier -- and ``lam`` after.  Built for ``compute_dtype="float32"`` only.
+    ``fit`` logs the loss above and the accuracy of the mean softmax.  Not built: data parallel, TrainPipeline."""
+
+    name = "macer_categorical_crossentropy"
+
+    def __init__(self, sigma, draws=16, lam=12.0, gamma=8.0, beta=16.0, warmup_steps=0, seed=0, clip_values=None):
+        super().__init__(sigma, draws=draws, seed=seed, clip_values=clip_values)
+        if not (0.0 <= float(lam) < math.inf):
+            raise ValueError(f"lam = {lam!r}: a finite number >= 0")
+        for k, v in (("gamma", gamma), ("beta", beta)):
+            if not (0.0 < float(v) < math.inf):
+                raise ValueError(f"{k} = {v!r}: a finite number > 0")
+        if int(warmup_steps) < 0:
+            raise ValueError(f"warmup_steps = {warmup_steps!r}: >= 0")
+        self.lam, self.gamma, self.beta, self.warmup_steps = float(lam), float(gamma), float(beta), int(warmup_steps)
+
+    def schedule(self, step):
+        """lam_t of the ``step``-th call of train_on_batch, counted from 0."""
+        return 0.0 if int(step) < self.warmup_steps else self.lam
+
+    def dz_bound(self, clips, lam_t):
+        """A bound of max |dz| for lipasr_mlp_train_bwd.  The classification term is at most 1 / clips per entry (w_j <= 1).  The
+        robust term has no bound that holds a priori (a_c grows like 1 / q_c): exact fp32, the only arithmetic this loss runs in,
+        ignores the figure."""
+        return (1.0 + lam_t * 0.5 * self.sigma * self.beta) / clips
+
+    def train_step(self, model, xb, yb, masks=None, dropout=True):
+        """One MACER step of ``model``; always True.  ``masks``: [clips * draws, width] per layer.  Nothing synchronises."""
+        if model._compute_dtype != "float32":
+            raise NotImplementedError(f"MACERCrossentropy is built for compute_dtype='float32', not {model._compute_dtype!r}: the fp16 "
+                                      "planes scale the gradient at the logits by a bound known beforehand, and MACER's robust "
+                                      "gradient (sqrt(2 pi) exp(Phi^-1(q)^2 / 2) grows without limit as q -> 0) has none")
+        clips, m = xb.shape[0], self.draws
+        lam_t = self.schedule(self.step)
+        noisy, rows = self._expand(model, xb)
+        self.step += 1
+        buf = self._buffers(model, xb.shape[1])
+        logits, dz = buf["logits"][:rows], buf["dz"][:rows]
+        cfg = model._dropout_cfg(masks, dropout)
+        N.check(N.lib.lipasr_mlp_train_fwd(model._plan, N.ptr(model._params), N.ptr(model._bnstate), N.ptr(noisy), rows, N.C.byref(cfg),
+                                           N.ptr(logits), N.stream_ptr()))
+        smooth_loss(logits, yb.argmax(dim=1).to(torch.int32), m, self.sigma, lam_t, self.gamma, self.beta, 1.0 / clips, dz,
+                    model._loss_rows[:clips], model._correct_rows[:clips])
+        N.check(N.lib.lipasr_mlp_train_bwd(model._plan, N.ptr(model._params), N.ptr(noisy), N.ptr(dz), rows, self.dz_bound(clips, lam_t),
+                                           N.C.byref(cfg), N.ptr(model._grads), N.stream_ptr()))
+        model.apply_adam()
+        return True

@@ -136,8 +136,49 @@ def certified_loss(args):
                            ramp_steps=args.certified_ramp)
 
 
+def add_smooth_arguments(ap):
+    """The flags of training for randomized smoothing (lipasr.smoothing.GaussianCrossentropy / MACERCrossentropy); without
+    --smooth-sigma training is unchanged.  Mutually exclusive with --certified-eps (smooth_loss refuses both through ap.error)."""
+    ap.add_argument("--smooth-sigma", type=float, default=None, help="train on copies with N(0, sigma^2) noise on the standardised "
+                                                                       "features, for lipasr.smoothing.Smooth at this sigma; default: off")
+    ap.add_argument("--smooth-method", choices=("gaussian", "macer"), default="gaussian", help="cross-entropy on the noisy copies "
+                    "(GaussianCrossentropy) or MACER's certified-radius loss (MACERCrossentropy)")
+    ap.add_argument("--smooth-draws", type=int, default=None, help="noisy copies per clip and step (default: gaussian 1, macer 16); the "
+                                                                     "model is planned for batch x draws rows")
+    ap.add_argument("--smooth-lambda", type=float, default=12.0, help="macer: weight of the robust term")
+    ap.add_argument("--smooth-gamma", type=float, default=8.0, help="macer: the hinge on Phi^-1(q_y) - Phi^-1(q_B)")
+    ap.add_argument("--smooth-beta", type=float, default=16.0, help="macer: inverse temperature of the soft votes")
+    ap.add_argument("--smooth-warmup", type=int, default=0, help="macer: steps at lambda 0 before the robust term counts")
+    return ap
+
+
+def smooth_draws(args):
+    """Noisy copies per clip the flags ask for (1 without --smooth-sigma): the drivers plan the model for batch x this many rows."""
+    if args.smooth_sigma is None:
+        return 1
+    return args.smooth_draws if args.smooth_draws is not None else (16 if args.smooth_method == "macer" else 1)
+
+
+def smooth_loss(args, ap=None):
+    """The GaussianCrossentropy or MACERCrossentropy the flags ask for, or None.  Together with --certified-eps: an argparse error
+    (``ap.error``; a ValueError without a parser)."""
+    if args.smooth_sigma is None:
+        return None
+    if getattr(args, "certified_eps", None) is not None:
+        msg = "argument --smooth-sigma: not allowed with argument --certified-eps"
+        if ap is not None:
+            ap.error(msg)
+        raise ValueError(msg)
+    from .smoothing import GaussianCrossentropy, MACERCrossentropy
+
+    if args.smooth_method == "macer":
+        return MACERCrossentropy(args.smooth_sigma, draws=smooth_draws(args), lam=args.smooth_lambda, gamma=args.smooth_gamma,
+                                 beta=args.smooth_beta, warmup_steps=args.smooth_warmup)
+    return GaussianCrossentropy(args.smooth_sigma, draws=smooth_draws(args))
+
+
 def main(argv=None):
-    ap = add_certified_arguments(argparse.ArgumentParser())
+    ap = add_smooth_arguments(add_certified_arguments(argparse.ArgumentParser()))
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--rho", type=float, default=0.1)
     ap.add_argument("--small", action="store_true", help="2048/512/512 clips instead of the reference's split sizes")
@@ -155,8 +196,9 @@ def main(argv=None):
     train_dataset = Dataset.from_tensor_slices((train_data, train_label)).shuffle(880, reshuffle_each_iteration=False).batch(512)
     val_dataset = Dataset.from_tensor_slices((val_data, val_label)).shuffle(880, reshuffle_each_iteration=False).batch(512)
 
-    model = get_model()
-    model.compile(optimizer="adam", loss=certified_loss(args) or CategoricalCrossentropy(), metrics=["accuracy"])
+    loss = smooth_loss(args, ap) or certified_loss(args) or CategoricalCrossentropy()
+    model = get_model(**({"max_batch": max(1024, 512 * smooth_draws(args))} if args.smooth_sigma is not None else {}))
+    model.compile(optimizer="adam", loss=loss, metrics=["accuracy"])
     print(model.summary())
     model.fit(train_dataset, epochs=args.epochs, validation_data=val_dataset, verbose=2,
               callbacks=[EarlyStopping(monitor="val_loss", patience=6000, restore_best_weights=False),

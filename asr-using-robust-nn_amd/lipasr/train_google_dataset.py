@@ -13,6 +13,7 @@ from .attacks import standardize_dataset
 from .keras import Dataset, EarlyStopping, ModelCheckpoint, load_model, to_categorical
 from .train_constraints import get_model_unconstrained as get_model  # noqa: F401  (train_google_dataset.py:49-74)
 from .train_constraints import add_certified_arguments, certified_arguments, certified_loss  # noqa: F401
+from .train_constraints import add_smooth_arguments, smooth_draws, smooth_loss  # noqa: F401
 from .train_constraints import load_processed_dataset, synthetic_dataset
 
 
@@ -37,7 +38,7 @@ def run(model, splits, n_classes, batch, epochs, patience, checkpoint, callbacks
     train_data, val_data, test_data = standardize_dataset(train_data, val_data, test_data)
     train_dataset = Dataset.from_tensor_slices((train_data, train_label)).shuffle(shuffle[0], reshuffle_each_iteration=False).batch(batch)
     val_dataset = Dataset.from_tensor_slices((val_data, val_label)).shuffle(shuffle[1], reshuffle_each_iteration=False).batch(batch)
-    model.compile(optimizer="adam", loss=loss or "categorical_crossentropy", metrics=["accuracy"])  # loss: an IBPCrossentropy
+    model.compile(optimizer="adam", loss=loss or "categorical_crossentropy", metrics=["accuracy"])  # loss: an IBPCrossentropy or a loss of lipasr.smoothing
     print(model.summary())
     model.fit(train_dataset, epochs=epochs, validation_data=val_dataset, verbose=2,
               callbacks=[EarlyStopping(monitor="val_loss", patience=patience, restore_best_weights=False), *callbacks,
@@ -51,15 +52,17 @@ def run(model, splits, n_classes, batch, epochs, patience, checkpoint, callbacks
 
 
 def main(argv=None):
-    ap = add_certified_arguments(argparse.ArgumentParser())
+    ap = add_smooth_arguments(add_certified_arguments(argparse.ArgumentParser()))
     ap.add_argument("--epochs", type=int, default=10000)
     ap.add_argument("--data", default=None, help="folder with the six .npy files (train_google_dataset.py:15-24); default: synthetic clips")
     ap.add_argument("--small", action="store_true", help="synthetic 2048/512/512 split")
     ap.add_argument("--checkpoint", default="bin/models/baselineV2.h5")
     args = ap.parse_args(argv)
     splits = load_processed_dataset(args.data) if args.data else synthetic_dataset(*((2048, 512, 512) if args.small else ()))
-    model, y, results = run(get_model(), splits, 10, batch=256, epochs=args.epochs, patience=200, checkpoint=args.checkpoint,
-                            loss=certified_loss(args))
+    loss = smooth_loss(args, ap) or certified_loss(args)
+    kw = {"max_batch": max(1024, 256 * smooth_draws(args))} if args.smooth_sigma is not None else {}
+    model, y, results = run(get_model(**kw), splits, 10, batch=256, epochs=args.epochs, patience=200, checkpoint=args.checkpoint,
+                            loss=loss)
     conf_matrix = confusion_matrix(splits[2][1], y, 10)
     print(conf_matrix)
     return model, results, conf_matrix

@@ -8,7 +8,7 @@
  * "/root/reference/Voice digit recogniton/") whose arithmetic it replaces.
  * INTEGRATION.md shows the ctypes binding a maintainer would add.
  *
- * lipasr_version(): 760. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
+ * lipasr_version(): 770. ABI history: 300 (round 3) -> round 4 added lipasr_flag_signal / lipasr_flag_wait and
  * lipasr_debug_chain_head without a bump -> 500: lipasr_flag_wait reports and keeps waiting (see its comment), plus the
  * round-5 entry points marked "(round 5)" below (lipasr_gemm_f16x2, lipasr_mlp_set_fuse_bn / _set_cu_budget / _exchange_errors,
  * lipasr_debug_launch_count).  510: the Lp attack entry points lipasr_lp_step, lipasr_lp_ball_init, lipasr_mlp_attack_step_lp.
@@ -63,6 +63,10 @@
  * lipasr_mlp_bounds_grad_workspace, their _host twins and the test hook lipasr_debug_bounds_grad_launches.
  * 760: CROWN-IBP certified training: lipasr_mlp_bounds_crown_grad (the backward pass of the relaxation with respect to the parameters),
  * lipasr_mlp_bounds_crown_grad_workspace, their _host twins and the test hook lipasr_debug_bounds_crown_grad_launches.
+ * (lipasr_version(): 760 was the last library without the entry points below.)
+ * 770: training for randomized smoothing: lipasr_mlp_train_fwd / lipasr_mlp_train_bwd (the training step with the loss gradient
+ * supplied from outside), lipasr_smooth_loss (the Gaussian-noise / MACER loss over the noisy copies of every clip with its gradient at
+ * the logits), the host-only lipasr_smooth_loss_host and lipasr_smooth_probit_host, and the test hook lipasr_debug_smooth_loss_launches.
  *
  * Conventions
  *   - every function returns int: 0 = LIPASR_OK, negative = LIPASR_E*; nothing
@@ -316,6 +320,33 @@ int lipasr_mlp_train_fwd_bwd_head(lipasr_mlp_t m, const float* params, float* bn
 int lipasr_mlp_train_dw0(lipasr_mlp_t m, const float* x, int batch, float* grads, lipasr_stream_t stream);
 int lipasr_mlp_grad_split(lipasr_mlp_t m, size_t* late_floats);
 
+/* The training step with the loss gradient supplied from outside (ours: Keras fuses softmax cross-entropy into train_step,
+ * train_constraints.py:94-105; a loss over SEVERAL rows -- lipasr_smooth_loss over the noisy copies of a clip -- has a gradient at
+ * the logits that is no (p - y) / B of one row).  The same kernels as lipasr_mlp_train_fwd_bwd in two calls, counted under the same
+ * ids of lipasr_debug_gemm_launches / lipasr_debug_group_launches / lipasr_debug_k2_launches; no kernel of their own.
+ *   _train_fwd: the forward pass of lipasr_mlp_train_fwd_bwd as it stands: training-mode BatchNorm (moving statistics in bnstate
+ *     updated), dropout, every activation and saved statistic kept in the plan's workspace.  The last GEMM's epilogue runs without
+ *     labels: it leaves the logits and the probabilities in the workspace (lipasr_debug_mlp_stage 5 and 6) and writes neither a loss
+ *     nor a gradient; the plan's gradient slot at the logits (stage 3 of the last layer) keeps what the last plain step left there.
+ *     logits_out [batch][classes] receives a copy of the logits (a device-to-device copy on `stream`, no kernel).  The logits, the
+ *     probabilities, the activations, the saved statistics and bnstate equal bit for bit what lipasr_mlp_train_fwd_bwd leaves for the
+ *     same inputs, in every arithmetic mode and with lipasr_mlp_set_fuse_bn 0 and 1.
+ *   _train_bwd: the dX chain and the weight gradients of lipasr_mlp_train_fwd_bwd (the first layer's as the plain entry launches
+ *     it), reading dz [batch][classes], the caller's gradient at the logits, where the plain step reads its own (p - y) * inv_batch.
+ *     It relies on the workspace of the lipasr_mlp_train_fwd JUST BEFORE it on the same plan and stream, with the same x, params,
+ *     batch and dropout -- as lipasr_mlp_train_dw0 relies on lipasr_mlp_train_fwd_bwd_head; nothing checks it.  grads is overwritten.
+ *     dz_bound: the caller's promise max |dz| <= dz_bound (finite, > 0, else LIPASR_EINVAL).  It stands wherever the plain step uses
+ *     inv_batch as the bound of the gradient at the logits: arithmetic mode 2 (the fp16 planes) derives the scale of dz from it, a
+ *     dz beyond 256 dz_bound leaves fp16's range there and turns the gradients inf / NaN (loud); a later lipasr_mlp_train_dw0 reads
+ *     it too.  Exact fp32 and bf16 ignore it.  dz given as (p - y) * inv_batch with dz_bound = inv_batch reproduces
+ *     lipasr_mlp_train_fwd_bwd's grads bit for bit.
+ * Refusals: those of lipasr_mlp_train_fwd_bwd (null plan or argument, batch outside [1, max_batch], bnstate null for a plan with
+ * BatchNorm, dropout mode).  Not built: the synchronized-BatchNorm segments and the head / dw0 split of data parallelism. */
+int lipasr_mlp_train_fwd(lipasr_mlp_t m, const float* params, float* bnstate, const float* x, int batch,
+                         const lipasr_dropout_cfg* dropout, float* logits_out /* [batch][classes] */, lipasr_stream_t stream);
+int lipasr_mlp_train_bwd(lipasr_mlp_t m, const float* params, const float* x, const float* dz /* [batch][classes] */, int batch,
+                         float dz_bound, const lipasr_dropout_cfg* dropout, float* grads, lipasr_stream_t stream);
+
 /* Synchronized BatchNorm under data parallelism (opt-in, for runs that must reproduce the single-device statistics of
  * train_constraints.py:68-83 exactly; the default is per-replica statistics): lipasr_mlp_train_fwd_bwd cut into
  * segments that end right after each GEMM whose epilogue leaves BatchNorm column partial sums -- sums of a and a^2 in the
@@ -509,6 +540,45 @@ int lipasr_smooth_vote(lipasr_handle_t h, const float* logits, int batch, int dr
 /* Host-only (no GPU needed): z_out[k] = normal4(seed, k >> 2, clip, draw)[k & 3] for k = 0 .. n - 1, the draws lipasr_smooth_expand
  * adds to clip `clip`, draw `draw` (the host's logf / sinf / cosf: equal to the device's to a few units in the last place). */
 int lipasr_smooth_noise_host(uint64_t seed, uint32_t clip, uint32_t draw, int n, float* z_out /* host [n] */);
+
+/* (ours: the reference measures accuracy under add_white_noise, attacks.py:73-86, 335-339, and trains on clean rows only)  The loss
+ * of training FOR randomized smoothing over the noisy copies of every clip, with its gradient at the logits, in one launch:
+ * Gaussian-noise training of the smoothed classifier (lam = 0) and MACER (Zhai et al., ICLR 2020; lam > 0).  Rows b * draws ..
+ * b * draws + draws - 1 of logits are the copies of clip b (lipasr_smooth_expand's layout).  Everything is computed in fp64 from the
+ * fp32 logits and rounded once to fp32 on store.  Per clip, y = label[b], m = draws, j a copy, c a class:
+ *   p_j = softmax(z_j), s_j = softmax(beta z_j) (both max-subtracted);  p^ = mean_j p_j,  q = mean_j s_j  (summed in the order of j)
+ *   L_C = -log p^_y = log m - logsumexp_j (z_jy - logsumexp_c z_jc), finite for any finite logits;
+ *         dL_C/dz_jc = -w_j (d_cy - p_jc),  w_j = exp(log p_jy - logsumexp_j log p_jy)
+ *   A = argmax_c q_c,  B = argmax_{c != y} q_c (the lowest index on a tie),  xi = Phi^-1(q_y) - Phi^-1(q_B),
+ *         Phi^-1(0) = -inf, Phi^-1(1) = +inf; classes == 1: there is no B, q_B counts as 0 and xi = +inf
+ *   the robust term is ACTIVE iff lam > 0, classes > 1, A == y, 0 < q_B, q_y < 1 and xi <= gamma:
+ *         L_R = (sigma / 2) (gamma - xi) if active, else 0
+ *         dxi/dz_jc = (beta / m) [a_y s_jy (d_cy - s_jc) - a_B s_jB (d_cB - s_jc)],  a_c = sqrt(2 pi) exp(Phi^-1(q_c)^2 / 2)
+ *   (d_cc - p_jc is taken as the sum of the OTHER classes' p_jk in the order of k, which does not cancel when p_jc is close to 1)
+ *   loss[b] = L_C + lam L_R;  dz = scale (dL_C/dz - lam (sigma / 2) dxi/dz)  (the second term only where active);
+ *   correct[b] = 1.0 where argmax_c p^_c == y (the lowest index on a tie), else 0.0;
+ *   radius[b] = (sigma / 2) xi where A == y and sigma > 0 (+inf is possible), else 0: the soft radius MACER maximises.
+ * lam = 0 and draws = 1: loss is the plain cross-entropy of the row and dz = scale (p - onehot(y)).
+ * A NaN or inf in any logit of a clip, or a label outside [0, classes): NaN in loss[b] and in every dz row of that clip, correct 0,
+ * radius 0; the other clips are untouched.
+ * LIPASR_EINVAL, before the device is touched: classes outside 1..32, draws outside 1..64, a negative clips, sigma < 0, lam < 0,
+ * gamma <= 0, beta <= 0, any of them or scale not finite; then a null handle; clips == 0 returns LIPASR_OK with nothing written;
+ * then null logits, label, dz or loss.  correct and radius may be NULL.  logits and dz may be the same buffer.
+ * Phi^-1 is Wichura's AS 241 (PPND16, 1e-16 relative) in fp64.  One launch, one workgroup of 64 threads per clip with the clip's
+ * logits, both softmaxes and its gradient rows in LDS, a lane per copy for the rows and a lane per class for the means; sums in a
+ * fixed order, no atomics, no workspace, nothing waits on another workgroup: two runs give the same bits.
+ * _host: the same arithmetic text compiled for the host (host pointers, no handle, no stream): it differs from the device by the
+ * last places of libm's exp / log / sqrt.  lipasr_smooth_probit_host: out[i] = Phi^-1(q[i]) as the kernel computes it (n >= 0).
+ * lipasr_debug_smooth_loss_launches (test hook): launches since load of 0 the loss kernel, 1 lipasr_smooth_expand's kernel; -1 for
+ * an unknown id. */
+int lipasr_smooth_loss(lipasr_handle_t h, const float* logits /* [clips * draws][classes] */, const int* label /* [clips] */,
+                       int clips, int draws, int classes, float sigma, float lam, float gamma, float beta, float scale,
+                       float* dz /* [clips * draws][classes] */, float* loss /* [clips] */, float* correct /* [clips] or NULL */,
+                       float* radius /* [clips] or NULL */, lipasr_stream_t stream);
+int lipasr_smooth_loss_host(const float* logits, const int* label, int clips, int draws, int classes, float sigma, float lam,
+                            float gamma, float beta, float scale, float* dz, float* loss, float* correct, float* radius);
+int lipasr_smooth_probit_host(const double* q /* host [n] */, int n, double* out /* host [n] */);
+int lipasr_debug_smooth_loss_launches(int id);
 
 /* (ours: the reference's black-box side is three noise sweeps, attacks.py:73-86, 145-294, none of which looks at the model's answer;
  * this is the genetic algorithm of Alzantot, Balaji, Srivastava 2018, which needs scores only)  One generation's children, written
