@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lipasr", "liblipasr.so")
 SOURCES = ["core.hip", "spectral.hip", "spectral_chain.hip", "spectral_sigma.hip", "spectral_pi.hip", "spectral_clip.hip", "gemm.hip", "gemm_frag.hip", "gemm_lds.hip", "gemm_ring.hip", "gemm_ring_group.hip", "gemm_ring2.hip", "mlp.hip", "mlp_train.hip", "mlp_infer.hip", "optim.hip", "mfcc.hip", "resample.hip", "stft_mel.hip", "mfcc_fused.hip", "mfcc_vjp.hip", "mfcc_vjp_ragged.hip", "mfcc_vjp_short.hip", "stft_bdft.hip", "lp_attack.hip", "dolphin.hip", "jacobian.hip", "psycho.hip", "deepfool.hip", "smoothing.hip", "smooth_train.hip", "genetic.hip", "apgd.hip", "square.hip", "hsj.hip", "room.hip", "universal.hip", "bounds.hip", "bounds_grad.hip", "bounds_crown_grad.hip", "warp.hip", "defence.hip"]
-HEADERS = ["common.h", "row.h", "mlp.h", "bounds.h", "bounds_grad.h", "spectral.h", "gemm.h", "gemm_device.h", "gemm_lds_tile.h", "gemm_ring_tile.h", "mfcc_tables.h", "stft.h", "mfcc_vjp.h", "mfcc_plan.h", "dolphin_tables.h", "psycho_tables.h", os.path.join("..", "..", "include", "lipasr.h")]
+HEADERS = ["common.h", "row.h", "mlp.h", "bounds.h", "bounds_grad.h", "bounds_tile.h", "spectral.h", "gemm.h", "gemm_device.h", "gemm_lds_tile.h", "gemm_ring_tile.h", "mfcc_tables.h", "stft.h", "mfcc_vjp.h", "mfcc_plan.h", "dolphin_tables.h", "psycho_tables.h", os.path.join("..", "..", "include", "lipasr.h")]
 # per-source flags.  stft_bdft.hip: the SLP vectoriser turns the kernel's scalar fp32 chains into v_pk_* with a v_mov per operand
 # pair (111 moves per frame), which also cost 39 spilled registers; measured 166 us with it, 118 us without (round 4).
 EXTRA = {"stft_bdft.hip": ["-fno-slp-vectorize"]}

@@ -1,7 +1,7 @@
 // What bounds.hip (the interval and CROWN-IBP bounds), bounds_grad.hip (the backward pass of the interval bounds) and
 // bounds_crown_grad.hip (the backward pass of the relaxation) share: the classifier's shape in the flat layout of lipasr_mlp_create,
-// the inference-mode BatchNorm affine, the slope of a ReLU line, the workspace alignment, and the two launch sequences that
-// bounds_crown_grad.hip borrows.
+// the inference-mode BatchNorm affine, the slope of a ReLU line, the workspace alignment, the checks every entry point makes, and
+// the two launch sequences that bounds_crown_grad.hip borrows.  bounds_tile.h holds the MFMA tile of the six product kernels.
 #pragma once
 #include "common.h"
 #include "row.h"
@@ -38,11 +38,13 @@ BD_HD double bd_slope(double p, float zlo, float zhi, bool& upper) {
 
 // h = s relu(z) + t in inference mode; tm bounds the magnitudes t was made of
 struct BdAff { double s, t, tm; };
-BD_HD BdAff bd_aff(const float* gamma, const float* beta, const float* mmean, const float* mvar, int j) {
-  if (!gamma) return BdAff{1.0, 0.0, 0.0};
-  const double s = (double)gamma[j] / sqrt((double)mvar[j] + (double)kBnEps);
-  const double sm = s * (double)mmean[j];
-  return BdAff{s, (double)beta[j] - sm, fabs((double)beta[j]) + fabs(sm)};
+// the BatchNorm of one layer: four nulls where the layer has none
+struct BdBn { const float *gamma, *beta, *mmean, *mvar; };
+BD_HD BdAff bd_aff(const BdBn& bn, int j) {
+  if (!bn.gamma) return BdAff{1.0, 0.0, 0.0};
+  const double s = (double)bn.gamma[j] / sqrt((double)bn.mvar[j] + (double)kBnEps);
+  const double sm = s * (double)bn.mmean[j];
+  return BdAff{s, (double)bn.beta[j] - sm, fabs((double)bn.beta[j]) + fabs(sm)};
 }
 
 struct BdShape {
@@ -71,12 +73,32 @@ inline BdBoxes bd_boxes(const BdShape& sh, int batch) {
   return x;
 }
 
+inline BdBn bd_bn(const BdShape& sh, const float* params, const float* bnstate, int l) {
+  if (!sh.bn[l]) return BdBn{nullptr, nullptr, nullptr, nullptr};
+  return BdBn{params + sh.offg[l], params + sh.offbe[l], bnstate + sh.offmm[l], bnstate + sh.offmv[l]};
+}
+
 inline size_t bd_align4(size_t v) { return (v + 3) & ~(size_t)3; }
 inline float* bd_base(float* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15); }
 
 // the shape from widths and BatchNorm flags (the host twins) / from a classifier plan; both refuse what the kernels do not take
 int bd_shape_from(const char* fn, int n_layers, const int* widths, const int* bn, BdShape* sh);
 int bd_shape_of(const char* fn, lipasr_mlp_t m, BdShape* sh);
+
+// batch >= 1 and batch x classes <= 2^24 / no written span (an output, the workspace) overlaps another one; null spans are skipped
+struct BdSpan { const void* p; size_t bytes; bool written; };
+int bd_batch_check(const char* fn, const BdShape& sh, int batch);
+int bd_check_spans(const char* fn, const BdSpan* sp, int n);
+
+// every *_workspace entry point: the shape's verdict, the checks, then the total of the family's plan
+template <class Plan>
+int bd_workspace(const char* fn, int shape_rc, const BdShape& sh, int batch, size_t* floats, Plan plan) {
+  if (shape_rc) return shape_rc;
+  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
+  *floats = plan(sh, batch).total;
+  return LIPASR_OK;
+}
 
 // bounds.hip: out[m][i] = sum_j A[m][j] W[i][j] on the tile of bounds_back_kernel, without its relaxation epilogue
 int bd_launch_product(hipStream_t st, const float* A, const float* W, int M, int K, int N, int C, float* out);

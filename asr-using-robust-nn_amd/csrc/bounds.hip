@@ -4,23 +4,24 @@
 //
 //   bounds_prep_kernel   1 launch   the input box [x - eps_b, x + eps_b] /\ [clip_lo, clip_hi] rounded outward, the row's NaN flag,
 //                                   and (norm 2) the column norms of W_1
-//   bounds_layer_kernel  L - 1      one hidden layer: a 32 x 128 tile of (W c, |W| r, |W| |c|) from ONE read of W on
-//                                   v_mfma_f32_32x32x2_f32, three accumulators per wavefront (48 accumulator registers), |W| and |c|
-//                                   formed in registers, the next chunk's loads in flight during the MFMAs; epilogue: bias, widening, store (lo_z, hi_z, S), ReLU, BatchNorm affine with
-//                                   the sign of s, outward rounding, store the next (lo, hi)
+//   bounds_layer_kernel  L - 1      one hidden layer: the tile of bounds_tile.h (narrow operand by output row, W k-major) with (W c,
+//                                   |W| r, |W| |c|) from ONE read of W, three accumulators per wavefront (48 accumulator registers),
+//                                   c and r formed as the box is staged, |W| and |c| in registers; epilogue: bias, widening, store
+//                                   (lo_z, hi_z, S), ReLU, BatchNorm affine with the sign of s, outward rounding, store the next (lo, hi)
 //   bounds_head_kernel   1          Lambda_L[b][k] = W_L[y_b] - W_L[k], the IBP margins, and the relaxation of layer L - 1
-//   bounds_back_kernel   L - 1      Lambda_{l-1} = Lambda_l W_l^T for M = batch x classes rows on the same tile; epilogue: layer
+//   bounds_back_kernel   L - 1      Lambda_{l-1} = Lambda_l W_l^T for M = batch x classes rows on the same tile, W n-major; epilogue: layer
 //                                   l - 1's BatchNorm and ReLU relaxation from row b = m / C's bounds, the constant and the slack of
 //                                   the row's 32 columns as ONE partial each (a butterfly over the 32 lanes: fixed order, no atomics)
 //   bounds_tail_kernel   1          the input reduction, the partials in index order, margin_crown and slack
 //
 // Forward L + 1 launches, backward L (none when margin_crown is null).  Every sum has one order that depends on the shapes alone:
 // the MFMA is an fmaf chain in ascending k, a row's constant is the butterfly of each 32-column tile, then the tiles in ascending
-// order, then the stages top-down.  The host twin runs the same inline functions in those orders, so host and device give the
+// order, then the stages top-down.  Head, tail and prep run one BD_HD function per element and per row (bd_head_point,
+// bd_head_finish, bd_tail_point, bd_tail_finish, bd_prep_point) that the host twin calls too, in those orders, so host and device give the
 // same values (a zero may differ in sign: the padded k steps of a tile turn a -0 accumulator into +0).
 // Rows are independent everywhere, so a NaN stays in its row; the flag of bounds_prep_kernel makes such a row's margins NaN.
 // Loads and stores are single floats, guarded: any width, any batch, any alignment.  Nothing allocates or synchronises.
-#include "bounds.h"
+#include "bounds_tile.h"
 
 // host and device must round alike, and a product that is rounded before its sum is what the error bounds below assume
 #pragma clang fp contract(off)
@@ -160,6 +161,88 @@ BD_HD double bd_red_finish(const BdRed& r, bool l2, float eps) {
   return v - kBdD * r.mag;
 }
 
+// --------------------------------------------------------------------------------- the steps the kernels and the host twin share
+// a row of bounds_prep_kernel: what makes it a NaN row apart from its x / one element: the input box, and whether x is a NaN
+BD_HD int bd_prep_row(float eps, int y, int classes) { return !(eps >= 0.0f) || y < 0 || y >= classes; }
+BD_HD int bd_prep_point(const float* x, size_t at, float eps, float clip_lo, float clip_hi, float* lo0, float* hi0) {
+  const float v = x[at];
+  bd_input_box(v, eps, clip_lo, clip_hi, lo0[at], hi0[at]);
+  return v != v;
+}
+BD_HD float bd_colnorm(double sum_sq) { return bd_up(sqrt(sum_sq) * (1.0 + kBdD)); }
+
+// the label a row is bounded for: a flagged row takes class 0 and ends as NaN
+BD_HD int bd_row_label(const int* flag, const int* y, int b) { return flag[b] ? 0 : y[b]; }
+
+// column j of row (b, k) in the head: d = W_L[j][y] - W_L[j][k] in fp64, lam its fp32 rounding (0 on the row's own class).
+// lo / hi: the box of h_{L-1} [batch][nh], x = null; one layer: the input box, and x its centre.  rx.on: the relaxation of layer
+// L - 1 turns lam into nu.  r: the terms of the IBP margin; dc, ds: the column's constant and slack
+struct BdRelaxAt {  // the layer a relaxation applies: its BatchNorm, its z box and S [batch][n], its bias [n]; on = false: none
+  bool on;
+  BdBn bn;
+  const float *zlo, *zhi, *S, *bias;
+};
+BD_HD void bd_head_point(const float* WL, int C, int nh, int b, int k, int yb, int j, const float* lo, const float* hi, const float* x,
+                         bool l2, const BdRelaxAt& rx, float& nu, double& dc, double& ds, BdRed& r) {
+  const size_t at = (size_t)b * nh + j;
+  const double d = (double)WL[(size_t)j * C + yb] - (double)WL[(size_t)j * C + k];
+  const float lam = k == yb ? 0.0f : (float)d;
+  const float l = lo[at], u = hi[at];
+  bd_red_add(r, d, l, u, l2, x ? x[at] : 0.0f);
+  // lam is the real difference rounded to fp32
+  const double H = bd_max(bd_max(fabs((double)l), fabs((double)u)), x ? fabs((double)x[at]) : 0.0);
+  dc = 0.0;
+  ds = 2.0 * kBdU * fabs((double)lam) * H;
+  nu = lam;
+  if (rx.on) {
+    double rc, rs;
+    bd_relax(lam, bd_aff(rx.bn, j), rx.zlo[at], rx.zhi[at], rx.S[at], rx.bias[j], 0, nh, nu, rc, rs);
+    dc = rc;
+    ds = ds + rs;
+  }
+}
+// the head's row (b, k) from its sums: the constant and the slack so far (acc[0 .. 1]) and the IBP margin.  own: k == y_b
+BD_HD void bd_head_finish(double csum, double ssum, const BdRed& tot, float by, float bk, bool l2, float eps, bool bad, bool own,
+                          double* acc, float* margin_ibp) {
+  const double c0 = (double)by - (double)bk;
+  acc[0] = csum + c0;
+  acc[1] = ssum + kBdD * (fabs((double)by) + fabs((double)bk) + fabs(csum));
+  const double v = bd_red_finish(tot, l2, eps) + c0 - kBdD * (fabs((double)by) + fabs((double)bk) + fabs(tot.boxmin));
+  *margin_ibp = bad ? NAN : (own ? INFINITY : bd_dn(v));
+}
+
+// column j of a row in the tail: the term of the input reduction of Lambda_0 and the subnormal steps of the product that made it
+BD_HD void bd_tail_point(const float* lam0, size_t m, int n0, int b, int j, const float* lo0, const float* hi0, const float* x, bool l2,
+                         int kin, double& ds, BdRed& r) {
+  const size_t at = (size_t)b * n0 + j;
+  const float l = lo0[at], u = hi0[at];
+  bd_red_add(r, (double)lam0[m * n0 + j], l, u, l2, x[at]);
+  ds = kin ? (kin + 1) * kBdTiny * bd_max(fabs((double)l), fabs((double)u)) : 0.0;
+}
+// the partial sums of the back stages, top-down, as the tail reads them
+struct BdStages {
+  int count;
+  int tiles[LIPASR_MAX_LAYERS];
+  const double* part[LIPASR_MAX_LAYERS];
+};
+// the tail's row m: the head's (constant, slack), the stages' partials in their fixed order, margin_crown and the slack
+BD_HD void bd_tail_finish(const double* rowacc, double ssum, const BdRed& tot, const BdStages& st, size_t m, bool l2, float eps,
+                          bool bad, bool own, float* margin_crown, float* slack) {
+  double c = rowacc[2 * m], s = rowacc[2 * m + 1] + ssum, cm = fabs(c);
+  for (int g = 0; g < st.count; ++g) {
+    const double* p = st.part[g] + 2 * m * st.tiles[g];
+    for (int t = 0; t < st.tiles[g]; ++t) {
+      c = c + p[2 * t];
+      cm = cm + fabs(p[2 * t]);
+      s = s + p[2 * t + 1];
+    }
+  }
+  const double red = bd_red_finish(tot, l2, eps);
+  s = (s + kBdD * (cm + fabs(red))) * (1.0 + kBdD);
+  margin_crown[m] = bad ? NAN : (own ? INFINITY : bd_dn(red + c - s));
+  if (slack) slack[m] = bad ? NAN : (own ? 0.0f : bd_up(s));
+}
+
 // ------------------------------------------------------------------------------------------------------------------- the plan
 // the workspace, in floats from a 16-byte boundary.  The lo family is one span [lo0 | zlo_1 | hlo_1 | zlo_2 | ...], the hi family
 // likewise: layer_lo / layer_hi are one copy each.
@@ -196,12 +279,17 @@ static BdPlan bd_plan(const BdShape& sh, int batch) {
   return p;
 }
 
-// the partial sums of the back stages, as the tail reads them
-struct BdStages {
-  int count;
-  int tiles[LIPASR_MAX_LAYERS];
-  const double* part[LIPASR_MAX_LAYERS];
-};
+// the stages of a call in the tail's order: l = L - 2 down to 1
+static BdStages bd_stages(const BdShape& sh, const BdPlan& pl, const float* ws) {
+  BdStages stg;
+  stg.count = 0;
+  for (int l = sh.L - 2; l >= 1; --l) {
+    stg.tiles[stg.count] = pl.tiles[l];
+    stg.part[stg.count] = reinterpret_cast<const double*>(ws + pl.offPart[l]);
+    ++stg.count;
+  }
+  return stg;
+}
 
 // -------------------------------------------------------------------------------------------------------------------- kernels
 constexpr int kBdNormSlices = kBdThreads / 32;
@@ -217,6 +305,20 @@ static inline double bd_sum32_host(double (&v)[32]) {
     for (int i = 0; i < o; ++i) v[i] = v[i] + v[i + o];
   return v[0];
 }
+// tot += the 32 lanes' terms of the input reduction, each field under the butterfly; on the host the lanes are r[0 .. 32)
+__device__ __forceinline__ void bd_red_sum32(BdRed& tot, const BdRed& r) {
+  tot.boxmin = tot.boxmin + bd_sum32(r.boxmin);
+  tot.dot = tot.dot + bd_sum32(r.dot);
+  tot.sq = tot.sq + bd_sum32(r.sq);
+  tot.mag = tot.mag + bd_sum32(r.mag);
+}
+static inline void bd_red_sum32_host(BdRed& tot, const BdRed (&r)[32]) {
+  for (double BdRed::*f : {&BdRed::boxmin, &BdRed::dot, &BdRed::sq, &BdRed::mag}) {
+    double v[32];
+    for (int q = 0; q < 32; ++q) v[q] = r[q].*f;
+    tot.*f = tot.*f + bd_sum32_host(v);
+  }
+}
 
 // blocks [0, batch): one row's input box and flag.  blocks from batch on (norm 2): 32 column norms of W_1 each, a column's squares
 // in 8 interleaved fp64 partial sums (thread slice s takes i = s, s + 8, ...) that meet in index order.
@@ -229,15 +331,8 @@ __global__ __launch_bounds__(kBdThreads) void bounds_prep_kernel(const float* __
   if ((int)blockIdx.x < batch) {
     const int b = blockIdx.x;
     const float e = eps[b];
-    int bad = !(e >= 0.0f) || y[b] < 0 || y[b] >= classes;
-    for (int i = tid; i < n0; i += kBdThreads) {
-      const float v = x[(size_t)b * n0 + i];
-      bad |= v != v;
-      float lo, hi;
-      bd_input_box(v, e, clip_lo, clip_hi, lo, hi);
-      lo0[(size_t)b * n0 + i] = lo;
-      hi0[(size_t)b * n0 + i] = hi;
-    }
+    int bad = bd_prep_row(e, y[b], classes);
+    for (int i = tid; i < n0; i += kBdThreads) bad |= bd_prep_point(x, (size_t)b * n0 + i, e, clip_lo, clip_hi, lo0, hi0);
     bad = __syncthreads_or(bad);
     if (tid == 0) flag[b] = bad;
   } else {
@@ -256,7 +351,7 @@ __global__ __launch_bounds__(kBdThreads) void bounds_prep_kernel(const float* __
     if (sl == 0 && j < n1) {
       double tot = parts[0][jl];
       for (int q = 1; q < kBdNormSlices; ++q) tot = tot + parts[q][jl];
-      colnorm[j] = bd_up(sqrt(tot) * (1.0 + kBdD));
+      colnorm[j] = bd_colnorm(tot);
     }
   }
 }
@@ -266,72 +361,56 @@ __global__ __launch_bounds__(kBdThreads) void bounds_prep_kernel(const float* __
 __global__ __launch_bounds__(kBdThreads) void bounds_layer_kernel(const float* __restrict__ lo, const float* __restrict__ hi,
                                                                   const float* __restrict__ x, const float* __restrict__ eps,
                                                                   const float* __restrict__ colnorm, const float* __restrict__ W,
-                                                                  const float* __restrict__ bias, const float* __restrict__ gamma,
-                                                                  const float* __restrict__ beta, const float* __restrict__ mmean,
-                                                                  const float* __restrict__ mvar, int batch, int K, int N,
+                                                                  const float* __restrict__ bias, BdBn bn, int batch, int K, int N,
                                                                   float* __restrict__ zlo, float* __restrict__ zhi,
                                                                   float* __restrict__ Sout, float* __restrict__ hlo,
                                                                   float* __restrict__ hhi) {
-  __shared__ float cs[32 * 33], rs[32 * 33], wsm[32 * 128];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  __shared__ float cs[kBtNarrow], rs[kBtNarrow], wsm[kBtWideK];
+  const BtThread t;
   const int b0 = blockIdx.x * 32, n0 = blockIdx.y * 128;
-  bd_f32x16 acc_c, acc_r, acc_s;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc_c[e] = acc_r[e] = acc_s[e] = 0.0f;
-  // the next chunk's 28 loads per thread are in flight while the current one feeds 48 MFMAs per wavefront; an element past the
-  // batch or past K is the point box 0, whose centre and radius are 0
+  bd_f32x16 acc_c = bt_zero(), acc_r = bt_zero(), acc_s = bt_zero();
+  // 28 loads per thread and chunk, 48 MFMAs per wavefront; an element past the batch or past K is the point box 0, whose centre
+  // and radius are 0.  |W| and |c| are formed in registers, the centre and the radius as the box is staged
   float lreg[4], hreg[4], xreg[4], wreg[16];
   auto fetch = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+    bt_narrow_each(t.tid, [&](int q, int row, int kk) {
       const int b = b0 + row, k = k0 + kk;
       const bool in = b < batch && k < K;
       const size_t at = (size_t)b * K + k;
       lreg[q] = in ? lo[at] : 0.0f;
       hreg[q] = in ? hi[at] : 0.0f;
       xreg[q] = (in && x) ? x[at] : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q, kk = idx >> 7, col = idx & 127;
+    });
+    bt_wide_k_each(t.tid, [&](int q, int kk, int col) {
       const int k = k0 + kk, j = n0 + col;
       wreg[q] = (k < K && j < N) ? W[(size_t)k * N + j] : 0.0f;
-    }
+    });
   };
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += 32) {
-    __syncthreads();  // the previous chunk is read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+  auto stage = [&] {
+    bt_narrow_each(t.tid, [&](int q, int row, int kk) {
       float c, r;
       if (x) bd_sym_rad(xreg[q], lreg[q], hreg[q], c, r);
       else bd_mid_rad(lreg[q], hreg[q], c, r);
-      cs[row * 33 + kk] = c;
-      rs[row * 33 + kk] = r;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) wsm[tid + kBdThreads * q] = wreg[q];
-    __syncthreads();
-    if (k0 + 32 < K) fetch(k0 + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const float c = cs[li * 33 + 2 * s + h], r = rs[li * 33 + 2 * s + h];
-      const float w = wsm[(2 * s + h) * 128 + wave * 32 + li], aw = fabsf(w);
-      acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(c, w, acc_c, 0, 0, 0);
-      acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(r, aw, acc_r, 0, 0, 0);
-      acc_s = __builtin_amdgcn_mfma_f32_32x32x2f32(fabsf(c), aw, acc_s, 0, 0, 0);
-    }
-  }
-  const int j = n0 + wave * 32 + li;
+      cs[bt_narrow_at(row, kk)] = c;
+      rs[bt_narrow_at(row, kk)] = r;
+    });
+    bt_wide_k_store(wsm, t.tid, wreg);
+  };
+  bt_pipeline(0, K, fetch, stage, [&](int s) {
+    const float c = bt_narrow_by_row(cs, t, s), r = bt_narrow_by_row(rs, t, s);
+    const float w = bt_wide_k(wsm, t, s), aw = fabsf(w);
+    acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(c, w, acc_c, 0, 0, 0);
+    acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(r, aw, acc_r, 0, 0, 0);
+    acc_s = __builtin_amdgcn_mfma_f32_32x32x2f32(fabsf(c), aw, acc_s, 0, 0, 0);
+  });
+  const int j = t.col(n0);
   if (j >= N) return;
-  const BdAff a = bd_aff(gamma, beta, mmean, mvar, j);
+  const BdAff a = bd_aff(bn, j);
   const float bj = bias[j];
   const float cn = x ? colnorm[j] : 0.0f;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int b = b0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    const int b = t.row(b0, e);
     if (b >= batch) continue;
     const size_t at = (size_t)b * N + j;
     float l, u, S, pl, pu;
@@ -351,9 +430,7 @@ __global__ __launch_bounds__(kBdThreads) void bounds_head_kernel(const float* __
                                                                  const int* __restrict__ y, const int* __restrict__ flag, int M, int C,
                                                                  int nh, const float* __restrict__ lo, const float* __restrict__ hi,
                                                                  const float* __restrict__ x, const float* __restrict__ eps, int l2,
-                                                                 int hidden, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, const float* __restrict__ mmean,
-                                                                 const float* __restrict__ mvar, const float* __restrict__ zlo,
+                                                                 int hidden, BdBn bn, const float* __restrict__ zlo,
                                                                  const float* __restrict__ zhi, const float* __restrict__ S,
                                                                  const float* __restrict__ bias, float* __restrict__ lam_out,
                                                                  double* __restrict__ rowacc,
@@ -361,10 +438,8 @@ __global__ __launch_bounds__(kBdThreads) void bounds_head_kernel(const float* __
   const int li = threadIdx.x & 31;
   const int m = blockIdx.x * (kBdThreads / 32) + (threadIdx.x >> 5);
   if (m >= M) return;  // whole 32-lane groups leave; the butterflies below stay inside a group
-  const int b = m / C, k = m % C;
-  const int bad = flag[b];
-  const int yb = bad ? 0 : y[b];
-  const float e = eps[b];
+  const int b = m / C, k = m % C, yb = bd_row_label(flag, y, b);
+  const BdRelaxAt rx{hidden != 0, bn, zlo, zhi, S, bias};
   double csum = 0.0, ssum = 0.0;
   BdRed tot{0.0, 0.0, 0.0, 0.0};
   for (int j0 = 0; j0 < nh; j0 += 32) {
@@ -372,95 +447,54 @@ __global__ __launch_bounds__(kBdThreads) void bounds_head_kernel(const float* __
     double dc = 0.0, ds = 0.0;
     BdRed r{0.0, 0.0, 0.0, 0.0};
     if (j < nh) {
-      const size_t at = (size_t)b * nh + j;
-      const double d = (double)WL[(size_t)j * C + yb] - (double)WL[(size_t)j * C + k];
-      const float lam = k == yb ? 0.0f : (float)d;
-      const float l = lo[at], u = hi[at];
-      bd_red_add(r, d, l, u, l2 != 0, x ? x[at] : 0.0f);
-      // lam is the real difference rounded to fp32
-      const double H = bd_max(bd_max(fabs((double)l), fabs((double)u)), x ? fabs((double)x[at]) : 0.0);
-      ds = 2.0 * kBdU * fabs((double)lam) * H;
-      float nu = lam;
-      if (hidden) {
-        double rc, rs;
-        bd_relax(lam, bd_aff(gamma, beta, mmean, mvar, j), zlo[at], zhi[at], S[at], bias[j], 0, nh, nu, rc, rs);
-        dc = rc;
-        ds = ds + rs;
-      }
+      float nu;
+      bd_head_point(WL, C, nh, b, k, yb, j, lo, hi, x, l2 != 0, rx, nu, dc, ds, r);
       lam_out[(size_t)m * nh + j] = nu;
     }
     csum = csum + bd_sum32(dc);
     ssum = ssum + bd_sum32(ds);
-    tot.boxmin = tot.boxmin + bd_sum32(r.boxmin);
-    tot.dot = tot.dot + bd_sum32(r.dot);
-    tot.sq = tot.sq + bd_sum32(r.sq);
-    tot.mag = tot.mag + bd_sum32(r.mag);
+    bd_red_sum32(tot, r);
   }
-  if (li == 0) {
-    const double c0 = (double)bL[yb] - (double)bL[k];
-    rowacc[2 * (size_t)m] = csum + c0;
-    rowacc[2 * (size_t)m + 1] = ssum + kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(csum));
-    const double v = bd_red_finish(tot, l2 != 0, e) + c0 - kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(tot.boxmin));
-    margin_ibp[m] = bad ? NAN : (k == yb ? INFINITY : bd_dn(v));
-  }
+  if (li == 0)
+    bd_head_finish(csum, ssum, tot, bL[yb], bL[k], l2 != 0, eps[b], flag[b] != 0, k == yb, rowacc + 2 * (size_t)m, margin_ibp + m);
 }
 
 // out[m][i] = sum_j A[m][j] W[i][j]: rows m0 .. m0 + 31 (blockIdx.x), columns i0 .. i0 + 127 (blockIdx.y).  relax: the epilogue
 // applies the layer below (its BatchNorm parameters and the z box and S of row m / C) and writes one partial per row and wavefront.
 __global__ __launch_bounds__(kBdThreads) void bounds_back_kernel(const float* __restrict__ A, const float* __restrict__ W, int M, int K,
-                                                                 int N, int C, int relax, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, const float* __restrict__ mmean,
-                                                                 const float* __restrict__ mvar, const float* __restrict__ zlo,
+                                                                 int N, int C, int relax, BdBn bn, const float* __restrict__ zlo,
                                                                  const float* __restrict__ zhi, const float* __restrict__ S,
                                                                  const float* __restrict__ bias, float* __restrict__ out,
                                                                  double* __restrict__ part, int tiles) {
-  __shared__ float as[32 * 33], wt[128 * 33];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
-  const int m0 = blockIdx.x * 32, i0 = blockIdx.y * 128;
-  bd_f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-  float areg[4], wreg[16];  // the next chunk, in flight while the current one feeds the MFMAs
+  __shared__ float as[kBtNarrow], wt[kBtWideN];
+  const BtThread t;
+  const int m0 = blockIdx.x * 32, i0 = blockIdx.y * 128, li = t.li, wave = t.wave;
+  bd_f32x16 acc = bt_zero();
+  float areg[4], wreg[16];
   auto fetch = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+    bt_narrow_each(t.tid, [&](int q, int row, int kk) {
       const int m = m0 + row, k = k0 + kk;
       areg[q] = (m < M && k < K) ? A[(size_t)m * K + k] : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q, il = idx >> 5, kk = idx & 31;
+    });
+    bt_wide_n_each(t.tid, [&](int q, int il, int kk) {
       const int i = i0 + il, k = k0 + kk;
       wreg[q] = (i < N && k < K) ? W[(size_t)i * K + k] : 0.0f;
-    }
+    });
   };
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += 32) {
-    __syncthreads();  // the previous chunk is read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q;
-      as[(idx >> 5) * 33 + (idx & 31)] = areg[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q;
-      wt[(idx >> 5) * 33 + (idx & 31)] = wreg[q];
-    }
-    __syncthreads();
-    if (k0 + 32 < K) fetch(k0 + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[li * 33 + 2 * s + h], wt[(wave * 32 + li) * 33 + 2 * s + h], acc, 0, 0, 0);
-  }
-  const int i = i0 + wave * 32 + li;
+  auto stage = [&] {
+    bt_narrow_store(as, t.tid, areg);
+    bt_wide_n_store(wt, t.tid, wreg);
+  };
+  bt_pipeline(0, K, fetch, stage, [&](int s) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bt_narrow_by_row(as, t, s), bt_wide_n(wt, t, s), acc, 0, 0, 0);
+  });
+  const int i = t.col(i0);
   const bool col = i < N;
   BdAff a{1.0, 0.0, 0.0};
-  if (relax && col) a = bd_aff(gamma, beta, mmean, mvar, i);
+  if (relax && col) a = bd_aff(bn, i);
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;  // the same for the 32 lanes of a half
+    const int m = t.row(m0, e);
     const bool ok = col && m < M;
     float nu = acc[e];
     double dc = 0.0, ds = 0.0;
@@ -483,8 +517,8 @@ __global__ __launch_bounds__(kBdThreads) void bounds_back_kernel(const float* __
 
 // the plain product out = A W^T of bounds_back_kernel (no relaxation, no partials), for the chain that bounds_crown_grad.hip keeps
 int bd_launch_product(hipStream_t st, const float* A, const float* W, int M, int K, int N, int C, float* out) {
-  hipLaunchKernelGGL(bounds_back_kernel, dim3((M + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, A, W, M, K, N, C, 0, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out, nullptr, 0);
+  hipLaunchKernelGGL(bounds_back_kernel, dim3((M + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, A, W, M, K, N, C, 0, BdBn{}, nullptr,
+                     nullptr, nullptr, nullptr, out, nullptr, 0);
   LP_LAUNCH_CHECK();
   return LIPASR_OK;
 }
@@ -499,42 +533,18 @@ __global__ __launch_bounds__(kBdThreads) void bounds_tail_kernel(const float* __
   const int li = threadIdx.x & 31;
   const int m = blockIdx.x * (kBdThreads / 32) + (threadIdx.x >> 5);
   if (m >= M) return;
-  const int b = m / C, k = m % C;
-  const int bad = flag[b];
-  const int yb = bad ? 0 : y[b];
+  const int b = m / C, k = m % C, yb = bd_row_label(flag, y, b);
   double ssum = 0.0;
   BdRed tot{0.0, 0.0, 0.0, 0.0};
   for (int j0 = 0; j0 < n0; j0 += 32) {
     const int j = j0 + li;
     double ds = 0.0;
     BdRed r{0.0, 0.0, 0.0, 0.0};
-    if (j < n0) {
-      const size_t at = (size_t)b * n0 + j;
-      const float l = lo0[at], u = hi0[at];
-      bd_red_add(r, (double)lam0[(size_t)m * n0 + j], l, u, l2 != 0, x[at]);
-      if (kin) ds = (kin + 1) * kBdTiny * bd_max(fabs((double)l), fabs((double)u));
-    }
+    if (j < n0) bd_tail_point(lam0, m, n0, b, j, lo0, hi0, x, l2 != 0, kin, ds, r);
     ssum = ssum + bd_sum32(ds);
-    tot.boxmin = tot.boxmin + bd_sum32(r.boxmin);
-    tot.dot = tot.dot + bd_sum32(r.dot);
-    tot.sq = tot.sq + bd_sum32(r.sq);
-    tot.mag = tot.mag + bd_sum32(r.mag);
+    bd_red_sum32(tot, r);
   }
-  if (li != 0) return;
-  double c = rowacc[2 * (size_t)m], s = rowacc[2 * (size_t)m + 1] + ssum, cm = fabs(c);
-  for (int g = 0; g < st.count; ++g) {
-    const double* p = st.part[g] + 2 * (size_t)m * st.tiles[g];
-    for (int t = 0; t < st.tiles[g]; ++t) {
-      c = c + p[2 * t];
-      cm = cm + fabs(p[2 * t]);
-      s = s + p[2 * t + 1];
-    }
-  }
-  const double red = bd_red_finish(tot, l2 != 0, eps[b]);
-  s = (s + kBdD * (cm + fabs(red))) * (1.0 + kBdD);
-  const bool unused = k == yb;
-  margin_crown[m] = bad ? NAN : (unused ? INFINITY : bd_dn(red + c - s));
-  if (slack) slack[m] = bad ? NAN : (unused ? 0.0f : bd_up(s));
+  if (li == 0) bd_tail_finish(rowacc, ssum, tot, st, m, l2 != 0, eps[b], flag[b] != 0, k == yb, margin_crown, slack);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host twin
@@ -546,19 +556,10 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
   float* hi = ws + pl.offHi;
   int* flag = reinterpret_cast<int*>(ws + pl.offFlag);
   float* colnorm = ws + pl.offNorm;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
   // prep
   for (int b = 0; b < batch; ++b) {
-    int bad = !(eps[b] >= 0.0f) || y[b] < 0 || y[b] >= C;
-    for (int i = 0; i < n0; ++i) {
-      const float v = x[(size_t)b * n0 + i];
-      bad |= v != v;
-      bd_input_box(v, eps[b], clip_lo, clip_hi, lo[(size_t)b * n0 + i], hi[(size_t)b * n0 + i]);
-    }
-    flag[b] = bad;
+    flag[b] = bd_prep_row(eps[b], y[b], C);
+    for (int i = 0; i < n0; ++i) flag[b] |= bd_prep_point(x, (size_t)b * n0 + i, eps[b], clip_lo, clip_hi, lo, hi);
   }
   if (l2 && L > 1) {
     const float* W1 = params + sh.offW[0];
@@ -566,12 +567,11 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
     for (int j = 0; j < n1; ++j) {
       double part[kBdNormSlices] = {};
       for (int i = 0; i < n0; ++i) {
-        const double w = W1[(size_t)i * n1 + j];
-        part[i % kBdNormSlices] = part[i % kBdNormSlices] + w * w;
+        const double w1 = W1[(size_t)i * n1 + j];
+        part[i % kBdNormSlices] = part[i % kBdNormSlices] + w1 * w1;
       }
-      double tot = part[0];
-      for (int q = 1; q < kBdNormSlices; ++q) tot = tot + part[q];
-      colnorm[j] = bd_up(sqrt(tot) * (1.0 + kBdD));
+      for (int q = 1; q < kBdNormSlices; ++q) part[0] = part[0] + part[q];
+      colnorm[j] = bd_colnorm(part[0]);
     }
   }
   // hidden layers
@@ -580,8 +580,7 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
     const int K = sh.n[l], N = sh.n[l + 1];
     const float* W = params + sh.offW[l];
     const float* bias = params + sh.offb[l];
-    const float *g, *be, *mm, *mv;
-    bnp(l, g, be, mm, mv);
+    const BdBn bn = bd_bn(sh, params, bnstate, l);
     const float* ilo = l == 0 ? lo : lo + pl.h[l - 1];
     const float* ihi = l == 0 ? hi : hi + pl.h[l - 1];
     const bool first2 = l2 && l == 0;
@@ -610,7 +609,7 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
         lo[pl.z[l] + at] = zl;
         hi[pl.z[l] + at] = zu;
         ws[pl.offS[l] + at] = S;
-        bd_post_box(zl, zu, bd_aff(g, be, mm, mv, j), lo[pl.h[l] + at], hi[pl.h[l] + at]);
+        bd_post_box(zl, zu, bd_aff(bn, j), lo[pl.h[l] + at], hi[pl.h[l] + at]);
       }
     }
   }
@@ -624,50 +623,27 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
   const bool hl2 = l2 && !hidden;
   double* rowacc = reinterpret_cast<double*>(ws + pl.offAcc);
   float* lam = ws + pl.offLam[0];
-  const float *g, *be, *mm, *mv;
-  if (hidden) bnp(L - 2, g, be, mm, mv);
-  double vc[32], vs[32], v0[32], v1[32], v2[32], v3[32];
+  BdRelaxAt rx{false, BdBn{}, nullptr, nullptr, nullptr, nullptr};
+  if (hidden) rx = BdRelaxAt{true, bd_bn(sh, params, bnstate, L - 2), lo + pl.z[L - 2], hi + pl.z[L - 2], ws + pl.offS[L - 2], params + sh.offb[L - 2]};
+  double vc[32], vs[32];
+  BdRed vr[32];
   for (int m = 0; m < M; ++m) {
-    const int b = m / C, k = m % C, bad = flag[b], yb = bad ? 0 : y[b];
+    const int b = m / C, k = m % C, yb = bd_row_label(flag, y, b);
     double csum = 0.0, ssum = 0.0;
     BdRed tot{0.0, 0.0, 0.0, 0.0};
     for (int j0 = 0; j0 < nh; j0 += 32) {
       for (int q = 0; q < 32; ++q) {
         const int j = j0 + q;
-        double dc = 0.0, ds = 0.0;
-        BdRed rr{0.0, 0.0, 0.0, 0.0};
-        if (j < nh) {
-          const size_t at = (size_t)b * nh + j;
-          const double d = (double)WL[(size_t)j * C + yb] - (double)WL[(size_t)j * C + k];
-          const float la = k == yb ? 0.0f : (float)d;
-          const float l = hl[at], u = hu[at];
-          bd_red_add(rr, d, l, u, hl2, hidden ? 0.0f : x[at]);
-          const double H = bd_max(bd_max(fabs((double)l), fabs((double)u)), hidden ? 0.0 : fabs((double)x[at]));
-          ds = 2.0 * kBdU * fabs((double)la) * H;
-          float nu = la;
-          if (hidden) {
-            double rc, rs;
-            bd_relax(la, bd_aff(g, be, mm, mv, j), lo[pl.z[L - 2] + at], hi[pl.z[L - 2] + at], ws[pl.offS[L - 2] + at],
-                     params[sh.offb[L - 2] + j], 0, nh, nu, rc, rs);
-            dc = rc;
-            ds = ds + rs;
-          }
-          lam[(size_t)m * nh + j] = nu;
-        }
-        vc[q] = dc; vs[q] = ds; v0[q] = rr.boxmin; v1[q] = rr.dot; v2[q] = rr.sq; v3[q] = rr.mag;
+        vc[q] = vs[q] = 0.0;
+        vr[q] = BdRed{0.0, 0.0, 0.0, 0.0};
+        if (j < nh)
+          bd_head_point(WL, C, nh, b, k, yb, j, hl, hu, hidden ? nullptr : x, hl2, rx, lam[(size_t)m * nh + j], vc[q], vs[q], vr[q]);
       }
       csum = csum + bd_sum32_host(vc);
       ssum = ssum + bd_sum32_host(vs);
-      tot.boxmin = tot.boxmin + bd_sum32_host(v0);
-      tot.dot = tot.dot + bd_sum32_host(v1);
-      tot.sq = tot.sq + bd_sum32_host(v2);
-      tot.mag = tot.mag + bd_sum32_host(v3);
+      bd_red_sum32_host(tot, vr);
     }
-    const double c0 = (double)bL[yb] - (double)bL[k];
-    rowacc[2 * (size_t)m] = csum + c0;
-    rowacc[2 * (size_t)m + 1] = ssum + kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(csum));
-    const double v = bd_red_finish(tot, hl2, eps[b]) + c0 - kBdD * (fabs((double)bL[yb]) + fabs((double)bL[k]) + fabs(tot.boxmin));
-    margin_ibp[m] = bad ? NAN : (k == yb ? INFINITY : bd_dn(v));
+    bd_head_finish(csum, ssum, tot, bL[yb], bL[k], hl2, eps[b], flag[b] != 0, k == yb, rowacc + 2 * (size_t)m, margin_ibp + m);
   }
   if (!margin_crown) return;
   // back
@@ -679,7 +655,7 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
     const float* A = ws + pl.offLam[cur];
     float* out = ws + pl.offLam[cur ^ 1];
     const bool relax = l > 0;
-    if (relax) bnp(l - 1, g, be, mm, mv);
+    const BdBn bn = relax ? bd_bn(sh, params, bnstate, l - 1) : BdBn{};
     double* part = relax ? reinterpret_cast<double*>(ws + pl.offPart[l]) : nullptr;
     const int tiles = pl.tiles[l];
     for (int m = 0; m < M; ++m) {
@@ -699,7 +675,7 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
           if (i < N) {
             const size_t at = (size_t)(m / C) * N + i;
             float nu;
-            bd_relax(acc[i], bd_aff(g, be, mm, mv, i), lo[pl.z[l - 1] + at], hi[pl.z[l - 1] + at], ws[pl.offS[l - 1] + at],
+            bd_relax(acc[i], bd_aff(bn, i), lo[pl.z[l - 1] + at], hi[pl.z[l - 1] + at], ws[pl.offS[l - 1] + at],
                      params[sh.offb[l - 1] + i], K, N, nu, dc, ds);
             out[(size_t)m * N + i] = nu;
           }
@@ -714,42 +690,22 @@ static void bd_host(const BdShape& sh, const BdPlan& pl, const float* params, co
   // tail
   const float* lam0 = ws + pl.offLam[cur];
   const int kin = hidden ? sh.n[1] : 0;
+  const BdStages stg = bd_stages(sh, pl, ws);
   for (int m = 0; m < M; ++m) {
-    const int b = m / C, k = m % C, bad = flag[b], yb = bad ? 0 : y[b];
+    const int b = m / C, k = m % C, yb = bd_row_label(flag, y, b);
     double ssum = 0.0;
     BdRed tot{0.0, 0.0, 0.0, 0.0};
     for (int j0 = 0; j0 < n0; j0 += 32) {
       for (int q = 0; q < 32; ++q) {
         const int j = j0 + q;
-        double ds = 0.0;
-        BdRed rr{0.0, 0.0, 0.0, 0.0};
-        if (j < n0) {
-          const size_t at = (size_t)b * n0 + j;
-          bd_red_add(rr, (double)lam0[(size_t)m * n0 + j], lo[at], hi[at], l2, x[at]);
-          if (kin) ds = (kin + 1) * kBdTiny * bd_max(fabs((double)lo[at]), fabs((double)hi[at]));
-        }
-        vs[q] = ds; v0[q] = rr.boxmin; v1[q] = rr.dot; v2[q] = rr.sq; v3[q] = rr.mag;
+        vs[q] = 0.0;
+        vr[q] = BdRed{0.0, 0.0, 0.0, 0.0};
+        if (j < n0) bd_tail_point(lam0, m, n0, b, j, lo, hi, x, l2, kin, vs[q], vr[q]);
       }
       ssum = ssum + bd_sum32_host(vs);
-      tot.boxmin = tot.boxmin + bd_sum32_host(v0);
-      tot.dot = tot.dot + bd_sum32_host(v1);
-      tot.sq = tot.sq + bd_sum32_host(v2);
-      tot.mag = tot.mag + bd_sum32_host(v3);
+      bd_red_sum32_host(tot, vr);
     }
-    double cc = rowacc[2 * (size_t)m], s = rowacc[2 * (size_t)m + 1] + ssum, cm = fabs(cc);
-    for (int l = L - 2; l >= 1; --l) {
-      const double* p = reinterpret_cast<const double*>(ws + pl.offPart[l]) + 2 * (size_t)m * pl.tiles[l];
-      for (int t = 0; t < pl.tiles[l]; ++t) {
-        cc = cc + p[2 * t];
-        cm = cm + fabs(p[2 * t]);
-        s = s + p[2 * t + 1];
-      }
-    }
-    const double red = bd_red_finish(tot, l2, eps[b]);
-    s = (s + kBdD * (cm + fabs(red))) * (1.0 + kBdD);
-    const bool unused = k == yb;
-    margin_crown[m] = bad ? NAN : (unused ? INFINITY : bd_dn(red + cc - s));
-    if (slack) slack[m] = bad ? NAN : (unused ? 0.0f : bd_up(s));
+    bd_tail_finish(rowacc, ssum, tot, stg, m, l2, eps[b], flag[b] != 0, k == yb, margin_crown, slack);
   }
 }
 
@@ -801,6 +757,19 @@ int bd_shape_of(const char* fn, lipasr_mlp_t m, BdShape* sh) {
   return LIPASR_OK;
 }
 
+int bd_batch_check(const char* fn, const BdShape& sh, int batch) {
+  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  return LIPASR_OK;
+}
+
+int bd_check_spans(const char* fn, const BdSpan* sp, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j)
+      LP_CHECK_ARG(!((sp[i].written || sp[j].written) && sp[i].p && sp[j].p && spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes)),
+                   "%s: an output or the workspace overlaps another argument", fn);
+  return LIPASR_OK;
+}
+
 static int bd_check(const char* fn, const BdShape& sh, const BdPlan& pl, const float* params, const float* bnstate, const float* x,
                     const float* eps, float norm, float clip_lo, float clip_hi, const int* y, int batch, const float* ws,
                     size_t ws_floats, const float* margin_ibp, const float* margin_crown, const float* slack, const float* layer_lo,
@@ -814,17 +783,11 @@ static int bd_check(const char* fn, const BdShape& sh, const BdPlan& pl, const f
   LP_CHECK_ARG(ws_floats >= pl.total, "%s: workspace of %zu floats; %zu are needed", fn, ws_floats, pl.total);
   *l2 = norm == 2.0f;
   const size_t B = batch, C = sh.n[sh.L];
-  struct Span { const void* p; size_t bytes; bool written; };
-  const Span sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {x, B * sh.n[0] * 4, false},
-                     {eps, B * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true}, {margin_ibp, B * C * 4, true},
-                     {margin_crown, margin_crown ? B * C * 4 : 0, true}, {slack, slack ? B * C * 4 : 0, true},
-                     {layer_lo, layer_lo ? pl.fam * 4 : 0, true}, {layer_hi, layer_hi ? pl.fam * 4 : 0, true}};
-  const int ns = sizeof(sp) / sizeof(sp[0]);
-  for (int i = 0; i < ns; ++i)
-    for (int j = i + 1; j < ns; ++j)
-      LP_CHECK_ARG(!((sp[i].written || sp[j].written) && sp[i].p && sp[j].p && spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes)),
-                   "%s: an output or the workspace overlaps another argument", fn);
-  return LIPASR_OK;
+  const BdSpan sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {x, B * sh.n[0] * 4, false},
+                       {eps, B * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true}, {margin_ibp, B * C * 4, true},
+                       {margin_crown, margin_crown ? B * C * 4 : 0, true}, {slack, slack ? B * C * 4 : 0, true},
+                       {layer_lo, layer_lo ? pl.fam * 4 : 0, true}, {layer_hi, layer_hi ? pl.fam * 4 : 0, true}};
+  return bd_check_spans(fn, sp, sizeof(sp) / sizeof(sp[0]));
 }
 
 }  // namespace lipasr
@@ -838,21 +801,13 @@ long lipasr_debug_bounds_launches(int kernel) { return (kernel >= 0 && kernel < 
 int lipasr_mlp_bounds_workspace(lipasr_mlp_t m, int batch, size_t* floats) {
   const char* fn = "lipasr_mlp_bounds_workspace";
   BdShape sh;
-  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
-  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
-  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
-  *floats = bd_plan(sh, batch).total;
-  return LIPASR_OK;
+  return bd_workspace(fn, bd_shape_of(fn, m, &sh), sh, batch, floats, bd_plan);
 }
 
 int lipasr_mlp_bounds_workspace_host(int n_layers, const int* widths, int batch, size_t* floats) {
   const char* fn = "lipasr_mlp_bounds_workspace_host";
   BdShape sh;
-  if (int rc = bd_shape_from(fn, n_layers, widths, nullptr, &sh)) return rc;
-  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
-  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
-  *floats = bd_plan(sh, batch).total;
-  return LIPASR_OK;
+  return bd_workspace(fn, bd_shape_from(fn, n_layers, widths, nullptr, &sh), sh, batch, floats, bd_plan);
 }
 
 int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate, const float* x, const float* eps, float norm,
@@ -861,7 +816,7 @@ int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate,
   const char* fn = "lipasr_mlp_bounds";
   BdShape sh;
   if (int rc = bd_shape_of(fn, m, &sh)) return rc;
-  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
   const BdPlan pl = bd_plan(sh, batch);
   bool l2 = false;
   if (int rc = bd_check(fn, sh, pl, params, bnstate, x, eps, norm, clip_lo, clip_hi, y, batch, workspace, workspace_floats, margin_ibp,
@@ -876,11 +831,6 @@ int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate,
   int* flag = reinterpret_cast<int*>(ws + pl.offFlag);
   float* colnorm = ws + pl.offNorm;
   const bool hidden = L > 1;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
-  const float *g, *be, *mm, *mv;
   {
     const bool norms = l2 && hidden;
     const int n1 = hidden ? sh.n[1] : 0;
@@ -892,11 +842,10 @@ int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate,
   }
   for (int l = 0; l + 1 < L; ++l) {
     const int K = sh.n[l], N = sh.n[l + 1];
-    bnp(l, g, be, mm, mv);
     const bool first2 = l2 && l == 0;
     hipLaunchKernelGGL(bounds_layer_kernel, dim3((batch + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st,
                        l == 0 ? lo : lo + pl.h[l - 1], l == 0 ? hi : hi + pl.h[l - 1], first2 ? x : nullptr, eps, colnorm,
-                       params + sh.offW[l], params + sh.offb[l], g, be, mm, mv, batch, K, N, lo + pl.z[l], hi + pl.z[l],
+                       params + sh.offW[l], params + sh.offb[l], bd_bn(sh, params, bnstate, l), batch, K, N, lo + pl.z[l], hi + pl.z[l],
                        ws + pl.offS[l], lo + pl.h[l], hi + pl.h[l]);
     LP_LAUNCH_CHECK();
     ++g_bounds_launches[BD_LAYER];
@@ -905,11 +854,9 @@ int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate,
   const unsigned rowblocks = (unsigned)((M + kBdThreads / 32 - 1) / (kBdThreads / 32));
   {
     const int nh = sh.n[L - 1];
-    g = be = mm = mv = nullptr;
-    if (hidden) bnp(L - 2, g, be, mm, mv);
     hipLaunchKernelGGL(bounds_head_kernel, dim3(rowblocks), dim3(kBdThreads), 0, st, params + sh.offW[L - 1], params + sh.offb[L - 1], y,
                        flag, M, C, nh, hidden ? lo + pl.h[L - 2] : lo, hidden ? hi + pl.h[L - 2] : hi, hidden ? nullptr : x, eps,
-                       (l2 && !hidden) ? 1 : 0, hidden ? 1 : 0, g, be, mm, mv, hidden ? lo + pl.z[L - 2] : nullptr,
+                       (l2 && !hidden) ? 1 : 0, hidden ? 1 : 0, hidden ? bd_bn(sh, params, bnstate, L - 2) : BdBn{}, hidden ? lo + pl.z[L - 2] : nullptr,
                        hidden ? hi + pl.z[L - 2] : nullptr, hidden ? ws + pl.offS[L - 2] : nullptr,
                        hidden ? params + sh.offb[L - 2] : nullptr, ws + pl.offLam[0], rowacc,
                        margin_ibp);
@@ -918,30 +865,21 @@ int lipasr_mlp_bounds(lipasr_mlp_t m, const float* params, const float* bnstate,
   }
   if (margin_crown) {
     int cur = 0;
-    BdStages stg;
-    stg.count = 0;
     for (int l = L - 2; l >= 0; --l) {
       const int K = sh.n[l + 1], N = sh.n[l];
       const bool relax = l > 0;
-      g = be = mm = mv = nullptr;
-      if (relax) bnp(l - 1, g, be, mm, mv);
       double* part = relax ? reinterpret_cast<double*>(ws + pl.offPart[l]) : nullptr;
       hipLaunchKernelGGL(bounds_back_kernel, dim3((M + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, ws + pl.offLam[cur],
-                         params + sh.offW[l], M, K, N, C, relax ? 1 : 0, g, be, mm, mv, relax ? lo + pl.z[l - 1] : nullptr,
+                         params + sh.offW[l], M, K, N, C, relax ? 1 : 0, relax ? bd_bn(sh, params, bnstate, l - 1) : BdBn{}, relax ? lo + pl.z[l - 1] : nullptr,
                          relax ? hi + pl.z[l - 1] : nullptr, relax ? ws + pl.offS[l - 1] : nullptr,
                          relax ? params + sh.offb[l - 1] : nullptr, ws + pl.offLam[cur ^ 1], part,
                          pl.tiles[l]);
       LP_LAUNCH_CHECK();
       ++g_bounds_launches[BD_BACK];
-      if (relax) {
-        stg.tiles[stg.count] = pl.tiles[l];
-        stg.part[stg.count] = part;
-        ++stg.count;
-      }
       cur ^= 1;
     }
     hipLaunchKernelGGL(bounds_tail_kernel, dim3(rowblocks), dim3(kBdThreads), 0, st, ws + pl.offLam[cur], y, flag, M, C, n0,
-                       hidden ? sh.n[1] : 0, lo, hi, x, eps, l2 ? 1 : 0, rowacc, stg, margin_crown, slack);
+                       hidden ? sh.n[1] : 0, lo, hi, x, eps, l2 ? 1 : 0, rowacc, bd_stages(sh, pl, ws), margin_crown, slack);
     LP_LAUNCH_CHECK();
     ++g_bounds_launches[BD_TAIL];
   }
@@ -957,7 +895,7 @@ int lipasr_mlp_bounds_host(int n_layers, const int* widths, const int* bn, const
   const char* fn = "lipasr_mlp_bounds_host";
   BdShape sh;
   if (int rc = bd_shape_from(fn, n_layers, widths, bn, &sh)) return rc;
-  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
   const BdPlan pl = bd_plan(sh, batch);
   bool l2 = false;
   if (int rc = bd_check(fn, sh, pl, params, bnstate, x, eps, norm, clip_lo, clip_hi, y, batch, workspace, workspace_floats, margin_ibp,

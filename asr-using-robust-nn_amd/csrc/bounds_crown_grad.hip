@@ -14,14 +14,15 @@
 //   cg_soft_kernel     1 launch   a thread per row b: loss_rows and g
 //   cg_relax_kernel    max(L-1,1) the chain again, every level kept: Lambda_{L-1} from W_L, and nu_l from Lambda_l and row m / C's box
 //   bounds_back_kernel L - 1      (bounds.hip, bd_launch_product) Lambda_{l-1} = nu_l W_l^T
-//   cg_adjoint_kernel  L - 1      ascending: G_nu = G_Lambda_{l-1} W_l + g b_l on a 32 x 128 tile of v_mfma_f32_32x32x2_f32, the next chunk's
-//                                 loads in flight during the MFMAs; for the first layer the operand g sel is formed as it is loaded
-//                                 from Lambda_0 and the input box.  Epilogue: sigma again from the box and the stored Lambda_l, G_Lambda_l,
-//                                 and per element the term of ds and of the two injections
-//   cg_wgrad_kernel    L - 1      partial products of dW_l = G_Lambda_{l-1}^T nu_l, k = M split over blockIdx.z in spans of kCgSpan rows
+//   cg_adjoint_kernel  L - 1      ascending: G_nu = G_Lambda_{l-1} W_l + g b_l on the tile of bounds_tile.h (narrow operand by output
+//                                 row, W k-major); for the first layer the operand g sel is formed as it is loaded from Lambda_0
+//                                 and the input box (cg_operand).  Epilogue: sigma again from the box and the stored Lambda_l,
+//                                 G_Lambda_l, and per element the term of ds and of the two injections
+//   cg_wgrad_kernel    L - 1      partial products of dW_l = G_Lambda_{l-1}^T nu_l on the same tile (the same operand by reduction
+//                                 row, nu k-major), k = M split over blockIdx.z in spans of kCgSpan rows: the pipeline's [begin, end)
 //   cg_wreduce_kernel  L - 1      the partials in index order, the two scales, the store into grads
 //   cg_colsum_kernel   L - 1      the column sums over M behind db_l, dgamma_l, dbeta_l: 8 columns and one span of kCgSpan rows a block, the
-//                                 span in 32 interleaved fp64 slices that meet in index order; one fp64 partial per span and column
+//                                 span through bg_sliced_sum (bounds_grad.h); one fp64 partial per span and column
 //   cg_finish_kernel   L - 1      blocks [0, ceil(batch n_l / 256)): inj_lo, inj_hi [batch][n_l], a row's classes in index order, in fp64;
 //                                 the blocks after them: the spans' partials in index order, db_l, dgamma_l, dbeta_l and their scales
 //   cg_head_kernel     1          dW_L and db_L from G_Lambda_{L-1} and g
@@ -34,6 +35,7 @@
 // gradient, Lambda_0 > 0 selects lo.  A NaN row makes its loss and the whole gradient NaN.
 // Loads and stores are single floats, guarded: any width, any batch, any alignment.  Nothing allocates or synchronises.
 #include "bounds_grad.h"
+#include "bounds_tile.h"
 
 // host and device must round alike
 #pragma clang fp contract(off)
@@ -75,6 +77,16 @@ BD_HD float cg_nu(float lam, double s, float zlo, float zhi) {
 }
 // an element of G_Lambda_0 = g sel: never stored
 BD_HD float cg_a0(float g, float lam0, float lo, float hi) { return g * (lam0 > 0.0f ? lo : hi); }
+// element (m, i) of the operand A [M][K] of the adjoint and of the weight gradient: G_Lambda_{l-1} as stored, or (lam0 != null, the
+// first layer) g sel formed here from Lambda_0 and the input box; 0 from row mend and from unit K on
+BD_HD float cg_operand(const float* A, const float* lam0, const float* lo0, const float* hi0, const float* g, int C, int K, int m, int mend,
+                       int i) {
+  if (m >= mend || i >= K) return 0.0f;
+  const size_t at = (size_t)m * K + i;
+  if (!lam0) return A[at];
+  const size_t bx = (size_t)(m / C) * K + i;
+  return cg_a0(g[m], lam0[at], lo0[bx], hi0[bx]);
+}
 
 // one element of the adjoint's epilogue.  acc = (G_Lambda_{l-1} W_l)[m][j]; out: G_Lambda_l, the term of ds, the terms of the injections
 BD_HD void cg_point(float acc, float g, float lam, const BdAff& a, float zlo, float zhi, float bias, float& gl, float& es, float& ilo,
@@ -164,9 +176,7 @@ __global__ __launch_bounds__(kBdThreads) void cg_soft_kernel(const float* __rest
 
 // an element (m, j) a thread.  WL != null: the top level, Lambda is formed and stored; zlo != null: nu is formed and stored
 __global__ __launch_bounds__(kBdThreads) void cg_relax_kernel(const float* __restrict__ WL, const int* __restrict__ y, int M, int C, int N,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const float* __restrict__ mmean, const float* __restrict__ mvar,
-                                                              const float* __restrict__ zlo, const float* __restrict__ zhi,
+                                                              BdBn bn, const float* __restrict__ zlo, const float* __restrict__ zhi,
                                                               float* __restrict__ lam, float* __restrict__ nu) {
   const size_t at = (size_t)blockIdx.x * kBdThreads + threadIdx.x;
   if (at >= (size_t)M * N) return;
@@ -180,7 +190,7 @@ __global__ __launch_bounds__(kBdThreads) void cg_relax_kernel(const float* __res
   }
   if (zlo) {
     const size_t bx = (size_t)b * N + j;
-    nu[at] = cg_nu(v, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[bx], zhi[bx]);
+    nu[at] = cg_nu(v, bd_aff(bn, j).s, zlo[bx], zhi[bx]);
   }
 }
 
@@ -189,72 +199,42 @@ __global__ __launch_bounds__(kBdThreads) void cg_relax_kernel(const float* __res
 __global__ __launch_bounds__(kBdThreads) void cg_adjoint_kernel(const float* __restrict__ A, const float* __restrict__ lam0,
                                                                 const float* __restrict__ lo0, const float* __restrict__ hi0,
                                                                 const float* __restrict__ g, const float* __restrict__ W,
-                                                                const float* __restrict__ bias, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, const float* __restrict__ mmean,
-                                                                const float* __restrict__ mvar, const float* __restrict__ zlo,
+                                                                const float* __restrict__ bias, BdBn bn, const float* __restrict__ zlo,
                                                                 const float* __restrict__ zhi, const float* __restrict__ lam, int M, int C,
                                                                 int K, int N, float* __restrict__ gl, float* __restrict__ es,
                                                                 float* __restrict__ ilo, float* __restrict__ ihi) {
-  __shared__ float as[32 * 33], wsm[32 * 128];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  __shared__ float as[kBtNarrow], wsm[kBtWideK];
+  const BtThread t;
   const int m0 = blockIdx.x * 32, n0 = blockIdx.y * 128;
-  bd_f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-  float areg[4], wreg[16];  // the next chunk, in flight while the current one feeds the MFMAs
+  bd_f32x16 acc = bt_zero();
+  float areg[4], wreg[16];
   auto fetch = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
-      const int m = m0 + row, k = k0 + kk;
-      float v = 0.0f;
-      if (m < M && k < K) {
-        const size_t at = (size_t)m * K + k;
-        if (lam0) {
-          const size_t bx = (size_t)(m / C) * K + k;
-          v = cg_a0(g[m], lam0[at], lo0[bx], hi0[bx]);
-        } else {
-          v = A[at];
-        }
-      }
-      areg[q] = v;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q, kk = idx >> 7, col = idx & 127;
+    bt_narrow_each(t.tid, [&](int q, int row, int kk) { areg[q] = cg_operand(A, lam0, lo0, hi0, g, C, K, m0 + row, M, k0 + kk); });
+    bt_wide_k_each(t.tid, [&](int q, int kk, int col) {
       const int k = k0 + kk, j = n0 + col;
       wreg[q] = (k < K && j < N) ? W[(size_t)k * N + j] : 0.0f;
-    }
+    });
   };
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += 32) {
-    __syncthreads();  // the previous chunk is read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q;
-      as[(idx >> 5) * 33 + (idx & 31)] = areg[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) wsm[tid + kBdThreads * q] = wreg[q];
-    __syncthreads();
-    if (k0 + 32 < K) fetch(k0 + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[li * 33 + 2 * s + h], wsm[(2 * s + h) * 128 + wave * 32 + li], acc, 0, 0, 0);
-  }
-  const int j = n0 + wave * 32 + li;
+  auto stage = [&] {
+    bt_narrow_store(as, t.tid, areg);
+    bt_wide_k_store(wsm, t.tid, wreg);
+  };
+  bt_pipeline(0, K, fetch, stage, [&](int s) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bt_narrow_by_row(as, t, s), bt_wide_k(wsm, t, s), acc, 0, 0, 0);
+  });
+  const int j = t.col(n0);
   if (j >= N) return;
-  const BdAff a = bd_aff(gamma, beta, mmean, mvar, j);
+  const BdAff a = bd_aff(bn, j);
   const float bj = bias[j];
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    const int m = t.row(m0, e);
     if (m >= M) continue;
     const size_t at = (size_t)m * N + j, bx = (size_t)(m / C) * N + j;
     float vg, vs, vl, vh;
     cg_point(acc[e], g[m], lam[at], a, zlo[bx], zhi[bx], bj, vg, vs, vl, vh);
     gl[at] = vg;
-    if (gamma) es[at] = vs;
+    if (bn.gamma) es[at] = vs;
     ilo[at] = vl;
     ihi[at] = vh;
   }
@@ -266,63 +246,33 @@ __global__ __launch_bounds__(kBdThreads) void cg_wgrad_kernel(const float* __res
                                                               const float* __restrict__ lo0, const float* __restrict__ hi0,
                                                               const float* __restrict__ g, const float* __restrict__ nu, int M, int C, int K,
                                                               int N, float* __restrict__ part) {
-  __shared__ float as[32 * 33], ns[32 * 128];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  __shared__ float as[kBtNarrow], ns[kBtWideK];
+  const BtThread t;
   const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 128;
   const int mbeg = blockIdx.z * kCgSpan, mend = min(M, mbeg + kCgSpan);
-  bd_f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+  bd_f32x16 acc = bt_zero();
   // a row past the span, a unit past K and a column past N read as 0
   float areg[4], nreg[16];
   auto fetch = [&](int r0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, rr = idx >> 5, ii = idx & 31;
-      const int m = r0 + rr, i = i0 + ii;
-      float v = 0.0f;
-      if (m < mend && i < K) {
-        const size_t at = (size_t)m * K + i;
-        if (lam0) {
-          const size_t bx = (size_t)(m / C) * K + i;
-          v = cg_a0(g[m], lam0[at], lo0[bx], hi0[bx]);
-        } else {
-          v = A[at];
-        }
-      }
-      areg[q] = v;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q, rr = idx >> 7, col = idx & 127;
+    bt_narrow_each(t.tid, [&](int q, int rr, int ii) { areg[q] = cg_operand(A, lam0, lo0, hi0, g, C, K, r0 + rr, mend, i0 + ii); });
+    bt_wide_k_each(t.tid, [&](int q, int rr, int col) {
       const int m = r0 + rr, j = j0 + col;
       nreg[q] = (m < mend && j < N) ? nu[(size_t)m * N + j] : 0.0f;
-    }
+    });
   };
-  fetch(mbeg);
-  for (int r0 = mbeg; r0 < mend; r0 += 32) {
-    __syncthreads();  // the previous chunk is read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q;
-      as[(idx >> 5) * 33 + (idx & 31)] = areg[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) ns[tid + kBdThreads * q] = nreg[q];
-    __syncthreads();
-    if (r0 + 32 < mend) fetch(r0 + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int rr = 2 * s + h;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[rr * 33 + li], ns[rr * 128 + wave * 32 + li], acc, 0, 0, 0);
-    }
-  }
-  const int j = j0 + wave * 32 + li;
+  auto stage = [&] {
+    bt_narrow_store(as, t.tid, areg);
+    bt_wide_k_store(ns, t.tid, nreg);
+  };
+  bt_pipeline(mbeg, mend, fetch, stage, [&](int s) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bt_narrow_by_k(as, t, s), bt_wide_k(ns, t, s), acc, 0, 0, 0);
+  });
+  const int j = t.col(j0);
   if (j >= N) return;
   float* out = part + (size_t)blockIdx.z * K * N;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int i = i0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    const int i = t.row(i0, e);
     if (i < K) out[(size_t)i * N + j] = acc[e];
   }
 }
@@ -342,37 +292,25 @@ __global__ __launch_bounds__(kBdThreads) void cg_wreduce_kernel(const float* __r
 __global__ __launch_bounds__(kBdThreads) void cg_colsum_kernel(const float* __restrict__ g, const float* __restrict__ nu,
                                                                const float* __restrict__ lam, const float* __restrict__ es, int bn, int M,
                                                                int N, double* __restrict__ col) {
-  __shared__ double parts[3][kBgSlices][kBgCols];
-  const int jl = threadIdx.x % kBgCols, sl = threadIdx.x / kBgCols;
-  const int j = blockIdx.x * kBgCols + jl;
+  const int j = blockIdx.x * kBgCols + threadIdx.x % kBgCols;
   const int mbeg = blockIdx.y * kCgSpan, mend = min(M, mbeg + kCgSpan);
-  double ab = 0.0, as = 0.0, at = 0.0;
-  if (j < N)
-    for (int m = mbeg + sl; m < mend; m += kBgSlices) {
-      const size_t i = (size_t)m * N + j;
-      const double gm = g[m];
-      ab = ab + gm * (double)nu[i];
-      if (bn) {
-        as = as + (double)es[i];
-        at = at + gm * (double)lam[i];
-      }
-    }
-  parts[0][sl][jl] = ab;
-  parts[1][sl][jl] = as;
-  parts[2][sl][jl] = at;
-  __syncthreads();
-  if (sl == 0 && j < N) {
-    double tb = parts[0][0][jl], ts = parts[1][0][jl], tt = parts[2][0][jl];
-    for (int q = 1; q < kBgSlices; ++q) {
-      tb = tb + parts[0][q][jl];
-      ts = ts + parts[1][q][jl];
-      tt = tt + parts[2][q][jl];
-    }
-    double* out = col + (size_t)blockIdx.y * 3 * N;
-    out[j] = tb;
-    out[N + j] = ts;
-    out[2 * N + j] = tt;
-  }
+  bg_sliced_sum<3>(
+      j < N, mbeg, mend,
+      [&](int m, double* acc) {
+        const size_t i = (size_t)m * N + j;
+        const double gm = g[m];
+        acc[0] = acc[0] + gm * (double)nu[i];
+        if (bn) {
+          acc[1] = acc[1] + (double)es[i];
+          acc[2] = acc[2] + gm * (double)lam[i];
+        }
+      },
+      [&](const double* tot) {
+        double* out = col + (size_t)blockIdx.y * 3 * N;
+        out[j] = tot[0];
+        out[N + j] = tot[1];
+        out[2 * N + j] = tot[2];
+      });
 }
 
 // the spans' partials of column j in index order, then db and (BatchNorm) dgamma, dbeta
@@ -385,13 +323,7 @@ BD_HD void cg_column_finish(const double* col, int spans, int N, int j, const fl
     ts = ts + p[N + j];
     tt = tt + p[2 * N + j];
   }
-  db[j] = bg_mix(db[j], (float)tb, scale_old, scale_new);
-  if (dgamma) {
-    double dg, dbe;
-    bg_bn_grads(ts, tt, mmean[j], mvar[j], dg, dbe);
-    dgamma[j] = bg_mix(dgamma[j], (float)dg, scale_old, scale_new);
-    dbeta[j] = bg_mix(dbeta[j], (float)dbe, scale_old, scale_new);
-  }
+  bg_column_store(j, tb, ts, tt, mmean, mvar, scale_old, scale_new, db, dgamma, dbeta);
 }
 
 // an element (b, j) a thread: the classes of row b in index order
@@ -430,20 +362,11 @@ __global__ __launch_bounds__(kBdThreads) void cg_head_kernel(const int* __restri
                                                              const float* __restrict__ lo0, const float* __restrict__ hi0, int batch, int C,
                                                              int nh, float scale_old, float scale_new, float* __restrict__ dW,
                                                              float* __restrict__ db) {
-  __shared__ double parts[kBgSlices][kBgCols];
-  const int el = threadIdx.x % kBgCols, sl = threadIdx.x / kBgCols;
-  const int e = blockIdx.x * kBgCols + el, E = nh * C + C;
-  double acc = 0.0;
-  if (e < E)
-    for (int b = sl; b < batch; b += kBgSlices) acc = acc + cg_head_term(e, nh, C, b, bg_label(y[b], C), g, top, lam0, lo0, hi0);
-  parts[sl][el] = acc;
-  __syncthreads();
-  if (sl == 0 && e < E) {
-    double tot = parts[0][el];
-    for (int q = 1; q < kBgSlices; ++q) tot = tot + parts[q][el];
-    float* out = e < nh * C ? dW + e : db + (e - nh * C);
-    *out = bg_mix(*out, (float)tot, scale_old, scale_new);
-  }
+  const int e = blockIdx.x * kBgCols + threadIdx.x % kBgCols;
+  bg_sliced_sum<1>(
+      e < nh * C + C, 0, batch,
+      [&](int b, double* acc) { acc[0] = acc[0] + cg_head_term(e, nh, C, b, bg_label(y[b], C), g, top, lam0, lo0, hi0); },
+      [&](const double* tot) { bg_head_store(e, nh, C, tot[0], scale_old, scale_new, dW, db); });
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host twin
@@ -451,11 +374,6 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
                     const float* layer_lo, const float* layer_hi, const int* y, int batch, float beta, float* ws, float scale_old,
                     float scale_new, float* grads, float* loss_rows) {
   const int L = sh.L, C = sh.n[L], M = batch * C;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
-  const float *ga = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
   float* g = ws + pl.offG;
   for (int b = 0; b < batch; ++b) cg_soft_row(mi, mc, beta, y, C, b, g, loss_rows);
   // the chain, every level kept
@@ -464,7 +382,7 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
   for (int c = L - 1; c >= 0; --c) {
     const int N = sh.n[c];
     float* lam = ws + pl.offLam[c];
-    if (c >= 1) bnp(c - 1, ga, be, mm, mv);
+    const BdBn bn = c >= 1 ? bd_bn(sh, params, bnstate, c - 1) : BdBn{};
     for (int m = 0; m < M; ++m) {
       const int b = m / C, k = m % C;
       for (int j = 0; j < N; ++j) {
@@ -472,7 +390,7 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
         if (c == L - 1) lam[at] = cg_top(WL, C, j, bg_label(y[b], C), k);
         if (c >= 1) {
           const size_t bx = pl.z[c - 1] + (size_t)b * N + j;
-          ws[pl.offNu[c] + at] = cg_nu(lam[at], bd_aff(ga, be, mm, mv, j).s, layer_lo[bx], layer_hi[bx]);
+          ws[pl.offNu[c] + at] = cg_nu(lam[at], bd_aff(bn, j).s, layer_lo[bx], layer_hi[bx]);
         }
       }
     }
@@ -492,15 +410,7 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
   }
   // the sweep, ascending
   const float* lam0 = ws + pl.offLam[0];
-  auto sliced = [&](int count, auto term) {
-    double part[kBgSlices] = {};
-    for (int r = 0; r < count; ++r) part[r % kBgSlices] = part[r % kBgSlices] + term(r);
-    double tot = part[0];
-    for (int q = 1; q < kBgSlices; ++q) tot = tot + part[q];
-    return tot;
-  };
   int cur = 0;
-  std::vector<float> arow;
   for (int c = 1; c < L; ++c) {
     const int K = sh.n[c - 1], N = sh.n[c];
     const bool first = c == 1;
@@ -513,11 +423,8 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
     float* es = ws + pl.offEs;
     float* ilo = ws + pl.offIlo;
     float* ihi = ws + pl.offIhi;
-    bnp(c - 1, ga, be, mm, mv);
-    auto a_of = [&](int m, int i) {
-      const size_t at = (size_t)m * K + i, bx = (size_t)(m / C) * K + i;
-      return first ? cg_a0(g[m], lam0[at], layer_lo[bx], layer_hi[bx]) : A[at];
-    };
+    const BdBn bn = bd_bn(sh, params, bnstate, c - 1);
+    auto a_of = [&](int m, int i) { return cg_operand(first ? nullptr : A, first ? lam0 : nullptr, layer_lo, layer_hi, g, C, K, m, M, i); };
     for (int m = 0; m < M; ++m) {
       acc.assign(N, 0.0f);
       for (int i = 0; i < K; ++i) {
@@ -528,8 +435,8 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
       for (int j = 0; j < N; ++j) {
         const size_t at = (size_t)m * N + j, bx = pl.z[c - 1] + (size_t)(m / C) * N + j;
         float vs;
-        cg_point(acc[j], g[m], lam[at], bd_aff(ga, be, mm, mv, j), layer_lo[bx], layer_hi[bx], bias[j], gl[at], vs, ilo[at], ihi[at]);
-        if (ga) es[at] = vs;
+        cg_point(acc[j], g[m], lam[at], bd_aff(bn, j), layer_lo[bx], layer_hi[bx], bias[j], gl[at], vs, ilo[at], ihi[at]);
+        if (bn.gamma) es[at] = vs;
       }
     }
     // dW: the spans' partials, then in index order
@@ -552,17 +459,17 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
     }
     double* col = reinterpret_cast<double*>(ws + pl.offCol);
     for (int z = 0; z < pl.spans; ++z) {
-      const int mbeg = z * kCgSpan, count = std::min(M, mbeg + kCgSpan) - mbeg;
+      const int mbeg = z * kCgSpan, mend = std::min(M, mbeg + kCgSpan);
       double* out = col + (size_t)z * 3 * N;
       for (int j = 0; j < N; ++j) {
-        out[j] = sliced(count, [&](int r) { return (double)g[mbeg + r] * (double)nu[(size_t)(mbeg + r) * N + j]; });
-        out[N + j] = ga ? sliced(count, [&](int r) { return (double)es[(size_t)(mbeg + r) * N + j]; }) : 0.0;
-        out[2 * N + j] = ga ? sliced(count, [&](int r) { return (double)g[mbeg + r] * (double)lam[(size_t)(mbeg + r) * N + j]; }) : 0.0;
+        out[j] = bg_sliced_sum_host(mbeg, mend, [&](int m) { return (double)g[m] * (double)nu[(size_t)m * N + j]; });
+        out[N + j] = bn.gamma ? bg_sliced_sum_host(mbeg, mend, [&](int m) { return (double)es[(size_t)m * N + j]; }) : 0.0;
+        out[2 * N + j] = bn.gamma ? bg_sliced_sum_host(mbeg, mend, [&](int m) { return (double)g[m] * (double)lam[(size_t)m * N + j]; }) : 0.0;
       }
     }
     for (int j = 0; j < N; ++j)
-      cg_column_finish(col, pl.spans, N, j, mm, mv, scale_old, scale_new, grads + sh.offb[c - 1], ga ? grads + sh.offg[c - 1] : nullptr,
-                       ga ? grads + sh.offbe[c - 1] : nullptr);
+      cg_column_finish(col, pl.spans, N, j, bn.mmean, bn.mvar, scale_old, scale_new, grads + sh.offb[c - 1],
+                       bn.gamma ? grads + sh.offg[c - 1] : nullptr, bn.gamma ? grads + sh.offbe[c - 1] : nullptr);
     for (int b = 0; b < batch; ++b)
       for (int j = 0; j < N; ++j) {
         const size_t at = pl.z[c - 1] + (size_t)b * N + j;
@@ -573,9 +480,8 @@ static void cg_host(const BdShape& sh, const CgPlan& pl, const float* params, co
   const int nh = sh.n[L - 1];
   const float* top = L > 1 ? ws + pl.offGL[cur] : nullptr;
   for (int e = 0; e < nh * C + C; ++e) {
-    const double tot = sliced(batch, [&](int b) { return cg_head_term(e, nh, C, b, bg_label(y[b], C), g, top, lam0, layer_lo, layer_hi); });
-    float* out = e < nh * C ? grads + sh.offW[L - 1] + e : grads + sh.offb[L - 1] + (e - nh * C);
-    *out = bg_mix(*out, (float)tot, scale_old, scale_new);
+    const double tot = bg_sliced_sum_host(0, batch, [&](int b) { return cg_head_term(e, nh, C, b, bg_label(y[b], C), g, top, lam0, layer_lo, layer_hi); });
+    bg_head_store(e, nh, C, tot, scale_old, scale_new, grads + sh.offW[L - 1], grads + sh.offb[L - 1]);
   }
   const BgMixIn mix{mc, beta, L > 1 ? ws + pl.offInjLo : nullptr, L > 1 ? ws + pl.offInjHi : nullptr};
   bg_run_host(sh, params, bnstate, mi, layer_lo, layer_hi, y, batch, ws + pl.offIbp, 1.0f, scale_new, grads, loss_rows, &mix);
@@ -590,21 +496,10 @@ static int cg_check(const char* fn, const BdShape& sh, const CgPlan& pl, const f
   LP_CHECK_ARG(beta >= 0.0f && beta <= 1.0f, "%s: beta = %g outside [0, 1]", fn, (double)beta);
   LP_CHECK_ARG(ws_floats >= pl.total, "%s: workspace of %zu floats; %zu are needed", fn, ws_floats, pl.total);
   const size_t B = batch, C = sh.n[sh.L];
-  struct Span { const void* p; size_t bytes; bool written; };
-  const Span sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {mi, B * C * 4, false}, {mc, B * C * 4, false},
-                     {layer_lo, pl.fam * 4, false}, {layer_hi, pl.fam * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true},
-                     {grads, sh.n_params * 4, true}, {loss_rows, B * 4, true}};
-  const int ns = sizeof(sp) / sizeof(sp[0]);
-  for (int i = 0; i < ns; ++i)
-    for (int j = i + 1; j < ns; ++j)
-      LP_CHECK_ARG(!((sp[i].written || sp[j].written) && sp[i].p && sp[j].p && spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes)),
-                   "%s: an output or the workspace overlaps another argument", fn);
-  return LIPASR_OK;
-}
-
-static int cg_batch_check(const char* fn, const BdShape& sh, int batch) {
-  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
-  return LIPASR_OK;
+  const BdSpan sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {mi, B * C * 4, false}, {mc, B * C * 4, false},
+                       {layer_lo, pl.fam * 4, false}, {layer_hi, pl.fam * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true},
+                       {grads, sh.n_params * 4, true}, {loss_rows, B * 4, true}};
+  return bd_check_spans(fn, sp, sizeof(sp) / sizeof(sp[0]));
 }
 
 }  // namespace lipasr
@@ -620,21 +515,13 @@ long lipasr_debug_bounds_crown_grad_launches(int kernel) {
 int lipasr_mlp_bounds_crown_grad_workspace(lipasr_mlp_t m, int batch, size_t* floats) {
   const char* fn = "lipasr_mlp_bounds_crown_grad_workspace";
   BdShape sh;
-  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
-  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
-  if (int rc = cg_batch_check(fn, sh, batch)) return rc;
-  *floats = cg_plan(sh, batch).total;
-  return LIPASR_OK;
+  return bd_workspace(fn, bd_shape_of(fn, m, &sh), sh, batch, floats, cg_plan);
 }
 
 int lipasr_mlp_bounds_crown_grad_workspace_host(int n_layers, const int* widths, int batch, size_t* floats) {
   const char* fn = "lipasr_mlp_bounds_crown_grad_workspace_host";
   BdShape sh;
-  if (int rc = bd_shape_from(fn, n_layers, widths, nullptr, &sh)) return rc;
-  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
-  if (int rc = cg_batch_check(fn, sh, batch)) return rc;
-  *floats = cg_plan(sh, batch).total;
-  return LIPASR_OK;
+  return bd_workspace(fn, bd_shape_from(fn, n_layers, widths, nullptr, &sh), sh, batch, floats, cg_plan);
 }
 
 int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const float* bnstate, const float* margin_ibp,
@@ -644,7 +531,7 @@ int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const floa
   const char* fn = "lipasr_mlp_bounds_crown_grad";
   BdShape sh;
   if (int rc = bd_shape_of(fn, m, &sh)) return rc;
-  if (int rc = cg_batch_check(fn, sh, batch)) return rc;
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
   const CgPlan pl = cg_plan(sh, batch);
   if (int rc = cg_check(fn, sh, pl, params, bnstate, margin_ibp, margin_crown, layer_lo, layer_hi, y, batch, beta, workspace, workspace_floats,
                         grads, loss_rows))
@@ -656,11 +543,6 @@ int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const floa
     return bg_run_device(sh, st, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, ws + pl.offIbp, scale_old, scale_new, grads,
                          loss_rows, nullptr);
   const int L = sh.L, C = sh.n[L], M = batch * C;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
-  const float *ga = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
   auto blocks = [](size_t n) { return dim3((unsigned)((n + kBdThreads - 1) / kBdThreads)); };
   float* g = ws + pl.offG;
   hipLaunchKernelGGL(cg_soft_kernel, blocks(batch), dim3(kBdThreads), 0, st, margin_ibp, margin_crown, beta, y, batch, C, g, loss_rows);
@@ -670,9 +552,8 @@ int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const floa
     const int N = sh.n[c];
     const bool top = c == L - 1;
     if (top || c >= 1) {
-      if (c >= 1) bnp(c - 1, ga, be, mm, mv);
-      hipLaunchKernelGGL(cg_relax_kernel, blocks((size_t)M * N), dim3(kBdThreads), 0, st, top ? params + sh.offW[L - 1] : nullptr, y, M, C, N, ga, be,
-                         mm, mv, c >= 1 ? layer_lo + pl.z[c - 1] : nullptr, c >= 1 ? layer_hi + pl.z[c - 1] : nullptr, ws + pl.offLam[c],
+      hipLaunchKernelGGL(cg_relax_kernel, blocks((size_t)M * N), dim3(kBdThreads), 0, st, top ? params + sh.offW[L - 1] : nullptr, y, M, C, N,
+                         c >= 1 ? bd_bn(sh, params, bnstate, c - 1) : BdBn{}, c >= 1 ? layer_lo + pl.z[c - 1] : nullptr, c >= 1 ? layer_hi + pl.z[c - 1] : nullptr, ws + pl.offLam[c],
                          c >= 1 ? ws + pl.offNu[c] : nullptr);
       LP_LAUNCH_CHECK();
       ++g_bounds_crown_grad_launches[CG_RELAX];
@@ -688,9 +569,9 @@ int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const floa
     const bool first = c == 1;
     const float* A = first ? nullptr : ws + pl.offGL[cur];
     const float* l0 = first ? lam0 : nullptr;
-    bnp(c - 1, ga, be, mm, mv);
+    const BdBn bn = bd_bn(sh, params, bnstate, c - 1);
     hipLaunchKernelGGL(cg_adjoint_kernel, dim3((M + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, A, l0, layer_lo, layer_hi, g,
-                       params + sh.offW[c - 1], params + sh.offb[c - 1], ga, be, mm, mv, layer_lo + pl.z[c - 1], layer_hi + pl.z[c - 1],
+                       params + sh.offW[c - 1], params + sh.offb[c - 1], bn, layer_lo + pl.z[c - 1], layer_hi + pl.z[c - 1],
                        ws + pl.offLam[c], M, C, K, N, ws + pl.offGL[cur ^ 1], ws + pl.offEs, ws + pl.offIlo, ws + pl.offIhi);
     LP_LAUNCH_CHECK();
     ++g_bounds_crown_grad_launches[CG_ADJOINT];
@@ -704,14 +585,14 @@ int lipasr_mlp_bounds_crown_grad(lipasr_mlp_t m, const float* params, const floa
     ++g_bounds_crown_grad_launches[CG_WREDUCE];
     double* col = reinterpret_cast<double*>(ws + pl.offCol);
     hipLaunchKernelGGL(cg_colsum_kernel, dim3((N + kBgCols - 1) / kBgCols, pl.spans), dim3(kBdThreads), 0, st, g, ws + pl.offNu[c], ws + pl.offLam[c],
-                       ws + pl.offEs, ga ? 1 : 0, M, N, col);
+                       ws + pl.offEs, bn.gamma ? 1 : 0, M, N, col);
     LP_LAUNCH_CHECK();
     ++g_bounds_crown_grad_launches[CG_COLSUM];
     const unsigned inject_blocks = blocks((size_t)batch * N).x;
     hipLaunchKernelGGL(cg_finish_kernel, dim3(inject_blocks + (N + kBdThreads - 1) / kBdThreads), dim3(kBdThreads), 0, st, ws + pl.offIlo,
                        ws + pl.offIhi, batch, C, N, ws + pl.offInjLo + pl.z[c - 1], ws + pl.offInjHi + pl.z[c - 1], (int)inject_blocks, col,
-                       pl.spans, mm, mv, scale_old, scale_new, grads + sh.offb[c - 1], ga ? grads + sh.offg[c - 1] : nullptr,
-                       ga ? grads + sh.offbe[c - 1] : nullptr);
+                       pl.spans, bn.mmean, bn.mvar, scale_old, scale_new, grads + sh.offb[c - 1], bn.gamma ? grads + sh.offg[c - 1] : nullptr,
+                       bn.gamma ? grads + sh.offbe[c - 1] : nullptr);
     LP_LAUNCH_CHECK();
     ++g_bounds_crown_grad_launches[CG_FINISH];
     cur ^= 1;
@@ -735,7 +616,7 @@ int lipasr_mlp_bounds_crown_grad_host(int n_layers, const int* widths, const int
   const char* fn = "lipasr_mlp_bounds_crown_grad_host";
   BdShape sh;
   if (int rc = bd_shape_from(fn, n_layers, widths, bn, &sh)) return rc;
-  if (int rc = cg_batch_check(fn, sh, batch)) return rc;
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
   const CgPlan pl = cg_plan(sh, batch);
   if (int rc = cg_check(fn, sh, pl, params, bnstate, margin_ibp, margin_crown, layer_lo, layer_hi, y, batch, beta, workspace, workspace_floats,
                         grads, loss_rows))

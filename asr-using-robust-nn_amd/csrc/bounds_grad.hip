@@ -8,13 +8,15 @@
 //   bg_head_kernel     1 launch   a block per row: softmax of u, loss_rows, d loss / d u, the gradient into the last hidden box
 //                                 through the difference rows W_L[y] - W_L[k] (lo where the difference is > 0, hi otherwise), and
 //                                 the BatchNorm and ReLU gates of layer L - 1: (gc, gr) of that layer and what its column sums need
-//   bg_head_dw_kernel  1          dW_L and db_L: 8 entries a block, the batch in 32 interleaved fp64 slices that meet in index order
-//   bg_colsum_kernel   L - 1      db_l, dgamma_l, dbeta_l of a hidden layer: 8 columns a block, the same 32 slices
-//   bg_wgrad_kernel    L - 1      dW_l = c^T gc + sign(W_l) (r^T gr): a 32 x 128 tile of both products on v_mfma_f32_32x32x2_f32, the
-//                                 batch as the k dimension, c and r formed in registers from lo / hi, the next chunk's loads in flight
-//                                 during the MFMAs; epilogue: the sign of W, the two scales, the store into grads
-//   bg_back_kernel     L - 2      (g_c, g_r) = (gc W_l^T, gr |W_l|^T) from ONE read of W_l on the same tile; epilogue: g_lo, g_hi, layer
-//                                 l - 1's BatchNorm and ReLU gates, (gc, gr) of layer l - 1 and what its column sums need
+//   bg_head_dw_kernel  1          dW_L and db_L: 8 entries a block, the batch through bg_sliced_sum (bounds_grad.h): 32 interleaved
+//                                 fp64 slices that meet in index order
+//   bg_colsum_kernel   L - 1      db_l, dgamma_l, dbeta_l of a hidden layer: 8 columns a block, three such sums at once
+//   bg_wgrad_kernel    L - 1      dW_l = c^T gc + sign(W_l) (r^T gr): both products on the tile of bounds_tile.h, the batch as the k
+//                                 dimension (narrow operand by reduction row, two wide k-major operands), c and r formed from
+//                                 lo / hi as they are staged; epilogue: the sign of W, the two scales, the store into grads
+//   bg_back_kernel     L - 2      (g_c, g_r) = (gc W_l^T, gr |W_l|^T) from ONE read of W_l on the same tile (two narrow operands by
+//                                 output row, W n-major); epilogue: g_lo, g_hi, layer l - 1's BatchNorm and ReLU gates, (gc, gr) of
+//                                 layer l - 1 and what its column sums need
 //
 // Launches of one call with L layers: 2 for L = 1, 3 (L - 1) + 1 for L >= 2.  Every sum has one order that the shapes fix: the
 // MFMA is an fmaf chain in ascending k, a column sum is 32 interleaved slices in ascending row order that meet in slice order.  No
@@ -28,6 +30,7 @@
 // margin_crown, the head weighted by 1 - beta, and a gradient on every z box added in bg_gate.  With a null BgMixIn the extra
 // operands are null and every result is what it was without them.
 #include "bounds_grad.h"
+#include "bounds_tile.h"
 
 // host and device must round alike
 #pragma clang fp contract(off)
@@ -122,10 +125,9 @@ __global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __rest
                                                              const float* __restrict__ inj_lo, const float* __restrict__ inj_hi,
                                                              const int* __restrict__ y,
                                                              const float* __restrict__ WL, int C, int nh, const float* __restrict__ lo,
-                                                             const float* __restrict__ hi, int hidden, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, const float* __restrict__ mmean,
-                                                             const float* __restrict__ mvar, const float* __restrict__ zlo,
-                                                             const float* __restrict__ zhi, float* __restrict__ loss_rows,
+                                                             const float* __restrict__ hi, int hidden, BdBn bn,
+                                                             const float* __restrict__ zlo, const float* __restrict__ zhi,
+                                                             float* __restrict__ loss_rows,
                                                              float* __restrict__ coef, float* __restrict__ ty_out, float* __restrict__ gc,
                                                              float* __restrict__ gr, float* __restrict__ es, float* __restrict__ et) {
   __shared__ double p[32];
@@ -166,11 +168,11 @@ __global__ __launch_bounds__(kBdThreads) void bg_head_kernel(const float* __rest
     ty_out[at] = (float)ty;
     if (hidden) {
       float vc, vr, vs, vt;
-      if (inj_lo) bg_gate(glo, ghi, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[at], zhi[at], vc, vr, vs, vt, true, inj_lo[at], inj_hi[at]);
-      else bg_gate(glo, ghi, bd_aff(gamma, beta, mmean, mvar, j).s, zlo[at], zhi[at], vc, vr, vs, vt);
+      if (inj_lo) bg_gate(glo, ghi, bd_aff(bn, j).s, zlo[at], zhi[at], vc, vr, vs, vt, true, inj_lo[at], inj_hi[at]);
+      else bg_gate(glo, ghi, bd_aff(bn, j).s, zlo[at], zhi[at], vc, vr, vs, vt);
       gc[at] = vc;
       gr[at] = vr;
-      if (gamma) {
+      if (bn.gamma) {
         es[at] = vs;
         et[at] = vt;
       }
@@ -184,20 +186,11 @@ __global__ __launch_bounds__(kBdThreads) void bg_head_dw_kernel(const float* __r
                                                                 const float* __restrict__ lo, const float* __restrict__ hi, int batch, int C,
                                                                 int nh, float scale_old, float scale_new, float* __restrict__ dW,
                                                                 float* __restrict__ db) {
-  __shared__ double parts[kBgSlices][kBgCols];
-  const int el = threadIdx.x % kBgCols, sl = threadIdx.x / kBgCols;
-  const int e = blockIdx.x * kBgCols + el, E = nh * C + C;
-  double acc = 0.0;
-  if (e < E)
-    for (int b = sl; b < batch; b += kBgSlices) acc = acc + bg_head_dw_term(e, nh, C, b, bg_label(y[b], C), WL, coef, ty, lo, hi);
-  parts[sl][el] = acc;
-  __syncthreads();
-  if (sl == 0 && e < E) {
-    double tot = parts[0][el];
-    for (int q = 1; q < kBgSlices; ++q) tot = tot + parts[q][el];
-    float* out = e < nh * C ? dW + e : db + (e - nh * C);
-    *out = bg_mix(*out, (float)tot, scale_old, scale_new);
-  }
+  const int e = blockIdx.x * kBgCols + threadIdx.x % kBgCols;
+  bg_sliced_sum<1>(
+      e < nh * C + C, 0, batch,
+      [&](int b, double* acc) { acc[0] = acc[0] + bg_head_dw_term(e, nh, C, b, bg_label(y[b], C), WL, coef, ty, lo, hi); },
+      [&](const double* tot) { bg_head_store(e, nh, C, tot[0], scale_old, scale_new, dW, db); });
 }
 
 // kBgCols columns of a hidden layer a block: db, and (BatchNorm) dgamma and dbeta
@@ -206,38 +199,18 @@ __global__ __launch_bounds__(kBdThreads) void bg_colsum_kernel(const float* __re
                                                                const float* __restrict__ mvar, int batch, int N, float scale_old,
                                                                float scale_new, float* __restrict__ db, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta) {
-  __shared__ double parts[3][kBgSlices][kBgCols];
-  const int jl = threadIdx.x % kBgCols, sl = threadIdx.x / kBgCols;
-  const int j = blockIdx.x * kBgCols + jl;
-  double ab = 0.0, as = 0.0, at = 0.0;
-  if (j < N)
-    for (int b = sl; b < batch; b += kBgSlices) {
-      const size_t i = (size_t)b * N + j;
-      ab = ab + (double)gc[i];
-      if (dgamma) {
-        as = as + (double)es[i];
-        at = at + (double)et[i];
-      }
-    }
-  parts[0][sl][jl] = ab;
-  parts[1][sl][jl] = as;
-  parts[2][sl][jl] = at;
-  __syncthreads();
-  if (sl == 0 && j < N) {
-    double tb = parts[0][0][jl], ts = parts[1][0][jl], tt = parts[2][0][jl];
-    for (int q = 1; q < kBgSlices; ++q) {
-      tb = tb + parts[0][q][jl];
-      ts = ts + parts[1][q][jl];
-      tt = tt + parts[2][q][jl];
-    }
-    db[j] = bg_mix(db[j], (float)tb, scale_old, scale_new);
-    if (dgamma) {
-      double dg, dbe;
-      bg_bn_grads(ts, tt, mmean[j], mvar[j], dg, dbe);
-      dgamma[j] = bg_mix(dgamma[j], (float)dg, scale_old, scale_new);
-      dbeta[j] = bg_mix(dbeta[j], (float)dbe, scale_old, scale_new);
-    }
-  }
+  const int j = blockIdx.x * kBgCols + threadIdx.x % kBgCols;
+  bg_sliced_sum<3>(
+      j < N, 0, batch,
+      [&](int b, double* acc) {
+        const size_t i = (size_t)b * N + j;
+        acc[0] = acc[0] + (double)gc[i];
+        if (dgamma) {
+          acc[1] = acc[1] + (double)es[i];
+          acc[2] = acc[2] + (double)et[i];
+        }
+      },
+      [&](const double* tot) { bg_column_store(j, tot[0], tot[1], tot[2], mmean, mvar, scale_old, scale_new, db, dgamma, dbeta); });
 }
 
 // dW[i][j] = sum_b c[b][i] gc[b][j] + sign(W[i][j]) sum_b r[b][i] gr[b][j]: rows i0 .. i0 + 31 (blockIdx.x), columns
@@ -246,62 +219,47 @@ __global__ __launch_bounds__(kBdThreads) void bg_wgrad_kernel(const float* __res
                                                               const float* __restrict__ gc, const float* __restrict__ gr,
                                                               const float* __restrict__ W, int batch, int K, int N, float scale_old,
                                                               float scale_new, float* __restrict__ dW) {
-  __shared__ float cs[32 * 33], rs[32 * 33], gcs[32 * 128], grs[32 * 128];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  __shared__ float cs[kBtNarrow], rs[kBtNarrow], gcs[kBtWideK], grs[kBtWideK];
+  const BtThread t;
   const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 128;
-  bd_f32x16 acc_c, acc_r;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc_c[e] = acc_r[e] = 0.0f;
+  bd_f32x16 acc_c = bt_zero(), acc_r = bt_zero();
   // a row past the batch, a unit past K and a column past N read as 0
   float lreg[4], hreg[4], creg[16], rreg[16];
   auto fetch = [&](int b0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, bb = idx >> 5, ii = idx & 31;
+    bt_narrow_each(t.tid, [&](int q, int bb, int ii) {
       const int b = b0 + bb, i = i0 + ii;
       const bool in = b < batch && i < K;
       const size_t at = (size_t)b * K + i;
       lreg[q] = in ? lo[at] : 0.0f;
       hreg[q] = in ? hi[at] : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q, bb = idx >> 7, col = idx & 127;
+    });
+    bt_wide_k_each(t.tid, [&](int q, int bb, int col) {
       const int b = b0 + bb, j = j0 + col;
       const bool in = b < batch && j < N;
       const size_t at = (size_t)b * N + j;
       creg[q] = in ? gc[at] : 0.0f;
       rreg[q] = in ? gr[at] : 0.0f;
-    }
+    });
   };
-  fetch(0);
-  for (int b0 = 0; b0 < batch; b0 += 32) {
-    __syncthreads();  // the previous chunk is read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, bb = idx >> 5, ii = idx & 31;
-      cs[bb * 33 + ii] = 0.5f * (lreg[q] + hreg[q]);
-      rs[bb * 33 + ii] = 0.5f * (hreg[q] - lreg[q]);
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      gcs[tid + kBdThreads * q] = creg[q];
-      grs[tid + kBdThreads * q] = rreg[q];
-    }
-    __syncthreads();
-    if (b0 + 32 < batch) fetch(b0 + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int bb = 2 * s + h;
-      acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(cs[bb * 33 + li], gcs[bb * 128 + wave * 32 + li], acc_c, 0, 0, 0);
-      acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(rs[bb * 33 + li], grs[bb * 128 + wave * 32 + li], acc_r, 0, 0, 0);
-    }
-  }
-  const int j = j0 + wave * 32 + li;
+  auto stage = [&] {
+    bt_narrow_each(t.tid, [&](int q, int bb, int ii) {
+      cs[bt_narrow_at(bb, ii)] = 0.5f * (lreg[q] + hreg[q]);
+      rs[bt_narrow_at(bb, ii)] = 0.5f * (hreg[q] - lreg[q]);
+    });
+    bt_wide_k_each(t.tid, [&](int q, int bb, int col) {
+      gcs[bt_wide_k_at(bb, col)] = creg[q];
+      grs[bt_wide_k_at(bb, col)] = rreg[q];
+    });
+  };
+  bt_pipeline(0, batch, fetch, stage, [&](int s) {
+    acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(BT_NARROW_BY_K(cs, t, s), BT_WIDE_K(gcs, t, s), acc_c, 0, 0, 0);
+    acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(BT_NARROW_BY_K(rs, t, s), BT_WIDE_K(grs, t, s), acc_r, 0, 0, 0);
+  });
+  const int j = t.col(j0);
   if (j >= N) return;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int i = i0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    const int i = t.row(i0, e);
     if (i >= K) continue;
     const size_t at = (size_t)i * N + j;
     const float w = W[at];
@@ -313,66 +271,47 @@ __global__ __launch_bounds__(kBdThreads) void bg_wgrad_kernel(const float* __res
 // (g_c, g_r)[b][i] = sum_j (gc[b][j] W[i][j], gr[b][j] |W[i][j]|): rows b0 .. b0 + 31 (blockIdx.x), columns i0 .. i0 + 127
 // (blockIdx.y).  The epilogue applies the layer below: its BatchNorm scale and the z box of row b.
 __global__ __launch_bounds__(kBdThreads) void bg_back_kernel(const float* __restrict__ gc, const float* __restrict__ gr,
-                                                             const float* __restrict__ W, int batch, int K, int N,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             const float* __restrict__ mmean, const float* __restrict__ mvar,
+                                                             const float* __restrict__ W, int batch, int K, int N, BdBn bn,
                                                              const float* __restrict__ zlo, const float* __restrict__ zhi,
                                                              const float* __restrict__ inj_lo, const float* __restrict__ inj_hi,
                                                              float* __restrict__ gc_out, float* __restrict__ gr_out,
                                                              float* __restrict__ es, float* __restrict__ et) {
-  __shared__ float a1[32 * 33], a2[32 * 33], wt[128 * 33];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  __shared__ float a1[kBtNarrow], a2[kBtNarrow], wt[kBtWideN];
+  const BtThread t;
   const int b0 = blockIdx.x * 32, i0 = blockIdx.y * 128;
-  bd_f32x16 acc_c, acc_r;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc_c[e] = acc_r[e] = 0.0f;
-  float creg[4], rreg[4], wreg[16];  // the next chunk, in flight while the current one feeds the MFMAs
+  bd_f32x16 acc_c = bt_zero(), acc_r = bt_zero();
+  float creg[4], rreg[4], wreg[16];
   auto fetch = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q, row = idx >> 5, kk = idx & 31;
+    bt_narrow_each(t.tid, [&](int q, int row, int kk) {
       const int b = b0 + row, k = k0 + kk;
       const bool in = b < batch && k < K;
       const size_t at = (size_t)b * K + k;
       creg[q] = in ? gc[at] : 0.0f;
       rreg[q] = in ? gr[at] : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q, il = idx >> 5, kk = idx & 31;
+    });
+    bt_wide_n_each(t.tid, [&](int q, int il, int kk) {
       const int i = i0 + il, k = k0 + kk;
       wreg[q] = (i < N && k < K) ? W[(size_t)i * K + k] : 0.0f;
-    }
+    });
   };
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += 32) {
-    __syncthreads();  // the previous chunk is read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + kBdThreads * q;
-      a1[(idx >> 5) * 33 + (idx & 31)] = creg[q];
-      a2[(idx >> 5) * 33 + (idx & 31)] = rreg[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = tid + kBdThreads * q;
-      wt[(idx >> 5) * 33 + (idx & 31)] = wreg[q];
-    }
-    __syncthreads();
-    if (k0 + 32 < K) fetch(k0 + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const float w = wt[(wave * 32 + li) * 33 + 2 * s + h];
-      acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[li * 33 + 2 * s + h], w, acc_c, 0, 0, 0);
-      acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[li * 33 + 2 * s + h], fabsf(w), acc_r, 0, 0, 0);
-    }
-  }
-  const int i = i0 + wave * 32 + li;
+  auto stage = [&] {
+    bt_narrow_each(t.tid, [&](int q, int row, int kk) {
+      a1[bt_narrow_at(row, kk)] = creg[q];
+      a2[bt_narrow_at(row, kk)] = rreg[q];
+    });
+    bt_wide_n_store(wt, t.tid, wreg);
+  };
+  bt_pipeline(0, K, fetch, stage, [&](int s) {
+    const float w = BT_WIDE_N(wt, t, s);
+    acc_c = __builtin_amdgcn_mfma_f32_32x32x2f32(BT_NARROW_BY_ROW(a1, t, s), w, acc_c, 0, 0, 0);
+    acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(BT_NARROW_BY_ROW(a2, t, s), fabsf(w), acc_r, 0, 0, 0);
+  });
+  const int i = t.col(i0);
   if (i >= N) return;
-  const double s = bd_aff(gamma, beta, mmean, mvar, i).s;
+  const double s = bd_aff(bn, i).s;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int b = b0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    const int b = t.row(b0, e);
     if (b >= batch) continue;
     const size_t at = (size_t)b * N + i;
     const double c = acc_c[e], r = acc_r[e];
@@ -381,7 +320,7 @@ __global__ __launch_bounds__(kBdThreads) void bg_back_kernel(const float* __rest
     else bg_gate(0.5 * (c - r), 0.5 * (c + r), s, zlo[at], zhi[at], vc, vr, vs, vt);
     gc_out[at] = vc;
     gr_out[at] = vr;
-    if (gamma) {
+    if (bn.gamma) {
       es[at] = vs;
       et[at] = vt;
     }
@@ -396,11 +335,6 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
   const float mixbeta = mix ? mix->beta : 0.0f;
   const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
   const bool hidden = L > 1;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
-  const float *g = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
   float* coef = ws + pl.offCoef;
   float* ty = ws + pl.offTy;
   const float* WL = params + sh.offW[L - 1];
@@ -408,7 +342,7 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
   const float* hhi = hidden ? layer_hi + pl.h[L - 2] : layer_hi;
   int cur = 0;
   // head
-  if (hidden) bnp(L - 2, g, be, mm, mv);
+  BdBn bn = hidden ? bd_bn(sh, params, bnstate, L - 2) : BdBn{};
   for (int b = 0; b < batch; ++b) {
     double p[32];
     const int yb = bg_label(y[b], C);
@@ -437,24 +371,16 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
       ty[at] = (float)t;
       if (hidden) {
         float vs, vt;
-        bg_gate(glo, ghi, bd_aff(g, be, mm, mv, j).s, layer_lo[pl.z[L - 2] + at], layer_hi[pl.z[L - 2] + at], ws[pl.offG[cur][0] + at],
+        bg_gate(glo, ghi, bd_aff(bn, j).s, layer_lo[pl.z[L - 2] + at], layer_hi[pl.z[L - 2] + at], ws[pl.offG[cur][0] + at],
                 ws[pl.offG[cur][1] + at], vs, vt, mix != nullptr, mix ? mix->inj_lo[pl.z[L - 2] + at] : 0.0,
                 mix ? mix->inj_hi[pl.z[L - 2] + at] : 0.0);
-        if (g) { ws[pl.offE[cur][0] + at] = vs; ws[pl.offE[cur][1] + at] = vt; }
+        if (bn.gamma) { ws[pl.offE[cur][0] + at] = vs; ws[pl.offE[cur][1] + at] = vt; }
       }
     }
   }
-  auto sliced = [&](auto term) {
-    double part[kBgSlices] = {};
-    for (int b = 0; b < batch; ++b) part[b % kBgSlices] = part[b % kBgSlices] + term(b);
-    double tot = part[0];
-    for (int q = 1; q < kBgSlices; ++q) tot = tot + part[q];
-    return tot;
-  };
   for (int e = 0; e < nh * C + C; ++e) {
-    const double tot = sliced([&](int b) { return bg_head_dw_term(e, nh, C, b, bg_label(y[b], C), WL, coef, ty, hlo, hhi); });
-    float* out = e < nh * C ? grads + sh.offW[L - 1] + e : grads + sh.offb[L - 1] + (e - nh * C);
-    *out = bg_mix(*out, (float)tot, scale_old, scale_new);
+    const double tot = bg_sliced_sum_host(0, batch, [&](int b) { return bg_head_dw_term(e, nh, C, b, bg_label(y[b], C), WL, coef, ty, hlo, hhi); });
+    bg_head_store(e, nh, C, tot, scale_old, scale_new, grads + sh.offW[L - 1], grads + sh.offb[L - 1]);
   }
   // hidden layers, top down
   std::vector<float> accc, accr;
@@ -465,21 +391,13 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
     const float* es = ws + pl.offE[cur][0];
     const float* et = ws + pl.offE[cur][1];
     const float* W = params + sh.offW[l];
-    bnp(l, g, be, mm, mv);
+    bn = bd_bn(sh, params, bnstate, l);
     for (int j = 0; j < N; ++j) {
-      const double tb = sliced([&](int b) { return (double)gc[(size_t)b * N + j]; });
-      float* db = grads + sh.offb[l] + j;
-      *db = bg_mix(*db, (float)tb, scale_old, scale_new);
-      if (g) {
-        const double ts = sliced([&](int b) { return (double)es[(size_t)b * N + j]; });
-        const double tt = sliced([&](int b) { return (double)et[(size_t)b * N + j]; });
-        double dg, dbe;
-        bg_bn_grads(ts, tt, mm[j], mv[j], dg, dbe);
-        float* og = grads + sh.offg[l] + j;
-        float* ob = grads + sh.offbe[l] + j;
-        *og = bg_mix(*og, (float)dg, scale_old, scale_new);
-        *ob = bg_mix(*ob, (float)dbe, scale_old, scale_new);
-      }
+      const double tb = bg_sliced_sum_host(0, batch, [&](int b) { return (double)gc[(size_t)b * N + j]; });
+      const double ts = bn.gamma ? bg_sliced_sum_host(0, batch, [&](int b) { return (double)es[(size_t)b * N + j]; }) : 0.0;
+      const double tt = bn.gamma ? bg_sliced_sum_host(0, batch, [&](int b) { return (double)et[(size_t)b * N + j]; }) : 0.0;
+      bg_column_store(j, tb, ts, tt, bn.mmean, bn.mvar, scale_old, scale_new, grads + sh.offb[l], bn.gamma ? grads + sh.offg[l] : nullptr,
+                      bn.gamma ? grads + sh.offbe[l] : nullptr);
     }
     const float* ilo = l == 0 ? layer_lo : layer_lo + pl.h[l - 1];
     const float* ihi = l == 0 ? layer_hi : layer_hi + pl.h[l - 1];
@@ -503,7 +421,7 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
     }
     if (l == 0) break;
     // back: the gradient into the box of layer l - 1, through its gates
-    bnp(l - 1, g, be, mm, mv);
+    bn = bd_bn(sh, params, bnstate, l - 1);
     for (int b = 0; b < batch; ++b) {
       accc.assign(K, 0.0f); accr.assign(K, 0.0f);
       for (int j = 0; j < N; ++j) {
@@ -518,10 +436,10 @@ static void bg_host(const BdShape& sh, const BgPlan& pl, const float* params, co
         const size_t at = (size_t)b * K + i;
         const double c = accc[i], r = accr[i];
         float vs, vt;
-        bg_gate(0.5 * (c - r), 0.5 * (c + r), bd_aff(g, be, mm, mv, i).s, layer_lo[pl.z[l - 1] + at], layer_hi[pl.z[l - 1] + at],
+        bg_gate(0.5 * (c - r), 0.5 * (c + r), bd_aff(bn, i).s, layer_lo[pl.z[l - 1] + at], layer_hi[pl.z[l - 1] + at],
                 ws[pl.offG[cur ^ 1][0] + at], ws[pl.offG[cur ^ 1][1] + at], vs, vt, mix != nullptr, mix ? mix->inj_lo[pl.z[l - 1] + at] : 0.0,
                 mix ? mix->inj_hi[pl.z[l - 1] + at] : 0.0);
-        if (g) { ws[pl.offE[cur ^ 1][0] + at] = vs; ws[pl.offE[cur ^ 1][1] + at] = vt; }
+        if (bn.gamma) { ws[pl.offE[cur ^ 1][0] + at] = vs; ws[pl.offE[cur ^ 1][1] + at] = vt; }
       }
     }
     cur ^= 1;
@@ -536,21 +454,10 @@ static int bg_check(const char* fn, const BdShape& sh, const BgPlan& pl, const f
   LP_CHECK_ARG(sh.n_state == 0 || bnstate, "%s: bnstate is null", fn);
   LP_CHECK_ARG(ws_floats >= pl.total, "%s: workspace of %zu floats; %zu are needed", fn, ws_floats, pl.total);
   const size_t B = batch, C = sh.n[sh.L];
-  struct Span { const void* p; size_t bytes; bool written; };
-  const Span sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {margin, B * C * 4, false},
-                     {layer_lo, pl.fam * 4, false}, {layer_hi, pl.fam * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true},
-                     {grads, sh.n_params * 4, true}, {loss_rows, B * 4, true}};
-  const int ns = sizeof(sp) / sizeof(sp[0]);
-  for (int i = 0; i < ns; ++i)
-    for (int j = i + 1; j < ns; ++j)
-      LP_CHECK_ARG(!((sp[i].written || sp[j].written) && sp[i].p && sp[j].p && spans_overlap(sp[i].p, sp[i].bytes, sp[j].p, sp[j].bytes)),
-                   "%s: an output or the workspace overlaps another argument", fn);
-  return LIPASR_OK;
-}
-
-static int bg_batch_check(const char* fn, const BdShape& sh, int batch) {
-  LP_CHECK_ARG(batch >= 1 && (long long)batch * sh.n[sh.L] <= (1 << 24), "%s: batch %d", fn, batch);
-  return LIPASR_OK;
+  const BdSpan sp[] = {{params, sh.n_params * 4, false}, {bnstate, sh.n_state * 4, false}, {margin, B * C * 4, false},
+                       {layer_lo, pl.fam * 4, false}, {layer_hi, pl.fam * 4, false}, {y, B * 4, false}, {ws, ws_floats * 4, true},
+                       {grads, sh.n_params * 4, true}, {loss_rows, B * 4, true}};
+  return bd_check_spans(fn, sp, sizeof(sp) / sizeof(sp[0]));
 }
 
 size_t bg_workspace_floats(const BdShape& sh, int batch) { return bg_plan(sh, batch).total; }
@@ -571,20 +478,15 @@ int bg_run_device(const BdShape& sh, hipStream_t st, const float* params, const 
   const float* ihi = mix ? mix->inj_hi : nullptr;
   const int L = sh.L, C = sh.n[L], nh = sh.n[L - 1];
   const bool hidden = L > 1;
-  auto bnp = [&](int l, const float*& g, const float*& be, const float*& mm, const float*& mv) {
-    g = be = mm = mv = nullptr;
-    if (sh.bn[l]) { g = params + sh.offg[l]; be = params + sh.offbe[l]; mm = bnstate + sh.offmm[l]; mv = bnstate + sh.offmv[l]; }
-  };
-  const float *g = nullptr, *be = nullptr, *mm = nullptr, *mv = nullptr;
   float* coef = ws + pl.offCoef;
   float* ty = ws + pl.offTy;
   const float* WL = params + sh.offW[L - 1];
   const float* hlo = hidden ? layer_lo + pl.h[L - 2] : layer_lo;
   const float* hhi = hidden ? layer_hi + pl.h[L - 2] : layer_hi;
   int cur = 0;
-  if (hidden) bnp(L - 2, g, be, mm, mv);
   hipLaunchKernelGGL(bg_head_kernel, dim3(batch), dim3(kBdThreads), 0, st, margin, margin2, mixbeta,
-                     (hidden && ilo) ? ilo + pl.z[L - 2] : nullptr, (hidden && ihi) ? ihi + pl.z[L - 2] : nullptr, y, WL, C, nh, hlo, hhi, hidden ? 1 : 0, g, be, mm, mv,
+                     (hidden && ilo) ? ilo + pl.z[L - 2] : nullptr, (hidden && ihi) ? ihi + pl.z[L - 2] : nullptr, y, WL, C, nh, hlo, hhi,
+                     hidden ? 1 : 0, hidden ? bd_bn(sh, params, bnstate, L - 2) : BdBn{},
                      hidden ? layer_lo + pl.z[L - 2] : nullptr, hidden ? layer_hi + pl.z[L - 2] : nullptr, loss_rows, coef, ty,
                      ws + pl.offG[cur][0], ws + pl.offG[cur][1], ws + pl.offE[cur][0], ws + pl.offE[cur][1]);
   LP_LAUNCH_CHECK();
@@ -597,10 +499,10 @@ int bg_run_device(const BdShape& sh, hipStream_t st, const float* params, const 
     const int K = sh.n[l], N = sh.n[l + 1];
     const float* gc = ws + pl.offG[cur][0];
     const float* gr = ws + pl.offG[cur][1];
-    bnp(l, g, be, mm, mv);
-    hipLaunchKernelGGL(bg_colsum_kernel, dim3((N + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, gc, ws + pl.offE[cur][0], ws + pl.offE[cur][1], mm, mv,
-                       batch, N, scale_old, scale_new, grads + sh.offb[l], g ? grads + sh.offg[l] : nullptr,
-                       g ? grads + sh.offbe[l] : nullptr);
+    const BdBn bn = bd_bn(sh, params, bnstate, l);
+    hipLaunchKernelGGL(bg_colsum_kernel, dim3((N + kBgCols - 1) / kBgCols), dim3(kBdThreads), 0, st, gc, ws + pl.offE[cur][0], ws + pl.offE[cur][1],
+                       bn.mmean, bn.mvar, batch, N, scale_old, scale_new, grads + sh.offb[l], bn.gamma ? grads + sh.offg[l] : nullptr,
+                       bn.gamma ? grads + sh.offbe[l] : nullptr);
     LP_LAUNCH_CHECK();
     ++g_bounds_grad_launches[BG_COLSUM];
     hipLaunchKernelGGL(bg_wgrad_kernel, dim3((K + 31) / 32, (N + 127) / 128), dim3(kBdThreads), 0, st, l == 0 ? layer_lo : layer_lo + pl.h[l - 1],
@@ -609,9 +511,8 @@ int bg_run_device(const BdShape& sh, hipStream_t st, const float* params, const 
     LP_LAUNCH_CHECK();
     ++g_bounds_grad_launches[BG_WGRAD];
     if (l == 0) break;
-    bnp(l - 1, g, be, mm, mv);
     hipLaunchKernelGGL(bg_back_kernel, dim3((batch + 31) / 32, (K + 127) / 128), dim3(kBdThreads), 0, st, gc, gr, params + sh.offW[l], batch, N,
-                       K, g, be, mm, mv, layer_lo + pl.z[l - 1], layer_hi + pl.z[l - 1], ilo ? ilo + pl.z[l - 1] : nullptr,
+                       K, bd_bn(sh, params, bnstate, l - 1), layer_lo + pl.z[l - 1], layer_hi + pl.z[l - 1], ilo ? ilo + pl.z[l - 1] : nullptr,
                        ihi ? ihi + pl.z[l - 1] : nullptr, ws + pl.offG[cur ^ 1][0], ws + pl.offG[cur ^ 1][1],
                        ws + pl.offE[cur ^ 1][0], ws + pl.offE[cur ^ 1][1]);
     LP_LAUNCH_CHECK();
@@ -632,21 +533,13 @@ long lipasr_debug_bounds_grad_launches(int kernel) { return (kernel >= 0 && kern
 int lipasr_mlp_bounds_grad_workspace(lipasr_mlp_t m, int batch, size_t* floats) {
   const char* fn = "lipasr_mlp_bounds_grad_workspace";
   BdShape sh;
-  if (int rc = bd_shape_of(fn, m, &sh)) return rc;
-  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
-  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
-  *floats = bg_plan(sh, batch).total;
-  return LIPASR_OK;
+  return bd_workspace(fn, bd_shape_of(fn, m, &sh), sh, batch, floats, bg_plan);
 }
 
 int lipasr_mlp_bounds_grad_workspace_host(int n_layers, const int* widths, int batch, size_t* floats) {
   const char* fn = "lipasr_mlp_bounds_grad_workspace_host";
   BdShape sh;
-  if (int rc = bd_shape_from(fn, n_layers, widths, nullptr, &sh)) return rc;
-  LP_CHECK_ARG(floats != nullptr, "%s: null argument", fn);
-  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
-  *floats = bg_plan(sh, batch).total;
-  return LIPASR_OK;
+  return bd_workspace(fn, bd_shape_from(fn, n_layers, widths, nullptr, &sh), sh, batch, floats, bg_plan);
 }
 
 int lipasr_mlp_bounds_grad(lipasr_mlp_t m, const float* params, const float* bnstate, const float* margin_ibp, const float* layer_lo,
@@ -655,7 +548,7 @@ int lipasr_mlp_bounds_grad(lipasr_mlp_t m, const float* params, const float* bns
   const char* fn = "lipasr_mlp_bounds_grad";
   BdShape sh;
   if (int rc = bd_shape_of(fn, m, &sh)) return rc;
-  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
   const BgPlan pl = bg_plan(sh, batch);
   if (int rc = bg_check(fn, sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, workspace, workspace_floats, grads, loss_rows))
     return rc;
@@ -671,7 +564,7 @@ int lipasr_mlp_bounds_grad_host(int n_layers, const int* widths, const int* bn, 
   const char* fn = "lipasr_mlp_bounds_grad_host";
   BdShape sh;
   if (int rc = bd_shape_from(fn, n_layers, widths, bn, &sh)) return rc;
-  if (int rc = bg_batch_check(fn, sh, batch)) return rc;
+  if (int rc = bd_batch_check(fn, sh, batch)) return rc;
   const BgPlan pl = bg_plan(sh, batch);
   if (int rc = bg_check(fn, sh, pl, params, bnstate, margin_ibp, layer_lo, layer_hi, y, batch, workspace, workspace_floats, grads, loss_rows))
     return rc;

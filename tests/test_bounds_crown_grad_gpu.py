@@ -87,6 +87,30 @@ def test_device_equals_host_twin(case, beta):
         assert np.array_equal(dev_out[k], twin[k]), k
 
 
+# M = batch x classes past one span of 1024 rows: (widths, BatchNorm layers, batch)
+SPAN_CASES = {"second_span_26_rows": ([37, 33, 18, 5], (0, 1), 210), "second_span_1_row": ([37, 33, 18, 5], (0, 1), 205),
+              "second_span_one_chunk": ([19, 40, 32], (0,), 33)}
+
+
+@pytest.mark.parametrize("name", list(SPAN_CASES))
+def test_device_equals_host_twin_across_spans(name):
+    """Two spans of rows: cg_wgrad_kernel's second span starts at row 1024 and ends mid-chunk (26 rows, 1 row) or after exactly one
+    chunk, and cg_wreduce_kernel and cg_finish_kernel add two partials each."""
+    widths, bn, B = SPAN_CASES[name]
+    m = R.make_model(widths, 2, bn=bn)
+    assert 1024 < B * widths[-1] <= 2048
+    x, eps, y = R.case_inputs(m, B, 8)
+    model = build(m, max_batch=256)
+    fwd = device_call(model, x, eps, y, INF, crown=True)
+    got = grad_call(model, fwd, y, 1.0)
+    params, state = R.pack(m, layout_of(m))
+    twin = N.mlp_bounds_crown_grad_host(m["widths"], R.bn_flags(m), params, state, fwd["margin_ibp"], fwd["margin_crown"], fwd["lo"],
+                                        fwd["hi"], y, 1.0)
+    assert np.isfinite(twin["grads"]).all() and np.abs(twin["grads"]).max() > 0
+    for k in got:
+        assert np.array_equal(got[k], twin[k]), k
+
+
 @pytest.mark.parametrize("case", ["signed70", "wide"])
 def test_same_bits_twice_and_at_a_shifted_workspace(case):
     fwd, y = device_forward(case)
